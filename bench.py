@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — MCL updates/s as particle*beam/s on synthetic scans (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 One "step" = one full update (resample -> motion -> ray cast + likelihood -> normalise -> expected
 pose) of the 4M-particle x 1081-beam Spielberg workload (BASELINE.json configs[2]; SURVEY.md §8(d)
@@ -11,7 +11,10 @@ fixed-point weights, all-to-all fetch of the DISTINCT selected parents, two smal
 (monte_carlo_localization_amd/dist.py).  Inputs are resident in HBM before the timed region; the
 per-update host->device traffic is the 1081-float scan and the 3-double action only.
 
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K updates and prints the headline (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`) with what the run itself gives (first update, pose, counters).  `--full`
+adds the untimed extras below: the `roofline` block, the `cpu_baseline` and the oracle's `parity_check` of the timed run.
+`--dump-outputs DIR` writes what the last timed update computed (dump_outputs) for comparing two builds output for output.
 
 `roofline` names the bound that applies to the dominant kernel (k_rays_sweep): VALU issue (a wave64 VALU instruction occupies
 its SIMD for one quad-cycle; 1024 SIMDs x 2.4 GHz).  `roofline.frac` is the USEFUL-WORK fraction -- the instructions the rays of
@@ -200,6 +203,23 @@ def roofline_block(kernel_name, k_ms, n, B, sbar, profiled_workload=True, trips_
     return block
 
 
+DUMP_SAMPLE = 1 << 19          # particles whose state --dump-outputs writes (seven float64 rows of this length: 29 MB)
+
+
+def dump_outputs(out_dir, e, pose, n):
+    """What a caller of the timed update receives after the last timed step, as float64 .npy files in `out_dir`: the expected
+    pose and, for a fixed seeded sample of DUMP_SAMPLE particles (all of them when there are fewer; `sample_index` says which),
+    their pose, weight and log-weight and the parent index the step's resampling drew for them.  A sharded run writes rank 0's
+    shard (the pose is the whole set's)."""
+    os.makedirs(out_dir, exist_ok=True)
+    pick = np.arange(n) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+    arrays = {"expected_pose": pose, "sample_index": pick, "particles": e.get_particles()[:, pick],
+              "weights": e.get_weights()[pick], "log_weights": e.log_weights()[pick],
+              "resample_indices": e.resample_indices()[pick]}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -212,16 +232,21 @@ def parse_args(argv=None):
                          "a synthetic 0.025 m map (MAX_RANGE_PX = 479: cpp:195 puts no bound on it), the long-range case")
     ap.add_argument("--regime", choices=["tracking", "global"], default="tracking")
     ap.add_argument("--resample", choices=["multinomial", "systematic"], default="multinomial")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-baseline-256k", action="store_true",
-                    help="also time one oracle update at 262 144 x 1081 on one thread (SURVEY 8(d); about a minute, 11 GB)")
-    ap.add_argument("--no-parity-check", action="store_true")
+                    help="--full: also time one oracle update at 262 144 x 1081 on one thread (SURVEY 8(d); about a minute, 11 GB)")
+    ap.add_argument("--no-parity-check", action="store_true", help="--full without the untimed update whose resample indices the oracle checks")
     ap.add_argument("--no-overlap", action="store_true", help="sharded runs: gather the exchange synchronously")
     ap.add_argument("--force-dist", action="store_true",
                     help="take the sharded (torch.distributed/RCCL) path even with one rank (rehearsal)")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="collective backend of the sharded path; gloo + --one-device rehearses --gpus N on a one-GPU box")
     ap.add_argument("--one-device", action="store_true", help="rehearsal: every rank uses GPU 0 (needs --backend gloo)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, the oracle's parity check of the timed run and the roofline block (untimed; off by "
+                         "default, when the line holds the headline figures only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64; see dump_outputs)")
     return ap.parse_args(argv)
 
 
@@ -397,15 +422,20 @@ def main():
     exit_code = 0
     kernel_name = e.ray_kernel_name()
     kernel_variant = e.ray_kernel_variant() if kernel_name == "k_rays_sweep" else None      # (of the last TIMED update)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, e, pose, n)
 
-    # ---- after the timed region: the state the last timed update left, then ONE more untimed update (probe counter on) whose
-    #      resample indices the oracle checks.  A sharded run gathers every rank's log-weights and children's parents on rank 0
-    #      (all ranks take part in the two gathers), so that a line with N > 1 proves its indices like the single-GPU line does.
+    # ---- after the timed region, with --full: the state the last timed update left, then ONE more untimed update (probe counter
+    #      on) whose resample indices the oracle checks.  A sharded run gathers every rank's log-weights and children's parents on
+    #      rank 0 (all ranks take part in the two gathers), so that a line with N > 1 proves its indices like the single-GPU line
+    #      does.
     n_total = n * world
-    pt_last = e.get_particles() if rank == 0 else None
-    lw_last = e.log_weights()
-    lw_all, idx_all, probes_live = (lw_last if world == 1 else None), None, None
-    if not args.no_parity_check:
+    pt_last, lw_last, lw_all, idx_all, probes_live = None, None, None, None, None
+    if args.full:
+        pt_last = e.get_particles() if rank == 0 else None
+        lw_last = e.log_weights()
+        lw_all = lw_last if world == 1 else None
+    if args.full and not args.no_parity_check:
         def gather_all(a):
             t = torch.from_numpy(np.ascontiguousarray(a))
             if args.backend == "nccl":
@@ -425,58 +455,59 @@ def main():
     if rank == 0:
         ms = elapsed * 1e3 / args.steps
         value = n * world * B / (elapsed / args.steps)
-        base, sbar_first, sbar_timed = None, None, None
-        if world == 1 and not args.no_cpu_baseline:
-            base = cpu_baseline(m, ang, scan, true_pose, big=args.cpu_baseline_256k)
-        parity, sbar_err = None, None
-        checker_failed = False
-        orc = None
-        try:
-            # the oracle is test infrastructure: a box without it (no gcc, no oracle/) still gets its line, marked unchecked
-            from oracle import oracle as orc
-            orc.lib()
-        except (ImportError, OSError, subprocess.CalledProcessError) as ex:
-            orc, sbar_err = None, repr(ex)
-        if orc is not None:
+        parity, checker_failed = None, False
+        if args.full:
+            base, sbar_first, sbar_timed = None, None, None
+            if world == 1 and not args.no_cpu_baseline:
+                base = cpu_baseline(m, ang, scan, true_pose, big=args.cpu_baseline_256k)
+            sbar_err = None
+            orc = None
             try:
-                # The oracle as the CHECKER of the run that was just timed (never inside the timed region): the log-weights the
-                # last timed update left for 4000 sampled particles of rank 0 against orc_eng_log_weights on those particles (which
-                # also gives S-bar, the reference's samples per ray, cpp:622-647), then the resample indices of the untimed update
-                # above -- all children of all ranks -- against the oracle's exact-CDF draw from the weights the timed update left.
-                # An oracle error or a mismatch from here on fails the run.
-                om = orc.OracleMap(m.data, m.resolution, m.origin_x, m.origin_y)
-                L = orc.eng_log_table(orc.sensor_table(om.max_range_px))
-                oi = orc.obs_index(scan, om)
-                pick = np.random.default_rng(7).choice(n, size=min(4000, n), replace=False)
-                logw_o, _, probes_o = orc.eng_log_weights(om, np.ascontiguousarray(pt_last[:, pick]), ang, oi, L)
-                sbar_timed = probes_o / float(pick.size * B)
-                _, _, probes_f = orc.eng_log_weights(om, sample_first, ang, oi, L)
-                sbar_first = probes_f / float(sample_first.shape[1] * B)
-                parity = {"n": int(pick.size), "logw_mismatches": int(np.count_nonzero(lw_last[pick] != logw_o))}
-                if idx_all is not None:
-                    _, q_prev, _ = orc.eng_weights_from_log(lw_all)          # fixed-point weights of the WHOLE set (global maximum)
-                    if mode == engine.RESAMPLE_MULTINOMIAL:
-                        want = orc.eng_resample_indices(q_prev, 0, k53=orc.eng_philox_k53(42, n_updates, 0, n_total))
-                    else:
-                        want = orc.eng_resample_indices(q_prev, 1, k0=orc.eng_philox_k0(42, n_updates))
-                    parity.update({"idx_n": int(n_total), "idx_mismatches": int(np.count_nonzero(idx_all != want)),
-                                   "idx_scope": "all children of all ranks (global parent indices)" if world > 1 else "all children"})
-                    del q_prev, want
-            except Exception as ex:                  # noqa: BLE001 -- the checker failed: the line still goes out, marked, and the run fails
-                parity = {"error": repr(ex)}
-                checker_failed = True
-        del pt_last, lw_all, idx_all
-        k_ms = float(np.mean(ray_ms))
-        roof = roofline_block(kernel_name, k_ms, n, B, sbar_timed if sbar_timed is not None else 43.4,
-                              profiled_workload=(args.map == "spielberg" and args.regime == "tracking"), trips_live=probes_live,
-                              variant=kernel_variant)
-        # which kernel class AUTO gave this map / scan / size, and why, when it is not the fast windowed kernel
-        roof["kernel_class_planned"] = planned_kernel
-        if kernel_name != "k_rays_sweep":
-            roof["kernel_class_reason"] = planned_reason
-        roof["algorithmic"]["s_bar_first_update"] = sbar_first
-        # what the kernel itself examines: loop trips per ray counted by an extra, untimed update (debug_count_probes)
-        roof["probe_trips_per_ray_live"] = probes_live
+                # the oracle is test infrastructure: a box without it (no gcc, no oracle/) still gets its line, marked unchecked
+                from oracle import oracle as orc
+                orc.lib()
+            except (ImportError, OSError, subprocess.CalledProcessError) as ex:
+                orc, sbar_err = None, repr(ex)
+            if orc is not None:
+                try:
+                    # The oracle as the CHECKER of the run that was just timed (never inside the timed region): the log-weights the
+                    # last timed update left for 4000 sampled particles of rank 0 against orc_eng_log_weights on those particles (which
+                    # also gives S-bar, the reference's samples per ray, cpp:622-647), then the resample indices of the untimed update
+                    # above -- all children of all ranks -- against the oracle's exact-CDF draw from the weights the timed update left.
+                    # An oracle error or a mismatch from here on fails the run.
+                    om = orc.OracleMap(m.data, m.resolution, m.origin_x, m.origin_y)
+                    L = orc.eng_log_table(orc.sensor_table(om.max_range_px))
+                    oi = orc.obs_index(scan, om)
+                    pick = np.random.default_rng(7).choice(n, size=min(4000, n), replace=False)
+                    logw_o, _, probes_o = orc.eng_log_weights(om, np.ascontiguousarray(pt_last[:, pick]), ang, oi, L)
+                    sbar_timed = probes_o / float(pick.size * B)
+                    _, _, probes_f = orc.eng_log_weights(om, sample_first, ang, oi, L)
+                    sbar_first = probes_f / float(sample_first.shape[1] * B)
+                    parity = {"n": int(pick.size), "logw_mismatches": int(np.count_nonzero(lw_last[pick] != logw_o))}
+                    if idx_all is not None:
+                        _, q_prev, _ = orc.eng_weights_from_log(lw_all)          # fixed-point weights of the WHOLE set (global maximum)
+                        if mode == engine.RESAMPLE_MULTINOMIAL:
+                            want = orc.eng_resample_indices(q_prev, 0, k53=orc.eng_philox_k53(42, n_updates, 0, n_total))
+                        else:
+                            want = orc.eng_resample_indices(q_prev, 1, k0=orc.eng_philox_k0(42, n_updates))
+                        parity.update({"idx_n": int(n_total), "idx_mismatches": int(np.count_nonzero(idx_all != want)),
+                                       "idx_scope": "all children of all ranks (global parent indices)" if world > 1 else "all children"})
+                        del q_prev, want
+                except Exception as ex:                  # noqa: BLE001 -- the checker failed: the line still goes out, marked, and the run fails
+                    parity = {"error": repr(ex)}
+                    checker_failed = True
+            del pt_last, lw_all, idx_all
+            k_ms = float(np.mean(ray_ms))
+            roof = roofline_block(kernel_name, k_ms, n, B, sbar_timed if sbar_timed is not None else 43.4,
+                                  profiled_workload=(args.map == "spielberg" and args.regime == "tracking"), trips_live=probes_live,
+                                  variant=kernel_variant)
+            # which kernel class AUTO gave this map / scan / size, and why, when it is not the fast windowed kernel
+            roof["kernel_class_planned"] = planned_kernel
+            if kernel_name != "k_rays_sweep":
+                roof["kernel_class_reason"] = planned_reason
+            roof["algorithmic"]["s_bar_first_update"] = sbar_first
+            # what the kernel itself examines: loop trips per ray counted by an extra, untimed update (debug_count_probes)
+            roof["probe_trips_per_ray_live"] = probes_live
         line = {
             "metric": "MCL updates/sec (particle*beam/s)",
             "value": value, "unit": "particle*beam/s", "n_gpus": world, "steps": args.steps,
@@ -496,12 +527,12 @@ def main():
                                       if world > 1 else "single GPU"},
             "first_update_ms": first_ms, "first_update_ray_kernel_ms": first_ray_ms,
             "steady_state_ms": ms,
-            "roofline": roof,
-            "cpu_baseline": base,
             "pose": [float(v) for v in pose],
             "counters_last_update": counters,
-            "parity_check": parity if parity is not None else {"skipped": sbar_err},
         }
+        if args.full:
+            line.update({"roofline": roof, "cpu_baseline": base,
+                         "parity_check": parity if parity is not None else {"skipped": sbar_err}})
         if use_dist:
             line["exchange_bytes_per_update_per_gpu"] = sf.exchange_bytes
             # stream synchronisations of one steady-state update on this rank (dist.py: 1 = device-ordered, the small exchanges

@@ -54,6 +54,44 @@ def test_single_gpu_call_runs_in_process():
     b = importlib.import_module("bench")
     a = b.parse_args([])
     assert (a.gpus, a.steps, a.warmup, a.particles_per_gpu) == (1, 20, 3, 4 * 1024 * 1024)
+    assert not a.full and a.dump_outputs is None          # a plain run: the headline only, nothing written
+
+
+def test_dump_outputs_writes_a_fixed_float64_sample(tmp_path):
+    """--dump-outputs: float64 .npy files of a seeded particle sample (the same particles every run), under 64 MB in all,
+    rows taken from what the engine's accessors return."""
+    sys.path.insert(0, ROOT)
+    import importlib
+    import numpy as np
+    b = importlib.import_module("bench")
+    n = 3 * b.DUMP_SAMPLE
+
+    class FakeEngine:
+        def get_particles(self):
+            return np.arange(3 * n, dtype=np.float64).reshape(3, n)
+
+        def get_weights(self):
+            return np.full(n, 1.0 / n)
+
+        def log_weights(self):
+            return -np.arange(n, dtype=np.float64)
+
+        def resample_indices(self):
+            return np.arange(n, dtype=np.int32)[::-1].copy()
+
+    b.dump_outputs(str(tmp_path / "a"), FakeEngine(), np.array([1.0, 2.0, 3.0]), n)
+    b.dump_outputs(str(tmp_path / "b"), FakeEngine(), np.array([1.0, 2.0, 3.0]), n)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b")) and "particles.npy" in files and "expected_pose.npy" in files
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) < 64e6
+    d = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(v.dtype == np.float64 for v in d.values())
+    for f in files:
+        assert np.array_equal(d[f[:-4]], np.load(tmp_path / "b" / f))
+    pick = d["sample_index"].astype(np.int64)
+    assert pick.size == b.DUMP_SAMPLE and np.all(np.diff(pick) > 0) and pick[-1] < n
+    assert np.array_equal(d["particles"][1], n + pick) and np.array_equal(d["resample_indices"], n - 1 - pick)
+    assert np.array_equal(d["expected_pose"], [1.0, 2.0, 3.0])
 
 
 import pytest
@@ -66,7 +104,7 @@ def test_bench_gpus_2_end_to_end_on_one_gpu_over_gloo():
     update (dense first, then list exchanges), rank 0's line comes back with the run's own parity check green."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--one-device",
-                        "--particles-per-gpu", "131072", "--beam-step", "4", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"],
+                        "--particles-per-gpu", "131072", "--beam-step", "4", "--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]

@@ -1,17 +1,16 @@
 """The host patch as an artefact: integration/particle_filter_hip.patch is a unified diff against the
-reference's src/particle_filter.cpp, include/particle_filter_cpp/particle_filter.hpp and CMakeLists.txt.  Where the
-reference checkout exists (this container) the diff must apply cleanly; everywhere, every C-ABI symbol it calls must be
-declared in include/mcl_hip_engine.h and exported by the built library, and the class surface must be untouched apart
-from the four private additions."""
+reference's src/particle_filter.cpp, include/particle_filter_cpp/particle_filter.hpp and CMakeLists.txt.  The diff must
+apply cleanly to the reference (checked against digests of the reference's lines, tests/golden/integration_patch_preimage.json),
+every C-ABI symbol it calls must be declared in include/mcl_hip_engine.h and exported by the built library, and the class
+surface must be untouched apart from the four private additions."""
+import hashlib
+import json
 import os
 import re
-import subprocess
-
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PATCH = os.path.join(ROOT, "integration", "particle_filter_hip.patch")
-REFERENCE = "/root/reference"
+PREIMAGE = os.path.join(ROOT, "tests", "golden", "integration_patch_preimage.json")
 
 
 def patch_text():
@@ -48,7 +47,45 @@ def test_class_surface_unchanged():
         "void sync_host_state();", "void push_host_state();"]
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="the reference checkout only exists in the build container")
+def parse_hunks(text):
+    """{file: [(old_start, old_count, new_start, new_count, old_lines, new_lines), ...]} of a unified diff."""
+    files, cur, hunk = {}, None, None
+    for l in text.splitlines():
+        if l.startswith("--- a/"):
+            continue
+        if l.startswith("+++ b/"):
+            cur, hunk = files.setdefault(l[6:].strip(), []), None
+            continue
+        m = re.match(r"^@@ -(\d+)(?:,(\d+))? \+(\d+)(?:,(\d+))? @@", l)
+        if m:
+            hunk = (int(m.group(1)), int(m.group(2) or 1), int(m.group(3)), int(m.group(4) or 1), [], [])
+            cur.append(hunk)
+            continue
+        assert hunk is not None, l
+        tag, body = (l[0], l[1:]) if l else (" ", "")
+        assert tag in " -+", l
+        if tag in " -":
+            hunk[4].append(body)
+        if tag in " +":
+            hunk[5].append(body)
+    return files
+
+
 def test_patch_applies_to_the_reference():
-    r = subprocess.run(["git", "apply", "--check", "--verbose", PATCH], cwd=REFERENCE, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    """`git apply --check` against the reference without its checkout: every hunk's body agrees with its header, the hunks
+    lie in order inside the file and their new ranges follow from the old ones, and the lines each hunk replaces (its context
+    and removed lines) hash to the digest of the reference's own lines at that place (tools/make_patch_fixture.py writes the
+    digests from a reference checkout)."""
+    want = json.load(open(PREIMAGE))
+    got = parse_hunks(patch_text())
+    assert sorted(got) == sorted(want)
+    for f, hunks in got.items():
+        ref = want[f]
+        assert [(h[0], h[1]) for h in hunks] == [(r["old_start"], r["old_count"]) for r in ref["hunks"]], f
+        end, delta = 0, 0
+        for (o_start, o_count, n_start, n_count, old, new), r in zip(hunks, ref["hunks"]):
+            assert (len(old), len(new)) == (o_count, n_count), (f, o_start)
+            assert o_start > end and o_start - 1 + o_count <= ref["lines"], (f, o_start)
+            assert n_start == o_start + delta, (f, o_start)
+            assert hashlib.sha256("\n".join(old).encode()).hexdigest() == r["sha256"], (f, o_start)
+            end, delta = o_start - 1 + o_count, delta + n_count - o_count

@@ -48,12 +48,12 @@ python3 tools/roofline_inputs.py "$TAG" "$PROF/${TAG}_pmc_sq.csv" "$PROF/${TAG}_
 cp "$PROF/${TAG}_roofline_inputs.json" "profiles/${TAG}_roofline_inputs.json"
 # per-kernel achieved bandwidth of the streaming kernels (algorithmic bytes / steady-state duration) + their VALU issue time
 python3 tools/kernel_bandwidth.py "$PROF/${TAG}_kernel_trace_summary.json" 4194304 "$PROF/${TAG}_kernel_bandwidth.md" "$PROF/${TAG}_pmc_sq.csv" > /dev/null
-python bench.py > "$OUT/b_4m.json"
-python bench.py --no-cpu-baseline --particles-per-gpu 262144 > "$OUT/b_256k.json"
-python bench.py --no-cpu-baseline --map levine > "$OUT/b_levine.json"
-python bench.py --no-cpu-baseline --regime global > "$OUT/b_global.json"
-python bench.py --no-cpu-baseline --regime global --map levine --steps 5 > "$OUT/b_global_levine.json"
-python bench.py --no-cpu-baseline --resample systematic > "$OUT/b_sys.json"
-python bench.py --no-cpu-baseline --map fine025 --steps 10 > "$OUT/b_fine025.json"
+python bench.py --full > "$OUT/b_4m.json"
+python bench.py --full --no-cpu-baseline --particles-per-gpu 262144 > "$OUT/b_256k.json"
+python bench.py --full --no-cpu-baseline --map levine > "$OUT/b_levine.json"
+python bench.py --full --no-cpu-baseline --regime global > "$OUT/b_global.json"
+python bench.py --full --no-cpu-baseline --regime global --map levine --steps 5 > "$OUT/b_global_levine.json"
+python bench.py --full --no-cpu-baseline --resample systematic > "$OUT/b_sys.json"
+python bench.py --full --no-cpu-baseline --map fine025 --steps 10 > "$OUT/b_fine025.json"
 for n in 4m 256k levine global global_levine sys fine025; do tail -n 1 "$OUT/b_$n.json" > "$PROF/${TAG}_bench_$n.json"; done
 echo "$PROF/${TAG}_* refreshed"

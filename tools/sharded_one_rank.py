@@ -19,7 +19,7 @@ VARIANTS = [
 
 
 def run(extra, env, n):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", *extra] + (["--particles-per-gpu", str(n)] if n else [])
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", *extra] + (["--particles-per-gpu", str(n)] if n else [])
     out = subprocess.run(cmd, env=dict(os.environ, **env), capture_output=True, text=True, check=True).stdout
     return json.loads(out.strip().splitlines()[-1])
 
@@ -29,7 +29,7 @@ def main():
     out_dir = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "gpurun_out", "profiles_new")
     os.makedirs(out_dir, exist_ok=True)
     rows = ["One rank through the sharded path against the single engine, one MI355X, one run of tools/sharded_one_rank.py:",
-            "`python bench.py --no-cpu-baseline [--force-dist] [--particles-per-gpu 262144]`, 3 warm-up + 20 timed updates.  rest = ms per update - ray",
+            "`python bench.py --full --no-cpu-baseline [--force-dist] [--particles-per-gpu 262144]`, 3 warm-up + 20 timed updates.  rest = ms per update - ray",
             "kernel ms (everything that is not the ray kernel: the comparable column, the ray kernel's own time moves by +-0.05 ms between runs).",
             f"Every line's parity check (all resample indices against the oracle) is clean.  The lines: `profiles/{tag}_sharded_one_rank.jsonl`.", "",
             "| host | 4M x 1081: ms | ray kernel | rest | 262 144 x 1081: ms | ray kernel | rest | host waits per update |", "|---|---|---|---|---|---|---|---|"]

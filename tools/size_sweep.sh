@@ -6,7 +6,7 @@ OUT=${1:-gpurun_out/sw}
 mkdir -p "$OUT"
 failed=0
 for n in 65536 131072 262144 524288 1048576 2097152 4194304 8388608 16777216 33554432; do
-  if ! python bench.py --particles-per-gpu $n --no-cpu-baseline --no-parity-check --steps 8 > "$OUT/$n.json" 2> "$OUT/$n.err"; then
+  if ! python bench.py --full --particles-per-gpu $n --no-cpu-baseline --no-parity-check --steps 8 > "$OUT/$n.json" 2> "$OUT/$n.err"; then
     echo "size_sweep: $n particles FAILED (see $OUT/$n.err)" >&2
     tail -n 3 "$OUT/$n.err" >&2
     failed=1
