@@ -227,6 +227,57 @@ int mcl_get_planned_ray_kernel(const mcl_engine_t *h, int64_t n_particles, int32
  * (always 1 with resample_neff_permille == 0). */
 int mcl_get_effective_sample_size(const mcl_engine_t *h, double *n_eff, int32_t *resampled_last_update);
 
+/* ---- KLD-adaptive particle count (KLD sampling, Fox 2003, as in AMCL) --------------------------------
+ * Off by default.  With it on, every mcl_update counts how many pose-space bins the parents it drew occupy, and the NEXT update
+ * draws the smallest set that keeps the KL divergence to the posterior within err with confidence z: N_{t+1} is decided from
+ * the count of update t, one update of lag -- the batch form of KLD sampling on a GPU (the count is final when the resampling
+ * kernel ends, the set it sizes is drawn by the next one).
+ *   What is counted: inside update t, the pose of the parent of every one of the N_t children, before the motion model (the
+ *     drawn sample, as a KD-tree insertion counts it); in an update that kept its particles (resample_neff_permille) each
+ *     particle's own pose.  mcl_sensor_update counts nothing.
+ *   Bins: nx = ceil(W * res / bin_x_m), ny = ceil(H * res / bin_y_m) in double (res widened from float); ix = floor((x - ox) *
+ *     (1 / bin_x_m)), iy = floor((y - oy) * (1 / bin_y_m)), the reciprocals computed once in double; it = floor((theta + pi) *
+ *     (n_theta_bins / (2 pi))) as int64, mod n_theta_bins, non-negative.  A pose whose ix or iy falls outside the grid, any of
+ *     whose x, y, theta is not finite, or with |theta| >= 1e9 lands in ONE extra "outside" bin.  Each formula is an add or
+ *     subtract followed by a multiply (nothing FMA contraction could fuse): the device, mcl_host_kld_bins and a numpy
+ *     restatement agree bit for bit, bin edges included.  A grid of more than 2^31 bits (nx * ny * n_theta_bins + 1) is refused
+ *     by mcl_set_kld / mcl_set_map with MCL_ERR_INVALID_ARG.
+ *   Target: for k <= 1 occupied bins, max_particles; otherwise a = 2 / (9 (k - 1)), b = 1 - a + sqrt(a) * z,
+ *     n = ceil((k - 1) / (2 err) * (b * b * b)), rounded UP to a multiple of round_to, then clamped to [min, max].
+ *     n_next = n_current when target <= n_current and target * 1000 >= n_current * shrink_permille (exact integers), otherwise
+ *     the target: the hysteresis keeps N steady once tracking, so that the small-update paths (captured graph, three launches)
+ *     stay warm.
+ *   mcl_set_kld, mcl_set_particles* and mcl_init_* set n_next = clamp(N, min, max) (and bins_last = -1).  An update that kept
+ *     its particles and mcl_sensor_update leave n_next alone; with KLD on an update keeps its particles only when n_next == N.
+ *   Injected draws: with KLD on, mcl_update's normals / uniforms hold n_next rows (read it with mcl_get_kld_state first).
+ *     After the update mcl_get_particle_count is the new N, which mcl_get_particles, _weights, _resample_indices (values below
+ *     the previous N), _log_weights, ... take.
+ *   Single engine only: mcl_set_kld on an engine with a communicator or in a device group, mcl_comm_create on an engine with
+ *     KLD on, and every mcl_stage_* call while KLD is on return MCL_ERR_UNSUPPORTED. */
+typedef struct {
+    int64_t min_particles, max_particles;   /* 1 <= min <= max <= cfg.max_particles                                          */
+    double err;                             /* epsilon of the KLD bound, default 0.01                                         */
+    double z;                               /* upper standard-normal quantile (>= 0), default 2.326 (0.99)                    */
+    double bin_x_m, bin_y_m;                /* default 0.5, 0.5                                                               */
+    int32_t n_theta_bins;                   /* heading bins over one turn, default 36 (10 degrees)                            */
+    int32_t round_to;                       /* targets rounded UP to a multiple of this, default 256                          */
+    int32_t shrink_permille;                /* keep N while target >= N * permille / 1000 (0..1000, default 800; 1000 = none) */
+    int32_t reserved;                       /* must be 0                                                                      */
+} mcl_kld_config_t;
+/* defaults above; min_particles 256, max_particles 4194304 */
+void mcl_default_kld_config(mcl_kld_config_t *k);
+int mcl_set_kld(mcl_engine_t *h, const mcl_kld_config_t *k);          /* NULL = off (the default)                           */
+int mcl_get_particle_count(const mcl_engine_t *h, int64_t *n);         /* particles held now (the parents of the next update) */
+/* bins occupied by the last update's draw (-1: none counted), children the next update draws (N when KLD is off); either
+ * pointer may be NULL */
+int mcl_get_kld_state(const mcl_engine_t *h, int64_t *bins_last, int64_t *n_next);
+/* the two rules above on the host, without a device: occupied bins of n poses (x, y, th: n doubles each) on a width x height
+ * map; the next particle count after an update that counted `bins` with n_current particles (k->max_particles is not checked
+ * against any engine here) */
+int mcl_host_kld_bins(const double *x, const double *y, const double *th, int64_t n, uint32_t width, uint32_t height,
+                      float resolution, double origin_x, double origin_y, const mcl_kld_config_t *k, int64_t *bins);
+int mcl_host_kld_target(const mcl_kld_config_t *k, int64_t bins, int64_t n_current, int64_t *n_next);
+
 /* ---- host-side precomputation, callable without a device (what mcl_set_map uploads) --------- */
 /* (P+1)^2 doubles, Eigen column-major (index d*(P+1)+r): the restatement of precompute_sensor_model
  * (cpp:233-292) the engine uses. */

@@ -891,15 +891,20 @@ int sensor_and_weights(mcl_engine *h, const double *d_global_max, bool defer_sum
 }
 
 // weights, sums and the CDF of the current log-weights (the tail of an update).  Small updates take one launch.
-int weights_and_cdf(mcl_engine *h, bool result_to_host = false)
+// kld (a small update with KLD on, result_to_host): the tail also clears the words the resampling kernel marked
+int weights_and_cdf(mcl_engine *h, bool result_to_host = false, const mcl::KldArgs *kld = nullptr)
 {
     const int64_t n = h->N;
     if (h->cfg.weight_mode == MCL_WEIGHT_LOG && h->cfg.resample_neff_permille == 0 && n <= mcl::kTinyTailMax) {
         // d_pc holds (cos, sin) of the current headings whenever a ray kernel other than the literal march ran on them
         const double4 *pc = h->last_mode >= 2 ? h->d_pc : nullptr;
-        hipLaunchKernelGGL(mcl::k_tiny_tail, dim3(1), dim3(1024), (size_t)n * sizeof(uint64_t), h->stream, h->d_logw, h->d_x[h->cur],
-                           h->d_y[h->cur], h->d_th[h->cur], pc, n, h->d_w, h->d_q, h->d_cdf, h->d_scalars,
-                           result_to_host ? h->h_result : (unsigned long long *)nullptr, ++h->result_seq);
+        if (kld && result_to_host)
+            hipLaunchKernelGGL(mcl::k_tiny_tail<true>, dim3(1), dim3(1024), (size_t)n * sizeof(uint64_t), h->stream, h->d_logw, h->d_x[h->cur],
+                               h->d_y[h->cur], h->d_th[h->cur], pc, n, h->d_w, h->d_q, h->d_cdf, h->d_scalars, h->h_result, ++h->result_seq, *kld);
+        else
+            hipLaunchKernelGGL(mcl::k_tiny_tail<false>, dim3(1), dim3(1024), (size_t)n * sizeof(uint64_t), h->stream, h->d_logw, h->d_x[h->cur],
+                               h->d_y[h->cur], h->d_th[h->cur], pc, n, h->d_w, h->d_q, h->d_cdf, h->d_scalars,
+                               result_to_host ? h->h_result : (unsigned long long *)nullptr, ++h->result_seq, mcl::KldArgs{});
         HIPCHK(h, hipGetLastError());
         h->max_partials_ready = false;
         h->carry_pending = false;
@@ -922,6 +927,100 @@ float elapsed(hipEvent_t a, hipEvent_t b)
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, a, b);
     return ms;
+}
+
+// ---- KLD-adaptive particle count (mcl_set_kld)
+// why a KLD configuration is refused (null: it is not); cap > 0: the engine's max_particles
+const char *kld_invalid(const mcl_kld_config_t *k, int64_t cap)
+{
+    if (!(k->min_particles >= 1 && k->min_particles <= k->max_particles)) return "KLD: need 1 <= min_particles <= max_particles";
+    if (k->max_particles >= MCL_MAX_TOTAL_PARTICLES) return "KLD: max_particles must stay below 2^27";
+    if (cap > 0 && k->max_particles > cap) return "KLD: max_particles exceeds the engine's max_particles";
+    if (!(std::isfinite(k->err) && k->err > 0.0)) return "KLD: err must be finite and positive";
+    if (!(std::isfinite(k->z) && k->z >= 0.0)) return "KLD: z must be finite and non-negative";
+    if (!(std::isfinite(k->bin_x_m) && k->bin_x_m > 0.0 && std::isfinite(k->bin_y_m) && k->bin_y_m > 0.0))
+        return "KLD: bin sizes must be finite and positive";
+    if (k->n_theta_bins < 1) return "KLD: n_theta_bins must be >= 1";
+    if (k->round_to < 1) return "KLD: round_to must be >= 1";
+    if (k->shrink_permille < 0 || k->shrink_permille > 1000) return "KLD: shrink_permille must be in [0, 1000]";
+    if (k->reserved != 0) return "KLD: reserved must be 0";
+    return nullptr;
+}
+
+// the bin grid over a W x H map (false: more than 2^31 bits)
+bool kld_grid(const mcl_kld_config_t *k, uint32_t W, uint32_t H, float res, int64_t &nx, int64_t &ny, uint64_t &bits)
+{
+    const double fx = std::ceil((double)W * (double)res / k->bin_x_m), fy = std::ceil((double)H * (double)res / k->bin_y_m);
+    if (!(fx >= 1.0 && fy >= 1.0 && fx * fy * (double)k->n_theta_bins + 1.0 <= 2147483648.0)) return false;
+    nx = (int64_t)fx; ny = (int64_t)fy;
+    bits = (uint64_t)(nx * ny * k->n_theta_bins) + 1;
+    return true;
+}
+
+mcl::KldArgs kld_args_of(const mcl_kld_config_t *k, int64_t nx, int64_t ny, double ox, double oy)
+{
+    mcl::KldArgs a{};
+    a.ox = ox; a.oy = oy;
+    a.inv_bx = 1.0 / k->bin_x_m; a.inv_by = 1.0 / k->bin_y_m;
+    a.th_scale = (double)k->n_theta_bins / (2.0 * 3.14159265358979323846);
+    a.nx = (uint32_t)nx; a.ny = (uint32_t)ny; a.nth = (uint32_t)k->n_theta_bins;
+    a.nx_d = (double)nx; a.ny_d = (double)ny;
+    a.nth_d = (double)k->n_theta_bins; a.inv_nth = 1.0 / (double)k->n_theta_bins;
+    a.outside = (uint32_t)(nx * ny * k->n_theta_bins);
+    return a;
+}
+
+int64_t kld_target(const mcl_kld_config_t *k, int64_t bins, int64_t n_current)
+{
+    int64_t target = k->max_particles;
+    if (bins > 1) {
+        const double km1 = (double)(bins - 1);
+        const double a = 2.0 / (9.0 * km1);
+        const double b = 1.0 - a + std::sqrt(a) * k->z;
+        const double n = std::ceil(km1 / (2.0 * k->err) * (b * b * b));
+        if (n < (double)k->max_particles) {            // (rounding up and clamping cannot go below max from there)
+            const int64_t r = k->round_to, ni = n > 0.0 ? (int64_t)n : 0;
+            target = std::min(std::max((ni + r - 1) / r * r, k->min_particles), k->max_particles);
+        }
+    }
+    if (target <= n_current && target * 1000 >= n_current * (int64_t)k->shrink_permille) return n_current;
+    return target;
+}
+
+// the bitmap, the list and the two counters for the current map (allocated on the first need, grown, zeroed)
+int kld_alloc(mcl_engine *h)
+{
+    if (!h->kld_on || !h->have_map) return MCL_OK;
+    const size_t words = (size_t)((h->kld_bits + 31) / 32);
+    const size_t list = (size_t)std::min<uint64_t>((uint64_t)h->cap, h->kld_bits);
+    if (words > h->kld_bm_words) {
+        dfree(h->d_kld_bm); h->kld_bm_words = 0;
+        HIPCHK(h, hipMalloc(&h->d_kld_bm, words * sizeof(uint32_t)));
+        h->kld_bm_words = words;
+    }
+    if (list > h->kld_list_cap) {
+        dfree(h->d_kld_list); h->kld_list_cap = 0;
+        HIPCHK(h, hipMalloc(&h->d_kld_list, list * sizeof(uint32_t)));
+        h->kld_list_cap = list;
+    }
+    if (!h->d_kld_cnt) HIPCHK(h, hipMalloc(&h->d_kld_cnt, 2 * sizeof(unsigned int)));
+    HIPCHK(h, hipMemsetAsync(h->d_kld_bm, 0, words * sizeof(uint32_t), h->stream));
+    HIPCHK(h, hipMemsetAsync(h->d_kld_cnt, 0, 2 * sizeof(unsigned int), h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->kld_parity = 0;
+    return MCL_OK;
+}
+
+// a new particle set (set / initialised): the next update draws clamp(N, min, max)
+void kld_reset(mcl_engine *h)
+{
+    h->kld_bins_last = -1;
+    h->kld_n_next = h->kld_on ? std::min(std::max(h->N, h->kld.min_particles), h->kld.max_particles) : h->N;
+}
+
+int kld_refuse_stage(mcl_engine *h)
+{
+    return fail(h, MCL_ERR_UNSUPPORTED, "KLD sampling (mcl_set_kld) is single-engine only: the mcl_stage_* calls are refused while it is on");
 }
 
 }  // namespace
@@ -1087,7 +1186,8 @@ int mcl_create(const mcl_config_t *cfg, mcl_engine_t **out)
     CRT(hipFuncSetAttribute(reinterpret_cast<const void *>(&mcl::k_rays_cell<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
     CRT(hipFuncSetAttribute(reinterpret_cast<const void *>(&mcl::k_rays_cell<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
 #endif
-    CRT(hipFuncSetAttribute(reinterpret_cast<const void *>(&mcl::k_tiny_tail), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+    CRT(hipFuncSetAttribute(reinterpret_cast<const void *>(&mcl::k_tiny_tail<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+    CRT(hipFuncSetAttribute(reinterpret_cast<const void *>(&mcl::k_tiny_tail<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
     CRT(hipFuncSetAttribute(reinterpret_cast<const void *>(&mcl::k_sweep_plan), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     CRT(hipFuncSetAttribute(reinterpret_cast<const void *>(&mcl::k_rays_sweep<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
     CRT(hipFuncSetAttribute(reinterpret_cast<const void *>(&mcl::k_rays_sweep<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
@@ -1147,6 +1247,7 @@ void mcl_destroy(mcl_engine_t *h)
     for (int b = 0; b < 2; ++b) { dfree(h->d_x[b]); dfree(h->d_y[b]); dfree(h->d_th[b]); }
     dfree(h->d_w); dfree(h->d_logw); dfree(h->d_tmp); dfree(h->d_logw_acc); dfree(h->d_carry[0]); dfree(h->d_carry[1]); dfree(h->d_q); dfree(h->d_cdf); dfree(h->d_blocktot); dfree(h->d_bm); dfree(h->d_bm_pop); dfree(h->d_bm_pref);
     dfree(h->d_gcdf); dfree(h->d_gtop);
+    dfree(h->d_kld_bm); dfree(h->d_kld_list); dfree(h->d_kld_cnt);
     dfree(h->d_blockcnt); dfree(h->d_ccdf); dfree(h->d_ctop); dfree(h->d_cidx); dfree(h->d_crec);
     dfree(h->d_idx); dfree(h->d_steps); dfree(h->d_part); dfree(h->d_maxpart); dfree(h->d_result); if (h->h_result) { (void)hipHostFree(h->h_result); h->h_result = nullptr; } dfree(h->d_inject); dfree(h->d_pc); dfree(h->d_qr); dfree(h->d_far); dfree(h->d_far_list); dfree(h->d_far_sorted); dfree(h->d_far_cnt); dfree(h->d_pcs); dfree(h->d_ths); dfree(h->d_distw); dfree(h->d_distg); dfree(h->d_leaders); dfree(h->d_pack[0]); dfree(h->d_pack[1]); dfree(h->d_perm); dfree(h->d_skey); dfree(h->d_srank); dfree(h->d_skey2); dfree(h->d_sval2); dfree(h->d_sort_tmp); dfree(h->d_hist); dfree(h->d_histpart); dfree(h->d_tile_used); dfree(h->d_bbox); dfree(h->d_cut_start); dfree(h->d_cut_end); dfree(h->d_tilemap); dfree(h->d_tilemark); dfree(h->d_slice_mean); dfree(h->d_fix_list); dfree(h->d_fix_count); dfree(h->d_exact_list);
     dfree(h->d_grid); dfree(h->d_dist); dfree(h->d_dist4); dfree(h->d_L); dfree(h->d_table);
@@ -1171,6 +1272,10 @@ int mcl_set_map(mcl_engine_t *h, const int8_t *data, uint32_t width, uint32_t he
 {
     if (!h) return MCL_ERR_INVALID_ARG;
     if (!data || width == 0 || height == 0 || width > 200000 || height > 200000) return fail(h, MCL_ERR_INVALID_ARG, "bad map dimensions");
+    int64_t kld_nx = 0, kld_ny = 0;
+    uint64_t kld_bits = 0;
+    if (h->kld_on && resolution > 0.0f && !kld_grid(&h->kld, width, height, resolution, kld_nx, kld_ny, kld_bits))
+        return fail(h, MCL_ERR_INVALID_ARG, "KLD: the bin grid over this map exceeds 2^31 bits");
     graph_reset(h);
     if (!(resolution > 0.0f)) return fail(h, MCL_ERR_INVALID_ARG, "invalid map resolution");   // cpp:236-240
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -1290,6 +1395,11 @@ int mcl_set_map(mcl_engine_t *h, const int8_t *data, uint32_t width, uint32_t he
         }
     }
     h->have_map = true;
+    if (h->kld_on) {
+        h->kld_nx = kld_nx; h->kld_ny = kld_ny; h->kld_bits = kld_bits;
+        const int rc = kld_alloc(h);
+        if (rc) { h->have_map = false; return rc; }
+    }
     return MCL_OK;
 }
 
@@ -1440,6 +1550,7 @@ static int set_particles_impl(mcl_engine_t *h, const double *xyz, const double *
     h->have_idx = h->have_steps = h->have_logw = false;
     comm_forget(h->comm);                   // a sharded set: the other shards' lists are unknown again
     h->stage_kept = false;
+    kld_reset(h);
     return MCL_OK;
 }
 
@@ -1472,6 +1583,7 @@ static int finish_init(mcl_engine *h, int64_t n, int64_t n_total)
     comm_forget(h->comm);                   // a sharded set: the other shards' lists are unknown again
     h->stage_kept = false;
     h->init_idx++;
+    kld_reset(h);
     return MCL_OK;
 }
 
@@ -1651,6 +1763,13 @@ static int layout_adopt(mcl_engine *h, int64_t n)
     return MCL_OK;
 }
 
+// after an update with KLD on: the count came back in word 17 of the result block; a resampling update decides the next size
+static void kld_decide(mcl_engine *h, bool kept)
+{
+    h->kld_bins_last = (int64_t)h->h_result[17];
+    if (!kept) h->kld_n_next = kld_target(&h->kld, h->kld_bins_last, h->N);
+}
+
 static int do_update(mcl_engine_t *h, const double action[3], const float *obs, int32_t n_beams, const double *normals,
                      const double *uniforms, bool resample_and_move, int obs_stride = 1)
 {
@@ -1659,7 +1778,11 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
     if (!obs || n_beams != h->B || (resample_and_move && !action)) return fail(h, MCL_ERR_INVALID_ARG, "bad action/observation");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     auto t0 = std::chrono::steady_clock::now();
-    const int64_t n = h->N;
+    // parents and children: the same number unless KLD sampling (mcl_set_kld) decided another size for this update's draw
+    const int64_t n_par = h->N;
+    const bool kld = resample_and_move && h->kld_on;
+    int64_t n = kld ? h->kld_n_next : n_par;     // children: every stage after the resampling kernel runs on them
+    if (kld && (n < 1 || n > h->cap)) return fail(h, MCL_ERR_INVALID_ARG, "KLD: particle count out of range");
     const double *d_norm = nullptr, *d_uni = nullptr;
     if (resample_and_move) {
         if (normals) {
@@ -1673,14 +1796,21 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
     }
     // adaptive resampling (off by default): keep the particles when the previous update left an effective sample
     // size (sum w)^2 / sum w^2 of at least r * N; their weights then multiply, i.e. the log-weights add
+    // (with KLD on only while the next size is the current one: a kept set cannot change its size)
     bool keep = false;
-    if (resample_and_move && h->cfg.resample_neff_permille > 0 && h->carry_valid && !uniforms) {
+    if (resample_and_move && h->cfg.resample_neff_permille > 0 && h->carry_valid && !uniforms && n == n_par) {
         const double sw = h->h_scalars[1], sww = h->h_scalars[7];
         keep = sww > 0.0 && sw * sw >= ((double)h->cfg.resample_neff_permille / 1000.0) * (double)n * sww;
     }
     if (h->cfg.resample_neff_permille > 0 && h->cfg.weight_mode == MCL_WEIGHT_PRODUCT)
         return fail(h, MCL_ERR_UNSUPPORTED, "resample_neff_permille needs weight_mode LOG");
     if (!resample_and_move) HIPCHK(h, hipMemsetAsync(h->d_counters, 0, 4 * sizeof(unsigned long long), h->stream));   // else: the resampling kernel
+    if (n != n_par) {
+        // another size: nothing made for the old one is reused (captured graphs, the warm small-update paths, the previous
+        // update's ordering layout, the cleared-word cache), as when the particles are set from outside
+        graph_reset(h);
+        h->far_fresh = true;
+    }
     h->pc_ready = false;
     h->layout_stale_used = false; h->keys_done = false;      // (set below when this update orders by the previous update's layout)
     // A small update (k_rays_skip, the whole tail in one workgroup) is three launches and no copy: resampling + motion +
@@ -1690,12 +1820,13 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
                       choose_ray_mode(h, n, false) == 2 && h->cfg.weight_mode == MCL_WEIGHT_LOG && h->cfg.resample_neff_permille == 0;
     if (!tiny) HIPCHK(h, hipEventRecord(h->ev[EV_START], h->stream));
     bool obs_early = false;
+    mcl::KldArgs kld_cur{};
     if (resample_and_move) {
         const int c = h->cur, nx = c ^ 1;
         mcl::ResampleArgs a{};
         a.px = h->d_x[c]; a.py = h->d_y[c]; a.pth = h->d_th[c];
-        a.cdf = h->d_cdf; a.n_parents = n; a.q_total = h->q_total;
-        a.tile_excl = (h->blocktot_for == h->d_cdf && h->blocktot_n == n) ? h->d_blocktot : nullptr;   // spine of the scan that produced d_cdf
+        a.cdf = h->d_cdf; a.n_parents = n_par; a.q_total = h->q_total;
+        a.tile_excl = (h->blocktot_for == h->d_cdf && h->blocktot_n == n_par) ? h->d_blocktot : nullptr;   // spine of the scan that produced d_cdf
         a.leaders = a.tile_excl ? h->d_leaders : nullptr;
         // parents: the compact list the last scan left (the particles that carry weight: a few per cent after an update
         // with many beams) when it exists, else the full CDF and the packed records
@@ -1704,8 +1835,8 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
             a.ccdf = h->d_ccdf; a.ctop = h->d_ctop; a.n_compact = h->compact_n; a.cidx = h->d_cidx; a.crec = h->d_crec;
             a.cpack = nullptr;               // the next update most likely draws from a compact list again: no record per child
         } else {
-            if (!h->pack_valid[c] && n > 65536 && !keep) {       // records first: one fetch per gathered parent instead of three
-                hipLaunchKernelGGL(mcl::k_pack_records, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d_x[c], h->d_y[c], h->d_th[c], n, h->d_pack[c]);
+            if (!h->pack_valid[c] && n_par > 65536 && !keep) {   // records first: one fetch per gathered parent instead of three
+                hipLaunchKernelGGL(mcl::k_pack_records, dim3((unsigned)((n_par + 255) / 256)), dim3(256), 0, h->stream, h->d_x[c], h->d_y[c], h->d_th[c], n_par, h->d_pack[c]);
                 h->pack_valid[c] = true;
             }
             a.ppack = h->pack_valid[c] ? h->d_pack[c] : nullptr;
@@ -1741,15 +1872,35 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
         }
         resample_ray_extras(h, n, a);
         size_t cdf_lds = 0;
-        if (!a.tile_excl && a.do_resample && n <= mcl::kTinyTailMax) { a.cdf_lds_entries = (int)n; cdf_lds = (size_t)n * sizeof(uint64_t); }
+        if (!a.tile_excl && a.do_resample && n_par <= mcl::kTinyTailMax) { a.cdf_lds_entries = (int)n_par; cdf_lds = (size_t)n_par * sizeof(uint64_t); }
         h->ev_resample_bound = false;
-        if (!tiny && !h->capturing) {
-            hipExtLaunchKernelGGL(mcl::k_resample_motion, dim3((unsigned)((n + 255) / 256)), dim3(256), cdf_lds, h->stream, nullptr, h->ev[EV_RESAMPLE], 0, a);
+        const dim3 grid((unsigned)((n + 255) / 256));
+        if (kld) {
+            // the bins of the drawn parents are marked by the resampling kernel; the words it set are cleared and the count
+            // lands in word 17 of the result block -- by the one-workgroup tail of a small update, else by one launch right here
+            kld_cur = kld_args_of(&h->kld, h->kld_nx, h->kld_ny, h->ox, h->oy);
+            kld_cur.bm = h->d_kld_bm; kld_cur.list = h->d_kld_list;
+            kld_cur.count = h->d_kld_cnt + h->kld_parity; kld_cur.count_next = h->d_kld_cnt + (h->kld_parity ^ 1);
+            kld_cur.result = h->d_result + 17;
+            h->kld_parity ^= 1;
+            if (!tiny && !h->capturing) {
+                hipExtLaunchKernelGGL(mcl::k_resample_motion_kld, grid, dim3(256), cdf_lds, h->stream, nullptr, h->ev[EV_RESAMPLE], 0, a, kld_cur);
+                h->ev_resample_bound = true;
+            } else {
+                hipLaunchKernelGGL(mcl::k_resample_motion_kld, grid, dim3(256), cdf_lds, h->stream, a, kld_cur);
+            }
+            if (!tiny) {
+                const int64_t most = std::min<int64_t>(n, (int64_t)h->kld_bits);
+                hipLaunchKernelGGL(mcl::k_kld_clear, dim3((unsigned)std::min<int64_t>((most + 255) / 256, 1024)), dim3(256), 0, h->stream, kld_cur);
+            }
+        } else if (!tiny && !h->capturing) {
+            hipExtLaunchKernelGGL(mcl::k_resample_motion, grid, dim3(256), cdf_lds, h->stream, nullptr, h->ev[EV_RESAMPLE], 0, a);
             h->ev_resample_bound = true;
         } else {
-            hipLaunchKernelGGL(mcl::k_resample_motion, dim3((unsigned)((n + 255) / 256)), dim3(256), cdf_lds, h->stream, a);
+            hipLaunchKernelGGL(mcl::k_resample_motion, grid, dim3(256), cdf_lds, h->stream, a);
         }
         HIPCHK(h, hipGetLastError());
+        h->N = n;                          // the children: the ray stage and everything after it run on them
         if (a.pc_out) { const int rc_l = layout_mark(h, n); if (rc_l) return rc_l; }
         // The tables of this update's scan (table rows of the observed ranges, Lt, Ltd) depend on nothing the resampling and ordering
         // kernels produce: with a windowed ray kernel they are built on a second stream beside those, and the ray stage waits for
@@ -1773,7 +1924,7 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
     int rc;
     if (tiny) {
         rc = launch_rays(h, h->d_x[h->cur], h->d_y[h->cur], h->d_th[h->cur], n, false, true);
-        if (!rc) rc = weights_and_cdf(h, true);
+        if (!rc) rc = weights_and_cdf(h, true, kld ? &kld_cur : nullptr);
         if (rc) return rc;
         // The result block lands in pinned memory stamped with this update's sequence number: spin on the stamp instead of
         // the stream's completion signal (the signal's path through the runtime costs several microseconds at this size).
@@ -1790,6 +1941,7 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
         }
         if (!seen) HIPCHK(h, hipStreamSynchronize(h->stream));
         unpack_result(h);
+        if (kld) kld_decide(h, keep);
         h->have_logw = true;
         h->have_steps = h->cfg.keep_ray_steps != 0;
         h->update_idx++;
@@ -1849,6 +2001,7 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
         HIPCHK(h, hipStreamSynchronize(h->stream));
         h->compact_pending = h->d_ccdf != nullptr && !h->env_no_compact && n > mcl::kTinyTailMax;   // the captured scan wrote a list
         unpack_result(h);
+        if (kld) kld_decide(h, keep);
         h->carry_pending = false;
         h->have_logw = true;
         h->have_steps = h->cfg.keep_ray_steps != 0;
@@ -1910,6 +2063,7 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
     }
     if (h->carry_pending) { h->carry_idx ^= 1; h->carry_valid = true; h->carry_pending = false; }   // this update's logw - max
     { const int rc_l = layout_adopt(h, n); if (rc_l) return rc_l; }
+    if (kld) kld_decide(h, keep);
     h->graph_warm = true;                  // every buffer this configuration needs exists now
     h->have_logw = true;
     h->have_steps = h->cfg.keep_ray_steps != 0;
@@ -2082,6 +2236,79 @@ int mcl_get_effective_sample_size(const mcl_engine_t *h, double *n_eff, int32_t 
     return MCL_OK;
 }
 
+void mcl_default_kld_config(mcl_kld_config_t *k)
+{
+    if (!k) return;
+    *k = mcl_kld_config_t{};
+    k->min_particles = 256; k->max_particles = 4194304;
+    k->err = 0.01; k->z = 2.326;
+    k->bin_x_m = 0.5; k->bin_y_m = 0.5;
+    k->n_theta_bins = 36; k->round_to = 256; k->shrink_permille = 800;
+}
+
+int mcl_set_kld(mcl_engine_t *h, const mcl_kld_config_t *k)
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    if (!k) {
+        h->kld_on = false;
+        kld_reset(h);
+        return MCL_OK;
+    }
+    if (h->comm || h->in_group)
+        return fail(h, MCL_ERR_UNSUPPORTED, "KLD sampling is single-engine only: this engine has a communicator or belongs to a device group");
+    if (const char *why = kld_invalid(k, h->cap)) return fail(h, MCL_ERR_INVALID_ARG, why);
+    int64_t nx = 0, ny = 0;
+    uint64_t bits = 0;
+    if (h->have_map && !kld_grid(k, (uint32_t)h->W, (uint32_t)h->H, (float)h->res, nx, ny, bits))
+        return fail(h, MCL_ERR_INVALID_ARG, "KLD: the bin grid over this map exceeds 2^31 bits");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    h->kld = *k; h->kld_nx = nx; h->kld_ny = ny; h->kld_bits = bits;
+    h->kld_on = true;
+    const int rc = kld_alloc(h);
+    if (rc) { h->kld_on = false; return rc; }
+    kld_reset(h);
+    return MCL_OK;
+}
+
+int mcl_get_particle_count(const mcl_engine_t *h, int64_t *n)
+{
+    if (!h || !n) return MCL_ERR_INVALID_ARG;
+    *n = h->have_particles ? h->N : 0;
+    return MCL_OK;
+}
+
+int mcl_get_kld_state(const mcl_engine_t *h, int64_t *bins_last, int64_t *n_next)
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    if (bins_last) *bins_last = h->kld_on ? h->kld_bins_last : -1;
+    if (n_next) *n_next = h->kld_on ? h->kld_n_next : (h->have_particles ? h->N : 0);
+    return MCL_OK;
+}
+
+int mcl_host_kld_bins(const double *x, const double *y, const double *th, int64_t n, uint32_t width, uint32_t height,
+                      float resolution, double origin_x, double origin_y, const mcl_kld_config_t *k, int64_t *bins)
+{
+    if (!k || !bins || n < 0 || (n > 0 && (!x || !y || !th)) || width == 0 || height == 0 || !(resolution > 0.0f) ||
+        !std::isfinite(resolution) || kld_invalid(k, 0))
+        return MCL_ERR_INVALID_ARG;
+    int64_t nx = 0, ny = 0;
+    uint64_t nbits = 0;
+    if (!kld_grid(k, width, height, resolution, nx, ny, nbits)) return MCL_ERR_INVALID_ARG;
+    const mcl::KldArgs a = kld_args_of(k, nx, ny, origin_x, origin_y);
+    std::vector<uint32_t> b((size_t)n);
+    for (int64_t i = 0; i < n; ++i) b[(size_t)i] = mcl::kld_bin(a, x[i], y[i], th[i]);
+    std::sort(b.begin(), b.end());
+    *bins = (int64_t)(std::unique(b.begin(), b.end()) - b.begin());
+    return MCL_OK;
+}
+
+int mcl_host_kld_target(const mcl_kld_config_t *k, int64_t bins, int64_t n_current, int64_t *n_next)
+{
+    if (!k || !n_next || n_current < 0 || n_current >= MCL_MAX_TOTAL_PARTICLES || kld_invalid(k, 0)) return MCL_ERR_INVALID_ARG;
+    *n_next = kld_target(k, bins, n_current);
+    return MCL_OK;
+}
+
 int mcl_host_sensor_table(const mcl_config_t *cfg, int32_t P, double *out, size_t n)
 {
     if (!cfg || !out || P < 1 || n != (size_t)(P + 1) * (P + 1)) return MCL_ERR_INVALID_ARG;
@@ -2216,6 +2443,7 @@ int mcl_export_records_at(mcl_engine_t *h, const int64_t *d_index, int64_t count
 int mcl_stage_distinct_parents(mcl_engine_t *h, const int32_t *d_parent, int64_t n_children, int64_t n_total, int64_t *d_distinct,
                                int32_t *d_slot, int64_t *count)
 {
+    if (h && h->kld_on) return kld_refuse_stage(h);
     if (!h || !d_parent || !d_distinct || !d_slot || !count || n_children <= 0 || n_total <= 0) return MCL_ERR_INVALID_ARG;
     if (n_total > MCL_MAX_TOTAL_PARTICLES) return fail(h, MCL_ERR_INVALID_ARG, "n_total exceeds MCL_MAX_TOTAL_PARTICLES");
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -2359,6 +2587,7 @@ static int stage_resample_sync(mcl_engine_t *h, const ParentSource &src, const u
 int mcl_stage_resample(mcl_engine_t *h, const double *d_px, const double *d_py, const double *d_pth, const uint64_t *d_cdf,
                        int64_t n_parents, uint64_t q_total, int64_t child_first, int64_t n_children_total, const double action[3])
 {
+    if (h && h->kld_on) return kld_refuse_stage(h);
     ParentSource src; src.px = d_px; src.py = d_py; src.pth = d_pth;
     if (!d_px || !d_py || !d_pth) return h ? fail(h, MCL_ERR_INVALID_ARG, "bad stage_resample arguments") : MCL_ERR_INVALID_ARG;
     return stage_resample_sync(h, src, d_cdf, n_parents, q_total, child_first, n_children_total, action);
@@ -2367,6 +2596,7 @@ int mcl_stage_resample(mcl_engine_t *h, const double *d_px, const double *d_py, 
 int mcl_stage_resample_records(mcl_engine_t *h, const void *d_records, const uint64_t *d_cdf, int64_t n_parents, uint64_t q_total,
                                int64_t child_first, int64_t n_children_total, const double action[3])
 {
+    if (h && h->kld_on) return kld_refuse_stage(h);
     ParentSource src; src.records = d_records;
     if (!d_records) return h ? fail(h, MCL_ERR_INVALID_ARG, "bad stage_resample arguments") : MCL_ERR_INVALID_ARG;
     return stage_resample_sync(h, src, d_cdf, n_parents, q_total, child_first, n_children_total, action);
@@ -2375,6 +2605,7 @@ int mcl_stage_resample_records(mcl_engine_t *h, const void *d_records, const uin
 int mcl_stage_resample_indices(mcl_engine_t *h, const uint64_t *d_cdf, int64_t n_parents, uint64_t q_total, int64_t child_first,
                                int64_t n_children_total, int32_t *d_parent_idx)
 {
+    if (h && h->kld_on) return kld_refuse_stage(h);
     ParentSource src; src.idx_only_out = d_parent_idx;
     if (!d_parent_idx || !d_cdf) return h ? fail(h, MCL_ERR_INVALID_ARG, "bad stage_resample_indices arguments") : MCL_ERR_INVALID_ARG;
     return stage_resample_sync(h, src, d_cdf, n_parents, q_total, child_first, n_children_total, nullptr);
@@ -2383,6 +2614,7 @@ int mcl_stage_resample_indices(mcl_engine_t *h, const uint64_t *d_cdf, int64_t n
 int mcl_stage_motion_records(mcl_engine_t *h, const void *d_records, int64_t n_records, const int32_t *d_record_of_child, int64_t child_first,
                              int64_t n_children_total, const double action[3])
 {
+    if (h && h->kld_on) return kld_refuse_stage(h);
     ParentSource src; src.records = d_records; src.idx_in = d_record_of_child;
     if (!d_records || !d_record_of_child || n_records <= 0) return h ? fail(h, MCL_ERR_INVALID_ARG, "bad stage_motion_records arguments") : MCL_ERR_INVALID_ARG;
     return stage_resample_sync(h, src, nullptr, n_records, 0, child_first, n_children_total, action);
@@ -2461,6 +2693,7 @@ int mcl_stage_resample_compact(mcl_engine_t *h, const void *d_chunks, int32_t n_
                                const uint64_t *totals, int64_t n_per_shard, int32_t self_shard, int64_t child_first, int64_t n_children_total,
                                const double action[3])
 {
+    if (h && h->kld_on) return kld_refuse_stage(h);
     const int rc = stage_resample_compact_launch(h, d_chunks, n_shards, chunk_entries, counts, totals, n_per_shard, self_shard, child_first,
                                                  n_children_total, action, nullptr);
     if (rc) return rc;
@@ -2536,6 +2769,7 @@ static int stage_rays_finish(mcl_engine_t *h, const float *obs, int32_t n_beams)
 
 int mcl_stage_rays(mcl_engine_t *h, const float *obs, int32_t n_beams)
 {
+    if (h && h->kld_on) return kld_refuse_stage(h);
     int rc = stage_rays_launch(h, obs, n_beams, false);
     if (rc) return rc;
     return stage_rays_finish(h, obs, n_beams);
@@ -2545,6 +2779,7 @@ int mcl_stage_propagate(mcl_engine_t *h, const double *d_px, const double *d_py,
                         int64_t n_parents, uint64_t q_total, int64_t child_first, int64_t n_children_total,
                         const double action[3], const float *obs, int32_t n_beams)
 {
+    if (h && h->kld_on) return kld_refuse_stage(h);
     if (!h) return MCL_ERR_INVALID_ARG;
     if (!obs || n_beams != h->B) return fail(h, MCL_ERR_INVALID_ARG, "bad observation");
     int rc = mcl_stage_resample(h, d_px, d_py, d_pth, d_cdf, n_parents, q_total, child_first, n_children_total, action);
@@ -2600,6 +2835,7 @@ static int stage_weights_finish(mcl_engine_t *h)
 
 int mcl_stage_weights(mcl_engine_t *h, double global_max_logw)
 {
+    if (h && h->kld_on) return kld_refuse_stage(h);
     int rc = stage_weights_launch(h, global_max_logw);
     if (rc) return rc;
     return stage_weights_finish(h);
@@ -2614,6 +2850,7 @@ static void stage_commit_carry(mcl_engine_t *h)
 
 int mcl_stage_finish(mcl_engine_t *h, const double global_sums[5])
 {
+    if (h && h->kld_on) return kld_refuse_stage(h);
     if (!h || !global_sums) return MCL_ERR_INVALID_ARG;
     for (int i = 0; i < 5; ++i) h->global_sums[i] = global_sums[i];
     stage_commit_carry(h);
@@ -2627,6 +2864,7 @@ int mcl_stage_finish(mcl_engine_t *h, const double global_sums[5])
 // previous update's log-weights minus their global maximum, as mcl_update does.  Launch only (no wait).
 int mcl_stage_keep(mcl_engine_t *h, int64_t child_first, int64_t n_children_total, const double action[3])
 {
+    if (h && h->kld_on) return kld_refuse_stage(h);
     if (!h || !action) return MCL_ERR_INVALID_ARG;
     if (h->cfg.resample_neff_permille <= 0) return fail(h, MCL_ERR_UNSUPPORTED, "mcl_stage_keep needs resample_neff_permille > 0");
     if (!h->carry_valid) return fail(h, MCL_ERR_NOT_READY, "no log-weights of a previous update to carry");
@@ -2667,12 +2905,14 @@ int mcl_stage_resample_compact_async(mcl_engine_t *h, const void *d_chunks, int3
                                      const uint64_t *totals, int64_t n_per_shard, int32_t self_shard, int64_t child_first,
                                      int64_t n_children_total, const double action[3])
 {
+    if (h && h->kld_on) return kld_refuse_stage(h);
     return stage_resample_compact_launch(h, d_chunks, n_shards, chunk_entries, counts, totals, n_per_shard, self_shard, child_first,
                                          n_children_total, action, nullptr);
 }
 
 int mcl_stage_rays_async(mcl_engine_t *h, const float *obs, int32_t n_beams, double *d_local_max)
 {
+    if (h && h->kld_on) return kld_refuse_stage(h);
     if (!h || !d_local_max) return MCL_ERR_INVALID_ARG;
     const int rc = stage_rays_launch(h, obs, n_beams, false, d_local_max);
     if (rc) return rc;
@@ -2682,6 +2922,7 @@ int mcl_stage_rays_async(mcl_engine_t *h, const float *obs, int32_t n_beams, dou
 
 int mcl_stage_weights_async(mcl_engine_t *h, const double *d_global_max, double *d_vec, int32_t n_shards, int32_t self_shard)
 {
+    if (h && h->kld_on) return kld_refuse_stage(h);
     if (!h || !d_global_max || !d_vec || n_shards <= 0 || n_shards > mcl::kMaxShards || self_shard < 0 || self_shard >= n_shards)
         return MCL_ERR_INVALID_ARG;
     if (!h->stage_async_rays) return fail(h, MCL_ERR_NOT_READY, "mcl_stage_rays_async first");
@@ -2696,6 +2937,7 @@ int mcl_stage_weights_async(mcl_engine_t *h, const double *d_global_max, double 
 
 int mcl_stage_complete(mcl_engine_t *h, const double global_sums[5], int32_t *redo)
 {
+    if (h && h->kld_on) return kld_refuse_stage(h);
     if (!h || !global_sums || !redo) return MCL_ERR_INVALID_ARG;
     if (!h->stage_async_rays || !h->stage_async_weights) return fail(h, MCL_ERR_NOT_READY, "mcl_stage_rays_async and mcl_stage_weights_async first");
     h->stage_async_rays = h->stage_async_weights = false;

@@ -22,8 +22,9 @@ enum { EV_START = 0, EV_RESAMPLE, EV_QUERY, EV_RAYS, EV_SENSOR, EV_K0, EV_K1, EV
 
 constexpr unsigned long long kExactCap = 1ull << 16;   // level-3 rays per launch handled by k_rays_exact (more: inline)
 // d_result / h_result: [0..7] scalars, [8..11] counters, [12] work-list overflow flag, [13] work counter, [14] level-3 list
-// length, [15] far-list length (and the staging word of a global maximum), [16] length of the compact parent list
-constexpr int kResultWords = 17;
+// length, [15] far-list length (and the staging word of a global maximum), [16] length of the compact parent list, [17] pose-space
+// bins the update's draw occupied (KLD sampling, mcl_set_kld)
+constexpr int kResultWords = 18;
 constexpr int kResultStage = 40;             // h_result word that stages a host value on its way to the device
 constexpr int kResultStamp = 32;             // h_result word a small update's last kernel stamps (the host polls it)
 
@@ -237,6 +238,20 @@ struct mcl_engine {
     bool ray_ms_is_graph_tail = false;  // ray_ms is the whole captured tail of a small update, not one kernel
     unsigned long long h_counters[4]{};
     unsigned long long h_fix_count = 0;
+    // KLD-adaptive particle count (mcl_set_kld): the resampling kernel marks the bin of every drawn parent in
+    // d_kld_bm and lists the words of new bins in d_kld_list; the counter of update t is d_kld_cnt[kld_parity], the clearing
+    // kernel of that update zeroes the other one
+    bool kld_on = false;
+    bool in_group = false;              // one of a device group's engines (mcl_group_create): KLD is refused
+    mcl_kld_config_t kld{};
+    int64_t kld_nx = 0, kld_ny = 0;     // bin grid of the current map
+    uint64_t kld_bits = 0;              // kld_nx * kld_ny * n_theta_bins + 1 (the outside bin)
+    int64_t kld_n_next = 0;             // children the next mcl_update draws
+    int64_t kld_bins_last = -1;         // bins the last update's draw occupied (-1: none counted)
+    uint32_t *d_kld_bm = nullptr, *d_kld_list = nullptr;
+    unsigned int *d_kld_cnt = nullptr;  // 2 counters
+    size_t kld_bm_words = 0, kld_list_cap = 0;
+    int kld_parity = 0;
 };
 
 #define HIPCHK(h, call)                                                                          \

@@ -103,6 +103,7 @@ int mcl_group_create(const mcl_config_t *cfg, const int32_t *devices, int32_t n_
         mcl_engine_t *e = nullptr;
         const int rc = mcl_create(&c, &e);
         if (rc != MCL_OK) { mcl_group_destroy(g); return rc; }
+        e->in_group = true;                 // (KLD sampling is single-engine only: mcl_set_kld refuses this engine)
         g->eng.push_back(e);
     }
     g->d_qall.assign(n_devices, nullptr); g->d_cdfall.assign(n_devices, nullptr); g->d_remote.assign(n_devices, nullptr);

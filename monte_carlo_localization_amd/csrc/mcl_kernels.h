@@ -291,7 +291,64 @@ __device__ __forceinline__ double4 particle_constants(double x, double y, double
     return make_double4(c, s, heading_ok ? (x - ox) / res : nanv, heading_ok ? (y - oy) / res : nanv);
 }
 
-__global__ __launch_bounds__(256) void k_resample_motion(ResampleArgs a)
+// KLD-adaptive particle count: the pose-space bin of every child's parent pose (before the motion model) is
+// marked in a bitmap of nx * ny * n_theta + 1 bits (the last one: "outside"), test-then-set, and the lane whose fetch-or found
+// the bit clear owns the new bin: owners are summed per wave (one atomic per wave) and append their word index to a list, so
+// that the count is exact and independent of the order, and the clearing kernel touches only those words.
+struct KldArgs {
+    uint32_t *bm;                     // bitmap (all zero on entry)
+    uint32_t *list;                   // word index of every new bin, in the order the waves reserved them (*count entries)
+    unsigned int *count;              // bins found by this update (zero on entry)
+    unsigned int *count_next;         // the next update's counter: zeroed by the clearing kernel
+    unsigned long long *result;       // where the clearing kernel leaves *count (a word of the result block)
+    double ox, oy, inv_bx, inv_by;    // map origin, 1 / bin size (computed once in double on the host)
+    double th_scale;                  // n_theta / (2 pi)
+    double nx_d, ny_d;                // bins per axis (as doubles: the range test happens before any conversion)
+    double nth_d, inv_nth;            // n_theta and its reciprocal
+    uint32_t nx, ny, nth;
+    uint32_t outside;                 // nx * ny * n_theta: the bin of every pose off the grid, non-finite or with |theta| >= 1e9
+};
+
+// bin of a pose: ix = floor((x - ox) * inv_bx), iy alike, it = floor((theta + pi) * th_scale) mod n_theta; each an add or
+// subtract followed by a multiply (no form FMA contraction could fuse: the host restatement agrees bit for bit)
+__host__ __device__ __forceinline__ uint32_t kld_bin(const KldArgs &k, double x, double y, double th)
+{
+    const double fx = floor((x - k.ox) * k.inv_bx), fy = floor((y - k.oy) * k.inv_by);
+    if (!(fx >= 0.0 && fx < k.nx_d && fy >= 0.0 && fy < k.ny_d && fabs(th) < 1e9)) return k.outside;   // (NaN fails every test)
+    // the heading bin: t mod n_theta of the integral t, in double (an emulated 64-bit remainder is a long sequence per child).
+    // Below 2^52 the quotient from the reciprocal is off by at most one and q * n_theta, t - q * n_theta are exact integers,
+    // so one correction gives the exact remainder; beyond (only with tens of millions of heading bins) the integer form.
+    const double t = floor((th + 3.14159265358979323846) * k.th_scale);
+    uint32_t it;
+    if (fabs(t) < 4503599627370496.0) {
+        double r = t - floor(t * k.inv_nth) * k.nth_d;
+        if (r < 0.0) r += k.nth_d;
+        else if (r >= k.nth_d) r -= k.nth_d;
+        it = (uint32_t)r;
+    } else {
+        int64_t i = (int64_t)t % (int64_t)k.nth;
+        if (i < 0) i += (int64_t)k.nth;
+        it = (uint32_t)i;
+    }
+    // (every partial index is below nx * ny * n_theta <= 2^31)
+    return (it * k.ny + (uint32_t)fy) * k.nx + (uint32_t)fx;
+}
+
+// the words the update's owners listed back to zero, the next counter zeroed, the count into the result block; thread i of n
+__device__ __forceinline__ void kld_clear_part(const KldArgs &k, int64_t i, int64_t nthreads)
+{
+    const unsigned int c = *k.count;
+    for (int64_t j = i; j < (int64_t)c; j += nthreads) k.bm[k.list[j]] = 0u;
+    if (i == 0) { *k.count_next = 0u; *k.result = c; }
+}
+
+__global__ __launch_bounds__(256) void k_kld_clear(KldArgs k)
+{
+    kld_clear_part(k, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+}
+
+template <bool KLD>
+__device__ __forceinline__ void resample_motion_body(const ResampleArgs &a, const KldArgs &k)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char resample_lds[];
     int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -433,6 +490,7 @@ __global__ __launch_bounds__(256) void k_resample_motion(ResampleArgs a)
         }
     } else if (a.ppack) { const double4 pr = a.ppack[idx]; x = pr.x; y = pr.y; th = pr.z; }
     else { x = a.px[idx]; y = a.py[idx]; th = a.pth[idx]; }
+    [[maybe_unused]] const double kx = x, ky = y, kth = th;     // (KLD: the parent's pose, marked at the end of the kernel)
     if (a.do_motion) {
         double n0, n1, n2;
         if (a.normals) {
@@ -492,7 +550,36 @@ __global__ __launch_bounds__(256) void k_resample_motion(ResampleArgs a)
     }
     if (a.clr_logw_acc) a.clr_logw_acc[m] = 0.0;
     if (a.clr_far_flags) a.clr_far_flags[m] = 0u;
+    if constexpr (KLD) {
+        // the parent's pose (a kept update: the particle's own), after the child's stores (the marking's dependent loads and
+        // atomics then wait behind them, not in front of them): plain load first, the atomic only for a bit not seen set, and
+        // only by one lane per distinct bin of the wave (the children of a parent are neighbours, a tracking set has a few tens
+        // of bins: one fetch-or per lane would pile thousands of waves' atomics onto the same few words)
+        const uint32_t b = kld_bin(k, kx, ky, kth);
+        const uint32_t wi = b >> 5, bit = 1u << (b & 31u);
+        const int lane = (int)(threadIdx.x & 63);
+        const bool need = !(k.bm[wi] & bit);
+        bool owner = false;
+        for (unsigned long long pending = __ballot(need); pending;) {
+            const int l = __ffsll((long long)pending) - 1;
+            const uint32_t bl = (uint32_t)__shfl((int)b, l);
+            pending &= ~__ballot(need && b == bl);
+            if (lane == l) owner = !(__hip_atomic_fetch_or(&k.bm[wi], bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit);
+        }
+        const unsigned long long own = __ballot(owner);
+        if (own) {
+            const int first = __ffsll((long long)own) - 1;
+            unsigned int base = 0;
+            if (lane == first) base = atomicAdd(k.count, (unsigned int)__popcll(own));
+            base = (unsigned int)__shfl((int)base, first);
+            if (owner) k.list[base + (unsigned int)__popcll(own & ((1ull << lane) - 1ull))] = wi;
+        }
+    }
 }
+
+__global__ __launch_bounds__(256) void k_resample_motion(ResampleArgs a) { resample_motion_body<false>(a, KldArgs{}); }
+// the same with the KLD bin marking (a separate instantiation: the kernel without it is the one above, unchanged)
+__global__ __launch_bounds__(256) void k_resample_motion_kld(ResampleArgs a, KldArgs k) { resample_motion_body<true>(a, k); }
 
 // The shards' compact lists, gathered as chunks ([ccdf | crec | cidx], ccap entries each), become ONE searchable CDF: chunk r's
 // column plus the fixed-point total of the shards before it, its unused tail turned into a plateau at the shard's end value
@@ -2230,14 +2317,17 @@ __global__ __launch_bounds__(kRedThreads) void k_final_sums(const double *__rest
 // particles; the fixed-point weights wait in LDS for the scan, which needs consecutive runs per thread.  The sums are
 // reduced in this kernel's own fixed order (thread-strided, wave butterflies, waves in order): deterministic for a given N.
 // pc: (cos, sin, ., .) of every heading as k_particle_prep left them (the same sincos call), or null.
+// KLD: the one workgroup also clears the bitmap words the resampling kernel listed (<= n) and reports the bin count (word 17).
 constexpr int64_t kTinyTailMax = 8192;
+template <bool KLD>
 __global__ __launch_bounds__(1024) void k_tiny_tail(const double *__restrict__ logw, const double *__restrict__ x, const double *__restrict__ y,
                                                    const double *__restrict__ th, const double4 *__restrict__ pc, int64_t n,
                                                    double *__restrict__ w_out, uint64_t *__restrict__ q_out, uint64_t *__restrict__ cdf_out,
                                                    double *__restrict__ scalars, unsigned long long *__restrict__ host_out,
-                                                   unsigned long long host_seq)
+                                                   unsigned long long host_seq, KldArgs kld)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char tail_lds[];
+    if constexpr (KLD) kld_clear_part(kld, threadIdx.x, 1024);
     uint64_t *q_sh = reinterpret_cast<uint64_t *>(tail_lds);       // n entries
     __shared__ double sm[16][7];
     __shared__ uint64_t wave_tot[16];
@@ -2297,6 +2387,7 @@ __global__ __launch_bounds__(1024) void k_tiny_tail(const double *__restrict__ l
             const unsigned long long *blk = reinterpret_cast<const unsigned long long *>(scalars);
             for (int k = 0; k < 8; ++k) host_out[k] = (unsigned long long)__double_as_longlong(scalars[k]);
             for (int k = 8; k < 14; ++k) host_out[k] = blk[k];
+            if constexpr (KLD) host_out[17] = *kld.count;
             // the host may be polling word 32 (kResultStamp) instead of waiting for the stream's completion signal
             __threadfence_system();
             __hip_atomic_store(&host_out[32], host_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);

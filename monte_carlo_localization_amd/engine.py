@@ -43,6 +43,7 @@ EXPORTS = [
     "mcl_stage_rays_async", "mcl_stage_weights_async", "mcl_stage_complete", "mcl_stage_keep",
     "mcl_comm_available", "mcl_comm_unique_id", "mcl_comm_create", "mcl_comm_destroy", "mcl_comm_update", "mcl_comm_stats", "mcl_comm_set_lists", "mcl_comm_get_vector", "mcl_comm_last_exchange", "mcl_comm_selftest",
     "mcl_host_sweep_global_layout", "mcl_get_ray_kernel_variant",
+    "mcl_default_kld_config", "mcl_set_kld", "mcl_get_particle_count", "mcl_get_kld_state", "mcl_host_kld_bins", "mcl_host_kld_target",
 ]
 
 
@@ -55,6 +56,15 @@ class Config(C.Structure):
         ("weight_mode", C.c_int32), ("ray_kernel", C.c_int32), ("keep_ray_steps", C.c_int32),
         ("debug_force_exact", C.c_int32), ("debug_count_probes", C.c_int32), ("rays_per_lane", C.c_int32),
         ("resample_neff_permille", C.c_int32), ("graph_mode", C.c_int32), ("reserved", C.c_int32 * 3),
+    ]
+
+
+class KldConfig(C.Structure):
+    """mcl_kld_config_t: KLD-adaptive particle count (Engine.set_kld)."""
+    _fields_ = [
+        ("min_particles", C.c_int64), ("max_particles", C.c_int64), ("err", C.c_double), ("z", C.c_double),
+        ("bin_x_m", C.c_double), ("bin_y_m", C.c_double), ("n_theta_bins", C.c_int32), ("round_to", C.c_int32),
+        ("shrink_permille", C.c_int32), ("reserved", C.c_int32),
     ]
 
 
@@ -116,6 +126,14 @@ def load_library(legacy=False):
         lib.mcl_group_create.argtypes = [C.POINTER(Config), C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
         lib.mcl_group_destroy.argtypes = [C.c_void_p]
         lib.mcl_group_destroy.restype = None
+        lib.mcl_default_kld_config.argtypes = [C.POINTER(KldConfig)]
+        lib.mcl_default_kld_config.restype = None
+        lib.mcl_set_kld.argtypes = [C.c_void_p, C.POINTER(KldConfig)]
+        lib.mcl_get_particle_count.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        lib.mcl_get_kld_state.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        lib.mcl_host_kld_bins.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint32, C.c_uint32, C.c_float,
+                                          C.c_double, C.c_double, C.POINTER(KldConfig), C.POINTER(C.c_int64)]
+        lib.mcl_host_kld_target.argtypes = [C.POINTER(KldConfig), C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
         _libs[path] = _lib = lib
     return _lib
 
@@ -128,6 +146,38 @@ def default_config(**over) -> Config:
             raise AttributeError(k)
         setattr(cfg, k, v)
     return cfg
+
+
+def default_kld_config(**over) -> KldConfig:
+    """mcl_default_kld_config, with fields overridden by keyword."""
+    k = KldConfig()
+    load_library().mcl_default_kld_config(C.byref(k))
+    for name, v in over.items():
+        if name not in dict(KldConfig._fields_):
+            raise AttributeError(name)
+        setattr(k, name, v)
+    return k
+
+
+def host_kld_bins(x, y, th, width, height, resolution, origin_x, origin_y, kld: KldConfig) -> int:
+    """Pose-space bins the poses (x, y, th) occupy under the KLD bin rule (mcl_host_kld_bins; no device needed)."""
+    x, y, th = _c(x, np.float64), _c(y, np.float64), _c(th, np.float64)
+    assert x.size == y.size == th.size
+    out = C.c_int64()
+    rc = load_library().mcl_host_kld_bins(_p(x), _p(y), _p(th), x.size, width, height, np.float32(resolution), origin_x, origin_y,
+                                          C.byref(kld), C.byref(out))
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_kld_bins rc={rc}", rc)
+    return out.value
+
+
+def host_kld_target(kld: KldConfig, bins: int, n_current: int) -> int:
+    """The particle count the update after one that counted `bins` with n_current particles draws (mcl_host_kld_target)."""
+    out = C.c_int64()
+    rc = load_library().mcl_host_kld_target(C.byref(kld), int(bins), int(n_current), C.byref(out))
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_kld_target rc={rc}", rc)
+    return out.value
 
 
 def _p(a):
@@ -250,7 +300,7 @@ class Engine:
         n = p.shape[1]
         assert w.size == n
         self._chk(self.lib.mcl_set_particles(self._h, _p(p), _p(w), C.c_int64(n)), "mcl_set_particles")
-        self.n = n
+        self.n = self.particle_count()
 
     def set_particles_shard(self, xyz_colmajor, weights, max_weight_of_the_whole_set):
         """set_particles for one shard of a larger set: weights are quantised against the whole set's maximum weight."""
@@ -260,22 +310,23 @@ class Engine:
         assert p.ndim == 2 and p.shape[0] == 3 and w.size == n
         self._chk(self.lib.mcl_set_particles_shard(self._h, _p(p), _p(w), C.c_int64(n), C.c_double(max_weight_of_the_whole_set)),
                   "mcl_set_particles_shard")
-        self.n = n
+        self.n = self.particle_count()
 
     def init_particles_pose(self, pose, n, first_global_index=0, n_total=None):
         p = _c(pose, np.float64)
         self._chk(self.lib.mcl_init_particles_pose(self._h, _p(p), C.c_int64(n), C.c_int64(first_global_index),
                                                    C.c_int64(n_total or n)), "mcl_init_particles_pose")
-        self.n = n
+        self.n = self.particle_count()
 
     def init_global(self, n, first_global_index=0, n_total=None):
         self._chk(self.lib.mcl_init_global(self._h, C.c_int64(n), C.c_int64(first_global_index), C.c_int64(n_total or n)),
                   "mcl_init_global")
-        self.n = n
+        self.n = self.particle_count()
 
     def update_scan(self, action, ranges, angle_step):
         a, r = _c(action, np.float64), _c(ranges, np.float32)
         self._chk(self.lib.mcl_update_scan(self._h, _p(a), _p(r), C.c_int32(r.size), C.c_int32(angle_step)), "mcl_update_scan")
+        self.n = self.particle_count()
 
     def get_particles(self):
         out = np.empty((3, self.n), np.float64)
@@ -303,11 +354,36 @@ class Engine:
         a = _c(action, np.float64)
         o = _c(obs, np.float32)
         nrm, u = _c(normals, np.float64), _c(uniforms, np.float64)
+        rows = self.kld_state()[1] if (nrm is not None or u is not None) else self.n    # (KLD on: the size of this update's draw)
         if nrm is not None:
-            assert nrm.size == 3 * self.n
+            assert nrm.size == 3 * rows
         if u is not None:
-            assert u.size == self.n
+            assert u.size == rows
         self._chk(self.lib.mcl_update(self._h, _p(a), _p(o), C.c_int32(o.size), _p(nrm), _p(u)), "mcl_update")
+        self.n = self.particle_count()
+
+    # -- KLD-adaptive particle count (off by default)
+    def set_kld(self, on=True, **fields):
+        """Switches KLD sampling on with mcl_default_kld_config's values overridden by `fields` (max_particles defaults to the
+        smaller of 4194304 and the engine's max_particles), or off (on=False)."""
+        if not on:
+            self._chk(self.lib.mcl_set_kld(self._h, None), "mcl_set_kld")
+            return None
+        fields.setdefault("max_particles", min(4194304, int(self.cfg.max_particles)))
+        k = default_kld_config(**fields)
+        self._chk(self.lib.mcl_set_kld(self._h, C.byref(k)), "mcl_set_kld")
+        return k
+
+    def kld_state(self):
+        """(bins the last update's draw occupied or -1, children the next update draws)"""
+        b, n = C.c_int64(), C.c_int64()
+        self._chk(self.lib.mcl_get_kld_state(self._h, C.byref(b), C.byref(n)), "mcl_get_kld_state")
+        return b.value, n.value
+
+    def particle_count(self) -> int:
+        n = C.c_int64()
+        self._chk(self.lib.mcl_get_particle_count(self._h, C.byref(n)), "mcl_get_particle_count")
+        return n.value
 
     def sensor_update(self, obs):
         o = _c(obs, np.float32)
