@@ -123,6 +123,9 @@ void mcl_default_config(mcl_config_t *cfg);
 int mcl_abi_version(void);
 
 /* ---- lifetime ---------------------------------------------------------------------------- */
+/* MCL_ERR_INVALID_ARG, before any device is opened, for a config the engine cannot run: max_particles outside [1, 2^27), a
+ * squash_factor or max_range_m that is not finite and > 0, a non-finite or negative z_* or motion_dispersion_*, all four z_* zero,
+ * a sigma_hit that is not finite and > 0; mcl_last_error(NULL) says which. */
 int mcl_create(const mcl_config_t *cfg, mcl_engine_t **out);
 void mcl_destroy(mcl_engine_t *h);
 /* Message of the last failing call on this handle ("" if none).  h may be NULL for mcl_create. */
@@ -280,7 +283,8 @@ int mcl_host_kld_target(const mcl_kld_config_t *k, int64_t bins, int64_t n_curre
 
 /* ---- host-side precomputation, callable without a device (what mcl_set_map uploads) --------- */
 /* (P+1)^2 doubles, Eigen column-major (index d*(P+1)+r): the restatement of precompute_sensor_model
- * (cpp:233-292) the engine uses. */
+ * (cpp:233-292) the engine uses.  MCL_ERR_INVALID_ARG for the sensor fields mcl_create refuses (a non-finite or negative
+ * z_*, all four z_* zero, a non-finite sigma_hit or sigma_hit <= 0). */
 int mcl_host_sensor_table(const mcl_config_t *cfg, int32_t max_range_px, double *out, size_t n);
 /* Skip-distance field of DESIGN.md §4.2 on the padded grid: (height+1) x (width+1) bytes, row-major,
  * 0 = stop cell, otherwise how many samples the fixed-step march may advance from a sample in that cell. */

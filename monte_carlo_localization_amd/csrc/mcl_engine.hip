@@ -49,6 +49,18 @@ void dfree(T *&p)
     if (p) { (void)hipFree(p); p = nullptr; }
 }
 
+// What the sensor model's fields must satisfy for the table to be a probability table (null: they do).  The reference does not
+// check them; here a NaN or a zero row would reach every log-weight (E5).
+const char *bad_sensor_fields(const mcl_config_t &c)
+{
+    const double z[4] = {c.z_hit, c.z_short, c.z_max, c.z_rand};
+    for (double v : z)
+        if (!std::isfinite(v) || v < 0.0) return "bad config (z_hit, z_short, z_max and z_rand must be finite and >= 0)";
+    if (z[0] == 0.0 && z[1] == 0.0 && z[2] == 0.0 && z[3] == 0.0) return "bad config (z_hit, z_short, z_max and z_rand are all 0)";
+    if (!std::isfinite(c.sigma_hit) || !(c.sigma_hit > 0.0)) return "bad config (sigma_hit must be finite and > 0)";
+    return nullptr;
+}
+
 // cpp:233-292, restated; column-major (d*(tw)+r).
 void build_sensor_table(const mcl_config_t &c, int P, std::vector<double> &t)
 {
@@ -1057,6 +1069,19 @@ int mcl_create(const mcl_config_t *cfg, mcl_engine_t **out)
     if (cfg->max_particles <= 0 || cfg->max_particles >= MCL_MAX_TOTAL_PARTICLES || cfg->squash_factor <= 0 || cfg->max_range_m <= 0) {
         g_create_error = "bad config (max_particles must be in [1, 2^27) / squash_factor / max_range_m)";
         return MCL_ERR_INVALID_ARG;
+    }
+    if (!std::isfinite(cfg->squash_factor) || !std::isfinite(cfg->max_range_m)) {
+        g_create_error = "bad config (squash_factor and max_range_m must be finite)";
+        return MCL_ERR_INVALID_ARG;
+    }
+    if (const char *why = bad_sensor_fields(*cfg)) { g_create_error = why; return MCL_ERR_INVALID_ARG; }
+    {
+        const double disp[3] = {cfg->motion_dispersion_x, cfg->motion_dispersion_y, cfg->motion_dispersion_theta};
+        for (double v : disp)
+            if (!std::isfinite(v) || v < 0.0) {
+                g_create_error = "bad config (motion_dispersion_x/y/theta must be finite and >= 0)";
+                return MCL_ERR_INVALID_ARG;
+            }
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device < 0 || cfg->device >= ndev) {
@@ -2311,7 +2336,7 @@ int mcl_host_kld_target(const mcl_kld_config_t *k, int64_t bins, int64_t n_curre
 
 int mcl_host_sensor_table(const mcl_config_t *cfg, int32_t P, double *out, size_t n)
 {
-    if (!cfg || !out || P < 1 || n != (size_t)(P + 1) * (P + 1)) return MCL_ERR_INVALID_ARG;
+    if (!cfg || !out || P < 1 || n != (size_t)(P + 1) * (P + 1) || bad_sensor_fields(*cfg)) return MCL_ERR_INVALID_ARG;
     std::vector<double> t;
     build_sensor_table(*cfg, P, t);
     std::memcpy(out, t.data(), n * sizeof(double));

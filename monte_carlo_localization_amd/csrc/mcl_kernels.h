@@ -2209,7 +2209,8 @@ __global__ void k_stage_pack(const unsigned long long *__restrict__ res, double 
     }
 }
 
-// from_log: w = det_exp(logw - *maxp) (max element -> exactly 1); else w given, scaled by 1/ *maxp
+// from_log: w = det_exp(logw - *maxp) (max element -> exactly 1), and w = 0 where logw = -inf (E5: also when the maximum is
+// -inf, where logw - max would be NaN); else w given, scaled by 1/ *maxp
 // for the fixed-point value only.  Writes w, q and per-block partials
 // [sum w, sum q (bits), sum w x, sum w y, sum w sin, sum w cos].
 __global__ __launch_bounds__(kRedThreads) void k_weights(const double *__restrict__ logw_or_w, int from_log,
@@ -2242,7 +2243,11 @@ __global__ __launch_bounds__(kRedThreads) void k_weights(const double *__restric
     uint64_t sq = 0;
     for (int64_t i = (int64_t)blockIdx.x * kRedThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kRedThreads) {
         double w, wq;
-        if (from_log) { const double d = logw_or_w[i] - mx; w = det_exp(d); wq = w; if (carry_out) carry_out[i] = d; }
+        if (from_log) {
+            const double lw = logw_or_w[i];
+            const double d = lw == -INFINITY ? -INFINITY : lw - mx;
+            w = det_exp(d); wq = w; if (carry_out) carry_out[i] = d;
+        }
         else {
             w = logw_or_w[i];
             wq = (mx > 0.0 && w > 0.0) ? (w / mx) : 0.0;
@@ -2347,7 +2352,8 @@ __global__ __launch_bounds__(1024) void k_tiny_tail(const double *__restrict__ l
     const double mx = mx_sh;
     double sw = 0, swx = 0, swy = 0, sws = 0, swc = 0, sww = 0;
     for (int64_t i = threadIdx.x; i < n; i += 1024) {
-        const double w = det_exp(logw[i] - mx);
+        const double lw = logw[i];
+        const double w = det_exp(lw == -INFINITY ? -INFINITY : lw - mx);      // E5: logw = -inf -> w = 0, even when mx = -inf
         const uint64_t q = (uint64_t)(w * kWeightScale);
         w_out[i] = w;
         q_out[i] = q;

@@ -474,13 +474,14 @@ double orc_eng_det_exp(double x)
 
 #define ORC_WEIGHT_FRAC_BITS 36
 
-/* E5: w_i = det_exp(logw_i - max), q_i = floor(w_i * 2^36).  Returns max. */
+/* E5: w_i = det_exp(logw_i - max), q_i = floor(w_i * 2^36); logw_i = -inf -> w_i = q_i = 0 (also when max = -inf,
+ * where logw_i - max is NaN).  Returns max. */
 double orc_eng_weights_from_log(int64_t N, const double *logw, double *w_out, uint64_t *q_out)
 {
     double mx = -INFINITY;
     for (int64_t i = 0; i < N; ++i) if (logw[i] > mx) mx = logw[i];
     for (int64_t i = 0; i < N; ++i) {
-        double w = orc_eng_det_exp(logw[i] - mx);
+        double w = (logw[i] == -INFINITY) ? 0.0 : orc_eng_det_exp(logw[i] - mx);
         if (w_out) w_out[i] = w;
         if (q_out) q_out[i] = (uint64_t)(w * 68719476736.0);
     }

@@ -18,11 +18,13 @@ def main():
     # MCL_TEST_NCCL=1: RCCL with one DISTINCT device per rank (needs at least `world` GPUs); else gloo, the ranks share GPU 0
     nccl = os.environ.get("MCL_TEST_NCCL") == "1"
     dev_index = rank if nccl else 0
+    # MCL_TEST_STORE: the ranks meet in this file (tests/test_dist.py); else MASTER_ADDR / MASTER_PORT
+    init = "file://" + os.environ["MCL_TEST_STORE"] if os.environ.get("MCL_TEST_STORE") else "env://"
     if nccl:
         torch.cuda.set_device(dev_index)
-        dist.init_process_group(backend="nccl", rank=rank, world_size=world, device_id=torch.device("cuda", dev_index))
+        dist.init_process_group(backend="nccl", init_method=init, rank=rank, world_size=world, device_id=torch.device("cuda", dev_index))
     else:
-        dist.init_process_group(backend="gloo", rank=rank, world_size=world)
+        dist.init_process_group(backend="gloo", init_method=init, rank=rank, world_size=world)
     from monte_carlo_localization_amd import maps
     from monte_carlo_localization_amd.dist import ShardedFilter
     from oracle import oracle as orc

@@ -168,7 +168,8 @@ class OracleShard:
         return self._scalars.copy()
 
     def stage_weights(self, global_max):
-        w = orc.eng_det_exp(self.logw - global_max)
+        with np.errstate(invalid="ignore"):             # E5: logw = -inf -> w = 0, also when global_max = -inf
+            w = orc.eng_det_exp(np.where(self.logw == -np.inf, -np.inf, self.logw - global_max))
         self.w = w
         self.q = np.floor(w * 2.0 ** 36).astype(np.uint64)
         s = self._scalars

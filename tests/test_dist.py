@@ -4,7 +4,6 @@ CPU test: the shard is the oracle-backed stand-in (tests/oracle_shard.py); the s
 bit-identical to the unsharded one (exact integer CDF, global Philox counters, exact log-weight sums).
 GPU test: the same, with the real HIP engine in both ranks (sharing the single GPU of the test box)."""
 import os
-import socket
 import subprocess
 import sys
 
@@ -14,24 +13,24 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def run_world(kind, out_dir, world, n_local, steps, mode, overlap=False, **extra_env):
-    port = free_port()
+    # the ranks meet in a file store in the world's own (fresh) directory, not at a TCP port: a port chosen here and listened on
+    # later in the worker can be taken in between by another process on the host (EADDRINUSE, or ranks that join a foreign store)
+    store = os.path.join(str(out_dir), "rendezvous")
     procs = []
     for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
+        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), MCL_TEST_STORE=store,
                    HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2", **extra_env)
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "dist_worker.py"), kind, str(out_dir),
                                        str(n_local), str(steps), str(mode), "overlap" if overlap else "sync"], env=env))
-    for p in procs:
-        assert p.wait(timeout=600) == 0
+    try:
+        for p in procs:
+            assert p.wait(timeout=600) == 0
+    finally:
+        for p in procs:                 # a rank that failed or hung: its peers wait in a collective, end them too
+            if p.poll() is None:
+                p.kill()
+                p.wait()
     return [np.load(os.path.join(out_dir, f"rank{r}.npz")) for r in range(world)]
 
 
