@@ -66,7 +66,7 @@ class Checker:
         else:
             nrm = np.concatenate([orc.eng_philox_normals(self.seed, self.upd, int(i), 1) for i in sub])
         np.testing.assert_allclose(parts[:, sub], orc.motion_model(self.p[:, idx[sub]], ACTION, nrm), rtol=1e-13, atol=1e-13)
-        pick = np.sort(self.rng.choice(n, min(n, 512), replace=False))
+        pick = np.arange(n) if n <= self.full_motion_max else np.sort(self.rng.choice(n, 512, replace=False))
         lw = e.log_weights()
         if resampled:
             logw, _, _ = orc.eng_log_weights(self.om, np.ascontiguousarray(parts[:, pick]), self.ang, self.oi, self.L)

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, make_engine, tracking_cloud
+from whole_set import native_sample_k53
 
 pytestmark = pytest.mark.gpu
 
@@ -391,7 +392,9 @@ def test_sample_particles_and_mean(orc, engine_mod, sibal1):
     np.testing.assert_allclose(e.particle_mean(), p.mean(axis=1), rtol=1e-12)
     np.testing.assert_allclose(e.get_weights(), w / w.sum(), rtol=1e-13)
     np.testing.assert_allclose(e.expected_pose(), orc.expected_pose(p, w / w.sum()), atol=1e-12)
-    assert e.sample_particles(60).shape == (3, 60)
+    native = e.sample_particles(60)                                   # no uniforms: Philox stream 4, counter (m, updates so far)
+    idx = orc.eng_resample_indices(orc.eng_quantize_weights(w), 0, n_children=60, k53=native_sample_k53(orc, e.cfg.seed, 0, 60))
+    assert np.array_equal(native, p[:, idx])
 
 
 def test_error_codes(orc, engine_mod, sibal1):
