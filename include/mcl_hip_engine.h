@@ -281,6 +281,42 @@ int mcl_host_kld_bins(const double *x, const double *y, const double *th, int64_
                       float resolution, double origin_x, double origin_y, const mcl_kld_config_t *k, int64_t *bins);
 int mcl_host_kld_target(const mcl_kld_config_t *k, int64_t bins, int64_t n_current, int64_t *n_next);
 
+/* ---- pose hypotheses: weighted clusters of the particle set ----------------------------------------------
+ * mcl_pose_clusters groups the particles the engine holds now (mcl_get_particle_count) by their fixed-point weights q (those
+ * mcl_export_state exports) into connected components of occupied pose-space bins, and reports each with its weight, mean and
+ * covariance -- AMCL's cluster statistics.  It runs only when called, on the engine's stream with one host wait, and leaves every
+ * engine state as it was: the next update is the one an engine that never clustered would run.
+ *   Bins: the KLD bin rule above with this config's bin sizes and heading bins.  A particle with q = 0 or in the "outside" bin
+ *     belongs to no cluster (its bin is not occupied).  Two occupied bins touch when |dix| <= 1, |diy| <= 1 and the heading bins
+ *     differ by at most 1 modulo n_theta_bins (the heading wraps, x and y do not).  A cluster is a connected component; its name
+ *     first_bin is its smallest bin index.
+ *   Sums: weight_q = sum q (exact), weight = weight_q / Q with Q = sum q over every particle; mean = (sum q x / W, sum q y / W,
+ *     atan2(sum q sin, sum q cos)) with W = weight_q as a double; cov = sum q d d^T / W about the mean, d = (x - mx, y - my,
+ *     remainder(theta - mth, 2 pi)), row-major.  The fp64 sums have a fixed order: the same state gives the same bits.
+ *   Order: weight_q descending, ties by first_bin ascending.  mcl_get_cluster_labels: the rank of each particle's cluster, or -1.
+ *   Q = 0 gives no clusters.  MCL_ERR_INVALID_ARG for a bin size that is not finite and > 0, n_theta_bins < 1, reserved != 0,
+ *     max_clusters outside [0, 65536] or a grid of more than 2^31 bits; MCL_ERR_NOT_READY without a map or particles (labels:
+ *     before any clustering or after the set changed); MCL_ERR_UNSUPPORTED on an engine with a communicator or in a device group
+ *     (a shard cannot cluster the whole set). */
+typedef struct {
+    double bin_x_m, bin_y_m;                /* default 0.5, 0.5                                                               */
+    int32_t n_theta_bins;                   /* default 36                                                                     */
+    int32_t reserved;                       /* must be 0                                                                      */
+} mcl_cluster_config_t;
+typedef struct {
+    uint64_t weight_q;                      /* sum of the members' q                                                          */
+    double weight;                          /* weight_q / Q                                                                   */
+    int64_t n_particles, n_bins, first_bin;
+    double mean[3];                         /* x, y, heading                                                                  */
+    double cov[9];                          /* row-major, x y heading                                                         */
+} mcl_cluster_t;
+void mcl_default_cluster_config(mcl_cluster_config_t *c);
+/* the max_clusters heaviest into out (out may be NULL when max_clusters == 0); *n_clusters = all of them; totals = {Q, q of the
+ * outside bin, particles in the outside bin}.  n_clusters and totals may be NULL. */
+int mcl_pose_clusters(mcl_engine_t *h, const mcl_cluster_config_t *c, int32_t max_clusters, mcl_cluster_t *out, int64_t *n_clusters,
+                      uint64_t totals[3]);
+int mcl_get_cluster_labels(mcl_engine_t *h, int32_t *labels, int64_t n);   /* of the last mcl_pose_clusters; n == N */
+
 /* ---- host-side precomputation, callable without a device (what mcl_set_map uploads) --------- */
 /* (P+1)^2 doubles, Eigen column-major (index d*(P+1)+r): the restatement of precompute_sensor_model
  * (cpp:233-292) the engine uses.  MCL_ERR_INVALID_ARG for the sensor fields mcl_create refuses (a non-finite or negative

@@ -1268,6 +1268,7 @@ void mcl_destroy(mcl_engine_t *h)
     (void)hipSetDevice(h->cfg.device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->comm) { comm_free(h->comm); h->comm = nullptr; }
+    if (h->clu) { cluster_free(h->clu); h->clu = nullptr; }
     graph_reset(h);
     for (int b = 0; b < 2; ++b) { dfree(h->d_x[b]); dfree(h->d_y[b]); dfree(h->d_th[b]); }
     dfree(h->d_w); dfree(h->d_logw); dfree(h->d_tmp); dfree(h->d_logw_acc); dfree(h->d_carry[0]); dfree(h->d_carry[1]); dfree(h->d_q); dfree(h->d_cdf); dfree(h->d_blocktot); dfree(h->d_bm); dfree(h->d_bm_pop); dfree(h->d_bm_pref);
@@ -1549,6 +1550,7 @@ static int set_particles_impl(mcl_engine_t *h, const double *xyz, const double *
 {
     if (h) graph_reset(h);
     if (!h) return MCL_ERR_INVALID_ARG;
+    h->set_epoch++;
     if (!xyz || !weights || n <= 0 || n > h->cap) return fail(h, MCL_ERR_INVALID_ARG, "bad particle arrays / count");
     if (weight_scale && !(*weight_scale > 0.0)) return fail(h, MCL_ERR_INVALID_ARG, "weight scale must be positive");
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -1592,6 +1594,7 @@ int mcl_set_particles_shard(mcl_engine_t *h, const double *xyz, const double *we
 static int finish_init(mcl_engine *h, int64_t n, int64_t n_total)
 {
     graph_reset(h);
+    h->set_epoch++;
     h->N = n;
     hipLaunchKernelGGL(mcl::k_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d_w, n, 1.0 / (double)n_total);
     HIPCHK(h, hipGetLastError());
@@ -1799,6 +1802,7 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
                      const double *uniforms, bool resample_and_move, int obs_stride = 1)
 {
     if (!h) return MCL_ERR_INVALID_ARG;
+    h->set_epoch++;                         // (the labels of a clustering are void from here on)
     if (!ready(h, true)) return fail(h, MCL_ERR_NOT_READY, "map, beam angles and particles must be set first");
     if (!obs || n_beams != h->B || (resample_and_move && !action)) return fail(h, MCL_ERR_INVALID_ARG, "bad action/observation");
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -2528,6 +2532,7 @@ static int stage_resample_launch(mcl_engine_t *h, const ParentSource &src, const
                                  int64_t child_first, int64_t n_children_total, const double action[3])
 {
     if (!h) return MCL_ERR_INVALID_ARG;
+    h->set_epoch++;                         // (the labels of a clustering are void from here on)
     if (!ready(h, true)) return fail(h, MCL_ERR_NOT_READY, "map, beam angles and particles must be set first");
     const bool have_parents = src.records || src.n_per_rank > 0 || (src.px && src.py && src.pth) || src.idx_only_out || src.gcdf;
     if (!have_parents || (!d_cdf && !src.idx_in && !src.gcdf && !src.keep) || (!action && !src.idx_only_out) || n_parents <= 0 ||
@@ -2824,6 +2829,7 @@ int mcl_set_reserved_cus(mcl_engine_t *h, int32_t n_cus)
 static int stage_weights_launch(mcl_engine_t *h, double global_max_logw, const double *d_global_max = nullptr)
 {
     if (!h) return MCL_ERR_INVALID_ARG;
+    h->set_epoch++;                         // (the labels of a clustering are void from here on)
     if (!h->have_logw && !d_global_max) return MCL_ERR_NOT_READY;
     if (h->cfg.weight_mode != MCL_WEIGHT_LOG)
         return fail(h, MCL_ERR_UNSUPPORTED, "the staged (sharded) flow needs weight_mode LOG");
@@ -3013,6 +3019,8 @@ float elapsed(hipEvent_t a, hipEvent_t b) { return ::elapsed(a, b); }
 void graph_reset(mcl_engine *h) { ::graph_reset(h); }
 int scan_weights(mcl_engine *h, const uint64_t *d_q, uint64_t *d_cdf, int64_t n, uint64_t offset, uint64_t *d_total) { return ::scan_weights(h, d_q, d_cdf, n, offset, d_total); }
 void unpack_result(mcl_engine *h) { ::unpack_result(h); }
+bool kld_grid(const mcl_kld_config_t *k, uint32_t W, uint32_t H, float res, int64_t &nx, int64_t &ny, uint64_t &bits) { return ::kld_grid(k, W, H, res, nx, ny, bits); }
+mcl::KldArgs kld_args_of(const mcl_kld_config_t *k, int64_t nx, int64_t ny, double ox, double oy) { return ::kld_args_of(k, nx, ny, ox, oy); }
 int layout_adopt(mcl_engine *h, int64_t n) { return ::layout_adopt(h, n); }
 int set_particles_impl(mcl_engine_t *h, const double *xyz, const double *weights, int64_t n, const double *weight_scale) { return ::set_particles_impl(h, xyz, weights, n, weight_scale); }
 int stage_resample_launch(mcl_engine_t *h, const ParentSource &src, const uint64_t *d_cdf, int64_t n_parents, uint64_t q_total,

@@ -3,6 +3,7 @@
 //   mcl_engine.hip   the engine: map / beams / particles, the update and its stages, every kernel
 //   mcl_comm.hip     mcl_comm_*: one process per GPU, the collectives of an update over RCCL on the engine's stream
 //   mcl_group.hip    mcl_group_*: several GPUs behind one handle, driven by one process (peer copies)
+//   mcl_cluster.hip  mcl_pose_clusters: the pose hypotheses of the particle set (its own kernels, called outside the update)
 // Only mcl_engine.hip includes the kernels (mcl_kernels.h); the other two reach the few kernels they launch through the
 // launch_* functions below.
 #pragma once
@@ -31,6 +32,8 @@ constexpr int kResultStamp = 32;             // h_result word a small update's l
 struct mcl_comm;
 void comm_free(struct mcl_comm *c);        // mcl_comm.hip
 void comm_forget(struct mcl_comm *c);      // mcl_comm.hip: the particle set changed, what the exchange knew is void
+struct mcl_cluster;
+void cluster_free(struct mcl_cluster *c);  // mcl_cluster.hip
 struct mcl_engine {
     mcl_config_t cfg{};
     int num_cu = 256;
@@ -252,6 +255,10 @@ struct mcl_engine {
     unsigned int *d_kld_cnt = nullptr;  // 2 counters
     size_t kld_bm_words = 0, kld_list_cap = 0;
     int kld_parity = 0;
+    // pose clustering (mcl_pose_clusters): its own buffers, allocated on the first call; set_epoch counts the
+    // changes of the particle set or its weights (the labels of a clustering are valid while it is unchanged)
+    struct mcl_cluster *clu = nullptr;
+    unsigned long long set_epoch = 0;
 };
 
 #define HIPCHK(h, call)                                                                          \
@@ -295,6 +302,8 @@ float elapsed(hipEvent_t a, hipEvent_t b);
 void graph_reset(mcl_engine *h);
 int scan_weights(mcl_engine *h, const uint64_t *d_q, uint64_t *d_cdf, int64_t n, uint64_t offset, uint64_t *d_total);
 void unpack_result(mcl_engine *h);
+bool kld_grid(const mcl_kld_config_t *k, uint32_t W, uint32_t H, float res, int64_t &nx, int64_t &ny, uint64_t &bits);
+mcl::KldArgs kld_args_of(const mcl_kld_config_t *k, int64_t nx, int64_t ny, double ox, double oy);
 int layout_adopt(mcl_engine *h, int64_t n);
 int set_particles_impl(mcl_engine_t *h, const double *xyz, const double *weights, int64_t n, const double *weight_scale);
 int stage_resample_launch(mcl_engine_t *h, const ParentSource &src, const uint64_t *d_cdf, int64_t n_parents, uint64_t q_total,

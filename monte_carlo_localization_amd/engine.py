@@ -44,6 +44,7 @@ EXPORTS = [
     "mcl_comm_available", "mcl_comm_unique_id", "mcl_comm_create", "mcl_comm_destroy", "mcl_comm_update", "mcl_comm_stats", "mcl_comm_set_lists", "mcl_comm_get_vector", "mcl_comm_last_exchange", "mcl_comm_selftest",
     "mcl_host_sweep_global_layout", "mcl_get_ray_kernel_variant",
     "mcl_default_kld_config", "mcl_set_kld", "mcl_get_particle_count", "mcl_get_kld_state", "mcl_host_kld_bins", "mcl_host_kld_target",
+    "mcl_default_cluster_config", "mcl_pose_clusters", "mcl_get_cluster_labels",
 ]
 
 
@@ -66,6 +67,25 @@ class KldConfig(C.Structure):
         ("bin_x_m", C.c_double), ("bin_y_m", C.c_double), ("n_theta_bins", C.c_int32), ("round_to", C.c_int32),
         ("shrink_permille", C.c_int32), ("reserved", C.c_int32),
     ]
+
+
+class ClusterConfig(C.Structure):
+    """mcl_cluster_config_t: the bins of the pose clustering (Engine.pose_clusters)."""
+    _fields_ = [("bin_x_m", C.c_double), ("bin_y_m", C.c_double), ("n_theta_bins", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Cluster(C.Structure):
+    """mcl_cluster_t: one pose hypothesis."""
+    _fields_ = [
+        ("weight_q", C.c_uint64), ("weight", C.c_double), ("n_particles", C.c_int64), ("n_bins", C.c_int64),
+        ("first_bin", C.c_int64), ("mean", C.c_double * 3), ("cov", C.c_double * 9),
+    ]
+
+
+# the numpy view of an array of mcl_cluster_t (Engine.pose_clusters)
+CLUSTER_DTYPE = np.dtype([("weight_q", np.uint64), ("weight", np.float64), ("n_particles", np.int64), ("n_bins", np.int64),
+                          ("first_bin", np.int64), ("mean", np.float64, (3,)), ("cov", np.float64, (3, 3))])
+assert CLUSTER_DTYPE.itemsize == C.sizeof(Cluster)
 
 
 class EngineError(RuntimeError):
@@ -134,6 +154,11 @@ def load_library(legacy=False):
         lib.mcl_host_kld_bins.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint32, C.c_uint32, C.c_float,
                                           C.c_double, C.c_double, C.POINTER(KldConfig), C.POINTER(C.c_int64)]
         lib.mcl_host_kld_target.argtypes = [C.POINTER(KldConfig), C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
+        lib.mcl_default_cluster_config.argtypes = [C.POINTER(ClusterConfig)]
+        lib.mcl_default_cluster_config.restype = None
+        lib.mcl_pose_clusters.argtypes = [C.c_void_p, C.POINTER(ClusterConfig), C.c_int32, C.c_void_p, C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_uint64)]
+        lib.mcl_get_cluster_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         _libs[path] = _lib = lib
     return _lib
 
@@ -157,6 +182,17 @@ def default_kld_config(**over) -> KldConfig:
             raise AttributeError(name)
         setattr(k, name, v)
     return k
+
+
+def default_cluster_config(**over) -> ClusterConfig:
+    """mcl_default_cluster_config, with fields overridden by keyword."""
+    c = ClusterConfig()
+    load_library().mcl_default_cluster_config(C.byref(c))
+    for name, v in over.items():
+        if name not in dict(ClusterConfig._fields_):
+            raise AttributeError(name)
+        setattr(c, name, v)
+    return c
 
 
 def host_kld_bins(x, y, th, width, height, resolution, origin_x, origin_y, kld: KldConfig) -> int:
@@ -384,6 +420,24 @@ class Engine:
         n = C.c_int64()
         self._chk(self.lib.mcl_get_particle_count(self._h, C.byref(n)), "mcl_get_particle_count")
         return n.value
+
+    def pose_clusters(self, max_clusters=16, **cfg_fields):
+        """The pose hypotheses of the particle set (mcl_pose_clusters): a structured array (CLUSTER_DTYPE) of the
+        max_clusters heaviest clusters, heaviest first, and {n_clusters, q_total, q_outside, n_outside}.  `cfg_fields` override
+        mcl_default_cluster_config (bin_x_m, bin_y_m, n_theta_bins)."""
+        cfg = default_cluster_config(**cfg_fields)
+        out = np.zeros(int(max_clusters), CLUSTER_DTYPE)
+        n = C.c_int64()
+        tot = (C.c_uint64 * 3)()
+        self._chk(self.lib.mcl_pose_clusters(self._h, C.byref(cfg), C.c_int32(int(max_clusters)), _p(out) if out.size else None,
+                                             C.byref(n), tot), "mcl_pose_clusters")
+        return out[:min(n.value, out.size)], dict(n_clusters=n.value, q_total=int(tot[0]), q_outside=int(tot[1]), n_outside=int(tot[2]))
+
+    def cluster_labels(self):
+        """Per particle, the rank of its cluster in the last pose_clusters, or -1 (no cluster)."""
+        out = np.empty(self.particle_count(), np.int32)
+        self._chk(self.lib.mcl_get_cluster_labels(self._h, _p(out), C.c_int64(out.size)), "mcl_get_cluster_labels")
+        return out
 
     def sensor_update(self, obs):
         o = _c(obs, np.float32)
