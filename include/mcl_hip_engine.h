@@ -317,6 +317,48 @@ int mcl_pose_clusters(mcl_engine_t *h, const mcl_cluster_config_t *c, int32_t ma
                       uint64_t totals[3]);
 int mcl_get_cluster_labels(mcl_engine_t *h, int32_t *labels, int64_t n);   /* of the last mcl_pose_clusters; n == N */
 
+/* ---- recovery by random-particle injection (augmented MCL, Probabilistic Robotics Table 8.3; AMCL's recovery_alpha_slow /
+ *      recovery_alpha_fast) -------------------------------------------------------------------------------
+ * Off by default.  With it on, a resampling mcl_update replaces each child, with probability p, by a pose drawn uniformly from
+ * the map's free cells, where p follows from two running averages of the update likelihood.
+ *   Likelihood of an update (every mcl_update, kept or resampled, and mcl_sensor_update): l = m + log(sum_w) - log(D), with
+ *     m = SCALARS[0] (max log-weight), sum_w = SCALARS[1], D = N for a resampled update and mcl_sensor_update, D = the previous
+ *     update's sum_w for an update that kept its particles (resample_neff_permille): log sum over the prior normalised weights
+ *     of p_i.  m = -inf gives l = -inf.  per_beam = 1 (the default) divides l by the engine's beam count.
+ *   Averages: S (slow) and F (fast) are each unset (NaN at the ABI) or a value in [-inf, +inf).  Fold: S <- l if unset, else
+ *     logaddexp(S + log1p(-alpha_slow), l + log(alpha_slow)); the same for F with alpha_fast.  logaddexp(a, b) = hi +
+ *     log1p(exp(lo - hi)), -inf when both are -inf.  A NaN l leaves both unchanged.  Host double, mcl_host_recovery_step.
+ *   Injection: p = 0 when S or F is unset or S = -inf, else clamp(1 - exp(F - S), 0, 1); threshold T = floor(p * 2^53).  A
+ *     resampling update with T > 0 unsets S and F before folding in its own l; an update that keeps its particles injects
+ *     nothing and resets nothing.
+ *   Per child g of update u (Philox as for the other draws): stream 8 gives coin = bits53(v0, v1), injected iff coin < T, and
+ *     pick = bits53(v2, v3): cell = free[umulhi(pick << 11, n_free)], x = col * res + ox, y = row * res + oy (mcl_init_global's
+ *     rule); stream 9 gives theta = (bits53(v0, v1) * 2^-53 - 0.5) * 2 pi.  An injected child skips the parent search and the
+ *     motion model, and its resample index is -1.  Every other child is bit-identical to the child of the same update with
+ *     recovery off.  With KLD on the injected pose is the child's counted sample.
+ *   mcl_set_particles*, mcl_init_*, mcl_set_map, mcl_set_beam_angles and mcl_set_recovery unset S and F.
+ *   MCL_ERR_INVALID_ARG unless 0 < alpha_slow < alpha_fast <= 1 (finite), per_beam is 0 or 1 and reserved is 0.
+ *   MCL_ERR_UNSUPPORTED for weight_mode PRODUCT, an engine with a communicator or in a device group, mcl_comm_create while it is
+ *     on and every mcl_stage_* call while it is on (single engine only).  MCL_ERR_NOT_READY for an update with T > 0 on a map
+ *     without free cells (before anything is launched). */
+typedef struct {
+    double alpha_slow, alpha_fast;          /* default 0.001, 0.1                                                             */
+    int32_t per_beam;                       /* 1 (default): l per beam; 0: AMCL's raw form                                    */
+    int32_t reserved;                       /* must be 0                                                                      */
+} mcl_recovery_config_t;
+void mcl_default_recovery_config(mcl_recovery_config_t *c);
+int mcl_set_recovery(mcl_engine_t *h, const mcl_recovery_config_t *c);    /* NULL = off (the default)                       */
+/* state = {S, F, p of the next update}; *injected_last = injected children of the last update (0 after one that injected
+ * nothing).  Either pointer may be NULL. */
+int mcl_get_recovery_state(mcl_engine_t *h, double state[3], int64_t *injected_last);
+/* sets S, F (NaN = unset; +inf and recovery off are refused): to restore a saved state, or to force p */
+int mcl_set_recovery_state(mcl_engine_t *h, const double state[2]);
+/* the rules above on the host, without a device: folds the likelihood of one update into in = {S, F} (reset: unset them
+ * first) and gives out = {S, F} and the p of the next update.  MCL_ERR_INVALID_ARG for a refused config, a null pointer,
+ * denom that is not > 0 or n_beams < 1. */
+int mcl_host_recovery_step(const mcl_recovery_config_t *c, const double in[2], int32_t reset, double max_logw, double sum_w,
+                           double denom, int32_t n_beams, double out[2], double *p_next);
+
 /* ---- host-side precomputation, callable without a device (what mcl_set_map uploads) --------- */
 /* (P+1)^2 doubles, Eigen column-major (index d*(P+1)+r): the restatement of precompute_sensor_model
  * (cpp:233-292) the engine uses.  MCL_ERR_INVALID_ARG for the sensor fields mcl_create refuses (a non-finite or negative

@@ -1035,6 +1035,59 @@ int kld_refuse_stage(mcl_engine *h)
     return fail(h, MCL_ERR_UNSUPPORTED, "KLD sampling (mcl_set_kld) is single-engine only: the mcl_stage_* calls are refused while it is on");
 }
 
+// ---- recovery by random-particle injection (mcl_set_recovery): host double throughout
+const char *recov_invalid(const mcl_recovery_config_t *c)
+{
+    if (!(std::isfinite(c->alpha_slow) && std::isfinite(c->alpha_fast) && c->alpha_slow > 0.0 && c->alpha_slow < c->alpha_fast &&
+          c->alpha_fast <= 1.0))
+        return "recovery: need 0 < alpha_slow < alpha_fast <= 1";
+    if (c->per_beam != 0 && c->per_beam != 1) return "recovery: per_beam must be 0 or 1";
+    if (c->reserved != 0) return "recovery: reserved must be 0";
+    return nullptr;
+}
+
+double recov_logaddexp(double a, double b)
+{
+    const double hi = a > b ? a : b, lo = a > b ? b : a;
+    if (hi == -INFINITY) return -INFINITY;
+    return hi + std::log1p(std::exp(lo - hi));
+}
+
+// l of one update: m + log(sum_w) - log(denom), -inf for m = -inf, divided by the beam count with per_beam
+double recov_likelihood(const mcl_recovery_config_t &c, double max_logw, double sum_w, double denom, int n_beams)
+{
+    double l = max_logw == -INFINITY ? -INFINITY : max_logw + std::log(sum_w) - std::log(denom);
+    if (c.per_beam) l = l / (double)n_beams;
+    return l;
+}
+
+// folds l into (S, F) (NaN: unset); a NaN l changes nothing
+void recov_fold(const mcl_recovery_config_t &c, double &S, double &F, double l)
+{
+    if (std::isnan(l)) return;
+    S = std::isnan(S) ? l : recov_logaddexp(S + std::log1p(-c.alpha_slow), l + std::log(c.alpha_slow));
+    F = std::isnan(F) ? l : recov_logaddexp(F + std::log1p(-c.alpha_fast), l + std::log(c.alpha_fast));
+}
+
+double recov_p(double S, double F)
+{
+    if (std::isnan(S) || std::isnan(F) || S == -INFINITY) return 0.0;
+    const double p = 1.0 - std::exp(F - S);
+    return p > 0.0 ? (p < 1.0 ? p : 1.0) : 0.0;
+}
+
+uint64_t recov_threshold(double p) { return (uint64_t)(p * 9007199254740992.0); }     // floor(p * 2^53), p in [0, 1]
+
+void recov_unset(mcl_engine *h)
+{
+    h->recov_S = h->recov_F = NAN;
+}
+
+int recov_refuse_stage(mcl_engine *h)
+{
+    return fail(h, MCL_ERR_UNSUPPORTED, "recovery (mcl_set_recovery) is single-engine only: the mcl_stage_* calls are refused while it is on");
+}
+
 }  // namespace
 
 extern "C" {
@@ -1273,7 +1326,7 @@ void mcl_destroy(mcl_engine_t *h)
     for (int b = 0; b < 2; ++b) { dfree(h->d_x[b]); dfree(h->d_y[b]); dfree(h->d_th[b]); }
     dfree(h->d_w); dfree(h->d_logw); dfree(h->d_tmp); dfree(h->d_logw_acc); dfree(h->d_carry[0]); dfree(h->d_carry[1]); dfree(h->d_q); dfree(h->d_cdf); dfree(h->d_blocktot); dfree(h->d_bm); dfree(h->d_bm_pop); dfree(h->d_bm_pref);
     dfree(h->d_gcdf); dfree(h->d_gtop);
-    dfree(h->d_kld_bm); dfree(h->d_kld_list); dfree(h->d_kld_cnt);
+    dfree(h->d_kld_bm); dfree(h->d_kld_list); dfree(h->d_kld_cnt); dfree(h->d_recov_cnt);
     dfree(h->d_blockcnt); dfree(h->d_ccdf); dfree(h->d_ctop); dfree(h->d_cidx); dfree(h->d_crec);
     dfree(h->d_idx); dfree(h->d_steps); dfree(h->d_part); dfree(h->d_maxpart); dfree(h->d_result); if (h->h_result) { (void)hipHostFree(h->h_result); h->h_result = nullptr; } dfree(h->d_inject); dfree(h->d_pc); dfree(h->d_qr); dfree(h->d_far); dfree(h->d_far_list); dfree(h->d_far_sorted); dfree(h->d_far_cnt); dfree(h->d_pcs); dfree(h->d_ths); dfree(h->d_distw); dfree(h->d_distg); dfree(h->d_leaders); dfree(h->d_pack[0]); dfree(h->d_pack[1]); dfree(h->d_perm); dfree(h->d_skey); dfree(h->d_srank); dfree(h->d_skey2); dfree(h->d_sval2); dfree(h->d_sort_tmp); dfree(h->d_hist); dfree(h->d_histpart); dfree(h->d_tile_used); dfree(h->d_bbox); dfree(h->d_cut_start); dfree(h->d_cut_end); dfree(h->d_tilemap); dfree(h->d_tilemark); dfree(h->d_slice_mean); dfree(h->d_fix_list); dfree(h->d_fix_count); dfree(h->d_exact_list);
     dfree(h->d_grid); dfree(h->d_dist); dfree(h->d_dist4); dfree(h->d_L); dfree(h->d_table);
@@ -1304,6 +1357,7 @@ int mcl_set_map(mcl_engine_t *h, const int8_t *data, uint32_t width, uint32_t he
         return fail(h, MCL_ERR_INVALID_ARG, "KLD: the bin grid over this map exceeds 2^31 bits");
     graph_reset(h);
     if (!(resolution > 0.0f)) return fail(h, MCL_ERR_INVALID_ARG, "invalid map resolution");   // cpp:236-240
+    recov_unset(h);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const double res = (double)resolution;                    // cpp:191
     const int P = (int)(h->cfg.max_range_m / res);            // cpp:195
@@ -1451,6 +1505,7 @@ int mcl_set_beam_angles(mcl_engine_t *h, const float *angles, int32_t n_beams)
     if (h) graph_reset(h);
     if (!h) return MCL_ERR_INVALID_ARG;
     if (!angles || n_beams <= 0 || n_beams > 65536) return fail(h, MCL_ERR_INVALID_ARG, "bad beam angles");
+    recov_unset(h);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     h->B = 0;                            // until every buffer below exists again (ready() tests B > 0)
     h->bpad = (n_beams + 63) & ~63;
@@ -1578,6 +1633,7 @@ static int set_particles_impl(mcl_engine_t *h, const double *xyz, const double *
     comm_forget(h->comm);                   // a sharded set: the other shards' lists are unknown again
     h->stage_kept = false;
     kld_reset(h);
+    recov_unset(h);
     return MCL_OK;
 }
 
@@ -1612,6 +1668,7 @@ static int finish_init(mcl_engine *h, int64_t n, int64_t n_total)
     h->stage_kept = false;
     h->init_idx++;
     kld_reset(h);
+    recov_unset(h);
     return MCL_OK;
 }
 
@@ -1716,7 +1773,7 @@ int mcl_particle_mean(mcl_engine_t *h, double out[3])
 // the per-particle constants come out of it (k_rays_skip: one launch less per small update; k_rays_cell / k_rays_sweep: also the
 // per-particle scratch their stage wants zeroed, a pass over the children less), and from the second update of a configuration on
 // the (key, index) pairs of the ordering and the few words launch_rays would clear.
-static void resample_ray_extras(mcl_engine *h, int64_t n, mcl::ResampleArgs &a)
+static void resample_ray_extras(mcl_engine *h, int64_t n, mcl::ResampleArgs &a, bool fresh_children = false)
 {
     const int rmode = choose_ray_mode(h, n, false);
     if (!(rmode == 2 || rmode >= 4)) return;
@@ -1728,7 +1785,8 @@ static void resample_ray_extras(mcl_engine *h, int64_t n, mcl::ResampleArgs &a)
     // Radix ordering: this kernel then writes the (key, index) pairs too and the sort starts right after it.
     const int ntx_abs = ((h->Wp * mcl::kSortSub - 1) >> 5) + 1, nty_abs = ((h->Hp * mcl::kSortSub - 1) >> 5) + 1;
     const bool tiles_ok = (int64_t)ntx_abs * nty_abs <= mcl::kSortMaxTiles;
-    if (rmode >= 4 && h->layout_valid && h->layout_n == n && !h->env_no_stale_layout) {
+    // (not for children injected anywhere on the map: fresh_children, an update of recovery injection -- DESIGN.md §4.9)
+    if (rmode >= 4 && h->layout_valid && h->layout_n == n && !h->env_no_stale_layout && !fresh_children) {
         h->layout_stale_used = true;
         const bool radix = h->env_sort_radix >= 0 ? h->env_sort_radix != 0 : n >= 3000000;
         if (radix && h->d_skey2) {
@@ -1798,6 +1856,15 @@ static void kld_decide(mcl_engine *h, bool kept)
     if (!kept) h->kld_n_next = kld_target(&h->kld, h->kld_bins_last, h->N);
 }
 
+// after an update that formed weights, with recovery on: the averages take in its likelihood (an injecting update unsets them first)
+static void recov_after(mcl_engine *h, bool injected, bool kept, double prev_sum_w, int64_t n)
+{
+    if (!h->recov_on) return;
+    if (injected) recov_unset(h);
+    const double l = recov_likelihood(h->recov, h->h_scalars[0], h->h_scalars[1], kept ? prev_sum_w : (double)n, h->B);
+    recov_fold(h->recov, h->recov_S, h->recov_F, l);
+}
+
 static int do_update(mcl_engine_t *h, const double action[3], const float *obs, int32_t n_beams, const double *normals,
                      const double *uniforms, bool resample_and_move, int obs_stride = 1)
 {
@@ -1812,6 +1879,21 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
     const bool kld = resample_and_move && h->kld_on;
     int64_t n = kld ? h->kld_n_next : n_par;     // children: every stage after the resampling kernel runs on them
     if (kld && (n < 1 || n > h->cap)) return fail(h, MCL_ERR_INVALID_ARG, "KLD: particle count out of range");
+    // adaptive resampling (off by default): keep the particles when the previous update left an effective sample
+    // size (sum w)^2 / sum w^2 of at least r * N; their weights then multiply, i.e. the log-weights add
+    // (with KLD on only while the next size is the current one: a kept set cannot change its size)
+    bool keep = false;
+    if (resample_and_move && h->cfg.resample_neff_permille > 0 && h->carry_valid && !uniforms && n == n_par) {
+        const double sw = h->h_scalars[1], sww = h->h_scalars[7];
+        keep = sww > 0.0 && sw * sw >= ((double)h->cfg.resample_neff_permille / 1000.0) * (double)n * sww;
+    }
+    if (h->cfg.resample_neff_permille > 0 && h->cfg.weight_mode == MCL_WEIGHT_PRODUCT)
+        return fail(h, MCL_ERR_UNSUPPORTED, "resample_neff_permille needs weight_mode LOG");
+    // recovery (mcl_set_recovery, off by default): a resampling update whose threshold is > 0 runs the injecting kernel
+    const double prev_sum_w = h->h_scalars[1];
+    const uint64_t rec_thr = (h->recov_on && resample_and_move && !keep) ? recov_threshold(recov_p(h->recov_S, h->recov_F)) : 0;
+    const bool rec = rec_thr > 0;
+    if (rec && h->n_free == 0) return fail(h, MCL_ERR_NOT_READY, "recovery: the map has no free cell to inject particles into");
     const double *d_norm = nullptr, *d_uni = nullptr;
     if (resample_and_move) {
         if (normals) {
@@ -1823,16 +1905,6 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
             d_uni = h->d_inject + (size_t)3 * h->cap;
         }
     }
-    // adaptive resampling (off by default): keep the particles when the previous update left an effective sample
-    // size (sum w)^2 / sum w^2 of at least r * N; their weights then multiply, i.e. the log-weights add
-    // (with KLD on only while the next size is the current one: a kept set cannot change its size)
-    bool keep = false;
-    if (resample_and_move && h->cfg.resample_neff_permille > 0 && h->carry_valid && !uniforms && n == n_par) {
-        const double sw = h->h_scalars[1], sww = h->h_scalars[7];
-        keep = sww > 0.0 && sw * sw >= ((double)h->cfg.resample_neff_permille / 1000.0) * (double)n * sww;
-    }
-    if (h->cfg.resample_neff_permille > 0 && h->cfg.weight_mode == MCL_WEIGHT_PRODUCT)
-        return fail(h, MCL_ERR_UNSUPPORTED, "resample_neff_permille needs weight_mode LOG");
     if (!resample_and_move) HIPCHK(h, hipMemsetAsync(h->d_counters, 0, 4 * sizeof(unsigned long long), h->stream));   // else: the resampling kernel
     if (n != n_par) {
         // another size: nothing made for the old one is reused (captured graphs, the warm small-update paths, the previous
@@ -1840,6 +1912,8 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
         graph_reset(h);
         h->far_fresh = true;
     }
+    if (rec) h->far_fresh = true;          // injected children anywhere on the map: the ray stage plans as for a set from outside
+    h->recov_cnt_slot = -1; h->recov_injected = 0;
     h->pc_ready = false;
     h->layout_stale_used = false; h->keys_done = false;      // (set below when this update orders by the previous update's layout)
     // A small update (k_rays_skip, the whole tail in one workgroup) is three launches and no copy: resampling + motion +
@@ -1899,11 +1973,19 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
             stage_observation(h, obs, obs_stride);
             a.obs_src = h->h_obs; a.obs_idx_out = h->d_obs_idx; a.obs_B = h->B; a.obs_P = h->P; a.res = h->res;
         }
-        resample_ray_extras(h, n, a);
+        resample_ray_extras(h, n, a, rec);
         size_t cdf_lds = 0;
         if (!a.tile_excl && a.do_resample && n_par <= mcl::kTinyTailMax) { a.cdf_lds_entries = (int)n_par; cdf_lds = (size_t)n_par * sizeof(uint64_t); }
         h->ev_resample_bound = false;
         const dim3 grid((unsigned)((n + 255) / 256));
+        mcl::RecArgs rec_args{};
+        if (rec) {
+            rec_args.thr = rec_thr; rec_args.free_cells = h->d_free; rec_args.n_free = h->n_free; rec_args.W = h->W;
+            rec_args.res = h->res; rec_args.ox = h->ox; rec_args.oy = h->oy;
+            rec_args.count = h->d_recov_cnt + h->recov_parity; rec_args.count_next = h->d_recov_cnt + (h->recov_parity ^ 1);
+            h->recov_cnt_slot = h->recov_parity; h->recov_injected = -1;
+            h->recov_parity ^= 1;
+        }
         if (kld) {
             // the bins of the drawn parents are marked by the resampling kernel; the words it set are cleared and the count
             // lands in word 17 of the result block -- by the one-workgroup tail of a small update, else by one launch right here
@@ -1912,7 +1994,12 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
             kld_cur.count = h->d_kld_cnt + h->kld_parity; kld_cur.count_next = h->d_kld_cnt + (h->kld_parity ^ 1);
             kld_cur.result = h->d_result + 17;
             h->kld_parity ^= 1;
-            if (!tiny && !h->capturing) {
+            if (rec && !tiny && !h->capturing) {
+                hipExtLaunchKernelGGL(mcl::k_resample_motion_kld_rec, grid, dim3(256), cdf_lds, h->stream, nullptr, h->ev[EV_RESAMPLE], 0, a, kld_cur, rec_args);
+                h->ev_resample_bound = true;
+            } else if (rec) {
+                hipLaunchKernelGGL(mcl::k_resample_motion_kld_rec, grid, dim3(256), cdf_lds, h->stream, a, kld_cur, rec_args);
+            } else if (!tiny && !h->capturing) {
                 hipExtLaunchKernelGGL(mcl::k_resample_motion_kld, grid, dim3(256), cdf_lds, h->stream, nullptr, h->ev[EV_RESAMPLE], 0, a, kld_cur);
                 h->ev_resample_bound = true;
             } else {
@@ -1922,6 +2009,11 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
                 const int64_t most = std::min<int64_t>(n, (int64_t)h->kld_bits);
                 hipLaunchKernelGGL(mcl::k_kld_clear, dim3((unsigned)std::min<int64_t>((most + 255) / 256, 1024)), dim3(256), 0, h->stream, kld_cur);
             }
+        } else if (rec && !tiny && !h->capturing) {
+            hipExtLaunchKernelGGL(mcl::k_resample_motion_rec, grid, dim3(256), cdf_lds, h->stream, nullptr, h->ev[EV_RESAMPLE], 0, a, rec_args);
+            h->ev_resample_bound = true;
+        } else if (rec) {
+            hipLaunchKernelGGL(mcl::k_resample_motion_rec, grid, dim3(256), cdf_lds, h->stream, a, rec_args);
         } else if (!tiny && !h->capturing) {
             hipExtLaunchKernelGGL(mcl::k_resample_motion, grid, dim3(256), cdf_lds, h->stream, nullptr, h->ev[EV_RESAMPLE], 0, a);
             h->ev_resample_bound = true;
@@ -1971,6 +2063,7 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
         if (!seen) HIPCHK(h, hipStreamSynchronize(h->stream));
         unpack_result(h);
         if (kld) kld_decide(h, keep);
+        recov_after(h, rec, keep, prev_sum_w, n);
         h->have_logw = true;
         h->have_steps = h->cfg.keep_ray_steps != 0;
         h->update_idx++;
@@ -2031,6 +2124,7 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
         h->compact_pending = h->d_ccdf != nullptr && !h->env_no_compact && n > mcl::kTinyTailMax;   // the captured scan wrote a list
         unpack_result(h);
         if (kld) kld_decide(h, keep);
+        recov_after(h, rec, keep, prev_sum_w, n);
         h->carry_pending = false;
         h->have_logw = true;
         h->have_steps = h->cfg.keep_ray_steps != 0;
@@ -2093,6 +2187,7 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
     if (h->carry_pending) { h->carry_idx ^= 1; h->carry_valid = true; h->carry_pending = false; }   // this update's logw - max
     { const int rc_l = layout_adopt(h, n); if (rc_l) return rc_l; }
     if (kld) kld_decide(h, keep);
+    recov_after(h, rec, keep, prev_sum_w, n);
     h->graph_warm = true;                  // every buffer this configuration needs exists now
     h->have_logw = true;
     h->have_steps = h->cfg.keep_ray_steps != 0;
@@ -2338,6 +2433,79 @@ int mcl_host_kld_target(const mcl_kld_config_t *k, int64_t bins, int64_t n_curre
     return MCL_OK;
 }
 
+void mcl_default_recovery_config(mcl_recovery_config_t *c)
+{
+    if (!c) return;
+    *c = mcl_recovery_config_t{};
+    c->alpha_slow = 0.001; c->alpha_fast = 0.1; c->per_beam = 1;
+}
+
+int mcl_set_recovery(mcl_engine_t *h, const mcl_recovery_config_t *c)
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    if (!c) {
+        h->recov_on = false;
+        recov_unset(h);
+        h->recov_cnt_slot = -1; h->recov_injected = 0;
+        return MCL_OK;
+    }
+    if (h->comm || h->in_group)
+        return fail(h, MCL_ERR_UNSUPPORTED, "recovery is single-engine only: this engine has a communicator or belongs to a device group");
+    if (h->cfg.weight_mode != MCL_WEIGHT_LOG) return fail(h, MCL_ERR_UNSUPPORTED, "recovery needs weight_mode LOG");
+    if (const char *why = recov_invalid(c)) return fail(h, MCL_ERR_INVALID_ARG, why);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (!h->d_recov_cnt) {
+        HIPCHK(h, hipMalloc(&h->d_recov_cnt, 2 * sizeof(unsigned int)));
+        HIPCHK(h, hipMemsetAsync(h->d_recov_cnt, 0, 2 * sizeof(unsigned int), h->stream));
+    }
+    h->recov = *c;
+    h->recov_on = true;
+    recov_unset(h);
+    h->recov_cnt_slot = -1; h->recov_injected = 0;
+    return MCL_OK;
+}
+
+int mcl_get_recovery_state(mcl_engine_t *h, double state[3], int64_t *injected_last)
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    if (state) {
+        state[0] = h->recov_S; state[1] = h->recov_F;
+        state[2] = h->recov_on ? recov_p(h->recov_S, h->recov_F) : 0.0;
+    }
+    if (injected_last) {
+        if (h->recov_cnt_slot >= 0 && h->recov_injected < 0) {
+            // the count of the last injecting update, read once (the update has synchronised with its kernels already)
+            HIPCHK(h, hipSetDevice(h->cfg.device));
+            unsigned int c = 0;
+            HIPCHK(h, hipMemcpyAsync(&c, h->d_recov_cnt + h->recov_cnt_slot, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            h->recov_injected = (int64_t)c;
+        }
+        *injected_last = h->recov_cnt_slot >= 0 ? h->recov_injected : 0;
+    }
+    return MCL_OK;
+}
+
+int mcl_set_recovery_state(mcl_engine_t *h, const double state[2])
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    if (!state || state[0] == INFINITY || state[1] == INFINITY) return fail(h, MCL_ERR_INVALID_ARG, "recovery: S and F must be NaN or below +inf");
+    if (!h->recov_on) return fail(h, MCL_ERR_NOT_READY, "recovery is off (mcl_set_recovery)");
+    h->recov_S = state[0]; h->recov_F = state[1];
+    return MCL_OK;
+}
+
+int mcl_host_recovery_step(const mcl_recovery_config_t *c, const double in[2], int32_t reset, double max_logw, double sum_w,
+                           double denom, int32_t n_beams, double out[2], double *p_next)
+{
+    if (!c || !in || !out || recov_invalid(c) || !(denom > 0.0) || n_beams < 1) return MCL_ERR_INVALID_ARG;
+    double S = reset ? NAN : in[0], F = reset ? NAN : in[1];
+    recov_fold(*c, S, F, recov_likelihood(*c, max_logw, sum_w, denom, n_beams));
+    out[0] = S; out[1] = F;
+    if (p_next) *p_next = recov_p(S, F);
+    return MCL_OK;
+}
+
 int mcl_host_sensor_table(const mcl_config_t *cfg, int32_t P, double *out, size_t n)
 {
     if (!cfg || !out || P < 1 || n != (size_t)(P + 1) * (P + 1) || bad_sensor_fields(*cfg)) return MCL_ERR_INVALID_ARG;
@@ -2473,6 +2641,7 @@ int mcl_stage_distinct_parents(mcl_engine_t *h, const int32_t *d_parent, int64_t
                                int32_t *d_slot, int64_t *count)
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
+    if (h && h->recov_on) return recov_refuse_stage(h);
     if (!h || !d_parent || !d_distinct || !d_slot || !count || n_children <= 0 || n_total <= 0) return MCL_ERR_INVALID_ARG;
     if (n_total > MCL_MAX_TOTAL_PARTICLES) return fail(h, MCL_ERR_INVALID_ARG, "n_total exceeds MCL_MAX_TOTAL_PARTICLES");
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -2618,6 +2787,7 @@ int mcl_stage_resample(mcl_engine_t *h, const double *d_px, const double *d_py, 
                        int64_t n_parents, uint64_t q_total, int64_t child_first, int64_t n_children_total, const double action[3])
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
+    if (h && h->recov_on) return recov_refuse_stage(h);
     ParentSource src; src.px = d_px; src.py = d_py; src.pth = d_pth;
     if (!d_px || !d_py || !d_pth) return h ? fail(h, MCL_ERR_INVALID_ARG, "bad stage_resample arguments") : MCL_ERR_INVALID_ARG;
     return stage_resample_sync(h, src, d_cdf, n_parents, q_total, child_first, n_children_total, action);
@@ -2627,6 +2797,7 @@ int mcl_stage_resample_records(mcl_engine_t *h, const void *d_records, const uin
                                int64_t child_first, int64_t n_children_total, const double action[3])
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
+    if (h && h->recov_on) return recov_refuse_stage(h);
     ParentSource src; src.records = d_records;
     if (!d_records) return h ? fail(h, MCL_ERR_INVALID_ARG, "bad stage_resample arguments") : MCL_ERR_INVALID_ARG;
     return stage_resample_sync(h, src, d_cdf, n_parents, q_total, child_first, n_children_total, action);
@@ -2636,6 +2807,7 @@ int mcl_stage_resample_indices(mcl_engine_t *h, const uint64_t *d_cdf, int64_t n
                                int64_t n_children_total, int32_t *d_parent_idx)
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
+    if (h && h->recov_on) return recov_refuse_stage(h);
     ParentSource src; src.idx_only_out = d_parent_idx;
     if (!d_parent_idx || !d_cdf) return h ? fail(h, MCL_ERR_INVALID_ARG, "bad stage_resample_indices arguments") : MCL_ERR_INVALID_ARG;
     return stage_resample_sync(h, src, d_cdf, n_parents, q_total, child_first, n_children_total, nullptr);
@@ -2645,6 +2817,7 @@ int mcl_stage_motion_records(mcl_engine_t *h, const void *d_records, int64_t n_r
                              int64_t n_children_total, const double action[3])
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
+    if (h && h->recov_on) return recov_refuse_stage(h);
     ParentSource src; src.records = d_records; src.idx_in = d_record_of_child;
     if (!d_records || !d_record_of_child || n_records <= 0) return h ? fail(h, MCL_ERR_INVALID_ARG, "bad stage_motion_records arguments") : MCL_ERR_INVALID_ARG;
     return stage_resample_sync(h, src, nullptr, n_records, 0, child_first, n_children_total, action);
@@ -2724,6 +2897,7 @@ int mcl_stage_resample_compact(mcl_engine_t *h, const void *d_chunks, int32_t n_
                                const double action[3])
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
+    if (h && h->recov_on) return recov_refuse_stage(h);
     const int rc = stage_resample_compact_launch(h, d_chunks, n_shards, chunk_entries, counts, totals, n_per_shard, self_shard, child_first,
                                                  n_children_total, action, nullptr);
     if (rc) return rc;
@@ -2800,6 +2974,7 @@ static int stage_rays_finish(mcl_engine_t *h, const float *obs, int32_t n_beams)
 int mcl_stage_rays(mcl_engine_t *h, const float *obs, int32_t n_beams)
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
+    if (h && h->recov_on) return recov_refuse_stage(h);
     int rc = stage_rays_launch(h, obs, n_beams, false);
     if (rc) return rc;
     return stage_rays_finish(h, obs, n_beams);
@@ -2810,6 +2985,7 @@ int mcl_stage_propagate(mcl_engine_t *h, const double *d_px, const double *d_py,
                         const double action[3], const float *obs, int32_t n_beams)
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
+    if (h && h->recov_on) return recov_refuse_stage(h);
     if (!h) return MCL_ERR_INVALID_ARG;
     if (!obs || n_beams != h->B) return fail(h, MCL_ERR_INVALID_ARG, "bad observation");
     int rc = mcl_stage_resample(h, d_px, d_py, d_pth, d_cdf, n_parents, q_total, child_first, n_children_total, action);
@@ -2867,6 +3043,7 @@ static int stage_weights_finish(mcl_engine_t *h)
 int mcl_stage_weights(mcl_engine_t *h, double global_max_logw)
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
+    if (h && h->recov_on) return recov_refuse_stage(h);
     int rc = stage_weights_launch(h, global_max_logw);
     if (rc) return rc;
     return stage_weights_finish(h);
@@ -2882,6 +3059,7 @@ static void stage_commit_carry(mcl_engine_t *h)
 int mcl_stage_finish(mcl_engine_t *h, const double global_sums[5])
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
+    if (h && h->recov_on) return recov_refuse_stage(h);
     if (!h || !global_sums) return MCL_ERR_INVALID_ARG;
     for (int i = 0; i < 5; ++i) h->global_sums[i] = global_sums[i];
     stage_commit_carry(h);
@@ -2896,6 +3074,7 @@ int mcl_stage_finish(mcl_engine_t *h, const double global_sums[5])
 int mcl_stage_keep(mcl_engine_t *h, int64_t child_first, int64_t n_children_total, const double action[3])
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
+    if (h && h->recov_on) return recov_refuse_stage(h);
     if (!h || !action) return MCL_ERR_INVALID_ARG;
     if (h->cfg.resample_neff_permille <= 0) return fail(h, MCL_ERR_UNSUPPORTED, "mcl_stage_keep needs resample_neff_permille > 0");
     if (!h->carry_valid) return fail(h, MCL_ERR_NOT_READY, "no log-weights of a previous update to carry");
@@ -2937,6 +3116,7 @@ int mcl_stage_resample_compact_async(mcl_engine_t *h, const void *d_chunks, int3
                                      int64_t n_children_total, const double action[3])
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
+    if (h && h->recov_on) return recov_refuse_stage(h);
     return stage_resample_compact_launch(h, d_chunks, n_shards, chunk_entries, counts, totals, n_per_shard, self_shard, child_first,
                                          n_children_total, action, nullptr);
 }
@@ -2944,6 +3124,7 @@ int mcl_stage_resample_compact_async(mcl_engine_t *h, const void *d_chunks, int3
 int mcl_stage_rays_async(mcl_engine_t *h, const float *obs, int32_t n_beams, double *d_local_max)
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
+    if (h && h->recov_on) return recov_refuse_stage(h);
     if (!h || !d_local_max) return MCL_ERR_INVALID_ARG;
     const int rc = stage_rays_launch(h, obs, n_beams, false, d_local_max);
     if (rc) return rc;
@@ -2954,6 +3135,7 @@ int mcl_stage_rays_async(mcl_engine_t *h, const float *obs, int32_t n_beams, dou
 int mcl_stage_weights_async(mcl_engine_t *h, const double *d_global_max, double *d_vec, int32_t n_shards, int32_t self_shard)
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
+    if (h && h->recov_on) return recov_refuse_stage(h);
     if (!h || !d_global_max || !d_vec || n_shards <= 0 || n_shards > mcl::kMaxShards || self_shard < 0 || self_shard >= n_shards)
         return MCL_ERR_INVALID_ARG;
     if (!h->stage_async_rays) return fail(h, MCL_ERR_NOT_READY, "mcl_stage_rays_async first");
@@ -2969,6 +3151,7 @@ int mcl_stage_weights_async(mcl_engine_t *h, const double *d_global_max, double 
 int mcl_stage_complete(mcl_engine_t *h, const double global_sums[5], int32_t *redo)
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
+    if (h && h->recov_on) return recov_refuse_stage(h);
     if (!h || !global_sums || !redo) return MCL_ERR_INVALID_ARG;
     if (!h->stage_async_rays || !h->stage_async_weights) return fail(h, MCL_ERR_NOT_READY, "mcl_stage_rays_async and mcl_stage_weights_async first");
     h->stage_async_rays = h->stage_async_weights = false;

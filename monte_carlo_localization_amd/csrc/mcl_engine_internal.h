@@ -255,6 +255,15 @@ struct mcl_engine {
     unsigned int *d_kld_cnt = nullptr;  // 2 counters
     size_t kld_bm_words = 0, kld_list_cap = 0;
     int kld_parity = 0;
+    // recovery by injection (mcl_set_recovery): the averages S, F (NaN: unset) on the host; an injecting update
+    // counts its injected children in d_recov_cnt[recov_parity] and zeroes the other counter.  recov_cnt_slot: the counter of the
+    // last update (-1: it injected nothing); recov_injected: the count once read (-1: not read yet)
+    bool recov_on = false;
+    mcl_recovery_config_t recov{};
+    double recov_S = __builtin_nan(""), recov_F = __builtin_nan("");
+    unsigned int *d_recov_cnt = nullptr;     // 2 counters
+    int recov_parity = 0, recov_cnt_slot = -1;
+    int64_t recov_injected = 0;
     // pose clustering (mcl_pose_clusters): its own buffers, allocated on the first call; set_epoch counts the
     // changes of the particle set or its weights (the labels of a clustering are valid while it is unchanged)
     struct mcl_cluster *clu = nullptr;

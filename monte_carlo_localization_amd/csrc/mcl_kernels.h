@@ -306,8 +306,22 @@ __global__ __launch_bounds__(256) void k_kld_clear(KldArgs k)
     kld_clear_part(k, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
-template <bool KLD>
-__device__ __forceinline__ void resample_motion_body(const ResampleArgs &a, const KldArgs &k)
+// Recovery by random-particle injection (mcl_set_recovery): the _rec kernels are launched only for an update whose
+// injection threshold thr = floor(p * 2^53) is > 0.  Child g is injected iff bits53 of Philox stream 8 is below thr; its pose is a
+// free cell drawn as k_init_global draws one (stream 8's second half) and a heading from stream 9, it skips the parent search and the
+// motion model and reports parent -1.  Every other child is the one the plain kernel would make.
+struct RecArgs {
+    uint64_t thr;                     // injection threshold, > 0
+    const uint32_t *free_cells;       // the map's free cells (row * W + col), n_free > 0 of them
+    uint64_t n_free;
+    int W;
+    double res, ox, oy;
+    unsigned int *count;              // += injected children of this update
+    unsigned int *count_next;         // the other counter, zeroed for the next injecting update
+};
+
+template <bool KLD, bool REC>
+__device__ __forceinline__ void resample_motion_body(const ResampleArgs &a, const KldArgs &k, const RecArgs &r)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char resample_lds[];
     int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -324,11 +338,29 @@ __device__ __forceinline__ void resample_motion_body(const ResampleArgs &a, cons
         __syncthreads();
         cdf = c_sh;
     }
+    if constexpr (REC) { if (m == 0) *r.count_next = 0u; }
     if (m >= a.n_children) return;
     uint64_t g = (uint64_t)(a.child_first + m);
+    [[maybe_unused]] bool inj = false;        // (REC: this child is a drawn free-space pose)
+    [[maybe_unused]] double ix = 0.0, iy = 0.0, ith = 0.0;
+    if constexpr (REC) {
+        u32x4 o = philox4x32((uint32_t)g, a.update_idx, 8u, (uint32_t)(g >> 32), a.seed_lo, a.seed_hi);
+        inj = bits53(o.v[0], o.v[1]) < r.thr;
+        if (inj) {
+            const uint64_t pick = __umul64hi(bits53(o.v[2], o.v[3]) << 11, r.n_free);     // floor(k/2^53 * n_free)
+            const uint32_t cell = r.free_cells[pick];
+            const int row = (int)(cell / (uint32_t)r.W), col = (int)(cell - (uint32_t)row * (uint32_t)r.W);
+            ix = col * r.res + r.ox;                                 // the k_init_global rule (cpp:438-439)
+            iy = row * r.res + r.oy;
+            o = philox4x32((uint32_t)g, a.update_idx, 9u, (uint32_t)(g >> 32), a.seed_lo, a.seed_hi);
+            ith = ((double)bits53(o.v[0], o.v[1]) * (1.0 / 9007199254740992.0) - 0.5) * (2.0 * 3.14159265358979323846);   // [-pi, pi)
+        }
+    }
     int64_t idx = m;
     int64_t cpos = -1;                        // position in the compact parent list, when that is what was searched
-    if (a.idx_in) {
+    if (REC && inj) {
+        idx = -1;
+    } else if (a.idx_in) {
         idx = a.idx_in[m];
     } else if (a.do_resample) {
         idx = 0;
@@ -437,6 +469,8 @@ __device__ __forceinline__ void resample_motion_body(const ResampleArgs &a, cons
     if (a.idx_out) a.idx_out[m] = (int32_t)((a.do_resample || a.idx_in) ? idx : idx + a.idx_out_base);
     if (a.index_only) return;
     if (have_rec) {
+    } else if (REC && inj) {
+        x = ix; y = iy; th = ith;
     } else if (a.n_per_rank > 0) {
         // the parent's record straight from the shard that owns it (this GPU or a peer over xGMI): only selected
         // parents ever cross a link, and a parent many children share is served from this GPU's L2 after the first fetch
@@ -449,8 +483,8 @@ __device__ __forceinline__ void resample_motion_body(const ResampleArgs &a, cons
         }
     } else if (a.ppack) { const double4 pr = a.ppack[idx]; x = pr.x; y = pr.y; th = pr.z; }
     else { x = a.px[idx]; y = a.py[idx]; th = a.pth[idx]; }
-    [[maybe_unused]] const double kx = x, ky = y, kth = th;     // (KLD: the parent's pose, marked at the end of the kernel)
-    if (a.do_motion) {
+    [[maybe_unused]] const double kx = x, ky = y, kth = th;     // (KLD: the parent's pose, marked at the end of the kernel; REC: the injected pose)
+    if (a.do_motion && !(REC && inj)) {
         double n0, n1, n2;
         if (a.normals) {
             n0 = a.normals[3 * m + 0]; n1 = a.normals[3 * m + 1]; n2 = a.normals[3 * m + 2];
@@ -509,6 +543,11 @@ __device__ __forceinline__ void resample_motion_body(const ResampleArgs &a, cons
     }
     if (a.clr_logw_acc) a.clr_logw_acc[m] = 0.0;
     if (a.clr_far_flags) a.clr_far_flags[m] = 0u;
+    if constexpr (REC) {
+        // the injected children of the wave: one atomic
+        const unsigned long long injm = __ballot(inj);
+        if (injm && (threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) atomicAdd(r.count, (unsigned int)__popcll(injm));
+    }
     if constexpr (KLD) {
         // the parent's pose (a kept update: the particle's own), after the child's stores (the marking's dependent loads and
         // atomics then wait behind them, not in front of them): plain load first, the atomic only for a bit not seen set, and
@@ -536,9 +575,12 @@ __device__ __forceinline__ void resample_motion_body(const ResampleArgs &a, cons
     }
 }
 
-__global__ __launch_bounds__(256) void k_resample_motion(ResampleArgs a) { resample_motion_body<false>(a, KldArgs{}); }
+__global__ __launch_bounds__(256) void k_resample_motion(ResampleArgs a) { resample_motion_body<false, false>(a, KldArgs{}, RecArgs{}); }
 // the same with the KLD bin marking (a separate instantiation: the kernel without it is the one above, unchanged)
-__global__ __launch_bounds__(256) void k_resample_motion_kld(ResampleArgs a, KldArgs k) { resample_motion_body<true>(a, k); }
+__global__ __launch_bounds__(256) void k_resample_motion_kld(ResampleArgs a, KldArgs k) { resample_motion_body<true, false>(a, k, RecArgs{}); }
+// the two with recovery injection (launched only for an update whose threshold is > 0)
+__global__ __launch_bounds__(256) void k_resample_motion_rec(ResampleArgs a, RecArgs r) { resample_motion_body<false, true>(a, KldArgs{}, r); }
+__global__ __launch_bounds__(256) void k_resample_motion_kld_rec(ResampleArgs a, KldArgs k, RecArgs r) { resample_motion_body<true, true>(a, k, r); }
 
 // The shards' compact lists, gathered as chunks ([ccdf | crec | cidx], ccap entries each), become ONE searchable CDF: chunk r's
 // column plus the fixed-point total of the shards before it, its unused tail turned into a plateau at the shard's end value

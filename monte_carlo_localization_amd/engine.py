@@ -45,6 +45,7 @@ EXPORTS = [
     "mcl_host_sweep_global_layout", "mcl_get_ray_kernel_variant",
     "mcl_default_kld_config", "mcl_set_kld", "mcl_get_particle_count", "mcl_get_kld_state", "mcl_host_kld_bins", "mcl_host_kld_target",
     "mcl_default_cluster_config", "mcl_pose_clusters", "mcl_get_cluster_labels",
+    "mcl_default_recovery_config", "mcl_set_recovery", "mcl_get_recovery_state", "mcl_set_recovery_state", "mcl_host_recovery_step",
 ]
 
 
@@ -67,6 +68,11 @@ class KldConfig(C.Structure):
         ("bin_x_m", C.c_double), ("bin_y_m", C.c_double), ("n_theta_bins", C.c_int32), ("round_to", C.c_int32),
         ("shrink_permille", C.c_int32), ("reserved", C.c_int32),
     ]
+
+
+class RecoveryConfig(C.Structure):
+    """mcl_recovery_config_t: recovery by random-particle injection (Engine.set_recovery)."""
+    _fields_ = [("alpha_slow", C.c_double), ("alpha_fast", C.c_double), ("per_beam", C.c_int32), ("reserved", C.c_int32)]
 
 
 class ClusterConfig(C.Structure):
@@ -159,6 +165,13 @@ def load_library(legacy=False):
         lib.mcl_pose_clusters.argtypes = [C.c_void_p, C.POINTER(ClusterConfig), C.c_int32, C.c_void_p, C.POINTER(C.c_int64),
                                           C.POINTER(C.c_uint64)]
         lib.mcl_get_cluster_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        lib.mcl_default_recovery_config.argtypes = [C.POINTER(RecoveryConfig)]
+        lib.mcl_default_recovery_config.restype = None
+        lib.mcl_set_recovery.argtypes = [C.c_void_p, C.POINTER(RecoveryConfig)]
+        lib.mcl_get_recovery_state.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        lib.mcl_set_recovery_state.argtypes = [C.c_void_p, C.c_void_p]
+        lib.mcl_host_recovery_step.argtypes = [C.POINTER(RecoveryConfig), C.c_void_p, C.c_int32, C.c_double, C.c_double,
+                                               C.c_double, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]
         _libs[path] = _lib = lib
     return _lib
 
@@ -182,6 +195,29 @@ def default_kld_config(**over) -> KldConfig:
             raise AttributeError(name)
         setattr(k, name, v)
     return k
+
+
+def default_recovery_config(**over) -> RecoveryConfig:
+    """mcl_default_recovery_config, with fields overridden by keyword."""
+    c = RecoveryConfig()
+    load_library().mcl_default_recovery_config(C.byref(c))
+    for name, v in over.items():
+        if name not in dict(RecoveryConfig._fields_):
+            raise AttributeError(name)
+        setattr(c, name, v)
+    return c
+
+
+def host_recovery_step(cfg: RecoveryConfig, S, F, reset, max_logw, sum_w, denom, n_beams):
+    """One update of the recovery averages on the host (mcl_host_recovery_step; no device needed): (S, F, p of the next
+    update) after folding in the likelihood of an update with SCALARS max_logw, sum_w and denominator denom (N, or the previous
+    update's sum_w for a kept update); NaN = unset."""
+    st, out, p = (C.c_double * 2)(S, F), (C.c_double * 2)(), C.c_double()
+    rc = load_library().mcl_host_recovery_step(C.byref(cfg), st, C.c_int32(1 if reset else 0), C.c_double(max_logw),
+                                               C.c_double(sum_w), C.c_double(denom), C.c_int32(int(n_beams)), out, C.byref(p))
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_recovery_step rc={rc}", rc)
+    return out[0], out[1], p.value
 
 
 def default_cluster_config(**over) -> ClusterConfig:
@@ -415,6 +451,28 @@ class Engine:
         b, n = C.c_int64(), C.c_int64()
         self._chk(self.lib.mcl_get_kld_state(self._h, C.byref(b), C.byref(n)), "mcl_get_kld_state")
         return b.value, n.value
+
+    # -- recovery by random-particle injection (off by default)
+    def set_recovery(self, on=True, **fields):
+        """Switches recovery on with mcl_default_recovery_config's values overridden by `fields`, or off (on=False); either way
+        the averages start unset."""
+        if not on:
+            self._chk(self.lib.mcl_set_recovery(self._h, None), "mcl_set_recovery")
+            return None
+        c = default_recovery_config(**fields)
+        self._chk(self.lib.mcl_set_recovery(self._h, C.byref(c)), "mcl_set_recovery")
+        return c
+
+    def recovery_state(self):
+        """(S, F, p of the next update, children the last update injected); S and F are NaN while unset"""
+        st, k = (C.c_double * 3)(), C.c_int64()
+        self._chk(self.lib.mcl_get_recovery_state(self._h, st, C.byref(k)), "mcl_get_recovery_state")
+        return st[0], st[1], st[2], k.value
+
+    def set_recovery_state(self, S, F):
+        """Sets the averages (NaN = unset): restores a saved state, or forces the p of the next update."""
+        st = (C.c_double * 2)(S, F)
+        self._chk(self.lib.mcl_set_recovery_state(self._h, st), "mcl_set_recovery_state")
 
     def particle_count(self) -> int:
         n = C.c_int64()
