@@ -359,6 +359,44 @@ int mcl_set_recovery_state(mcl_engine_t *h, const double state[2]);
 int mcl_host_recovery_step(const mcl_recovery_config_t *c, const double in[2], int32_t reset, double max_logw, double sum_w,
                            double denom, int32_t n_beams, double out[2], double *p_next);
 
+/* ---- likelihood-field ("endpoint") sensor model (Probabilistic Robotics §6.4; AMCL's laser_model_type likelihood_field;
+ *      DESIGN.md §4.10) ---------------------------------------------------------------------------------------------------
+ * Off by default (the beam model above).  With it on, the log-weights of mcl_update, mcl_update_scan and mcl_sensor_update come
+ * from the end points of the beams looked up in a distance field instead of from ray casts; everything after the log-weights
+ * (weights, resampling, adaptive resampling, KLD, recovery, clusters, expected pose) is unchanged.
+ *   Field: D[c] = min(d2(c), K), d2 the exact integer squared distance in cells from cell c to the nearest occupied cell (value
+ *     > 50; a map without one: D = K everywhere), K = ceil((max_occ_dist_m / res)^2), res the map's float resolution widened to
+ *     double.  H x W uint16, row-major; built on the device when the model is switched on with a map set and on every mcl_set_map
+ *     while it is on.  K > 65535 is refused (MCL_ERR_INVALID_ARG) by mcl_set_likelihood_field / mcl_set_map.
+ *   Table: Lf[k] = (float)(log(z_hit * exp(-(k * res^2) / (2 sigma^2)) + z_rand / max_range_m) * (1 / squash_factor)) for
+ *     0 <= k < K, Lf[K] the same with the distance max_occ_dist_m (-(m * m) / (2 sigma^2)); host double, log(0) = -inf.
+ *   Beams used: 0 <= r_j < max_range_m (NaN, +-inf, negative and max-range readings contribute nothing).
+ *   End point: cell (floor((x + r_j cos(theta + a_j) - ox) / res), floor((y + r_j sin(theta + a_j) - oy) / res)) in fp64;
+ *     off the map it reads K.  logw = sum over the used beams, in beam order, of (double)Lf[D[cell]].
+ *   MCL_ERR_INVALID_ARG for sigma_hit_m or max_occ_dist_m not finite and > 0, a z_* negative or not finite, z_hit = z_rand = 0,
+ *     reserved != 0.  MCL_ERR_UNSUPPORTED for weight_mode PRODUCT, an engine with a communicator or in a device group,
+ *     mcl_comm_create while it is on, every mcl_stage_* call while it is on, and the ray read-backs (mcl_get_ray_steps*,
+ *     mcl_get_ray_kernel_id, mcl_get_ray_kernel_variant) after a likelihood-field update.  Switching the model (either way)
+ *     drops what the beam model's updates cache between updates: the next update plans as after mcl_set_particles. */
+typedef struct {
+    double z_hit, z_rand;                   /* default 0.5, 0.5                                                               */
+    double sigma_hit_m;                     /* default 0.2                                                                    */
+    double max_occ_dist_m;                  /* default 2.0 (AMCL's laser_likelihood_max_dist)                                 */
+    int32_t reserved[2];                    /* must be 0                                                                      */
+} mcl_likelihood_field_config_t;
+void mcl_default_likelihood_field_config(mcl_likelihood_field_config_t *c);
+int mcl_set_likelihood_field(mcl_engine_t *h, const mcl_likelihood_field_config_t *c);   /* NULL = beam model (the default) */
+/* the device field (H x W uint16) and table (K + 1 floats); MCL_ERR_NOT_READY while the model is off or no map is set.  The
+ * table: out may be NULL (n is then ignored), *K (may be NULL) receives K. */
+int mcl_get_likelihood_field(mcl_engine_t *h, uint16_t *out, size_t n);
+int mcl_get_likelihood_table(mcl_engine_t *h, float *out, size_t n, int32_t *K);
+/* the same on the host, without a device (the restatements the device is tested against); cfg supplies max_range_m and
+ * squash_factor */
+int mcl_host_likelihood_field(const int8_t *data, uint32_t width, uint32_t height, float resolution,
+                              const mcl_likelihood_field_config_t *c, uint16_t *out, size_t n);
+int mcl_host_likelihood_table(const mcl_config_t *cfg, const mcl_likelihood_field_config_t *c, float resolution, float *out,
+                              size_t n, int32_t *K);
+
 /* ---- host-side precomputation, callable without a device (what mcl_set_map uploads) --------- */
 /* (P+1)^2 doubles, Eigen column-major (index d*(P+1)+r): the restatement of precompute_sensor_model
  * (cpp:233-292) the engine uses.  MCL_ERR_INVALID_ARG for the sensor fields mcl_create refuses (a non-finite or negative

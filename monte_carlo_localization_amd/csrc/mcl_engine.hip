@@ -23,6 +23,7 @@
 
 #include "mcl_engine_internal.h"
 #include "mcl_kernels.h"
+#include "mcl_lfield.h"
 
 namespace {
 
@@ -545,6 +546,7 @@ int launch_rays(mcl_engine *h, const double *x, const double *y, const double *t
     a.counters = h->d_counters;
     a.force_exact = h->cfg.debug_force_exact;
     h->last_quad = false;
+    h->last_lf = false;
     h->max_partials_ready = false;
     const int mode = choose_ray_mode(h, n, force_skip);
     if (mode == 0) return fail(h, MCL_ERR_UNSUPPORTED, "MCL_RAYS_QUAD / MCL_RAYS_CELL / MCL_RAYS_SWEEP not usable with this map / beam set");
@@ -909,7 +911,7 @@ int weights_and_cdf(mcl_engine *h, bool result_to_host = false, const mcl::KldAr
     const int64_t n = h->N;
     if (h->cfg.weight_mode == MCL_WEIGHT_LOG && h->cfg.resample_neff_permille == 0 && n <= mcl::kTinyTailMax) {
         // d_pc holds (cos, sin) of the current headings whenever a ray kernel other than the literal march ran on them
-        const double4 *pc = h->last_mode >= 2 ? h->d_pc : nullptr;
+        const double4 *pc = h->last_mode >= 2 && !h->last_lf ? h->d_pc : nullptr;
         if (kld && result_to_host)
             hipLaunchKernelGGL(mcl::k_tiny_tail<true>, dim3(1), dim3(1024), (size_t)n * sizeof(uint64_t), h->stream, h->d_logw, h->d_x[h->cur],
                                h->d_y[h->cur], h->d_th[h->cur], pc, n, h->d_w, h->d_q, h->d_cdf, h->d_scalars, h->h_result, ++h->result_seq, *kld);
@@ -1086,6 +1088,134 @@ void recov_unset(mcl_engine *h)
 int recov_refuse_stage(mcl_engine *h)
 {
     return fail(h, MCL_ERR_UNSUPPORTED, "recovery (mcl_set_recovery) is single-engine only: the mcl_stage_* calls are refused while it is on");
+}
+
+// ---- likelihood-field sensor model (mcl_set_likelihood_field): the field on the device, the table in host double
+const char *lf_invalid(const mcl_likelihood_field_config_t *c)
+{
+    const double z[2] = {c->z_hit, c->z_rand};
+    for (double v : z)
+        if (!std::isfinite(v) || v < 0.0) return "likelihood field: z_hit and z_rand must be finite and >= 0";
+    if (z[0] == 0.0 && z[1] == 0.0) return "likelihood field: z_hit and z_rand are both 0";
+    if (!(std::isfinite(c->sigma_hit_m) && c->sigma_hit_m > 0.0)) return "likelihood field: sigma_hit_m must be finite and > 0";
+    if (!(std::isfinite(c->max_occ_dist_m) && c->max_occ_dist_m > 0.0)) return "likelihood field: max_occ_dist_m must be finite and > 0";
+    if (c->reserved[0] != 0 || c->reserved[1] != 0) return "likelihood field: reserved must be 0";
+    return nullptr;
+}
+
+// K = ceil((max_occ_dist / res)^2) (LF1), res the float resolution widened; -1 above 65535 (D is uint16)
+int lf_cap(const mcl_likelihood_field_config_t *c, float resolution)
+{
+    const double q = c->max_occ_dist_m / (double)resolution;
+    const double k = std::ceil(q * q);
+    return k <= 65535.0 ? (int)k : -1;
+}
+
+// LF2: Lf[k] for 0 <= k < K, Lf[K] at the distance max_occ_dist_m; log(0) = -inf
+void lf_table(const mcl_config_t &cfg, const mcl_likelihood_field_config_t &c, double res, int K, std::vector<float> &t)
+{
+    t.resize((size_t)K + 1);
+    const double res2 = res * res, den = 2.0 * c.sigma_hit_m * c.sigma_hit_m, rnd = c.z_rand / cfg.max_range_m;
+    const double inv_squash = 1.0 / cfg.squash_factor;
+    for (int k = 0; k <= K; ++k) {
+        const double e = k < K ? std::exp(-((double)k * res2) / den) : std::exp(-(c.max_occ_dist_m * c.max_occ_dist_m) / den);
+        t[(size_t)k] = (float)(std::log(c.z_hit * e + rnd) * inv_squash);
+    }
+}
+
+// LF1 on the host: exact squared distances from the lower envelopes of edt_1d (columns, then rows), clamped to K
+void lf_field_host(const int8_t *grid, int W, int H, int K, uint16_t *out)
+{
+    const int64_t INF = (int64_t)1 << 40;
+    const int n = std::max(W, H);
+    std::vector<int64_t> f((size_t)n), d((size_t)n), col((size_t)W * H);
+    std::vector<int> v((size_t)n);
+    std::vector<double> z((size_t)n + 1);
+    for (int x = 0; x < W; ++x) {
+        for (int y = 0; y < H; ++y) f[(size_t)y] = grid[(size_t)y * W + x] > 50 ? 0 : INF;
+        edt_1d(f.data(), H, d.data(), v.data(), z.data());
+        for (int y = 0; y < H; ++y) col[(size_t)y * W + x] = d[(size_t)y];
+    }
+    for (int y = 0; y < H; ++y) {
+        edt_1d(col.data() + (size_t)y * W, W, d.data(), v.data(), z.data());
+        for (int x = 0; x < W; ++x) out[(size_t)y * W + x] = (uint16_t)std::min<int64_t>(d[(size_t)x], K);
+    }
+}
+
+int lf_refuse_stage(mcl_engine *h)
+{
+    return fail(h, MCL_ERR_UNSUPPORTED, "the likelihood field (mcl_set_likelihood_field) is single-engine only: the mcl_stage_* calls are refused while it is on");
+}
+
+// the field and the table of the current map on the device (model on, map set, K checked by the caller)
+int lf_build(mcl_engine *h)
+{
+    const int K = lf_cap(&h->lf, (float)h->res);
+    int reach = (int)std::ceil(std::sqrt((double)K));                    // the least reach with reach^2 >= K
+    while (reach * reach < K) ++reach;
+    while (reach > 0 && (reach - 1) * (reach - 1) >= K) --reach;
+    lf_table(h->cfg, h->lf, h->res, K, h->lf_tab);
+    h->lf_K = -1;                                                         // until both buffers hold this map's
+    dfree(h->d_lf_D); dfree(h->d_lf_tab);
+    const size_t cells = (size_t)h->W * h->H;
+    HIPCHK(h, hipMalloc(&h->d_lf_D, cells * sizeof(uint16_t)));
+    HIPCHK(h, hipMalloc(&h->d_lf_tab, h->lf_tab.size() * sizeof(float)));
+    uint16_t *d_g = nullptr;
+    HIPCHK(h, hipMalloc(&d_g, cells * sizeof(uint16_t)));
+    const dim3 grid((unsigned)((cells + 255) / 256));
+    hipLaunchKernelGGL(mcl::k_lf_cols, grid, dim3(256), 0, h->stream, h->d_grid, h->W, h->H, reach, d_g);
+    hipLaunchKernelGGL(mcl::k_lf_rows, grid, dim3(256), 0, h->stream, d_g, h->W, h->H, reach, K, h->d_lf_D);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(h->d_lf_tab, h->lf_tab.data(), h->lf_tab.size() * sizeof(float), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    (void)hipFree(d_g);
+    if (e != hipSuccess) return fail(h, MCL_ERR_HIP, std::string("building the likelihood field: ") + hipGetErrorString(e));
+    h->lf_K = K;
+    return MCL_OK;
+}
+
+// The sensor stage of a likelihood-field update: the used beams of the scan in beam order (LF3), one copy, k_lfield (LF4, LF5).
+// EV_QUERY / EV_K0 .. EV_K1 bracket the kernel (stage 3 and mcl_get_ray_kernel_ms).
+int launch_lfield(mcl_engine *h, const float *obs, int stride, int64_t n)
+{
+    if (h->lf_beams_cap < h->B) {
+        if (h->h_lf_beams) { (void)hipHostFree(h->h_lf_beams); h->h_lf_beams = nullptr; }
+        dfree(h->d_lf_beams);
+        h->lf_beams_cap = 0;
+        HIPCHK(h, hipHostMalloc(&h->h_lf_beams, (size_t)h->B * sizeof(double2)));
+        HIPCHK(h, hipMalloc(&h->d_lf_beams, (size_t)h->B * sizeof(double2)));
+        h->lf_beams_cap = h->B;
+    }
+    const double inv_res = 1.0 / h->res;
+    int nb = 0;
+    for (int j = 0; j < h->B; ++j) {
+        const double r = (double)obs[(size_t)j * stride];
+        if (!(r >= 0.0 && r < h->cfg.max_range_m)) continue;             // NaN, +-inf, negative, max range: no contribution
+        h->h_lf_beams[nb++] = make_double2(r * h->beam_cs_host[(size_t)j].x * inv_res, r * h->beam_cs_host[(size_t)j].y * inv_res);
+    }
+    if (nb > 0)
+        HIPCHK(h, hipMemcpyAsync(h->d_lf_beams, h->h_lf_beams, (size_t)nb * sizeof(double2), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipEventRecord(h->ev[EV_QUERY], h->stream));
+    HIPCHK(h, hipEventRecord(h->ev[EV_K0], h->stream));
+    mcl::LfArgs a{};
+    a.x = h->d_x[h->cur]; a.y = h->d_y[h->cur]; a.th = h->d_th[h->cur]; a.n = n;
+    a.beams = h->d_lf_beams; a.nb = nb;
+    a.D = h->d_lf_D; a.W = h->W; a.H = h->H;
+    a.ox = h->ox; a.oy = h->oy; a.inv_res = inv_res;
+    a.lf = h->d_lf_tab; a.K = h->lf_K;
+    a.logw = h->d_logw;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (h->lf_K < mcl::kLfLdsEntries)
+        hipLaunchKernelGGL(mcl::k_lfield<true>, grid, dim3(256), (size_t)(h->lf_K + 1) * sizeof(float), h->stream, a);
+    else
+        hipLaunchKernelGGL(mcl::k_lfield<false>, grid, dim3(256), 0, h->stream, a);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev[EV_K1], h->stream));
+    h->max_partials_ready = false;
+    h->last_quad = false;
+    h->last_lf = true;
+    return MCL_OK;
 }
 
 }  // namespace
@@ -1330,6 +1460,8 @@ void mcl_destroy(mcl_engine_t *h)
     dfree(h->d_blockcnt); dfree(h->d_ccdf); dfree(h->d_ctop); dfree(h->d_cidx); dfree(h->d_crec);
     dfree(h->d_idx); dfree(h->d_steps); dfree(h->d_part); dfree(h->d_maxpart); dfree(h->d_result); if (h->h_result) { (void)hipHostFree(h->h_result); h->h_result = nullptr; } dfree(h->d_inject); dfree(h->d_pc); dfree(h->d_qr); dfree(h->d_far); dfree(h->d_far_list); dfree(h->d_far_sorted); dfree(h->d_far_cnt); dfree(h->d_pcs); dfree(h->d_ths); dfree(h->d_distw); dfree(h->d_distg); dfree(h->d_leaders); dfree(h->d_pack[0]); dfree(h->d_pack[1]); dfree(h->d_perm); dfree(h->d_skey); dfree(h->d_srank); dfree(h->d_skey2); dfree(h->d_sval2); dfree(h->d_sort_tmp); dfree(h->d_hist); dfree(h->d_histpart); dfree(h->d_tile_used); dfree(h->d_bbox); dfree(h->d_cut_start); dfree(h->d_cut_end); dfree(h->d_tilemap); dfree(h->d_tilemark); dfree(h->d_slice_mean); dfree(h->d_fix_list); dfree(h->d_fix_count); dfree(h->d_exact_list);
     dfree(h->d_grid); dfree(h->d_dist); dfree(h->d_dist4); dfree(h->d_L); dfree(h->d_table);
+    dfree(h->d_lf_D); dfree(h->d_lf_tab); dfree(h->d_lf_beams);
+    if (h->h_lf_beams) (void)hipHostFree(h->h_lf_beams);
     for (int q = 0; q < 4; ++q) dfree(h->d_distq[q]);
     dfree(h->d_angle); dfree(h->d_beam_cs); dfree(h->d_beam_csx); dfree(h->d_beam_csxg); dfree(h->d_beam_csi); dfree(h->d_beam_err); dfree(h->d_obs_idx); dfree(h->d_Lt); dfree(h->d_Ltd); dfree(h->d_items); dfree(h->d_centres); dfree(h->d_nitems); dfree(h->d_unit_sums); dfree(h->d_unit_begin); dfree(h->d_nunits); dfree(h->d_obs); dfree(h->d_free);
     if (h->h_obs) (void)hipHostFree(h->h_obs);
@@ -1355,6 +1487,8 @@ int mcl_set_map(mcl_engine_t *h, const int8_t *data, uint32_t width, uint32_t he
     uint64_t kld_bits = 0;
     if (h->kld_on && resolution > 0.0f && !kld_grid(&h->kld, width, height, resolution, kld_nx, kld_ny, kld_bits))
         return fail(h, MCL_ERR_INVALID_ARG, "KLD: the bin grid over this map exceeds 2^31 bits");
+    if (h->lf_on && resolution > 0.0f && lf_cap(&h->lf, resolution) < 0)
+        return fail(h, MCL_ERR_INVALID_ARG, "likelihood field: K = ceil((max_occ_dist_m / resolution)^2) exceeds 65535 on this map");
     graph_reset(h);
     if (!(resolution > 0.0f)) return fail(h, MCL_ERR_INVALID_ARG, "invalid map resolution");   // cpp:236-240
     recov_unset(h);
@@ -1480,6 +1614,11 @@ int mcl_set_map(mcl_engine_t *h, const int8_t *data, uint32_t width, uint32_t he
         const int rc = kld_alloc(h);
         if (rc) { h->have_map = false; return rc; }
     }
+    h->lf_K = -1;                        // (the model off: built when it is switched on)
+    if (h->lf_on) {
+        const int rc = lf_build(h);
+        if (rc) { h->have_map = false; return rc; }
+    }
     return MCL_OK;
 }
 
@@ -1522,6 +1661,7 @@ int mcl_set_beam_angles(mcl_engine_t *h, const float *angles, int32_t n_beams)
         double a = (double)angles[j < n_beams ? j : n_beams - 1];   // cpp:533 widens the float angle
         cs[j] = make_double2(std::cos(a), std::sin(a));
     }
+    h->beam_cs_host.assign(cs.begin(), cs.begin() + n_beams);
     // k_rays_sweep pads the lanes whose scan begins or ends inside a wedge with virtual beams -- the angular grid of the scan
     // continued beyond its ends -- up to the beams of a full wedge.  Only for an evenly spaced scan (every angle within a quarter
     // of the spacing of the grid through the first and the last) that leaves a wedge of the turn uncovered (no second range).
@@ -1919,7 +2059,8 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
     // A small update (k_rays_skip, the whole tail in one workgroup) is three launches and no copy: resampling + motion +
     // per-particle constants + table rows of the scan | rays against the static table | weights, sums, CDF and the result
     // block written straight to pinned host memory.  Every buffer exists once a regular update has run (graph_warm).
-    const bool tiny = resample_and_move && h->cfg.graph_mode != 1 && h->graph_warm && n <= mcl::kTinyTailMax && !keep &&
+    // (a likelihood-field update -- DESIGN.md §4.10 -- takes neither this nor the captured graph: its tail runs launch by launch)
+    const bool tiny = resample_and_move && !h->lf_on && h->cfg.graph_mode != 1 && h->graph_warm && n <= mcl::kTinyTailMax && !keep &&
                       choose_ray_mode(h, n, false) == 2 && h->cfg.weight_mode == MCL_WEIGHT_LOG && h->cfg.resample_neff_permille == 0;
     if (!tiny) HIPCHK(h, hipEventRecord(h->ev[EV_START], h->stream));
     bool obs_early = false;
@@ -1973,7 +2114,7 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
             stage_observation(h, obs, obs_stride);
             a.obs_src = h->h_obs; a.obs_idx_out = h->d_obs_idx; a.obs_B = h->B; a.obs_P = h->P; a.res = h->res;
         }
-        resample_ray_extras(h, n, a, rec);
+        if (!h->lf_on) resample_ray_extras(h, n, a, rec);
         size_t cdf_lds = 0;
         if (!a.tile_excl && a.do_resample && n_par <= mcl::kTinyTailMax) { a.cdf_lds_entries = (int)n_par; cdf_lds = (size_t)n_par * sizeof(uint64_t); }
         h->ev_resample_bound = false;
@@ -2027,7 +2168,7 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
         // kernels produce: with a windowed ray kernel they are built on a second stream beside those, and the ray stage waits for
         // them (a copy and two or three small launches off the critical path of an update: ~15 us).  Enqueued AFTER the resampling
         // kernel: that one is on the critical path, and a small update is bound by the order the host submits in.
-        if (!tiny && !h->env_no_obs_overlap && choose_ray_mode(h, n, false) >= 3) {
+        if (!tiny && !h->lf_on && !h->env_no_obs_overlap && choose_ray_mode(h, n, false) >= 3) {
             std::swap(h->stream, h->stream2);
             const int rc_obs = prepare_observation(h, obs, obs_stride);
             hipError_t ee = rc_obs ? hipSuccess : hipEventRecord(h->ev_obs, h->stream);
@@ -2082,7 +2223,7 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
     // particle buffer (observation upload, table build, rays, weights, CDF, result read-back: all arguments are fixed).
     // Eligibility is a pure function of the configuration and the sizes (choose_ray_mode), never of what the previous
     // update happened to run: k_rays_skip chosen outright has no work lists, no allocation and no fallback.
-    bool graph_ok = h->cfg.graph_mode != 1 && h->graph_warm && resample_and_move && choose_ray_mode(h, n, false) == 2 && !keep && !h->cfg.debug_count_probes &&
+    bool graph_ok = h->cfg.graph_mode != 1 && !h->lf_on && h->graph_warm && resample_and_move && choose_ray_mode(h, n, false) == 2 && !keep && !h->cfg.debug_count_probes &&
                     h->cfg.weight_mode == MCL_WEIGHT_LOG && h->cfg.resample_neff_permille == 0;
     if (graph_ok) {
         stage_observation(h, obs, obs_stride);
@@ -2140,23 +2281,30 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
         return MCL_OK;
     }
     h->ray_ms_is_graph_tail = false;
-    if (obs_early) {
-        // (the ordering kernels of the ray stage do not read the tables either: the stream waits for them where the ray kernel is
-        //  launched -- launch_rays --, not here: 13 us of a 262 144-particle update)
-        h->obs_wait_pending = true;
+    h->ev_rays_bound = false;
+    if (h->lf_on) {
+        // the likelihood field: no observation tables, no ordering, no ray stage; k_lfield writes d_logw
+        h->ev_query_skipped = false;
+        rc = launch_lfield(h, obs, obs_stride, n);
+        if (rc) return rc;
     } else {
-        rc = prepare_observation(h, obs, obs_stride);
+        if (obs_early) {
+            // (the ordering kernels of the ray stage do not read the tables either: the stream waits for them where the ray kernel is
+            //  launched -- launch_rays --, not here: 13 us of a 262 144-particle update)
+            h->obs_wait_pending = true;
+        } else {
+            rc = prepare_observation(h, obs, obs_stride);
+            if (rc) return rc;
+        }
+        // (the tables were made beside the ordering: no query-preparation stage on this stream, nothing to time)
+        h->ev_query_skipped = obs_early;
+        if (!obs_early) HIPCHK(h, hipEventRecord(h->ev[EV_QUERY], h->stream));
+        rc = launch_rays(h, h->d_x[h->cur], h->d_y[h->cur], h->d_th[h->cur], n);
+        if (h->obs_wait_pending) { h->obs_wait_pending = false; HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_obs, 0)); }      // (a path that launched no windowed kernel)
+        if (rc) return rc;
+        rc = next_layout_launch(h, n);          // (second stream; behind the ray stage in submission order, beside it on the device)
         if (rc) return rc;
     }
-    // (the tables were made beside the ordering: no query-preparation stage on this stream, nothing to time)
-    h->ev_query_skipped = obs_early;
-    if (!obs_early) HIPCHK(h, hipEventRecord(h->ev[EV_QUERY], h->stream));
-    h->ev_rays_bound = false;
-    rc = launch_rays(h, h->d_x[h->cur], h->d_y[h->cur], h->d_th[h->cur], n);
-    if (h->obs_wait_pending) { h->obs_wait_pending = false; HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_obs, 0)); }      // (a path that launched no windowed kernel)
-    if (rc) return rc;
-    rc = next_layout_launch(h, n);          // (second stream; behind the ray stage in submission order, beside it on the device)
-    if (rc) return rc;
     if (keep) {
         hipLaunchKernelGGL(mcl::k_add_carry, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d_logw, h->d_carry[h->carry_idx], n);
         h->max_partials_ready = false;
@@ -2190,7 +2338,7 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
     recov_after(h, rec, keep, prev_sum_w, n);
     h->graph_warm = true;                  // every buffer this configuration needs exists now
     h->have_logw = true;
-    h->have_steps = h->cfg.keep_ray_steps != 0;
+    h->have_steps = h->cfg.keep_ray_steps != 0 && !h->lf_on;
     if (resample_and_move) h->update_idx++;
     h->timings[0] = elapsed(h->ev[EV_START], h->ev[EV_RESAMPLE]);
     h->timings[1] = 0.0;                   // motion is fused into the resample/gather kernel
@@ -2252,9 +2400,15 @@ int mcl_get_resample_indices(mcl_engine_t *h, int32_t *idx, int64_t n)
     return MCL_OK;
 }
 
+static int lf_refuse_rays(const mcl_engine_t *h)
+{
+    return fail(const_cast<mcl_engine_t *>(h), MCL_ERR_UNSUPPORTED, "the last update used the likelihood field (mcl_set_likelihood_field): it cast no rays");
+}
+
 int mcl_get_ray_steps(mcl_engine_t *h, uint8_t *steps, size_t n)
 {
     if (!h || !steps) return MCL_ERR_INVALID_ARG;
+    if (h->last_lf) return lf_refuse_rays(h);
     if (!h->cfg.keep_ray_steps) return fail(h, MCL_ERR_UNSUPPORTED, "engine created without keep_ray_steps");
     if (h->P > 255) return fail(h, MCL_ERR_UNSUPPORTED, "MAX_RANGE_PX > 255: step indices do not fit bytes, use mcl_get_ray_steps16");
     if (!h->have_steps) return MCL_ERR_NOT_READY;
@@ -2268,6 +2422,7 @@ int mcl_get_ray_steps(mcl_engine_t *h, uint8_t *steps, size_t n)
 int mcl_get_ray_steps16(mcl_engine_t *h, uint16_t *steps, size_t n)
 {
     if (!h || !steps) return MCL_ERR_INVALID_ARG;
+    if (h->last_lf) return lf_refuse_rays(h);
     if (!h->cfg.keep_ray_steps) return fail(h, MCL_ERR_UNSUPPORTED, "engine created without keep_ray_steps");
     if (!h->have_steps) return MCL_ERR_NOT_READY;
     if (n != (size_t)h->N * h->B) return MCL_ERR_INVALID_ARG;
@@ -2328,6 +2483,7 @@ int mcl_get_ray_kernel_ms(const mcl_engine_t *h, double *ms)
 int mcl_get_ray_kernel_id(const mcl_engine_t *h, int32_t *kernel)
 {
     if (!h || !kernel) return MCL_ERR_INVALID_ARG;
+    if (h->last_lf) return lf_refuse_rays(h);
     *kernel = h->last_mode;
     return MCL_OK;
 }
@@ -2335,6 +2491,7 @@ int mcl_get_ray_kernel_id(const mcl_engine_t *h, int32_t *kernel)
 int mcl_get_ray_kernel_variant(const mcl_engine_t *h, int32_t out[3])
 {
     if (!h || !out) return MCL_ERR_INVALID_ARG;
+    if (h->last_lf) return lf_refuse_rays(h);
     out[0] = h->last_sweep_global; out[1] = h->last_sweep_rec; out[2] = h->last_sweep_pairs;
     return MCL_OK;
 }
@@ -2506,6 +2663,96 @@ int mcl_host_recovery_step(const mcl_recovery_config_t *c, const double in[2], i
     return MCL_OK;
 }
 
+void mcl_default_likelihood_field_config(mcl_likelihood_field_config_t *c)
+{
+    if (!c) return;
+    *c = mcl_likelihood_field_config_t{};
+    c->z_hit = 0.5; c->z_rand = 0.5; c->sigma_hit_m = 0.2; c->max_occ_dist_m = 2.0;   // AMCL's defaults
+}
+
+int mcl_set_likelihood_field(mcl_engine_t *h, const mcl_likelihood_field_config_t *c)
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    if (c) {
+        if (h->comm || h->in_group)
+            return fail(h, MCL_ERR_UNSUPPORTED, "the likelihood field is single-engine only: this engine has a communicator or belongs to a device group");
+        if (h->cfg.weight_mode != MCL_WEIGHT_LOG) return fail(h, MCL_ERR_UNSUPPORTED, "the likelihood field needs weight_mode LOG");
+        if (const char *why = lf_invalid(c)) return fail(h, MCL_ERR_INVALID_ARG, why);
+        if (h->have_map && lf_cap(c, (float)h->res) < 0)
+            return fail(h, MCL_ERR_INVALID_ARG, "likelihood field: K = ceil((max_occ_dist_m / resolution)^2) exceeds 65535 on this map");
+    }
+    // either way, what the beam model's updates keep between updates (captured graphs, the warm small-update paths, the ordering
+    // layout, the cleared-word cache, the far-pass state) is dropped: the next update plans as after mcl_set_particles
+    graph_reset(h);
+    h->far_fresh = true;
+    if (!c) {
+        h->lf_on = false;
+        return MCL_OK;
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    h->lf = *c;
+    h->lf_on = true;
+    h->lf_K = -1;
+    if (h->have_map) {
+        const int rc = lf_build(h);
+        if (rc) { h->lf_on = false; return rc; }
+    }
+    return MCL_OK;
+}
+
+int mcl_get_likelihood_field(mcl_engine_t *h, uint16_t *out, size_t n)
+{
+    if (!h || !out) return MCL_ERR_INVALID_ARG;
+    if (!h->lf_on || !h->have_map || h->lf_K < 0) return fail(h, MCL_ERR_NOT_READY, "the likelihood field is off or no map is set");
+    if (n != (size_t)h->W * h->H) return fail(h, MCL_ERR_INVALID_ARG, "the field has width x height entries");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipMemcpyAsync(out, h->d_lf_D, n * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MCL_OK;
+}
+
+int mcl_get_likelihood_table(mcl_engine_t *h, float *out, size_t n, int32_t *K)
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    if (!h->lf_on || !h->have_map || h->lf_K < 0) return fail(h, MCL_ERR_NOT_READY, "the likelihood field is off or no map is set");
+    if (K) *K = h->lf_K;
+    if (!out) return MCL_OK;
+    if (n != (size_t)h->lf_K + 1) return fail(h, MCL_ERR_INVALID_ARG, "the table has K + 1 entries");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipMemcpyAsync(out, h->d_lf_tab, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MCL_OK;
+}
+
+int mcl_host_likelihood_field(const int8_t *data, uint32_t width, uint32_t height, float resolution,
+                              const mcl_likelihood_field_config_t *c, uint16_t *out, size_t n)
+{
+    if (!data || !out || !c || width == 0 || height == 0 || width > 200000 || height > 200000 || !(resolution > 0.0f) ||
+        !std::isfinite(resolution) || lf_invalid(c) || n != (size_t)width * height)
+        return MCL_ERR_INVALID_ARG;
+    const int K = lf_cap(c, resolution);
+    if (K < 0) return MCL_ERR_INVALID_ARG;
+    lf_field_host(data, (int)width, (int)height, K, out);
+    return MCL_OK;
+}
+
+int mcl_host_likelihood_table(const mcl_config_t *cfg, const mcl_likelihood_field_config_t *c, float resolution, float *out,
+                              size_t n, int32_t *K)
+{
+    if (!cfg || !c || !(resolution > 0.0f) || !std::isfinite(resolution) || lf_invalid(c)) return MCL_ERR_INVALID_ARG;
+    if (!(std::isfinite(cfg->max_range_m) && cfg->max_range_m > 0.0 && std::isfinite(cfg->squash_factor) && cfg->squash_factor > 0.0))
+        return MCL_ERR_INVALID_ARG;
+    const int k = lf_cap(c, resolution);
+    if (k < 0) return MCL_ERR_INVALID_ARG;
+    if (K) *K = k;
+    if (!out) return MCL_OK;
+    if (n != (size_t)k + 1) return MCL_ERR_INVALID_ARG;
+    std::vector<float> t;
+    lf_table(*cfg, *c, (double)resolution, k, t);
+    std::memcpy(out, t.data(), n * sizeof(float));
+    return MCL_OK;
+}
+
 int mcl_host_sensor_table(const mcl_config_t *cfg, int32_t P, double *out, size_t n)
 {
     if (!cfg || !out || P < 1 || n != (size_t)(P + 1) * (P + 1) || bad_sensor_fields(*cfg)) return MCL_ERR_INVALID_ARG;
@@ -2642,6 +2889,7 @@ int mcl_stage_distinct_parents(mcl_engine_t *h, const int32_t *d_parent, int64_t
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
     if (h && h->recov_on) return recov_refuse_stage(h);
+    if (h && h->lf_on) return lf_refuse_stage(h);
     if (!h || !d_parent || !d_distinct || !d_slot || !count || n_children <= 0 || n_total <= 0) return MCL_ERR_INVALID_ARG;
     if (n_total > MCL_MAX_TOTAL_PARTICLES) return fail(h, MCL_ERR_INVALID_ARG, "n_total exceeds MCL_MAX_TOTAL_PARTICLES");
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -2788,6 +3036,7 @@ int mcl_stage_resample(mcl_engine_t *h, const double *d_px, const double *d_py, 
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
     if (h && h->recov_on) return recov_refuse_stage(h);
+    if (h && h->lf_on) return lf_refuse_stage(h);
     ParentSource src; src.px = d_px; src.py = d_py; src.pth = d_pth;
     if (!d_px || !d_py || !d_pth) return h ? fail(h, MCL_ERR_INVALID_ARG, "bad stage_resample arguments") : MCL_ERR_INVALID_ARG;
     return stage_resample_sync(h, src, d_cdf, n_parents, q_total, child_first, n_children_total, action);
@@ -2798,6 +3047,7 @@ int mcl_stage_resample_records(mcl_engine_t *h, const void *d_records, const uin
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
     if (h && h->recov_on) return recov_refuse_stage(h);
+    if (h && h->lf_on) return lf_refuse_stage(h);
     ParentSource src; src.records = d_records;
     if (!d_records) return h ? fail(h, MCL_ERR_INVALID_ARG, "bad stage_resample arguments") : MCL_ERR_INVALID_ARG;
     return stage_resample_sync(h, src, d_cdf, n_parents, q_total, child_first, n_children_total, action);
@@ -2808,6 +3058,7 @@ int mcl_stage_resample_indices(mcl_engine_t *h, const uint64_t *d_cdf, int64_t n
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
     if (h && h->recov_on) return recov_refuse_stage(h);
+    if (h && h->lf_on) return lf_refuse_stage(h);
     ParentSource src; src.idx_only_out = d_parent_idx;
     if (!d_parent_idx || !d_cdf) return h ? fail(h, MCL_ERR_INVALID_ARG, "bad stage_resample_indices arguments") : MCL_ERR_INVALID_ARG;
     return stage_resample_sync(h, src, d_cdf, n_parents, q_total, child_first, n_children_total, nullptr);
@@ -2818,6 +3069,7 @@ int mcl_stage_motion_records(mcl_engine_t *h, const void *d_records, int64_t n_r
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
     if (h && h->recov_on) return recov_refuse_stage(h);
+    if (h && h->lf_on) return lf_refuse_stage(h);
     ParentSource src; src.records = d_records; src.idx_in = d_record_of_child;
     if (!d_records || !d_record_of_child || n_records <= 0) return h ? fail(h, MCL_ERR_INVALID_ARG, "bad stage_motion_records arguments") : MCL_ERR_INVALID_ARG;
     return stage_resample_sync(h, src, nullptr, n_records, 0, child_first, n_children_total, action);
@@ -2898,6 +3150,7 @@ int mcl_stage_resample_compact(mcl_engine_t *h, const void *d_chunks, int32_t n_
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
     if (h && h->recov_on) return recov_refuse_stage(h);
+    if (h && h->lf_on) return lf_refuse_stage(h);
     const int rc = stage_resample_compact_launch(h, d_chunks, n_shards, chunk_entries, counts, totals, n_per_shard, self_shard, child_first,
                                                  n_children_total, action, nullptr);
     if (rc) return rc;
@@ -2975,6 +3228,7 @@ int mcl_stage_rays(mcl_engine_t *h, const float *obs, int32_t n_beams)
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
     if (h && h->recov_on) return recov_refuse_stage(h);
+    if (h && h->lf_on) return lf_refuse_stage(h);
     int rc = stage_rays_launch(h, obs, n_beams, false);
     if (rc) return rc;
     return stage_rays_finish(h, obs, n_beams);
@@ -2986,6 +3240,7 @@ int mcl_stage_propagate(mcl_engine_t *h, const double *d_px, const double *d_py,
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
     if (h && h->recov_on) return recov_refuse_stage(h);
+    if (h && h->lf_on) return lf_refuse_stage(h);
     if (!h) return MCL_ERR_INVALID_ARG;
     if (!obs || n_beams != h->B) return fail(h, MCL_ERR_INVALID_ARG, "bad observation");
     int rc = mcl_stage_resample(h, d_px, d_py, d_pth, d_cdf, n_parents, q_total, child_first, n_children_total, action);
@@ -3044,6 +3299,7 @@ int mcl_stage_weights(mcl_engine_t *h, double global_max_logw)
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
     if (h && h->recov_on) return recov_refuse_stage(h);
+    if (h && h->lf_on) return lf_refuse_stage(h);
     int rc = stage_weights_launch(h, global_max_logw);
     if (rc) return rc;
     return stage_weights_finish(h);
@@ -3060,6 +3316,7 @@ int mcl_stage_finish(mcl_engine_t *h, const double global_sums[5])
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
     if (h && h->recov_on) return recov_refuse_stage(h);
+    if (h && h->lf_on) return lf_refuse_stage(h);
     if (!h || !global_sums) return MCL_ERR_INVALID_ARG;
     for (int i = 0; i < 5; ++i) h->global_sums[i] = global_sums[i];
     stage_commit_carry(h);
@@ -3075,6 +3332,7 @@ int mcl_stage_keep(mcl_engine_t *h, int64_t child_first, int64_t n_children_tota
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
     if (h && h->recov_on) return recov_refuse_stage(h);
+    if (h && h->lf_on) return lf_refuse_stage(h);
     if (!h || !action) return MCL_ERR_INVALID_ARG;
     if (h->cfg.resample_neff_permille <= 0) return fail(h, MCL_ERR_UNSUPPORTED, "mcl_stage_keep needs resample_neff_permille > 0");
     if (!h->carry_valid) return fail(h, MCL_ERR_NOT_READY, "no log-weights of a previous update to carry");
@@ -3117,6 +3375,7 @@ int mcl_stage_resample_compact_async(mcl_engine_t *h, const void *d_chunks, int3
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
     if (h && h->recov_on) return recov_refuse_stage(h);
+    if (h && h->lf_on) return lf_refuse_stage(h);
     return stage_resample_compact_launch(h, d_chunks, n_shards, chunk_entries, counts, totals, n_per_shard, self_shard, child_first,
                                          n_children_total, action, nullptr);
 }
@@ -3125,6 +3384,7 @@ int mcl_stage_rays_async(mcl_engine_t *h, const float *obs, int32_t n_beams, dou
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
     if (h && h->recov_on) return recov_refuse_stage(h);
+    if (h && h->lf_on) return lf_refuse_stage(h);
     if (!h || !d_local_max) return MCL_ERR_INVALID_ARG;
     const int rc = stage_rays_launch(h, obs, n_beams, false, d_local_max);
     if (rc) return rc;
@@ -3136,6 +3396,7 @@ int mcl_stage_weights_async(mcl_engine_t *h, const double *d_global_max, double 
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
     if (h && h->recov_on) return recov_refuse_stage(h);
+    if (h && h->lf_on) return lf_refuse_stage(h);
     if (!h || !d_global_max || !d_vec || n_shards <= 0 || n_shards > mcl::kMaxShards || self_shard < 0 || self_shard >= n_shards)
         return MCL_ERR_INVALID_ARG;
     if (!h->stage_async_rays) return fail(h, MCL_ERR_NOT_READY, "mcl_stage_rays_async first");
@@ -3152,6 +3413,7 @@ int mcl_stage_complete(mcl_engine_t *h, const double global_sums[5], int32_t *re
 {
     if (h && h->kld_on) return kld_refuse_stage(h);
     if (h && h->recov_on) return recov_refuse_stage(h);
+    if (h && h->lf_on) return lf_refuse_stage(h);
     if (!h || !global_sums || !redo) return MCL_ERR_INVALID_ARG;
     if (!h->stage_async_rays || !h->stage_async_weights) return fail(h, MCL_ERR_NOT_READY, "mcl_stage_rays_async and mcl_stage_weights_async first");
     h->stage_async_rays = h->stage_async_weights = false;

@@ -264,6 +264,17 @@ struct mcl_engine {
     unsigned int *d_recov_cnt = nullptr;     // 2 counters
     int recov_parity = 0, recov_cnt_slot = -1;
     int64_t recov_injected = 0;
+    // likelihood-field sensor model (mcl_set_likelihood_field): the field and table of the current map (lf_K < 0:
+    // not built), the used beams of an update's scan staged in pinned memory; last_lf: the last log-weights came from k_lfield
+    bool lf_on = false, last_lf = false;
+    mcl_likelihood_field_config_t lf{};
+    int lf_K = -1;
+    uint16_t *d_lf_D = nullptr;
+    float *d_lf_tab = nullptr;
+    std::vector<float> lf_tab;
+    double2 *d_lf_beams = nullptr, *h_lf_beams = nullptr;
+    int lf_beams_cap = 0;
+    std::vector<double2> beam_cs_host;  // (cos, sin) of every beam angle (set_beam_angles)
     // pose clustering (mcl_pose_clusters): its own buffers, allocated on the first call; set_epoch counts the
     // changes of the particle set or its weights (the labels of a clustering are valid while it is unchanged)
     struct mcl_cluster *clu = nullptr;

@@ -46,6 +46,8 @@ EXPORTS = [
     "mcl_default_kld_config", "mcl_set_kld", "mcl_get_particle_count", "mcl_get_kld_state", "mcl_host_kld_bins", "mcl_host_kld_target",
     "mcl_default_cluster_config", "mcl_pose_clusters", "mcl_get_cluster_labels",
     "mcl_default_recovery_config", "mcl_set_recovery", "mcl_get_recovery_state", "mcl_set_recovery_state", "mcl_host_recovery_step",
+    "mcl_default_likelihood_field_config", "mcl_set_likelihood_field", "mcl_get_likelihood_field", "mcl_get_likelihood_table",
+    "mcl_host_likelihood_field", "mcl_host_likelihood_table",
 ]
 
 
@@ -73,6 +75,12 @@ class KldConfig(C.Structure):
 class RecoveryConfig(C.Structure):
     """mcl_recovery_config_t: recovery by random-particle injection (Engine.set_recovery)."""
     _fields_ = [("alpha_slow", C.c_double), ("alpha_fast", C.c_double), ("per_beam", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LikelihoodFieldConfig(C.Structure):
+    """mcl_likelihood_field_config_t: the likelihood-field sensor model (Engine.set_likelihood_field)."""
+    _fields_ = [("z_hit", C.c_double), ("z_rand", C.c_double), ("sigma_hit_m", C.c_double), ("max_occ_dist_m", C.c_double),
+                ("reserved", C.c_int32 * 2)]
 
 
 class ClusterConfig(C.Structure):
@@ -172,6 +180,15 @@ def load_library(legacy=False):
         lib.mcl_set_recovery_state.argtypes = [C.c_void_p, C.c_void_p]
         lib.mcl_host_recovery_step.argtypes = [C.POINTER(RecoveryConfig), C.c_void_p, C.c_int32, C.c_double, C.c_double,
                                                C.c_double, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]
+        lib.mcl_default_likelihood_field_config.argtypes = [C.POINTER(LikelihoodFieldConfig)]
+        lib.mcl_default_likelihood_field_config.restype = None
+        lib.mcl_set_likelihood_field.argtypes = [C.c_void_p, C.POINTER(LikelihoodFieldConfig)]
+        lib.mcl_get_likelihood_field.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.mcl_get_likelihood_table.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32)]
+        lib.mcl_host_likelihood_field.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(LikelihoodFieldConfig),
+                                                  C.c_void_p, C.c_size_t]
+        lib.mcl_host_likelihood_table.argtypes = [C.POINTER(Config), C.POINTER(LikelihoodFieldConfig), C.c_float, C.c_void_p,
+                                                  C.c_size_t, C.POINTER(C.c_int32)]
         _libs[path] = _lib = lib
     return _lib
 
@@ -218,6 +235,45 @@ def host_recovery_step(cfg: RecoveryConfig, S, F, reset, max_logw, sum_w, denom,
     if rc != MCL_OK:
         raise EngineError(f"mcl_host_recovery_step rc={rc}", rc)
     return out[0], out[1], p.value
+
+
+def default_likelihood_field_config(**over) -> LikelihoodFieldConfig:
+    """mcl_default_likelihood_field_config (AMCL's defaults), with fields overridden by keyword."""
+    c = LikelihoodFieldConfig()
+    load_library().mcl_default_likelihood_field_config(C.byref(c))
+    for name, v in over.items():
+        if name not in dict(LikelihoodFieldConfig._fields_):
+            raise AttributeError(name)
+        setattr(c, name, (C.c_int32 * 2)(*v) if name == "reserved" else v)
+    return c
+
+
+def host_likelihood_field(grid, resolution, **fields) -> np.ndarray:
+    """The likelihood field D of a map (mcl_host_likelihood_field; no device needed): shape (H, W), uint16."""
+    g = _c(grid, np.int8)
+    H, W = g.shape
+    out = np.empty((H, W), np.uint16)
+    c = default_likelihood_field_config(**fields)
+    rc = load_library().mcl_host_likelihood_field(_p(g), W, H, np.float32(resolution), C.byref(c), _p(out), out.size)
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_likelihood_field rc={rc}", rc)
+    return out
+
+
+def host_likelihood_table(resolution, cfg: Config | None = None, **fields) -> np.ndarray:
+    """The table Lf (K + 1 float32 entries) of the likelihood field (mcl_host_likelihood_table; no device needed); cfg supplies
+    max_range_m and squash_factor (default: mcl_default_config's)."""
+    cfg = cfg or default_config()
+    c = default_likelihood_field_config(**fields)
+    lib, K = load_library(), C.c_int32()
+    rc = lib.mcl_host_likelihood_table(C.byref(cfg), C.byref(c), np.float32(resolution), None, 0, C.byref(K))
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_likelihood_table rc={rc}", rc)
+    out = np.empty(K.value + 1, np.float32)
+    rc = lib.mcl_host_likelihood_table(C.byref(cfg), C.byref(c), np.float32(resolution), _p(out), out.size, None)
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_likelihood_table rc={rc}", rc)
+    return out
 
 
 def default_cluster_config(**over) -> ClusterConfig:
@@ -346,6 +402,7 @@ class Engine:
         H, W = g.shape
         self._chk(self.lib.mcl_set_map(self._h, _p(g), C.c_uint32(W), C.c_uint32(H), C.c_float(np.float32(resolution)),
                                        C.c_double(origin_x), C.c_double(origin_y)), "mcl_set_map")
+        self.map_shape = (H, W)
 
     @property
     def max_range_px(self) -> int:
@@ -473,6 +530,34 @@ class Engine:
         """Sets the averages (NaN = unset): restores a saved state, or forces the p of the next update."""
         st = (C.c_double * 2)(S, F)
         self._chk(self.lib.mcl_set_recovery_state(self._h, st), "mcl_set_recovery_state")
+
+    # -- likelihood-field sensor model (off by default; DESIGN.md §4.10)
+    def set_likelihood_field(self, on=True, **fields):
+        """Switches the likelihood-field sensor model on with mcl_default_likelihood_field_config's values (AMCL's) overridden by
+        `fields` -- z_hit, z_rand, sigma_hit_m, max_occ_dist_m -- or back to the beam model (on=False)."""
+        if not on:
+            self._chk(self.lib.mcl_set_likelihood_field(self._h, None), "mcl_set_likelihood_field")
+            return None
+        c = default_likelihood_field_config(**fields)
+        self._chk(self.lib.mcl_set_likelihood_field(self._h, C.byref(c)), "mcl_set_likelihood_field")
+        return c
+
+    def likelihood_field(self):
+        """The device's field D of the current map: shape (H, W), uint16."""
+        if getattr(self, "map_shape", None) is None:
+            raise EngineError("mcl_get_likelihood_field: no map set", MCL_ERR_NOT_READY)
+        H, W = self.map_shape
+        out = np.empty((H, W), np.uint16)
+        self._chk(self.lib.mcl_get_likelihood_field(self._h, _p(out), C.c_size_t(out.size)), "mcl_get_likelihood_field")
+        return out
+
+    def likelihood_table(self):
+        """The device's table Lf: K + 1 float32 entries."""
+        K = C.c_int32()
+        self._chk(self.lib.mcl_get_likelihood_table(self._h, None, C.c_size_t(0), C.byref(K)), "mcl_get_likelihood_table")
+        out = np.empty(K.value + 1, np.float32)
+        self._chk(self.lib.mcl_get_likelihood_table(self._h, _p(out), C.c_size_t(out.size), None), "mcl_get_likelihood_table")
+        return out
 
     def particle_count(self) -> int:
         n = C.c_int64()
