@@ -91,6 +91,23 @@ void ParticleFilterCore::initialize_particles_pose(const Vector3d &pose)
     push_state();
 }
 
+void ParticleFilterCore::initialize_particles_gaussian(const Vector3d &mean, const double cov[9])
+{
+    if (!engine_) return;
+    const double m[3] = {mean[0], mean[1], mean[2]};
+    if (mcl_init_particles_gaussian(engine_, m, cov, MAX_PARTICLES, 0, MAX_PARTICLES) != MCL_OK) {
+        fail("mcl_init_particles_gaussian");
+        return;
+    }
+    host_particles_stale_ = host_weights_stale_ = true;     // the cloud lives on the device: read back on demand
+}
+
+void ParticleFilterCore::set_motion_model(const mcl_motion_config_t *cfg)
+{
+    if (!engine_) return;
+    if (mcl_set_motion_model(engine_, cfg) != MCL_OK) fail("mcl_set_motion_model");
+}
+
 void ParticleFilterCore::initialize_global()
 {
     if (!map_initialized_) return;                                        // cpp:403

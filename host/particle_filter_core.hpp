@@ -77,6 +77,12 @@ class ParticleFilterCore {
 
     void initialize_particles_pose(const Vector3d &pose);   // cpp:382-399
     void initialize_global();                               // cpp:401-446
+    // /initialpose with its covariance (PoseWithCovarianceStamped: the x, y, yaw block, row-major 3 x 3), or a cluster that
+    // mcl_pose_clusters reported: drawn on the device (mcl_init_particles_gaussian), no upload
+    void initialize_particles_gaussian(const Vector3d &mean, const double cov[9]);
+    // AMCL's odometry motion models (mcl_set_motion_model; nullptr: the reference's model).  With one set, MCL()'s action is
+    // (dx, dy, dtheta) in the robot's frame at the previous update.
+    void set_motion_model(const mcl_motion_config_t *cfg);
 
     void MCL(const Vector3d &action, const std::vector<float> &observation);   // cpp:652-694
     Vector3d expected_pose();                                                   // cpp:696-716

@@ -397,6 +397,65 @@ int mcl_host_likelihood_field(const int8_t *data, uint32_t width, uint32_t heigh
 int mcl_host_likelihood_table(const mcl_config_t *cfg, const mcl_likelihood_field_config_t *c, float resolution, float *out,
                               size_t n, int32_t *K);
 
+/* ---- odometry motion models and covariance-based pose initialisation (Probabilistic Robotics Table 5.6,
+ *      sample_motion_model_odometry; AMCL's robot_model_type differential / omnidirectional with alpha1..alpha5;
+ *      DESIGN.md §4.11) ---------------------------------------------------------------------------------------------------
+ * Off by default (MCL_MOTION_REFERENCE: the reference's arc plus map-frame noise of fixed size, motion_dispersion_*).
+ *   M1 action.  With DIFF or OMNI, action = (dx, dy, dtheta): the robot's displacement since the previous update, expressed in
+ *     the robot's frame at the previous update (the odometry delta turned by minus the old odometry heading).  (forward, 0, yaw)
+ *     is a valid DIFF action.  With REFERENCE nothing changes (action[1] stays unused).
+ *   M2 angles.  norm(z) = atan2(sin z, cos z); adiff(a, b): a = norm(a); b = norm(b); d1 = a - b; d2 = 2 pi - |d1|; if d1 > 0:
+ *     d2 = -d2; return |d1| < |d2| ? d1 : d2.  Used on the host only.
+ *   M3 per-update scalars, host double, mcl_host_motion_scalars (the one function the engine itself calls for them):
+ *     trans = sqrt(dx^2 + dy^2); ft = floor_trans_m, fr = floor_rot_rad.
+ *     DIFF: rot1 = trans < 0.01 ? 0 : atan2(dy, dx); rot2 = adiff(dtheta, rot1); r1n = min(|adiff(rot1, 0)|, |adiff(rot1, pi)|),
+ *       r2n likewise from rot2 (a robot may reverse without a half turn of noise);
+ *       s1 = sqrt(a1 r1n^2 + a2 trans^2 + fr^2), st = sqrt(a3 trans^2 + a4 r1n^2 + a4 r2n^2 + ft^2),
+ *       s2 = sqrt(a1 r2n^2 + a2 trans^2 + fr^2).  out = {rot1, trans, rot2, s1, st, s2, 0, 0}.
+ *     OMNI: rot = dtheta, bearing = atan2(dy, dx); st = sqrt(a3 trans^2 + a1 rot^2 + ft^2), sr = sqrt(a4 rot^2 + a2 trans^2 + fr^2),
+ *       ss = sqrt(a1 rot^2 + a5 trans^2 + ft^2).  out = {bearing, trans, rot, st, sr, ss, 0, 0}.
+ *   M4 floors.  With every sigma 0 each child equals its parent, so the set of a standing robot collapses onto duplicates (AMCL
+ *     only updates after the robot moved; an engine updated on every tick does not).  The two floors are a standard deviation
+ *     added in quadrature; 0 (the default) is AMCL exactly.
+ *   M5 per child (normals n0, n1, n2 exactly the three the reference model draws: Philox streams 0 and 1, or row m of the injected
+ *     normals), fp64:
+ *     DIFF: r1 = rot1 - s1 n0; t = trans - st n1; r2 = rot2 - s2 n2; x' = x + t cos(theta + r1); y' = y + t sin(theta + r1);
+ *       theta' = normalize_angle(theta + (r1 + r2)).
+ *     OMNI: t = trans + st n0; r = rot + sr n1; s = ss n2; b = bearing + theta; x' = x + (t cos b + s sin b);
+ *       y' = y + (t sin b - s cos b); theta' = normalize_angle(theta + r).
+ *     normalize_angle: subtract / add 2 pi while outside [-pi, pi].  motion_dispersion_* are not used by DIFF / OMNI.
+ *   M6 what does not change: the draw of the parent, the Philox streams and counters, what KLD counts (the parent's pose before the
+ *     motion), recovery (an injected child skips the motion model whatever the model), kept updates of adaptive resampling (every
+ *     particle moves by M5), mcl_sensor_update (no motion), the per-particle constants and sort keys made from the moved pose.
+ *     The staged and sharded updates (mcl_stage_*, mcl_comm_update, mcl_group_update) honour the engine's model; every rank must
+ *     set the same config (not checked).  Children are bit-identical for any number of shards.
+ *   G1 Gaussian init.  cov row-major, symmetric to 1e-12 max|cov| and positive semi-definite.  The host forms the lower Cholesky
+ *     factor L in double; a pivot p with |p| <= 1e-12 max diag counts as 0 and zeroes its column (a covariance without heading
+ *     uncertainty is allowed), a pivot below that is MCL_ERR_INVALID_ARG, as are non-finite entries.  Particle g draws n0, n1, n2
+ *     as mcl_init_particles_pose does (streams 5 / 6, the init counter) and gets x = mx + L00 n0; y = my + (L10 n0 + L11 n1);
+ *     theta = normalize_angle(mt + (L20 n0 + L21 n1 + L22 n2)); weights 1 / n_total; everything else as mcl_init_particles_pose.
+ *   MCL_ERR_INVALID_ARG: unknown model, reserved != 0, a negative or non-finite alpha or floor, a null output.  The two
+ *     mcl_host_motion_* functions restate DIFF and OMNI only (MCL_ERR_INVALID_ARG for REFERENCE); a non-finite action is passed
+ *     through (NaN children).  Setting the model touches no particle state, drops no captured graph and resets no recovery average. */
+typedef enum { MCL_MOTION_REFERENCE = 0, MCL_MOTION_DIFF = 1, MCL_MOTION_OMNI = 2 } mcl_motion_model;
+typedef struct {
+    int32_t model;                          /* mcl_motion_model                                                               */
+    int32_t reserved;                       /* must be 0                                                                      */
+    double alpha1, alpha2, alpha3, alpha4, alpha5;   /* AMCL's, default 0.2 each; finite, >= 0                                */
+    double floor_trans_m, floor_rot_rad;    /* default 0, 0; finite, >= 0 (M4)                                                */
+} mcl_motion_config_t;
+void mcl_default_motion_config(mcl_motion_config_t *c);                  /* model = MCL_MOTION_DIFF, AMCL's defaults          */
+int mcl_set_motion_model(mcl_engine_t *h, const mcl_motion_config_t *c);  /* NULL or model REFERENCE = the reference's model  */
+int mcl_get_motion_model(const mcl_engine_t *h, mcl_motion_config_t *out);
+int mcl_host_motion_scalars(const mcl_motion_config_t *c, const double action[3], double out[8]);
+/* M5 on the host, without a device: n poses (column-major 3 x n) and normals (n x 3 row-major) -> children (column-major) */
+int mcl_host_motion_sample(const mcl_motion_config_t *c, const double action[3], const double *xyz_colmajor,
+                           const double *normals_nx3, int64_t n, double *out_colmajor);
+int mcl_init_particles_gaussian(mcl_engine_t *h, const double mean[3], const double cov[9], int64_t n,
+                                int64_t first_global_index, int64_t n_total);
+/* G1's factor on the host, without a device: L = {L00, L10, L11, L20, L21, L22}; MCL_ERR_INVALID_ARG as mcl_init_particles_gaussian */
+int mcl_host_gaussian_factor(const double cov[9], double L[6]);
+
 /* ---- host-side precomputation, callable without a device (what mcl_set_map uploads) --------- */
 /* (P+1)^2 doubles, Eigen column-major (index d*(P+1)+r): the restatement of precompute_sensor_model
  * (cpp:233-292) the engine uses.  MCL_ERR_INVALID_ARG for the sensor fields mcl_create refuses (a non-finite or negative
@@ -594,6 +653,9 @@ int mcl_group_set_beam_angles(mcl_group_t *g, const float *angles, int32_t n_bea
 int mcl_group_set_particles(mcl_group_t *g, const double *xyz, const double *weights, int64_t n_total);
 int mcl_group_init_particles_pose(mcl_group_t *g, const double pose[3], int64_t n_total);
 int mcl_group_init_global(mcl_group_t *g, int64_t n_total);
+/* mcl_init_particles_gaussian / mcl_set_motion_model on every shard (the same particles as one engine holding them all) */
+int mcl_group_init_particles_gaussian(mcl_group_t *g, const double mean[3], const double cov[9], int64_t n_total);
+int mcl_group_set_motion_model(mcl_group_t *g, const mcl_motion_config_t *c);
 int mcl_group_update(mcl_group_t *g, const double action[3], const float *obs, int32_t n_beams);
 int mcl_group_expected_pose(mcl_group_t *g, double out[3]);
 int mcl_group_get_particles(mcl_group_t *g, double *xyz, int64_t n_total);

@@ -2005,6 +2005,34 @@ static void recov_after(mcl_engine *h, bool injected, bool kept, double prev_sum
     recov_fold(h->recov, h->recov_S, h->recov_F, l);
 }
 
+static bool odo_args_of(const mcl_engine *h, const double action[3], mcl::OdoArgs &o);   // (with mcl_set_motion_model, below)
+
+// The resampling kernel of an update: one of eight entry points, [odometry model][KLD][recovery]; the arguments follow
+// ResampleArgs in that order of the ones that are present (kld, rec, odo: null = absent).  timed: EV_RESAMPLE is the kernel's
+// stop event.
+static void launch_resample(mcl_engine *h, dim3 grid, size_t lds, bool timed, mcl::ResampleArgs &a, mcl::KldArgs *kld, mcl::RecArgs *rec,
+                            mcl::OdoArgs *odo)
+{
+    static const void *const entry[2][2][2] = {
+        {{(const void *)mcl::k_resample_motion, (const void *)mcl::k_resample_motion_rec},
+         {(const void *)mcl::k_resample_motion_kld, (const void *)mcl::k_resample_motion_kld_rec}},
+        {{(const void *)mcl::k_resample_odo, (const void *)mcl::k_resample_odo_rec},
+         {(const void *)mcl::k_resample_odo_kld, (const void *)mcl::k_resample_odo_kld_rec}}};
+    void *args[4];
+    int na = 0;
+    args[na++] = &a;
+    if (kld) args[na++] = kld;
+    if (rec) args[na++] = rec;
+    if (odo) args[na++] = odo;
+    const void *fn = entry[odo ? 1 : 0][kld ? 1 : 0][rec ? 1 : 0];
+    if (timed) {
+        (void)hipExtLaunchKernel(fn, grid, dim3(256), args, lds, h->stream, nullptr, h->ev[EV_RESAMPLE], 0);
+        h->ev_resample_bound = true;
+    } else {
+        (void)hipLaunchKernel(fn, grid, dim3(256), args, lds, h->stream);
+    }
+}
+
 static int do_update(mcl_engine_t *h, const double action[3], const float *obs, int32_t n_beams, const double *normals,
                      const double *uniforms, bool resample_and_move, int obs_stride = 1)
 {
@@ -2135,31 +2163,14 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
             kld_cur.count = h->d_kld_cnt + h->kld_parity; kld_cur.count_next = h->d_kld_cnt + (h->kld_parity ^ 1);
             kld_cur.result = h->d_result + 17;
             h->kld_parity ^= 1;
-            if (rec && !tiny && !h->capturing) {
-                hipExtLaunchKernelGGL(mcl::k_resample_motion_kld_rec, grid, dim3(256), cdf_lds, h->stream, nullptr, h->ev[EV_RESAMPLE], 0, a, kld_cur, rec_args);
-                h->ev_resample_bound = true;
-            } else if (rec) {
-                hipLaunchKernelGGL(mcl::k_resample_motion_kld_rec, grid, dim3(256), cdf_lds, h->stream, a, kld_cur, rec_args);
-            } else if (!tiny && !h->capturing) {
-                hipExtLaunchKernelGGL(mcl::k_resample_motion_kld, grid, dim3(256), cdf_lds, h->stream, nullptr, h->ev[EV_RESAMPLE], 0, a, kld_cur);
-                h->ev_resample_bound = true;
-            } else {
-                hipLaunchKernelGGL(mcl::k_resample_motion_kld, grid, dim3(256), cdf_lds, h->stream, a, kld_cur);
-            }
-            if (!tiny) {
-                const int64_t most = std::min<int64_t>(n, (int64_t)h->kld_bits);
-                hipLaunchKernelGGL(mcl::k_kld_clear, dim3((unsigned)std::min<int64_t>((most + 255) / 256, 1024)), dim3(256), 0, h->stream, kld_cur);
-            }
-        } else if (rec && !tiny && !h->capturing) {
-            hipExtLaunchKernelGGL(mcl::k_resample_motion_rec, grid, dim3(256), cdf_lds, h->stream, nullptr, h->ev[EV_RESAMPLE], 0, a, rec_args);
-            h->ev_resample_bound = true;
-        } else if (rec) {
-            hipLaunchKernelGGL(mcl::k_resample_motion_rec, grid, dim3(256), cdf_lds, h->stream, a, rec_args);
-        } else if (!tiny && !h->capturing) {
-            hipExtLaunchKernelGGL(mcl::k_resample_motion, grid, dim3(256), cdf_lds, h->stream, nullptr, h->ev[EV_RESAMPLE], 0, a);
-            h->ev_resample_bound = true;
-        } else {
-            hipLaunchKernelGGL(mcl::k_resample_motion, grid, dim3(256), cdf_lds, h->stream, a);
+        }
+        // (the motion model's scalars are plain arguments of this launch, which is outside the captured graph and the tail)
+        mcl::OdoArgs odo_cur{};
+        const bool odo = odo_args_of(h, action, odo_cur);
+        launch_resample(h, grid, cdf_lds, !tiny && !h->capturing, a, kld ? &kld_cur : nullptr, rec ? &rec_args : nullptr, odo ? &odo_cur : nullptr);
+        if (kld && !tiny) {
+            const int64_t most = std::min<int64_t>(n, (int64_t)h->kld_bits);
+            hipLaunchKernelGGL(mcl::k_kld_clear, dim3((unsigned)std::min<int64_t>((most + 255) / 256, 1024)), dim3(256), 0, h->stream, kld_cur);
         }
         HIPCHK(h, hipGetLastError());
         h->N = n;                          // the children: the ray stage and everything after it run on them
@@ -2590,6 +2601,174 @@ int mcl_host_kld_target(const mcl_kld_config_t *k, int64_t bins, int64_t n_curre
     return MCL_OK;
 }
 
+// ---- odometry motion models and the Gaussian pose initialisation (the header's M1-M6 / G1) ----
+static const char *motion_invalid(const mcl_motion_config_t *c)
+{
+    if (c->model != MCL_MOTION_REFERENCE && c->model != MCL_MOTION_DIFF && c->model != MCL_MOTION_OMNI) return "motion model: unknown model";
+    if (c->reserved != 0) return "motion model: reserved must be 0";
+    const double v[7] = {c->alpha1, c->alpha2, c->alpha3, c->alpha4, c->alpha5, c->floor_trans_m, c->floor_rot_rad};
+    for (double e : v)
+        if (!std::isfinite(e) || e < 0.0) return "motion model: the alphas and floors must be finite and >= 0";
+    return nullptr;
+}
+
+void mcl_default_motion_config(mcl_motion_config_t *c)
+{
+    if (!c) return;
+    *c = mcl_motion_config_t{};
+    c->model = MCL_MOTION_DIFF;
+    c->alpha1 = c->alpha2 = c->alpha3 = c->alpha4 = c->alpha5 = 0.2;
+}
+
+int mcl_set_motion_model(mcl_engine_t *h, const mcl_motion_config_t *c)
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    if (!c) { h->motion = mcl_motion_config_t{}; return MCL_OK; }
+    if (const char *why = motion_invalid(c)) return fail(h, MCL_ERR_INVALID_ARG, why);
+    h->motion = *c;
+    return MCL_OK;
+}
+
+int mcl_get_motion_model(const mcl_engine_t *h, mcl_motion_config_t *out)
+{
+    if (!h || !out) return MCL_ERR_INVALID_ARG;
+    *out = h->motion;
+    return MCL_OK;
+}
+
+static double odo_norm(double z) { return std::atan2(std::sin(z), std::cos(z)); }
+static double odo_adiff(double a, double b)
+{
+    const double PI = 3.14159265358979323846;
+    a = odo_norm(a); b = odo_norm(b);
+    const double d1 = a - b;
+    double d2 = 2.0 * PI - std::fabs(d1);
+    if (d1 > 0.0) d2 = -d2;
+    return std::fabs(d1) < std::fabs(d2) ? d1 : d2;
+}
+
+int mcl_host_motion_scalars(const mcl_motion_config_t *c, const double action[3], double out[8])
+{
+    if (!c || !action || !out || motion_invalid(c) || c->model == MCL_MOTION_REFERENCE) return MCL_ERR_INVALID_ARG;
+    const double PI = 3.14159265358979323846;
+    const double dx = action[0], dy = action[1], dth = action[2];
+    const double trans = std::sqrt(dx * dx + dy * dy);
+    const double ft2 = c->floor_trans_m * c->floor_trans_m, fr2 = c->floor_rot_rad * c->floor_rot_rad;
+    const double t2 = trans * trans;
+    if (c->model == MCL_MOTION_DIFF) {
+        const double rot1 = trans < 0.01 ? 0.0 : std::atan2(dy, dx);
+        const double rot2 = odo_adiff(dth, rot1);
+        const double r1n = std::fmin(std::fabs(odo_adiff(rot1, 0.0)), std::fabs(odo_adiff(rot1, PI)));
+        const double r2n = std::fmin(std::fabs(odo_adiff(rot2, 0.0)), std::fabs(odo_adiff(rot2, PI)));
+        out[0] = rot1; out[1] = trans; out[2] = rot2;
+        out[3] = std::sqrt(c->alpha1 * (r1n * r1n) + c->alpha2 * t2 + fr2);
+        out[4] = std::sqrt(c->alpha3 * t2 + c->alpha4 * (r1n * r1n) + c->alpha4 * (r2n * r2n) + ft2);
+        out[5] = std::sqrt(c->alpha1 * (r2n * r2n) + c->alpha2 * t2 + fr2);
+    } else {
+        const double rot = dth, r2 = rot * rot;
+        out[0] = std::atan2(dy, dx); out[1] = trans; out[2] = rot;
+        out[3] = std::sqrt(c->alpha3 * t2 + c->alpha1 * r2 + ft2);
+        out[4] = std::sqrt(c->alpha4 * r2 + c->alpha2 * t2 + fr2);
+        out[5] = std::sqrt(c->alpha1 * r2 + c->alpha5 * t2 + ft2);
+    }
+    out[6] = 0.0; out[7] = 0.0;
+    return MCL_OK;
+}
+
+// the odometry arguments of an update's resampling kernel; false: the reference model (the kernels and arguments of always)
+static bool odo_args_of(const mcl_engine *h, const double action[3], mcl::OdoArgs &o)
+{
+    if (h->motion.model == MCL_MOTION_REFERENCE || !action) return false;
+    double s[8];
+    if (mcl_host_motion_scalars(&h->motion, action, s) != MCL_OK) return false;
+    o.model = h->motion.model; o.pad = 0;
+    for (int i = 0; i < 6; ++i) o.s[i] = s[i];
+    return true;
+}
+
+// mcl_device_math.h's normalize_angle on the host
+static double host_normalize_angle(double a)
+{
+    const double PI = 3.14159265358979323846;
+    int it = 0;
+    while (a > PI && it < 64) { a -= 2.0 * PI; ++it; }
+    while (a < -PI && it < 128) { a += 2.0 * PI; ++it; }
+    if (it >= 64 && (a > PI || a < -PI)) a = std::remainder(a, 2.0 * PI);
+    return a;
+}
+
+int mcl_host_motion_sample(const mcl_motion_config_t *c, const double action[3], const double *xyz, const double *normals, int64_t n,
+                           double *out)
+{
+    if (!xyz || !normals || !out || n < 0) return MCL_ERR_INVALID_ARG;
+    double s[8];
+    const int rc = mcl_host_motion_scalars(c, action, s);
+    if (rc) return rc;
+    mcl::OdoArgs o{};
+    o.model = c->model;
+    for (int i = 0; i < 6; ++i) o.s[i] = s[i];
+    for (int64_t m = 0; m < n; ++m) {
+        double x = xyz[m], y = xyz[n + m], th = xyz[2 * n + m];
+        mcl::odo_step(o, x, y, th, normals[3 * m], normals[3 * m + 1], normals[3 * m + 2]);
+        out[m] = x; out[n + m] = y; out[2 * n + m] = host_normalize_angle(th);
+    }
+    return MCL_OK;
+}
+
+// G1: the lower Cholesky factor of a symmetric positive semi-definite 3 x 3 matrix (row-major), L = {L00, L10, L11, L20, L21, L22}
+static const char *gaussian_factor(const double cov[9], double L[6])
+{
+    double amax = 0.0, dmax = 0.0;
+    for (int i = 0; i < 9; ++i) {
+        if (!std::isfinite(cov[i])) return "gaussian init: the covariance must be finite";
+        amax = std::max(amax, std::fabs(cov[i]));
+    }
+    for (int i = 0; i < 3; ++i) {
+        dmax = std::max(dmax, cov[4 * i]);
+        for (int j = 0; j < i; ++j)
+            if (std::fabs(cov[3 * i + j] - cov[3 * j + i]) > 1e-12 * amax) return "gaussian init: the covariance must be symmetric";
+    }
+    const double tol = 1e-12 * dmax;
+    double l[3][3] = {};
+    for (int j = 0; j < 3; ++j) {
+        double p = cov[4 * j];
+        for (int k = 0; k < j; ++k) p -= l[j][k] * l[j][k];
+        if (std::fabs(p) <= tol) continue;               // a zero pivot: the column stays zero
+        if (p < 0.0) return "gaussian init: the covariance must be positive semi-definite";
+        l[j][j] = std::sqrt(p);
+        for (int i = j + 1; i < 3; ++i) {
+            double v = cov[3 * i + j];
+            for (int k = 0; k < j; ++k) v -= l[i][k] * l[j][k];
+            l[i][j] = v / l[j][j];
+        }
+    }
+    L[0] = l[0][0]; L[1] = l[1][0]; L[2] = l[1][1]; L[3] = l[2][0]; L[4] = l[2][1]; L[5] = l[2][2];
+    return nullptr;
+}
+
+int mcl_host_gaussian_factor(const double cov[9], double L[6])
+{
+    if (!cov || !L) return MCL_ERR_INVALID_ARG;
+    return gaussian_factor(cov, L) ? MCL_ERR_INVALID_ARG : MCL_OK;
+}
+
+int mcl_init_particles_gaussian(mcl_engine_t *h, const double mean[3], const double cov[9], int64_t n, int64_t first_global_index,
+                                int64_t n_total)
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    if (!mean || !cov || n <= 0 || n > h->cap || first_global_index < 0 || n_total < n || n_total >= MCL_MAX_TOTAL_PARTICLES)
+        return fail(h, MCL_ERR_INVALID_ARG, "bad init arguments (the sharded total must stay below 2^27)");
+    double L[6];
+    if (const char *why = gaussian_factor(cov, L)) return fail(h, MCL_ERR_INVALID_ARG, why);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int c = h->cur;
+    hipLaunchKernelGGL(mcl::k_init_gaussian, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, mean[0], mean[1], mean[2], L[0],
+                       L[1], L[2], L[3], L[4], L[5], n, first_global_index, (uint32_t)h->cfg.seed, (uint32_t)(h->cfg.seed >> 32), h->init_idx,
+                       h->d_x[c], h->d_y[c], h->d_th[c]);
+    HIPCHK(h, hipGetLastError());
+    return finish_init(h, n, n_total);
+}
+
 void mcl_default_recovery_config(mcl_recovery_config_t *c)
 {
     if (!c) return;
@@ -3002,8 +3181,11 @@ static int stage_resample_launch(mcl_engine_t *h, const ParentSource &src, const
     // as in mcl_update: the ray stage's per-particle constants, its zeroed scratch and (by the previous update's layout) the sort
     // keys come out of this kernel; the layout of these children is made on the second stream for the next update
     if (!index_only) resample_ray_extras(h, n, a);
-    if (!index_only) hipExtLaunchKernelGGL(mcl::k_resample_motion, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, nullptr, h->ev[EV_RESAMPLE], 0, a);
-    else hipLaunchKernelGGL(mcl::k_resample_motion, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, a);
+    mcl::OdoArgs odo_cur{};
+    const bool odo = !index_only && odo_args_of(h, action, odo_cur);       // (an index-only pass moves nothing)
+    const bool bound_before = h->ev_resample_bound;
+    launch_resample(h, dim3((unsigned)((n + 255) / 256)), 0, !index_only, a, nullptr, nullptr, odo ? &odo_cur : nullptr);
+    h->ev_resample_bound = bound_before;               // (the staged flow reads EV_RESAMPLE itself)
     HIPCHK(h, hipGetLastError());
     if (a.pc_out) { const int rc_l = layout_mark(h, n); if (rc_l) return rc_l; }
     if (index_only) {

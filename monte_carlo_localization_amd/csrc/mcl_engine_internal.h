@@ -275,6 +275,9 @@ struct mcl_engine {
     double2 *d_lf_beams = nullptr, *h_lf_beams = nullptr;
     int lf_beams_cap = 0;
     std::vector<double2> beam_cs_host;  // (cos, sin) of every beam angle (set_beam_angles)
+    // motion model (mcl_set_motion_model): REFERENCE, or an odometry model whose per-update scalars go to the
+    // k_resample_odo* kernels as plain arguments
+    mcl_motion_config_t motion{};
     // pose clustering (mcl_pose_clusters): its own buffers, allocated on the first call; set_epoch counts the
     // changes of the particle set or its weights (the labels of a clustering are valid while it is unchanged)
     struct mcl_cluster *clu = nullptr;

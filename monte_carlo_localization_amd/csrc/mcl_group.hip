@@ -208,6 +208,28 @@ int mcl_group_init_particles_pose(mcl_group_t *g, const double pose[3], int64_t 
     return group_sync_q_total(g);
 }
 
+int mcl_group_init_particles_gaussian(mcl_group_t *g, const double mean[3], const double cov[9], int64_t n_total)
+{
+    if (!g || !mean || !cov) return MCL_ERR_INVALID_ARG;
+    int rc = group_check_total(g, n_total);
+    if (rc) return rc;
+    for (size_t d = 0; d < g->eng.size(); ++d) {
+        rc = mcl_init_particles_gaussian(g->eng[d], mean, cov, g->n_per, (int64_t)d * g->n_per, n_total);
+        if (rc) return gfail(g, rc, g->eng[d]->err);
+    }
+    return group_sync_q_total(g);
+}
+
+int mcl_group_set_motion_model(mcl_group_t *g, const mcl_motion_config_t *c)
+{
+    if (!g) return MCL_ERR_INVALID_ARG;
+    for (auto *e : g->eng) {
+        const int rc = mcl_set_motion_model(e, c);
+        if (rc) return gfail(g, rc, e->err);
+    }
+    return MCL_OK;
+}
+
 int mcl_group_init_global(mcl_group_t *g, int64_t n_total)
 {
     if (!g) return MCL_ERR_INVALID_ARG;

@@ -13,6 +13,7 @@
 #include <type_traits>
 #include "mcl_device_math.h"
 #include "mcl_wedge.h"
+#include "mcl_motion.h"
 
 namespace mcl {
 
@@ -320,8 +321,11 @@ struct RecArgs {
     unsigned int *count_next;         // the other counter, zeroed for the next injecting update
 };
 
-template <bool KLD, bool REC>
-__device__ __forceinline__ void resample_motion_body(const ResampleArgs &a, const KldArgs &k, const RecArgs &r)
+// ODO: the odometry motion models (mcl_set_motion_model): the child moves by odo_step (mcl_motion.h) with the same
+// three normals instead of by the reference's arc and map-frame noise; everything else is the kernel without it.
+template <bool KLD, bool REC, bool ODO = false>
+__device__ __forceinline__ void resample_motion_body(const ResampleArgs &a, const KldArgs &k, const RecArgs &r,
+                                                     [[maybe_unused]] const OdoArgs &od = OdoArgs{})
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char resample_lds[];
     int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -506,6 +510,10 @@ __device__ __forceinline__ void resample_motion_body(const ResampleArgs &a, cons
             n2 = rad * cos(TWO_PI * u2);
         }
         double nx, ny, nth;
+        if constexpr (ODO) {
+            nx = x; ny = y; nth = th;
+            odo_step(od, nx, ny, nth, n0, n1, n2);
+        } else {
         if (fabs(a.w) < 1e-6) {                       // cpp:480-484
             double sn, cs;
             sincos(th, &sn, &cs);
@@ -525,6 +533,7 @@ __device__ __forceinline__ void resample_motion_body(const ResampleArgs &a, cons
         nx += n0 * a.disp_x;                          // cpp:496-498
         ny += n1 * a.disp_y;
         nth += n2 * a.disp_th;
+        }
         nth = normalize_angle(nth);                   // cpp:501
         x = nx; y = ny; th = nth;
     }
@@ -581,6 +590,11 @@ __global__ __launch_bounds__(256) void k_resample_motion_kld(ResampleArgs a, Kld
 // the two with recovery injection (launched only for an update whose threshold is > 0)
 __global__ __launch_bounds__(256) void k_resample_motion_rec(ResampleArgs a, RecArgs r) { resample_motion_body<false, true>(a, KldArgs{}, r); }
 __global__ __launch_bounds__(256) void k_resample_motion_kld_rec(ResampleArgs a, KldArgs k, RecArgs r) { resample_motion_body<true, true>(a, k, r); }
+// the four with an odometry motion model (DIFF / OMNI: one instantiation each, the model is a wave-uniform branch in odo_step)
+__global__ __launch_bounds__(256) void k_resample_odo(ResampleArgs a, OdoArgs o) { resample_motion_body<false, false, true>(a, KldArgs{}, RecArgs{}, o); }
+__global__ __launch_bounds__(256) void k_resample_odo_kld(ResampleArgs a, KldArgs k, OdoArgs o) { resample_motion_body<true, false, true>(a, k, RecArgs{}, o); }
+__global__ __launch_bounds__(256) void k_resample_odo_rec(ResampleArgs a, RecArgs r, OdoArgs o) { resample_motion_body<false, true, true>(a, KldArgs{}, r, o); }
+__global__ __launch_bounds__(256) void k_resample_odo_kld_rec(ResampleArgs a, KldArgs k, RecArgs r, OdoArgs o) { resample_motion_body<true, true, true>(a, k, r, o); }
 
 // The shards' compact lists, gathered as chunks ([ccdf | crec | cidx], ccap entries each), become ONE searchable CDF: chunk r's
 // column plus the fixed-point total of the shards before it, its unused tail turned into a plateau at the shard's end value
@@ -701,6 +715,31 @@ __global__ __launch_bounds__(256) void k_init_pose(double px, double py, double 
     x[i] = px + n0 * 0.5;
     y[i] = py + n1 * 0.5;
     th[i] = normalize_angle(pt + n2 * 0.4);
+}
+
+// mcl_init_particles_gaussian (G1): k_init_pose's draw with the lower Cholesky factor of the covariance as six scalars
+__global__ __launch_bounds__(256) void k_init_gaussian(double px, double py, double pt, double l00, double l10, double l11, double l20,
+                                                      double l21, double l22, int64_t n, int64_t first, uint32_t seed_lo,
+                                                      uint32_t seed_hi, uint32_t init_idx, double *__restrict__ x,
+                                                      double *__restrict__ y, double *__restrict__ th)
+{
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint64_t g = (uint64_t)(first + i);
+    const double TWO_M53 = 1.0 / 9007199254740992.0;
+    const double TWO_PI = 2.0 * 3.14159265358979323846;
+    u32x4 o = philox4x32((uint32_t)g, init_idx, 5u, (uint32_t)(g >> 32), seed_lo, seed_hi);
+    double u1 = (double)(bits53(o.v[0], o.v[1]) + 1) * TWO_M53;
+    double u2 = (double)bits53(o.v[2], o.v[3]) * TWO_M53;
+    double rad = sqrt(-2.0 * log(u1));
+    double n0 = rad * cos(TWO_PI * u2), n1 = rad * sin(TWO_PI * u2);
+    o = philox4x32((uint32_t)g, init_idx, 6u, (uint32_t)(g >> 32), seed_lo, seed_hi);
+    u1 = (double)(bits53(o.v[0], o.v[1]) + 1) * TWO_M53;
+    u2 = (double)bits53(o.v[2], o.v[3]) * TWO_M53;
+    double n2 = sqrt(-2.0 * log(u1)) * cos(TWO_PI * u2);
+    x[i] = px + l00 * n0;
+    y[i] = py + (l10 * n0 + l11 * n1);
+    th[i] = normalize_angle(pt + (l20 * n0 + l21 * n1 + l22 * n2));
 }
 
 __global__ __launch_bounds__(256) void k_init_global(const uint32_t *__restrict__ free_cells, uint64_t n_free, int W, double res,

@@ -534,6 +534,16 @@ class ShardedFilter:
         self.shard.set_particles_shard(xyz_colmajor, w, float(mx.item()))
         self.reset()
 
+    def set_motion_model(self, model="diff", **fields):
+        """Engine.set_motion_model on this rank's shard.  Every rank must set the same model (as for the configuration; not
+        checked): the children are then those of one engine holding the whole set."""
+        return self.shard.set_motion_model(model, **fields)
+
+    def init_particles_gaussian(self, mean, cov):
+        """This rank's part of a Gaussian cloud of n_total particles (Engine.init_particles_gaussian with the shard's offset)."""
+        self.shard.init_particles_gaussian(mean, cov, self.n, first_global_index=self.rank * self.n, n_total=self.n_total)
+        self.reset()
+
     def expected_pose(self):
         return self.pose
 

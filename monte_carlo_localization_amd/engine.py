@@ -48,7 +48,11 @@ EXPORTS = [
     "mcl_default_recovery_config", "mcl_set_recovery", "mcl_get_recovery_state", "mcl_set_recovery_state", "mcl_host_recovery_step",
     "mcl_default_likelihood_field_config", "mcl_set_likelihood_field", "mcl_get_likelihood_field", "mcl_get_likelihood_table",
     "mcl_host_likelihood_field", "mcl_host_likelihood_table",
+    "mcl_default_motion_config", "mcl_set_motion_model", "mcl_get_motion_model", "mcl_host_motion_scalars", "mcl_host_motion_sample",
+    "mcl_init_particles_gaussian", "mcl_host_gaussian_factor", "mcl_group_set_motion_model", "mcl_group_init_particles_gaussian",
 ]
+MOTION_REFERENCE, MOTION_DIFF, MOTION_OMNI = 0, 1, 2
+MOTION_MODELS = {"reference": MOTION_REFERENCE, "diff": MOTION_DIFF, "omni": MOTION_OMNI}
 
 
 class Config(C.Structure):
@@ -81,6 +85,13 @@ class LikelihoodFieldConfig(C.Structure):
     """mcl_likelihood_field_config_t: the likelihood-field sensor model (Engine.set_likelihood_field)."""
     _fields_ = [("z_hit", C.c_double), ("z_rand", C.c_double), ("sigma_hit_m", C.c_double), ("max_occ_dist_m", C.c_double),
                 ("reserved", C.c_int32 * 2)]
+
+
+class MotionConfig(C.Structure):
+    """mcl_motion_config_t: the odometry motion models (Engine.set_motion_model)."""
+    _fields_ = [("model", C.c_int32), ("reserved", C.c_int32), ("alpha1", C.c_double), ("alpha2", C.c_double),
+                ("alpha3", C.c_double), ("alpha4", C.c_double), ("alpha5", C.c_double), ("floor_trans_m", C.c_double),
+                ("floor_rot_rad", C.c_double)]
 
 
 class ClusterConfig(C.Structure):
@@ -189,6 +200,16 @@ def load_library(legacy=False):
                                                   C.c_void_p, C.c_size_t]
         lib.mcl_host_likelihood_table.argtypes = [C.POINTER(Config), C.POINTER(LikelihoodFieldConfig), C.c_float, C.c_void_p,
                                                   C.c_size_t, C.POINTER(C.c_int32)]
+        lib.mcl_default_motion_config.argtypes = [C.POINTER(MotionConfig)]
+        lib.mcl_default_motion_config.restype = None
+        lib.mcl_set_motion_model.argtypes = [C.c_void_p, C.POINTER(MotionConfig)]
+        lib.mcl_get_motion_model.argtypes = [C.c_void_p, C.POINTER(MotionConfig)]
+        lib.mcl_host_motion_scalars.argtypes = [C.POINTER(MotionConfig), C.c_void_p, C.c_void_p]
+        lib.mcl_host_motion_sample.argtypes = [C.POINTER(MotionConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.mcl_init_particles_gaussian.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64]
+        lib.mcl_host_gaussian_factor.argtypes = [C.c_void_p, C.c_void_p]
+        lib.mcl_group_set_motion_model.argtypes = [C.c_void_p, C.POINTER(MotionConfig)]
+        lib.mcl_group_init_particles_gaussian.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
         _libs[path] = _lib = lib
     return _lib
 
@@ -274,6 +295,49 @@ def host_likelihood_table(resolution, cfg: Config | None = None, **fields) -> np
     if rc != MCL_OK:
         raise EngineError(f"mcl_host_likelihood_table rc={rc}", rc)
     return out
+
+
+def default_motion_config(**over) -> MotionConfig:
+    """mcl_default_motion_config (DIFF, AMCL's alphas), with fields overridden by keyword; `model` may be a name
+    ("reference", "diff", "omni")."""
+    c = MotionConfig()
+    load_library().mcl_default_motion_config(C.byref(c))
+    for name, v in over.items():
+        if name not in dict(MotionConfig._fields_):
+            raise AttributeError(name)
+        setattr(c, name, MOTION_MODELS[v] if name == "model" and isinstance(v, str) else v)
+    return c
+
+
+def host_motion_scalars(cfg: MotionConfig, action) -> np.ndarray:
+    """The per-update scalars of an odometry model (mcl_host_motion_scalars; no device needed): 8 doubles."""
+    a, out = _c(action, np.float64), np.empty(8)
+    assert a.size == 3
+    rc = load_library().mcl_host_motion_scalars(C.byref(cfg), _p(a), _p(out))
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_motion_scalars rc={rc}", rc)
+    return out
+
+
+def host_motion_sample(cfg: MotionConfig, action, xyz_colmajor, normals_nx3) -> np.ndarray:
+    """The children of the poses (3, n) under an odometry model with the normals (n, 3) (mcl_host_motion_sample; no device)."""
+    a, p, nrm = _c(action, np.float64), _c(xyz_colmajor, np.float64), _c(normals_nx3, np.float64)
+    assert a.size == 3 and p.ndim == 2 and p.shape[0] == 3 and nrm.size == 3 * p.shape[1]
+    out = np.empty_like(p)
+    rc = load_library().mcl_host_motion_sample(C.byref(cfg), _p(a), _p(p), _p(nrm), C.c_int64(p.shape[1]), _p(out))
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_motion_sample rc={rc}", rc)
+    return out
+
+
+def host_gaussian_factor(cov) -> np.ndarray:
+    """The lower Cholesky factor init_particles_gaussian draws with (mcl_host_gaussian_factor; no device needed), 3 x 3."""
+    c, L = _c(cov, np.float64), np.empty(6)
+    assert c.size == 9
+    rc = load_library().mcl_host_gaussian_factor(_p(c), _p(L))
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_gaussian_factor rc={rc}", rc)
+    return np.array([[L[0], 0.0, 0.0], [L[1], L[2], 0.0], [L[3], L[4], L[5]]])
 
 
 def default_cluster_config(**over) -> ClusterConfig:
@@ -451,6 +515,31 @@ class Engine:
         self._chk(self.lib.mcl_init_global(self._h, C.c_int64(n), C.c_int64(first_global_index), C.c_int64(n_total or n)),
                   "mcl_init_global")
         self.n = self.particle_count()
+
+    def init_particles_gaussian(self, mean, cov, n, first_global_index=0, n_total=None):
+        """A Gaussian cloud around `mean` with the 3 x 3 covariance `cov` (an /initialpose, or a cluster of pose_clusters), drawn on
+        the device (mcl_init_particles_gaussian)."""
+        m, c = _c(mean, np.float64), _c(cov, np.float64)
+        assert m.size == 3 and c.size == 9
+        self._chk(self.lib.mcl_init_particles_gaussian(self._h, _p(m), _p(c), C.c_int64(n), C.c_int64(first_global_index),
+                                                       C.c_int64(n_total or n)), "mcl_init_particles_gaussian")
+        self.n = self.particle_count()
+
+    # -- odometry motion models (off by default: the reference's model; DESIGN.md §4.11)
+    def set_motion_model(self, model="diff", **fields):
+        """Selects the motion model of the updates that follow: "diff" / "omni" with mcl_default_motion_config's values (AMCL's
+        alphas) overridden by `fields`, or None / "reference" for the reference's model."""
+        if model is None:
+            self._chk(self.lib.mcl_set_motion_model(self._h, None), "mcl_set_motion_model")
+            return None
+        c = default_motion_config(model=model, **fields)
+        self._chk(self.lib.mcl_set_motion_model(self._h, C.byref(c)), "mcl_set_motion_model")
+        return c
+
+    def motion_model(self) -> MotionConfig:
+        c = MotionConfig()
+        self._chk(self.lib.mcl_get_motion_model(self._h, C.byref(c)), "mcl_get_motion_model")
+        return c
 
     def update_scan(self, action, ranges, angle_step):
         a, r = _c(action, np.float64), _c(ranges, np.float32)
@@ -931,6 +1020,22 @@ class Group:
     def init_global(self, n_total):
         self.n_total = int(n_total)
         self._chk(self.lib.mcl_group_init_global(self._h, C.c_int64(n_total)), "mcl_group_init_global")
+
+    def init_particles_gaussian(self, mean, cov, n_total):
+        m, c = _c(mean, np.float64), _c(cov, np.float64)
+        assert m.size == 3 and c.size == 9
+        self.n_total = int(n_total)
+        self._chk(self.lib.mcl_group_init_particles_gaussian(self._h, _p(m), _p(c), C.c_int64(n_total)),
+                  "mcl_group_init_particles_gaussian")
+
+    def set_motion_model(self, model="diff", **fields):
+        """Engine.set_motion_model on every shard."""
+        if model is None:
+            self._chk(self.lib.mcl_group_set_motion_model(self._h, None), "mcl_group_set_motion_model")
+            return None
+        c = default_motion_config(model=model, **fields)
+        self._chk(self.lib.mcl_group_set_motion_model(self._h, C.byref(c)), "mcl_group_set_motion_model")
+        return c
 
     def update(self, action, obs):
         a = _c(action, np.float64)
