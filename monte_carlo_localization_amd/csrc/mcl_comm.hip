@@ -370,14 +370,14 @@ static int comm_gather_lists(mcl_engine_t *h, const int64_t *counts, CommLocal &
         if (c->d_chunk_all) (void)hipFree(c->d_chunk_all);
         c->d_chunk_local = c->d_chunk_all = nullptr; c->chunk_capacity = 0;
         const size_t cap = (size_t)entries + (size_t)entries / 4;            // lists breathe from update to update
-        ok = ok && hipMalloc(&c->d_chunk_local, cap * 44) == hipSuccess && hipMalloc(&c->d_chunk_all, cap * 44 * (size_t)G) == hipSuccess;
+        ok = ok && hipMalloc(&c->d_chunk_local, cap * kCompactEntryBytes) == hipSuccess && hipMalloc(&c->d_chunk_all, cap * kCompactEntryBytes * (size_t)G) == hipSuccess;
         if (!ok) { comm_abort(h, "alloc"); return fail(h, MCL_ERR_HIP, "mcl_comm_update: no memory for the list exchange (communicator aborted)"); }
         c->chunk_capacity = cap;
     }
     if (!loc.bad()) loc.note(h, export_compact_launch(h, c->d_chunk_local, entries, h->cfg.device, h->stream));
-    NCCLCHK(h, api.AllGather(c->d_chunk_local, c->d_chunk_all, (size_t)entries * 44, ncclChar, c->comm, h->stream));
-    c->bytes_received = (uint64_t)entries * 44u * (uint64_t)(G - 1);
-    c->bytes_payload = (uint64_t)(listed - counts[c->rank]) * 44u;
+    NCCLCHK(h, api.AllGather(c->d_chunk_local, c->d_chunk_all, (size_t)entries * kCompactEntryBytes, ncclChar, c->comm, h->stream));
+    c->bytes_received = (uint64_t)entries * (uint64_t)kCompactEntryBytes * (uint64_t)(G - 1);
+    c->bytes_payload = (uint64_t)(listed - counts[c->rank]) * (uint64_t)kCompactEntryBytes;
     c->gathered = !loc.bad(); c->gathered_epoch = h->list_epoch; c->gathered_entries = entries;
     for (int r = 0; r < G; ++r) c->gathered_counts[r] = counts[r];
     return MCL_OK;

@@ -1,14 +1,9 @@
-// mcl_engine.hip — C-ABI shim (include/mcl_hip_engine.h) over the HIP kernels in mcl_kernels.h.
-//
-// Host-side work done here, all of it init-time or O(beams) per update:
-//   * sensor table (cpp:233-292) in double, its fp32 log form, the padded distance field;
-//   * motion scalars (cpp:452-471), obs_idx (cpp:549-554,570,573);
-//   * kernel launches on the engine's own stream + HIP-event stage timings (utils.hpp:51-57).
+// mcl_engine.hip — C-ABI shim (include/mcl_hip_engine.h) over the HIP kernels in mcl_kernels.h: the engine object, its buffers and
+// streams, the update and its stages (kernel launches on the engine's own stream + HIP-event stage timings, utils.hpp:51-57).
+// The host arithmetic (sensor table, distance fields, motion scalars, ...) is in mcl_host_math.hip.
 // There is NO CPU fallback: without a gfx950 device mcl_create fails with MCL_ERR_NO_DEVICE.
 #include "../../include/mcl_hip_engine.h"
 
-#include <cstring>
-#include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -23,233 +18,16 @@
 
 #include "mcl_engine_internal.h"
 #include "mcl_kernels.h"
+#include "mcl_host_math.h"
 #include "mcl_lfield.h"
+
+static_assert(MCL_WEDGES == mcl::kWedges || MCL_KWEDGES != 16, "include/mcl_hip_engine.h and csrc/mcl_wedge.h disagree");
+
+using namespace mcl_host;
 
 namespace {
 
 thread_local std::string g_create_error;
-
-}  // namespace
-
-static_assert(MCL_WEDGES == mcl::kWedges || MCL_KWEDGES != 16, "include/mcl_hip_engine.h and csrc/mcl_wedge.h disagree");
-
-
-namespace {
-
-
-int fail(mcl_engine *h, int code, const char *msg)
-{
-    if (h) h->err = msg;
-    return code;
-}
-int fail(mcl_engine *h, int code, const std::string &msg) { return fail(h, code, msg.c_str()); }
-
-template <class T>
-void dfree(T *&p)
-{
-    if (p) { (void)hipFree(p); p = nullptr; }
-}
-
-// What the sensor model's fields must satisfy for the table to be a probability table (null: they do).  The reference does not
-// check them; here a NaN or a zero row would reach every log-weight (E5).
-const char *bad_sensor_fields(const mcl_config_t &c)
-{
-    const double z[4] = {c.z_hit, c.z_short, c.z_max, c.z_rand};
-    for (double v : z)
-        if (!std::isfinite(v) || v < 0.0) return "bad config (z_hit, z_short, z_max and z_rand must be finite and >= 0)";
-    if (z[0] == 0.0 && z[1] == 0.0 && z[2] == 0.0 && z[3] == 0.0) return "bad config (z_hit, z_short, z_max and z_rand are all 0)";
-    if (!std::isfinite(c.sigma_hit) || !(c.sigma_hit > 0.0)) return "bad config (sigma_hit must be finite and > 0)";
-    return nullptr;
-}
-
-// cpp:233-292, restated; column-major (d*(tw)+r).
-void build_sensor_table(const mcl_config_t &c, int P, std::vector<double> &t)
-{
-    const int tw = P + 1;
-    t.assign((size_t)tw * tw, 0.0);
-    for (int d = 0; d < tw; ++d) {
-        double norm = 0.0;
-        for (int r = 0; r < tw; ++r) {
-            double prob = 0.0;
-            double z = (double)(r - d);
-            prob += c.z_hit * std::exp(-(z * z) / (2.0 * c.sigma_hit * c.sigma_hit)) / (c.sigma_hit * std::sqrt(2.0 * M_PI));
-            if (r < d) prob += 2.0 * c.z_short * (d - r) / (double)d;
-            if (r == P) prob += c.z_max;
-            if (r < P) prob += c.z_rand * 1.0 / (double)P;
-            norm += prob;
-            t[(size_t)d * tw + r] = prob;
-        }
-        if (norm > 0)
-            for (int r = 0; r < tw; ++r) t[(size_t)d * tw + r] /= norm;
-    }
-}
-
-// Padded stop grid + skip-distance field.
-// Padded cell (xp,yp), xp in [0,W], yp in [0,H], stands for reference cell (max(xp-1,0), max(yp-1,0)):
-// the reference truncates toward zero (cpp:628-629), so pixel coordinates in (-1,0) read cell 0.
-// Everything outside the padded grid is "stop" (map boundary, cpp:632-636).
-//
-// skip(c) = how far the fixed-step march may jump from a sample inside cell c without being able to
-// land in a stop cell earlier.  Samples are exactly one pixel apart along the ray, so sample k+j lies at
-// Euclidean distance j from sample k; it can be inside stop cell t only if j >= dist(p_k, t) >= gap(c, t),
-// the distance between the two (closed) cell squares, with equality only for p_k on the boundary of c
-// (such samples are caught by the kernel's boundary guard).  Hence skip(c) = floor(min_t gap(c,t)) + 1.
-// gap^2(c,t) = max(|dx|-1,0)^2 + max(|dy|-1,0)^2 is the squared centre distance from c to the 3x3
-// dilation of t, so one exact integer squared-EDT (Felzenszwalb & Huttenlocher lower envelopes) of the
-// dilated stop set gives it.  Stop cells get 0; values are capped at 255.
-void edt_1d(const int64_t *f, int n, int64_t *d, int *v, double *z)
-{
-    const int64_t INF = (int64_t)1 << 40;
-    int k = 0;
-    v[0] = 0; z[0] = -1e30; z[1] = 1e30;
-    for (int q = 1; q < n; ++q) {
-        if (f[q] >= INF) continue;
-        while (true) {
-            if (f[v[k]] >= INF) { v[k] = q; z[k] = -1e30; z[k + 1] = 1e30; break; }
-            double s = ((double)(f[q] + (int64_t)q * q) - (double)(f[v[k]] + (int64_t)v[k] * v[k])) / (2.0 * q - 2.0 * v[k]);
-            if (s <= z[k]) { --k; if (k < 0) { k = 0; v[0] = q; z[0] = -1e30; z[1] = 1e30; break; } continue; }
-            ++k; v[k] = q; z[k] = s; z[k + 1] = 1e30;
-            break;
-        }
-    }
-    k = 0;
-    for (int q = 0; q < n; ++q) {
-        while (z[k + 1] < q) ++k;
-        int64_t dq = (int64_t)(q - v[k]);
-        d[q] = (f[v[k]] >= INF) ? INF : dq * dq + f[v[k]];
-    }
-}
-
-void build_distance_field(const int8_t *grid, int W, int H, int Wp, int Hp, int Wps, std::vector<uint8_t> &dist)
-{
-    // work grid = padded grid plus a one-cell stop border on every side
-    const int Ww = Wp + 2, Hw = Hp + 2;
-    std::vector<uint8_t> stop((size_t)Hw * Ww, 1), dil((size_t)Hw * Ww, 0);
-    for (int yp = 0; yp < Hp; ++yp)
-        for (int xp = 0; xp < Wp; ++xp) {
-            int gx = std::max(xp - 1, 0), gy = std::max(yp - 1, 0);
-            stop[(size_t)(yp + 1) * Ww + xp + 1] = grid[(size_t)gy * W + gx] > 50;
-        }
-    for (int y = 0; y < Hw; ++y)
-        for (int x = 0; x < Ww; ++x) {
-            if (!stop[(size_t)y * Ww + x]) continue;
-            for (int dy = -1; dy <= 1; ++dy)
-                for (int dx = -1; dx <= 1; ++dx) {
-                    int yy = y + dy, xx = x + dx;
-                    if (yy >= 0 && yy < Hw && xx >= 0 && xx < Ww) dil[(size_t)yy * Ww + xx] = 1;
-                }
-        }
-    const int64_t INF = (int64_t)1 << 40;
-    std::vector<int64_t> g((size_t)Hw * Ww);
-    const int nmax = std::max(Ww, Hw);
-    std::vector<int64_t> f(nmax), d(nmax);
-    std::vector<int> v(nmax + 1);
-    std::vector<double> z(nmax + 2);
-    for (int x = 0; x < Ww; ++x) {            // columns
-        for (int y = 0; y < Hw; ++y) f[y] = dil[(size_t)y * Ww + x] ? 0 : INF;
-        edt_1d(f.data(), Hw, d.data(), v.data(), z.data());
-        for (int y = 0; y < Hw; ++y) g[(size_t)y * Ww + x] = d[y];
-    }
-    dist.assign((size_t)Hp * Wps, 0);
-    for (int y = 1; y <= Hp; ++y) {           // rows
-        for (int x = 0; x < Ww; ++x) f[x] = g[(size_t)y * Ww + x];
-        edt_1d(f.data(), Ww, d.data(), v.data(), z.data());
-        for (int x = 1; x <= Wp; ++x) {
-            int val = 0;
-            if (!stop[(size_t)y * Ww + x]) {
-                int64_t g2 = d[x];
-                int64_t r = (int64_t)std::sqrt((double)g2);
-                while (r * r > g2) --r;
-                while ((r + 1) * (r + 1) <= g2) ++r;
-                val = (int)std::min<int64_t>(r + 1, 255);
-            }
-            dist[(size_t)(y - 1) * Wps + (x - 1)] = (uint8_t)val;
-        }
-    }
-}
-
-// Directional skip field for k_rays_quad, quadrant q = (sx, sy): a ray whose direction has sign sx in x and sy
-// in y can only ever enter cells t with sx*(t_x - c_x) >= 0 and sy*(t_y - c_y) >= 0, so only those stop cells
-// bound the jump: skip_q(c) = floor(min over forward stop cells t of gap(c, t)) + 1, gap as in
-// build_distance_field.  Walls beside or behind a ray no longer shorten its jumps (-30 % probes on the
-// benchmark input).  Exact integer arithmetic: per row the forward x-gap h to the next stop, then per column
-// a one-sided squared distance transform (lower envelope of parabolas, sources only ahead of the query).
-void build_directional_field(const int8_t *grid, int W, int H, int Wp, int Hp, int Wps, int sx, int sy, std::vector<uint8_t> &dist)
-{
-    const int64_t INF = (int64_t)1 << 40;
-    // stop(xf, yf) in "forward" coordinates: xf = sx > 0 ? xp : Wp-1-xp, same for y
-    auto stop_at = [&](int xf, int yf) -> bool {
-        int xp = sx > 0 ? xf : Wp - 1 - xf, yp = sy > 0 ? yf : Hp - 1 - yf;
-        int gx = std::max(xp - 1, 0), gy = std::max(yp - 1, 0);
-        return grid[(size_t)gy * W + gx] > 50;
-    };
-    // h[yf][xf]: gap in x to the nearest stop at x' >= xf in the same row (the cell just outside the grid is a stop)
-    std::vector<int32_t> h((size_t)(Hp + 1) * Wp);
-    for (int yf = 0; yf < Hp; ++yf) {
-        int nxt = Wp;
-        for (int xf = Wp - 1; xf >= 0; --xf) {
-            if (stop_at(xf, yf)) nxt = xf;
-            h[(size_t)yf * Wp + xf] = std::max(nxt - xf - 1, 0);
-        }
-    }
-    for (int xf = 0; xf < Wp; ++xf) h[(size_t)Hp * Wp + xf] = 0;      // the row beyond the grid is all stop
-    dist.assign((size_t)Hp * Wps, 0);
-    std::vector<int> vp(Hp + 2);          // envelope: source positions (in r = decreasing-y order)
-    std::vector<double> z(Hp + 3);
-    std::vector<int64_t> hg(Hp + 2);      // heights of the sources
-    for (int xf = 0; xf < Wp; ++xf) {
-        // g2(yf) = min( h(yf)^2 , min over p >= yf of (p - yf)^2 + h(p+1)^2 ): sources p = Hp-1 .. 0 arrive in
-        // decreasing p, i.e. increasing r = Hp-1-p; the query sits at the newest source's position.
-        int k = -1;
-        for (int yf = Hp - 1; yf >= 0; --yf) {
-            const int r = Hp - 1 - yf;
-            const int64_t hv = h[(size_t)(yf + 1) * Wp + xf];
-            const int64_t fh = hv * hv;
-            // insert parabola (r, fh)
-            while (true) {
-                if (k < 0) { k = 0; vp[0] = r; hg[0] = fh; z[0] = -1e30; z[1] = 1e30; break; }
-                double sI = ((double)(fh + (int64_t)r * r) - (double)(hg[k] + (int64_t)vp[k] * vp[k])) / (2.0 * r - 2.0 * vp[k]);
-                if (sI <= z[k]) { --k; continue; }
-                ++k; vp[k] = r; hg[k] = fh; z[k] = sI; z[k + 1] = 1e30;
-                break;
-            }
-            // query at r: the parabola whose interval contains r
-            int kk = k;
-            while (z[kk] > (double)r) --kk;
-            int64_t dq = (int64_t)(r - vp[kk]);
-            int64_t g2 = dq * dq + hg[kk];
-            // exactness of the envelope near interval ends: also try the neighbours
-            if (kk > 0) { int64_t d2 = (int64_t)(r - vp[kk - 1]); g2 = std::min(g2, d2 * d2 + hg[kk - 1]); }
-            if (kk < k) { int64_t d2 = (int64_t)(r - vp[kk + 1]); g2 = std::min(g2, d2 * d2 + hg[kk + 1]); }
-            const int64_t hs = h[(size_t)yf * Wp + xf];
-            g2 = std::min(g2, hs * hs);
-            int val = 0;
-            if (!stop_at(xf, yf)) {
-                int64_t rt = (int64_t)std::sqrt((double)g2);
-                while (rt * rt > g2) --rt;
-                while ((rt + 1) * (rt + 1) <= g2) ++rt;
-                val = (int)std::min<int64_t>(rt + 1, 255);
-            }
-            int xp = sx > 0 ? xf : Wp - 1 - xf, yp = sy > 0 ? yf : Hp - 1 - yf;
-            dist[(size_t)yp * Wps + xp] = (uint8_t)val;
-        }
-    }
-    (void)INF; (void)H;
-}
-
-// cpp:452-471
-void motion_scalars(const double action[3], double &dt, double &v, double &w)
-{
-    dt = 0.01; v = 0.0; w = 0.0;
-    double fd = action[0], ad = action[2];
-    if (std::abs(fd) > 0.001) {
-        if (std::abs(fd) < 0.1) dt = std::abs(fd) / 1.0;
-        else dt = std::abs(fd) / 5.0;
-        dt = std::max(0.001, std::min(dt, 0.1));
-        v = fd / dt;
-    }
-    if (std::abs(ad) > 0.001) w = ad / dt;
-}
 
 int ensure_lt(mcl_engine *h)
 {
@@ -270,45 +48,7 @@ int ensure_lt(mcl_engine *h)
     return MCL_OK;
 }
 
-void graph_reset(mcl_engine *h);
 void build_ltd(mcl_engine *h);
-
-int scan_weights(mcl_engine *h, const uint64_t *d_q, uint64_t *d_cdf, int64_t n, uint64_t offset, uint64_t *d_total)
-{
-    int nb = (int)((n + mcl::kScanTile - 1) / mcl::kScanTile);
-    // the scan of the engine's own weights also leaves the compact list of the particles that carry weight
-    mcl::CompactOut co{};
-    const bool own = d_q == h->d_q && d_cdf == h->d_cdf && offset == 0 && !h->env_no_compact && h->d_ccdf;
-    if (own) {
-        co.block_cnt = h->d_blockcnt; co.ccdf = h->d_ccdf; co.cidx = h->d_cidx; co.crec = h->d_crec; co.ctop = h->d_ctop;
-        co.x = h->d_x[h->cur]; co.y = h->d_y[h->cur]; co.th = h->d_th[h->cur];
-        co.cap = (uint32_t)h->compact_cap; co.total = h->d_result + 16;
-    }
-    hipLaunchKernelGGL(mcl::k_scan_partials, dim3(nb), dim3(mcl::kScanThreads), 0, h->stream, d_q, n, h->d_blocktot, co.block_cnt);
-    // (the spine is one workgroup that runs right after k_weights: it also finishes that kernel's partial sums, when asked)
-    const bool fold = h->sums_pending && d_q == h->d_q;
-    hipLaunchKernelGGL(mcl::k_scan_spine, dim3(1), dim3(1024), 0, h->stream, h->d_blocktot, nb, offset, d_total, co.block_cnt, co.total,
-                       fold ? h->d_part : (const double *)nullptr, mcl::kRedBlocks, h->d_scalars);
-    if (fold) h->sums_pending = false;
-    const size_t nlead = (size_t)((n + 15) >> mcl::kLeaderShift) + 1;
-    if (nlead > h->leaders_capacity) {
-        graph_reset(h);                    // a captured update graph holds the old pointer
-        dfree(h->d_leaders);
-        HIPCHK(h, hipMalloc(&h->d_leaders, nlead * 8));
-        h->leaders_capacity = nlead;
-    }
-    if (h->bind_sensor_event && own && !h->capturing) {          // the update's last kernel: EV_SENSOR is its stop event
-        hipExtLaunchKernelGGL(mcl::k_scan_final, dim3(nb), dim3(mcl::kScanThreads), 0, h->stream, nullptr, h->ev[EV_SENSOR], 0, d_q, n, h->d_blocktot, d_cdf,
-                              h->d_leaders, co);
-        h->ev_sensor_bound = true; h->bind_sensor_event = false;
-    } else {
-        hipLaunchKernelGGL(mcl::k_scan_final, dim3(nb), dim3(mcl::kScanThreads), 0, h->stream, d_q, n, h->d_blocktot, d_cdf, h->d_leaders, co);
-    }
-    HIPCHK(h, hipGetLastError());
-    h->blocktot_for = d_cdf; h->blocktot_n = n;
-    if (d_cdf == h->d_cdf) { h->compact_n = -1; h->compact_pending = own; h->list_epoch++; }
-    return MCL_OK;
-}
 
 // weights/q/sums from either log-weights (from_log) or raw weights already in d_w.  defer_sums: the caller scans d_q next
 // (scan_weights), whose one-workgroup spine then also reduces the partial sums -- one launch less.
@@ -335,8 +75,6 @@ int weight_stats(mcl_engine *h, bool from_log, const double *d_max_override, boo
     return MCL_OK;
 }
 
-void unpack_result(mcl_engine *h);
-
 int fetch_scalars(mcl_engine *h)
 {
     // scalars, counters and the work-list overflow flag in one copy into pinned memory
@@ -344,27 +82,6 @@ int fetch_scalars(mcl_engine *h)
     HIPCHK(h, hipStreamSynchronize(h->stream));
     unpack_result(h);
     return MCL_OK;
-}
-
-void unpack_result(mcl_engine *h)
-{
-    std::memcpy(h->h_scalars, h->h_result, 8 * sizeof(double));
-    std::memcpy(h->h_counters, h->h_result + 8, 4 * sizeof(unsigned long long));
-    h->h_fix_count = h->h_result[12];
-    uint64_t qt;
-    std::memcpy(&qt, &h->h_scalars[2], 8);
-    h->q_total = qt;
-    h->global_sums[0] = h->h_scalars[1];
-    h->global_sums[1] = h->h_scalars[3];
-    h->global_sums[2] = h->h_scalars[4];
-    h->global_sums[3] = h->h_scalars[5];
-    h->global_sums[4] = h->h_scalars[6];
-    // length of the compact list the scan of this update's weights wrote (word 16); unusable when it outgrew its arrays
-    if (h->compact_pending) {
-        const unsigned long long na = h->h_result[16];
-        h->compact_n = na <= (unsigned long long)h->compact_cap ? (int64_t)na : -1;       // 0: a valid, empty list (no weight here)
-        h->compact_pending = false;
-    }
 }
 
 // Work items of k_rays_sweep: made on the device from this update's unit statistics (k_sweep_plan, mcl_rays_sweep.h);
@@ -488,6 +205,14 @@ int choose_ray_mode(const mcl_engine *h, int64_t n, bool force_skip, const char 
     if (!h->skip_layout_ok) { w = "k_rays_skip's LDS layout check failed at mcl_create: literal march"; return 1; }
     w = !big ? "AUTO: fewer than 65536 particles or 2^23 rays: the self-contained k_rays_skip is the quickest" : no_sweep;
     return 2;
+}
+
+// The ordering's tiles over the padded map: occupied tiles are numbered compactly when the map has at most kSortMaxTiles of them
+struct SortTiles { int ntx_abs, nty_abs; bool ok; };
+SortTiles sort_tiles(const mcl_engine *h)
+{
+    const int ntx_abs = ((h->Wp * mcl::kSortSub - 1) >> 5) + 1, nty_abs = ((h->Hp * mcl::kSortSub - 1) >> 5) + 1;
+    return {ntx_abs, nty_abs, (int64_t)ntx_abs * nty_abs <= mcl::kSortMaxTiles};
 }
 
 // The windowed pass over what k_rays_sweep's windows did not fit (k_rays_skip<.., FAR>): ordered list of the flagged slots,
@@ -654,8 +379,7 @@ int launch_rays(mcl_engine *h, const double *x, const double *y, const double *t
             const int nparts = (int)(mcl::kSortKeySpace / mcl::kHistTile);
             const int bstride = n >= (1 << 20) ? 16 : 1;
             // occupied tiles of the map are numbered compactly when the map has at most kSortMaxTiles of them (bbox[5] says so)
-            const int ntx_abs = ((h->Wp * mcl::kSortSub - 1) >> 5) + 1, nty_abs = ((h->Hp * mcl::kSortSub - 1) >> 5) + 1;
-            const bool tiles_ok = (int64_t)ntx_abs * nty_abs <= mcl::kSortMaxTiles;
+            const auto [ntx_abs, nty_abs, tiles_ok] = sort_tiles(h);
             const bool stale_layout = h->layout_stale_used;
             if (!stale_layout) {
                 hipLaunchKernelGGL(mcl::k_cell_bbox, dim3((unsigned)std::min<int64_t>((n / bstride + 255) / 256, 128)), dim3(256), 0,
@@ -880,16 +604,6 @@ int prepare_observation(mcl_engine *h, const float *obs, int stride)
     return upload_observation(h);
 }
 
-void graph_reset(mcl_engine *h)
-{
-    for (int k = 0; k < 2; ++k)
-        if (h->graph_exec[k]) { (void)hipGraphExecDestroy(h->graph_exec[k]); h->graph_exec[k] = nullptr; }
-    h->graph_warm = false;
-    h->prep_cache_valid = false; h->prep_folded = false;
-    h->layout_valid = false; h->layout_stale_used = false; h->keys_done = false;
-    h->pc_ready = false;                    // whatever changed (map, beams, particles, a buffer): the ray stage makes its own constants
-}
-
 int sensor_and_weights(mcl_engine *h, const double *d_global_max, bool defer_sums = false)
 {
     // d_logw holds the log-weights of the current particle set
@@ -931,76 +645,7 @@ int weights_and_cdf(mcl_engine *h, bool result_to_host = false, const mcl::KldAr
     return scan_weights(h, h->d_q, h->d_cdf, n, 0, nullptr);   // CDF for the next resample / visualize
 }
 
-bool ready(mcl_engine *h, bool need_particles)
-{
-    return h && h->have_map && h->B > 0 && (!need_particles || h->have_particles);
-}
-
-float elapsed(hipEvent_t a, hipEvent_t b)
-{
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, a, b);
-    return ms;
-}
-
 // ---- KLD-adaptive particle count (mcl_set_kld)
-// why a KLD configuration is refused (null: it is not); cap > 0: the engine's max_particles
-const char *kld_invalid(const mcl_kld_config_t *k, int64_t cap)
-{
-    if (!(k->min_particles >= 1 && k->min_particles <= k->max_particles)) return "KLD: need 1 <= min_particles <= max_particles";
-    if (k->max_particles >= MCL_MAX_TOTAL_PARTICLES) return "KLD: max_particles must stay below 2^27";
-    if (cap > 0 && k->max_particles > cap) return "KLD: max_particles exceeds the engine's max_particles";
-    if (!(std::isfinite(k->err) && k->err > 0.0)) return "KLD: err must be finite and positive";
-    if (!(std::isfinite(k->z) && k->z >= 0.0)) return "KLD: z must be finite and non-negative";
-    if (!(std::isfinite(k->bin_x_m) && k->bin_x_m > 0.0 && std::isfinite(k->bin_y_m) && k->bin_y_m > 0.0))
-        return "KLD: bin sizes must be finite and positive";
-    if (k->n_theta_bins < 1) return "KLD: n_theta_bins must be >= 1";
-    if (k->round_to < 1) return "KLD: round_to must be >= 1";
-    if (k->shrink_permille < 0 || k->shrink_permille > 1000) return "KLD: shrink_permille must be in [0, 1000]";
-    if (k->reserved != 0) return "KLD: reserved must be 0";
-    return nullptr;
-}
-
-// the bin grid over a W x H map (false: more than 2^31 bits)
-bool kld_grid(const mcl_kld_config_t *k, uint32_t W, uint32_t H, float res, int64_t &nx, int64_t &ny, uint64_t &bits)
-{
-    const double fx = std::ceil((double)W * (double)res / k->bin_x_m), fy = std::ceil((double)H * (double)res / k->bin_y_m);
-    if (!(fx >= 1.0 && fy >= 1.0 && fx * fy * (double)k->n_theta_bins + 1.0 <= 2147483648.0)) return false;
-    nx = (int64_t)fx; ny = (int64_t)fy;
-    bits = (uint64_t)(nx * ny * k->n_theta_bins) + 1;
-    return true;
-}
-
-mcl::KldArgs kld_args_of(const mcl_kld_config_t *k, int64_t nx, int64_t ny, double ox, double oy)
-{
-    mcl::KldArgs a{};
-    a.ox = ox; a.oy = oy;
-    a.inv_bx = 1.0 / k->bin_x_m; a.inv_by = 1.0 / k->bin_y_m;
-    a.th_scale = (double)k->n_theta_bins / (2.0 * 3.14159265358979323846);
-    a.nx = (uint32_t)nx; a.ny = (uint32_t)ny; a.nth = (uint32_t)k->n_theta_bins;
-    a.nx_d = (double)nx; a.ny_d = (double)ny;
-    a.nth_d = (double)k->n_theta_bins; a.inv_nth = 1.0 / (double)k->n_theta_bins;
-    a.outside = (uint32_t)(nx * ny * k->n_theta_bins);
-    return a;
-}
-
-int64_t kld_target(const mcl_kld_config_t *k, int64_t bins, int64_t n_current)
-{
-    int64_t target = k->max_particles;
-    if (bins > 1) {
-        const double km1 = (double)(bins - 1);
-        const double a = 2.0 / (9.0 * km1);
-        const double b = 1.0 - a + std::sqrt(a) * k->z;
-        const double n = std::ceil(km1 / (2.0 * k->err) * (b * b * b));
-        if (n < (double)k->max_particles) {            // (rounding up and clamping cannot go below max from there)
-            const int64_t r = k->round_to, ni = n > 0.0 ? (int64_t)n : 0;
-            target = std::min(std::max((ni + r - 1) / r * r, k->min_particles), k->max_particles);
-        }
-    }
-    if (target <= n_current && target * 1000 >= n_current * (int64_t)k->shrink_permille) return n_current;
-    return target;
-}
-
 // the bitmap, the list and the two counters for the current map (allocated on the first need, grown, zeroed)
 int kld_alloc(mcl_engine *h)
 {
@@ -1037,49 +682,6 @@ int kld_refuse_stage(mcl_engine *h)
     return fail(h, MCL_ERR_UNSUPPORTED, "KLD sampling (mcl_set_kld) is single-engine only: the mcl_stage_* calls are refused while it is on");
 }
 
-// ---- recovery by random-particle injection (mcl_set_recovery): host double throughout
-const char *recov_invalid(const mcl_recovery_config_t *c)
-{
-    if (!(std::isfinite(c->alpha_slow) && std::isfinite(c->alpha_fast) && c->alpha_slow > 0.0 && c->alpha_slow < c->alpha_fast &&
-          c->alpha_fast <= 1.0))
-        return "recovery: need 0 < alpha_slow < alpha_fast <= 1";
-    if (c->per_beam != 0 && c->per_beam != 1) return "recovery: per_beam must be 0 or 1";
-    if (c->reserved != 0) return "recovery: reserved must be 0";
-    return nullptr;
-}
-
-double recov_logaddexp(double a, double b)
-{
-    const double hi = a > b ? a : b, lo = a > b ? b : a;
-    if (hi == -INFINITY) return -INFINITY;
-    return hi + std::log1p(std::exp(lo - hi));
-}
-
-// l of one update: m + log(sum_w) - log(denom), -inf for m = -inf, divided by the beam count with per_beam
-double recov_likelihood(const mcl_recovery_config_t &c, double max_logw, double sum_w, double denom, int n_beams)
-{
-    double l = max_logw == -INFINITY ? -INFINITY : max_logw + std::log(sum_w) - std::log(denom);
-    if (c.per_beam) l = l / (double)n_beams;
-    return l;
-}
-
-// folds l into (S, F) (NaN: unset); a NaN l changes nothing
-void recov_fold(const mcl_recovery_config_t &c, double &S, double &F, double l)
-{
-    if (std::isnan(l)) return;
-    S = std::isnan(S) ? l : recov_logaddexp(S + std::log1p(-c.alpha_slow), l + std::log(c.alpha_slow));
-    F = std::isnan(F) ? l : recov_logaddexp(F + std::log1p(-c.alpha_fast), l + std::log(c.alpha_fast));
-}
-
-double recov_p(double S, double F)
-{
-    if (std::isnan(S) || std::isnan(F) || S == -INFINITY) return 0.0;
-    const double p = 1.0 - std::exp(F - S);
-    return p > 0.0 ? (p < 1.0 ? p : 1.0) : 0.0;
-}
-
-uint64_t recov_threshold(double p) { return (uint64_t)(p * 9007199254740992.0); }     // floor(p * 2^53), p in [0, 1]
-
 void recov_unset(mcl_engine *h)
 {
     h->recov_S = h->recov_F = NAN;
@@ -1090,61 +692,18 @@ int recov_refuse_stage(mcl_engine *h)
     return fail(h, MCL_ERR_UNSUPPORTED, "recovery (mcl_set_recovery) is single-engine only: the mcl_stage_* calls are refused while it is on");
 }
 
-// ---- likelihood-field sensor model (mcl_set_likelihood_field): the field on the device, the table in host double
-const char *lf_invalid(const mcl_likelihood_field_config_t *c)
-{
-    const double z[2] = {c->z_hit, c->z_rand};
-    for (double v : z)
-        if (!std::isfinite(v) || v < 0.0) return "likelihood field: z_hit and z_rand must be finite and >= 0";
-    if (z[0] == 0.0 && z[1] == 0.0) return "likelihood field: z_hit and z_rand are both 0";
-    if (!(std::isfinite(c->sigma_hit_m) && c->sigma_hit_m > 0.0)) return "likelihood field: sigma_hit_m must be finite and > 0";
-    if (!(std::isfinite(c->max_occ_dist_m) && c->max_occ_dist_m > 0.0)) return "likelihood field: max_occ_dist_m must be finite and > 0";
-    if (c->reserved[0] != 0 || c->reserved[1] != 0) return "likelihood field: reserved must be 0";
-    return nullptr;
-}
-
-// K = ceil((max_occ_dist / res)^2) (LF1), res the float resolution widened; -1 above 65535 (D is uint16)
-int lf_cap(const mcl_likelihood_field_config_t *c, float resolution)
-{
-    const double q = c->max_occ_dist_m / (double)resolution;
-    const double k = std::ceil(q * q);
-    return k <= 65535.0 ? (int)k : -1;
-}
-
-// LF2: Lf[k] for 0 <= k < K, Lf[K] at the distance max_occ_dist_m; log(0) = -inf
-void lf_table(const mcl_config_t &cfg, const mcl_likelihood_field_config_t &c, double res, int K, std::vector<float> &t)
-{
-    t.resize((size_t)K + 1);
-    const double res2 = res * res, den = 2.0 * c.sigma_hit_m * c.sigma_hit_m, rnd = c.z_rand / cfg.max_range_m;
-    const double inv_squash = 1.0 / cfg.squash_factor;
-    for (int k = 0; k <= K; ++k) {
-        const double e = k < K ? std::exp(-((double)k * res2) / den) : std::exp(-(c.max_occ_dist_m * c.max_occ_dist_m) / den);
-        t[(size_t)k] = (float)(std::log(c.z_hit * e + rnd) * inv_squash);
-    }
-}
-
-// LF1 on the host: exact squared distances from the lower envelopes of edt_1d (columns, then rows), clamped to K
-void lf_field_host(const int8_t *grid, int W, int H, int K, uint16_t *out)
-{
-    const int64_t INF = (int64_t)1 << 40;
-    const int n = std::max(W, H);
-    std::vector<int64_t> f((size_t)n), d((size_t)n), col((size_t)W * H);
-    std::vector<int> v((size_t)n);
-    std::vector<double> z((size_t)n + 1);
-    for (int x = 0; x < W; ++x) {
-        for (int y = 0; y < H; ++y) f[(size_t)y] = grid[(size_t)y * W + x] > 50 ? 0 : INF;
-        edt_1d(f.data(), H, d.data(), v.data(), z.data());
-        for (int y = 0; y < H; ++y) col[(size_t)y * W + x] = d[(size_t)y];
-    }
-    for (int y = 0; y < H; ++y) {
-        edt_1d(col.data() + (size_t)y * W, W, d.data(), v.data(), z.data());
-        for (int x = 0; x < W; ++x) out[(size_t)y * W + x] = (uint16_t)std::min<int64_t>(d[(size_t)x], K);
-    }
-}
-
 int lf_refuse_stage(mcl_engine *h)
 {
     return fail(h, MCL_ERR_UNSUPPORTED, "the likelihood field (mcl_set_likelihood_field) is single-engine only: the mcl_stage_* calls are refused while it is on");
+}
+
+// Every mcl_stage_* entry point starts here: the staged (sharded) flow is refused while a single-engine feature is on (MCL_OK: none is)
+int refuse_stage(mcl_engine *h)
+{
+    if (h && h->kld_on) return kld_refuse_stage(h);
+    if (h && h->recov_on) return recov_refuse_stage(h);
+    if (h && h->lf_on) return lf_refuse_stage(h);
+    return MCL_OK;
 }
 
 // the field and the table of the current map on the device (model on, map set, K checked by the caller)
@@ -1220,25 +779,93 @@ int launch_lfield(mcl_engine *h, const float *obs, int stride, int64_t n)
 
 }  // namespace
 
-extern "C" {
+// ---- engine functions the other units use too (mcl_engine_internal.h); the stage_* ones are further down, beside their entry points
+int mcl_host::fail(mcl_engine *h, int code, const char *msg) { if (h) h->err = msg; return code; }
+int mcl_host::fail(mcl_engine *h, int code, const std::string &msg) { return fail(h, code, msg.c_str()); }
+
+std::string &mcl_host::create_error() { return g_create_error; }      // what mcl_*_last_error(NULL) reports
+
+bool mcl_host::ready(mcl_engine *h, bool need_particles)
+{
+    return h && h->have_map && h->B > 0 && (!need_particles || h->have_particles);
+}
+
+float mcl_host::elapsed(hipEvent_t a, hipEvent_t b)
+{
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, a, b);
+    return ms;
+}
+
+void mcl_host::graph_reset(mcl_engine *h)
+{
+    for (int k = 0; k < 2; ++k)
+        if (h->graph_exec[k]) { (void)hipGraphExecDestroy(h->graph_exec[k]); h->graph_exec[k] = nullptr; }
+    h->graph_warm = false;
+    h->prep_cache_valid = false; h->prep_folded = false;
+    h->layout_valid = false; h->layout_stale_used = false; h->keys_done = false;
+    h->pc_ready = false;                    // whatever changed (map, beams, particles, a buffer): the ray stage makes its own constants
+}
+
+int mcl_host::scan_weights(mcl_engine *h, const uint64_t *d_q, uint64_t *d_cdf, int64_t n, uint64_t offset, uint64_t *d_total)
+{
+    int nb = (int)((n + mcl::kScanTile - 1) / mcl::kScanTile);
+    // the scan of the engine's own weights also leaves the compact list of the particles that carry weight
+    mcl::CompactOut co{};
+    const bool own = d_q == h->d_q && d_cdf == h->d_cdf && offset == 0 && !h->env_no_compact && h->d_ccdf;
+    if (own) {
+        co.block_cnt = h->d_blockcnt; co.ccdf = h->d_ccdf; co.cidx = h->d_cidx; co.crec = h->d_crec; co.ctop = h->d_ctop;
+        co.x = h->d_x[h->cur]; co.y = h->d_y[h->cur]; co.th = h->d_th[h->cur];
+        co.cap = (uint32_t)h->compact_cap; co.total = h->d_result + 16;
+    }
+    hipLaunchKernelGGL(mcl::k_scan_partials, dim3(nb), dim3(mcl::kScanThreads), 0, h->stream, d_q, n, h->d_blocktot, co.block_cnt);
+    // (the spine is one workgroup that runs right after k_weights: it also finishes that kernel's partial sums, when asked)
+    const bool fold = h->sums_pending && d_q == h->d_q;
+    hipLaunchKernelGGL(mcl::k_scan_spine, dim3(1), dim3(1024), 0, h->stream, h->d_blocktot, nb, offset, d_total, co.block_cnt, co.total,
+                       fold ? h->d_part : (const double *)nullptr, mcl::kRedBlocks, h->d_scalars);
+    if (fold) h->sums_pending = false;
+    const size_t nlead = (size_t)((n + 15) >> mcl::kLeaderShift) + 1;
+    if (nlead > h->leaders_capacity) {
+        graph_reset(h);                    // a captured update graph holds the old pointer
+        dfree(h->d_leaders);
+        HIPCHK(h, hipMalloc(&h->d_leaders, nlead * 8));
+        h->leaders_capacity = nlead;
+    }
+    if (h->bind_sensor_event && own && !h->capturing) {          // the update's last kernel: EV_SENSOR is its stop event
+        hipExtLaunchKernelGGL(mcl::k_scan_final, dim3(nb), dim3(mcl::kScanThreads), 0, h->stream, nullptr, h->ev[EV_SENSOR], 0, d_q, n, h->d_blocktot, d_cdf,
+                              h->d_leaders, co);
+        h->ev_sensor_bound = true; h->bind_sensor_event = false;
+    } else {
+        hipLaunchKernelGGL(mcl::k_scan_final, dim3(nb), dim3(mcl::kScanThreads), 0, h->stream, d_q, n, h->d_blocktot, d_cdf, h->d_leaders, co);
+    }
+    HIPCHK(h, hipGetLastError());
+    h->blocktot_for = d_cdf; h->blocktot_n = n;
+    if (d_cdf == h->d_cdf) { h->compact_n = -1; h->compact_pending = own; h->list_epoch++; }
+    return MCL_OK;
+}
+
+void mcl_host::unpack_result(mcl_engine *h)
+{
+    std::memcpy(h->h_scalars, h->h_result, 8 * sizeof(double));
+    std::memcpy(h->h_counters, h->h_result + 8, 4 * sizeof(unsigned long long));
+    h->h_fix_count = h->h_result[12];
+    uint64_t qt;
+    std::memcpy(&qt, &h->h_scalars[2], 8);
+    h->q_total = qt;
+    h->global_sums[0] = h->h_scalars[1];
+    h->global_sums[1] = h->h_scalars[3];
+    h->global_sums[2] = h->h_scalars[4];
+    h->global_sums[3] = h->h_scalars[5];
+    h->global_sums[4] = h->h_scalars[6];
+    // length of the compact list the scan of this update's weights wrote (word 16); unusable when it outgrew its arrays
+    if (h->compact_pending) {
+        const unsigned long long na = h->h_result[16];
+        h->compact_n = na <= (unsigned long long)h->compact_cap ? (int64_t)na : -1;       // 0: a valid, empty list (no weight here)
+        h->compact_pending = false;
+    }
+}
 
 int mcl_abi_version(void) { return MCL_ABI_VERSION; }
-
-void mcl_default_config(mcl_config_t *c)
-{
-    if (!c) return;
-    std::memset(c, 0, sizeof(*c));
-    c->max_particles = 2000;       // cpp:24, yaml:6
-    c->device = 0;
-    c->seed = 0;
-    c->max_range_m = 12.0;         // cpp:27
-    c->z_hit = 0.80; c->z_short = 0.01; c->z_max = 0.07; c->z_rand = 0.12; c->sigma_hit = 8.0;   // cpp:30-34
-    c->squash_factor = 2.2;        // cpp:26
-    c->motion_dispersion_x = 0.05; c->motion_dispersion_y = 0.025; c->motion_dispersion_theta = 0.25;   // cpp:35-37
-    c->resample_mode = MCL_RESAMPLE_MULTINOMIAL;
-    c->weight_mode = MCL_WEIGHT_LOG;
-    c->ray_kernel = MCL_RAYS_AUTO;
-}
 
 const char *mcl_last_error(const mcl_engine_t *h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
@@ -1739,9 +1366,28 @@ int mcl_set_beam_angles(mcl_engine_t *h, const float *angles, int32_t n_beams)
     return MCL_OK;
 }
 
+// The particles in the current buffer and the weights in d_w are a new set of n (set from outside or initialised): its fixed-point
+// weights, sums and CDF (d_max_override: the weight to scale by, on the device), and everything kept about the old set is dropped.
+static int adopt_particle_set(mcl_engine *h, int64_t n, const double *d_max_override)
+{
+    int rc = weight_stats(h, false, d_max_override, true);
+    if (!rc) rc = scan_weights(h, h->d_q, h->d_cdf, n, 0, nullptr);
+    if (!rc) rc = fetch_scalars(h);
+    if (rc) return rc;
+    h->have_particles = true;
+    h->far_fresh = true;
+    h->pack_valid[0] = h->pack_valid[1] = false;
+    h->have_idx = h->have_steps = h->have_logw = false;
+    comm_forget(h->comm);                   // a sharded set: the other shards' lists are unknown again
+    h->stage_kept = false;
+    kld_reset(h);
+    recov_unset(h);
+    return MCL_OK;
+}
+
 // weight_scale: the weight the fixed-point values are scaled by (null: this call's own maximum).  A shard of a larger set
 // must use the maximum over the WHOLE set, or the shards' fixed-point weights are not comparable.
-static int set_particles_impl(mcl_engine_t *h, const double *xyz, const double *weights, int64_t n, const double *weight_scale)
+int mcl_host::set_particles_impl(mcl_engine_t *h, const double *xyz, const double *weights, int64_t n, const double *weight_scale)
 {
     if (h) graph_reset(h);
     if (!h) return MCL_ERR_INVALID_ARG;
@@ -1760,21 +1406,7 @@ static int set_particles_impl(mcl_engine_t *h, const double *xyz, const double *
         std::memcpy(&h->h_result[kResultStage], weight_scale, sizeof(double));        // pinned: stays valid until the copy has run
         HIPCHK(h, hipMemcpyAsync(h->d_scalars, &h->h_result[kResultStage], sizeof(double), hipMemcpyHostToDevice, h->stream));
     }
-    int rc = weight_stats(h, false, weight_scale ? h->d_scalars : nullptr, true);
-    if (rc) return rc;
-    rc = scan_weights(h, h->d_q, h->d_cdf, n, 0, nullptr);
-    if (rc) return rc;
-    rc = fetch_scalars(h);
-    if (rc) return rc;
-    h->have_particles = true;
-    h->far_fresh = true;
-    h->pack_valid[0] = h->pack_valid[1] = false;
-    h->have_idx = h->have_steps = h->have_logw = false;
-    comm_forget(h->comm);                   // a sharded set: the other shards' lists are unknown again
-    h->stage_kept = false;
-    kld_reset(h);
-    recov_unset(h);
-    return MCL_OK;
+    return adopt_particle_set(h, n, weight_scale ? h->d_scalars : nullptr);
 }
 
 int mcl_set_particles(mcl_engine_t *h, const double *xyz, const double *weights, int64_t n)
@@ -1794,22 +1426,9 @@ static int finish_init(mcl_engine *h, int64_t n, int64_t n_total)
     h->N = n;
     hipLaunchKernelGGL(mcl::k_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d_w, n, 1.0 / (double)n_total);
     HIPCHK(h, hipGetLastError());
-    int rc = weight_stats(h, false, nullptr, true);
-    if (rc) return rc;
-    rc = scan_weights(h, h->d_q, h->d_cdf, n, 0, nullptr);
-    if (rc) return rc;
-    rc = fetch_scalars(h);
-    if (rc) return rc;
-    h->have_particles = true;
-    h->far_fresh = true;
-    h->pack_valid[0] = h->pack_valid[1] = false;
-    h->have_idx = h->have_steps = h->have_logw = false;
-    comm_forget(h->comm);                   // a sharded set: the other shards' lists are unknown again
-    h->stage_kept = false;
-    h->init_idx++;
-    kld_reset(h);
-    recov_unset(h);
-    return MCL_OK;
+    const int rc = adopt_particle_set(h, n, nullptr);
+    if (rc == MCL_OK) h->init_idx++;
+    return rc;
 }
 
 int mcl_init_particles_pose(mcl_engine_t *h, const double pose[3], int64_t n, int64_t first_global_index, int64_t n_total)
@@ -1908,6 +1527,22 @@ int mcl_particle_mean(mcl_engine_t *h, double out[3])
     return MCL_OK;
 }
 
+// The fields of ResampleArgs that mcl_update and the staged resample fill alike: the CDF and the spine of the scan that produced it,
+// mode, seed, the systematic offset of this update, the reference model's dispersions, the children's columns in the other buffer.
+static void resample_common_args(const mcl_engine *h, mcl::ResampleArgs &a, const uint64_t *d_cdf, int64_t n_parents)
+{
+    a.cdf = d_cdf; a.n_parents = n_parents;
+    a.tile_excl = (d_cdf && h->blocktot_for == d_cdf && h->blocktot_n == n_parents) ? h->d_blocktot : nullptr;   // spine of the scan that produced d_cdf
+    a.leaders = a.tile_excl ? h->d_leaders : nullptr;
+    a.mode = h->cfg.resample_mode;
+    a.seed_lo = (uint32_t)h->cfg.seed; a.seed_hi = (uint32_t)(h->cfg.seed >> 32);
+    a.update_idx = h->update_idx;
+    a.k0 = a.mode == MCL_RESAMPLE_SYSTEMATIC ? systematic_offset(a.seed_lo, a.seed_hi, h->update_idx) : 0;
+    a.disp_x = h->cfg.motion_dispersion_x; a.disp_y = h->cfg.motion_dispersion_y; a.disp_th = h->cfg.motion_dispersion_theta;
+    const int nx = h->cur ^ 1;
+    a.cx = h->d_x[nx]; a.cy = h->d_y[nx]; a.cth = h->d_th[nx];
+    a.do_motion = 1;
+}
 
 // What the resampling kernel does for the ray stage that follows it in the same update (mcl_update and the staged flow alike):
 // the per-particle constants come out of it (k_rays_skip: one launch less per small update; k_rays_cell / k_rays_sweep: also the
@@ -1923,8 +1558,7 @@ static void resample_ray_extras(mcl_engine *h, int64_t n, mcl::ResampleArgs &a, 
     // The ordering of the ray stage works from the layout (bounding box, occupied tiles) of the PREVIOUS update's children
     // when there is one: the set moves by a cell or so per update and the order only decides which rays share a wave.
     // Radix ordering: this kernel then writes the (key, index) pairs too and the sort starts right after it.
-    const int ntx_abs = ((h->Wp * mcl::kSortSub - 1) >> 5) + 1, nty_abs = ((h->Hp * mcl::kSortSub - 1) >> 5) + 1;
-    const bool tiles_ok = (int64_t)ntx_abs * nty_abs <= mcl::kSortMaxTiles;
+    const auto [ntx_abs, nty_abs, tiles_ok] = sort_tiles(h);
     // (not for children injected anywhere on the map: fresh_children, an update of recovery injection -- DESIGN.md §4.9)
     if (rmode >= 4 && h->layout_valid && h->layout_n == n && !h->env_no_stale_layout && !fresh_children) {
         h->layout_stale_used = true;
@@ -1961,8 +1595,7 @@ static int next_layout_launch(mcl_engine *h, int64_t n)
 {
     if (!h->layout_wanted) return MCL_OK;
     h->layout_wanted = false;
-    const int ntx_abs = ((h->Wp * mcl::kSortSub - 1) >> 5) + 1, nty_abs = ((h->Hp * mcl::kSortSub - 1) >> 5) + 1;
-    const bool tiles_ok = (int64_t)ntx_abs * nty_abs <= mcl::kSortMaxTiles;
+    const auto [ntx_abs, nty_abs, tiles_ok] = sort_tiles(h);
     const int bstride = n >= (1 << 20) ? 16 : 1;
     // (the layout of the NEXT update, made beside this one's ray stage: whether that update takes the hybrid form is not known
     //  yet -- its units are cut for the hybrid's windows, which costs the global-field form nothing but shorter runs)
@@ -1980,7 +1613,7 @@ static int next_layout_launch(mcl_engine *h, int64_t n)
 }
 
 // End of an update: the layout made beside its ray stage becomes the one the next update orders by.
-static int layout_adopt(mcl_engine *h, int64_t n)
+int mcl_host::layout_adopt(mcl_engine *h, int64_t n)
 {
     if (!h->layout_pending) return MCL_OK;
     HIPCHK(h, hipEventSynchronize(h->ev_layout));
@@ -2005,7 +1638,16 @@ static void recov_after(mcl_engine *h, bool injected, bool kept, double prev_sum
     recov_fold(h->recov, h->recov_S, h->recov_F, l);
 }
 
-static bool odo_args_of(const mcl_engine *h, const double action[3], mcl::OdoArgs &o);   // (with mcl_set_motion_model, below)
+// the odometry arguments of an update's resampling kernel; false: the reference model (the kernels and arguments of always)
+static bool odo_args_of(const mcl_engine *h, const double action[3], mcl::OdoArgs &o)
+{
+    if (h->motion.model == MCL_MOTION_REFERENCE || !action) return false;
+    double s[8];
+    if (mcl_host_motion_scalars(&h->motion, action, s) != MCL_OK) return false;
+    o.model = h->motion.model; o.pad = 0;
+    for (int i = 0; i < 6; ++i) o.s[i] = s[i];
+    return true;
+}
 
 // The resampling kernel of an update: one of eight entry points, [odometry model][KLD][recovery]; the arguments follow
 // ResampleArgs in that order of the ones that are present (kld, rec, odo: null = absent).  timed: EV_RESAMPLE is the kernel's
@@ -2033,294 +1675,258 @@ static void launch_resample(mcl_engine *h, dim3 grid, size_t lds, bool timed, mc
     }
 }
 
-static int do_update(mcl_engine_t *h, const double action[3], const float *obs, int32_t n_beams, const double *normals,
-                     const double *uniforms, bool resample_and_move, int obs_stride = 1)
+// One mcl_update / mcl_sensor_update, on do_update's stack: the call, what plan_update decided about it, what the resampling launch left
+struct Update {
+    const double *action; const float *obs; int obs_stride; const double *uniforms; bool resample_and_move;
+    std::chrono::steady_clock::time_point t0;
+    int64_t n_par, n;                   // parents; children: every stage after the resampling kernel runs on them
+    bool kld, keep, rec;                // KLD sizes this draw | adaptive resampling keeps the set | the injecting kernel runs
+    uint64_t rec_thr; double prev_sum_w;
+    bool tiny, graph_ok;                // the tail: one workgroup | the captured graph | (neither) launch by launch
+    mcl::KldArgs kld_cur; bool obs_early;   // (resampling launch) the bins the tiny tail clears | the scan's tables are built on the second stream
+};
+
+// Phase 1: what this update is -- sizes, keep, recovery, and which of the three tails it takes.  Nothing is submitted here.
+static int plan_update(mcl_engine *h, Update &u)
 {
-    if (!h) return MCL_ERR_INVALID_ARG;
-    h->set_epoch++;                         // (the labels of a clustering are void from here on)
-    if (!ready(h, true)) return fail(h, MCL_ERR_NOT_READY, "map, beam angles and particles must be set first");
-    if (!obs || n_beams != h->B || (resample_and_move && !action)) return fail(h, MCL_ERR_INVALID_ARG, "bad action/observation");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    auto t0 = std::chrono::steady_clock::now();
     // parents and children: the same number unless KLD sampling (mcl_set_kld) decided another size for this update's draw
-    const int64_t n_par = h->N;
-    const bool kld = resample_and_move && h->kld_on;
-    int64_t n = kld ? h->kld_n_next : n_par;     // children: every stage after the resampling kernel runs on them
-    if (kld && (n < 1 || n > h->cap)) return fail(h, MCL_ERR_INVALID_ARG, "KLD: particle count out of range");
+    u.n_par = h->N;
+    u.kld = u.resample_and_move && h->kld_on;
+    u.n = u.kld ? h->kld_n_next : u.n_par;
+    if (u.kld && (u.n < 1 || u.n > h->cap)) return fail(h, MCL_ERR_INVALID_ARG, "KLD: particle count out of range");
     // adaptive resampling (off by default): keep the particles when the previous update left an effective sample
     // size (sum w)^2 / sum w^2 of at least r * N; their weights then multiply, i.e. the log-weights add
     // (with KLD on only while the next size is the current one: a kept set cannot change its size)
-    bool keep = false;
-    if (resample_and_move && h->cfg.resample_neff_permille > 0 && h->carry_valid && !uniforms && n == n_par) {
+    if (u.resample_and_move && h->cfg.resample_neff_permille > 0 && h->carry_valid && !u.uniforms && u.n == u.n_par) {
         const double sw = h->h_scalars[1], sww = h->h_scalars[7];
-        keep = sww > 0.0 && sw * sw >= ((double)h->cfg.resample_neff_permille / 1000.0) * (double)n * sww;
+        u.keep = sww > 0.0 && sw * sw >= ((double)h->cfg.resample_neff_permille / 1000.0) * (double)u.n * sww;
     }
     if (h->cfg.resample_neff_permille > 0 && h->cfg.weight_mode == MCL_WEIGHT_PRODUCT)
         return fail(h, MCL_ERR_UNSUPPORTED, "resample_neff_permille needs weight_mode LOG");
     // recovery (mcl_set_recovery, off by default): a resampling update whose threshold is > 0 runs the injecting kernel
-    const double prev_sum_w = h->h_scalars[1];
-    const uint64_t rec_thr = (h->recov_on && resample_and_move && !keep) ? recov_threshold(recov_p(h->recov_S, h->recov_F)) : 0;
-    const bool rec = rec_thr > 0;
-    if (rec && h->n_free == 0) return fail(h, MCL_ERR_NOT_READY, "recovery: the map has no free cell to inject particles into");
-    const double *d_norm = nullptr, *d_uni = nullptr;
-    if (resample_and_move) {
-        if (normals) {
-            HIPCHK(h, hipMemcpyAsync(h->d_inject, normals, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            d_norm = h->d_inject;
+    u.prev_sum_w = h->h_scalars[1];
+    u.rec_thr = (h->recov_on && u.resample_and_move && !u.keep) ? recov_threshold(recov_p(h->recov_S, h->recov_F)) : 0;
+    u.rec = u.rec_thr > 0;
+    if (u.rec && h->n_free == 0) return fail(h, MCL_ERR_NOT_READY, "recovery: the map has no free cell to inject particles into");
+    // Small updates are launch-bound (about twenty launches for ~0.06 ms of kernels): once a regular update has run with these sizes
+    // (graph_warm: every buffer exists) on the k_rays_skip path, one of two short tails takes its place.  Eligibility is a pure function
+    // of the configuration and the sizes (choose_ray_mode), never of what the previous update happened to run: k_rays_skip chosen
+    // outright has no work lists, no allocation and no fallback.  (Neither a likelihood-field update -- DESIGN.md §4.10 -- nor one that
+    // changes the size of the set, which do_update treats as a set from outside, takes them.)
+    const bool small = u.resample_and_move && !h->lf_on && h->cfg.graph_mode != 1 && h->graph_warm && u.n == u.n_par && !u.keep &&
+                       h->cfg.weight_mode == MCL_WEIGHT_LOG && h->cfg.resample_neff_permille == 0 && choose_ray_mode(h, u.n, false) == 2;
+    // tiny: three launches and no copy: resampling + motion + per-particle constants + table rows of the scan | rays against the static
+    // table | weights, sums, CDF and the result block written straight to pinned host memory, all in one workgroup
+    u.tiny = small && u.n <= mcl::kTinyTailMax;
+    // graph: everything after the resampling kernel is one hipGraph per particle buffer (observation upload ... result read-back)
+    u.graph_ok = small && !u.tiny && !h->cfg.debug_count_probes;
+    return MCL_OK;
+}
+
+// Phase 2: the resampling kernel (+ motion) of an update, and what is submitted right behind it.
+static int launch_update_resample(mcl_engine *h, Update &u, const double *d_norm, const double *d_uni)
+{
+    const int64_t n = u.n, n_par = u.n_par;
+    const int c = h->cur, nx = c ^ 1;
+    mcl::ResampleArgs a{};
+    a.px = h->d_x[c]; a.py = h->d_y[c]; a.pth = h->d_th[c]; a.q_total = h->q_total;
+    resample_common_args(h, a, h->d_cdf, n_par);
+    // parents: the compact list the last scan left (the particles that carry weight: a few per cent after an update
+    // with many beams) when it exists, else the full CDF and the packed records
+    const bool compact = !u.keep && h->compact_n > 0;
+    if (compact) {
+        a.ccdf = h->d_ccdf; a.ctop = h->d_ctop; a.n_compact = h->compact_n; a.cidx = h->d_cidx; a.crec = h->d_crec;
+        a.cpack = nullptr;               // the next update most likely draws from a compact list again: no record per child
+    } else {
+        if (!h->pack_valid[c] && n_par > 65536 && !u.keep) {   // records first: one fetch per gathered parent instead of three
+            hipLaunchKernelGGL(mcl::k_pack_records, dim3((unsigned)((n_par + 255) / 256)), dim3(256), 0, h->stream, h->d_x[c], h->d_y[c], h->d_th[c], n_par, h->d_pack[c]);
+            h->pack_valid[c] = true;
         }
-        if (uniforms) {
-            HIPCHK(h, hipMemcpyAsync(h->d_inject + (size_t)3 * h->cap, uniforms, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            d_uni = h->d_inject + (size_t)3 * h->cap;
+        a.ppack = h->pack_valid[c] ? h->d_pack[c] : nullptr;
+        a.cpack = h->d_pack[nx];
+    }
+    a.idx_out = h->d_idx;
+    a.n_children = n; a.child_first = 0; a.n_children_total = n;
+    a.uniforms = d_uni; a.normals = d_norm;
+    if (a.mode == MCL_RESAMPLE_SYSTEMATIC && u.uniforms)
+        a.k0 = (uint32_t)(std::min(std::max(u.uniforms[0], 0.0), 0.99999999976716936) * 4294967296.0);
+    motion_scalars(u.action, a.dt, a.v, a.w);
+    a.do_resample = u.keep ? 0 : 1;
+    a.clear_counters = h->d_counters;
+    if (u.tiny) {
+        // the scan goes from the pinned staging buffer to table rows inside this kernel (no copy node, no table build)
+        stage_observation(h, u.obs, u.obs_stride);
+        a.obs_src = h->h_obs; a.obs_idx_out = h->d_obs_idx; a.obs_B = h->B; a.obs_P = h->P; a.res = h->res;
+    }
+    if (!h->lf_on) resample_ray_extras(h, n, a, u.rec);
+    size_t cdf_lds = 0;
+    if (!a.tile_excl && a.do_resample && n_par <= mcl::kTinyTailMax) { a.cdf_lds_entries = (int)n_par; cdf_lds = (size_t)n_par * sizeof(uint64_t); }
+    h->ev_resample_bound = false;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    mcl::RecArgs rec_args{};
+    if (u.rec) {
+        rec_args.thr = u.rec_thr; rec_args.free_cells = h->d_free; rec_args.n_free = h->n_free; rec_args.W = h->W;
+        rec_args.res = h->res; rec_args.ox = h->ox; rec_args.oy = h->oy;
+        rec_args.count = h->d_recov_cnt + h->recov_parity; rec_args.count_next = h->d_recov_cnt + (h->recov_parity ^ 1);
+        h->recov_cnt_slot = h->recov_parity; h->recov_injected = -1;
+        h->recov_parity ^= 1;
+    }
+    if (u.kld) {
+        // the bins of the drawn parents are marked by the resampling kernel; the words it set are cleared and the count
+        // lands in word 17 of the result block -- by the one-workgroup tail of a small update, else by one launch right here
+        u.kld_cur = kld_args_of(&h->kld, h->kld_nx, h->kld_ny, h->ox, h->oy);
+        u.kld_cur.bm = h->d_kld_bm; u.kld_cur.list = h->d_kld_list;
+        u.kld_cur.count = h->d_kld_cnt + h->kld_parity; u.kld_cur.count_next = h->d_kld_cnt + (h->kld_parity ^ 1);
+        u.kld_cur.result = h->d_result + 17;
+        h->kld_parity ^= 1;
+    }
+    // (the motion model's scalars are plain arguments of this launch, which is outside the captured graph and the tail)
+    mcl::OdoArgs odo_cur{};
+    const bool odo = odo_args_of(h, u.action, odo_cur);
+    launch_resample(h, grid, cdf_lds, !u.tiny && !h->capturing, a, u.kld ? &u.kld_cur : nullptr, u.rec ? &rec_args : nullptr, odo ? &odo_cur : nullptr);
+    if (u.kld && !u.tiny) {
+        const int64_t most = std::min<int64_t>(n, (int64_t)h->kld_bits);
+        hipLaunchKernelGGL(mcl::k_kld_clear, dim3((unsigned)std::min<int64_t>((most + 255) / 256, 1024)), dim3(256), 0, h->stream, u.kld_cur);
+    }
+    HIPCHK(h, hipGetLastError());
+    h->N = n;                          // the children: the ray stage and everything after it run on them
+    if (a.pc_out) { const int rc_l = layout_mark(h, n); if (rc_l) return rc_l; }
+    // The tables of this update's scan (table rows of the observed ranges, Lt, Ltd) depend on nothing the resampling and ordering
+    // kernels produce: with a windowed ray kernel they are built on a second stream beside those, and the ray stage waits for
+    // them (a copy and two or three small launches off the critical path of an update: ~15 us).  Enqueued AFTER the resampling
+    // kernel: that one is on the critical path, and a small update is bound by the order the host submits in.
+    if (!u.tiny && !h->lf_on && !h->env_no_obs_overlap && choose_ray_mode(h, n, false) >= 3) {
+        std::swap(h->stream, h->stream2);
+        const int rc_obs = prepare_observation(h, u.obs, u.obs_stride);
+        hipError_t ee = rc_obs ? hipSuccess : hipEventRecord(h->ev_obs, h->stream);
+        std::swap(h->stream, h->stream2);
+        if (rc_obs) return rc_obs;
+        HIPCHK(h, ee);
+        u.obs_early = true;
+    }
+    h->cur = nx;                       // cpp:689 as a pointer swap
+    h->resampled_last = !u.keep;
+    h->pack_valid[nx] = a.cpack != nullptr;
+    h->compact_used = compact;
+    h->have_idx = true;
+    return MCL_OK;
+}
+
+// Phase 3, the one-workgroup tail of a small update: rays against the static table, then weights, sums, CDF and result in one launch.
+static int tail_tiny(mcl_engine *h, const Update &u)
+{
+    int rc = launch_rays(h, h->d_x[h->cur], h->d_y[h->cur], h->d_th[h->cur], u.n, false, true);
+    if (!rc) rc = weights_and_cdf(h, true, u.kld ? &u.kld_cur : nullptr);
+    if (rc) return rc;
+    // The result block lands in pinned memory stamped with this update's sequence number: spin on the stamp instead of
+    // the stream's completion signal (the signal's path through the runtime costs several microseconds at this size).
+    // Everything later on this engine is ordered behind the kernels by the stream; a stamp that never comes (a faulted
+    // kernel) ends in the ordinary synchronisation, which reports the error.
+    bool seen = false;
+    if (h->env_tiny_poll) {
+        const volatile unsigned long long *stamp = h->h_result + kResultStamp;
+        const auto give_up = u.t0 + std::chrono::milliseconds(20);
+        for (unsigned spin = 0; !seen; ++spin) {
+            seen = __atomic_load_n(stamp, __ATOMIC_ACQUIRE) == h->result_seq;
+            if (!seen && (spin & 1023u) == 1023u && std::chrono::steady_clock::now() > give_up) break;
         }
     }
-    if (!resample_and_move) HIPCHK(h, hipMemsetAsync(h->d_counters, 0, 4 * sizeof(unsigned long long), h->stream));   // else: the resampling kernel
-    if (n != n_par) {
-        // another size: nothing made for the old one is reused (captured graphs, the warm small-update paths, the previous
-        // update's ordering layout, the cleared-word cache), as when the particles are set from outside
-        graph_reset(h);
-        h->far_fresh = true;
-    }
-    if (rec) h->far_fresh = true;          // injected children anywhere on the map: the ray stage plans as for a set from outside
-    h->recov_cnt_slot = -1; h->recov_injected = 0;
+    if (!seen) HIPCHK(h, hipStreamSynchronize(h->stream));
+    unpack_result(h);
+    // one unit, reported as the ray-cast stage (resampling, query prep and the tail are inside it), so that the six
+    // stages still add up to the total the host uses for delay compensation: finish_update fills in [3] = [5]
+    h->timings[0] = 0.0; h->timings[1] = 0.0; h->timings[2] = 0.0; h->timings[4] = 0.0;
+    h->ray_ms_is_graph_tail = true;
+    return MCL_OK;
+}
+
+// The captured tail of this particle buffer exists (captured here on its first use); the scan is staged for it.  false: this
+// update -- and, after a failed capture, every later one of this engine -- runs launch by launch.
+static bool graph_ready(mcl_engine *h, const Update &u)
+{
+    stage_observation(h, u.obs, u.obs_stride);
+    const int gi = h->cur;
+    if (h->graph_exec[gi]) return true;
+    // nothing executes during capture, so a failure here simply falls back to the launch-by-launch path
+    hipGraph_t graph = nullptr;
+    if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return false;
+    h->capturing = true;
+    int rc = upload_observation(h);
+    if (!rc) rc = launch_rays(h, h->d_x[gi], h->d_y[gi], h->d_th[gi], u.n);
+    if (!rc) rc = weights_and_cdf(h);
+    hipError_t ce = hipSuccess;
+    if (!rc) ce = hipMemcpyAsync(h->h_result, h->d_result, kResultWords * 8, hipMemcpyDeviceToHost, h->stream);
+    h->capturing = false;
+    const hipError_t ee = hipStreamEndCapture(h->stream, &graph);
+    hipError_t ie = hipErrorUnknown;
+    if (!rc && ce == hipSuccess && ee == hipSuccess && graph && h->last_mode == 2)
+        ie = hipGraphInstantiate(&h->graph_exec[gi], graph, nullptr, nullptr, 0);
+    if (graph) (void)hipGraphDestroy(graph);
+    if (ie == hipSuccess) return true;
+    h->graph_exec[gi] = nullptr;
+    graph_reset(h);
+    (void)hipGetLastError();
+    h->cfg.graph_mode = 1;          // do not try again on this engine
+    return false;
+}
+
+// Phase 3, the captured tail: one graph launch and one wait.
+static int tail_graph(mcl_engine *h, const Update &u)
+{
+    HIPCHK(h, hipGraphLaunch(h->graph_exec[h->cur], h->stream));
     h->pc_ready = false;
-    h->layout_stale_used = false; h->keys_done = false;      // (set below when this update orders by the previous update's layout)
-    // A small update (k_rays_skip, the whole tail in one workgroup) is three launches and no copy: resampling + motion +
-    // per-particle constants + table rows of the scan | rays against the static table | weights, sums, CDF and the result
-    // block written straight to pinned host memory.  Every buffer exists once a regular update has run (graph_warm).
-    // (a likelihood-field update -- DESIGN.md §4.10 -- takes neither this nor the captured graph: its tail runs launch by launch)
-    const bool tiny = resample_and_move && !h->lf_on && h->cfg.graph_mode != 1 && h->graph_warm && n <= mcl::kTinyTailMax && !keep &&
-                      choose_ray_mode(h, n, false) == 2 && h->cfg.weight_mode == MCL_WEIGHT_LOG && h->cfg.resample_neff_permille == 0;
-    if (!tiny) HIPCHK(h, hipEventRecord(h->ev[EV_START], h->stream));
-    bool obs_early = false;
-    mcl::KldArgs kld_cur{};
-    if (resample_and_move) {
-        const int c = h->cur, nx = c ^ 1;
-        mcl::ResampleArgs a{};
-        a.px = h->d_x[c]; a.py = h->d_y[c]; a.pth = h->d_th[c];
-        a.cdf = h->d_cdf; a.n_parents = n_par; a.q_total = h->q_total;
-        a.tile_excl = (h->blocktot_for == h->d_cdf && h->blocktot_n == n_par) ? h->d_blocktot : nullptr;   // spine of the scan that produced d_cdf
-        a.leaders = a.tile_excl ? h->d_leaders : nullptr;
-        // parents: the compact list the last scan left (the particles that carry weight: a few per cent after an update
-        // with many beams) when it exists, else the full CDF and the packed records
-        const bool compact = !keep && h->compact_n > 0;
-        if (compact) {
-            a.ccdf = h->d_ccdf; a.ctop = h->d_ctop; a.n_compact = h->compact_n; a.cidx = h->d_cidx; a.crec = h->d_crec;
-            a.cpack = nullptr;               // the next update most likely draws from a compact list again: no record per child
-        } else {
-            if (!h->pack_valid[c] && n_par > 65536 && !keep) {   // records first: one fetch per gathered parent instead of three
-                hipLaunchKernelGGL(mcl::k_pack_records, dim3((unsigned)((n_par + 255) / 256)), dim3(256), 0, h->stream, h->d_x[c], h->d_y[c], h->d_th[c], n_par, h->d_pack[c]);
-                h->pack_valid[c] = true;
-            }
-            a.ppack = h->pack_valid[c] ? h->d_pack[c] : nullptr;
-            a.cpack = h->d_pack[nx];
-        }
-        a.cx = h->d_x[nx]; a.cy = h->d_y[nx]; a.cth = h->d_th[nx];
-        a.idx_out = h->d_idx;
-        a.n_children = n; a.child_first = 0; a.n_children_total = n;
-        a.mode = h->cfg.resample_mode;
-        a.uniforms = d_uni; a.normals = d_norm;
-        a.seed_lo = (uint32_t)h->cfg.seed; a.seed_hi = (uint32_t)(h->cfg.seed >> 32);
-        a.update_idx = h->update_idx;
-        a.k0 = 0;
-        if (a.mode == MCL_RESAMPLE_SYSTEMATIC) {
-            // one 32-bit offset per update: Philox stream 3 (host restatement of the same function)
-            uint32_t c0 = 0, c1 = h->update_idx, c2 = 3, c3 = 0, k0 = a.seed_lo, k1 = a.seed_hi;
-            for (int r = 0; r < 10; ++r) {
-                uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-                uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-                c0 = n0; c1 = n1; c2 = n2; c3 = n3; k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-            }
-            a.k0 = c0;
-            if (uniforms) a.k0 = (uint32_t)(std::min(std::max(uniforms[0], 0.0), 0.99999999976716936) * 4294967296.0);
-        }
-        motion_scalars(action, a.dt, a.v, a.w);
-        a.disp_x = h->cfg.motion_dispersion_x; a.disp_y = h->cfg.motion_dispersion_y; a.disp_th = h->cfg.motion_dispersion_theta;
-        a.do_resample = keep ? 0 : 1; a.do_motion = 1;
-        a.clear_counters = h->d_counters;
-        if (tiny) {
-            // the scan goes from the pinned staging buffer to table rows inside this kernel (no copy node, no table build)
-            stage_observation(h, obs, obs_stride);
-            a.obs_src = h->h_obs; a.obs_idx_out = h->d_obs_idx; a.obs_B = h->B; a.obs_P = h->P; a.res = h->res;
-        }
-        if (!h->lf_on) resample_ray_extras(h, n, a, rec);
-        size_t cdf_lds = 0;
-        if (!a.tile_excl && a.do_resample && n_par <= mcl::kTinyTailMax) { a.cdf_lds_entries = (int)n_par; cdf_lds = (size_t)n_par * sizeof(uint64_t); }
-        h->ev_resample_bound = false;
-        const dim3 grid((unsigned)((n + 255) / 256));
-        mcl::RecArgs rec_args{};
-        if (rec) {
-            rec_args.thr = rec_thr; rec_args.free_cells = h->d_free; rec_args.n_free = h->n_free; rec_args.W = h->W;
-            rec_args.res = h->res; rec_args.ox = h->ox; rec_args.oy = h->oy;
-            rec_args.count = h->d_recov_cnt + h->recov_parity; rec_args.count_next = h->d_recov_cnt + (h->recov_parity ^ 1);
-            h->recov_cnt_slot = h->recov_parity; h->recov_injected = -1;
-            h->recov_parity ^= 1;
-        }
-        if (kld) {
-            // the bins of the drawn parents are marked by the resampling kernel; the words it set are cleared and the count
-            // lands in word 17 of the result block -- by the one-workgroup tail of a small update, else by one launch right here
-            kld_cur = kld_args_of(&h->kld, h->kld_nx, h->kld_ny, h->ox, h->oy);
-            kld_cur.bm = h->d_kld_bm; kld_cur.list = h->d_kld_list;
-            kld_cur.count = h->d_kld_cnt + h->kld_parity; kld_cur.count_next = h->d_kld_cnt + (h->kld_parity ^ 1);
-            kld_cur.result = h->d_result + 17;
-            h->kld_parity ^= 1;
-        }
-        // (the motion model's scalars are plain arguments of this launch, which is outside the captured graph and the tail)
-        mcl::OdoArgs odo_cur{};
-        const bool odo = odo_args_of(h, action, odo_cur);
-        launch_resample(h, grid, cdf_lds, !tiny && !h->capturing, a, kld ? &kld_cur : nullptr, rec ? &rec_args : nullptr, odo ? &odo_cur : nullptr);
-        if (kld && !tiny) {
-            const int64_t most = std::min<int64_t>(n, (int64_t)h->kld_bits);
-            hipLaunchKernelGGL(mcl::k_kld_clear, dim3((unsigned)std::min<int64_t>((most + 255) / 256, 1024)), dim3(256), 0, h->stream, kld_cur);
-        }
-        HIPCHK(h, hipGetLastError());
-        h->N = n;                          // the children: the ray stage and everything after it run on them
-        if (a.pc_out) { const int rc_l = layout_mark(h, n); if (rc_l) return rc_l; }
-        // The tables of this update's scan (table rows of the observed ranges, Lt, Ltd) depend on nothing the resampling and ordering
-        // kernels produce: with a windowed ray kernel they are built on a second stream beside those, and the ray stage waits for
-        // them (a copy and two or three small launches off the critical path of an update: ~15 us).  Enqueued AFTER the resampling
-        // kernel: that one is on the critical path, and a small update is bound by the order the host submits in.
-        if (!tiny && !h->lf_on && !h->env_no_obs_overlap && choose_ray_mode(h, n, false) >= 3) {
-            std::swap(h->stream, h->stream2);
-            const int rc_obs = prepare_observation(h, obs, obs_stride);
-            hipError_t ee = rc_obs ? hipSuccess : hipEventRecord(h->ev_obs, h->stream);
-            std::swap(h->stream, h->stream2);
-            if (rc_obs) return rc_obs;
-            HIPCHK(h, ee);
-            obs_early = true;
-        }
-        h->cur = nx;                       // cpp:689 as a pointer swap
-        h->resampled_last = !keep;
-        h->pack_valid[nx] = a.cpack != nullptr;
-        h->compact_used = compact;
-        h->have_idx = true;
-    }
+    HIPCHK(h, hipEventRecord(h->ev[EV_SENSOR], h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->compact_pending = h->d_ccdf != nullptr && !h->env_no_compact && u.n > mcl::kTinyTailMax;   // the captured scan wrote a list
+    unpack_result(h);
+    h->carry_pending = false;
+    // the captured tail is one unit: its time is reported as the ray-cast stage (query prep and table evaluation
+    // are inside it), so that the six stages still add up to the total the host uses for delay compensation
+    h->timings[0] = elapsed(h->ev[EV_START], h->ev[EV_RESAMPLE]);
+    h->timings[1] = 0.0; h->timings[2] = 0.0; h->timings[4] = 0.0;
+    h->timings[3] = elapsed(h->ev[EV_RESAMPLE], h->ev[EV_SENSOR]);      // the graph as a whole
+    h->ray_ms_is_graph_tail = true;
+    return MCL_OK;
+}
+
+// adaptive resampling kept the set: the previous update's log-weights (minus their maximum) add to this one's
+static void add_carry(mcl_engine *h, int64_t n)
+{
+    hipLaunchKernelGGL(mcl::k_add_carry, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d_logw, h->d_carry[h->carry_idx], n);
+    h->max_partials_ready = false;
+}
+
+// Phase 3, launch by launch: every regular update, and the first of a configuration (which leaves graph_warm).
+static int tail_launches(mcl_engine *h, const Update &u)
+{
     int rc;
-    if (tiny) {
-        rc = launch_rays(h, h->d_x[h->cur], h->d_y[h->cur], h->d_th[h->cur], n, false, true);
-        if (!rc) rc = weights_and_cdf(h, true, kld ? &kld_cur : nullptr);
-        if (rc) return rc;
-        // The result block lands in pinned memory stamped with this update's sequence number: spin on the stamp instead of
-        // the stream's completion signal (the signal's path through the runtime costs several microseconds at this size).
-        // Everything later on this engine is ordered behind the kernels by the stream; a stamp that never comes (a faulted
-        // kernel) ends in the ordinary synchronisation, which reports the error.
-        bool seen = false;
-        if (h->env_tiny_poll) {
-            const volatile unsigned long long *stamp = h->h_result + kResultStamp;
-            const auto give_up = t0 + std::chrono::milliseconds(20);
-            for (unsigned spin = 0; !seen; ++spin) {
-                seen = __atomic_load_n(stamp, __ATOMIC_ACQUIRE) == h->result_seq;
-                if (!seen && (spin & 1023u) == 1023u && std::chrono::steady_clock::now() > give_up) break;
-            }
-        }
-        if (!seen) HIPCHK(h, hipStreamSynchronize(h->stream));
-        unpack_result(h);
-        if (kld) kld_decide(h, keep);
-        recov_after(h, rec, keep, prev_sum_w, n);
-        h->have_logw = true;
-        h->have_steps = h->cfg.keep_ray_steps != 0;
-        h->update_idx++;
-        // one unit, reported as the ray-cast stage (resampling, query prep and the tail are inside it), so that the six
-        // stages still add up to the total the host uses for delay compensation
-        h->timings[0] = 0.0; h->timings[1] = 0.0; h->timings[2] = 0.0; h->timings[4] = 0.0;
-        h->timings[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        h->timings[3] = h->timings[5];
-        h->ray_ms = h->timings[3];
-        h->ray_ms_is_graph_tail = true;
-        return MCL_OK;
-    }
-    if (!(resample_and_move && h->ev_resample_bound)) HIPCHK(h, hipEventRecord(h->ev[EV_RESAMPLE], h->stream));
-    // Small updates are launch-bound (about twenty launches for ~0.06 ms of kernels): once a regular update has run with
-    // these sizes on the k_rays_skip path, everything after the resampling kernel is replayed as one hipGraph per
-    // particle buffer (observation upload, table build, rays, weights, CDF, result read-back: all arguments are fixed).
-    // Eligibility is a pure function of the configuration and the sizes (choose_ray_mode), never of what the previous
-    // update happened to run: k_rays_skip chosen outright has no work lists, no allocation and no fallback.
-    bool graph_ok = h->cfg.graph_mode != 1 && !h->lf_on && h->graph_warm && resample_and_move && choose_ray_mode(h, n, false) == 2 && !keep && !h->cfg.debug_count_probes &&
-                    h->cfg.weight_mode == MCL_WEIGHT_LOG && h->cfg.resample_neff_permille == 0;
-    if (graph_ok) {
-        stage_observation(h, obs, obs_stride);
-        const int gi = h->cur;
-        if (!h->graph_exec[gi]) {
-            // nothing executes during capture, so a failure here simply falls back to the launch-by-launch path below
-            hipGraph_t graph = nullptr;
-            if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-                graph_ok = false;
-            } else {
-                h->capturing = true;
-                rc = upload_observation(h);
-                if (!rc) rc = launch_rays(h, h->d_x[gi], h->d_y[gi], h->d_th[gi], n);
-                if (!rc) rc = weights_and_cdf(h);
-                hipError_t ce = hipSuccess;
-                if (!rc) ce = hipMemcpyAsync(h->h_result, h->d_result, kResultWords * 8, hipMemcpyDeviceToHost, h->stream);
-                h->capturing = false;
-                const hipError_t ee = hipStreamEndCapture(h->stream, &graph);
-                hipError_t ie = hipErrorUnknown;
-                if (!rc && ce == hipSuccess && ee == hipSuccess && graph && h->last_mode == 2)
-                    ie = hipGraphInstantiate(&h->graph_exec[gi], graph, nullptr, nullptr, 0);
-                if (graph) (void)hipGraphDestroy(graph);
-                if (ie != hipSuccess) {
-                    h->graph_exec[gi] = nullptr;
-                    graph_reset(h);
-                    (void)hipGetLastError();
-                    h->cfg.graph_mode = 1;          // do not try again on this engine
-                    graph_ok = false;
-                }
-            }
-        }
-    }
-    if (graph_ok) {
-        const int gi = h->cur;
-        HIPCHK(h, hipGraphLaunch(h->graph_exec[gi], h->stream));
-        h->pc_ready = false;
-        HIPCHK(h, hipEventRecord(h->ev[EV_SENSOR], h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        h->compact_pending = h->d_ccdf != nullptr && !h->env_no_compact && n > mcl::kTinyTailMax;   // the captured scan wrote a list
-        unpack_result(h);
-        if (kld) kld_decide(h, keep);
-        recov_after(h, rec, keep, prev_sum_w, n);
-        h->carry_pending = false;
-        h->have_logw = true;
-        h->have_steps = h->cfg.keep_ray_steps != 0;
-        if (resample_and_move) h->update_idx++;
-        // the captured tail is one unit: its time is reported as the ray-cast stage (query prep and table evaluation
-        // are inside it), so that the six stages still add up to the total the host uses for delay compensation
-        h->timings[0] = elapsed(h->ev[EV_START], h->ev[EV_RESAMPLE]);
-        h->timings[1] = 0.0; h->timings[2] = 0.0; h->timings[4] = 0.0;
-        h->timings[3] = elapsed(h->ev[EV_RESAMPLE], h->ev[EV_SENSOR]);      // the graph as a whole
-        h->timings[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        h->ray_ms = h->timings[3];
-        h->ray_ms_is_graph_tail = true;
-        return MCL_OK;
-    }
     h->ray_ms_is_graph_tail = false;
     h->ev_rays_bound = false;
     if (h->lf_on) {
         // the likelihood field: no observation tables, no ordering, no ray stage; k_lfield writes d_logw
         h->ev_query_skipped = false;
-        rc = launch_lfield(h, obs, obs_stride, n);
+        rc = launch_lfield(h, u.obs, u.obs_stride, u.n);
         if (rc) return rc;
     } else {
-        if (obs_early) {
+        if (u.obs_early) {
             // (the ordering kernels of the ray stage do not read the tables either: the stream waits for them where the ray kernel is
             //  launched -- launch_rays --, not here: 13 us of a 262 144-particle update)
             h->obs_wait_pending = true;
         } else {
-            rc = prepare_observation(h, obs, obs_stride);
+            rc = prepare_observation(h, u.obs, u.obs_stride);
             if (rc) return rc;
         }
         // (the tables were made beside the ordering: no query-preparation stage on this stream, nothing to time)
-        h->ev_query_skipped = obs_early;
-        if (!obs_early) HIPCHK(h, hipEventRecord(h->ev[EV_QUERY], h->stream));
-        rc = launch_rays(h, h->d_x[h->cur], h->d_y[h->cur], h->d_th[h->cur], n);
+        h->ev_query_skipped = u.obs_early;
+        if (!u.obs_early) HIPCHK(h, hipEventRecord(h->ev[EV_QUERY], h->stream));
+        rc = launch_rays(h, h->d_x[h->cur], h->d_y[h->cur], h->d_th[h->cur], u.n);
         if (h->obs_wait_pending) { h->obs_wait_pending = false; HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_obs, 0)); }      // (a path that launched no windowed kernel)
         if (rc) return rc;
-        rc = next_layout_launch(h, n);          // (second stream; behind the ray stage in submission order, beside it on the device)
+        rc = next_layout_launch(h, u.n);          // (second stream; behind the ray stage in submission order, beside it on the device)
         if (rc) return rc;
     }
-    if (keep) {
-        hipLaunchKernelGGL(mcl::k_add_carry, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d_logw, h->d_carry[h->carry_idx], n);
-        h->max_partials_ready = false;
-    }
-    if (keep || !h->ev_rays_bound) HIPCHK(h, hipEventRecord(h->ev[EV_RAYS], h->stream));
+    if (u.keep) add_carry(h, u.n);
+    if (u.keep || !h->ev_rays_bound) HIPCHK(h, hipEventRecord(h->ev[EV_RAYS], h->stream));
     h->bind_sensor_event = true; h->ev_sensor_bound = false;
     rc = weights_and_cdf(h);
     h->bind_sensor_event = false;
@@ -2332,32 +1938,78 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
         // more undecided rays than the work list holds (only with debug_force_exact at large sizes or a
         // pathological map): redo the ray stage with the self-contained k_rays_skip
         HIPCHK(h, hipMemsetAsync(h->d_counters, 0, 4 * sizeof(unsigned long long), h->stream));
-        rc = launch_rays(h, h->d_x[h->cur], h->d_y[h->cur], h->d_th[h->cur], n, true);
-        if (rc) return rc;
-        if (keep) {
-            hipLaunchKernelGGL(mcl::k_add_carry, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d_logw, h->d_carry[h->carry_idx], n);
-            h->max_partials_ready = false;
-        }
-        rc = weights_and_cdf(h);
-        if (rc) return rc;
-        rc = fetch_scalars(h);
+        rc = launch_rays(h, h->d_x[h->cur], h->d_y[h->cur], h->d_th[h->cur], u.n, true);
+        if (!rc && u.keep) add_carry(h, u.n);
+        if (!rc) rc = weights_and_cdf(h);
+        if (!rc) rc = fetch_scalars(h);
         if (rc) return rc;
     }
     if (h->carry_pending) { h->carry_idx ^= 1; h->carry_valid = true; h->carry_pending = false; }   // this update's logw - max
-    { const int rc_l = layout_adopt(h, n); if (rc_l) return rc_l; }
-    if (kld) kld_decide(h, keep);
-    recov_after(h, rec, keep, prev_sum_w, n);
+    if ((rc = layout_adopt(h, u.n)) != MCL_OK) return rc;
     h->graph_warm = true;                  // every buffer this configuration needs exists now
-    h->have_logw = true;
-    h->have_steps = h->cfg.keep_ray_steps != 0 && !h->lf_on;
-    if (resample_and_move) h->update_idx++;
     h->timings[0] = elapsed(h->ev[EV_START], h->ev[EV_RESAMPLE]);
     h->timings[1] = 0.0;                   // motion is fused into the resample/gather kernel
     h->timings[2] = h->ev_query_skipped ? 0.0 : elapsed(h->ev[EV_RESAMPLE], h->ev[EV_QUERY]);
     h->timings[3] = elapsed(h->ev[h->ev_query_skipped ? EV_RESAMPLE : EV_QUERY], h->ev[EV_RAYS]);
     h->timings[4] = elapsed(h->ev[EV_RAYS], h->ev[EV_SENSOR]);
-    h->timings[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    h->ray_ms = elapsed(h->ev[EV_K0], h->ev[EV_K1]);
+    return MCL_OK;
+}
+
+// Phase 4: what every tail ends in, once the update's result block has been unpacked.
+static void finish_update(mcl_engine *h, const Update &u)
+{
+    if (u.kld) kld_decide(h, u.keep);
+    recov_after(h, u.rec, u.keep, u.prev_sum_w, u.n);
+    h->have_logw = true;
+    h->have_steps = h->cfg.keep_ray_steps != 0 && !h->lf_on;
+    if (u.resample_and_move) h->update_idx++;
+    h->timings[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u.t0).count();
+    if (u.tiny) h->timings[3] = h->timings[5];
+    h->ray_ms = h->ray_ms_is_graph_tail ? h->timings[3] : elapsed(h->ev[EV_K0], h->ev[EV_K1]);
+}
+
+static int do_update(mcl_engine_t *h, const double action[3], const float *obs, int32_t n_beams, const double *normals,
+                     const double *uniforms, bool resample_and_move, int obs_stride = 1)
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    h->set_epoch++;                         // (the labels of a clustering are void from here on)
+    if (!ready(h, true)) return fail(h, MCL_ERR_NOT_READY, "map, beam angles and particles must be set first");
+    if (!obs || n_beams != h->B || (resample_and_move && !action)) return fail(h, MCL_ERR_INVALID_ARG, "bad action/observation");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    Update u{action, obs, obs_stride, uniforms, resample_and_move, std::chrono::steady_clock::now()};     // (the rest: zero)
+    int rc = plan_update(h, u);
+    if (rc) return rc;
+    const double *d_norm = nullptr, *d_uni = nullptr;
+    if (resample_and_move) {
+        if (normals) {
+            HIPCHK(h, hipMemcpyAsync(h->d_inject, normals, (size_t)u.n * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            d_norm = h->d_inject;
+        }
+        if (uniforms) {
+            HIPCHK(h, hipMemcpyAsync(h->d_inject + (size_t)3 * h->cap, uniforms, (size_t)u.n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            d_uni = h->d_inject + (size_t)3 * h->cap;
+        }
+    }
+    if (!resample_and_move) HIPCHK(h, hipMemsetAsync(h->d_counters, 0, 4 * sizeof(unsigned long long), h->stream));   // else: the resampling kernel
+    if (u.n != u.n_par) {
+        // another size: nothing made for the old one is reused (captured graphs, the warm small-update paths, the previous
+        // update's ordering layout, the cleared-word cache), as when the particles are set from outside
+        graph_reset(h);
+        h->far_fresh = true;
+    }
+    if (u.rec) h->far_fresh = true;        // injected children anywhere on the map: the ray stage plans as for a set from outside
+    h->recov_cnt_slot = -1; h->recov_injected = 0;
+    h->pc_ready = false;
+    h->layout_stale_used = false; h->keys_done = false;      // (set by the resampling launch when this update orders by the previous update's layout)
+    if (!u.tiny) HIPCHK(h, hipEventRecord(h->ev[EV_START], h->stream));
+    if (resample_and_move) {
+        rc = launch_update_resample(h, u, d_norm, d_uni);
+        if (rc) return rc;
+    }
+    if (!u.tiny && !(resample_and_move && h->ev_resample_bound)) HIPCHK(h, hipEventRecord(h->ev[EV_RESAMPLE], h->stream));
+    rc = u.tiny ? tail_tiny(h, u) : (u.graph_ok && graph_ready(h, u)) ? tail_graph(h, u) : tail_launches(h, u);
+    if (rc) return rc;
+    finish_update(h, u);
     return MCL_OK;
 }
 
@@ -2413,13 +2065,14 @@ int mcl_get_resample_indices(mcl_engine_t *h, int32_t *idx, int64_t n)
 
 static int lf_refuse_rays(const mcl_engine_t *h)
 {
+    if (!h->last_lf) return MCL_OK;
     return fail(const_cast<mcl_engine_t *>(h), MCL_ERR_UNSUPPORTED, "the last update used the likelihood field (mcl_set_likelihood_field): it cast no rays");
 }
 
 int mcl_get_ray_steps(mcl_engine_t *h, uint8_t *steps, size_t n)
 {
     if (!h || !steps) return MCL_ERR_INVALID_ARG;
-    if (h->last_lf) return lf_refuse_rays(h);
+    if (const int rc = lf_refuse_rays(h)) return rc;
     if (!h->cfg.keep_ray_steps) return fail(h, MCL_ERR_UNSUPPORTED, "engine created without keep_ray_steps");
     if (h->P > 255) return fail(h, MCL_ERR_UNSUPPORTED, "MAX_RANGE_PX > 255: step indices do not fit bytes, use mcl_get_ray_steps16");
     if (!h->have_steps) return MCL_ERR_NOT_READY;
@@ -2433,7 +2086,7 @@ int mcl_get_ray_steps(mcl_engine_t *h, uint8_t *steps, size_t n)
 int mcl_get_ray_steps16(mcl_engine_t *h, uint16_t *steps, size_t n)
 {
     if (!h || !steps) return MCL_ERR_INVALID_ARG;
-    if (h->last_lf) return lf_refuse_rays(h);
+    if (const int rc = lf_refuse_rays(h)) return rc;
     if (!h->cfg.keep_ray_steps) return fail(h, MCL_ERR_UNSUPPORTED, "engine created without keep_ray_steps");
     if (!h->have_steps) return MCL_ERR_NOT_READY;
     if (n != (size_t)h->N * h->B) return MCL_ERR_INVALID_ARG;
@@ -2494,7 +2147,7 @@ int mcl_get_ray_kernel_ms(const mcl_engine_t *h, double *ms)
 int mcl_get_ray_kernel_id(const mcl_engine_t *h, int32_t *kernel)
 {
     if (!h || !kernel) return MCL_ERR_INVALID_ARG;
-    if (h->last_lf) return lf_refuse_rays(h);
+    if (const int rc = lf_refuse_rays(h)) return rc;
     *kernel = h->last_mode;
     return MCL_OK;
 }
@@ -2502,7 +2155,7 @@ int mcl_get_ray_kernel_id(const mcl_engine_t *h, int32_t *kernel)
 int mcl_get_ray_kernel_variant(const mcl_engine_t *h, int32_t out[3])
 {
     if (!h || !out) return MCL_ERR_INVALID_ARG;
-    if (h->last_lf) return lf_refuse_rays(h);
+    if (const int rc = lf_refuse_rays(h)) return rc;
     out[0] = h->last_sweep_global; out[1] = h->last_sweep_rec; out[2] = h->last_sweep_pairs;
     return MCL_OK;
 }
@@ -2526,16 +2179,6 @@ int mcl_get_effective_sample_size(const mcl_engine_t *h, double *n_eff, int32_t 
     *n_eff = sww > 0.0 ? sw * sw / sww : 0.0;
     *resampled_last_update = h->resampled_last ? 1 : 0;
     return MCL_OK;
-}
-
-void mcl_default_kld_config(mcl_kld_config_t *k)
-{
-    if (!k) return;
-    *k = mcl_kld_config_t{};
-    k->min_particles = 256; k->max_particles = 4194304;
-    k->err = 0.01; k->z = 2.326;
-    k->bin_x_m = 0.5; k->bin_y_m = 0.5;
-    k->n_theta_bins = 36; k->round_to = 256; k->shrink_permille = 800;
 }
 
 int mcl_set_kld(mcl_engine_t *h, const mcl_kld_config_t *k)
@@ -2577,49 +2220,7 @@ int mcl_get_kld_state(const mcl_engine_t *h, int64_t *bins_last, int64_t *n_next
     return MCL_OK;
 }
 
-int mcl_host_kld_bins(const double *x, const double *y, const double *th, int64_t n, uint32_t width, uint32_t height,
-                      float resolution, double origin_x, double origin_y, const mcl_kld_config_t *k, int64_t *bins)
-{
-    if (!k || !bins || n < 0 || (n > 0 && (!x || !y || !th)) || width == 0 || height == 0 || !(resolution > 0.0f) ||
-        !std::isfinite(resolution) || kld_invalid(k, 0))
-        return MCL_ERR_INVALID_ARG;
-    int64_t nx = 0, ny = 0;
-    uint64_t nbits = 0;
-    if (!kld_grid(k, width, height, resolution, nx, ny, nbits)) return MCL_ERR_INVALID_ARG;
-    const mcl::KldArgs a = kld_args_of(k, nx, ny, origin_x, origin_y);
-    std::vector<uint32_t> b((size_t)n);
-    for (int64_t i = 0; i < n; ++i) b[(size_t)i] = mcl::kld_bin(a, x[i], y[i], th[i]);
-    std::sort(b.begin(), b.end());
-    *bins = (int64_t)(std::unique(b.begin(), b.end()) - b.begin());
-    return MCL_OK;
-}
-
-int mcl_host_kld_target(const mcl_kld_config_t *k, int64_t bins, int64_t n_current, int64_t *n_next)
-{
-    if (!k || !n_next || n_current < 0 || n_current >= MCL_MAX_TOTAL_PARTICLES || kld_invalid(k, 0)) return MCL_ERR_INVALID_ARG;
-    *n_next = kld_target(k, bins, n_current);
-    return MCL_OK;
-}
-
 // ---- odometry motion models and the Gaussian pose initialisation (the header's M1-M6 / G1) ----
-static const char *motion_invalid(const mcl_motion_config_t *c)
-{
-    if (c->model != MCL_MOTION_REFERENCE && c->model != MCL_MOTION_DIFF && c->model != MCL_MOTION_OMNI) return "motion model: unknown model";
-    if (c->reserved != 0) return "motion model: reserved must be 0";
-    const double v[7] = {c->alpha1, c->alpha2, c->alpha3, c->alpha4, c->alpha5, c->floor_trans_m, c->floor_rot_rad};
-    for (double e : v)
-        if (!std::isfinite(e) || e < 0.0) return "motion model: the alphas and floors must be finite and >= 0";
-    return nullptr;
-}
-
-void mcl_default_motion_config(mcl_motion_config_t *c)
-{
-    if (!c) return;
-    *c = mcl_motion_config_t{};
-    c->model = MCL_MOTION_DIFF;
-    c->alpha1 = c->alpha2 = c->alpha3 = c->alpha4 = c->alpha5 = 0.2;
-}
-
 int mcl_set_motion_model(mcl_engine_t *h, const mcl_motion_config_t *c)
 {
     if (!h) return MCL_ERR_INVALID_ARG;
@@ -2634,122 +2235,6 @@ int mcl_get_motion_model(const mcl_engine_t *h, mcl_motion_config_t *out)
     if (!h || !out) return MCL_ERR_INVALID_ARG;
     *out = h->motion;
     return MCL_OK;
-}
-
-static double odo_norm(double z) { return std::atan2(std::sin(z), std::cos(z)); }
-static double odo_adiff(double a, double b)
-{
-    const double PI = 3.14159265358979323846;
-    a = odo_norm(a); b = odo_norm(b);
-    const double d1 = a - b;
-    double d2 = 2.0 * PI - std::fabs(d1);
-    if (d1 > 0.0) d2 = -d2;
-    return std::fabs(d1) < std::fabs(d2) ? d1 : d2;
-}
-
-int mcl_host_motion_scalars(const mcl_motion_config_t *c, const double action[3], double out[8])
-{
-    if (!c || !action || !out || motion_invalid(c) || c->model == MCL_MOTION_REFERENCE) return MCL_ERR_INVALID_ARG;
-    const double PI = 3.14159265358979323846;
-    const double dx = action[0], dy = action[1], dth = action[2];
-    const double trans = std::sqrt(dx * dx + dy * dy);
-    const double ft2 = c->floor_trans_m * c->floor_trans_m, fr2 = c->floor_rot_rad * c->floor_rot_rad;
-    const double t2 = trans * trans;
-    if (c->model == MCL_MOTION_DIFF) {
-        const double rot1 = trans < 0.01 ? 0.0 : std::atan2(dy, dx);
-        const double rot2 = odo_adiff(dth, rot1);
-        const double r1n = std::fmin(std::fabs(odo_adiff(rot1, 0.0)), std::fabs(odo_adiff(rot1, PI)));
-        const double r2n = std::fmin(std::fabs(odo_adiff(rot2, 0.0)), std::fabs(odo_adiff(rot2, PI)));
-        out[0] = rot1; out[1] = trans; out[2] = rot2;
-        out[3] = std::sqrt(c->alpha1 * (r1n * r1n) + c->alpha2 * t2 + fr2);
-        out[4] = std::sqrt(c->alpha3 * t2 + c->alpha4 * (r1n * r1n) + c->alpha4 * (r2n * r2n) + ft2);
-        out[5] = std::sqrt(c->alpha1 * (r2n * r2n) + c->alpha2 * t2 + fr2);
-    } else {
-        const double rot = dth, r2 = rot * rot;
-        out[0] = std::atan2(dy, dx); out[1] = trans; out[2] = rot;
-        out[3] = std::sqrt(c->alpha3 * t2 + c->alpha1 * r2 + ft2);
-        out[4] = std::sqrt(c->alpha4 * r2 + c->alpha2 * t2 + fr2);
-        out[5] = std::sqrt(c->alpha1 * r2 + c->alpha5 * t2 + ft2);
-    }
-    out[6] = 0.0; out[7] = 0.0;
-    return MCL_OK;
-}
-
-// the odometry arguments of an update's resampling kernel; false: the reference model (the kernels and arguments of always)
-static bool odo_args_of(const mcl_engine *h, const double action[3], mcl::OdoArgs &o)
-{
-    if (h->motion.model == MCL_MOTION_REFERENCE || !action) return false;
-    double s[8];
-    if (mcl_host_motion_scalars(&h->motion, action, s) != MCL_OK) return false;
-    o.model = h->motion.model; o.pad = 0;
-    for (int i = 0; i < 6; ++i) o.s[i] = s[i];
-    return true;
-}
-
-// mcl_device_math.h's normalize_angle on the host
-static double host_normalize_angle(double a)
-{
-    const double PI = 3.14159265358979323846;
-    int it = 0;
-    while (a > PI && it < 64) { a -= 2.0 * PI; ++it; }
-    while (a < -PI && it < 128) { a += 2.0 * PI; ++it; }
-    if (it >= 64 && (a > PI || a < -PI)) a = std::remainder(a, 2.0 * PI);
-    return a;
-}
-
-int mcl_host_motion_sample(const mcl_motion_config_t *c, const double action[3], const double *xyz, const double *normals, int64_t n,
-                           double *out)
-{
-    if (!xyz || !normals || !out || n < 0) return MCL_ERR_INVALID_ARG;
-    double s[8];
-    const int rc = mcl_host_motion_scalars(c, action, s);
-    if (rc) return rc;
-    mcl::OdoArgs o{};
-    o.model = c->model;
-    for (int i = 0; i < 6; ++i) o.s[i] = s[i];
-    for (int64_t m = 0; m < n; ++m) {
-        double x = xyz[m], y = xyz[n + m], th = xyz[2 * n + m];
-        mcl::odo_step(o, x, y, th, normals[3 * m], normals[3 * m + 1], normals[3 * m + 2]);
-        out[m] = x; out[n + m] = y; out[2 * n + m] = host_normalize_angle(th);
-    }
-    return MCL_OK;
-}
-
-// G1: the lower Cholesky factor of a symmetric positive semi-definite 3 x 3 matrix (row-major), L = {L00, L10, L11, L20, L21, L22}
-static const char *gaussian_factor(const double cov[9], double L[6])
-{
-    double amax = 0.0, dmax = 0.0;
-    for (int i = 0; i < 9; ++i) {
-        if (!std::isfinite(cov[i])) return "gaussian init: the covariance must be finite";
-        amax = std::max(amax, std::fabs(cov[i]));
-    }
-    for (int i = 0; i < 3; ++i) {
-        dmax = std::max(dmax, cov[4 * i]);
-        for (int j = 0; j < i; ++j)
-            if (std::fabs(cov[3 * i + j] - cov[3 * j + i]) > 1e-12 * amax) return "gaussian init: the covariance must be symmetric";
-    }
-    const double tol = 1e-12 * dmax;
-    double l[3][3] = {};
-    for (int j = 0; j < 3; ++j) {
-        double p = cov[4 * j];
-        for (int k = 0; k < j; ++k) p -= l[j][k] * l[j][k];
-        if (std::fabs(p) <= tol) continue;               // a zero pivot: the column stays zero
-        if (p < 0.0) return "gaussian init: the covariance must be positive semi-definite";
-        l[j][j] = std::sqrt(p);
-        for (int i = j + 1; i < 3; ++i) {
-            double v = cov[3 * i + j];
-            for (int k = 0; k < j; ++k) v -= l[i][k] * l[j][k];
-            l[i][j] = v / l[j][j];
-        }
-    }
-    L[0] = l[0][0]; L[1] = l[1][0]; L[2] = l[1][1]; L[3] = l[2][0]; L[4] = l[2][1]; L[5] = l[2][2];
-    return nullptr;
-}
-
-int mcl_host_gaussian_factor(const double cov[9], double L[6])
-{
-    if (!cov || !L) return MCL_ERR_INVALID_ARG;
-    return gaussian_factor(cov, L) ? MCL_ERR_INVALID_ARG : MCL_OK;
 }
 
 int mcl_init_particles_gaussian(mcl_engine_t *h, const double mean[3], const double cov[9], int64_t n, int64_t first_global_index,
@@ -2767,13 +2252,6 @@ int mcl_init_particles_gaussian(mcl_engine_t *h, const double mean[3], const dou
                        h->d_x[c], h->d_y[c], h->d_th[c]);
     HIPCHK(h, hipGetLastError());
     return finish_init(h, n, n_total);
-}
-
-void mcl_default_recovery_config(mcl_recovery_config_t *c)
-{
-    if (!c) return;
-    *c = mcl_recovery_config_t{};
-    c->alpha_slow = 0.001; c->alpha_fast = 0.1; c->per_beam = 1;
 }
 
 int mcl_set_recovery(mcl_engine_t *h, const mcl_recovery_config_t *c)
@@ -2831,24 +2309,6 @@ int mcl_set_recovery_state(mcl_engine_t *h, const double state[2])
     return MCL_OK;
 }
 
-int mcl_host_recovery_step(const mcl_recovery_config_t *c, const double in[2], int32_t reset, double max_logw, double sum_w,
-                           double denom, int32_t n_beams, double out[2], double *p_next)
-{
-    if (!c || !in || !out || recov_invalid(c) || !(denom > 0.0) || n_beams < 1) return MCL_ERR_INVALID_ARG;
-    double S = reset ? NAN : in[0], F = reset ? NAN : in[1];
-    recov_fold(*c, S, F, recov_likelihood(*c, max_logw, sum_w, denom, n_beams));
-    out[0] = S; out[1] = F;
-    if (p_next) *p_next = recov_p(S, F);
-    return MCL_OK;
-}
-
-void mcl_default_likelihood_field_config(mcl_likelihood_field_config_t *c)
-{
-    if (!c) return;
-    *c = mcl_likelihood_field_config_t{};
-    c->z_hit = 0.5; c->z_rand = 0.5; c->sigma_hit_m = 0.2; c->max_occ_dist_m = 2.0;   // AMCL's defaults
-}
-
 int mcl_set_likelihood_field(mcl_engine_t *h, const mcl_likelihood_field_config_t *c)
 {
     if (!h) return MCL_ERR_INVALID_ARG;
@@ -2900,96 +2360,6 @@ int mcl_get_likelihood_table(mcl_engine_t *h, float *out, size_t n, int32_t *K)
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipMemcpyAsync(out, h->d_lf_tab, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    return MCL_OK;
-}
-
-int mcl_host_likelihood_field(const int8_t *data, uint32_t width, uint32_t height, float resolution,
-                              const mcl_likelihood_field_config_t *c, uint16_t *out, size_t n)
-{
-    if (!data || !out || !c || width == 0 || height == 0 || width > 200000 || height > 200000 || !(resolution > 0.0f) ||
-        !std::isfinite(resolution) || lf_invalid(c) || n != (size_t)width * height)
-        return MCL_ERR_INVALID_ARG;
-    const int K = lf_cap(c, resolution);
-    if (K < 0) return MCL_ERR_INVALID_ARG;
-    lf_field_host(data, (int)width, (int)height, K, out);
-    return MCL_OK;
-}
-
-int mcl_host_likelihood_table(const mcl_config_t *cfg, const mcl_likelihood_field_config_t *c, float resolution, float *out,
-                              size_t n, int32_t *K)
-{
-    if (!cfg || !c || !(resolution > 0.0f) || !std::isfinite(resolution) || lf_invalid(c)) return MCL_ERR_INVALID_ARG;
-    if (!(std::isfinite(cfg->max_range_m) && cfg->max_range_m > 0.0 && std::isfinite(cfg->squash_factor) && cfg->squash_factor > 0.0))
-        return MCL_ERR_INVALID_ARG;
-    const int k = lf_cap(c, resolution);
-    if (k < 0) return MCL_ERR_INVALID_ARG;
-    if (K) *K = k;
-    if (!out) return MCL_OK;
-    if (n != (size_t)k + 1) return MCL_ERR_INVALID_ARG;
-    std::vector<float> t;
-    lf_table(*cfg, *c, (double)resolution, k, t);
-    std::memcpy(out, t.data(), n * sizeof(float));
-    return MCL_OK;
-}
-
-int mcl_host_sensor_table(const mcl_config_t *cfg, int32_t P, double *out, size_t n)
-{
-    if (!cfg || !out || P < 1 || n != (size_t)(P + 1) * (P + 1) || bad_sensor_fields(*cfg)) return MCL_ERR_INVALID_ARG;
-    std::vector<double> t;
-    build_sensor_table(*cfg, P, t);
-    std::memcpy(out, t.data(), n * sizeof(double));
-    return MCL_OK;
-}
-
-int mcl_host_skip_field_dir(const int8_t *data, uint32_t width, uint32_t height, int32_t quadrant, uint8_t *out, size_t n)
-{
-    if (!data || !out || width == 0 || height == 0 || quadrant < 0 || quadrant > 3 || n != (size_t)(width + 1) * (height + 1))
-        return MCL_ERR_INVALID_ARG;
-    static const int qsx[4] = {1, -1, -1, 1}, qsy[4] = {1, 1, -1, -1};
-    const int Wp = (int)width + 1, Hp = (int)height + 1, Wps = (Wp + 7) & ~7;
-    std::vector<uint8_t> d;
-    build_directional_field(data, (int)width, (int)height, Wp, Hp, Wps, qsx[quadrant], qsy[quadrant], d);
-    for (int y = 0; y < Hp; ++y) std::memcpy(out + (size_t)y * Wp, d.data() + (size_t)y * Wps, Wp);
-    return MCL_OK;
-}
-
-int mcl_host_skip_field_wedge(const int8_t *data, uint32_t width, uint32_t height, int32_t wedge, uint8_t *out, size_t n)
-{
-    if (!data || !out || width == 0 || height == 0 || wedge < 0 || wedge >= mcl::kWedges || n != (size_t)(width + 1) * (height + 1))
-        return MCL_ERR_INVALID_ARG;
-    const int W = (int)width, H = (int)height, Wp = W + 1, Hp = H + 1;
-    std::vector<int32_t> nxt((size_t)Wp * Hp), prv((size_t)Wp * Hp);
-    for (int y = 0; y < Hp; ++y) {
-        auto stop = [&](int x) { return data[(size_t)std::max(y - 1, 0) * W + std::max(x - 1, 0)] > 50; };
-        int last = -1;
-        for (int x = 0; x < Wp; ++x) { if (stop(x)) last = x; prv[(size_t)y * Wp + x] = last; }
-        int next = Wp;
-        for (int x = Wp - 1; x >= 0; --x) { if (stop(x)) next = x; nxt[(size_t)y * Wp + x] = next; }
-    }
-    std::vector<mcl::WedgeRow> rows(2 * mcl::kWedgeR + 1);
-    mcl::wedge_rows(wedge, rows.data());
-    for (int y = 0; y < Hp; ++y)
-        for (int x = 0; x < Wp; ++x) out[(size_t)y * Wp + x] = (uint8_t)mcl::wedge_skip_cell(nxt.data(), prv.data(), Wp, Hp, x, y, rows.data());
-    return MCL_OK;
-}
-
-int mcl_host_skip_field(const int8_t *data, uint32_t width, uint32_t height, uint8_t *out, size_t n)
-{
-    if (!data || !out || width == 0 || height == 0 || n != (size_t)(width + 1) * (height + 1)) return MCL_ERR_INVALID_ARG;
-    const int Wp = (int)width + 1, Hp = (int)height + 1, Wps = (Wp + 7) & ~7;
-    std::vector<uint8_t> d;
-    build_distance_field(data, (int)width, (int)height, Wp, Hp, Wps, d);
-    for (int y = 0; y < Hp; ++y) std::memcpy(out + (size_t)y * Wp, d.data() + (size_t)y * Wps, Wp);
-    return MCL_OK;
-}
-
-int mcl_host_sweep_global_layout(uint32_t width, uint32_t height, int32_t max_range_px, int64_t out[6])
-{
-    if (!out || width == 0 || height == 0 || max_range_px < 1) return MCL_ERR_INVALID_ARG;
-    const int Wp = (int)width + 1, Hp = (int)height + 1;
-    const mcl::SweepGlobalLayout g = mcl::sweep_global_layout(Wp, Hp, max_range_px);
-    out[0] = g.ok ? 1 : 0; out[1] = g.pitch; out[2] = g.rows; out[3] = (int64_t)g.stride; out[4] = (int64_t)g.alloc;
-    out[5] = (int64_t)mcl::sweep_global_max_offset(g, Wp, Hp, max_range_px, mcl::kWedges - 1);
     return MCL_OK;
 }
 
@@ -3066,9 +2436,7 @@ int mcl_export_records_at(mcl_engine_t *h, const int64_t *d_index, int64_t count
 int mcl_stage_distinct_parents(mcl_engine_t *h, const int32_t *d_parent, int64_t n_children, int64_t n_total, int64_t *d_distinct,
                                int32_t *d_slot, int64_t *count)
 {
-    if (h && h->kld_on) return kld_refuse_stage(h);
-    if (h && h->recov_on) return recov_refuse_stage(h);
-    if (h && h->lf_on) return lf_refuse_stage(h);
+    if (const int rc = refuse_stage(h)) return rc;
     if (!h || !d_parent || !d_distinct || !d_slot || !count || n_children <= 0 || n_total <= 0) return MCL_ERR_INVALID_ARG;
     if (n_total > MCL_MAX_TOTAL_PARTICLES) return fail(h, MCL_ERR_INVALID_ARG, "n_total exceeds MCL_MAX_TOTAL_PARTICLES");
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -3121,10 +2489,9 @@ int mcl_get_host_scalars(const mcl_engine_t *h, double out[8])
     return MCL_OK;
 }
 
-
 // Launches the staged resample (+ motion) on the engine's stream; no synchronisation.  An index-only pass leaves the
 // engine untouched; otherwise the children land in the other particle buffer, which becomes current.
-static int stage_resample_launch(mcl_engine_t *h, const ParentSource &src, const uint64_t *d_cdf, int64_t n_parents, uint64_t q_total,
+int mcl_host::stage_resample_launch(mcl_engine_t *h, const ParentSource &src, const uint64_t *d_cdf, int64_t n_parents, uint64_t q_total,
                                  int64_t child_first, int64_t n_children_total, const double action[3])
 {
     if (!h) return MCL_ERR_INVALID_ARG;
@@ -3145,7 +2512,8 @@ static int stage_resample_launch(mcl_engine_t *h, const ParentSource &src, const
     }
     const int nx = h->cur ^ 1;
     mcl::ResampleArgs a{};
-    a.px = src.px; a.py = src.py; a.pth = src.pth; a.cdf = d_cdf; a.n_parents = n_parents; a.q_total = q_total;
+    a.px = src.px; a.py = src.py; a.pth = src.pth; a.q_total = q_total;
+    resample_common_args(h, a, d_cdf, n_parents);
     a.ppack = reinterpret_cast<const double4 *>(src.records);
     for (int r = 0; r < mcl::kMaxShards; ++r) a.ppack_rank[r] = src.rank_records[r];
     a.n_per_rank = src.n_per_rank; a.self_rank = src.self_rank; a.remote_count = src.remote_count;
@@ -3153,29 +2521,13 @@ static int stage_resample_launch(mcl_engine_t *h, const ParentSource &src, const
     a.cpack = h->d_pack[nx];
     if (src.gcdf) {
         a.ccdf = src.gcdf; a.ctop = src.gtop; a.n_compact = n_parents; a.cchunks = src.cchunks;
-        a.ccap = src.cchunk_entries; a.cchunk_bytes = src.cchunk_entries * 44;
+        a.ccap = src.cchunk_entries; a.cchunk_bytes = src.cchunk_entries * kCompactEntryBytes;
         a.cpack = nullptr;
     }
-    a.tile_excl = (d_cdf && h->blocktot_for == d_cdf && h->blocktot_n == n_parents) ? h->d_blocktot : nullptr;   // spine of the scan that produced d_cdf
-    a.leaders = a.tile_excl ? h->d_leaders : nullptr;
-    a.cx = h->d_x[nx]; a.cy = h->d_y[nx]; a.cth = h->d_th[nx];
     a.idx_out = src.idx_in ? nullptr : h->d_idx;       // the global parents of an earlier index-only pass stay in d_idx
     a.n_children = n; a.child_first = child_first; a.n_children_total = n_children_total;
-    a.mode = h->cfg.resample_mode;
-    a.seed_lo = (uint32_t)h->cfg.seed; a.seed_hi = (uint32_t)(h->cfg.seed >> 32);
-    a.update_idx = h->update_idx;
-    if (a.mode == MCL_RESAMPLE_SYSTEMATIC) {
-        uint32_t c0 = 0, c1 = h->update_idx, c2 = 3, c3 = 0, k0 = a.seed_lo, k1 = a.seed_hi;
-        for (int r = 0; r < 10; ++r) {
-            uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-            uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-            c0 = n0; c1 = n1; c2 = n2; c3 = n3; k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-        }
-        a.k0 = c0;
-    }
     if (action) motion_scalars(action, a.dt, a.v, a.w);
-    a.disp_x = h->cfg.motion_dispersion_x; a.disp_y = h->cfg.motion_dispersion_y; a.disp_th = h->cfg.motion_dispersion_theta;
-    a.do_resample = src.keep ? 0 : 1; a.do_motion = 1;
+    a.do_resample = src.keep ? 0 : 1;
     a.idx_out_base = src.keep ? child_first : 0;
     h->layout_stale_used = false; h->keys_done = false; h->pc_ready = false;
     // as in mcl_update: the ray stage's per-particle constants, its zeroed scratch and (by the previous update's layout) the sort
@@ -3216,9 +2568,7 @@ static int stage_resample_sync(mcl_engine_t *h, const ParentSource &src, const u
 int mcl_stage_resample(mcl_engine_t *h, const double *d_px, const double *d_py, const double *d_pth, const uint64_t *d_cdf,
                        int64_t n_parents, uint64_t q_total, int64_t child_first, int64_t n_children_total, const double action[3])
 {
-    if (h && h->kld_on) return kld_refuse_stage(h);
-    if (h && h->recov_on) return recov_refuse_stage(h);
-    if (h && h->lf_on) return lf_refuse_stage(h);
+    if (const int rc = refuse_stage(h)) return rc;
     ParentSource src; src.px = d_px; src.py = d_py; src.pth = d_pth;
     if (!d_px || !d_py || !d_pth) return h ? fail(h, MCL_ERR_INVALID_ARG, "bad stage_resample arguments") : MCL_ERR_INVALID_ARG;
     return stage_resample_sync(h, src, d_cdf, n_parents, q_total, child_first, n_children_total, action);
@@ -3227,9 +2577,7 @@ int mcl_stage_resample(mcl_engine_t *h, const double *d_px, const double *d_py, 
 int mcl_stage_resample_records(mcl_engine_t *h, const void *d_records, const uint64_t *d_cdf, int64_t n_parents, uint64_t q_total,
                                int64_t child_first, int64_t n_children_total, const double action[3])
 {
-    if (h && h->kld_on) return kld_refuse_stage(h);
-    if (h && h->recov_on) return recov_refuse_stage(h);
-    if (h && h->lf_on) return lf_refuse_stage(h);
+    if (const int rc = refuse_stage(h)) return rc;
     ParentSource src; src.records = d_records;
     if (!d_records) return h ? fail(h, MCL_ERR_INVALID_ARG, "bad stage_resample arguments") : MCL_ERR_INVALID_ARG;
     return stage_resample_sync(h, src, d_cdf, n_parents, q_total, child_first, n_children_total, action);
@@ -3238,9 +2586,7 @@ int mcl_stage_resample_records(mcl_engine_t *h, const void *d_records, const uin
 int mcl_stage_resample_indices(mcl_engine_t *h, const uint64_t *d_cdf, int64_t n_parents, uint64_t q_total, int64_t child_first,
                                int64_t n_children_total, int32_t *d_parent_idx)
 {
-    if (h && h->kld_on) return kld_refuse_stage(h);
-    if (h && h->recov_on) return recov_refuse_stage(h);
-    if (h && h->lf_on) return lf_refuse_stage(h);
+    if (const int rc = refuse_stage(h)) return rc;
     ParentSource src; src.idx_only_out = d_parent_idx;
     if (!d_parent_idx || !d_cdf) return h ? fail(h, MCL_ERR_INVALID_ARG, "bad stage_resample_indices arguments") : MCL_ERR_INVALID_ARG;
     return stage_resample_sync(h, src, d_cdf, n_parents, q_total, child_first, n_children_total, nullptr);
@@ -3249,9 +2595,7 @@ int mcl_stage_resample_indices(mcl_engine_t *h, const uint64_t *d_cdf, int64_t n
 int mcl_stage_motion_records(mcl_engine_t *h, const void *d_records, int64_t n_records, const int32_t *d_record_of_child, int64_t child_first,
                              int64_t n_children_total, const double action[3])
 {
-    if (h && h->kld_on) return kld_refuse_stage(h);
-    if (h && h->recov_on) return recov_refuse_stage(h);
-    if (h && h->lf_on) return lf_refuse_stage(h);
+    if (const int rc = refuse_stage(h)) return rc;
     ParentSource src; src.records = d_records; src.idx_in = d_record_of_child;
     if (!d_records || !d_record_of_child || n_records <= 0) return h ? fail(h, MCL_ERR_INVALID_ARG, "bad stage_motion_records arguments") : MCL_ERR_INVALID_ARG;
     return stage_resample_sync(h, src, nullptr, n_records, 0, child_first, n_children_total, action);
@@ -3261,11 +2605,11 @@ int mcl_stage_motion_records(mcl_engine_t *h, const void *d_records, int64_t n_r
 int mcl_compact_chunk_bytes(int64_t chunk_entries, int64_t *bytes)
 {
     if (!bytes || chunk_entries <= 0 || (chunk_entries & 63)) return MCL_ERR_INVALID_ARG;
-    *bytes = chunk_entries * 44;             // [ccdf: 8 | crec: 32 | cidx: 4] per entry, column by column
+    *bytes = chunk_entries * kCompactEntryBytes;
     return MCL_OK;
 }
 
-static int export_compact_launch(mcl_engine_t *h, void *d_chunk, int64_t chunk_entries, int dst_device, hipStream_t stream)
+int mcl_host::export_compact_launch(mcl_engine_t *h, void *d_chunk, int64_t chunk_entries, int dst_device, hipStream_t stream)
 {
     if (!h || !d_chunk || chunk_entries <= 0 || (chunk_entries & 63)) return MCL_ERR_INVALID_ARG;
     if (h->compact_n < 0 || h->compact_n > chunk_entries) return fail(h, MCL_ERR_NOT_READY, "no compact list of that size (mcl_get_compact_list)");
@@ -3290,7 +2634,7 @@ int mcl_export_compact(mcl_engine_t *h, void *d_chunk, int64_t chunk_entries)
 }
 
 // merge of the gathered chunks + staged resample from them, on the engine's stream; no synchronisation
-static int stage_resample_compact_launch(mcl_engine_t *h, const void *d_chunks, int32_t n_shards, int64_t chunk_entries, const int64_t *counts,
+int mcl_host::stage_resample_compact_launch(mcl_engine_t *h, const void *d_chunks, int32_t n_shards, int64_t chunk_entries, const int64_t *counts,
                                          const uint64_t *totals, int64_t n_per_shard, int32_t self_shard, int64_t child_first,
                                          int64_t n_children_total, const double action[3], unsigned long long *remote_count)
 {
@@ -3300,7 +2644,7 @@ static int stage_resample_compact_launch(mcl_engine_t *h, const void *d_chunks, 
         return fail(h, MCL_ERR_INVALID_ARG, "bad stage_resample_compact arguments");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     mcl::MergeArgs m{};
-    m.chunks = static_cast<const unsigned char *>(d_chunks); m.chunk_bytes = chunk_entries * 44; m.ccap = chunk_entries; m.n_shards = n_shards;
+    m.chunks = static_cast<const unsigned char *>(d_chunks); m.chunk_bytes = chunk_entries * kCompactEntryBytes; m.ccap = chunk_entries; m.n_shards = n_shards;
     uint64_t off = 0;
     for (int r = 0; r < n_shards; ++r) {
         if (counts[r] < 0 || counts[r] > chunk_entries) return fail(h, MCL_ERR_INVALID_ARG, "a list is longer than its chunk");
@@ -3330,9 +2674,7 @@ int mcl_stage_resample_compact(mcl_engine_t *h, const void *d_chunks, int32_t n_
                                const uint64_t *totals, int64_t n_per_shard, int32_t self_shard, int64_t child_first, int64_t n_children_total,
                                const double action[3])
 {
-    if (h && h->kld_on) return kld_refuse_stage(h);
-    if (h && h->recov_on) return recov_refuse_stage(h);
-    if (h && h->lf_on) return lf_refuse_stage(h);
+    if (const int rc = refuse_stage(h)) return rc;
     const int rc = stage_resample_compact_launch(h, d_chunks, n_shards, chunk_entries, counts, totals, n_per_shard, self_shard, child_first,
                                                  n_children_total, action, nullptr);
     if (rc) return rc;
@@ -3340,7 +2682,7 @@ int mcl_stage_resample_compact(mcl_engine_t *h, const void *d_chunks, int32_t n_
     return MCL_OK;
 }
 
-static int stage_rays_launch(mcl_engine_t *h, const float *obs, int32_t n_beams, bool force_skip, double *d_max_out = nullptr)
+int mcl_host::stage_rays_launch(mcl_engine_t *h, const float *obs, int32_t n_beams, bool force_skip, double *d_max_out)
 {
     if (!h) return MCL_ERR_INVALID_ARG;
     if (!ready(h, true)) return fail(h, MCL_ERR_NOT_READY, "map, beam angles and particles must be set first");
@@ -3363,8 +2705,7 @@ static int stage_rays_launch(mcl_engine_t *h, const float *obs, int32_t n_beams,
     rc = next_layout_launch(h, n);
     if (rc) return rc;
     if (h->stage_kept) {
-        hipLaunchKernelGGL(mcl::k_add_carry, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d_logw, h->d_carry[h->carry_idx], n);
-        h->max_partials_ready = false;
+        add_carry(h, n);
         HIPCHK(h, hipEventRecord(h->ev[EV_RAYS], h->stream));
     } else if (!h->ev_rays_bound) HIPCHK(h, hipEventRecord(h->ev[EV_RAYS], h->stream));
     if (!h->max_partials_ready)
@@ -3378,7 +2719,7 @@ static int stage_rays_launch(mcl_engine_t *h, const float *obs, int32_t n_beams,
 }
 
 // the host-side notes of a finished ray stage (its stream has been waited for)
-static void stage_rays_note(mcl_engine_t *h)
+void mcl_host::stage_rays_note(mcl_engine_t *h)
 {
     h->have_logw = true;
     h->have_steps = h->cfg.keep_ray_steps != 0;
@@ -3389,7 +2730,7 @@ static void stage_rays_note(mcl_engine_t *h)
     h->ray_ms = elapsed(h->ev[EV_K0], h->ev[EV_K1]);
 }
 
-static int stage_rays_finish(mcl_engine_t *h, const float *obs, int32_t n_beams)
+int mcl_host::stage_rays_finish(mcl_engine_t *h, const float *obs, int32_t n_beams)
 {
     HIPCHK(h, hipSetDevice(h->cfg.device));
     for (int attempt = 0; attempt < 2; ++attempt) {
@@ -3408,9 +2749,7 @@ static int stage_rays_finish(mcl_engine_t *h, const float *obs, int32_t n_beams)
 
 int mcl_stage_rays(mcl_engine_t *h, const float *obs, int32_t n_beams)
 {
-    if (h && h->kld_on) return kld_refuse_stage(h);
-    if (h && h->recov_on) return recov_refuse_stage(h);
-    if (h && h->lf_on) return lf_refuse_stage(h);
+    if (const int rc = refuse_stage(h)) return rc;
     int rc = stage_rays_launch(h, obs, n_beams, false);
     if (rc) return rc;
     return stage_rays_finish(h, obs, n_beams);
@@ -3420,9 +2759,7 @@ int mcl_stage_propagate(mcl_engine_t *h, const double *d_px, const double *d_py,
                         int64_t n_parents, uint64_t q_total, int64_t child_first, int64_t n_children_total,
                         const double action[3], const float *obs, int32_t n_beams)
 {
-    if (h && h->kld_on) return kld_refuse_stage(h);
-    if (h && h->recov_on) return recov_refuse_stage(h);
-    if (h && h->lf_on) return lf_refuse_stage(h);
+    if (const int rc = refuse_stage(h)) return rc;
     if (!h) return MCL_ERR_INVALID_ARG;
     if (!obs || n_beams != h->B) return fail(h, MCL_ERR_INVALID_ARG, "bad observation");
     int rc = mcl_stage_resample(h, d_px, d_py, d_pth, d_cdf, n_parents, q_total, child_first, n_children_total, action);
@@ -3439,7 +2776,7 @@ int mcl_set_reserved_cus(mcl_engine_t *h, int32_t n_cus)
 
 // d_global_max: the global maximum in device memory (the device-ordered flow: the log-weights need not have been seen by the
 // host yet), else the host's value is staged
-static int stage_weights_launch(mcl_engine_t *h, double global_max_logw, const double *d_global_max = nullptr)
+int mcl_host::stage_weights_launch(mcl_engine_t *h, double global_max_logw, const double *d_global_max)
 {
     if (!h) return MCL_ERR_INVALID_ARG;
     h->set_epoch++;                         // (the labels of a clustering are void from here on)
@@ -3468,7 +2805,7 @@ static int stage_weights_launch(mcl_engine_t *h, double global_max_logw, const d
     return MCL_OK;
 }
 
-static int stage_weights_finish(mcl_engine_t *h)
+int mcl_host::stage_weights_finish(mcl_engine_t *h)
 {
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3479,16 +2816,14 @@ static int stage_weights_finish(mcl_engine_t *h)
 
 int mcl_stage_weights(mcl_engine_t *h, double global_max_logw)
 {
-    if (h && h->kld_on) return kld_refuse_stage(h);
-    if (h && h->recov_on) return recov_refuse_stage(h);
-    if (h && h->lf_on) return lf_refuse_stage(h);
+    if (const int rc = refuse_stage(h)) return rc;
     int rc = stage_weights_launch(h, global_max_logw);
     if (rc) return rc;
     return stage_weights_finish(h);
 }
 
 // end of a staged update: the carry its weights stage wrote becomes the current one
-static void stage_commit_carry(mcl_engine_t *h)
+void mcl_host::stage_commit_carry(mcl_engine_t *h)
 {
     if (h->carry_pending) { h->carry_idx ^= 1; h->carry_valid = true; h->carry_pending = false; }
     h->stage_kept = false;
@@ -3496,9 +2831,7 @@ static void stage_commit_carry(mcl_engine_t *h)
 
 int mcl_stage_finish(mcl_engine_t *h, const double global_sums[5])
 {
-    if (h && h->kld_on) return kld_refuse_stage(h);
-    if (h && h->recov_on) return recov_refuse_stage(h);
-    if (h && h->lf_on) return lf_refuse_stage(h);
+    if (const int rc = refuse_stage(h)) return rc;
     if (!h || !global_sums) return MCL_ERR_INVALID_ARG;
     for (int i = 0; i < 5; ++i) h->global_sums[i] = global_sums[i];
     stage_commit_carry(h);
@@ -3512,9 +2845,7 @@ int mcl_stage_finish(mcl_engine_t *h, const double global_sums[5])
 // previous update's log-weights minus their global maximum, as mcl_update does.  Launch only (no wait).
 int mcl_stage_keep(mcl_engine_t *h, int64_t child_first, int64_t n_children_total, const double action[3])
 {
-    if (h && h->kld_on) return kld_refuse_stage(h);
-    if (h && h->recov_on) return recov_refuse_stage(h);
-    if (h && h->lf_on) return lf_refuse_stage(h);
+    if (const int rc = refuse_stage(h)) return rc;
     if (!h || !action) return MCL_ERR_INVALID_ARG;
     if (h->cfg.resample_neff_permille <= 0) return fail(h, MCL_ERR_UNSUPPORTED, "mcl_stage_keep needs resample_neff_permille > 0");
     if (!h->carry_valid) return fail(h, MCL_ERR_NOT_READY, "no log-weights of a previous update to carry");
@@ -3555,18 +2886,14 @@ int mcl_stage_resample_compact_async(mcl_engine_t *h, const void *d_chunks, int3
                                      const uint64_t *totals, int64_t n_per_shard, int32_t self_shard, int64_t child_first,
                                      int64_t n_children_total, const double action[3])
 {
-    if (h && h->kld_on) return kld_refuse_stage(h);
-    if (h && h->recov_on) return recov_refuse_stage(h);
-    if (h && h->lf_on) return lf_refuse_stage(h);
+    if (const int rc = refuse_stage(h)) return rc;
     return stage_resample_compact_launch(h, d_chunks, n_shards, chunk_entries, counts, totals, n_per_shard, self_shard, child_first,
                                          n_children_total, action, nullptr);
 }
 
 int mcl_stage_rays_async(mcl_engine_t *h, const float *obs, int32_t n_beams, double *d_local_max)
 {
-    if (h && h->kld_on) return kld_refuse_stage(h);
-    if (h && h->recov_on) return recov_refuse_stage(h);
-    if (h && h->lf_on) return lf_refuse_stage(h);
+    if (const int rc = refuse_stage(h)) return rc;
     if (!h || !d_local_max) return MCL_ERR_INVALID_ARG;
     const int rc = stage_rays_launch(h, obs, n_beams, false, d_local_max);
     if (rc) return rc;
@@ -3576,9 +2903,7 @@ int mcl_stage_rays_async(mcl_engine_t *h, const float *obs, int32_t n_beams, dou
 
 int mcl_stage_weights_async(mcl_engine_t *h, const double *d_global_max, double *d_vec, int32_t n_shards, int32_t self_shard)
 {
-    if (h && h->kld_on) return kld_refuse_stage(h);
-    if (h && h->recov_on) return recov_refuse_stage(h);
-    if (h && h->lf_on) return lf_refuse_stage(h);
+    if (const int rc = refuse_stage(h)) return rc;
     if (!h || !d_global_max || !d_vec || n_shards <= 0 || n_shards > mcl::kMaxShards || self_shard < 0 || self_shard >= n_shards)
         return MCL_ERR_INVALID_ARG;
     if (!h->stage_async_rays) return fail(h, MCL_ERR_NOT_READY, "mcl_stage_rays_async first");
@@ -3593,9 +2918,7 @@ int mcl_stage_weights_async(mcl_engine_t *h, const double *d_global_max, double 
 
 int mcl_stage_complete(mcl_engine_t *h, const double global_sums[5], int32_t *redo)
 {
-    if (h && h->kld_on) return kld_refuse_stage(h);
-    if (h && h->recov_on) return recov_refuse_stage(h);
-    if (h && h->lf_on) return lf_refuse_stage(h);
+    if (const int rc = refuse_stage(h)) return rc;
     if (!h || !global_sums || !redo) return MCL_ERR_INVALID_ARG;
     if (!h->stage_async_rays || !h->stage_async_weights) return fail(h, MCL_ERR_NOT_READY, "mcl_stage_rays_async and mcl_stage_weights_async first");
     h->stage_async_rays = h->stage_async_weights = false;
@@ -3615,7 +2938,6 @@ int mcl_stage_complete(mcl_engine_t *h, const double global_sums[5], int32_t *re
     return MCL_OK;
 }
 
-
 int mcl_scan_weights(mcl_engine_t *h, const uint64_t *d_q, uint64_t *d_cdf, int64_t n, uint64_t offset)
 {
     if (!h || !d_q || !d_cdf || n <= 0) return MCL_ERR_INVALID_ARG;
@@ -3633,41 +2955,8 @@ int mcl_scan_weights(mcl_engine_t *h, const uint64_t *d_q, uint64_t *d_cdf, int6
     return MCL_OK;
 }
 
-
-}  // extern "C"
-
-// ---- what mcl_comm.hip / mcl_group.hip reach of this translation unit (mcl_engine_internal.h)
+// ---- the few kernels mcl_comm.hip / mcl_group.hip launch themselves (mcl_engine_internal.h): the kernels are compiled here only
 namespace mcl_host {
-int fail(mcl_engine *h, int code, const char *msg) { return ::fail(h, code, msg); }
-int fail(mcl_engine *h, int code, const std::string &msg) { return ::fail(h, code, msg); }
-std::string &create_error() { return g_create_error; }
-bool ready(mcl_engine *h, bool need_particles) { return ::ready(h, need_particles); }
-float elapsed(hipEvent_t a, hipEvent_t b) { return ::elapsed(a, b); }
-void graph_reset(mcl_engine *h) { ::graph_reset(h); }
-int scan_weights(mcl_engine *h, const uint64_t *d_q, uint64_t *d_cdf, int64_t n, uint64_t offset, uint64_t *d_total) { return ::scan_weights(h, d_q, d_cdf, n, offset, d_total); }
-void unpack_result(mcl_engine *h) { ::unpack_result(h); }
-bool kld_grid(const mcl_kld_config_t *k, uint32_t W, uint32_t H, float res, int64_t &nx, int64_t &ny, uint64_t &bits) { return ::kld_grid(k, W, H, res, nx, ny, bits); }
-mcl::KldArgs kld_args_of(const mcl_kld_config_t *k, int64_t nx, int64_t ny, double ox, double oy) { return ::kld_args_of(k, nx, ny, ox, oy); }
-int layout_adopt(mcl_engine *h, int64_t n) { return ::layout_adopt(h, n); }
-int set_particles_impl(mcl_engine_t *h, const double *xyz, const double *weights, int64_t n, const double *weight_scale) { return ::set_particles_impl(h, xyz, weights, n, weight_scale); }
-int stage_resample_launch(mcl_engine_t *h, const ParentSource &src, const uint64_t *d_cdf, int64_t n_parents, uint64_t q_total,
-                          int64_t child_first, int64_t n_children_total, const double action[3])
-{
-    return ::stage_resample_launch(h, src, d_cdf, n_parents, q_total, child_first, n_children_total, action);
-}
-int export_compact_launch(mcl_engine_t *h, void *d_chunk, int64_t chunk_entries, int dst_device, hipStream_t stream) { return ::export_compact_launch(h, d_chunk, chunk_entries, dst_device, stream); }
-int stage_resample_compact_launch(mcl_engine_t *h, const void *d_chunks, int32_t n_shards, int64_t chunk_entries, const int64_t *counts,
-                                  const uint64_t *totals, int64_t n_per_shard, int32_t self_shard, int64_t child_first,
-                                  int64_t n_children_total, const double action[3], unsigned long long *remote_count)
-{
-    return ::stage_resample_compact_launch(h, d_chunks, n_shards, chunk_entries, counts, totals, n_per_shard, self_shard, child_first, n_children_total, action, remote_count);
-}
-int stage_rays_launch(mcl_engine_t *h, const float *obs, int32_t n_beams, bool force_skip, double *d_max_out) { return ::stage_rays_launch(h, obs, n_beams, force_skip, d_max_out); }
-void stage_rays_note(mcl_engine_t *h) { ::stage_rays_note(h); }
-int stage_rays_finish(mcl_engine_t *h, const float *obs, int32_t n_beams) { return ::stage_rays_finish(h, obs, n_beams); }
-int stage_weights_launch(mcl_engine_t *h, double global_max_logw, const double *d_global_max) { return ::stage_weights_launch(h, global_max_logw, d_global_max); }
-int stage_weights_finish(mcl_engine_t *h) { return ::stage_weights_finish(h); }
-void stage_commit_carry(mcl_engine_t *h) { ::stage_commit_carry(h); }
 void launch_copy_double(hipStream_t stream, const double *src, double *dst) { hipLaunchKernelGGL(mcl::k_copy_double, dim3(1), dim3(1), 0, stream, src, dst); }
 void launch_set_double(hipStream_t stream, double *dst, double v) { hipLaunchKernelGGL(mcl::k_set_double, dim3(1), dim3(1), 0, stream, dst, v); }
 void launch_spin_ms(hipStream_t stream, double ms) { hipLaunchKernelGGL(mcl::k_spin_ms, dim3(1), dim3(64), 0, stream, ms); }
@@ -3681,4 +2970,3 @@ void launch_pack_records(hipStream_t stream, const double *x, const double *y, c
 }
 void launch_group_max(hipStream_t stream, const mcl::GroupMaxArgs &a) { hipLaunchKernelGGL(mcl::k_group_max, dim3(1), dim3(1), 0, stream, a); }
 }  // namespace mcl_host
-

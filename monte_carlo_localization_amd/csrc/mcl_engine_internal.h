@@ -1,11 +1,12 @@
 // mcl_engine_internal.h -- what the translation units of libmcl_hip_engine.so share: the engine object, the status helpers, and
 // the handful of engine-side functions the sharded hosts are built on.  Not part of the ABI (include/mcl_hip_engine.h is).
 //   mcl_engine.hip   the engine: map / beams / particles, the update and its stages, every kernel
+//   mcl_host_math.hip  the host arithmetic (tables, fields, per-update scalars) and the ABI's mcl_host_*: no HIP, no mcl_engine
 //   mcl_comm.hip     mcl_comm_*: one process per GPU, the collectives of an update over RCCL on the engine's stream
 //   mcl_group.hip    mcl_group_*: several GPUs behind one handle, driven by one process (peer copies)
 //   mcl_cluster.hip  mcl_pose_clusters: the pose hypotheses of the particle set (its own kernels, called outside the update)
-// Only mcl_engine.hip includes the kernels (mcl_kernels.h); the other two reach the few kernels they launch through the
-// launch_* functions below.
+// Only mcl_engine.hip includes the kernels (mcl_kernels.h); mcl_comm.hip and mcl_group.hip reach the few kernels they launch
+// through the launch_* functions below.  Every function declared here is defined once, under this name.
 #pragma once
 #include "../../include/mcl_hip_engine.h"
 
@@ -17,6 +18,7 @@
 #include <vector>
 
 #include "mcl_types.h"
+#include "mcl_host_math.h"
 
 enum { EV_START = 0, EV_RESAMPLE, EV_QUERY, EV_RAYS, EV_SENSOR, EV_K0, EV_K1, EV_COUNT };   // K0..K1 bracket the dominant kernel
 
@@ -28,6 +30,9 @@ constexpr unsigned long long kExactCap = 1ull << 16;   // level-3 rays per launc
 constexpr int kResultWords = 18;
 constexpr int kResultStage = 40;             // h_result word that stages a host value on its way to the device
 constexpr int kResultStamp = 32;             // h_result word a small update's last kernel stamps (the host polls it)
+// An entry of a compact list as the shards exchange it (mcl_export_compact): [ccdf: 8 | crec: 32 | cidx: 4] bytes,
+// stored column by column in a chunk of chunk_entries entries (the ccdf column, then the crec column, then the cidx column)
+constexpr int kCompactEntryBytes = 44;
 
 struct mcl_comm;
 void comm_free(struct mcl_comm *c);        // mcl_comm.hip
@@ -309,7 +314,7 @@ struct ParentSource {
     bool keep = false;                                              // adaptive resampling kept the set: every particle is its own parent (motion only)
 };
 
-// ---- engine-side functions the sharded hosts use (defined in mcl_engine.hip)
+// ---- engine-side functions the sharded hosts and the clustering use (defined in mcl_engine.hip)
 namespace mcl_host {
 int fail(mcl_engine *h, int code, const char *msg);
 int fail(mcl_engine *h, int code, const std::string &msg);
@@ -325,8 +330,6 @@ float elapsed(hipEvent_t a, hipEvent_t b);
 void graph_reset(mcl_engine *h);
 int scan_weights(mcl_engine *h, const uint64_t *d_q, uint64_t *d_cdf, int64_t n, uint64_t offset, uint64_t *d_total);
 void unpack_result(mcl_engine *h);
-bool kld_grid(const mcl_kld_config_t *k, uint32_t W, uint32_t H, float res, int64_t &nx, int64_t &ny, uint64_t &bits);
-mcl::KldArgs kld_args_of(const mcl_kld_config_t *k, int64_t nx, int64_t ny, double ox, double oy);
 int layout_adopt(mcl_engine *h, int64_t n);
 int set_particles_impl(mcl_engine_t *h, const double *xyz, const double *weights, int64_t n, const double *weight_scale);
 int stage_resample_launch(mcl_engine_t *h, const ParentSource &src, const uint64_t *d_cdf, int64_t n_parents, uint64_t q_total,

@@ -259,7 +259,7 @@ int mcl_group_update(mcl_group_t *g, const double action[3], const float *obs, i
     // parent data (records or compact list, weights) may be read by its peers; ev_children[d] = device d has drawn its children
     // and no longer reads anybody's parent data.  The host waits only where it needs a value (the maxima, the sums).
     // Exchange: when every shard has a compact parent list (the usual case after an update with many beams) the devices copy
-    // each other's LISTS (44 B per particle that carries weight); otherwise every weight (8 B per particle) and the
+    // each other's LISTS (kCompactEntryBytes per particle that carries weight); otherwise every weight (8 B per particle) and the
     // selected parents are read where they live.
     // Adaptive resampling (E9, cfg.resample_neff_permille > 0): the set is kept -- no exchange, no resampling -- when the effective
     // sample size of the WHOLE set after the previous update is at least r / 1000 of it (mcl_update's rule on the group's sums)
@@ -298,7 +298,7 @@ int mcl_group_update(mcl_group_t *g, const double action[3], const float *obs, i
         if (keep) {
             rc = mcl_stage_keep(e, (int64_t)d * n, nt, action);
         } else if (compact) {
-            const size_t need = (size_t)G * (size_t)centries * 44;
+            const size_t need = (size_t)G * (size_t)centries * kCompactEntryBytes;
             if (need > g->chunks_capacity[d]) {
                 if (g->d_chunks[d]) { GHIP(g, hipStreamSynchronize(e->stream)); (void)hipFree(g->d_chunks[d]); g->d_chunks[d] = nullptr; }
                 g->chunks_capacity[d] = 0;
@@ -306,7 +306,7 @@ int mcl_group_update(mcl_group_t *g, const double action[3], const float *obs, i
                 g->chunks_capacity[d] = need;
             }
             for (int s = 0; s < G; ++s) {
-                rc = export_compact_launch(g->eng[s], g->d_chunks[d] + (size_t)s * (size_t)centries * 44, centries, e->cfg.device, e->stream);
+                rc = export_compact_launch(g->eng[s], g->d_chunks[d] + (size_t)s * (size_t)centries * kCompactEntryBytes, centries, e->cfg.device, e->stream);
                 if (rc) return gfail(g, rc, g->eng[s]->err);
             }
             rc = stage_resample_compact_launch(e, g->d_chunks[d], G, centries, counts, totals, n, d, (int64_t)d * n, nt, action, g->d_remote[d]);
@@ -398,7 +398,7 @@ int mcl_group_update(mcl_group_t *g, const double action[3], const float *obs, i
     // (lists are copied entry-exact, not as padded chunks: the device that holds the shortest list receives the most)
     uint64_t shortest = ~0ull;
     for (int d = 0; d < G; ++d) shortest = std::min<uint64_t>(shortest, compact ? (uint64_t)counts[d] : 0u);
-    g->bytes_weights = compact ? (listed - shortest) * 44u : (uint64_t)(G - 1) * (uint64_t)n * 8u;
+    g->bytes_weights = compact ? (listed - shortest) * (unsigned)kCompactEntryBytes : (uint64_t)(G - 1) * (uint64_t)n * 8u;
     g->bytes_parents = compact ? 0u : (uint64_t)remote * 32u;         // upper bound: children of remote parents x record size
     if (keep) { g->bytes_weights = 0; g->bytes_parents = 0; }         // nothing was exchanged
     g->compact_last = compact;

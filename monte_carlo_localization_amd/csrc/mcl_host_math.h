@@ -1,0 +1,30 @@
+// mcl_host_math.h -- the host arithmetic of the engine (mcl_host_math.hip): plain functions that neither call HIP nor touch a mcl_engine.
+// It builds the tables, fields and per-update scalars; the ABI's mcl_host_* entry points (same unit) expose them to the tests bit for bit.
+#pragma once
+#include "../../include/mcl_hip_engine.h"
+#include <cstdint>
+#include <vector>
+#include "mcl_types.h"
+
+namespace mcl_host {
+const char *bad_sensor_fields(const mcl_config_t &c);
+void build_sensor_table(const mcl_config_t &c, int P, std::vector<double> &t);
+void build_distance_field(const int8_t *grid, int W, int H, int Wp, int Hp, int Wps, std::vector<uint8_t> &dist);
+void build_directional_field(const int8_t *grid, int W, int H, int Wp, int Hp, int Wps, int sx, int sy, std::vector<uint8_t> &dist);
+void motion_scalars(const double action[3], double &dt, double &v, double &w);
+uint32_t systematic_offset(uint32_t seed_lo, uint32_t seed_hi, uint32_t update_idx);
+const char *kld_invalid(const mcl_kld_config_t *k, int64_t cap);
+bool kld_grid(const mcl_kld_config_t *k, uint32_t W, uint32_t H, float res, int64_t &nx, int64_t &ny, uint64_t &bits);
+mcl::KldArgs kld_args_of(const mcl_kld_config_t *k, int64_t nx, int64_t ny, double ox, double oy);
+int64_t kld_target(const mcl_kld_config_t *k, int64_t bins, int64_t n_current);
+const char *recov_invalid(const mcl_recovery_config_t *c);
+double recov_likelihood(const mcl_recovery_config_t &c, double max_logw, double sum_w, double denom, int n_beams);
+void recov_fold(const mcl_recovery_config_t &c, double &S, double &F, double l);
+double recov_p(double S, double F);
+uint64_t recov_threshold(double p);
+const char *lf_invalid(const mcl_likelihood_field_config_t *c);
+int lf_cap(const mcl_likelihood_field_config_t *c, float resolution);
+void lf_table(const mcl_config_t &cfg, const mcl_likelihood_field_config_t &c, double res, int K, std::vector<float> &t);
+const char *motion_invalid(const mcl_motion_config_t *c);
+const char *gaussian_factor(const double cov[9], double L[6]);
+}  // namespace mcl_host

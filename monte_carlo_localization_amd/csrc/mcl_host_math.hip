@@ -1,0 +1,678 @@
+// mcl_host_math.hip -- the host arithmetic of the engine: everything that neither calls HIP nor touches a mcl_engine.  The tables and
+// fields built here are defined bit for bit (compiled with the flags of the other units: -ffp-contract=off), and the mcl_host_*
+// entry points of the ABI (include/mcl_hip_engine.h) hand them to the tests as they are.  No kernels: mcl_kernels.h is not included;
+// the few __host__ __device__ rules shared with the kernels live in mcl_types.h (kld_bin), mcl_motion.h (odo_step) and mcl_wedge.h.
+#include "mcl_host_math.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "mcl_motion.h"
+#include "mcl_wedge.h"
+
+namespace mcl_host {
+
+// What the sensor model's fields must satisfy for the table to be a probability table (null: they do).  The reference does not
+// check them; here a NaN or a zero row would reach every log-weight (E5).
+const char *bad_sensor_fields(const mcl_config_t &c)
+{
+    const double z[4] = {c.z_hit, c.z_short, c.z_max, c.z_rand};
+    for (double v : z)
+        if (!std::isfinite(v) || v < 0.0) return "bad config (z_hit, z_short, z_max and z_rand must be finite and >= 0)";
+    if (z[0] == 0.0 && z[1] == 0.0 && z[2] == 0.0 && z[3] == 0.0) return "bad config (z_hit, z_short, z_max and z_rand are all 0)";
+    if (!std::isfinite(c.sigma_hit) || !(c.sigma_hit > 0.0)) return "bad config (sigma_hit must be finite and > 0)";
+    return nullptr;
+}
+
+// cpp:233-292, restated; column-major (d*(tw)+r).
+void build_sensor_table(const mcl_config_t &c, int P, std::vector<double> &t)
+{
+    const int tw = P + 1;
+    t.assign((size_t)tw * tw, 0.0);
+    for (int d = 0; d < tw; ++d) {
+        double norm = 0.0;
+        for (int r = 0; r < tw; ++r) {
+            double prob = 0.0;
+            double z = (double)(r - d);
+            prob += c.z_hit * std::exp(-(z * z) / (2.0 * c.sigma_hit * c.sigma_hit)) / (c.sigma_hit * std::sqrt(2.0 * M_PI));
+            if (r < d) prob += 2.0 * c.z_short * (d - r) / (double)d;
+            if (r == P) prob += c.z_max;
+            if (r < P) prob += c.z_rand * 1.0 / (double)P;
+            norm += prob;
+            t[(size_t)d * tw + r] = prob;
+        }
+        if (norm > 0)
+            for (int r = 0; r < tw; ++r) t[(size_t)d * tw + r] /= norm;
+    }
+}
+
+// Padded stop grid + skip-distance field.
+// Padded cell (xp,yp), xp in [0,W], yp in [0,H], stands for reference cell (max(xp-1,0), max(yp-1,0)):
+// the reference truncates toward zero (cpp:628-629), so pixel coordinates in (-1,0) read cell 0.
+// Everything outside the padded grid is "stop" (map boundary, cpp:632-636).
+//
+// skip(c) = how far the fixed-step march may jump from a sample inside cell c without being able to
+// land in a stop cell earlier.  Samples are exactly one pixel apart along the ray, so sample k+j lies at
+// Euclidean distance j from sample k; it can be inside stop cell t only if j >= dist(p_k, t) >= gap(c, t),
+// the distance between the two (closed) cell squares, with equality only for p_k on the boundary of c
+// (such samples are caught by the kernel's boundary guard).  Hence skip(c) = floor(min_t gap(c,t)) + 1.
+// gap^2(c,t) = max(|dx|-1,0)^2 + max(|dy|-1,0)^2 is the squared centre distance from c to the 3x3
+// dilation of t, so one exact integer squared-EDT (Felzenszwalb & Huttenlocher lower envelopes) of the
+// dilated stop set gives it.  Stop cells get 0; values are capped at 255.
+static void edt_1d(const int64_t *f, int n, int64_t *d, int *v, double *z)
+{
+    const int64_t INF = (int64_t)1 << 40;
+    int k = 0;
+    v[0] = 0; z[0] = -1e30; z[1] = 1e30;
+    for (int q = 1; q < n; ++q) {
+        if (f[q] >= INF) continue;
+        while (true) {
+            if (f[v[k]] >= INF) { v[k] = q; z[k] = -1e30; z[k + 1] = 1e30; break; }
+            double s = ((double)(f[q] + (int64_t)q * q) - (double)(f[v[k]] + (int64_t)v[k] * v[k])) / (2.0 * q - 2.0 * v[k]);
+            if (s <= z[k]) { --k; if (k < 0) { k = 0; v[0] = q; z[0] = -1e30; z[1] = 1e30; break; } continue; }
+            ++k; v[k] = q; z[k] = s; z[k + 1] = 1e30;
+            break;
+        }
+    }
+    k = 0;
+    for (int q = 0; q < n; ++q) {
+        while (z[k + 1] < q) ++k;
+        int64_t dq = (int64_t)(q - v[k]);
+        d[q] = (f[v[k]] >= INF) ? INF : dq * dq + f[v[k]];
+    }
+}
+
+void build_distance_field(const int8_t *grid, int W, int H, int Wp, int Hp, int Wps, std::vector<uint8_t> &dist)
+{
+    // work grid = padded grid plus a one-cell stop border on every side
+    const int Ww = Wp + 2, Hw = Hp + 2;
+    std::vector<uint8_t> stop((size_t)Hw * Ww, 1), dil((size_t)Hw * Ww, 0);
+    for (int yp = 0; yp < Hp; ++yp)
+        for (int xp = 0; xp < Wp; ++xp) {
+            int gx = std::max(xp - 1, 0), gy = std::max(yp - 1, 0);
+            stop[(size_t)(yp + 1) * Ww + xp + 1] = grid[(size_t)gy * W + gx] > 50;
+        }
+    for (int y = 0; y < Hw; ++y)
+        for (int x = 0; x < Ww; ++x) {
+            if (!stop[(size_t)y * Ww + x]) continue;
+            for (int dy = -1; dy <= 1; ++dy)
+                for (int dx = -1; dx <= 1; ++dx) {
+                    int yy = y + dy, xx = x + dx;
+                    if (yy >= 0 && yy < Hw && xx >= 0 && xx < Ww) dil[(size_t)yy * Ww + xx] = 1;
+                }
+        }
+    const int64_t INF = (int64_t)1 << 40;
+    std::vector<int64_t> g((size_t)Hw * Ww);
+    const int nmax = std::max(Ww, Hw);
+    std::vector<int64_t> f(nmax), d(nmax);
+    std::vector<int> v(nmax + 1);
+    std::vector<double> z(nmax + 2);
+    for (int x = 0; x < Ww; ++x) {            // columns
+        for (int y = 0; y < Hw; ++y) f[y] = dil[(size_t)y * Ww + x] ? 0 : INF;
+        edt_1d(f.data(), Hw, d.data(), v.data(), z.data());
+        for (int y = 0; y < Hw; ++y) g[(size_t)y * Ww + x] = d[y];
+    }
+    dist.assign((size_t)Hp * Wps, 0);
+    for (int y = 1; y <= Hp; ++y) {           // rows
+        for (int x = 0; x < Ww; ++x) f[x] = g[(size_t)y * Ww + x];
+        edt_1d(f.data(), Ww, d.data(), v.data(), z.data());
+        for (int x = 1; x <= Wp; ++x) {
+            int val = 0;
+            if (!stop[(size_t)y * Ww + x]) {
+                int64_t g2 = d[x];
+                int64_t r = (int64_t)std::sqrt((double)g2);
+                while (r * r > g2) --r;
+                while ((r + 1) * (r + 1) <= g2) ++r;
+                val = (int)std::min<int64_t>(r + 1, 255);
+            }
+            dist[(size_t)(y - 1) * Wps + (x - 1)] = (uint8_t)val;
+        }
+    }
+}
+
+// Directional skip field for k_rays_quad, quadrant q = (sx, sy): a ray whose direction has sign sx in x and sy
+// in y can only ever enter cells t with sx*(t_x - c_x) >= 0 and sy*(t_y - c_y) >= 0, so only those stop cells
+// bound the jump: skip_q(c) = floor(min over forward stop cells t of gap(c, t)) + 1, gap as in
+// build_distance_field.  Walls beside or behind a ray no longer shorten its jumps (-30 % probes on the
+// benchmark input).  Exact integer arithmetic: per row the forward x-gap h to the next stop, then per column
+// a one-sided squared distance transform (lower envelope of parabolas, sources only ahead of the query).
+void build_directional_field(const int8_t *grid, int W, int H, int Wp, int Hp, int Wps, int sx, int sy, std::vector<uint8_t> &dist)
+{
+    const int64_t INF = (int64_t)1 << 40;
+    // stop(xf, yf) in "forward" coordinates: xf = sx > 0 ? xp : Wp-1-xp, same for y
+    auto stop_at = [&](int xf, int yf) -> bool {
+        int xp = sx > 0 ? xf : Wp - 1 - xf, yp = sy > 0 ? yf : Hp - 1 - yf;
+        int gx = std::max(xp - 1, 0), gy = std::max(yp - 1, 0);
+        return grid[(size_t)gy * W + gx] > 50;
+    };
+    // h[yf][xf]: gap in x to the nearest stop at x' >= xf in the same row (the cell just outside the grid is a stop)
+    std::vector<int32_t> h((size_t)(Hp + 1) * Wp);
+    for (int yf = 0; yf < Hp; ++yf) {
+        int nxt = Wp;
+        for (int xf = Wp - 1; xf >= 0; --xf) {
+            if (stop_at(xf, yf)) nxt = xf;
+            h[(size_t)yf * Wp + xf] = std::max(nxt - xf - 1, 0);
+        }
+    }
+    for (int xf = 0; xf < Wp; ++xf) h[(size_t)Hp * Wp + xf] = 0;      // the row beyond the grid is all stop
+    dist.assign((size_t)Hp * Wps, 0);
+    std::vector<int> vp(Hp + 2);          // envelope: source positions (in r = decreasing-y order)
+    std::vector<double> z(Hp + 3);
+    std::vector<int64_t> hg(Hp + 2);      // heights of the sources
+    for (int xf = 0; xf < Wp; ++xf) {
+        // g2(yf) = min( h(yf)^2 , min over p >= yf of (p - yf)^2 + h(p+1)^2 ): sources p = Hp-1 .. 0 arrive in
+        // decreasing p, i.e. increasing r = Hp-1-p; the query sits at the newest source's position.
+        int k = -1;
+        for (int yf = Hp - 1; yf >= 0; --yf) {
+            const int r = Hp - 1 - yf;
+            const int64_t hv = h[(size_t)(yf + 1) * Wp + xf];
+            const int64_t fh = hv * hv;
+            // insert parabola (r, fh)
+            while (true) {
+                if (k < 0) { k = 0; vp[0] = r; hg[0] = fh; z[0] = -1e30; z[1] = 1e30; break; }
+                double sI = ((double)(fh + (int64_t)r * r) - (double)(hg[k] + (int64_t)vp[k] * vp[k])) / (2.0 * r - 2.0 * vp[k]);
+                if (sI <= z[k]) { --k; continue; }
+                ++k; vp[k] = r; hg[k] = fh; z[k] = sI; z[k + 1] = 1e30;
+                break;
+            }
+            // query at r: the parabola whose interval contains r
+            int kk = k;
+            while (z[kk] > (double)r) --kk;
+            int64_t dq = (int64_t)(r - vp[kk]);
+            int64_t g2 = dq * dq + hg[kk];
+            // exactness of the envelope near interval ends: also try the neighbours
+            if (kk > 0) { int64_t d2 = (int64_t)(r - vp[kk - 1]); g2 = std::min(g2, d2 * d2 + hg[kk - 1]); }
+            if (kk < k) { int64_t d2 = (int64_t)(r - vp[kk + 1]); g2 = std::min(g2, d2 * d2 + hg[kk + 1]); }
+            const int64_t hs = h[(size_t)yf * Wp + xf];
+            g2 = std::min(g2, hs * hs);
+            int val = 0;
+            if (!stop_at(xf, yf)) {
+                int64_t rt = (int64_t)std::sqrt((double)g2);
+                while (rt * rt > g2) --rt;
+                while ((rt + 1) * (rt + 1) <= g2) ++rt;
+                val = (int)std::min<int64_t>(rt + 1, 255);
+            }
+            int xp = sx > 0 ? xf : Wp - 1 - xf, yp = sy > 0 ? yf : Hp - 1 - yf;
+            dist[(size_t)yp * Wps + xp] = (uint8_t)val;
+        }
+    }
+    (void)INF; (void)H;
+}
+
+// cpp:452-471
+void motion_scalars(const double action[3], double &dt, double &v, double &w)
+{
+    dt = 0.01; v = 0.0; w = 0.0;
+    double fd = action[0], ad = action[2];
+    if (std::abs(fd) > 0.001) {
+        if (std::abs(fd) < 0.1) dt = std::abs(fd) / 1.0;
+        else dt = std::abs(fd) / 5.0;
+        dt = std::max(0.001, std::min(dt, 0.1));
+        v = fd / dt;
+    }
+    if (std::abs(ad) > 0.001) w = ad / dt;
+}
+
+// The 32-bit offset of a systematic resampling draw, one per update: word 0 of Philox-4x32-10 stream 3, counter (0, update_idx, 3, 0),
+// key (seed_lo, seed_hi) -- the host's one restatement of philox4x32 (mcl_device_math.h).
+uint32_t systematic_offset(uint32_t seed_lo, uint32_t seed_hi, uint32_t update_idx)
+{
+    uint32_t c0 = 0, c1 = update_idx, c2 = 3, c3 = 0, k0 = seed_lo, k1 = seed_hi;
+    for (int r = 0; r < 10; ++r) {
+        uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3; k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return c0;
+}
+
+// ---- KLD-adaptive particle count (mcl_set_kld)
+// why a KLD configuration is refused (null: it is not); cap > 0: the engine's max_particles
+const char *kld_invalid(const mcl_kld_config_t *k, int64_t cap)
+{
+    if (!(k->min_particles >= 1 && k->min_particles <= k->max_particles)) return "KLD: need 1 <= min_particles <= max_particles";
+    if (k->max_particles >= MCL_MAX_TOTAL_PARTICLES) return "KLD: max_particles must stay below 2^27";
+    if (cap > 0 && k->max_particles > cap) return "KLD: max_particles exceeds the engine's max_particles";
+    if (!(std::isfinite(k->err) && k->err > 0.0)) return "KLD: err must be finite and positive";
+    if (!(std::isfinite(k->z) && k->z >= 0.0)) return "KLD: z must be finite and non-negative";
+    if (!(std::isfinite(k->bin_x_m) && k->bin_x_m > 0.0 && std::isfinite(k->bin_y_m) && k->bin_y_m > 0.0))
+        return "KLD: bin sizes must be finite and positive";
+    if (k->n_theta_bins < 1) return "KLD: n_theta_bins must be >= 1";
+    if (k->round_to < 1) return "KLD: round_to must be >= 1";
+    if (k->shrink_permille < 0 || k->shrink_permille > 1000) return "KLD: shrink_permille must be in [0, 1000]";
+    if (k->reserved != 0) return "KLD: reserved must be 0";
+    return nullptr;
+}
+
+// the bin grid over a W x H map (false: more than 2^31 bits)
+bool kld_grid(const mcl_kld_config_t *k, uint32_t W, uint32_t H, float res, int64_t &nx, int64_t &ny, uint64_t &bits)
+{
+    const double fx = std::ceil((double)W * (double)res / k->bin_x_m), fy = std::ceil((double)H * (double)res / k->bin_y_m);
+    if (!(fx >= 1.0 && fy >= 1.0 && fx * fy * (double)k->n_theta_bins + 1.0 <= 2147483648.0)) return false;
+    nx = (int64_t)fx; ny = (int64_t)fy;
+    bits = (uint64_t)(nx * ny * k->n_theta_bins) + 1;
+    return true;
+}
+
+mcl::KldArgs kld_args_of(const mcl_kld_config_t *k, int64_t nx, int64_t ny, double ox, double oy)
+{
+    mcl::KldArgs a{};
+    a.ox = ox; a.oy = oy;
+    a.inv_bx = 1.0 / k->bin_x_m; a.inv_by = 1.0 / k->bin_y_m;
+    a.th_scale = (double)k->n_theta_bins / (2.0 * 3.14159265358979323846);
+    a.nx = (uint32_t)nx; a.ny = (uint32_t)ny; a.nth = (uint32_t)k->n_theta_bins;
+    a.nx_d = (double)nx; a.ny_d = (double)ny;
+    a.nth_d = (double)k->n_theta_bins; a.inv_nth = 1.0 / (double)k->n_theta_bins;
+    a.outside = (uint32_t)(nx * ny * k->n_theta_bins);
+    return a;
+}
+
+int64_t kld_target(const mcl_kld_config_t *k, int64_t bins, int64_t n_current)
+{
+    int64_t target = k->max_particles;
+    if (bins > 1) {
+        const double km1 = (double)(bins - 1);
+        const double a = 2.0 / (9.0 * km1);
+        const double b = 1.0 - a + std::sqrt(a) * k->z;
+        const double n = std::ceil(km1 / (2.0 * k->err) * (b * b * b));
+        if (n < (double)k->max_particles) {            // (rounding up and clamping cannot go below max from there)
+            const int64_t r = k->round_to, ni = n > 0.0 ? (int64_t)n : 0;
+            target = std::min(std::max((ni + r - 1) / r * r, k->min_particles), k->max_particles);
+        }
+    }
+    if (target <= n_current && target * 1000 >= n_current * (int64_t)k->shrink_permille) return n_current;
+    return target;
+}
+
+// ---- recovery by random-particle injection (mcl_set_recovery): host double throughout
+const char *recov_invalid(const mcl_recovery_config_t *c)
+{
+    if (!(std::isfinite(c->alpha_slow) && std::isfinite(c->alpha_fast) && c->alpha_slow > 0.0 && c->alpha_slow < c->alpha_fast &&
+          c->alpha_fast <= 1.0))
+        return "recovery: need 0 < alpha_slow < alpha_fast <= 1";
+    if (c->per_beam != 0 && c->per_beam != 1) return "recovery: per_beam must be 0 or 1";
+    if (c->reserved != 0) return "recovery: reserved must be 0";
+    return nullptr;
+}
+
+static double recov_logaddexp(double a, double b)
+{
+    const double hi = a > b ? a : b, lo = a > b ? b : a;
+    if (hi == -INFINITY) return -INFINITY;
+    return hi + std::log1p(std::exp(lo - hi));
+}
+
+// l of one update: m + log(sum_w) - log(denom), -inf for m = -inf, divided by the beam count with per_beam
+double recov_likelihood(const mcl_recovery_config_t &c, double max_logw, double sum_w, double denom, int n_beams)
+{
+    double l = max_logw == -INFINITY ? -INFINITY : max_logw + std::log(sum_w) - std::log(denom);
+    if (c.per_beam) l = l / (double)n_beams;
+    return l;
+}
+
+// folds l into (S, F) (NaN: unset); a NaN l changes nothing
+void recov_fold(const mcl_recovery_config_t &c, double &S, double &F, double l)
+{
+    if (std::isnan(l)) return;
+    S = std::isnan(S) ? l : recov_logaddexp(S + std::log1p(-c.alpha_slow), l + std::log(c.alpha_slow));
+    F = std::isnan(F) ? l : recov_logaddexp(F + std::log1p(-c.alpha_fast), l + std::log(c.alpha_fast));
+}
+
+double recov_p(double S, double F)
+{
+    if (std::isnan(S) || std::isnan(F) || S == -INFINITY) return 0.0;
+    const double p = 1.0 - std::exp(F - S);
+    return p > 0.0 ? (p < 1.0 ? p : 1.0) : 0.0;
+}
+
+uint64_t recov_threshold(double p) { return (uint64_t)(p * 9007199254740992.0); }     // floor(p * 2^53), p in [0, 1]
+
+// ---- likelihood-field sensor model (mcl_set_likelihood_field): the field on the device, the table in host double
+const char *lf_invalid(const mcl_likelihood_field_config_t *c)
+{
+    const double z[2] = {c->z_hit, c->z_rand};
+    for (double v : z)
+        if (!std::isfinite(v) || v < 0.0) return "likelihood field: z_hit and z_rand must be finite and >= 0";
+    if (z[0] == 0.0 && z[1] == 0.0) return "likelihood field: z_hit and z_rand are both 0";
+    if (!(std::isfinite(c->sigma_hit_m) && c->sigma_hit_m > 0.0)) return "likelihood field: sigma_hit_m must be finite and > 0";
+    if (!(std::isfinite(c->max_occ_dist_m) && c->max_occ_dist_m > 0.0)) return "likelihood field: max_occ_dist_m must be finite and > 0";
+    if (c->reserved[0] != 0 || c->reserved[1] != 0) return "likelihood field: reserved must be 0";
+    return nullptr;
+}
+
+// K = ceil((max_occ_dist / res)^2) (LF1), res the float resolution widened; -1 above 65535 (D is uint16)
+int lf_cap(const mcl_likelihood_field_config_t *c, float resolution)
+{
+    const double q = c->max_occ_dist_m / (double)resolution;
+    const double k = std::ceil(q * q);
+    return k <= 65535.0 ? (int)k : -1;
+}
+
+// LF2: Lf[k] for 0 <= k < K, Lf[K] at the distance max_occ_dist_m; log(0) = -inf
+void lf_table(const mcl_config_t &cfg, const mcl_likelihood_field_config_t &c, double res, int K, std::vector<float> &t)
+{
+    t.resize((size_t)K + 1);
+    const double res2 = res * res, den = 2.0 * c.sigma_hit_m * c.sigma_hit_m, rnd = c.z_rand / cfg.max_range_m;
+    const double inv_squash = 1.0 / cfg.squash_factor;
+    for (int k = 0; k <= K; ++k) {
+        const double e = k < K ? std::exp(-((double)k * res2) / den) : std::exp(-(c.max_occ_dist_m * c.max_occ_dist_m) / den);
+        t[(size_t)k] = (float)(std::log(c.z_hit * e + rnd) * inv_squash);
+    }
+}
+
+// LF1 on the host: exact squared distances from the lower envelopes of edt_1d (columns, then rows), clamped to K
+static void lf_field_host(const int8_t *grid, int W, int H, int K, uint16_t *out)
+{
+    const int64_t INF = (int64_t)1 << 40;
+    const int n = std::max(W, H);
+    std::vector<int64_t> f((size_t)n), d((size_t)n), col((size_t)W * H);
+    std::vector<int> v((size_t)n);
+    std::vector<double> z((size_t)n + 1);
+    for (int x = 0; x < W; ++x) {
+        for (int y = 0; y < H; ++y) f[(size_t)y] = grid[(size_t)y * W + x] > 50 ? 0 : INF;
+        edt_1d(f.data(), H, d.data(), v.data(), z.data());
+        for (int y = 0; y < H; ++y) col[(size_t)y * W + x] = d[(size_t)y];
+    }
+    for (int y = 0; y < H; ++y) {
+        edt_1d(col.data() + (size_t)y * W, W, d.data(), v.data(), z.data());
+        for (int x = 0; x < W; ++x) out[(size_t)y * W + x] = (uint16_t)std::min<int64_t>(d[(size_t)x], K);
+    }
+}
+
+// ---- odometry motion models and the Gaussian pose initialisation (the header's M1-M6 / G1) ----
+const char *motion_invalid(const mcl_motion_config_t *c)
+{
+    if (c->model != MCL_MOTION_REFERENCE && c->model != MCL_MOTION_DIFF && c->model != MCL_MOTION_OMNI) return "motion model: unknown model";
+    if (c->reserved != 0) return "motion model: reserved must be 0";
+    const double v[7] = {c->alpha1, c->alpha2, c->alpha3, c->alpha4, c->alpha5, c->floor_trans_m, c->floor_rot_rad};
+    for (double e : v)
+        if (!std::isfinite(e) || e < 0.0) return "motion model: the alphas and floors must be finite and >= 0";
+    return nullptr;
+}
+
+static double odo_norm(double z) { return std::atan2(std::sin(z), std::cos(z)); }
+static double odo_adiff(double a, double b)
+{
+    const double PI = 3.14159265358979323846;
+    a = odo_norm(a); b = odo_norm(b);
+    const double d1 = a - b;
+    double d2 = 2.0 * PI - std::fabs(d1);
+    if (d1 > 0.0) d2 = -d2;
+    return std::fabs(d1) < std::fabs(d2) ? d1 : d2;
+}
+
+// mcl_device_math.h's normalize_angle on the host
+static double host_normalize_angle(double a)
+{
+    const double PI = 3.14159265358979323846;
+    int it = 0;
+    while (a > PI && it < 64) { a -= 2.0 * PI; ++it; }
+    while (a < -PI && it < 128) { a += 2.0 * PI; ++it; }
+    if (it >= 64 && (a > PI || a < -PI)) a = std::remainder(a, 2.0 * PI);
+    return a;
+}
+
+// G1: the lower Cholesky factor of a symmetric positive semi-definite 3 x 3 matrix (row-major), L = {L00, L10, L11, L20, L21, L22}
+const char *gaussian_factor(const double cov[9], double L[6])
+{
+    double amax = 0.0, dmax = 0.0;
+    for (int i = 0; i < 9; ++i) {
+        if (!std::isfinite(cov[i])) return "gaussian init: the covariance must be finite";
+        amax = std::max(amax, std::fabs(cov[i]));
+    }
+    for (int i = 0; i < 3; ++i) {
+        dmax = std::max(dmax, cov[4 * i]);
+        for (int j = 0; j < i; ++j)
+            if (std::fabs(cov[3 * i + j] - cov[3 * j + i]) > 1e-12 * amax) return "gaussian init: the covariance must be symmetric";
+    }
+    const double tol = 1e-12 * dmax;
+    double l[3][3] = {};
+    for (int j = 0; j < 3; ++j) {
+        double p = cov[4 * j];
+        for (int k = 0; k < j; ++k) p -= l[j][k] * l[j][k];
+        if (std::fabs(p) <= tol) continue;               // a zero pivot: the column stays zero
+        if (p < 0.0) return "gaussian init: the covariance must be positive semi-definite";
+        l[j][j] = std::sqrt(p);
+        for (int i = j + 1; i < 3; ++i) {
+            double v = cov[3 * i + j];
+            for (int k = 0; k < j; ++k) v -= l[i][k] * l[j][k];
+            l[i][j] = v / l[j][j];
+        }
+    }
+    L[0] = l[0][0]; L[1] = l[1][0]; L[2] = l[1][1]; L[3] = l[2][0]; L[4] = l[2][1]; L[5] = l[2][2];
+    return nullptr;
+}
+
+}  // namespace mcl_host
+
+using namespace mcl_host;
+
+extern "C" {
+
+void mcl_default_config(mcl_config_t *c)
+{
+    if (!c) return;
+    std::memset(c, 0, sizeof(*c));
+    c->max_particles = 2000;       // cpp:24, yaml:6
+    c->device = 0;
+    c->seed = 0;
+    c->max_range_m = 12.0;         // cpp:27
+    c->z_hit = 0.80; c->z_short = 0.01; c->z_max = 0.07; c->z_rand = 0.12; c->sigma_hit = 8.0;   // cpp:30-34
+    c->squash_factor = 2.2;        // cpp:26
+    c->motion_dispersion_x = 0.05; c->motion_dispersion_y = 0.025; c->motion_dispersion_theta = 0.25;   // cpp:35-37
+    c->resample_mode = MCL_RESAMPLE_MULTINOMIAL;
+    c->weight_mode = MCL_WEIGHT_LOG;
+    c->ray_kernel = MCL_RAYS_AUTO;
+}
+
+int mcl_host_sensor_table(const mcl_config_t *cfg, int32_t P, double *out, size_t n)
+{
+    if (!cfg || !out || P < 1 || n != (size_t)(P + 1) * (P + 1) || bad_sensor_fields(*cfg)) return MCL_ERR_INVALID_ARG;
+    std::vector<double> t;
+    build_sensor_table(*cfg, P, t);
+    std::memcpy(out, t.data(), n * sizeof(double));
+    return MCL_OK;
+}
+
+int mcl_host_skip_field_dir(const int8_t *data, uint32_t width, uint32_t height, int32_t quadrant, uint8_t *out, size_t n)
+{
+    if (!data || !out || width == 0 || height == 0 || quadrant < 0 || quadrant > 3 || n != (size_t)(width + 1) * (height + 1))
+        return MCL_ERR_INVALID_ARG;
+    static const int qsx[4] = {1, -1, -1, 1}, qsy[4] = {1, 1, -1, -1};
+    const int Wp = (int)width + 1, Hp = (int)height + 1, Wps = (Wp + 7) & ~7;
+    std::vector<uint8_t> d;
+    build_directional_field(data, (int)width, (int)height, Wp, Hp, Wps, qsx[quadrant], qsy[quadrant], d);
+    for (int y = 0; y < Hp; ++y) std::memcpy(out + (size_t)y * Wp, d.data() + (size_t)y * Wps, Wp);
+    return MCL_OK;
+}
+
+int mcl_host_skip_field_wedge(const int8_t *data, uint32_t width, uint32_t height, int32_t wedge, uint8_t *out, size_t n)
+{
+    if (!data || !out || width == 0 || height == 0 || wedge < 0 || wedge >= mcl::kWedges || n != (size_t)(width + 1) * (height + 1))
+        return MCL_ERR_INVALID_ARG;
+    const int W = (int)width, H = (int)height, Wp = W + 1, Hp = H + 1;
+    std::vector<int32_t> nxt((size_t)Wp * Hp), prv((size_t)Wp * Hp);
+    for (int y = 0; y < Hp; ++y) {
+        auto stop = [&](int x) { return data[(size_t)std::max(y - 1, 0) * W + std::max(x - 1, 0)] > 50; };
+        int last = -1;
+        for (int x = 0; x < Wp; ++x) { if (stop(x)) last = x; prv[(size_t)y * Wp + x] = last; }
+        int next = Wp;
+        for (int x = Wp - 1; x >= 0; --x) { if (stop(x)) next = x; nxt[(size_t)y * Wp + x] = next; }
+    }
+    std::vector<mcl::WedgeRow> rows(2 * mcl::kWedgeR + 1);
+    mcl::wedge_rows(wedge, rows.data());
+    for (int y = 0; y < Hp; ++y)
+        for (int x = 0; x < Wp; ++x) out[(size_t)y * Wp + x] = (uint8_t)mcl::wedge_skip_cell(nxt.data(), prv.data(), Wp, Hp, x, y, rows.data());
+    return MCL_OK;
+}
+
+int mcl_host_skip_field(const int8_t *data, uint32_t width, uint32_t height, uint8_t *out, size_t n)
+{
+    if (!data || !out || width == 0 || height == 0 || n != (size_t)(width + 1) * (height + 1)) return MCL_ERR_INVALID_ARG;
+    const int Wp = (int)width + 1, Hp = (int)height + 1, Wps = (Wp + 7) & ~7;
+    std::vector<uint8_t> d;
+    build_distance_field(data, (int)width, (int)height, Wp, Hp, Wps, d);
+    for (int y = 0; y < Hp; ++y) std::memcpy(out + (size_t)y * Wp, d.data() + (size_t)y * Wps, Wp);
+    return MCL_OK;
+}
+
+int mcl_host_sweep_global_layout(uint32_t width, uint32_t height, int32_t max_range_px, int64_t out[6])
+{
+    if (!out || width == 0 || height == 0 || max_range_px < 1) return MCL_ERR_INVALID_ARG;
+    const int Wp = (int)width + 1, Hp = (int)height + 1;
+    const mcl::SweepGlobalLayout g = mcl::sweep_global_layout(Wp, Hp, max_range_px);
+    out[0] = g.ok ? 1 : 0; out[1] = g.pitch; out[2] = g.rows; out[3] = (int64_t)g.stride; out[4] = (int64_t)g.alloc;
+    out[5] = (int64_t)mcl::sweep_global_max_offset(g, Wp, Hp, max_range_px, mcl::kWedges - 1);
+    return MCL_OK;
+}
+
+void mcl_default_kld_config(mcl_kld_config_t *k)
+{
+    if (!k) return;
+    *k = mcl_kld_config_t{};
+    k->min_particles = 256; k->max_particles = 4194304;
+    k->err = 0.01; k->z = 2.326;
+    k->bin_x_m = 0.5; k->bin_y_m = 0.5;
+    k->n_theta_bins = 36; k->round_to = 256; k->shrink_permille = 800;
+}
+
+int mcl_host_kld_bins(const double *x, const double *y, const double *th, int64_t n, uint32_t width, uint32_t height,
+                      float resolution, double origin_x, double origin_y, const mcl_kld_config_t *k, int64_t *bins)
+{
+    if (!k || !bins || n < 0 || (n > 0 && (!x || !y || !th)) || width == 0 || height == 0 || !(resolution > 0.0f) ||
+        !std::isfinite(resolution) || kld_invalid(k, 0))
+        return MCL_ERR_INVALID_ARG;
+    int64_t nx = 0, ny = 0;
+    uint64_t nbits = 0;
+    if (!kld_grid(k, width, height, resolution, nx, ny, nbits)) return MCL_ERR_INVALID_ARG;
+    const mcl::KldArgs a = kld_args_of(k, nx, ny, origin_x, origin_y);
+    std::vector<uint32_t> b((size_t)n);
+    for (int64_t i = 0; i < n; ++i) b[(size_t)i] = mcl::kld_bin(a, x[i], y[i], th[i]);
+    std::sort(b.begin(), b.end());
+    *bins = (int64_t)(std::unique(b.begin(), b.end()) - b.begin());
+    return MCL_OK;
+}
+
+int mcl_host_kld_target(const mcl_kld_config_t *k, int64_t bins, int64_t n_current, int64_t *n_next)
+{
+    if (!k || !n_next || n_current < 0 || n_current >= MCL_MAX_TOTAL_PARTICLES || kld_invalid(k, 0)) return MCL_ERR_INVALID_ARG;
+    *n_next = kld_target(k, bins, n_current);
+    return MCL_OK;
+}
+
+void mcl_default_motion_config(mcl_motion_config_t *c)
+{
+    if (!c) return;
+    *c = mcl_motion_config_t{};
+    c->model = MCL_MOTION_DIFF;
+    c->alpha1 = c->alpha2 = c->alpha3 = c->alpha4 = c->alpha5 = 0.2;
+}
+
+int mcl_host_motion_scalars(const mcl_motion_config_t *c, const double action[3], double out[8])
+{
+    if (!c || !action || !out || motion_invalid(c) || c->model == MCL_MOTION_REFERENCE) return MCL_ERR_INVALID_ARG;
+    const double PI = 3.14159265358979323846;
+    const double dx = action[0], dy = action[1], dth = action[2];
+    const double trans = std::sqrt(dx * dx + dy * dy);
+    const double ft2 = c->floor_trans_m * c->floor_trans_m, fr2 = c->floor_rot_rad * c->floor_rot_rad;
+    const double t2 = trans * trans;
+    if (c->model == MCL_MOTION_DIFF) {
+        const double rot1 = trans < 0.01 ? 0.0 : std::atan2(dy, dx);
+        const double rot2 = odo_adiff(dth, rot1);
+        const double r1n = std::fmin(std::fabs(odo_adiff(rot1, 0.0)), std::fabs(odo_adiff(rot1, PI)));
+        const double r2n = std::fmin(std::fabs(odo_adiff(rot2, 0.0)), std::fabs(odo_adiff(rot2, PI)));
+        out[0] = rot1; out[1] = trans; out[2] = rot2;
+        out[3] = std::sqrt(c->alpha1 * (r1n * r1n) + c->alpha2 * t2 + fr2);
+        out[4] = std::sqrt(c->alpha3 * t2 + c->alpha4 * (r1n * r1n) + c->alpha4 * (r2n * r2n) + ft2);
+        out[5] = std::sqrt(c->alpha1 * (r2n * r2n) + c->alpha2 * t2 + fr2);
+    } else {
+        const double rot = dth, r2 = rot * rot;
+        out[0] = std::atan2(dy, dx); out[1] = trans; out[2] = rot;
+        out[3] = std::sqrt(c->alpha3 * t2 + c->alpha1 * r2 + ft2);
+        out[4] = std::sqrt(c->alpha4 * r2 + c->alpha2 * t2 + fr2);
+        out[5] = std::sqrt(c->alpha1 * r2 + c->alpha5 * t2 + ft2);
+    }
+    out[6] = 0.0; out[7] = 0.0;
+    return MCL_OK;
+}
+
+int mcl_host_motion_sample(const mcl_motion_config_t *c, const double action[3], const double *xyz, const double *normals, int64_t n,
+                           double *out)
+{
+    if (!xyz || !normals || !out || n < 0) return MCL_ERR_INVALID_ARG;
+    double s[8];
+    const int rc = mcl_host_motion_scalars(c, action, s);
+    if (rc) return rc;
+    mcl::OdoArgs o{};
+    o.model = c->model;
+    for (int i = 0; i < 6; ++i) o.s[i] = s[i];
+    for (int64_t m = 0; m < n; ++m) {
+        double x = xyz[m], y = xyz[n + m], th = xyz[2 * n + m];
+        mcl::odo_step(o, x, y, th, normals[3 * m], normals[3 * m + 1], normals[3 * m + 2]);
+        out[m] = x; out[n + m] = y; out[2 * n + m] = host_normalize_angle(th);
+    }
+    return MCL_OK;
+}
+
+int mcl_host_gaussian_factor(const double cov[9], double L[6])
+{
+    if (!cov || !L) return MCL_ERR_INVALID_ARG;
+    return gaussian_factor(cov, L) ? MCL_ERR_INVALID_ARG : MCL_OK;
+}
+
+void mcl_default_recovery_config(mcl_recovery_config_t *c)
+{
+    if (!c) return;
+    *c = mcl_recovery_config_t{};
+    c->alpha_slow = 0.001; c->alpha_fast = 0.1; c->per_beam = 1;
+}
+
+int mcl_host_recovery_step(const mcl_recovery_config_t *c, const double in[2], int32_t reset, double max_logw, double sum_w,
+                           double denom, int32_t n_beams, double out[2], double *p_next)
+{
+    if (!c || !in || !out || recov_invalid(c) || !(denom > 0.0) || n_beams < 1) return MCL_ERR_INVALID_ARG;
+    double S = reset ? NAN : in[0], F = reset ? NAN : in[1];
+    recov_fold(*c, S, F, recov_likelihood(*c, max_logw, sum_w, denom, n_beams));
+    out[0] = S; out[1] = F;
+    if (p_next) *p_next = recov_p(S, F);
+    return MCL_OK;
+}
+
+void mcl_default_likelihood_field_config(mcl_likelihood_field_config_t *c)
+{
+    if (!c) return;
+    *c = mcl_likelihood_field_config_t{};
+    c->z_hit = 0.5; c->z_rand = 0.5; c->sigma_hit_m = 0.2; c->max_occ_dist_m = 2.0;   // AMCL's defaults
+}
+
+int mcl_host_likelihood_field(const int8_t *data, uint32_t width, uint32_t height, float resolution,
+                              const mcl_likelihood_field_config_t *c, uint16_t *out, size_t n)
+{
+    if (!data || !out || !c || width == 0 || height == 0 || width > 200000 || height > 200000 || !(resolution > 0.0f) ||
+        !std::isfinite(resolution) || lf_invalid(c) || n != (size_t)width * height)
+        return MCL_ERR_INVALID_ARG;
+    const int K = lf_cap(c, resolution);
+    if (K < 0) return MCL_ERR_INVALID_ARG;
+    lf_field_host(data, (int)width, (int)height, K, out);
+    return MCL_OK;
+}
+
+int mcl_host_likelihood_table(const mcl_config_t *cfg, const mcl_likelihood_field_config_t *c, float resolution, float *out,
+                              size_t n, int32_t *K)
+{
+    if (!cfg || !c || !(resolution > 0.0f) || !std::isfinite(resolution) || lf_invalid(c)) return MCL_ERR_INVALID_ARG;
+    if (!(std::isfinite(cfg->max_range_m) && cfg->max_range_m > 0.0 && std::isfinite(cfg->squash_factor) && cfg->squash_factor > 0.0))
+        return MCL_ERR_INVALID_ARG;
+    const int k = lf_cap(c, resolution);
+    if (k < 0) return MCL_ERR_INVALID_ARG;
+    if (K) *K = k;
+    if (!out) return MCL_OK;
+    if (n != (size_t)k + 1) return MCL_ERR_INVALID_ARG;
+    std::vector<float> t;
+    lf_table(*cfg, *c, (double)resolution, k, t);
+    std::memcpy(out, t.data(), n * sizeof(float));
+    return MCL_OK;
+}
+
+}  // extern "C"

@@ -3,7 +3,7 @@
 // skip_k(c) bounds how far the fixed-step march (cast_ray, cpp:611-650) may jump from a sample inside cell c
 // when the ray's direction angle lies in wedge k = [2*pi*k/K, 2*pi*(k+1)/K]:
 //     skip_k(c) = floor( min over stop cells t REACHABLE from c in wedge k of gap(c, t) ) + 1,
-// gap(c,t)^2 = max(|dx|-1,0)^2 + max(|dy|-1,0)^2 as for the isotropic field (mcl_engine.hip).  A sample p in
+// gap(c,t)^2 = max(|dx|-1,0)^2 + max(|dy|-1,0)^2 as for the isotropic field (mcl_host_math.hip).  A sample p in
 // the half-open square of c and a later sample p + s*u (u in the wedge) inside the square of t differ by a
 // vector of the wedge that lies in the OPEN square (t - c) + (-1,1)^2, so t is reachable only if that open
 // square meets the closed wedge.  The wedge is the intersection of two half-planes n1.v >= 0, n2.v >= 0 inside
