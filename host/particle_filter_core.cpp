@@ -102,6 +102,19 @@ void ParticleFilterCore::initialize_particles_gaussian(const Vector3d &mean, con
     host_particles_stale_ = host_weights_stale_ = true;     // the cloud lives on the device: read back on demand
 }
 
+std::vector<float> ParticleFilterCore::expected_scan(const Vector3d &pose)
+{
+    std::vector<float> ranges;
+    if (!engine_ || !map_initialized_ || downsampled_angles_.empty()) return ranges;
+    const double p[3] = {pose[0], pose[1], pose[2]};             // 1 x 3 column-major
+    ranges.resize(downsampled_angles_.size());
+    if (mcl_query_scans(engine_, p, 1, ranges.data(), nullptr) != MCL_OK) {
+        fail("mcl_query_scans");
+        ranges.clear();
+    }
+    return ranges;
+}
+
 void ParticleFilterCore::set_motion_model(const mcl_motion_config_t *cfg)
 {
     if (!engine_) return;

@@ -86,6 +86,9 @@ class ParticleFilterCore {
 
     void MCL(const Vector3d &action, const std::vector<float> &observation);   // cpp:652-694
     Vector3d expected_pose();                                                   // cpp:696-716
+    // The scan the map predicts at `pose`: one range in metres per downsampled angle, max range where nothing is hit -- the
+    // "fake scan" of the reference's ancestors (mcl_query_scans; the particle set is not touched).  Empty on failure.
+    std::vector<float> expected_scan(const Vector3d &pose);
 
     // lazily synced copies of the reference's members (hpp:102-103); readers: visualize cpp:946-958,
     // get_current_pose cpp:903-908

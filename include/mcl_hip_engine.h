@@ -317,6 +317,52 @@ int mcl_pose_clusters(mcl_engine_t *h, const mcl_cluster_config_t *c, int32_t ma
                       uint64_t totals[3]);
 int mcl_get_cluster_labels(mcl_engine_t *h, int32_t *labels, int64_t n);   /* of the last mcl_pose_clusters; n == N */
 
+/* ---- pose query: expected scans and scan scores of poses that are not particles --------------------------
+ * mcl_query_scans casts the beams last set from K given poses -- the "fake scan" of the reference's ancestors, range_libc's
+ * calc_range_many -- and mcl_score_poses says how well a scan supports each pose: what a node needs to rank the means of
+ * mcl_pose_clusters, to publish the expected scan at its estimate, or to vet an /initialpose before
+ * mcl_init_particles_gaussian seeds a cloud there.  Neither touches the particle set.  poses_colmajor is K x 3 column-major
+ * (x, y, theta) like every particle array of this header, 1 <= K <= 65536; B is the number of beam angles set.
+ *   Q1 step.  steps[k * B + j] is E3's r for a particle at pose k and beam j: bit for bit what mcl_get_ray_steps16 reports for
+ *     a particle at that pose, whatever the pose (non-finite, |theta| >= 1e6, off the map, in an occupied cell).  The device
+ *     functions are those of the update's ray stage: the fp64 walk on the isotropic skip field with its guard (level 2), the
+ *     literal march (level 3) where the guard says so, where the pose is not sane, or with debug_force_exact.
+ *   Q2 metres.  ranges_m[k * B + j] is cast_ray's return (cpp:635 / 644 / 649): (float)(r * res) with res the map's float
+ *     resolution widened to double for r < MAX_RANGE_PX, and (float)max_range_m of the engine's config for a miss.
+ *   Q3 log-likelihood, under the sensor model the engine has now.  Beam model: E4's sum_j (double)L[obs_idx_j][r_kj] with
+ *     obs_idx from E2.  Likelihood field on: LF3-LF5, the in-order fp64 sum, by the update's own kernel on the query's buffers.
+ *     Either way the value is bit for bit what mcl_get_log_weights gives for a particle at that pose after
+ *     mcl_sensor_update(obs).  No fp64 atomics: one wave per pose, lane l adds beams l, l + 64, ... in order, then a fixed
+ *     butterfly -- under E4's condition the order is invisible, outside it the value is still reproducible.  weight_mode
+ *     PRODUCT refuses mcl_score_poses (MCL_ERR_INVALID_ARG); mcl_query_scans works in that mode.
+ *   Q4 agreement, in integers (exact), from cast rays under either sensor model.  Beam j is valid iff its reading is finite and
+ *     obs_idx_j < MAX_RANGE_PX; it agrees iff it is valid and |obs_idx_j - r_kj| <= tol_steps, 0 <= tol_steps <= MAX_RANGE_PX.
+ *     n_miss counts the rays of the pose with r = MAX_RANGE_PX, valid beam or not.
+ *   Q5 read-only.  Both calls use buffers of their own, allocated on the first call and grown with K * B (an engine that never
+ *     queries allocates nothing), and none of the update's scratch, tables of the staged observation included.  Captured graphs
+ *     and the warm small-update path stay valid: every later update is bit-identical to one of an engine that never queried.
+ *     One host wait per call, at its end.
+ *   Q6 where it works.  Any engine with a map and beam angles; no particles are needed (MCL_ERR_NOT_READY without a map or
+ *     beams).  Shards of a device group and engines with a communicator are accepted: map and beams are replicated and the call
+ *     is local.  MCL_ERR_INVALID_ARG for K outside [1, 65536], null poses (null obs / out for the score), n_beams != B,
+ *     tol_steps outside [0, MAX_RANGE_PX].
+ *   Cost scales with K * B, one lane per ray on the global skip field: made for tens to thousands of poses, not a substitute
+ *     for the update at particle-set sizes. */
+typedef struct {
+    double  log_likelihood;                 /* Q3                                                                             */
+    int32_t n_valid;                        /* Q4                                                                             */
+    int32_t n_agree;                        /* Q4                                                                             */
+    int32_t n_miss;                         /* rays of this pose that ended at step MAX_RANGE_PX (nothing hit in range)       */
+    int32_t reserved;
+} mcl_pose_score_t;
+/* ranges_m, steps: K * B entries each, pose-major; either may be NULL */
+int mcl_query_scans(mcl_engine_t *h, const double *poses_colmajor, int32_t K, float *ranges_m, uint16_t *steps);
+int mcl_score_poses(mcl_engine_t *h, const double *poses_colmajor, int32_t K, const float *obs, int32_t n_beams,
+                    int32_t tol_steps, mcl_pose_score_t *out /* K */);
+/* of the pose query: [0] rays of the last call the literal march decided (level 3), [1] bytes of device memory the query's
+ * buffers have asked for so far (0 on an engine that never queried) */
+int mcl_get_query_counters(const mcl_engine_t *h, uint64_t out[2]);
+
 /* ---- recovery by random-particle injection (augmented MCL, Probabilistic Robotics Table 8.3; AMCL's recovery_alpha_slow /
  *      recovery_alpha_fast) -------------------------------------------------------------------------------
  * Off by default.  With it on, a resampling mcl_update replaces each child, with probability p, by a pose drawn uniformly from

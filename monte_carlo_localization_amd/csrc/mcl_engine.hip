@@ -746,30 +746,13 @@ int launch_lfield(mcl_engine *h, const float *obs, int stride, int64_t n)
         HIPCHK(h, hipMalloc(&h->d_lf_beams, (size_t)h->B * sizeof(double2)));
         h->lf_beams_cap = h->B;
     }
-    const double inv_res = 1.0 / h->res;
-    int nb = 0;
-    for (int j = 0; j < h->B; ++j) {
-        const double r = (double)obs[(size_t)j * stride];
-        if (!(r >= 0.0 && r < h->cfg.max_range_m)) continue;             // NaN, +-inf, negative, max range: no contribution
-        h->h_lf_beams[nb++] = make_double2(r * h->beam_cs_host[(size_t)j].x * inv_res, r * h->beam_cs_host[(size_t)j].y * inv_res);
-    }
+    const int nb = mcl_host::lf_used_beams(h, obs, stride, h->h_lf_beams);
     if (nb > 0)
         HIPCHK(h, hipMemcpyAsync(h->d_lf_beams, h->h_lf_beams, (size_t)nb * sizeof(double2), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipEventRecord(h->ev[EV_QUERY], h->stream));
     HIPCHK(h, hipEventRecord(h->ev[EV_K0], h->stream));
-    mcl::LfArgs a{};
-    a.x = h->d_x[h->cur]; a.y = h->d_y[h->cur]; a.th = h->d_th[h->cur]; a.n = n;
-    a.beams = h->d_lf_beams; a.nb = nb;
-    a.D = h->d_lf_D; a.W = h->W; a.H = h->H;
-    a.ox = h->ox; a.oy = h->oy; a.inv_res = inv_res;
-    a.lf = h->d_lf_tab; a.K = h->lf_K;
-    a.logw = h->d_logw;
-    const dim3 grid((unsigned)((n + 255) / 256));
-    if (h->lf_K < mcl::kLfLdsEntries)
-        hipLaunchKernelGGL(mcl::k_lfield<true>, grid, dim3(256), (size_t)(h->lf_K + 1) * sizeof(float), h->stream, a);
-    else
-        hipLaunchKernelGGL(mcl::k_lfield<false>, grid, dim3(256), 0, h->stream, a);
-    HIPCHK(h, hipGetLastError());
+    const int rc = mcl_host::launch_lfield_on(h, h->d_x[h->cur], h->d_y[h->cur], h->d_th[h->cur], n, h->d_lf_beams, nb, h->d_logw);
+    if (rc != MCL_OK) return rc;
     HIPCHK(h, hipEventRecord(h->ev[EV_K1], h->stream));
     h->max_partials_ready = false;
     h->last_quad = false;
@@ -1079,6 +1062,7 @@ void mcl_destroy(mcl_engine_t *h)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->comm) { comm_free(h->comm); h->comm = nullptr; }
     if (h->clu) { cluster_free(h->clu); h->clu = nullptr; }
+    if (h->qry) { query_free(h->qry); h->qry = nullptr; }
     graph_reset(h);
     for (int b = 0; b < 2; ++b) { dfree(h->d_x[b]); dfree(h->d_y[b]); dfree(h->d_th[b]); }
     dfree(h->d_w); dfree(h->d_logw); dfree(h->d_tmp); dfree(h->d_logw_acc); dfree(h->d_carry[0]); dfree(h->d_carry[1]); dfree(h->d_q); dfree(h->d_cdf); dfree(h->d_blocktot); dfree(h->d_bm); dfree(h->d_bm_pop); dfree(h->d_bm_pref);
@@ -2967,6 +2951,35 @@ void launch_stage_pack(hipStream_t stream, const unsigned long long *d_result, d
 void launch_pack_records(hipStream_t stream, const double *x, const double *y, const double *th, int64_t n, double4 *out)
 {
     hipLaunchKernelGGL(mcl::k_pack_records, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x, y, th, n, out);
+}
+int lf_used_beams(const mcl_engine *h, const float *obs, int stride, double2 *out)
+{
+    const double inv_res = 1.0 / h->res;
+    int nb = 0;
+    for (int j = 0; j < h->B; ++j) {
+        const double r = (double)obs[(size_t)j * stride];
+        if (!(r >= 0.0 && r < h->cfg.max_range_m)) continue;             // NaN, +-inf, negative, max range: no contribution
+        out[nb++] = make_double2(r * h->beam_cs_host[(size_t)j].x * inv_res, r * h->beam_cs_host[(size_t)j].y * inv_res);
+    }
+    return nb;
+}
+int launch_lfield_on(mcl_engine *h, const double *x, const double *y, const double *th, int64_t n, const double2 *d_beams, int nb,
+                     double *logw)
+{
+    mcl::LfArgs a{};
+    a.x = x; a.y = y; a.th = th; a.n = n;
+    a.beams = d_beams; a.nb = nb;
+    a.D = h->d_lf_D; a.W = h->W; a.H = h->H;
+    a.ox = h->ox; a.oy = h->oy; a.inv_res = 1.0 / h->res;
+    a.lf = h->d_lf_tab; a.K = h->lf_K;
+    a.logw = logw;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (h->lf_K < mcl::kLfLdsEntries)
+        hipLaunchKernelGGL(mcl::k_lfield<true>, grid, dim3(256), (size_t)(h->lf_K + 1) * sizeof(float), h->stream, a);
+    else
+        hipLaunchKernelGGL(mcl::k_lfield<false>, grid, dim3(256), 0, h->stream, a);
+    HIPCHK(h, hipGetLastError());
+    return MCL_OK;
 }
 void launch_group_max(hipStream_t stream, const mcl::GroupMaxArgs &a) { hipLaunchKernelGGL(mcl::k_group_max, dim3(1), dim3(1), 0, stream, a); }
 }  // namespace mcl_host

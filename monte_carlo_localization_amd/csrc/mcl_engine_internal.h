@@ -5,6 +5,8 @@
 //   mcl_comm.hip     mcl_comm_*: one process per GPU, the collectives of an update over RCCL on the engine's stream
 //   mcl_group.hip    mcl_group_*: several GPUs behind one handle, driven by one process (peer copies)
 //   mcl_cluster.hip  mcl_pose_clusters: the pose hypotheses of the particle set (its own kernels, called outside the update)
+//   mcl_query.hip    mcl_query_scans / mcl_score_poses: expected scans and scan scores of poses that are not particles (its own
+//                    kernels and buffers, called outside the update)
 // Only mcl_engine.hip includes the kernels (mcl_kernels.h); mcl_comm.hip and mcl_group.hip reach the few kernels they launch
 // through the launch_* functions below.  Every function declared here is defined once, under this name.
 #pragma once
@@ -39,6 +41,8 @@ void comm_free(struct mcl_comm *c);        // mcl_comm.hip
 void comm_forget(struct mcl_comm *c);      // mcl_comm.hip: the particle set changed, what the exchange knew is void
 struct mcl_cluster;
 void cluster_free(struct mcl_cluster *c);  // mcl_cluster.hip
+struct mcl_query;
+void query_free(struct mcl_query *q);      // mcl_query.hip
 struct mcl_engine {
     mcl_config_t cfg{};
     int num_cu = 256;
@@ -287,6 +291,8 @@ struct mcl_engine {
     // changes of the particle set or its weights (the labels of a clustering are valid while it is unchanged)
     struct mcl_cluster *clu = nullptr;
     unsigned long long set_epoch = 0;
+    // pose query (mcl_query_scans / mcl_score_poses): its own buffers, allocated on the first call
+    struct mcl_query *qry = nullptr;
 };
 
 #define HIPCHK(h, call)                                                                          \
@@ -351,4 +357,9 @@ void launch_spin_ms(hipStream_t stream, double ms);
 void launch_stage_pack(hipStream_t stream, const unsigned long long *d_result, double *d_vec, int n_shards, int self, int listed, unsigned long long list_cap);
 void launch_pack_records(hipStream_t stream, const double *x, const double *y, const double *th, int64_t n, double4 *out);
 void launch_group_max(hipStream_t stream, const mcl::GroupMaxArgs &a);
+// the likelihood field outside the update (mcl_query.hip): the used beams of a scan in beam order (LF3) into `out` (B entries of
+// room), their number returned; k_lfield over n poses and nb such beams on the engine's stream, the caller's buffers throughout
+int lf_used_beams(const mcl_engine *h, const float *obs, int stride, double2 *out);
+int launch_lfield_on(mcl_engine *h, const double *x, const double *y, const double *th, int64_t n, const double2 *d_beams, int nb,
+                     double *logw);
 }  // namespace mcl_host

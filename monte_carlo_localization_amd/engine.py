@@ -45,6 +45,7 @@ EXPORTS = [
     "mcl_host_sweep_global_layout", "mcl_get_ray_kernel_variant",
     "mcl_default_kld_config", "mcl_set_kld", "mcl_get_particle_count", "mcl_get_kld_state", "mcl_host_kld_bins", "mcl_host_kld_target",
     "mcl_default_cluster_config", "mcl_pose_clusters", "mcl_get_cluster_labels",
+    "mcl_query_scans", "mcl_score_poses", "mcl_get_query_counters",
     "mcl_default_recovery_config", "mcl_set_recovery", "mcl_get_recovery_state", "mcl_set_recovery_state", "mcl_host_recovery_step",
     "mcl_default_likelihood_field_config", "mcl_set_likelihood_field", "mcl_get_likelihood_field", "mcl_get_likelihood_table",
     "mcl_host_likelihood_field", "mcl_host_likelihood_table",
@@ -111,6 +112,19 @@ class Cluster(C.Structure):
 CLUSTER_DTYPE = np.dtype([("weight_q", np.uint64), ("weight", np.float64), ("n_particles", np.int64), ("n_bins", np.int64),
                           ("first_bin", np.int64), ("mean", np.float64, (3,)), ("cov", np.float64, (3, 3))])
 assert CLUSTER_DTYPE.itemsize == C.sizeof(Cluster)
+
+
+class PoseScore(C.Structure):
+    """mcl_pose_score_t: how well a scan supports one pose (Engine.score_poses)."""
+    _fields_ = [("log_likelihood", C.c_double), ("n_valid", C.c_int32), ("n_agree", C.c_int32), ("n_miss", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+# the numpy view of an array of mcl_pose_score_t (Engine.score_poses)
+POSE_SCORE_DTYPE = np.dtype([("log_likelihood", np.float64), ("n_valid", np.int32), ("n_agree", np.int32), ("n_miss", np.int32),
+                             ("reserved", np.int32)])
+assert POSE_SCORE_DTYPE.itemsize == C.sizeof(PoseScore) == 24
+MAX_QUERY_POSES = 65536
 
 
 class EngineError(RuntimeError):
@@ -184,6 +198,9 @@ def load_library(legacy=False):
         lib.mcl_pose_clusters.argtypes = [C.c_void_p, C.POINTER(ClusterConfig), C.c_int32, C.c_void_p, C.POINTER(C.c_int64),
                                           C.POINTER(C.c_uint64)]
         lib.mcl_get_cluster_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        lib.mcl_query_scans.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        lib.mcl_score_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        lib.mcl_get_query_counters.argtypes = [C.c_void_p, C.c_void_p]
         lib.mcl_default_recovery_config.argtypes = [C.POINTER(RecoveryConfig)]
         lib.mcl_default_recovery_config.restype = None
         lib.mcl_set_recovery.argtypes = [C.c_void_p, C.POINTER(RecoveryConfig)]
@@ -671,6 +688,45 @@ class Engine:
         self._chk(self.lib.mcl_get_cluster_labels(self._h, _p(out), C.c_int64(out.size)), "mcl_get_cluster_labels")
         return out
 
+    @staticmethod
+    def _query_poses(poses):
+        """(K, 3) poses, or one length-3 pose, as the K x 3 column-major array the ABI takes"""
+        p = np.asarray(poses, np.float64)
+        if p.ndim == 1:
+            p = p.reshape(1, -1)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise ValueError("poses must be (K, 3) or a single (x, y, theta)")
+        return _c(p.T, np.float64)
+
+    def expected_scans(self, poses, want_steps=False):
+        """The expected scan of every pose (mcl_query_scans): the ranges in metres of the beams last set, a
+        (K, B) float32 array -- what a particle at that pose would see -- and, with want_steps, the step indices (uint16) too.
+        `poses`: (K, 3) rows of (x, y, theta), or one pose.  Reads the map and the beams only: the particle set is untouched."""
+        p = self._query_poses(poses)
+        K = p.shape[1]
+        ranges = np.empty((K, self.n_beams), np.float32)
+        steps = np.empty((K, self.n_beams), np.uint16) if want_steps else None
+        self._chk(self.lib.mcl_query_scans(self._h, _p(p) if K else None, C.c_int32(K), _p(ranges),
+                                           _p(steps) if want_steps else None), "mcl_query_scans")
+        return (ranges, steps) if want_steps else ranges
+
+    def score_poses(self, poses, obs, tol_steps=2):
+        """How well the scan `obs` supports every pose (mcl_score_poses): a structured array (POSE_SCORE_DTYPE) with the
+        log-likelihood a particle at that pose would get from sensor_update(obs) under the engine's sensor model, and the beams
+        that are valid / agree with the cast ray within tol_steps / hit nothing in range.  weight_mode LOG only."""
+        p = self._query_poses(poses)
+        K = p.shape[1]
+        o = _c(obs, np.float32)
+        out = np.zeros(K, POSE_SCORE_DTYPE)
+        self._chk(self.lib.mcl_score_poses(self._h, _p(p) if K else None, C.c_int32(K), _p(o), C.c_int32(o.size),
+                                           C.c_int32(int(tol_steps)), _p(out)), "mcl_score_poses")
+        return out
+
+    def query_counters(self):
+        out = np.zeros(2, np.uint64)
+        self._chk(self.lib.mcl_get_query_counters(self._h, _p(out)), "mcl_get_query_counters")
+        return dict(level3_rays=int(out[0]), device_bytes=int(out[1]))
+
     def sensor_update(self, obs):
         o = _c(obs, np.float32)
         self._chk(self.lib.mcl_sensor_update(self._h, _p(o), C.c_int32(o.size)), "mcl_sensor_update")
@@ -1005,6 +1061,7 @@ class Group:
     def set_beam_angles(self, angles):
         a = _c(angles, np.float32)
         self._chk(self.lib.mcl_group_set_beam_angles(self._h, _p(a), C.c_int32(a.size)), "mcl_group_set_beam_angles")
+        self.n_beams = a.size
 
     def set_particles(self, p_colmajor, weights):
         p = _c(p_colmajor, np.float64)
@@ -1072,7 +1129,7 @@ class Group:
         h = C.c_void_p()
         self._chk(self.lib.mcl_group_engine(self._h, C.c_int32(i), C.byref(h)), "mcl_group_engine")
         e = Engine.__new__(Engine)
-        e.lib, e.cfg, e._h, e.n, e.n_beams, e._borrowed = self.lib, self.cfg, h, self.n_total // self.size, 0, True
+        e.lib, e.cfg, e._h, e.n, e.n_beams, e._borrowed = self.lib, self.cfg, h, self.n_total // self.size, getattr(self, "n_beams", 0), True
         return e
 
     def exchange_bytes(self):
