@@ -363,6 +363,62 @@ int mcl_score_poses(mcl_engine_t *h, const double *poses_colmajor, int32_t K, co
  * buffers have asked for so far (0 on an engine that never queried) */
 int mcl_get_query_counters(const mcl_engine_t *h, uint64_t out[2]);
 
+/* ---- global search: score a pose lattice against a scan, seed from the hits --------------------------------
+ * The deterministic alternative to mcl_init_global: every pose of a regular lattice over the map's free cells is scored against
+ * one scan under the likelihood-field model, and the best-fitting poses are reported.  mcl_init_particles_mixture (below, with
+ * the Gaussian initialisation) turns several hits into one cloud.
+ *   S1 positions.  h0 = stride_cells / 2 (integer); lattice columns col = h0 + ix * stride_cells for every ix with col < W, rows
+ *     likewise; a lattice cell is a position iff data[row * W + col] == 0 (mcl_init_global's free rule).  Positions are numbered
+ *     p = 0 ... in row-major order of (iy, ix).  The pose sits at the cell centre: x = ox + ((double)col + 0.5) * res, res the
+ *     map's float resolution widened to double, the multiply and the add each rounded; y likewise.  The host forms the table.
+ *   S2 headings.  theta_k = (double)(2 k - n_headings) * (pi / n_headings), pi / n_headings formed once in double on the host.
+ *   S3 beams.  Beam j is used iff j % beam_stride == 0 and 0 <= r_j < max_range_m (LF3); the used beams, in beam order.
+ *   S4 score.  score[k * n_positions + p] is the likelihood-field log-likelihood (LF4 / LF5) of the pose (x_p, y_p, theta_k): bit
+ *     for bit what mcl_score_poses returns for that pose and the same obs (for beam_stride > 1: obs with the readings of the other
+ *     beams replaced by NaN).  The in-order fp64 sum, one lane per pose; finite or -inf, never NaN.
+ *   S5 hits.  Pose a is better than pose b iff score_a > score_b, or the scores are equal and index_a < index_b.  With nms = 1 a
+ *     pose is a candidate iff its score is > -inf and it is better than every lattice neighbour: the positions at (ix + dix,
+ *     iy + diy), dix, diy in {-1, 0, 1}, combined with the headings (k + dk) mod n_headings, dk in {-1, 0, 1}, the pose itself
+ *     excluded, lattice cells that are no position ignored.  With nms = 0 every pose with a score > -inf is a candidate.
+ *     *n_hits = the number of candidates; hits receives the min(max_hits, *n_hits) best, best first.  0 <= max_hits <= 65536;
+ *     hits may be NULL when max_hits is 0.  The order is total, so the result is unique.
+ *   S6 stats = {n_positions, poses scored, used beams, bytes of device memory the search's buffers have asked for so far}; stats
+ *     may be NULL.  mcl_get_search_scores copies the volume of the last search (n == n_headings * n_positions);
+ *     MCL_ERR_NOT_READY before any search and after mcl_set_map.
+ *   S7 read-only (as Q5).  The search uses buffers of its own, allocated on the first search (mcl_get_search_bytes: 0 on an
+ *     engine that never searched), and none of the update's scratch or staged observation; one host wait, at its end (a search
+ *     whose lattice differs from the last one's also uploads the new lattice first).  Every later update is bit-identical to
+ *     one of an engine that never searched.
+ *   S8 where it works.  A map, beam angles and the likelihood-field model ON (the search reads the engine's field D and table
+ *     Lf): MCL_ERR_NOT_READY otherwise -- the message says which is missing -- and when the lattice has no position.
+ *     MCL_ERR_INVALID_ARG for stride_cells, n_headings or beam_stride < 1, nms outside {0, 1}, reserved != 0, n_beams != B, a
+ *     null obs / n_hits (or hits with max_hits > 0), max_hits outside [0, 65536], n_positions * n_headings >=
+ *     MCL_MAX_TOTAL_PARTICLES.  Single engine only (the likelihood field is).  A node that tracks with the beam model switches
+ *     the field on, searches, seeds, and switches it off: either switch makes the next update plan as after mcl_set_particles. */
+typedef struct {
+    int32_t stride_cells;                   /* >= 1, default 2: lattice pitch in map cells                                    */
+    int32_t n_headings;                     /* >= 1, default 72                                                               */
+    int32_t beam_stride;                    /* >= 1, default 1: only beams j with j % beam_stride == 0 are candidates          */
+    int32_t nms;                            /* 1 (default): hits are local maxima of the score volume; 0: every pose          */
+    int32_t reserved[4];                    /* must be 0                                                                      */
+} mcl_search_config_t;
+typedef struct {
+    double  pose[3];                        /* x, y, theta                                                                    */
+    double  log_likelihood;                 /* S4                                                                             */
+    int64_t index;                          /* k * n_positions + p                                                            */
+} mcl_search_hit_t;
+void mcl_default_search_config(mcl_search_config_t *c);
+int mcl_global_search(mcl_engine_t *h, const mcl_search_config_t *c /* NULL = the defaults */, const float *obs, int32_t n_beams,
+                      int32_t max_hits, mcl_search_hit_t *hits, int64_t *n_hits, uint64_t stats[4]);
+int mcl_get_search_scores(mcl_engine_t *h, double *out, size_t n);
+int mcl_get_search_bytes(const mcl_engine_t *h, uint64_t *bytes);
+/* S1 / S2 on the host, without a device.  The lattice: *n_positions always; cells (the linear map cell row * W + col of every
+ * position) and xy (x, y per position) when given, n must then equal the number of positions (call once with both NULL for it).
+ * The headings: n == n_headings.  MCL_ERR_INVALID_ARG for a refused config, a null map or bad dimensions / resolution. */
+int mcl_host_search_lattice(const mcl_search_config_t *c, const int8_t *data, uint32_t width, uint32_t height, float resolution,
+                            double origin_x, double origin_y, uint32_t *cells, double *xy, size_t n, int64_t *n_positions);
+int mcl_host_search_headings(const mcl_search_config_t *c, double *theta, size_t n);
+
 /* ---- recovery by random-particle injection (augmented MCL, Probabilistic Robotics Table 8.3; AMCL's recovery_alpha_slow /
  *      recovery_alpha_fast) -------------------------------------------------------------------------------
  * Off by default.  With it on, a resampling mcl_update replaces each child, with probability p, by a pose drawn uniformly from
@@ -501,6 +557,15 @@ int mcl_init_particles_gaussian(mcl_engine_t *h, const double mean[3], const dou
                                 int64_t first_global_index, int64_t n_total);
 /* G1's factor on the host, without a device: L = {L00, L10, L11, L20, L21, L22}; MCL_ERR_INVALID_ARG as mcl_init_particles_gaussian */
 int mcl_host_gaussian_factor(const double cov[9], double L[6]);
+/* A mixture of n_components Gaussians (several hits of mcl_global_search, or several clusters, as ONE cloud).  means: M x 3, covs:
+ * M x 9 (row-major each), counts: M particles per component, >= 0, describing the WHOLE set: their sum must equal n_total; 1 <= M
+ * <= 4096.  The particle with global index g belongs to the component whose prefix range [sum counts[0..c), sum counts[0..c]) holds
+ * g; it draws n0, n1, n2 exactly as G1 does (same streams and counter, indexed by g) and applies that component's mean and factor
+ * by G1's rules.  So rows [a, b) of a mixture equal rows [a, b) of mcl_init_particles_gaussian(mean_c, cov_c) with the same n_total
+ * wherever [a, b) lies inside component c, and M = 1 is mcl_init_particles_gaussian bit for bit.  Everything else (weights
+ * 1 / n_total, what the call resets) as G1.  MCL_ERR_INVALID_ARG as G1 per component (the message names it); nothing changes then. */
+int mcl_init_particles_mixture(mcl_engine_t *h, int32_t n_components, const double *means, const double *covs, const int64_t *counts,
+                               int64_t n, int64_t first_global_index, int64_t n_total);
 
 /* ---- host-side precomputation, callable without a device (what mcl_set_map uploads) --------- */
 /* (P+1)^2 doubles, Eigen column-major (index d*(P+1)+r): the restatement of precompute_sensor_model

@@ -1063,6 +1063,7 @@ void mcl_destroy(mcl_engine_t *h)
     if (h->comm) { comm_free(h->comm); h->comm = nullptr; }
     if (h->clu) { cluster_free(h->clu); h->clu = nullptr; }
     if (h->qry) { query_free(h->qry); h->qry = nullptr; }
+    if (h->srch) { search_free(h->srch); h->srch = nullptr; }
     graph_reset(h);
     for (int b = 0; b < 2; ++b) { dfree(h->d_x[b]); dfree(h->d_y[b]); dfree(h->d_th[b]); }
     dfree(h->d_w); dfree(h->d_logw); dfree(h->d_tmp); dfree(h->d_logw_acc); dfree(h->d_carry[0]); dfree(h->d_carry[1]); dfree(h->d_q); dfree(h->d_cdf); dfree(h->d_blocktot); dfree(h->d_bm); dfree(h->d_bm_pop); dfree(h->d_bm_pref);
@@ -1111,6 +1112,8 @@ int mcl_set_map(mcl_engine_t *h, const int8_t *data, uint32_t width, uint32_t he
     if (P < 1 || P > 2047) return fail(h, MCL_ERR_UNSUPPORTED, "MAX_RANGE_PX must be in [1, 2047]");
     h->W = (int)width; h->H = (int)height; h->P = P;
     h->res = res; h->ox = origin_x; h->oy = origin_y;
+    h->grid_host.assign(data, data + (size_t)width * height);      // (the global search forms its lattice from it)
+    h->map_epoch++;
     h->Wp = h->W + 1; h->Hp = h->H + 1; h->Wps = (h->Wp + 7) & ~7;
     // LDS window: as large as 160 KiB allows (nibbles), multiple of 8 cells
     h->tw_cells = 568;
@@ -2235,6 +2238,41 @@ int mcl_init_particles_gaussian(mcl_engine_t *h, const double mean[3], const dou
                        L[1], L[2], L[3], L[4], L[5], n, first_global_index, (uint32_t)h->cfg.seed, (uint32_t)(h->cfg.seed >> 32), h->init_idx,
                        h->d_x[c], h->d_y[c], h->d_th[c]);
     HIPCHK(h, hipGetLastError());
+    return finish_init(h, n, n_total);
+}
+
+int mcl_init_particles_mixture(mcl_engine_t *h, int32_t n_components, const double *means, const double *covs, const int64_t *counts,
+                               int64_t n, int64_t first_global_index, int64_t n_total)
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    if (!means || !covs || !counts || n <= 0 || n > h->cap || first_global_index < 0 || n_total < n || n_total >= MCL_MAX_TOTAL_PARTICLES)
+        return fail(h, MCL_ERR_INVALID_ARG, "bad init arguments (the sharded total must stay below 2^27)");
+    if (n_components < 1 || n_components > 4096) return fail(h, MCL_ERR_INVALID_ARG, "mixture init: n_components must be in [1, 4096]");
+    if (first_global_index + n > n_total) return fail(h, MCL_ERR_INVALID_ARG, "mixture init: the shard ends beyond n_total");
+    std::vector<mcl::MixComponent> comp((size_t)n_components);
+    int64_t sum = 0;
+    for (int c = 0; c < n_components; ++c) {
+        const std::string who = "mixture init, component " + std::to_string(c) + ": ";
+        if (counts[c] < 0 || counts[c] > n_total) return fail(h, MCL_ERR_INVALID_ARG, who + "its count must be in [0, n_total]");
+        sum += counts[c];
+        comp[(size_t)c].end = sum;
+        for (int k = 0; k < 3; ++k) comp[(size_t)c].mean[k] = means[3 * c + k];
+        if (const char *why = gaussian_factor(covs + 9 * (size_t)c, comp[(size_t)c].l)) return fail(h, MCL_ERR_INVALID_ARG, who + why);
+    }
+    if (sum != n_total) return fail(h, MCL_ERR_INVALID_ARG, "mixture init: the counts must add up to n_total");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    mcl::MixComponent *d_comp = nullptr;
+    HIPCHK(h, hipMalloc(&d_comp, comp.size() * sizeof(mcl::MixComponent)));
+    int rc = MCL_OK;
+    if (hipMemcpy(d_comp, comp.data(), comp.size() * sizeof(mcl::MixComponent), hipMemcpyHostToDevice) != hipSuccess) rc = MCL_ERR_HIP;
+    if (rc == MCL_OK) {
+        const int c = h->cur;
+        hipLaunchKernelGGL(mcl::k_init_mixture, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, d_comp, n_components, n,
+                           first_global_index, (uint32_t)h->cfg.seed, (uint32_t)(h->cfg.seed >> 32), h->init_idx, h->d_x[c], h->d_y[c], h->d_th[c]);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) rc = MCL_ERR_HIP;   // (d_comp is freed below)
+    }
+    (void)hipFree(d_comp);
+    if (rc != MCL_OK) return fail(h, rc, "mixture init: uploading the components or the draw failed");
     return finish_init(h, n, n_total);
 }
 

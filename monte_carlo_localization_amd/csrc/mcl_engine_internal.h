@@ -7,6 +7,8 @@
 //   mcl_cluster.hip  mcl_pose_clusters: the pose hypotheses of the particle set (its own kernels, called outside the update)
 //   mcl_query.hip    mcl_query_scans / mcl_score_poses: expected scans and scan scores of poses that are not particles (its own
 //                    kernels and buffers, called outside the update)
+//   mcl_search.hip   mcl_global_search: the likelihood-field score of every pose of a lattice over the map, and its hits (its own
+//                    kernels and buffers, called outside the update)
 // Only mcl_engine.hip includes the kernels (mcl_kernels.h); mcl_comm.hip and mcl_group.hip reach the few kernels they launch
 // through the launch_* functions below.  Every function declared here is defined once, under this name.
 #pragma once
@@ -43,6 +45,8 @@ struct mcl_cluster;
 void cluster_free(struct mcl_cluster *c);  // mcl_cluster.hip
 struct mcl_query;
 void query_free(struct mcl_query *q);      // mcl_query.hip
+struct mcl_search;
+void search_free(struct mcl_search *s);    // mcl_search.hip
 struct mcl_engine {
     mcl_config_t cfg{};
     int num_cu = 256;
@@ -293,6 +297,12 @@ struct mcl_engine {
     unsigned long long set_epoch = 0;
     // pose query (mcl_query_scans / mcl_score_poses): its own buffers, allocated on the first call
     struct mcl_query *qry = nullptr;
+    // global search (mcl_global_search): its own buffers, allocated on the first call.  Its lattice is formed on
+    // the host from the map's cells (grid_host, kept by mcl_set_map); map_epoch counts the maps set (a lattice and a score volume
+    // belong to one of them)
+    struct mcl_search *srch = nullptr;
+    std::vector<int8_t> grid_host;
+    unsigned long long map_epoch = 0;
 };
 
 #define HIPCHK(h, call)                                                                          \

@@ -27,4 +27,10 @@ int lf_cap(const mcl_likelihood_field_config_t *c, float resolution);
 void lf_table(const mcl_config_t &cfg, const mcl_likelihood_field_config_t &c, double res, int K, std::vector<float> &t);
 const char *motion_invalid(const mcl_motion_config_t *c);
 const char *gaussian_factor(const double cov[9], double L[6]);
+const char *search_invalid(const mcl_search_config_t *c);
+// the lattice of a global search over a map (S1): positions in row-major order of (iy, ix).  Any output may be null: cells (the
+// position's linear map cell), xy (2 per position), lat (ix, iy per position), pmap (ny x nx: position or -1).  Returns the count.
+int64_t search_lattice(int stride, const int8_t *data, int W, int H, double res, double ox, double oy, std::vector<uint32_t> *cells,
+                       std::vector<double> *xy, std::vector<int32_t> *lat, std::vector<int32_t> *pmap, int &nx, int &ny);
+void search_headings(int n_headings, double *theta);
 }  // namespace mcl_host

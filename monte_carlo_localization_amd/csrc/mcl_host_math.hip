@@ -413,6 +413,50 @@ static double host_normalize_angle(double a)
     return a;
 }
 
+// ---- the global search (mcl_global_search): its config check, lattice (S1) and headings (S2)
+const char *search_invalid(const mcl_search_config_t *c)
+{
+    if (c->stride_cells < 1) return "global search: stride_cells must be >= 1";
+    if (c->n_headings < 1) return "global search: n_headings must be >= 1";
+    if (c->beam_stride < 1) return "global search: beam_stride must be >= 1";
+    if (c->nms != 0 && c->nms != 1) return "global search: nms must be 0 or 1";
+    for (int i = 0; i < 4; ++i)
+        if (c->reserved[i] != 0) return "global search: reserved must be 0";
+    return nullptr;
+}
+
+int64_t search_lattice(int stride, const int8_t *data, int W, int H, double res, double ox, double oy, std::vector<uint32_t> *cells,
+                       std::vector<double> *xy, std::vector<int32_t> *lat, std::vector<int32_t> *pmap, int &nx, int &ny)
+{
+    const int64_t h0 = stride / 2;
+    nx = h0 < W ? (int)(((int64_t)W - 1 - h0) / stride + 1) : 0;       // columns h0 + ix * stride < W
+    ny = h0 < H ? (int)(((int64_t)H - 1 - h0) / stride + 1) : 0;
+    if (pmap) pmap->assign((size_t)nx * (size_t)ny, -1);
+    int64_t np = 0;
+    for (int iy = 0; iy < ny; ++iy) {
+        const int64_t row = h0 + (int64_t)iy * stride;
+        for (int ix = 0; ix < nx; ++ix) {
+            const int64_t col = h0 + (int64_t)ix * stride;
+            if (data[(size_t)row * (size_t)W + (size_t)col] != 0) continue;         // the free rule of mcl_init_global
+            if (cells) cells->push_back((uint32_t)(row * W + col));
+            if (xy) {
+                xy->push_back(ox + ((double)col + 0.5) * res);       // the cell centre; the multiply and the add each rounded
+                xy->push_back(oy + ((double)row + 0.5) * res);
+            }
+            if (lat) { lat->push_back(ix); lat->push_back(iy); }
+            if (pmap) (*pmap)[(size_t)iy * (size_t)nx + (size_t)ix] = (int32_t)np;
+            ++np;
+        }
+    }
+    return np;
+}
+
+void search_headings(int n_headings, double *theta)
+{
+    const double step = 3.14159265358979323846 / (double)n_headings;     // formed once
+    for (int64_t k = 0; k < n_headings; ++k) theta[k] = (double)(2 * k - (int64_t)n_headings) * step;
+}
+
 // G1: the lower Cholesky factor of a symmetric positive semi-definite 3 x 3 matrix (row-major), L = {L00, L10, L11, L20, L21, L22}
 const char *gaussian_factor(const double cov[9], double L[6])
 {
@@ -672,6 +716,39 @@ int mcl_host_likelihood_table(const mcl_config_t *cfg, const mcl_likelihood_fiel
     std::vector<float> t;
     lf_table(*cfg, *c, (double)resolution, k, t);
     std::memcpy(out, t.data(), n * sizeof(float));
+    return MCL_OK;
+}
+
+void mcl_default_search_config(mcl_search_config_t *c)
+{
+    if (!c) return;
+    *c = mcl_search_config_t{};
+    c->stride_cells = 2; c->n_headings = 72; c->beam_stride = 1; c->nms = 1;
+}
+
+int mcl_host_search_lattice(const mcl_search_config_t *c, const int8_t *data, uint32_t width, uint32_t height, float resolution,
+                            double origin_x, double origin_y, uint32_t *cells, double *xy, size_t n, int64_t *n_positions)
+{
+    if (!c || search_invalid(c) || !data || !n_positions || width == 0 || height == 0 || width > 200000 || height > 200000 ||
+        !(resolution > 0.0f) || !std::isfinite(resolution))
+        return MCL_ERR_INVALID_ARG;
+    std::vector<uint32_t> vc;
+    std::vector<double> vxy;
+    int nx = 0, ny = 0;
+    const int64_t np = search_lattice(c->stride_cells, data, (int)width, (int)height, (double)resolution, origin_x, origin_y,
+                                      cells ? &vc : nullptr, xy ? &vxy : nullptr, nullptr, nullptr, nx, ny);
+    *n_positions = np;
+    if (!cells && !xy) return MCL_OK;
+    if (n != (size_t)np) return MCL_ERR_INVALID_ARG;
+    if (cells && np) std::memcpy(cells, vc.data(), (size_t)np * sizeof(uint32_t));
+    if (xy && np) std::memcpy(xy, vxy.data(), (size_t)np * 2 * sizeof(double));
+    return MCL_OK;
+}
+
+int mcl_host_search_headings(const mcl_search_config_t *c, double *theta, size_t n)
+{
+    if (!c || search_invalid(c) || !theta || n != (size_t)c->n_headings) return MCL_ERR_INVALID_ARG;
+    search_headings(c->n_headings, theta);
     return MCL_OK;
 }
 

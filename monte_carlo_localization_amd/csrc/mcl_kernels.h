@@ -694,6 +694,24 @@ __global__ __launch_bounds__(256) void k_init_pose(double px, double py, double 
     th[i] = normalize_angle(pt + n2 * 0.4);
 }
 
+// the three normals of particle g of an initialisation (k_init_pose's draw: streams 5 and 6, the init counter)
+__device__ __forceinline__ void init_normals(uint64_t g, uint32_t init_idx, uint32_t seed_lo, uint32_t seed_hi, double &n0, double &n1,
+                                             double &n2)
+{
+    const double TWO_M53 = 1.0 / 9007199254740992.0;
+    const double TWO_PI = 2.0 * 3.14159265358979323846;
+    u32x4 o = philox4x32((uint32_t)g, init_idx, 5u, (uint32_t)(g >> 32), seed_lo, seed_hi);
+    double u1 = (double)(bits53(o.v[0], o.v[1]) + 1) * TWO_M53;
+    double u2 = (double)bits53(o.v[2], o.v[3]) * TWO_M53;
+    double rad = sqrt(-2.0 * log(u1));
+    n0 = rad * cos(TWO_PI * u2);
+    n1 = rad * sin(TWO_PI * u2);
+    o = philox4x32((uint32_t)g, init_idx, 6u, (uint32_t)(g >> 32), seed_lo, seed_hi);
+    u1 = (double)(bits53(o.v[0], o.v[1]) + 1) * TWO_M53;
+    u2 = (double)bits53(o.v[2], o.v[3]) * TWO_M53;
+    n2 = sqrt(-2.0 * log(u1)) * cos(TWO_PI * u2);
+}
+
 // mcl_init_particles_gaussian (G1): k_init_pose's draw with the lower Cholesky factor of the covariance as six scalars
 __global__ __launch_bounds__(256) void k_init_gaussian(double px, double py, double pt, double l00, double l10, double l11, double l20,
                                                       double l21, double l22, int64_t n, int64_t first, uint32_t seed_lo,
@@ -702,21 +720,38 @@ __global__ __launch_bounds__(256) void k_init_gaussian(double px, double py, dou
 {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    uint64_t g = (uint64_t)(first + i);
-    const double TWO_M53 = 1.0 / 9007199254740992.0;
-    const double TWO_PI = 2.0 * 3.14159265358979323846;
-    u32x4 o = philox4x32((uint32_t)g, init_idx, 5u, (uint32_t)(g >> 32), seed_lo, seed_hi);
-    double u1 = (double)(bits53(o.v[0], o.v[1]) + 1) * TWO_M53;
-    double u2 = (double)bits53(o.v[2], o.v[3]) * TWO_M53;
-    double rad = sqrt(-2.0 * log(u1));
-    double n0 = rad * cos(TWO_PI * u2), n1 = rad * sin(TWO_PI * u2);
-    o = philox4x32((uint32_t)g, init_idx, 6u, (uint32_t)(g >> 32), seed_lo, seed_hi);
-    u1 = (double)(bits53(o.v[0], o.v[1]) + 1) * TWO_M53;
-    u2 = (double)bits53(o.v[2], o.v[3]) * TWO_M53;
-    double n2 = sqrt(-2.0 * log(u1)) * cos(TWO_PI * u2);
+    double n0, n1, n2;
+    init_normals((uint64_t)(first + i), init_idx, seed_lo, seed_hi, n0, n1, n2);
     x[i] = px + l00 * n0;
     y[i] = py + (l10 * n0 + l11 * n1);
     th[i] = normalize_angle(pt + (l20 * n0 + l21 * n1 + l22 * n2));
+}
+
+// mcl_init_particles_mixture: G1 per component.  Particle g belongs to the component whose prefix range holds g: the first c with
+// g < end[c] (end = the inclusive prefix sums of the counts, so an empty component is never chosen).
+struct MixComponent {
+    double mean[3];
+    double l[6];            // L00, L10, L11, L20, L21, L22
+    int64_t end;
+};
+__global__ __launch_bounds__(256) void k_init_mixture(const MixComponent *__restrict__ comp, int n_comp, int64_t n, int64_t first,
+                                                     uint32_t seed_lo, uint32_t seed_hi, uint32_t init_idx, double *__restrict__ x,
+                                                     double *__restrict__ y, double *__restrict__ th)
+{
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t g = first + i;
+    int lo = 0, hi = n_comp - 1;          // (g < end[n_comp - 1] = n_total)
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (g < comp[mid].end) hi = mid; else lo = mid + 1;
+    }
+    const MixComponent m = comp[lo];
+    double n0, n1, n2;
+    init_normals((uint64_t)g, init_idx, seed_lo, seed_hi, n0, n1, n2);
+    x[i] = m.mean[0] + m.l[0] * n0;
+    y[i] = m.mean[1] + (m.l[1] * n0 + m.l[2] * n1);
+    th[i] = normalize_angle(m.mean[2] + (m.l[3] * n0 + m.l[4] * n1 + m.l[5] * n2));
 }
 
 __global__ __launch_bounds__(256) void k_init_global(const uint32_t *__restrict__ free_cells, uint64_t n_free, int W, double res,

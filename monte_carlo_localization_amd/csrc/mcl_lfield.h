@@ -1,15 +1,10 @@
 // mcl_lfield.h -- the likelihood-field ("endpoint") sensor model (mcl_set_likelihood_field): the exact integer
 // distance field of the map and k_lfield, which turns every particle's beam end points into its log-weight.  Included by
-// mcl_engine.hip only.
+// mcl_engine.hip only; the per-beam arithmetic is mcl_lfield_core.h's, shared with the lattice search.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
+#include "mcl_lfield_core.h"
 
 namespace mcl {
-
-// Lf is staged in LDS below this many entries (32 KiB: five 256-thread workgroups per CU); a larger K reads it from global memory.
-constexpr int kLfLdsEntries = 8192;
 
 // Column pass of LF1: g[c] = |dy| to the nearest occupied cell (> 50) of the same column, exact below `reach`, else `reach`
 // (reach^2 >= K: a capped value only makes sums >= K, which the row pass clamps to K anyway).  One thread per cell, early exit.
@@ -74,19 +69,13 @@ __global__ __launch_bounds__(256) void k_lfield(LfArgs a)
     double s, c;
     sincos(a.th[i], &s, &c);
     // the particle in cell units; the end point of beam j is (px + c u_j - s v_j, py + s u_j + c v_j) (LF4, the rotation form)
-    const double px = (a.x[i] - a.ox) * a.inv_res, py = (a.y[i] - a.oy) * a.inv_res;
+    const double px = lf_cell_coord(a.x[i], a.ox, a.inv_res), py = lf_cell_coord(a.y[i], a.oy, a.inv_res);
     const double W = (double)a.W, H = (double)a.H;
     const float off = lf[a.K];
     double acc = 0.0;
 #pragma unroll 4
     for (int j = 0; j < a.nb; ++j) {
-        const double2 b = a.beams[j];
-        const double fx = floor(fma(c, b.x, fma(-s, b.y, px)));
-        const double fy = floor(fma(s, b.x, fma(c, b.y, py)));
-        float v = off;
-        if (fx >= 0.0 && fx < W && fy >= 0.0 && fy < H)       // (false for NaN: off the map)
-            v = lf[a.D[(size_t)(int)fy * (size_t)a.W + (size_t)(int)fx]];
-        acc += (double)v;
+        acc += (double)lf_beam_value(a.beams[j], s, c, px, py, W, H, a.W, a.D, lf, off);
     }
     a.logw[i] = acc;
 }

@@ -1,0 +1,118 @@
+// mcl_search.h -- the global search (mcl_global_search): the likelihood-field score of every pose of a regular
+// lattice over the map's free cells, and which of them are hits.  The arguments of its kernels and the kernels themselves; only
+// mcl_search.hip includes it.  A score comes from the per-beam arithmetic of k_lfield (mcl_lfield_core.h), so a lattice pose and
+// a particle (or a queried pose) at the same place agree bit for bit.
+#pragma once
+#include "mcl_engine_internal.h"
+#include "mcl_lfield_core.h"
+
+namespace mcl_srch {
+
+constexpr int kThreads = 256;
+constexpr uint64_t kNoCandidate = ~0ull;        // sort key of a pose that is no candidate: after every candidate's
+
+struct Args {
+    // the lattice: positions in row-major order of (iy, ix) (S1), headings (S2)
+    const double2 *xy;              // n_pos cell centres, formed on the host
+    const int2 *lat;                // n_pos lattice coordinates (ix, iy)
+    const int32_t *pmap;            // ny x nx, row-major: (iy, ix) -> position, -1: no position
+    const double *theta;            // n_head headings
+    int32_t n_pos, n_head, nx, ny;
+    uint32_t blocks_per_heading;    // ceil(n_pos / 256)
+    // the scan and the field
+    const double2 *beams;           // the used beams in beam order (S3)
+    int nb;
+    const uint16_t *D;              // H x W, row-major
+    int W, H;
+    double ox, oy, inv_res;
+    const float *lf;                // K + 1 entries
+    int K;
+    double *score;                  // n_head x n_pos: score[k * n_pos + p]
+    // the hits
+    int nms;
+    uint64_t *key;                  // per pose: its sort key (ascending keys = better poses first), kNoCandidate for none
+    uint32_t *val;                  // per pose: its index
+    unsigned long long *count;      // candidates
+};
+
+// Ascending order of the key == descending order of the score.  A score is finite or -inf here and never -0.0 (an in-order sum
+// that starts at +0.0), so equal scores have equal keys; `s + 0.0` states the latter.
+__device__ __forceinline__ uint64_t score_key(double s)
+{
+    const uint64_t b = (uint64_t)__double_as_longlong(s + 0.0);
+    const uint64_t asc = (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+    return ~asc;
+}
+
+// One lane per pose, a workgroup = 256 consecutive positions at ONE heading: the heading, its sine and cosine and every beam's
+// pair are uniform over the workgroup, and for one beam the end points of neighbouring lanes are neighbouring cells of the
+// field (same row of the lattice: stride_cells apart).  The in-order fp64 sum of LF5 per lane.  LDS_TABLE as in k_lfield.
+template <bool LDS_TABLE>
+__global__ __launch_bounds__(kThreads) void k_search_score(Args a)
+{
+    extern __shared__ float s_lf[];
+    const float *lf = a.lf;
+    if constexpr (LDS_TABLE) {
+        for (int k = threadIdx.x; k <= a.K; k += kThreads) s_lf[k] = a.lf[k];
+        __syncthreads();
+        lf = s_lf;
+    }
+    const uint32_t k = blockIdx.x / a.blocks_per_heading;
+    const uint32_t p = (blockIdx.x - k * a.blocks_per_heading) * (uint32_t)kThreads + threadIdx.x;
+    if (p >= (uint32_t)a.n_pos) return;
+    double s, c;
+    sincos(a.theta[k], &s, &c);
+    const double2 q = a.xy[p];
+    const double px = mcl::lf_cell_coord(q.x, a.ox, a.inv_res), py = mcl::lf_cell_coord(q.y, a.oy, a.inv_res);
+    const double W = (double)a.W, H = (double)a.H;
+    const float off = lf[a.K];
+    double acc = 0.0;
+#pragma unroll 4
+    for (int j = 0; j < a.nb; ++j)
+        acc += (double)mcl::lf_beam_value(a.beams[j], s, c, px, py, W, H, a.W, a.D, lf, off);
+    a.score[(size_t)k * (size_t)a.n_pos + p] = acc;
+}
+
+// One lane per pose i = k * n_pos + p: is it a candidate (S5)?  With nms, a pose must be better -- a higher score, or the same
+// score and a lower index -- than each of its up to 26 lattice neighbours (positions one lattice step away in ix / iy, headings
+// k - 1, k, k + 1 modulo n_head; with one or two headings the wrap lands on the pose itself or twice on the same neighbour, which
+// changes nothing).  Every pose gets its sort key and its index; the candidates are counted per wave.
+__global__ __launch_bounds__(kThreads) void k_search_mark(Args a)
+{
+    const uint64_t n_poses = (uint64_t)a.n_pos * (uint64_t)a.n_head;
+    const uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    bool cand = false;
+    if (i < n_poses) {
+        const int k = (int)(i / (uint64_t)a.n_pos);
+        const int p = (int)(i - (uint64_t)k * (uint64_t)a.n_pos);
+        const double s = a.score[i];
+        cand = s > -__builtin_inf();
+        if (cand && a.nms) {
+            const int2 at = a.lat[p];
+            for (int dk = -1; dk <= 1 && cand; ++dk) {
+                int kk = k + dk;
+                kk = kk < 0 ? kk + a.n_head : (kk >= a.n_head ? kk - a.n_head : kk);
+                for (int dy = -1; dy <= 1; ++dy) {
+                    const int jy = at.y + dy;
+                    if (jy < 0 || jy >= a.ny) continue;
+                    for (int dx = -1; dx <= 1; ++dx) {
+                        const int jx = at.x + dx;
+                        if (jx < 0 || jx >= a.nx) continue;
+                        const int32_t q = a.pmap[(size_t)jy * (size_t)a.nx + (size_t)jx];
+                        if (q < 0) continue;
+                        const uint64_t j = (uint64_t)kk * (uint64_t)a.n_pos + (uint64_t)q;
+                        if (j == i) continue;
+                        const double t = a.score[j];
+                        if (!(s > t || (s == t && i < j))) cand = false;
+                    }
+                }
+            }
+        }
+        a.key[i] = cand ? score_key(s) : kNoCandidate;
+        a.val[i] = (uint32_t)i;
+    }
+    const unsigned long long found = __ballot(cand);
+    if ((threadIdx.x & 63) == 0 && found) atomicAdd(a.count, (unsigned long long)__popcll(found));
+}
+
+}  // namespace mcl_srch

@@ -1,0 +1,299 @@
+// mcl_search.hip -- mcl_global_search: the likelihood-field score of every pose of a regular lattice over the
+// map's free cells against one scan, and the best-fitting poses.  Called outside the update: it reads the map's cells, the beams,
+// the likelihood field and its table, writes only buffers of its own (struct mcl_search) and leaves every engine state as it was.
+//
+// A call, on the engine's stream:
+//   (upload)         the lattice (positions, their lattice coordinates, the dense position map) and the headings, when they
+//                    differ from the last search's; the used beams of the scan from pinned staging
+//   k_search_score   one lane per pose, a workgroup = 256 consecutive positions at one heading: the score volume
+//   k_search_mark    one lane per pose: candidate or not (S5), every pose's sort key and index, the candidate count
+//   radix sort       (key, index) pairs, ascending and stable: the candidates first, best first, ties by index
+//   (copy)           the count and the first max_hits pairs; one host wait
+#include "mcl_search.h"
+
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+using namespace mcl_srch;
+
+constexpr int32_t kMaxHits = 65536;
+
+// the buffers of the search, kept between calls and grown with the lattice
+struct mcl_search {
+    // the lattice on the device and what it was made from
+    unsigned long long lattice_epoch = 0;       // map_epoch of the lattice (0: none)
+    int32_t lattice_stride = 0;
+    int64_t n_pos = 0;
+    int nx = 0, ny = 0;
+    std::vector<double> xy;                     // 2 n_pos: the table the device holds
+    int64_t cap_pos = 0, cap_map = 0;
+    double2 *d_xy = nullptr;
+    int2 *d_lat = nullptr;
+    int32_t *d_pmap = nullptr;
+    std::vector<double> theta;                  // the headings the device holds
+    int64_t cap_head = 0;
+    double *d_theta = nullptr;
+    // the scan
+    int64_t cap_b = 0;
+    double2 *d_beams = nullptr, *h_beams = nullptr;
+    float *h_obs = nullptr;
+    // the volume and the hits
+    int64_t cap_poses = 0;
+    double *d_score = nullptr;
+    uint64_t *d_key = nullptr, *d_key2 = nullptr;
+    uint32_t *d_val = nullptr, *d_val2 = nullptr;
+    void *d_tmp = nullptr;
+    size_t tmp_bytes = 0;
+    unsigned long long *d_count = nullptr, *h_count = nullptr;
+    uint64_t *h_key = nullptr;                  // kMaxHits each, pinned
+    uint32_t *h_val = nullptr;
+    // the volume d_score holds: of which map, how many poses (0: none)
+    unsigned long long volume_epoch = 0;
+    int64_t volume_n = 0;
+    size_t device_bytes = 0;
+};
+
+namespace {
+
+using mcl_host::dfree;
+using mcl_host::fail;
+
+template <class T>
+void hfree(T *&p)
+{
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+}
+
+template <class T>
+int grow_dev(mcl_engine *h, mcl_search *s, T *&p, size_t want)
+{
+    dfree(p);
+    HIPCHK(h, hipMalloc(&p, want * sizeof(T)));
+    s->device_bytes += want * sizeof(T);
+    return MCL_OK;
+}
+
+template <class T>
+int grow_host(mcl_engine *h, T *&p, size_t want)
+{
+    hfree(p);
+    HIPCHK(h, hipHostMalloc((void **)&p, want * sizeof(T)));
+    return MCL_OK;
+}
+
+#define SRCH_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
+
+// the lattice of this map at this stride on the device (formed and uploaded when either changed)
+int search_lattice_upload(mcl_engine *h, mcl_search *s, int stride)
+{
+    if (s->lattice_epoch == h->map_epoch && s->lattice_stride == stride) return MCL_OK;
+    s->lattice_epoch = 0;
+    std::vector<int32_t> lat, pmap;
+    s->xy.clear();
+    s->n_pos = mcl_host::search_lattice(stride, h->grid_host.data(), h->W, h->H, h->res, h->ox, h->oy, nullptr, &s->xy, &lat, &pmap, s->nx,
+                                        s->ny);
+    if (s->n_pos > 0) {
+        if (s->n_pos > s->cap_pos) {
+            s->cap_pos = 0;
+            SRCH_TRY(grow_dev(h, s, s->d_xy, (size_t)s->n_pos));
+            SRCH_TRY(grow_dev(h, s, s->d_lat, (size_t)s->n_pos));
+            s->cap_pos = s->n_pos;
+        }
+        if ((int64_t)pmap.size() > s->cap_map) {
+            s->cap_map = 0;
+            SRCH_TRY(grow_dev(h, s, s->d_pmap, pmap.size()));
+            s->cap_map = (int64_t)pmap.size();
+        }
+        HIPCHK(h, hipMemcpy(s->d_xy, s->xy.data(), (size_t)s->n_pos * sizeof(double2), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(s->d_lat, lat.data(), (size_t)s->n_pos * sizeof(int2), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(s->d_pmap, pmap.data(), pmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    s->lattice_epoch = h->map_epoch;
+    s->lattice_stride = stride;
+    return MCL_OK;
+}
+
+int search_headings_upload(mcl_engine *h, mcl_search *s, int n_head)
+{
+    if ((int64_t)s->theta.size() == n_head) return MCL_OK;
+    s->theta.clear();
+    std::vector<double> t((size_t)n_head);
+    mcl_host::search_headings(n_head, t.data());
+    if (n_head > s->cap_head) {
+        s->cap_head = 0;
+        SRCH_TRY(grow_dev(h, s, s->d_theta, (size_t)n_head));
+        s->cap_head = n_head;
+    }
+    HIPCHK(h, hipMemcpy(s->d_theta, t.data(), (size_t)n_head * sizeof(double), hipMemcpyHostToDevice));
+    s->theta.swap(t);
+    return MCL_OK;
+}
+
+// room for a volume of n_poses, its sort and a scan of B beams
+int search_alloc(mcl_engine *h, mcl_search *s, int64_t n_poses, int B)
+{
+    if (!s->d_count) {
+        SRCH_TRY(grow_dev(h, s, s->d_count, 1));
+        SRCH_TRY(grow_host(h, s->h_count, 1));
+        SRCH_TRY(grow_host(h, s->h_key, (size_t)kMaxHits));
+        SRCH_TRY(grow_host(h, s->h_val, (size_t)kMaxHits));
+    }
+    if (B > s->cap_b) {
+        s->cap_b = 0;
+        SRCH_TRY(grow_dev(h, s, s->d_beams, (size_t)B));
+        SRCH_TRY(grow_host(h, s->h_beams, (size_t)B));
+        SRCH_TRY(grow_host(h, s->h_obs, (size_t)B));
+        s->cap_b = B;
+    }
+    if (n_poses > s->cap_poses) {
+        s->cap_poses = 0;
+        s->volume_n = 0;
+        SRCH_TRY(grow_dev(h, s, s->d_score, (size_t)n_poses));
+        SRCH_TRY(grow_dev(h, s, s->d_key, (size_t)n_poses));
+        SRCH_TRY(grow_dev(h, s, s->d_key2, (size_t)n_poses));
+        SRCH_TRY(grow_dev(h, s, s->d_val, (size_t)n_poses));
+        SRCH_TRY(grow_dev(h, s, s->d_val2, (size_t)n_poses));
+        size_t tb = 0;
+        HIPCHK(h, rocprim::radix_sort_pairs(nullptr, tb, s->d_key, s->d_key2, s->d_val, s->d_val2, (size_t)n_poses, 0, 64, h->stream));
+        dfree(s->d_tmp);
+        s->tmp_bytes = std::max<size_t>(tb, 16);
+        HIPCHK(h, hipMalloc(&s->d_tmp, s->tmp_bytes));
+        s->device_bytes += s->tmp_bytes;
+        s->cap_poses = n_poses;
+    }
+    return MCL_OK;
+}
+
+// the score a sort key stands for (score_key's inverse)
+double key_score(uint64_t key)
+{
+    const uint64_t asc = ~key;
+    const uint64_t b = (asc >> 63) ? (asc & 0x7fffffffffffffffull) : ~asc;
+    double v;
+    std::memcpy(&v, &b, sizeof v);
+    return v;
+}
+
+}  // namespace
+
+void search_free(struct mcl_search *s)
+{
+    if (!s) return;
+    dfree(s->d_xy); dfree(s->d_lat); dfree(s->d_pmap); dfree(s->d_theta); dfree(s->d_beams); dfree(s->d_score); dfree(s->d_key); dfree(s->d_key2);
+    dfree(s->d_val); dfree(s->d_val2); dfree(s->d_tmp); dfree(s->d_count);
+    hfree(s->h_beams); hfree(s->h_obs); hfree(s->h_count); hfree(s->h_key); hfree(s->h_val);
+    delete s;
+}
+
+extern "C" {
+
+int mcl_global_search(mcl_engine_t *h, const mcl_search_config_t *cfg, const float *obs, int32_t n_beams, int32_t max_hits,
+                      mcl_search_hit_t *hits, int64_t *n_hits, uint64_t stats[4])
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    mcl_search_config_t c;
+    if (cfg) c = *cfg; else mcl_default_search_config(&c);
+    // arguments, then readiness (S8)
+    if (const char *why = mcl_host::search_invalid(&c)) return fail(h, MCL_ERR_INVALID_ARG, why);
+    if (!obs || !n_hits) return fail(h, MCL_ERR_INVALID_ARG, "global search: obs / n_hits is null");
+    if (max_hits < 0 || max_hits > kMaxHits) return fail(h, MCL_ERR_INVALID_ARG, "global search: max_hits must be in [0, 65536]");
+    if (max_hits > 0 && !hits) return fail(h, MCL_ERR_INVALID_ARG, "global search: hits is null");
+    if (!h->have_map) return fail(h, MCL_ERR_NOT_READY, "global search: no map is set");
+    if (h->B <= 0 || h->beam_cs_host.empty()) return fail(h, MCL_ERR_NOT_READY, "global search: no beam angles are set");
+    if (!h->lf_on || h->lf_K < 0 || !h->d_lf_D)
+        return fail(h, MCL_ERR_NOT_READY, "global search: the likelihood-field model is off (mcl_set_likelihood_field; the search reads its field and table)");
+    if (n_beams != h->B) return fail(h, MCL_ERR_INVALID_ARG, "global search: n_beams does not match the beam angles");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (!h->srch) h->srch = new mcl_search();
+    mcl_search *s = h->srch;
+    SRCH_TRY(search_lattice_upload(h, s, c.stride_cells));
+    if (s->n_pos == 0) return fail(h, MCL_ERR_NOT_READY, "global search: the lattice has no free position on this map");
+    const int64_t n_poses = s->n_pos * (int64_t)c.n_headings;
+    if (n_poses >= MCL_MAX_TOTAL_PARTICLES)
+        return fail(h, MCL_ERR_INVALID_ARG, "global search: n_positions * n_headings must stay below 2^27 (a larger stride_cells or fewer headings)");
+    SRCH_TRY(search_headings_upload(h, s, c.n_headings));
+    const int B = h->B;
+    SRCH_TRY(search_alloc(h, s, n_poses, B));
+    s->volume_n = 0;                                             // until this volume is whole
+
+    // S3: the readings of the candidate beams, the others NaN (no contribution), through the update's own rule
+    for (int j = 0; j < B; ++j) s->h_obs[j] = (j % c.beam_stride == 0) ? obs[j] : NAN;
+    const int nb = mcl_host::lf_used_beams(h, s->h_obs, 1, s->h_beams);
+    if (nb > 0) HIPCHK(h, hipMemcpyAsync(s->d_beams, s->h_beams, (size_t)nb * sizeof(double2), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(s->d_count, 0, sizeof(unsigned long long), h->stream));
+
+    Args a{};
+    a.xy = s->d_xy; a.lat = s->d_lat; a.pmap = s->d_pmap; a.theta = s->d_theta;
+    a.n_pos = (int32_t)s->n_pos; a.n_head = c.n_headings; a.nx = s->nx; a.ny = s->ny;
+    a.blocks_per_heading = (uint32_t)((s->n_pos + kThreads - 1) / kThreads);
+    a.beams = s->d_beams; a.nb = nb;
+    a.D = h->d_lf_D; a.W = h->W; a.H = h->H;
+    a.ox = h->ox; a.oy = h->oy; a.inv_res = 1.0 / h->res;
+    a.lf = h->d_lf_tab; a.K = h->lf_K;
+    a.score = s->d_score;
+    a.nms = c.nms;
+    a.key = s->d_key; a.val = s->d_val; a.count = s->d_count;
+    // (n_poses < 2^27, so both grids stay far below 2^31 workgroups)
+    const dim3 grid_score((unsigned)((uint64_t)a.blocks_per_heading * (uint64_t)c.n_headings));
+    if (h->lf_K < mcl::kLfLdsEntries)
+        hipLaunchKernelGGL(k_search_score<true>, grid_score, dim3(kThreads), (size_t)(h->lf_K + 1) * sizeof(float), h->stream, a);
+    else
+        hipLaunchKernelGGL(k_search_score<false>, grid_score, dim3(kThreads), 0, h->stream, a);
+    HIPCHK(h, hipGetLastError());
+    hipLaunchKernelGGL(k_search_mark, dim3((unsigned)((n_poses + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream, a);
+    HIPCHK(h, hipGetLastError());
+    const int64_t top = std::min<int64_t>(max_hits, n_poses);
+    if (top > 0) {
+        size_t tb = s->tmp_bytes;
+        HIPCHK(h, rocprim::radix_sort_pairs(s->d_tmp, tb, s->d_key, s->d_key2, s->d_val, s->d_val2, (size_t)n_poses, 0, 64, h->stream));
+        HIPCHK(h, hipMemcpyAsync(s->h_key, s->d_key2, (size_t)top * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(s->h_val, s->d_val2, (size_t)top * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipMemcpyAsync(s->h_count, s->d_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));                   // the one host wait
+    s->volume_epoch = h->map_epoch;
+    s->volume_n = n_poses;
+
+    const int64_t found = (int64_t)*s->h_count;
+    *n_hits = found;
+    const int64_t m = std::min<int64_t>(top, found);
+    for (int64_t r = 0; r < m; ++r) {
+        const int64_t idx = (int64_t)s->h_val[r];
+        const int64_t k = idx / s->n_pos, p = idx - k * s->n_pos;
+        hits[r].pose[0] = s->xy[(size_t)2 * p];
+        hits[r].pose[1] = s->xy[(size_t)2 * p + 1];
+        hits[r].pose[2] = s->theta[(size_t)k];
+        hits[r].log_likelihood = key_score(s->h_key[r]);
+        hits[r].index = idx;
+    }
+    if (stats) {
+        stats[0] = (uint64_t)s->n_pos; stats[1] = (uint64_t)n_poses; stats[2] = (uint64_t)nb; stats[3] = (uint64_t)s->device_bytes;
+    }
+    return MCL_OK;
+}
+
+int mcl_get_search_scores(mcl_engine_t *h, double *out, size_t n)
+{
+    if (!h || !out) return MCL_ERR_INVALID_ARG;
+    const mcl_search *s = h->srch;
+    if (!s || s->volume_n == 0 || s->volume_epoch != h->map_epoch || !h->have_map)
+        return fail(h, MCL_ERR_NOT_READY, "no score volume: no global search has run on this map");
+    if (n != (size_t)s->volume_n) return fail(h, MCL_ERR_INVALID_ARG, "the volume has n_headings x n_positions entries");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipMemcpyAsync(out, s->d_score, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MCL_OK;
+}
+
+int mcl_get_search_bytes(const mcl_engine_t *h, uint64_t *bytes)
+{
+    if (!h || !bytes) return MCL_ERR_INVALID_ARG;
+    *bytes = h->srch ? (uint64_t)h->srch->device_bytes : 0;
+    return MCL_OK;
+}
+
+}  // extern "C"

@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MCL_LIB") or os.path.join(_HERE, "libmcl_hip_engine.so")
 
 MCL_OK = 0
+MCL_ERR_INVALID_ARG = -1
 MCL_ERR_NOT_READY = -2
 MCL_ERR_PEER = -6          # sharded update: another rank reported a failure; the update is void on every rank
 MCL_ERR_TIMEOUT = -7       # sharded update: a collective did not finish in time; the communicator was aborted
@@ -46,6 +47,8 @@ EXPORTS = [
     "mcl_default_kld_config", "mcl_set_kld", "mcl_get_particle_count", "mcl_get_kld_state", "mcl_host_kld_bins", "mcl_host_kld_target",
     "mcl_default_cluster_config", "mcl_pose_clusters", "mcl_get_cluster_labels",
     "mcl_query_scans", "mcl_score_poses", "mcl_get_query_counters",
+    "mcl_default_search_config", "mcl_global_search", "mcl_get_search_scores", "mcl_get_search_bytes", "mcl_host_search_lattice",
+    "mcl_host_search_headings", "mcl_init_particles_mixture",
     "mcl_default_recovery_config", "mcl_set_recovery", "mcl_get_recovery_state", "mcl_set_recovery_state", "mcl_host_recovery_step",
     "mcl_default_likelihood_field_config", "mcl_set_likelihood_field", "mcl_get_likelihood_field", "mcl_get_likelihood_table",
     "mcl_host_likelihood_field", "mcl_host_likelihood_table",
@@ -127,6 +130,18 @@ assert POSE_SCORE_DTYPE.itemsize == C.sizeof(PoseScore) == 24
 MAX_QUERY_POSES = 65536
 
 
+class SearchConfig(C.Structure):
+    """mcl_search_config_t: the lattice of the global search (Engine.global_search)."""
+    _fields_ = [("stride_cells", C.c_int32), ("n_headings", C.c_int32), ("beam_stride", C.c_int32), ("nms", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
+# the numpy view of an array of mcl_search_hit_t (Engine.global_search)
+SEARCH_HIT_DTYPE = np.dtype([("pose", np.float64, (3,)), ("log_likelihood", np.float64), ("index", np.int64)])
+assert SEARCH_HIT_DTYPE.itemsize == 40
+MAX_SEARCH_HITS = 65536
+
+
 class EngineError(RuntimeError):
     """A call through the C ABI returned a negative mcl_status; `.status` holds it."""
 
@@ -201,6 +216,17 @@ def load_library(legacy=False):
         lib.mcl_query_scans.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         lib.mcl_score_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
         lib.mcl_get_query_counters.argtypes = [C.c_void_p, C.c_void_p]
+        lib.mcl_default_search_config.argtypes = [C.POINTER(SearchConfig)]
+        lib.mcl_default_search_config.restype = None
+        lib.mcl_global_search.argtypes = [C.c_void_p, C.POINTER(SearchConfig), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                          C.POINTER(C.c_int64), C.c_void_p]
+        lib.mcl_get_search_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.mcl_get_search_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        lib.mcl_host_search_lattice.argtypes = [C.POINTER(SearchConfig), C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_double,
+                                                C.c_double, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int64)]
+        lib.mcl_host_search_headings.argtypes = [C.POINTER(SearchConfig), C.c_void_p, C.c_size_t]
+        lib.mcl_init_particles_mixture.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                                   C.c_int64]
         lib.mcl_default_recovery_config.argtypes = [C.POINTER(RecoveryConfig)]
         lib.mcl_default_recovery_config.restype = None
         lib.mcl_set_recovery.argtypes = [C.c_void_p, C.POINTER(RecoveryConfig)]
@@ -355,6 +381,69 @@ def host_gaussian_factor(cov) -> np.ndarray:
     if rc != MCL_OK:
         raise EngineError(f"mcl_host_gaussian_factor rc={rc}", rc)
     return np.array([[L[0], 0.0, 0.0], [L[1], L[2], 0.0], [L[3], L[4], L[5]]])
+
+
+def default_search_config(**over) -> SearchConfig:
+    """mcl_default_search_config (stride 2, 72 headings, every beam, local maxima), with fields overridden by keyword."""
+    c = SearchConfig()
+    load_library().mcl_default_search_config(C.byref(c))
+    for name, v in over.items():
+        if name not in dict(SearchConfig._fields_):
+            raise AttributeError(name)
+        setattr(c, name, (C.c_int32 * 4)(*v) if name == "reserved" else v)
+    return c
+
+
+def host_search_lattice(grid, resolution, origin_x, origin_y, **fields):
+    """The positions of the global search's lattice over a map (mcl_host_search_lattice, rule S1; no device needed): (cells, xy) --
+    the linear map cell of every position (uint32) and its pose coordinates, shape (n_positions, 2)."""
+    g = _c(grid, np.int8)
+    H, W = g.shape
+    c = default_search_config(**fields)
+    lib, n = load_library(), C.c_int64()
+    args = (C.byref(c), _p(g), W, H, np.float32(resolution), float(origin_x), float(origin_y))
+    rc = lib.mcl_host_search_lattice(*args, None, None, 0, C.byref(n))
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_search_lattice rc={rc}", rc)
+    cells, xy = np.empty(n.value, np.uint32), np.empty((n.value, 2), np.float64)
+    if n.value:
+        rc = lib.mcl_host_search_lattice(*args, _p(cells), _p(xy), n.value, C.byref(n))
+        if rc != MCL_OK:
+            raise EngineError(f"mcl_host_search_lattice rc={rc}", rc)
+    return cells, xy
+
+
+def host_search_headings(**fields) -> np.ndarray:
+    """The headings of the global search (mcl_host_search_headings, rule S2; no device needed): n_headings doubles."""
+    c = default_search_config(**fields)
+    out = np.empty(max(int(c.n_headings), 0), np.float64)
+    rc = load_library().mcl_host_search_headings(C.byref(c), _p(out), out.size)
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_search_headings rc={rc}", rc)
+    return out
+
+
+def seed_counts(log_likelihoods, n) -> np.ndarray:
+    """How many of n particles each hit of a global search seeds (the counts of Engine.init_particles_mixture): shares
+    proportional to exp(ll - max ll), the floors of the exact shares first, the particles left over to the largest remainders,
+    ties to the earlier hit.  A hit at -inf gets none.  Pure Python (exact rationals), int64."""
+    import math
+    from fractions import Fraction
+    ll = [float(v) for v in np.asarray(log_likelihoods, np.float64).ravel()]
+    n = int(n)
+    if not ll or n < 0 or any(math.isnan(v) or v == math.inf for v in ll):
+        raise ValueError("seed_counts: needs at least one hit, n >= 0 and scores below +inf")
+    top = max(ll)
+    if top == -math.inf:
+        raise ValueError("seed_counts: every hit is at -inf")
+    w = [Fraction(math.exp(v - top)) for v in ll]            # (exp(-inf) = 0; the best hit weighs exactly 1)
+    total = sum(w)
+    share = [n * v / total for v in w]
+    counts = [int(v) for v in share]                         # floors (the shares are >= 0)
+    order = sorted(range(len(ll)), key=lambda i: (-(share[i] - counts[i]), i))
+    for i in order[:n - sum(counts)]:
+        counts[i] += 1
+    return np.array(counts, np.int64)
 
 
 def default_cluster_config(**over) -> ClusterConfig:
@@ -542,6 +631,20 @@ class Engine:
                                                        C.c_int64(n_total or n)), "mcl_init_particles_gaussian")
         self.n = self.particle_count()
 
+    def init_particles_mixture(self, means, covs, counts, n=None, first_global_index=0, n_total=None):
+        """One cloud from several Gaussians -- the hits of global_search, or clusters (mcl_init_particles_mixture): means (M, 3),
+        covs (M, 3, 3) or one (3, 3) for all, counts (M,) particles per component of the whole set (seed_counts makes them from hit
+        scores).  n / first_global_index: this engine's shard of the set (default: all of it)."""
+        m, k = _c(means, np.float64).reshape(-1, 3), _c(counts, np.int64).ravel()
+        c = _c(covs, np.float64)
+        c = _c(np.broadcast_to(c.reshape(-1, 3, 3), (m.shape[0], 3, 3)), np.float64)
+        assert k.size == m.shape[0]
+        n_total = int(k.sum()) if n_total is None else int(n_total)
+        n = n_total - first_global_index if n is None else int(n)
+        self._chk(self.lib.mcl_init_particles_mixture(self._h, C.c_int32(m.shape[0]), _p(m), _p(c), _p(k), C.c_int64(n),
+                                                      C.c_int64(first_global_index), C.c_int64(n_total)), "mcl_init_particles_mixture")
+        self.n = self.particle_count()
+
     # -- odometry motion models (off by default: the reference's model; DESIGN.md §4.11)
     def set_motion_model(self, model="diff", **fields):
         """Selects the motion model of the updates that follow: "diff" / "omni" with mcl_default_motion_config's values (AMCL's
@@ -726,6 +829,35 @@ class Engine:
         out = np.zeros(2, np.uint64)
         self._chk(self.lib.mcl_get_query_counters(self._h, _p(out)), "mcl_get_query_counters")
         return dict(level3_rays=int(out[0]), device_bytes=int(out[1]))
+
+    # -- global search (the likelihood-field model must be on)
+    def global_search(self, obs, max_hits=16, **fields):
+        """Scores every pose of a lattice over the map's free cells against the scan `obs` and reports the best-fitting ones
+        (mcl_global_search): a structured array (SEARCH_HIT_DTYPE: pose, log_likelihood, index) of at most max_hits hits, best
+        first, and {n_hits, n_positions, n_poses, used_beams, device_bytes}.  `fields` override mcl_default_search_config
+        (stride_cells, n_headings, beam_stride, nms).  Reads the map, the beams and the likelihood field only."""
+        c = default_search_config(**fields)
+        o = _c(obs, np.float32)
+        hits = np.zeros(int(max_hits), SEARCH_HIT_DTYPE)
+        n, st = C.c_int64(), np.zeros(4, np.uint64)
+        self._chk(self.lib.mcl_global_search(self._h, C.byref(c), _p(o), C.c_int32(o.size), C.c_int32(int(max_hits)),
+                                             _p(hits) if hits.size else None, C.byref(n), _p(st)), "mcl_global_search")
+        self._search_poses = int(st[1])
+        return hits[:min(n.value, hits.size)], dict(n_hits=n.value, n_positions=int(st[0]), n_poses=int(st[1]), used_beams=int(st[2]),
+                                                    device_bytes=int(st[3]))
+
+    def search_scores(self, n_headings=None):
+        """The score volume of the last global_search (mcl_get_search_scores): n_headings * n_positions doubles, heading-major;
+        with n_headings, reshaped to (n_headings, n_positions)."""
+        out = np.empty(getattr(self, "_search_poses", 0) or 1, np.float64)
+        self._chk(self.lib.mcl_get_search_scores(self._h, _p(out), C.c_size_t(out.size)), "mcl_get_search_scores")
+        return out.reshape(int(n_headings), -1) if n_headings else out
+
+    def search_bytes(self) -> int:
+        """Bytes of device memory the search's buffers have asked for so far (0 on an engine that never searched)."""
+        v = C.c_uint64()
+        self._chk(self.lib.mcl_get_search_bytes(self._h, C.byref(v)), "mcl_get_search_bytes")
+        return int(v.value)
 
     def sensor_update(self, obs):
         o = _c(obs, np.float32)
