@@ -419,6 +419,78 @@ int mcl_host_search_lattice(const mcl_search_config_t *c, const int8_t *data, ui
                             double origin_x, double origin_y, uint32_t *cells, double *xy, size_t n, int64_t *n_positions);
 int mcl_host_search_headings(const mcl_search_config_t *c, double *theta, size_t n);
 
+/* ---- pose refinement: a dense local window around each seed pose, scored against one scan (correlative scan matching on the
+ *      likelihood field) ---------------------------------------------------------------------------------
+ * A hit of mcl_global_search sits on the search's lattice, a cluster mean or an /initialpose is only roughly right.  For each of
+ * M seed poses the refinement scores every pose of a regular window in (x, y, theta) under the likelihood-field model and
+ * reports the best window pose and the likelihood-weighted mean and covariance of the window: what mcl_init_particles_mixture /
+ * mcl_init_particles_gaussian take.  Read-only, as the pose query and the search are.
+ *   R1 window.  nx = ny = 2 half_xy + 1, nt = 2 half_theta + 1, n_win = nx ny nt; the window index of (ix, iy, it) is
+ *     w = (it ny + iy) nx + ix (ix fastest).  sx = step_xy_cells * res, res the map's float resolution widened to double, formed
+ *     once on the host.  For a seed (x0, y0, t0): x = x0 + (double)(ix - half_xy) * sx, y = y0 + (double)(iy - half_xy) * sx,
+ *     theta = t0 + (double)(it - half_theta) * step_theta_rad, the multiply and the add each rounded (no fma) -- on the device
+ *     and in mcl_host_refine_window alike.  theta is NOT wrapped (the score takes sincos of any heading; a caller normalises if it
+ *     wants to).  The device forms the window poses from the M seeds; no pose table is uploaded.
+ *   R2 score.  score[m n_win + w] = LF3-LF5 of window pose w of seed m: bit for bit what mcl_score_poses returns for that pose
+ *     and the same obs, with the readings of the beams j, j % beam_stride != 0, replaced by NaN (S3's rule).  The in-order fp64
+ *     sum over the used beams; finite or -inf, never NaN.
+ *   R3 best.  With q = dix^2 + diy^2 + dit^2 (dix = ix - half_xy, ...: the integer offset from the window centre), pose a is
+ *     better than pose b iff score_a > score_b, or the scores are equal and q_a < q_b, or both are equal and w_a < w_b.  (The
+ *     field is piecewise constant, so equal scores are common at fine steps: among them the pose nearest the seed wins, not the
+ *     lowest index.)  The order is total, so the best pose is unique.  best = its pose by R1, best_index = its w,
+ *     best_log_likelihood = its score; seed_log_likelihood = the score of the window centre.
+ *   R4 moments, about the best pose b in integer step units: u_i = (ix_i - ix_b, iy_i - iy_b, it_i - it_b), w_i =
+ *     exp(s_i - s_b) (0 for s_i = -inf), S = sum w_i, m_a = sum w_i u_ia / S, C_ab = sum w_i u_ia u_ib / S - m_a m_b.  With step =
+ *     (sx, sx, step_theta_rad): mean_a = best_a + step_a m_a, cov_ab = (step_a step_b) C_ab + delta_ab step_a^2 / 12 (cov is
+ *     row-major and exactly symmetric).  The delta term is the variance of the box a window pose stands for: it keeps cov positive
+ *     definite when one pose carries all the weight, so G1 accepts every result.  weight_sum = S (1: one sharp pose; n_win: a
+ *     flat window).  All fp64 in a fixed order: window pose i goes to partial sum i % 256 in ascending i, the 256 partial sums
+ *     are added by a tree (l += l + 128, 64, ..., 1).  The same state gives the same bits; no atomics.
+ *     A void seed (every score of its window -inf): best = the window centre, best_log_likelihood = -inf, weight_sum = 0,
+ *     m = 0 and C = 0: mean = the seed, cov = the delta term alone.
+ *   R5 stats = {n_win, poses scored (M n_win), used beams, bytes of device memory the refinement's buffers have asked for so
+ *     far}; stats may be NULL.  mcl_get_refine_scores copies the volume of the last call (n == M n_win, seed-major);
+ *     MCL_ERR_NOT_READY before any call and after mcl_set_map.
+ *   R6 read-only (as Q5 / S7).  The refinement uses buffers of its own, allocated on the first call (mcl_get_refine_bytes: 0 on
+ *     an engine that never refined), and none of the update's scratch or staged observation; it drops no captured graph and
+ *     makes one host wait, at its end, before which only the M result records are copied back.  Every later update is
+ *     bit-identical to one of an engine that never refined.
+ *   R7 where it works.  A map, beam angles and the likelihood-field model ON: MCL_ERR_NOT_READY otherwise (the message says which
+ *     is missing).  MCL_ERR_INVALID_ARG for half_xy or half_theta < 0, a step that is not finite and > 0, beam_stride < 1,
+ *     reserved != 0, n_win > 32768, M outside [1, 4096], M n_win >= MCL_MAX_TOTAL_PARTICLES, a null seeds / obs / out,
+ *     n_beams != B, a seed with a non-finite component.  Seeds off the map or inside a wall are allowed and score like any pose.
+ *     Single engine only (the likelihood field is).  Seeds that refine to the same maximum are not merged, and the window is not
+ *     iterated: a caller re-centres and calls again if it wants to. */
+typedef struct {
+    int32_t half_xy;                        /* >= 0, default 4: window columns / rows = 2 half_xy + 1                          */
+    int32_t half_theta;                     /* >= 0, default 10: window headings = 2 half_theta + 1                            */
+    double  step_xy_cells;                  /* > 0, finite, default 0.5: position step in map cells                            */
+    double  step_theta_rad;                 /* > 0, finite, default pi / 360                                                   */
+    int32_t beam_stride;                    /* >= 1, default 1 (S3's rule)                                                     */
+    int32_t reserved[3];                    /* must be 0                                                                      */
+} mcl_refine_config_t;
+typedef struct {
+    double  best[3];                        /* R3                                                                             */
+    double  best_log_likelihood;
+    double  seed_log_likelihood;            /* the score of the window centre                                                 */
+    int64_t best_index;                     /* window index of best (R1)                                                      */
+    double  mean[3];                        /* R4                                                                             */
+    double  cov[9];                         /* R4, row-major                                                                  */
+    double  weight_sum;                     /* sum of exp(s_i - s_best): 1 = one sharp pose, 0 = a void seed                  */
+} mcl_refine_result_t;
+void mcl_default_refine_config(mcl_refine_config_t *c);
+/* seeds_colmajor: M x 3 column-major (x of every seed, then y, then theta), as the pose query takes its poses; out: M records */
+int mcl_refine_poses(mcl_engine_t *h, const mcl_refine_config_t *c /* NULL = the defaults */, const double *seeds_colmajor,
+                     int32_t M, const float *obs, int32_t n_beams, mcl_refine_result_t *out, uint64_t stats[4]);
+int mcl_get_refine_scores(mcl_engine_t *h, double *out, size_t n);
+int mcl_get_refine_bytes(const mcl_engine_t *h, uint64_t *bytes);
+/* R1 and R3 / R4 on the host, without a device.  The window: poses is n_win x 3 row-major, n_win must match the config.  The
+ * reduction: what mcl_refine_poses reports for one seed whose window scored `scores` (n_win of them; none may be NaN or +inf).
+ * MCL_ERR_INVALID_ARG for a refused config (R7), a null pointer, a resolution that is not finite and > 0, a non-finite seed. */
+int mcl_host_refine_window(const mcl_refine_config_t *c, const double seed[3], float resolution, double *poses, size_t n_win);
+int mcl_host_refine_reduce(const mcl_refine_config_t *c, const double seed[3], float resolution, const double *scores, size_t n_win,
+                           mcl_refine_result_t *out);
+
 /* ---- recovery by random-particle injection (augmented MCL, Probabilistic Robotics Table 8.3; AMCL's recovery_alpha_slow /
  *      recovery_alpha_fast) -------------------------------------------------------------------------------
  * Off by default.  With it on, a resampling mcl_update replaces each child, with probability p, by a pose drawn uniformly from

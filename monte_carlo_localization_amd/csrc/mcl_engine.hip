@@ -1064,6 +1064,7 @@ void mcl_destroy(mcl_engine_t *h)
     if (h->clu) { cluster_free(h->clu); h->clu = nullptr; }
     if (h->qry) { query_free(h->qry); h->qry = nullptr; }
     if (h->srch) { search_free(h->srch); h->srch = nullptr; }
+    if (h->rfn) { refine_free(h->rfn); h->rfn = nullptr; }
     graph_reset(h);
     for (int b = 0; b < 2; ++b) { dfree(h->d_x[b]); dfree(h->d_y[b]); dfree(h->d_th[b]); }
     dfree(h->d_w); dfree(h->d_logw); dfree(h->d_tmp); dfree(h->d_logw_acc); dfree(h->d_carry[0]); dfree(h->d_carry[1]); dfree(h->d_q); dfree(h->d_cdf); dfree(h->d_blocktot); dfree(h->d_bm); dfree(h->d_bm_pop); dfree(h->d_bm_pref);

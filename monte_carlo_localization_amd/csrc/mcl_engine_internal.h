@@ -9,6 +9,8 @@
 //                    kernels and buffers, called outside the update)
 //   mcl_search.hip   mcl_global_search: the likelihood-field score of every pose of a lattice over the map, and its hits (its own
 //                    kernels and buffers, called outside the update)
+//   mcl_refine.hip   mcl_refine_poses: the score of a dense window around each seed pose, its best pose, mean and covariance (its
+//                    own kernels and buffers, called outside the update)
 // Only mcl_engine.hip includes the kernels (mcl_kernels.h); mcl_comm.hip and mcl_group.hip reach the few kernels they launch
 // through the launch_* functions below.  Every function declared here is defined once, under this name.
 #pragma once
@@ -47,6 +49,8 @@ struct mcl_query;
 void query_free(struct mcl_query *q);      // mcl_query.hip
 struct mcl_search;
 void search_free(struct mcl_search *s);    // mcl_search.hip
+struct mcl_refine;
+void refine_free(struct mcl_refine *r);    // mcl_refine.hip
 struct mcl_engine {
     mcl_config_t cfg{};
     int num_cu = 256;
@@ -303,6 +307,8 @@ struct mcl_engine {
     struct mcl_search *srch = nullptr;
     std::vector<int8_t> grid_host;
     unsigned long long map_epoch = 0;
+    // pose refinement (mcl_refine_poses): its own buffers, allocated on the first call
+    struct mcl_refine *rfn = nullptr;
 };
 
 #define HIPCHK(h, call)                                                                          \

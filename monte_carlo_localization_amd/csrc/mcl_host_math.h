@@ -33,4 +33,5 @@ const char *search_invalid(const mcl_search_config_t *c);
 int64_t search_lattice(int stride, const int8_t *data, int W, int H, double res, double ox, double oy, std::vector<uint32_t> *cells,
                        std::vector<double> *xy, std::vector<int32_t> *lat, std::vector<int32_t> *pmap, int &nx, int &ny);
 void search_headings(int n_headings, double *theta);
+const char *refine_invalid(const mcl_refine_config_t *c);
 }  // namespace mcl_host

@@ -9,6 +9,7 @@
 #include <cstring>
 
 #include "mcl_motion.h"
+#include "mcl_refine_core.h"
 #include "mcl_wedge.h"
 
 namespace mcl_host {
@@ -457,6 +458,22 @@ void search_headings(int n_headings, double *theta)
     for (int64_t k = 0; k < n_headings; ++k) theta[k] = (double)(2 * k - (int64_t)n_headings) * step;
 }
 
+// ---- the pose refinement (mcl_refine_poses): its config check (R7)
+const char *refine_invalid(const mcl_refine_config_t *c)
+{
+    if (c->half_xy < 0 || c->half_theta < 0) return "refine: half_xy and half_theta must be >= 0";
+    if (!(std::isfinite(c->step_xy_cells) && c->step_xy_cells > 0.0)) return "refine: step_xy_cells must be finite and > 0";
+    if (!(std::isfinite(c->step_theta_rad) && c->step_theta_rad > 0.0)) return "refine: step_theta_rad must be finite and > 0";
+    if (c->beam_stride < 1) return "refine: beam_stride must be >= 1";
+    for (int i = 0; i < 3; ++i)
+        if (c->reserved[i] != 0) return "refine: reserved must be 0";
+    // n_win = (2 half_xy + 1)^2 (2 half_theta + 1) <= 32768, without overflow
+    if (c->half_xy > 90 || c->half_theta > 16383) return "refine: the window must have at most 32768 poses";
+    const int64_t nx = 2 * (int64_t)c->half_xy + 1, nt = 2 * (int64_t)c->half_theta + 1;
+    if (nx * nx * nt > mcl_rf::kMaxWindow) return "refine: the window must have at most 32768 poses";
+    return nullptr;
+}
+
 // G1: the lower Cholesky factor of a symmetric positive semi-definite 3 x 3 matrix (row-major), L = {L00, L10, L11, L20, L21, L22}
 const char *gaussian_factor(const double cov[9], double L[6])
 {
@@ -749,6 +766,68 @@ int mcl_host_search_headings(const mcl_search_config_t *c, double *theta, size_t
 {
     if (!c || search_invalid(c) || !theta || n != (size_t)c->n_headings) return MCL_ERR_INVALID_ARG;
     search_headings(c->n_headings, theta);
+    return MCL_OK;
+}
+
+void mcl_default_refine_config(mcl_refine_config_t *c)
+{
+    if (!c) return;
+    *c = mcl_refine_config_t{};
+    c->half_xy = 4; c->half_theta = 10; c->step_xy_cells = 0.5; c->step_theta_rad = 3.14159265358979323846 / 360.0; c->beam_stride = 1;
+}
+
+static bool refine_host_args_ok(const mcl_refine_config_t *c, const double seed[3], float resolution)
+{
+    return c && !refine_invalid(c) && seed && resolution > 0.0f && std::isfinite(resolution) && std::isfinite(seed[0]) &&
+           std::isfinite(seed[1]) && std::isfinite(seed[2]);
+}
+
+int mcl_host_refine_window(const mcl_refine_config_t *c, const double seed[3], float resolution, double *poses, size_t n_win)
+{
+    if (!refine_host_args_ok(c, seed, resolution) || !poses) return MCL_ERR_INVALID_ARG;
+    const mcl_rf::Window g = mcl_rf::window_of(*c, (double)resolution);
+    if (n_win != (size_t)g.n_win) return MCL_ERR_INVALID_ARG;
+    for (int32_t w = 0; w < g.n_win; ++w) {
+        int32_t dx, dy, dt;
+        mcl_rf::offsets(g, w, dx, dy, dt);
+        poses[3 * (size_t)w] = mcl_rf::coord(seed[0], dx, g.sx);
+        poses[3 * (size_t)w + 1] = mcl_rf::coord(seed[1], dy, g.sx);
+        poses[3 * (size_t)w + 2] = mcl_rf::coord(seed[2], dt, g.st);
+    }
+    return MCL_OK;
+}
+
+// k_refine_reduce on the host: the same order of R3, the same 256 partial sums and tree of R4
+int mcl_host_refine_reduce(const mcl_refine_config_t *c, const double seed[3], float resolution, const double *scores, size_t n_win,
+                           mcl_refine_result_t *out)
+{
+    if (!refine_host_args_ok(c, seed, resolution) || !scores || !out) return MCL_ERR_INVALID_ARG;
+    const mcl_rf::Window g = mcl_rf::window_of(*c, (double)resolution);
+    if (n_win != (size_t)g.n_win) return MCL_ERR_INVALID_ARG;
+    for (int32_t w = 0; w < g.n_win; ++w)
+        if (std::isnan(scores[w]) || scores[w] == INFINITY) return MCL_ERR_INVALID_ARG;
+    int32_t wb = 0, qb = 0;
+    for (int32_t w = 0; w < g.n_win; ++w) {
+        int32_t dx, dy, dt;
+        mcl_rf::offsets(g, w, dx, dy, dt);
+        const int32_t q = dx * dx + dy * dy + dt * dt;
+        if (w == 0 || mcl_rf::better(scores[w], q, w, scores[wb], qb, wb)) { wb = w; qb = q; }
+    }
+    int32_t bx, by, bt;
+    mcl_rf::offsets(g, wb, bx, by, bt);
+    std::vector<double> part((size_t)mcl_rf::kSums * mcl_rf::kThreads, 0.0);
+    for (int l = 0; l < mcl_rf::kThreads; ++l) {
+        double acc[mcl_rf::kSums] = {};
+        for (int32_t w = l; w < g.n_win; w += mcl_rf::kThreads) mcl_rf::accumulate(g, w, scores[w], scores[wb], bx, by, bt, acc);
+        for (int k = 0; k < mcl_rf::kSums; ++k) part[(size_t)k * mcl_rf::kThreads + l] = acc[k];
+    }
+    for (int st = mcl_rf::kThreads / 2; st > 0; st >>= 1)
+        for (int l = 0; l < st; ++l)
+            for (int k = 0; k < mcl_rf::kSums; ++k) part[(size_t)k * mcl_rf::kThreads + l] += part[(size_t)k * mcl_rf::kThreads + l + st];
+    double sums[mcl_rf::kSums];
+    for (int k = 0; k < mcl_rf::kSums; ++k) sums[k] = part[(size_t)k * mcl_rf::kThreads];
+    const int32_t wc = (g.half_theta * g.nx + g.half_xy) * g.nx + g.half_xy;
+    mcl_rf::finish(g, seed[0], seed[1], seed[2], wb, scores[wb], scores[wc], sums, out);
     return MCL_OK;
 }
 

@@ -49,6 +49,8 @@ EXPORTS = [
     "mcl_query_scans", "mcl_score_poses", "mcl_get_query_counters",
     "mcl_default_search_config", "mcl_global_search", "mcl_get_search_scores", "mcl_get_search_bytes", "mcl_host_search_lattice",
     "mcl_host_search_headings", "mcl_init_particles_mixture",
+    "mcl_default_refine_config", "mcl_refine_poses", "mcl_get_refine_scores", "mcl_get_refine_bytes", "mcl_host_refine_window",
+    "mcl_host_refine_reduce",
     "mcl_default_recovery_config", "mcl_set_recovery", "mcl_get_recovery_state", "mcl_set_recovery_state", "mcl_host_recovery_step",
     "mcl_default_likelihood_field_config", "mcl_set_likelihood_field", "mcl_get_likelihood_field", "mcl_get_likelihood_table",
     "mcl_host_likelihood_field", "mcl_host_likelihood_table",
@@ -142,6 +144,20 @@ assert SEARCH_HIT_DTYPE.itemsize == 40
 MAX_SEARCH_HITS = 65536
 
 
+class RefineConfig(C.Structure):
+    """mcl_refine_config_t: the window of the pose refinement (Engine.refine_poses)."""
+    _fields_ = [("half_xy", C.c_int32), ("half_theta", C.c_int32), ("step_xy_cells", C.c_double), ("step_theta_rad", C.c_double),
+                ("beam_stride", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+# the numpy view of an array of mcl_refine_result_t (Engine.refine_poses)
+REFINE_DTYPE = np.dtype([("best", np.float64, (3,)), ("best_log_likelihood", np.float64), ("seed_log_likelihood", np.float64),
+                         ("best_index", np.int64), ("mean", np.float64, (3,)), ("cov", np.float64, (3, 3)),
+                         ("weight_sum", np.float64)])
+assert REFINE_DTYPE.itemsize == 152 and C.sizeof(RefineConfig) == 40
+MAX_REFINE_SEEDS, MAX_REFINE_WINDOW = 4096, 32768
+
+
 class EngineError(RuntimeError):
     """A call through the C ABI returned a negative mcl_status; `.status` holds it."""
 
@@ -225,6 +241,14 @@ def load_library(legacy=False):
         lib.mcl_host_search_lattice.argtypes = [C.POINTER(SearchConfig), C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_double,
                                                 C.c_double, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int64)]
         lib.mcl_host_search_headings.argtypes = [C.POINTER(SearchConfig), C.c_void_p, C.c_size_t]
+        lib.mcl_default_refine_config.argtypes = [C.POINTER(RefineConfig)]
+        lib.mcl_default_refine_config.restype = None
+        lib.mcl_refine_poses.argtypes = [C.c_void_p, C.POINTER(RefineConfig), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                         C.c_void_p, C.c_void_p]
+        lib.mcl_get_refine_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.mcl_get_refine_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        lib.mcl_host_refine_window.argtypes = [C.POINTER(RefineConfig), C.c_void_p, C.c_float, C.c_void_p, C.c_size_t]
+        lib.mcl_host_refine_reduce.argtypes = [C.POINTER(RefineConfig), C.c_void_p, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.mcl_init_particles_mixture.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                                    C.c_int64]
         lib.mcl_default_recovery_config.argtypes = [C.POINTER(RecoveryConfig)]
@@ -421,6 +445,50 @@ def host_search_headings(**fields) -> np.ndarray:
     if rc != MCL_OK:
         raise EngineError(f"mcl_host_search_headings rc={rc}", rc)
     return out
+
+
+def default_refine_config(**over) -> RefineConfig:
+    """mcl_default_refine_config (a 9 x 9 x 21 window: +-2 cells in steps of half a cell, +-5 degrees in steps of half a degree,
+    every beam), with fields overridden by keyword."""
+    c = RefineConfig()
+    load_library().mcl_default_refine_config(C.byref(c))
+    for name, v in over.items():
+        if name not in dict(RefineConfig._fields_):
+            raise AttributeError(name)
+        setattr(c, name, (C.c_int32 * 3)(*v) if name == "reserved" else v)
+    return c
+
+
+def refine_window_size(c: RefineConfig) -> int:
+    """n_win of a config (rule R1), in Python's integers"""
+    return (2 * int(c.half_xy) + 1) ** 2 * (2 * int(c.half_theta) + 1)
+
+
+def host_refine_window(seed, resolution, **fields) -> np.ndarray:
+    """The window poses around `seed` (mcl_host_refine_window, rule R1; no device needed): (n_win, 3) rows of (x, y, theta) in
+    window-index order, ix fastest.  `fields` override mcl_default_refine_config."""
+    c = default_refine_config(**fields)
+    s = _c(seed, np.float64).ravel()
+    assert s.size == 3
+    n = refine_window_size(c)
+    out = np.empty((n if 0 < n <= MAX_REFINE_WINDOW else 1, 3), np.float64)
+    rc = load_library().mcl_host_refine_window(C.byref(c), _p(s), np.float32(resolution), _p(out), C.c_size_t(out.shape[0]))
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_refine_window rc={rc}", rc)
+    return out
+
+
+def host_refine_reduce(seed, resolution, scores, **fields) -> np.ndarray:
+    """What Engine.refine_poses reports for one seed whose window scored `scores` (mcl_host_refine_reduce, rules R3 / R4; no device
+    needed): one REFINE_DTYPE record."""
+    c = default_refine_config(**fields)
+    s, v = _c(seed, np.float64).ravel(), _c(scores, np.float64).ravel()
+    assert s.size == 3
+    out = np.zeros(1, REFINE_DTYPE)
+    rc = load_library().mcl_host_refine_reduce(C.byref(c), _p(s), np.float32(resolution), _p(v), C.c_size_t(v.size), _p(out))
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_refine_reduce rc={rc}", rc)
+    return out[0]
 
 
 def seed_counts(log_likelihoods, n) -> np.ndarray:
@@ -857,6 +925,40 @@ class Engine:
         """Bytes of device memory the search's buffers have asked for so far (0 on an engine that never searched)."""
         v = C.c_uint64()
         self._chk(self.lib.mcl_get_search_bytes(self._h, C.byref(v)), "mcl_get_search_bytes")
+        return int(v.value)
+
+    # -- pose refinement (the likelihood-field model must be on; DESIGN.md §4.14)
+    def refine_poses(self, poses, obs, **fields):
+        """Scores a dense window of poses around every seed pose against the scan `obs` (mcl_refine_poses): a structured array
+        (REFINE_DTYPE: best, best_log_likelihood, seed_log_likelihood, best_index, mean, cov, weight_sum), one record per seed, and
+        {n_win, n_poses, used_beams, device_bytes}.  `poses`: (M, 3) rows of (x, y, theta), or one pose -- the hits of global_search,
+        cluster means, an /initialpose.  `fields` override mcl_default_refine_config (half_xy, half_theta, step_xy_cells,
+        step_theta_rad, beam_stride).  Reads the beams and the likelihood field only.  The chain from one scan to a cloud:
+            hits, _ = e.global_search(obs)
+            r, _ = e.refine_poses(hits["pose"], obs)
+            e.init_particles_mixture(r["mean"], r["cov"], seed_counts(r["best_log_likelihood"], n))"""
+        c = default_refine_config(**fields)
+        p = self._query_poses(poses)
+        M = p.shape[1]
+        o = _c(obs, np.float32)
+        out = np.zeros(M, REFINE_DTYPE)
+        st = np.zeros(4, np.uint64)
+        self._chk(self.lib.mcl_refine_poses(self._h, C.byref(c), _p(p) if M else None, C.c_int32(M), _p(o), C.c_int32(o.size),
+                                            _p(out) if M else None, _p(st)), "mcl_refine_poses")
+        self._refine_shape = (M, int(st[0]))
+        return out, dict(n_win=int(st[0]), n_poses=int(st[1]), used_beams=int(st[2]), device_bytes=int(st[3]))
+
+    def refine_scores(self):
+        """The score volume of the last refine_poses (mcl_get_refine_scores): (M, n_win) doubles, window index ix fastest."""
+        shape = getattr(self, "_refine_shape", None) or (1, 1)
+        out = np.empty(shape, np.float64)
+        self._chk(self.lib.mcl_get_refine_scores(self._h, _p(out), C.c_size_t(out.size)), "mcl_get_refine_scores")
+        return out
+
+    def refine_bytes(self) -> int:
+        """Bytes of device memory the refinement's buffers have asked for so far (0 on an engine that never refined)."""
+        v = C.c_uint64()
+        self._chk(self.lib.mcl_get_refine_bytes(self._h, C.byref(v)), "mcl_get_refine_bytes")
         return int(v.value)
 
     def sensor_update(self, obs):
