@@ -419,6 +419,55 @@ int mcl_host_search_lattice(const mcl_search_config_t *c, const int8_t *data, ui
                             double origin_x, double origin_y, uint32_t *cells, double *xy, size_t n, int64_t *n_positions);
 int mcl_host_search_headings(const mcl_search_config_t *c, double *theta, size_t n);
 
+/* ---- global search over a scan sequence joined by odometry -------------------------------------------------
+ * One scan from inside a corridor fits many places equally well; the scan taken two metres earlier rarely fits the same places.
+ * mcl_global_search_sequence scores every lattice pose against S scans, each from where that pose implies the robot was when
+ * the scan arrived.  The lattice pose is the robot's pose at the ANCHOR; rel[s] = (dx, dy, dtheta) is the robot's pose at scan s
+ * expressed in the robot's frame at the anchor (mcl_host_relative_poses makes it from odometry).  A caller who wants "where am I
+ * now" anchors at the latest scan.  Any finite rel is accepted, zero included; no entry has to be zero.  scans is S x n_beams,
+ * scan-major; rel is S x 3, one (dx, dy, dtheta) per scan.  The lattice, the config and the hits are mcl_global_search's.
+ *   SQ1 offsets.  With theta_k of S2, ck = cos(theta_k) and sk = sin(theta_k) (the host's cos / sin, in double, once per
+ *     heading), the host forms for heading k and scan s
+ *       theta_ks = theta_k + dtheta_s                   (one rounded add)
+ *       ax_ks = ck * dx_s - sk * dy_s,  ay_ks = sk * dx_s + ck * dy_s     (two rounded multiplies, then one rounded add or subtract;
+ *                                                                        no fma: the host unit is compiled with contraction off)
+ *     and uploads the table off[(k * S + s) * 3 + {0, 1, 2}] = {ax_ks, ay_ks, theta_ks}.  The device never re-derives it: the
+ *     host's and the device's sincos need not agree in the last bit, and a displacement formed on the device could then not be
+ *     restated by a test.  mcl_host_search_sequence_offsets is the same code without a device (n == n_headings * S * 3).  A zero
+ *     rel gives ax = ay = 0 (of either sign) and theta_ks = theta_k.
+ *   SQ2 pose of scan s at lattice pose (p, k): (x_p + ax_ks, y_p + ay_ks, theta_ks), each coordinate one rounded fp64 add on
+ *     the device; the device takes sincos(theta_ks) as k_lfield takes it of a particle's heading.  theta_ks is NOT wrapped.
+ *   SQ3 beams.  S3 per scan: beam j of scan s is used iff j % beam_stride == 0 and 0 <= r_sj < max_range_m (LF3).  Every scan
+ *     gets its own list of used beams, in beam order, by the update's own rule; the lists are concatenated on the device, S + 1
+ *     offsets say where each begins.  Scans may have different numbers of used beams, zero included.
+ *   SQ4 score.  acc_s is, bit for bit, what mcl_score_poses returns for the pose of SQ2 and scan s (for beam_stride > 1: with the
+ *     readings of the other beams replaced by NaN).  score[k * n_positions + p] = ((+0.0 + acc_0) + acc_1) + ... in scan order,
+ *     in fp64: finite or -inf, never NaN, never -0.0.  A scan pose off the map scores Lf[K] per used beam, as any pose there.
+ *   SQ5 hits.  S5 unchanged, on the summed volume: the same marking, the same sort, the same total order.  A hit's pose is the
+ *     lattice pose (the anchor), its log_likelihood the summed score.
+ *   SQ6 read-only and placement.  As S7 / S8: the buffers are the search's own (mcl_get_search_bytes counts them), grown for the
+ *     S beam lists and the offset table; the volume, the sort keys and the indices do not grow with S.  One host wait, at the
+ *     end.  Likelihood-field model ON, single engine only.  mcl_get_search_scores returns the summed volume.  Every later update
+ *     is bit-identical to one of an engine that never searched.  stats = S6's four, then [4] = S.
+ *   SQ7 identity.  With S = 1 and rel = (0, 0, 0) the volume and the hits are bit for bit those of mcl_global_search with the same
+ *     scan: x_p + 0.0 (or + -0.0) is x_p, theta_k + 0.0 is theta_k (theta_k = 0 stays +0.0), and +0.0 + acc_0 is acc_0.
+ *   Refused with MCL_ERR_INVALID_ARG, the message naming the cause: n_scans outside [1, MCL_SEARCH_MAX_SCANS]; a null scans or
+ *     rel; a rel entry that is not finite; n_beams != B; and everything S8 refuses, MCL_ERR_NOT_READY where S8 says so.
+ *   Not here: refinement over a sequence (mcl_refine_poses on the anchor scan is the next step), the beam model, shards. */
+#define MCL_SEARCH_MAX_SCANS 16
+int mcl_global_search_sequence(mcl_engine_t *h, const mcl_search_config_t *c /* NULL = the defaults */, const float *scans,
+                               const double *rel, int32_t n_scans, int32_t n_beams, int32_t max_hits, mcl_search_hit_t *hits,
+                               int64_t *n_hits, uint64_t stats[5]);
+/* SQ1 on the host, without a device: out receives n == n_headings * n_scans * 3 doubles.  MCL_ERR_INVALID_ARG for a refused
+ * config, n_scans outside [1, MCL_SEARCH_MAX_SCANS], a null pointer, a rel entry that is not finite, a wrong n. */
+int mcl_host_search_sequence_offsets(const mcl_search_config_t *c, const double *rel, int32_t n_scans, double *out, size_t n);
+/* What a node has in hand: n_scans absolute odometry poses (n_scans x 3, one (x, y, theta) per scan, any common frame) to the rel
+ * of the call above, rel_s = odom_anchor^-1 o odom_s.  With (ex, ey) = (x_s - x_a, y_s - y_a), ca = cos(theta_a), sa = sin(theta_a):
+ * dx = ca * ex + sa * ey, dy = ca * ey - sa * ex, dtheta = theta_s - theta_a wrapped to (-pi, pi]; the anchor's row is exactly
+ * +0.0.  All in double on the host.  MCL_ERR_INVALID_ARG for n_scans < 1, anchor outside [0, n_scans), a null pointer, a
+ * pose that is not finite.  (n_scans is not held to MCL_SEARCH_MAX_SCANS: a node may keep more poses than it searches with.) */
+int mcl_host_relative_poses(const double *odom, int32_t n_scans, int32_t anchor, double *rel);
+
 /* ---- pose refinement: a dense local window around each seed pose, scored against one scan (correlative scan matching on the
  *      likelihood field) ---------------------------------------------------------------------------------
  * A hit of mcl_global_search sits on the search's lattice, a cluster mean or an /initialpose is only roughly right.  For each of

@@ -33,5 +33,8 @@ const char *search_invalid(const mcl_search_config_t *c);
 int64_t search_lattice(int stride, const int8_t *data, int W, int H, double res, double ox, double oy, std::vector<uint32_t> *cells,
                        std::vector<double> *xy, std::vector<int32_t> *lat, std::vector<int32_t> *pmap, int &nx, int &ny);
 void search_headings(int n_headings, double *theta);
+// SQ1: the table of a sequence search, off[(k * S + s) * 3 + {0, 1, 2}] = {ax_ks, ay_ks, theta_ks}; null when rel is fine, else why not
+const char *search_sequence_invalid(const double *rel, int n_scans);
+void search_sequence_offsets(int n_headings, const double *theta, const double *rel, int n_scans, double *out);
 const char *refine_invalid(const mcl_refine_config_t *c);
 }  // namespace mcl_host

@@ -458,6 +458,31 @@ void search_headings(int n_headings, double *theta)
     for (int64_t k = 0; k < n_headings; ++k) theta[k] = (double)(2 * k - (int64_t)n_headings) * step;
 }
 
+// ---- the search over a scan sequence (mcl_global_search_sequence): what it refuses of rel, and SQ1
+const char *search_sequence_invalid(const double *rel, int n_scans)
+{
+    static_assert(MCL_SEARCH_MAX_SCANS == 16, "the message below names the limit");
+    if (n_scans < 1 || n_scans > MCL_SEARCH_MAX_SCANS) return "global search: n_scans must be in [1, 16] (MCL_SEARCH_MAX_SCANS)";
+    if (!rel) return "global search: rel is null";
+    for (int i = 0; i < 3 * n_scans; ++i)
+        if (!std::isfinite(rel[i])) return "global search: rel has an entry that is not finite";
+    return nullptr;
+}
+
+void search_sequence_offsets(int n_headings, const double *theta, const double *rel, int n_scans, double *out)
+{
+    for (int k = 0; k < n_headings; ++k) {
+        const double ck = std::cos(theta[k]), sk = std::sin(theta[k]);
+        for (int s = 0; s < n_scans; ++s) {
+            const double dx = rel[3 * s], dy = rel[3 * s + 1];
+            double *o = out + ((size_t)k * (size_t)n_scans + (size_t)s) * 3;
+            o[0] = ck * dx - sk * dy;                  // each product rounded, then the difference (contraction is off)
+            o[1] = sk * dx + ck * dy;
+            o[2] = theta[k] + rel[3 * s + 2];
+        }
+    }
+}
+
 // ---- the pose refinement (mcl_refine_poses): its config check (R7)
 const char *refine_invalid(const mcl_refine_config_t *c)
 {
@@ -766,6 +791,37 @@ int mcl_host_search_headings(const mcl_search_config_t *c, double *theta, size_t
 {
     if (!c || search_invalid(c) || !theta || n != (size_t)c->n_headings) return MCL_ERR_INVALID_ARG;
     search_headings(c->n_headings, theta);
+    return MCL_OK;
+}
+
+int mcl_host_search_sequence_offsets(const mcl_search_config_t *c, const double *rel, int32_t n_scans, double *out, size_t n)
+{
+    if (!c || search_invalid(c) || search_sequence_invalid(rel, n_scans) || !out || n != (size_t)c->n_headings * (size_t)n_scans * 3)
+        return MCL_ERR_INVALID_ARG;
+    std::vector<double> theta((size_t)c->n_headings);
+    search_headings(c->n_headings, theta.data());
+    search_sequence_offsets(c->n_headings, theta.data(), rel, n_scans, out);
+    return MCL_OK;
+}
+
+int mcl_host_relative_poses(const double *odom, int32_t n_scans, int32_t anchor, double *rel)
+{
+    if (!odom || !rel || n_scans < 1 || anchor < 0 || anchor >= n_scans) return MCL_ERR_INVALID_ARG;
+    for (int64_t i = 0; i < 3 * (int64_t)n_scans; ++i)
+        if (!std::isfinite(odom[i])) return MCL_ERR_INVALID_ARG;
+    const double PI = 3.14159265358979323846;
+    const double xa = odom[3 * (size_t)anchor], ya = odom[3 * (size_t)anchor + 1], ta = odom[3 * (size_t)anchor + 2];
+    const double ca = std::cos(ta), sa = std::sin(ta);
+    for (int32_t s = 0; s < n_scans; ++s) {
+        double *r = rel + 3 * (size_t)s;
+        if (s == anchor) { r[0] = r[1] = r[2] = 0.0; continue; }
+        const double ex = odom[3 * (size_t)s] - xa, ey = odom[3 * (size_t)s + 1] - ya;
+        r[0] = ca * ex + sa * ey;
+        r[1] = ca * ey - sa * ex;
+        double d = std::remainder(odom[3 * (size_t)s + 2] - ta, 2.0 * PI);      // [-pi, pi]
+        if (d <= -PI) d += 2.0 * PI;                                              // (-pi, pi]
+        r[2] = d;
+    }
     return MCL_OK;
 }
 

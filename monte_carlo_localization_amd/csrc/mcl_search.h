@@ -1,5 +1,5 @@
-// mcl_search.h -- the global search (mcl_global_search): the likelihood-field score of every pose of a regular
-// lattice over the map's free cells, and which of them are hits.  The arguments of its kernels and the kernels themselves; only
+// mcl_search.h -- the global search (mcl_global_search; over a scan sequence: §4.15): the likelihood-field score of
+// every pose of a regular lattice over the map's free cells, and which of them are hits.  The arguments of its kernels and the kernels themselves; only
 // mcl_search.hip includes it.  A score comes from the per-beam arithmetic of k_lfield (mcl_lfield_core.h), so a lattice pose and
 // a particle (or a queried pose) at the same place agree bit for bit.
 #pragma once
@@ -71,6 +71,54 @@ __global__ __launch_bounds__(kThreads) void k_search_score(Args a)
     for (int j = 0; j < a.nb; ++j)
         acc += (double)mcl::lf_beam_value(a.beams[j], s, c, px, py, W, H, a.W, a.D, lf, off);
     a.score[(size_t)k * (size_t)a.n_pos + p] = acc;
+}
+
+// The search over a scan sequence (mcl_global_search_sequence): Args as above -- beams holds the S used-beam lists
+// one after the other, nb their total -- and what joins the scans.
+struct SeqArgs {
+    Args a;
+    const double *off;              // n_head x S triples (ax_ks, ay_ks, theta_ks), formed on the host (SQ1)
+    const int32_t *beam_begin;      // S + 1: scan s owns beams[beam_begin[s] .. beam_begin[s + 1])
+    int S;
+};
+
+// k_search_score's decomposition: one lane per lattice pose, a workgroup = 256 consecutive positions at ONE heading.  For one
+// (heading, scan) the triple of SQ1, the sine and cosine of theta_ks, the bounds of the beam list and every beam's pair are uniform
+// over the workgroup (scalar loads, addressed from blockIdx and the loop counters alone), and for one beam neighbouring lanes still
+// read neighbouring cells of the field: the displacement is the same for all of them.  The scans outside, the beams inside; one
+// accumulator per scan -- the in-order sum of LF5, what k_lfield gives for the pose of SQ2 -- folded into the total in scan order
+// (SQ4).  Lf is staged once per workgroup, not once per scan.
+template <bool LDS_TABLE>
+__global__ __launch_bounds__(kThreads) void k_search_score_seq(SeqArgs q)
+{
+    extern __shared__ float s_lf[];
+    const Args &a = q.a;
+    const float *lf = a.lf;
+    if constexpr (LDS_TABLE) {
+        for (int k = threadIdx.x; k <= a.K; k += kThreads) s_lf[k] = a.lf[k];
+        __syncthreads();
+        lf = s_lf;
+    }
+    const uint32_t k = blockIdx.x / a.blocks_per_heading;
+    const uint32_t p = (blockIdx.x - k * a.blocks_per_heading) * (uint32_t)kThreads + threadIdx.x;
+    if (p >= (uint32_t)a.n_pos) return;
+    const double2 xy = a.xy[p];
+    const double W = (double)a.W, H = (double)a.H;
+    const float off = lf[a.K];
+    const double *o = q.off + (size_t)k * (size_t)q.S * 3;
+    double total = 0.0;
+    for (int sc = 0; sc < q.S; ++sc, o += 3) {
+        double s, c;
+        sincos(o[2], &s, &c);
+        const double px = mcl::lf_cell_coord(xy.x + o[0], a.ox, a.inv_res), py = mcl::lf_cell_coord(xy.y + o[1], a.oy, a.inv_res);
+        const int j1 = q.beam_begin[sc + 1];
+        double acc = 0.0;
+#pragma unroll 4
+        for (int j = q.beam_begin[sc]; j < j1; ++j)
+            acc += (double)mcl::lf_beam_value(a.beams[j], s, c, px, py, W, H, a.W, a.D, lf, off);
+        total += acc;
+    }
+    a.score[(size_t)k * (size_t)a.n_pos + p] = total;
 }
 
 // One lane per pose i = k * n_pos + p: is it a candidate (S5)?  With nms, a pose must be better -- a higher score, or the same

@@ -9,6 +9,8 @@
 //   k_search_mark    one lane per pose: candidate or not (S5), every pose's sort key and index, the candidate count
 //   radix sort       (key, index) pairs, ascending and stable: the candidates first, best first, ties by index
 //   (copy)           the count and the first max_hits pairs; one host wait
+// mcl_global_search_sequence (§4.15) is the same call with S scans: the S used-beam lists one after the other, the table of SQ1
+// from the host, k_search_score_seq in k_search_score's place, and everything after it unchanged.
 #include "mcl_search.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -40,6 +42,10 @@ struct mcl_search {
     int64_t cap_b = 0;
     double2 *d_beams = nullptr, *h_beams = nullptr;
     float *h_obs = nullptr;
+    // the scan sequence: the table of SQ1 and where each scan's beams begin (pinned staging beside each)
+    int64_t cap_off = 0;
+    double *d_off = nullptr, *h_off = nullptr;
+    int32_t *d_begin = nullptr, *h_begin = nullptr;
     // the volume and the hits
     int64_t cap_poses = 0;
     double *d_score = nullptr;
@@ -178,26 +184,12 @@ double key_score(uint64_t key)
     return v;
 }
 
-}  // namespace
-
-void search_free(struct mcl_search *s)
+// What both searches do before they score: the arguments and the readiness (S8), the lattice and the headings on the device, room
+// for the volume and for n_scans scans.  c receives the config in force, n_poses the size of the volume.
+int search_prepare(mcl_engine *h, const mcl_search_config_t *cfg, const void *obs, int n_scans, int32_t n_beams, int32_t max_hits,
+                   const mcl_search_hit_t *hits, const int64_t *n_hits, mcl_search_config_t &c, int64_t &n_poses)
 {
-    if (!s) return;
-    dfree(s->d_xy); dfree(s->d_lat); dfree(s->d_pmap); dfree(s->d_theta); dfree(s->d_beams); dfree(s->d_score); dfree(s->d_key); dfree(s->d_key2);
-    dfree(s->d_val); dfree(s->d_val2); dfree(s->d_tmp); dfree(s->d_count);
-    hfree(s->h_beams); hfree(s->h_obs); hfree(s->h_count); hfree(s->h_key); hfree(s->h_val);
-    delete s;
-}
-
-extern "C" {
-
-int mcl_global_search(mcl_engine_t *h, const mcl_search_config_t *cfg, const float *obs, int32_t n_beams, int32_t max_hits,
-                      mcl_search_hit_t *hits, int64_t *n_hits, uint64_t stats[4])
-{
-    if (!h) return MCL_ERR_INVALID_ARG;
-    mcl_search_config_t c;
     if (cfg) c = *cfg; else mcl_default_search_config(&c);
-    // arguments, then readiness (S8)
     if (const char *why = mcl_host::search_invalid(&c)) return fail(h, MCL_ERR_INVALID_ARG, why);
     if (!obs || !n_hits) return fail(h, MCL_ERR_INVALID_ARG, "global search: obs / n_hits is null");
     if (max_hits < 0 || max_hits > kMaxHits) return fail(h, MCL_ERR_INVALID_ARG, "global search: max_hits must be in [0, 65536]");
@@ -212,38 +204,42 @@ int mcl_global_search(mcl_engine_t *h, const mcl_search_config_t *cfg, const flo
     mcl_search *s = h->srch;
     SRCH_TRY(search_lattice_upload(h, s, c.stride_cells));
     if (s->n_pos == 0) return fail(h, MCL_ERR_NOT_READY, "global search: the lattice has no free position on this map");
-    const int64_t n_poses = s->n_pos * (int64_t)c.n_headings;
+    n_poses = s->n_pos * (int64_t)c.n_headings;
     if (n_poses >= MCL_MAX_TOTAL_PARTICLES)
         return fail(h, MCL_ERR_INVALID_ARG, "global search: n_positions * n_headings must stay below 2^27 (a larger stride_cells or fewer headings)");
     SRCH_TRY(search_headings_upload(h, s, c.n_headings));
-    const int B = h->B;
-    SRCH_TRY(search_alloc(h, s, n_poses, B));
+    SRCH_TRY(search_alloc(h, s, n_poses, n_scans * h->B));
     s->volume_n = 0;                                             // until this volume is whole
+    return MCL_OK;
+}
 
-    // S3: the readings of the candidate beams, the others NaN (no contribution), through the update's own rule
-    for (int j = 0; j < B; ++j) s->h_obs[j] = (j % c.beam_stride == 0) ? obs[j] : NAN;
-    const int nb = mcl_host::lf_used_beams(h, s->h_obs, 1, s->h_beams);
-    if (nb > 0) HIPCHK(h, hipMemcpyAsync(s->d_beams, s->h_beams, (size_t)nb * sizeof(double2), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemsetAsync(s->d_count, 0, sizeof(unsigned long long), h->stream));
+// S3: the used beams of one scan at `out`, through the update's own rule -- the readings of the candidate beams, the others NaN
+// (no contribution).  Returns their number.
+int search_used_beams(mcl_engine *h, mcl_search *s, int beam_stride, const float *obs, double2 *out)
+{
+    for (int j = 0; j < h->B; ++j) s->h_obs[j] = (j % beam_stride == 0) ? obs[j] : NAN;
+    return mcl_host::lf_used_beams(h, s->h_obs, 1, out);
+}
 
+// everything of the kernels' arguments but the beams
+Args search_args(const mcl_engine *h, const mcl_search *s, const mcl_search_config_t &c)
+{
     Args a{};
     a.xy = s->d_xy; a.lat = s->d_lat; a.pmap = s->d_pmap; a.theta = s->d_theta;
     a.n_pos = (int32_t)s->n_pos; a.n_head = c.n_headings; a.nx = s->nx; a.ny = s->ny;
     a.blocks_per_heading = (uint32_t)((s->n_pos + kThreads - 1) / kThreads);
-    a.beams = s->d_beams; a.nb = nb;
     a.D = h->d_lf_D; a.W = h->W; a.H = h->H;
     a.ox = h->ox; a.oy = h->oy; a.inv_res = 1.0 / h->res;
     a.lf = h->d_lf_tab; a.K = h->lf_K;
     a.score = s->d_score;
     a.nms = c.nms;
     a.key = s->d_key; a.val = s->d_val; a.count = s->d_count;
-    // (n_poses < 2^27, so both grids stay far below 2^31 workgroups)
-    const dim3 grid_score((unsigned)((uint64_t)a.blocks_per_heading * (uint64_t)c.n_headings));
-    if (h->lf_K < mcl::kLfLdsEntries)
-        hipLaunchKernelGGL(k_search_score<true>, grid_score, dim3(kThreads), (size_t)(h->lf_K + 1) * sizeof(float), h->stream, a);
-    else
-        hipLaunchKernelGGL(k_search_score<false>, grid_score, dim3(kThreads), 0, h->stream, a);
-    HIPCHK(h, hipGetLastError());
+    return a;
+}
+
+// What both searches do with the volume in d_score (S5): the marking, the sort, the copies, the one host wait, the hits.
+int search_finish(mcl_engine *h, mcl_search *s, const Args &a, int64_t n_poses, int32_t max_hits, mcl_search_hit_t *hits, int64_t *n_hits)
+{
     hipLaunchKernelGGL(k_search_mark, dim3((unsigned)((n_poses + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream, a);
     HIPCHK(h, hipGetLastError());
     const int64_t top = std::min<int64_t>(max_hits, n_poses);
@@ -270,8 +266,101 @@ int mcl_global_search(mcl_engine_t *h, const mcl_search_config_t *cfg, const flo
         hits[r].log_likelihood = key_score(s->h_key[r]);
         hits[r].index = idx;
     }
+    return MCL_OK;
+}
+
+}  // namespace
+
+void search_free(struct mcl_search *s)
+{
+    if (!s) return;
+    dfree(s->d_xy); dfree(s->d_lat); dfree(s->d_pmap); dfree(s->d_theta); dfree(s->d_beams); dfree(s->d_score); dfree(s->d_key); dfree(s->d_key2);
+    dfree(s->d_val); dfree(s->d_val2); dfree(s->d_tmp); dfree(s->d_count); dfree(s->d_off); dfree(s->d_begin);
+    hfree(s->h_beams); hfree(s->h_obs); hfree(s->h_count); hfree(s->h_key); hfree(s->h_val); hfree(s->h_off); hfree(s->h_begin);
+    delete s;
+}
+
+extern "C" {
+
+int mcl_global_search(mcl_engine_t *h, const mcl_search_config_t *cfg, const float *obs, int32_t n_beams, int32_t max_hits,
+                      mcl_search_hit_t *hits, int64_t *n_hits, uint64_t stats[4])
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    mcl_search_config_t c;
+    int64_t n_poses = 0;
+    SRCH_TRY(search_prepare(h, cfg, obs, 1, n_beams, max_hits, hits, n_hits, c, n_poses));
+    mcl_search *s = h->srch;
+    const int nb = search_used_beams(h, s, c.beam_stride, obs, s->h_beams);
+    if (nb > 0) HIPCHK(h, hipMemcpyAsync(s->d_beams, s->h_beams, (size_t)nb * sizeof(double2), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(s->d_count, 0, sizeof(unsigned long long), h->stream));
+
+    Args a = search_args(h, s, c);
+    a.beams = s->d_beams; a.nb = nb;
+    // (n_poses < 2^27, so both grids stay far below 2^31 workgroups)
+    const dim3 grid_score((unsigned)((uint64_t)a.blocks_per_heading * (uint64_t)c.n_headings));
+    if (h->lf_K < mcl::kLfLdsEntries)
+        hipLaunchKernelGGL(k_search_score<true>, grid_score, dim3(kThreads), (size_t)(h->lf_K + 1) * sizeof(float), h->stream, a);
+    else
+        hipLaunchKernelGGL(k_search_score<false>, grid_score, dim3(kThreads), 0, h->stream, a);
+    HIPCHK(h, hipGetLastError());
+    SRCH_TRY(search_finish(h, s, a, n_poses, max_hits, hits, n_hits));
     if (stats) {
         stats[0] = (uint64_t)s->n_pos; stats[1] = (uint64_t)n_poses; stats[2] = (uint64_t)nb; stats[3] = (uint64_t)s->device_bytes;
+    }
+    return MCL_OK;
+}
+
+int mcl_global_search_sequence(mcl_engine_t *h, const mcl_search_config_t *cfg, const float *scans, const double *rel, int32_t n_scans,
+                               int32_t n_beams, int32_t max_hits, mcl_search_hit_t *hits, int64_t *n_hits, uint64_t stats[5])
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    // the sequence's own arguments, then everything the single search checks
+    if (const char *why = mcl_host::search_sequence_invalid(rel, n_scans)) return fail(h, MCL_ERR_INVALID_ARG, why);
+    if (!scans) return fail(h, MCL_ERR_INVALID_ARG, "global search: scans is null");
+    mcl_search_config_t c;
+    int64_t n_poses = 0;
+    SRCH_TRY(search_prepare(h, cfg, scans, n_scans, n_beams, max_hits, hits, n_hits, c, n_poses));
+    mcl_search *s = h->srch;
+    const int B = h->B, S = n_scans;
+    const int64_t n_off = (int64_t)c.n_headings * S * 3;
+    if (!s->d_begin) {
+        SRCH_TRY(grow_dev(h, s, s->d_begin, (size_t)MCL_SEARCH_MAX_SCANS + 1));
+        SRCH_TRY(grow_host(h, s->h_begin, (size_t)MCL_SEARCH_MAX_SCANS + 1));
+    }
+    if (n_off > s->cap_off) {
+        s->cap_off = 0;
+        SRCH_TRY(grow_dev(h, s, s->d_off, (size_t)n_off));
+        SRCH_TRY(grow_host(h, s->h_off, (size_t)n_off));
+        s->cap_off = n_off;
+    }
+
+    // SQ3: every scan's used beams, one list after the other; SQ1: the table
+    int nb = 0;
+    for (int sc = 0; sc < S; ++sc) {
+        s->h_begin[sc] = nb;
+        nb += search_used_beams(h, s, c.beam_stride, scans + (size_t)sc * (size_t)B, s->h_beams + nb);
+    }
+    s->h_begin[S] = nb;
+    mcl_host::search_sequence_offsets(c.n_headings, s->theta.data(), rel, S, s->h_off);
+    if (nb > 0) HIPCHK(h, hipMemcpyAsync(s->d_beams, s->h_beams, (size_t)nb * sizeof(double2), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(s->d_begin, s->h_begin, (size_t)(S + 1) * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(s->d_off, s->h_off, (size_t)n_off * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(s->d_count, 0, sizeof(unsigned long long), h->stream));
+
+    SeqArgs q{};
+    q.a = search_args(h, s, c);
+    q.a.beams = s->d_beams; q.a.nb = nb;
+    q.off = s->d_off; q.beam_begin = s->d_begin; q.S = S;
+    const dim3 grid_score((unsigned)((uint64_t)q.a.blocks_per_heading * (uint64_t)c.n_headings));
+    if (h->lf_K < mcl::kLfLdsEntries)
+        hipLaunchKernelGGL(k_search_score_seq<true>, grid_score, dim3(kThreads), (size_t)(h->lf_K + 1) * sizeof(float), h->stream, q);
+    else
+        hipLaunchKernelGGL(k_search_score_seq<false>, grid_score, dim3(kThreads), 0, h->stream, q);
+    HIPCHK(h, hipGetLastError());
+    SRCH_TRY(search_finish(h, s, q.a, n_poses, max_hits, hits, n_hits));
+    if (stats) {
+        stats[0] = (uint64_t)s->n_pos; stats[1] = (uint64_t)n_poses; stats[2] = (uint64_t)nb; stats[3] = (uint64_t)s->device_bytes;
+        stats[4] = (uint64_t)S;
     }
     return MCL_OK;
 }

@@ -49,6 +49,7 @@ EXPORTS = [
     "mcl_query_scans", "mcl_score_poses", "mcl_get_query_counters",
     "mcl_default_search_config", "mcl_global_search", "mcl_get_search_scores", "mcl_get_search_bytes", "mcl_host_search_lattice",
     "mcl_host_search_headings", "mcl_init_particles_mixture",
+    "mcl_global_search_sequence", "mcl_host_search_sequence_offsets", "mcl_host_relative_poses",
     "mcl_default_refine_config", "mcl_refine_poses", "mcl_get_refine_scores", "mcl_get_refine_bytes", "mcl_host_refine_window",
     "mcl_host_refine_reduce",
     "mcl_default_recovery_config", "mcl_set_recovery", "mcl_get_recovery_state", "mcl_set_recovery_state", "mcl_host_recovery_step",
@@ -142,6 +143,7 @@ class SearchConfig(C.Structure):
 SEARCH_HIT_DTYPE = np.dtype([("pose", np.float64, (3,)), ("log_likelihood", np.float64), ("index", np.int64)])
 assert SEARCH_HIT_DTYPE.itemsize == 40
 MAX_SEARCH_HITS = 65536
+MAX_SEARCH_SCANS = 16            # MCL_SEARCH_MAX_SCANS
 
 
 class RefineConfig(C.Structure):
@@ -241,6 +243,10 @@ def load_library(legacy=False):
         lib.mcl_host_search_lattice.argtypes = [C.POINTER(SearchConfig), C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_double,
                                                 C.c_double, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int64)]
         lib.mcl_host_search_headings.argtypes = [C.POINTER(SearchConfig), C.c_void_p, C.c_size_t]
+        lib.mcl_global_search_sequence.argtypes = [C.c_void_p, C.POINTER(SearchConfig), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                                   C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]
+        lib.mcl_host_search_sequence_offsets.argtypes = [C.POINTER(SearchConfig), C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t]
+        lib.mcl_host_relative_poses.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
         lib.mcl_default_refine_config.argtypes = [C.POINTER(RefineConfig)]
         lib.mcl_default_refine_config.restype = None
         lib.mcl_refine_poses.argtypes = [C.c_void_p, C.POINTER(RefineConfig), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
@@ -444,6 +450,43 @@ def host_search_headings(**fields) -> np.ndarray:
     rc = load_library().mcl_host_search_headings(C.byref(c), _p(out), out.size)
     if rc != MCL_OK:
         raise EngineError(f"mcl_host_search_headings rc={rc}", rc)
+    return out
+
+
+def _rel_rows(rel) -> np.ndarray:
+    """(S, 3) rows of (dx, dy, dtheta), or one such row, C-contiguous float64"""
+    r = np.asarray(rel, np.float64)
+    if r.ndim == 1:
+        r = r.reshape(1, -1)
+    if r.ndim != 2 or r.shape[1] != 3:
+        raise ValueError("expected (S, 3) rows of three values, or one row")
+    return _c(r, np.float64)
+
+
+def host_search_sequence_offsets(rel, **fields) -> np.ndarray:
+    """The table a search over a scan sequence uploads (mcl_host_search_sequence_offsets, rule SQ1; no device needed): shape
+    (n_headings, S, 3), [k, s] = (ax_ks, ay_ks, theta_ks) -- scan s's displacement from the anchor in the map frame at heading k,
+    and its heading.  `rel`: (S, 3) rows of (dx, dy, dtheta) in the anchor's frame."""
+    c = default_search_config(**fields)
+    r = _rel_rows(rel)
+    S = r.shape[0]
+    out = np.empty((max(int(c.n_headings), 0), S, 3), np.float64)
+    rc = load_library().mcl_host_search_sequence_offsets(C.byref(c), _p(r) if S else None, C.c_int32(S), _p(out), C.c_size_t(out.size))
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_search_sequence_offsets rc={rc}", rc)
+    return out
+
+
+def relative_poses(odom, anchor=-1) -> np.ndarray:
+    """Absolute odometry poses, (S, 3) rows of (x, y, theta), as poses relative to the one at `anchor` (mcl_host_relative_poses):
+    the `rel` of Engine.global_search_sequence.  anchor = -1, the default: the latest pose."""
+    o = _rel_rows(odom)
+    S = o.shape[0]
+    a = int(anchor) + S if int(anchor) < 0 else int(anchor)
+    out = np.empty((S, 3), np.float64)
+    rc = load_library().mcl_host_relative_poses(_p(o) if S else None, C.c_int32(S), C.c_int32(a), _p(out))
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_relative_poses rc={rc}", rc)
     return out
 
 
@@ -914,8 +957,34 @@ class Engine:
         return hits[:min(n.value, hits.size)], dict(n_hits=n.value, n_positions=int(st[0]), n_poses=int(st[1]), used_beams=int(st[2]),
                                                     device_bytes=int(st[3]))
 
+    def global_search_sequence(self, scans, rel, max_hits=16, **fields):
+        """global_search over a sequence of scans joined by odometry (mcl_global_search_sequence): every lattice
+        pose is the robot's pose at the anchor, and scan s is scored from where that pose puts the robot at scan s.  `scans`:
+        (S, B) ranges; `rel`: (S, 3) rows of (dx, dy, dtheta), the pose at scan s in the anchor's frame (relative_poses makes
+        them from odometry).  Returns what global_search returns, plus n_scans; used_beams counts all scans' beams.
+            rel = relative_poses(odom)
+            hits, _ = e.global_search_sequence(scans, rel)
+            r, _ = e.refine_poses(hits["pose"], scans[-1])"""
+        c = default_search_config(**fields)
+        o = _c(np.atleast_2d(np.asarray(scans, np.float32)), np.float32)
+        if o.ndim != 2:
+            raise ValueError("scans must be (S, B)")
+        r = _rel_rows(rel)
+        if r.shape[0] != o.shape[0]:
+            raise ValueError("scans and rel must have one row per scan")
+        S = o.shape[0]
+        hits = np.zeros(int(max_hits), SEARCH_HIT_DTYPE)
+        n, st = C.c_int64(), np.zeros(5, np.uint64)
+        self._chk(self.lib.mcl_global_search_sequence(self._h, C.byref(c), _p(o) if S else None, _p(r) if S else None, C.c_int32(S),
+                                                      C.c_int32(o.shape[1]), C.c_int32(int(max_hits)),
+                                                      _p(hits) if hits.size else None, C.byref(n), _p(st)),
+                  "mcl_global_search_sequence")
+        self._search_poses = int(st[1])
+        return hits[:min(n.value, hits.size)], dict(n_hits=n.value, n_positions=int(st[0]), n_poses=int(st[1]), used_beams=int(st[2]),
+                                                    device_bytes=int(st[3]), n_scans=int(st[4]))
+
     def search_scores(self, n_headings=None):
-        """The score volume of the last global_search (mcl_get_search_scores): n_headings * n_positions doubles, heading-major;
+        """The score volume of the last global_search or global_search_sequence (mcl_get_search_scores): n_headings * n_positions doubles, heading-major;
         with n_headings, reshaped to (n_headings, n_positions)."""
         out = np.empty(getattr(self, "_search_poses", 0) or 1, np.float64)
         self._chk(self.lib.mcl_get_search_scores(self._h, _p(out), C.c_size_t(out.size)), "mcl_get_search_scores")
