@@ -468,6 +468,64 @@ int mcl_host_search_sequence_offsets(const mcl_search_config_t *c, const double 
  * pose that is not finite.  (n_scans is not held to MCL_SEARCH_MAX_SCANS: a node may keep more poses than it searches with.) */
 int mcl_host_relative_poses(const double *odom, int32_t n_scans, int32_t anchor, double *rel);
 
+/* ---- global search in heading slabs: any lattice in a fixed memory budget -----------------------------------
+ * mcl_global_search and mcl_global_search_sequence hold the whole score volume and sort all of it, which caps the lattice at
+ * 2^27 poses and costs about 32 bytes per pose.  mcl_global_search_streamed reports the same hits from a walk over the volume in
+ * slabs of G headings: it keeps a ring of G + 2 score planes, compacts each slab's candidates and merges them into a running
+ * list of the best.  Rules S1-S5 and SQ1-SQ5 hold as they stand.  With n = n_headings:
+ *   ST1 identity.  The hits (pose, log_likelihood, index) and *n_hits are, bit for bit, those of mcl_global_search when
+ *     n_scans == 1 and rel is NULL or zero, and those of mcl_global_search_sequence otherwise -- for the same config and scans,
+ *     for every G and every budget, wherever the unstreamed call accepts the lattice.  The total order is S5's: the score, then
+ *     the lower index; equal scores on either side of a slab boundary come out in index order.  Nothing depends on the order in
+ *     which candidates were collected: a slab's candidates are compacted in index order (a scan over their flags) behind the
+ *     running list, whose indices are all lower, and the two are sorted stably by the score's key.
+ *   ST2 slabs and the ring.  G above n counts as n.  Slab t marks headings [tG, min((t + 1)G, n)).  Scores live in a ring of
+ *     G + 2 heading planes: with more than one slab the linear heading hh in [-1, n] sits in plane (hh + 1) mod (G + 2) and
+ *     stands for heading hh mod n, so slab t + 1 reuses the last two planes of slab t, and the wrap neighbours -- heading n - 1
+ *     of heading 0, heading 0 of heading n - 1 -- are two headings scored a second time: stats reports n + 2 headings scored.
+ *     With G >= n there is one slab, plane = heading, and n headings are scored, none twice.  n = 1 and n = 2 are exactly S5's:
+ *     with n = 1 k +- 1 is the pose itself and is excluded, with n = 2 k + 1 and k - 1 are the same neighbour.
+ *   ST3 selection.  Per slab the marking flags the candidates (S5, nms 0 or 1) and counts them on the device.  A candidate is
+ *     compacted as (key, 64-bit index) unless the running list already holds max_hits entries and the candidate is no better
+ *     than the last of them.  The compacted candidates are merged into the running list of the min(max_hits, found) best on the
+ *     device: one stable segmented radix sort (rocPRIM) over the list and the slab's compacted candidates, whose length the
+ *     device alone knows.  No whole-volume sort, no host wait and no read-back between slabs; one host wait, at the end of the
+ *     call (S7).  With max_hits = 0 nothing is compacted or sorted.
+ *   ST4 size.  (G + 2) * n_positions < 2^27 per slab; n_positions * n_headings < 2^40 per call; indices are 64-bit wherever they
+ *     leave a slab.  mcl_global_search and mcl_global_search_sequence keep their limit of 2^27 poses and its message.
+ *   ST5 budget.  mcl_host_search_slabs is the plan, on the host: G, the number of slabs ceil(n / G), and `bytes`, the sum of
+ *     every buffer whose size depends on G.  With P = n_positions and L = 65536 + G P:
+ *       bytes = 8 (G + 2) P  (the ring)  +  4 G P + 4 G P + 8 G P  (the slab's flags, their scan, the slab's keys)
+ *             + 2 * 16 L  (the running list of 65536 and the slab's candidates behind it, twice: the sort goes from one to the other)
+ *             + 262144 + floor(G P / 16)  (scratch of the scan and the sort).
+ *     mcl_global_search_streamed allocates exactly those, plus what the lattice, the headings and the scans take anyway.
+ *     slab_headings = 0: the largest G <= n with bytes <= budget_bytes (0: 1 GiB) that keeps ST4.  When G = 1 does not fit, or
+ *     an explicit G does not, the call is refused with MCL_ERR_INVALID_ARG and the message names the bytes needed; nothing is
+ *     allocated and no earlier result is disturbed.  Buffers a larger earlier plan left are reused, not shrunk.
+ *   ST6 state.  The buffers are the search's own (mcl_get_search_bytes counts them); nothing of the update is touched: every
+ *     later update is bit-identical to one of an engine that never searched.  No volume is kept: after a streamed search
+ *     mcl_get_search_scores returns MCL_ERR_NOT_READY until an unstreamed search has run.
+ *   Readiness and refusals as S8 and SQ (likelihood-field model ON, single engine only; rel may be NULL only with n_scans == 1),
+ *     and MCL_ERR_INVALID_ARG for reserved != 0, slab_headings < 0, a G that breaks ST4, n_positions * n_headings >= 2^40.
+ *   stats = {n_positions, poses, used beams, bytes of device memory the search's buffers have asked for so far, G, slabs,
+ *     headings scored, candidates compacted}; stats may be NULL.
+ *   Not here: pruning poses by bounds on partial sums, the beam model, shards.  With nms = 0 and a list that is not yet full,
+ *     every pose of a slab is compacted and one workgroup sorts them: correct, and slow on a large slab. */
+typedef struct {
+    uint64_t budget_bytes;                  /* device bytes the slab buffers may take; 0 = the default, 1 GiB                 */
+    int32_t  slab_headings;                 /* G: headings marked per slab; 0 = the largest G that fits the budget            */
+    int32_t  reserved[5];                   /* must be 0                                                                      */
+} mcl_search_stream_config_t;
+void mcl_default_search_stream_config(mcl_search_stream_config_t *c);
+int mcl_global_search_streamed(mcl_engine_t *h, const mcl_search_config_t *c /* NULL = the defaults */,
+                               const mcl_search_stream_config_t *sc /* NULL = the defaults */, const float *scans,
+                               const double *rel /* NULL with n_scans == 1: (0, 0, 0) */, int32_t n_scans, int32_t n_beams,
+                               int32_t max_hits, mcl_search_hit_t *hits, int64_t *n_hits, uint64_t stats[8]);
+/* ST5's plan on the host, without a device; any of the three outputs may be NULL.  MCL_ERR_INVALID_ARG for a refused config
+ * (either), n_scans outside [1, MCL_SEARCH_MAX_SCANS], n_positions < 1, and what ST4 / ST5 refuse. */
+int mcl_host_search_slabs(const mcl_search_config_t *c, const mcl_search_stream_config_t *sc, int64_t n_positions, int32_t n_scans,
+                          int32_t *slab_headings, int32_t *n_slabs, uint64_t *bytes);
+
 /* ---- pose refinement: a dense local window around each seed pose, scored against one scan (correlative scan matching on the
  *      likelihood field) ---------------------------------------------------------------------------------
  * A hit of mcl_global_search sits on the search's lattice, a cluster mean or an /initialpose is only roughly right.  For each of

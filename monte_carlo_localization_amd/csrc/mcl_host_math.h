@@ -3,6 +3,7 @@
 #pragma once
 #include "../../include/mcl_hip_engine.h"
 #include <cstdint>
+#include <string>
 #include <vector>
 #include "mcl_types.h"
 
@@ -36,5 +37,17 @@ void search_headings(int n_headings, double *theta);
 // SQ1: the table of a sequence search, off[(k * S + s) * 3 + {0, 1, 2}] = {ax_ks, ay_ks, theta_ks}; null when rel is fine, else why not
 const char *search_sequence_invalid(const double *rel, int n_scans);
 void search_sequence_offsets(int n_headings, const double *theta, const double *rel, int n_scans, double *out);
+// The plan of a streamed search (ST2 / ST4 / ST5): the bytes of every buffer whose size depends on G, part by part, and the plan
+// itself.  search_slabs returns an empty string and fills `plan`, or says why the call is refused.
+struct SearchSlabPlan {
+    int32_t G = 0, n_slabs = 0;
+    uint64_t slab_poses = 0;            // G * n_positions
+    uint64_t ring_bytes = 0, flag_bytes = 0, pos_bytes = 0, key_bytes = 0, list_entries = 0, list_bytes = 0, scratch_bytes = 0, bytes = 0;
+};
+constexpr uint64_t kSearchStreamDefaultBudget = 1ull << 30;
+constexpr uint64_t kSearchListHits = 65536;             // the running list is sized for the largest max_hits
+SearchSlabPlan search_slab_bytes(int64_t n_positions, int32_t G);
+std::string search_slabs(const mcl_search_config_t *c, const mcl_search_stream_config_t *sc, int64_t n_positions, int32_t n_scans,
+                         SearchSlabPlan &plan);
 const char *refine_invalid(const mcl_refine_config_t *c);
 }  // namespace mcl_host

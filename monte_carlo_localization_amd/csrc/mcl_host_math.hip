@@ -483,6 +483,62 @@ void search_sequence_offsets(int n_headings, const double *theta, const double *
     }
 }
 
+// ---- the streamed search (mcl_global_search_streamed): the plan of ST2 / ST4 / ST5
+SearchSlabPlan search_slab_bytes(int64_t n_positions, int32_t G)
+{
+    SearchSlabPlan p;
+    const uint64_t np = (uint64_t)n_positions;
+    p.G = G;
+    p.slab_poses = (uint64_t)G * np;
+    p.ring_bytes = ((uint64_t)G + 2) * np * sizeof(double);             // the ring of G + 2 score planes
+    p.flag_bytes = p.slab_poses * sizeof(uint32_t);                     // the slab's flags,
+    p.pos_bytes = p.slab_poses * sizeof(uint32_t);                      // their scan,
+    p.key_bytes = p.slab_poses * sizeof(uint64_t);                      // the slab's keys
+    p.list_entries = kSearchListHits + p.slab_poses;                    // the running list, behind it the slab's candidates:
+    p.list_bytes = 2 * p.list_entries * 2 * sizeof(uint64_t);           //   (key, index), twice (the sort goes from one to the other)
+    p.scratch_bytes = (256u << 10) + (p.slab_poses >> 4);               // what the scan and the sort may ask for
+    p.bytes = p.ring_bytes + p.flag_bytes + p.pos_bytes + p.key_bytes + p.list_bytes + p.scratch_bytes;
+    return p;
+}
+
+std::string search_slabs(const mcl_search_config_t *c, const mcl_search_stream_config_t *sc, int64_t n_positions, int32_t n_scans,
+                         SearchSlabPlan &plan)
+{
+    if (const char *why = search_invalid(c)) return why;
+    for (int i = 0; i < 5; ++i)
+        if (sc->reserved[i] != 0) return "streamed search: reserved must be 0";
+    if (sc->slab_headings < 0) return "streamed search: slab_headings must be >= 0";
+    if (n_scans < 1 || n_scans > MCL_SEARCH_MAX_SCANS) return "global search: n_scans must be in [1, 16] (MCL_SEARCH_MAX_SCANS)";
+    if (n_positions < 1) return "streamed search: n_positions must be >= 1";
+    const int64_t n = c->n_headings;
+    if (n_positions >= MCL_MAX_TOTAL_PARTICLES || n_positions * n >= ((int64_t)1 << 40))
+        return "streamed search: n_positions * n_headings must stay below 2^40 (and n_positions below 2^27)";
+    const uint64_t budget = sc->budget_bytes ? sc->budget_bytes : kSearchStreamDefaultBudget;
+    const auto st4 = [&](int64_t G) { return (G + 2) * n_positions < MCL_MAX_TOTAL_PARTICLES; };
+    const auto fits = [&](int64_t G) { return st4(G) && search_slab_bytes(n_positions, (int32_t)G).bytes <= budget; };
+    int64_t G = std::min<int64_t>(sc->slab_headings, n);                // a G above n_headings is n_headings: one slab
+    if (G > 0) {
+        if (!st4(G)) return "streamed search: (slab_headings + 2) * n_positions must stay below 2^27 (fewer headings per slab)";
+    } else if (fits(1)) {
+        int64_t lo = 1, hi = n;                                         // the largest G in [1, n] that fits: both bounds are monotone
+        while (lo < hi) {
+            const int64_t mid = lo + (hi - lo + 1) / 2;
+            if (fits(mid)) lo = mid; else hi = mid - 1;
+        }
+        G = lo;
+    } else {
+        G = 1;
+        if (!st4(G)) return "streamed search: 3 * n_positions must stay below 2^27 (a larger stride_cells)";
+    }
+    const SearchSlabPlan p = search_slab_bytes(n_positions, (int32_t)G);
+    if (p.bytes > budget)
+        return "streamed search: slabs of " + std::to_string(G) + " heading" + (G > 1 ? "s" : "") + " need " + std::to_string(p.bytes) +
+               " bytes, the budget is " + std::to_string(budget) + " bytes";
+    plan = p;
+    plan.n_slabs = (int32_t)((n + G - 1) / G);
+    return std::string();
+}
+
 // ---- the pose refinement (mcl_refine_poses): its config check (R7)
 const char *refine_invalid(const mcl_refine_config_t *c)
 {
@@ -801,6 +857,26 @@ int mcl_host_search_sequence_offsets(const mcl_search_config_t *c, const double 
     std::vector<double> theta((size_t)c->n_headings);
     search_headings(c->n_headings, theta.data());
     search_sequence_offsets(c->n_headings, theta.data(), rel, n_scans, out);
+    return MCL_OK;
+}
+
+void mcl_default_search_stream_config(mcl_search_stream_config_t *c)
+{
+    if (!c) return;
+    *c = mcl_search_stream_config_t{};
+}
+
+int mcl_host_search_slabs(const mcl_search_config_t *c, const mcl_search_stream_config_t *sc, int64_t n_positions, int32_t n_scans,
+                          int32_t *slab_headings, int32_t *n_slabs, uint64_t *bytes)
+{
+    if (!c) return MCL_ERR_INVALID_ARG;
+    mcl_search_stream_config_t d;
+    mcl_default_search_stream_config(&d);
+    SearchSlabPlan plan;
+    if (!search_slabs(c, sc ? sc : &d, n_positions, n_scans, plan).empty()) return MCL_ERR_INVALID_ARG;
+    if (slab_headings) *slab_headings = plan.G;
+    if (n_slabs) *n_slabs = plan.n_slabs;
+    if (bytes) *bytes = plan.bytes;
     return MCL_OK;
 }
 

@@ -50,6 +50,7 @@ EXPORTS = [
     "mcl_default_search_config", "mcl_global_search", "mcl_get_search_scores", "mcl_get_search_bytes", "mcl_host_search_lattice",
     "mcl_host_search_headings", "mcl_init_particles_mixture",
     "mcl_global_search_sequence", "mcl_host_search_sequence_offsets", "mcl_host_relative_poses",
+    "mcl_default_search_stream_config", "mcl_global_search_streamed", "mcl_host_search_slabs",
     "mcl_default_refine_config", "mcl_refine_poses", "mcl_get_refine_scores", "mcl_get_refine_bytes", "mcl_host_refine_window",
     "mcl_host_refine_reduce",
     "mcl_default_recovery_config", "mcl_set_recovery", "mcl_get_recovery_state", "mcl_set_recovery_state", "mcl_host_recovery_step",
@@ -137,6 +138,11 @@ class SearchConfig(C.Structure):
     """mcl_search_config_t: the lattice of the global search (Engine.global_search)."""
     _fields_ = [("stride_cells", C.c_int32), ("n_headings", C.c_int32), ("beam_stride", C.c_int32), ("nms", C.c_int32),
                 ("reserved", C.c_int32 * 4)]
+
+
+class SearchStreamConfig(C.Structure):
+    """mcl_search_stream_config_t: the memory budget and the slab of a streamed search (Engine.global_search_streamed)."""
+    _fields_ = [("budget_bytes", C.c_uint64), ("slab_headings", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
 # the numpy view of an array of mcl_search_hit_t (Engine.global_search)
@@ -247,6 +253,12 @@ def load_library(legacy=False):
                                                    C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]
         lib.mcl_host_search_sequence_offsets.argtypes = [C.POINTER(SearchConfig), C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t]
         lib.mcl_host_relative_poses.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        lib.mcl_default_search_stream_config.argtypes = [C.POINTER(SearchStreamConfig)]
+        lib.mcl_default_search_stream_config.restype = None
+        lib.mcl_global_search_streamed.argtypes = [C.c_void_p, C.POINTER(SearchConfig), C.POINTER(SearchStreamConfig), C.c_void_p, C.c_void_p,
+                                                   C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]
+        lib.mcl_host_search_slabs.argtypes = [C.POINTER(SearchConfig), C.POINTER(SearchStreamConfig), C.c_int64, C.c_int32,
+                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
         lib.mcl_default_refine_config.argtypes = [C.POINTER(RefineConfig)]
         lib.mcl_default_refine_config.restype = None
         lib.mcl_refine_poses.argtypes = [C.c_void_p, C.POINTER(RefineConfig), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
@@ -422,6 +434,27 @@ def default_search_config(**over) -> SearchConfig:
             raise AttributeError(name)
         setattr(c, name, (C.c_int32 * 4)(*v) if name == "reserved" else v)
     return c
+
+
+def search_stream_config(budget_bytes=0, slab_headings=0, reserved=(0, 0, 0, 0, 0)) -> SearchStreamConfig:
+    """mcl_search_stream_config_t: 0 bytes is the default budget (1 GiB), 0 headings the largest slab that fits it."""
+    c = SearchStreamConfig()
+    load_library().mcl_default_search_stream_config(C.byref(c))
+    c.budget_bytes, c.slab_headings, c.reserved = int(budget_bytes), int(slab_headings), (C.c_int32 * 5)(*reserved)
+    return c
+
+
+def host_search_slabs(n_positions, n_scans=1, budget_bytes=0, slab_headings=0, stream_reserved=(0, 0, 0, 0, 0), **fields):
+    """The plan of a streamed search (mcl_host_search_slabs, rules ST4 / ST5; no device needed): (G, n_slabs, bytes) -- the headings
+    per slab, the number of slabs, the device bytes of the slab buffers.  `fields` override mcl_default_search_config."""
+    c = default_search_config(**fields)
+    sc = search_stream_config(budget_bytes, slab_headings, stream_reserved)
+    G, ns, b = C.c_int32(), C.c_int32(), C.c_uint64()
+    rc = load_library().mcl_host_search_slabs(C.byref(c), C.byref(sc), C.c_int64(int(n_positions)), C.c_int32(int(n_scans)), C.byref(G),
+                                              C.byref(ns), C.byref(b))
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_search_slabs rc={rc}", rc)
+    return int(G.value), int(ns.value), int(b.value)
 
 
 def host_search_lattice(grid, resolution, origin_x, origin_y, **fields):
@@ -982,6 +1015,35 @@ class Engine:
         self._search_poses = int(st[1])
         return hits[:min(n.value, hits.size)], dict(n_hits=n.value, n_positions=int(st[0]), n_poses=int(st[1]), used_beams=int(st[2]),
                                                     device_bytes=int(st[3]), n_scans=int(st[4]))
+
+    def global_search_streamed(self, scans, rel=None, max_hits=16, budget_bytes=0, slab_headings=0, stream_reserved=(0, 0, 0, 0, 0),
+                               **fields):
+        """global_search (one scan, rel None) or global_search_sequence in slabs of headings (mcl_global_search_streamed, DESIGN.md
+        §4.16): the same hits, bit for bit, from at most `budget_bytes` of slab buffers (0: 1 GiB), for lattices of up to 2^40
+        poses.  slab_headings = 0 takes the largest slab that fits.  Keeps no volume (search_scores raises afterwards).  Returns
+        (hits, {n_hits, n_positions, n_poses, used_beams, device_bytes, slab_headings, n_slabs, headings_scored,
+        candidates_compacted})."""
+        c = default_search_config(**fields)
+        sc = search_stream_config(budget_bytes, slab_headings, stream_reserved)
+        o = _c(np.atleast_2d(np.asarray(scans, np.float32)), np.float32)
+        if o.ndim != 2:
+            raise ValueError("scans must be (B,) or (S, B)")
+        S = o.shape[0]
+        r = None
+        if rel is not None:
+            r = _rel_rows(rel)
+            if r.shape[0] != S:
+                raise ValueError("scans and rel must have one row per scan")
+        hits = np.zeros(int(max_hits), SEARCH_HIT_DTYPE)
+        n, st = C.c_int64(), np.zeros(8, np.uint64)
+        self._chk(self.lib.mcl_global_search_streamed(self._h, C.byref(c), C.byref(sc), _p(o) if o.size else None,
+                                                      _p(r) if r is not None and r.size else None, C.c_int32(S), C.c_int32(o.shape[1]),
+                                                      C.c_int32(int(max_hits)), _p(hits) if hits.size else None, C.byref(n), _p(st)),
+                  "mcl_global_search_streamed")
+        self._search_poses = 0
+        return hits[:min(n.value, hits.size)], dict(n_hits=n.value, n_positions=int(st[0]), n_poses=int(st[1]), used_beams=int(st[2]),
+                                                    device_bytes=int(st[3]), slab_headings=int(st[4]), n_slabs=int(st[5]),
+                                                    headings_scored=int(st[6]), candidates_compacted=int(st[7]))
 
     def search_scores(self, n_headings=None):
         """The score volume of the last global_search or global_search_sequence (mcl_get_search_scores): n_headings * n_positions doubles, heading-major;
