@@ -11,113 +11,63 @@
 //   k_query_score  (score) one wave per pose: the table sum in a fixed order, the three counts
 //   (copy)         the results; one host wait
 #include "mcl_query.h"
+#include "mcl_side_buffers.h"
 
 #include <algorithm>
-#include <cmath>
 #include <cstring>
 
 using namespace mcl_qry;
+using namespace mcl_side;
+using mcl_host::fail;
 
 // the buffers of the query, kept between calls and grown with K, B and K * B
 struct mcl_query {
-    int64_t cap_k = 0, cap_b = 0, cap_rays = 0, cap_ranges = 0, cap_list = 0;
-    double *d_pose = nullptr, *h_pose = nullptr;          // 3 K: x, y, theta columns
-    uint16_t *d_steps = nullptr;
-    float *d_ranges = nullptr;
-    unsigned long long *d_list = nullptr;
-    Header *d_hdr = nullptr, *h_hdr = nullptr;
-    float *d_obs = nullptr, *h_obs = nullptr;
-    uint32_t *d_obs_row = nullptr;
-    double2 *d_lf_beams = nullptr, *h_lf_beams = nullptr;
-    double *d_lf_logw = nullptr;
-    mcl_pose_score_t *d_out = nullptr, *h_out = nullptr;
+    DevBuf<double> d_pose;                      // 3 K: x, y, theta columns
+    HostBuf<double> h_pose;
+    DevBuf<uint16_t> d_steps;
+    DevBuf<float> d_ranges;
+    DevBuf<unsigned long long> d_list;
+    DevBuf<Header> d_hdr;
+    HostBuf<Header> h_hdr;
+    DevBuf<float> d_obs;
+    HostBuf<float> h_obs;
+    DevBuf<uint32_t> d_obs_row;
+    DevBuf<double2> d_lf_beams;
+    HostBuf<double2> h_lf_beams;
+    DevBuf<double> d_lf_logw;
+    DevBuf<mcl_pose_score_t> d_out;
+    HostBuf<mcl_pose_score_t> h_out;
     unsigned long long last_level3 = 0;
     size_t device_bytes = 0;
 };
 
 namespace {
 
-using mcl_host::dfree;
-using mcl_host::fail;
-
-template <class T>
-void hfree(T *&p)
-{
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-}
-
-template <class T>
-int grow_dev(mcl_engine *h, mcl_query *q, T *&p, int64_t want)
-{
-    dfree(p);
-    HIPCHK(h, hipMalloc(&p, (size_t)want * sizeof(T)));
-    q->device_bytes += (size_t)want * sizeof(T);
-    return MCL_OK;
-}
-
-template <class T>
-int grow_host(mcl_engine *h, T *&p, int64_t want)
-{
-    hfree(p);
-    HIPCHK(h, hipHostMalloc((void **)&p, (size_t)want * sizeof(T)));
-    return MCL_OK;
-}
-
-#define QRY_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
-
 // room for K poses of B beams; ranges / the score's buffers only for a call that wants them.  (device_bytes counts what was ever
-// asked of hipMalloc for the live buffers: a diagnostic, mcl_get_query_counters.)
-int query_alloc(mcl_engine *h, mcl_query *q, int64_t K, int64_t B, bool want_ranges, bool score)
+// asked of hipMalloc: a diagnostic, mcl_get_query_counters.)
+int query_alloc(mcl_engine *h, mcl_query *q, size_t K, size_t B, bool want_ranges, bool score)
 {
-    const int64_t rays = K * B;
-    if (!q->d_hdr) {
-        QRY_TRY(grow_dev(h, q, q->d_hdr, 1));
-        QRY_TRY(grow_host(h, q->h_hdr, 1));
-    }
-    if (K > q->cap_k) {
-        q->cap_k = 0;
-        QRY_TRY(grow_dev(h, q, q->d_pose, 3 * K));
-        QRY_TRY(grow_host(h, q->h_pose, 3 * K));
-        dfree(q->d_out); hfree(q->h_out); dfree(q->d_lf_logw);
-        q->cap_k = K;
-    }
-    if (rays > q->cap_rays) {
-        q->cap_rays = 0;
-        QRY_TRY(grow_dev(h, q, q->d_steps, rays));
-        q->cap_rays = rays;
-    }
-    const int64_t list = (int64_t)std::min<unsigned long long>((unsigned long long)rays, kListCap);
-    if (list > q->cap_list) {
-        q->cap_list = 0;
-        QRY_TRY(grow_dev(h, q, q->d_list, list));
-        q->cap_list = list;
-    }
-    if (want_ranges && rays > q->cap_ranges) {
-        q->cap_ranges = 0;
-        QRY_TRY(grow_dev(h, q, q->d_ranges, rays));
-        q->cap_ranges = rays;
-    }
-    if (score) {
-        if (B > q->cap_b) {
-            q->cap_b = 0;
-            QRY_TRY(grow_dev(h, q, q->d_obs, B));
-            QRY_TRY(grow_host(h, q->h_obs, B));
-            QRY_TRY(grow_dev(h, q, q->d_obs_row, B));
-            dfree(q->d_lf_beams); hfree(q->h_lf_beams);
-            q->cap_b = B;
-        }
-        if (!q->d_out) {
-            QRY_TRY(grow_dev(h, q, q->d_out, q->cap_k));
-            QRY_TRY(grow_host(h, q->h_out, q->cap_k));
-        }
-        if (h->lf_on) {
-            if (!q->d_lf_beams) {
-                QRY_TRY(grow_dev(h, q, q->d_lf_beams, q->cap_b));
-                QRY_TRY(grow_host(h, q->h_lf_beams, q->cap_b));
-            }
-            if (!q->d_lf_logw) QRY_TRY(grow_dev(h, q, q->d_lf_logw, q->cap_k));
-        }
+    size_t *bytes = &q->device_bytes;
+    const size_t rays = K * B;
+    SIDE_TRY(q->d_hdr.reserve(h, 1, bytes));
+    SIDE_TRY(q->h_hdr.reserve(h, 1));
+    SIDE_TRY(q->d_pose.reserve(h, 3 * K, bytes));
+    SIDE_TRY(q->h_pose.reserve(h, 3 * K));
+    SIDE_TRY(q->d_steps.reserve(h, rays, bytes));
+    SIDE_TRY(q->d_list.reserve(h, (size_t)std::min<unsigned long long>(rays, kListCap), bytes));
+    if (want_ranges) SIDE_TRY(q->d_ranges.reserve(h, rays, bytes));
+    if (!score) return MCL_OK;
+    SIDE_TRY(q->d_obs.reserve(h, B, bytes));
+    SIDE_TRY(q->h_obs.reserve(h, B));
+    SIDE_TRY(q->d_obs_row.reserve(h, B, bytes));
+    // what only a score needs is as large as the poses / the scan have room: grown here when they have grown since, in any call
+    const size_t room_k = q->d_pose.cap / 3, room_b = q->d_obs.cap;
+    SIDE_TRY(q->d_out.reserve(h, room_k, bytes));
+    SIDE_TRY(q->h_out.reserve(h, room_k));
+    if (h->lf_on) {
+        SIDE_TRY(q->d_lf_beams.reserve(h, room_b, bytes));
+        SIDE_TRY(q->h_lf_beams.reserve(h, room_b));
+        SIDE_TRY(q->d_lf_logw.reserve(h, room_k, bytes));
     }
     return MCL_OK;
 }
@@ -150,13 +100,13 @@ int query_cast(mcl_engine *h, mcl_query *q, Args &a, const double *poses, int32_
     a.steps = q->d_steps;
     a.ranges = want_ranges ? q->d_ranges : nullptr;
     a.miss_range = (float)h->cfg.max_range_m;
-    a.list = q->d_list; a.list_cap = (unsigned long long)q->cap_list;
+    a.list = q->d_list; a.list_cap = (unsigned long long)q->d_list.cap;
     a.hdr = q->d_hdr;
     const int64_t rays = (int64_t)K * h->B;
     hipLaunchKernelGGL(k_query_rays, dim3((unsigned)((rays + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream, a);
     HIPCHK(h, hipGetLastError());
     // one wave per listed ray, as many as the list can hold at this size (the count is read on the device)
-    const int64_t waves = std::min<int64_t>(rays, q->cap_list);
+    const int64_t waves = std::min<int64_t>(rays, (int64_t)q->d_list.cap);
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, (int64_t)h->num_cu * 8));
     hipLaunchKernelGGL(k_query_exact, dim3(grid), dim3(kThreads), 0, h->stream, a);
     HIPCHK(h, hipGetLastError());
@@ -173,27 +123,20 @@ int query_finish(mcl_engine *h, mcl_query *q)
 
 }  // namespace
 
-void query_free(struct mcl_query *q)
-{
-    if (!q) return;
-    dfree(q->d_pose); dfree(q->d_steps); dfree(q->d_ranges); dfree(q->d_list); dfree(q->d_hdr); dfree(q->d_obs); dfree(q->d_obs_row);
-    dfree(q->d_lf_beams); dfree(q->d_lf_logw); dfree(q->d_out);
-    hfree(q->h_pose); hfree(q->h_hdr); hfree(q->h_obs); hfree(q->h_lf_beams); hfree(q->h_out);
-    delete q;
-}
+void query_free(struct mcl_query *q) { delete q; }
 
 extern "C" {
 
 int mcl_query_scans(mcl_engine_t *h, const double *poses_colmajor, int32_t K, float *ranges_m, uint16_t *steps)
 {
     if (!h) return MCL_ERR_INVALID_ARG;
-    QRY_TRY(query_check(h, poses_colmajor, K, "query_scans"));
+    SIDE_TRY(query_check(h, poses_colmajor, K, "query_scans"));
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (!h->qry) h->qry = new mcl_query();
     mcl_query *q = h->qry;
-    QRY_TRY(query_alloc(h, q, K, h->B, ranges_m != nullptr, false));
+    SIDE_TRY(query_alloc(h, q, (size_t)K, (size_t)h->B, ranges_m != nullptr, false));
     Args a{};
-    QRY_TRY(query_cast(h, q, a, poses_colmajor, K, ranges_m != nullptr));
+    SIDE_TRY(query_cast(h, q, a, poses_colmajor, K, ranges_m != nullptr));
     const size_t rays = (size_t)K * h->B;
     if (ranges_m) HIPCHK(h, hipMemcpyAsync(ranges_m, q->d_ranges, rays * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     if (steps) HIPCHK(h, hipMemcpyAsync(steps, q->d_steps, rays * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream));
@@ -206,7 +149,7 @@ int mcl_score_poses(mcl_engine_t *h, const double *poses_colmajor, int32_t K, co
     if (!h) return MCL_ERR_INVALID_ARG;
     if (!obs || !out) return fail(h, MCL_ERR_INVALID_ARG, "score_poses: obs / out is null");
     if (h->cfg.weight_mode != MCL_WEIGHT_LOG) return fail(h, MCL_ERR_INVALID_ARG, "score_poses: weight_mode LOG only (mcl_query_scans works in PRODUCT mode)");
-    QRY_TRY(query_check(h, poses_colmajor, K, "score_poses"));
+    SIDE_TRY(query_check(h, poses_colmajor, K, "score_poses"));
     if (n_beams != h->B) return fail(h, MCL_ERR_INVALID_ARG, "score_poses: n_beams does not match the beam angles");
     if (tol_steps < 0 || tol_steps > h->P) return fail(h, MCL_ERR_INVALID_ARG, "score_poses: tol_steps must be in [0, MAX_RANGE_PX]");
     const bool lf = h->lf_on;
@@ -214,9 +157,9 @@ int mcl_score_poses(mcl_engine_t *h, const double *poses_colmajor, int32_t K, co
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (!h->qry) h->qry = new mcl_query();
     mcl_query *q = h->qry;
-    QRY_TRY(query_alloc(h, q, K, h->B, false, true));
+    SIDE_TRY(query_alloc(h, q, (size_t)K, (size_t)h->B, false, true));
     Args a{};
-    QRY_TRY(query_cast(h, q, a, poses_colmajor, K, false));
+    SIDE_TRY(query_cast(h, q, a, poses_colmajor, K, false));
     const int B = h->B;
     std::memcpy(q->h_obs, obs, (size_t)B * sizeof(float));
     HIPCHK(h, hipMemcpyAsync(q->d_obs, q->h_obs, (size_t)B * sizeof(float), hipMemcpyHostToDevice, h->stream));
@@ -230,13 +173,13 @@ int mcl_score_poses(mcl_engine_t *h, const double *poses_colmajor, int32_t K, co
         const int nb = mcl_host::lf_used_beams(h, q->h_obs, 1, q->h_lf_beams);
         if (nb > 0)
             HIPCHK(h, hipMemcpyAsync(q->d_lf_beams, q->h_lf_beams, (size_t)nb * sizeof(double2), hipMemcpyHostToDevice, h->stream));
-        QRY_TRY(mcl_host::launch_lfield_on(h, a.x, a.y, a.th, K, q->d_lf_beams, nb, q->d_lf_logw));
+        SIDE_TRY(mcl_host::launch_lfield_on(h, a.x, a.y, a.th, K, q->d_lf_beams, nb, q->d_lf_logw));
         a.lf_logw = q->d_lf_logw;
     }
     hipLaunchKernelGGL(k_query_score, dim3((unsigned)((K + 3) / 4)), dim3(kThreads), 0, h->stream, a);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(q->h_out, q->d_out, (size_t)K * sizeof(mcl_pose_score_t), hipMemcpyDeviceToHost, h->stream));
-    QRY_TRY(query_finish(h, q));
+    SIDE_TRY(query_finish(h, q));
     std::memcpy(out, q->h_out, (size_t)K * sizeof(mcl_pose_score_t));
     return MCL_OK;
 }
