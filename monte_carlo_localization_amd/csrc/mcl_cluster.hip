@@ -327,84 +327,46 @@ inline int bit_width(uint64_t v)
 
 }  // namespace mcl_clu
 
-// the buffers of the clustering, kept between calls and grown when the grid, N or max_clusters grows
+// the buffers of the clustering, kept between calls and grown when the grid, N or max_clusters grows (the fields of Args they fill)
 struct mcl_cluster {
-    int64_t cap_n = 0, cap_nodes = 0, cap_words = 0, cap_units = 0, cap_out = 0;
-    size_t cap_tmp = 0;
-    Args a{};
-    void *tmp = nullptr;
-    Header *h_hdr = nullptr;
-    mcl_cluster_t *h_out = nullptr;
-    int64_t cap_h_out = 0;
+    DevBuf<uint32_t> bm, wpref, pbin, node_bin, parent, rflag, cid, nbins, first_bin, key, val, key2, val2, seg_start, seg_end, ucnt, ubase;
+    DevBuf<uint64_t> wq, ckey, ckey2;
+    DevBuf<double> mean, part;
+    DevBuf<uint32_t> cval, cval2, rank_of;
+    DevBuf<unsigned long long> upart;
+    DevBuf<int32_t> label;
+    DevBuf<mcl_cluster_t> out;
+    DevBuf<Header> hdr;
+    DevBuf<unsigned char> tmp;               // rocPRIM's scratch, in bytes
+    HostBuf<Header> h_hdr;
+    HostBuf<mcl_cluster_t> h_out;
     bool labels_valid = false;
     unsigned long long labels_epoch = 0;
     int64_t labels_n = 0;
 };
 
-void cluster_free(struct mcl_cluster *c)
-{
-    if (!c) return;
-    using mcl_host::dfree;
-    Args &a = c->a;
-    dfree(a.bm); dfree(a.wpref); dfree(a.pbin); dfree(a.node_bin); dfree(a.parent); dfree(a.rflag); dfree(a.cid);
-    dfree(a.nbins); dfree(a.first_bin); dfree(a.key); dfree(a.val); dfree(a.key2); dfree(a.val2); dfree(a.seg_start); dfree(a.seg_end);
-    dfree(a.ucnt); dfree(a.ubase); dfree(a.wq); dfree(a.mean); dfree(a.ckey); dfree(a.ckey2); dfree(a.cval); dfree(a.cval2);
-    dfree(a.rank_of); dfree(a.part); dfree(a.upart); dfree(a.label); dfree(a.out); dfree(a.hdr);
-    if (c->tmp) (void)hipFree(c->tmp);
-    if (c->h_hdr) (void)hipHostFree(c->h_hdr);
-    if (c->h_out) (void)hipHostFree(c->h_out);
-    delete c;
-}
+void cluster_free(struct mcl_cluster *c) { delete c; }
 
 namespace {
 
 using mcl_host::fail;
 
-template <class T>
-int grow(mcl_engine *h, T *&p, int64_t want, int64_t have)
+// buffers for n particles, max_nodes nodes, nwords bitmap words, K reported clusters (none of them empty); a: the kernels' view
+int cluster_alloc(mcl_engine *h, mcl_cluster *c, int64_t n, int64_t max_nodes, int64_t nwords, int64_t K, Args &a)
 {
-    if (want <= have && p) return MCL_OK;
-    mcl_host::dfree(p);
-    HIPCHK(h, hipMalloc(&p, (size_t)std::max<int64_t>(want, 1) * sizeof(T)));
-    return MCL_OK;
-}
-
-#define CLU_GROW(ptr, want, have) do { const int rc_ = grow(h, ptr, want, have); if (rc_) return rc_; } while (0)
-
-// buffers for n particles, max_nodes nodes, nwords bitmap words, K reported clusters
-int cluster_alloc(mcl_engine *h, mcl_cluster *c, int64_t n, int64_t max_nodes, int64_t nwords, int64_t K)
-{
-    Args &a = c->a;
-    const int64_t units = (n + kChunk - 1) / kChunk + max_nodes;
-    if (nwords > c->cap_words) {
-        CLU_GROW(a.bm, nwords, 0); CLU_GROW(a.wpref, nwords, 0);
-        c->cap_words = nwords;
-    }
-    if (n > c->cap_n) {
-        CLU_GROW(a.pbin, n, 0); CLU_GROW(a.key, n, 0); CLU_GROW(a.val, n, 0); CLU_GROW(a.key2, n, 0); CLU_GROW(a.val2, n, 0);
-        CLU_GROW(a.label, n, 0);
-        c->cap_n = n;
-    }
-    if (max_nodes > c->cap_nodes) {
-        CLU_GROW(a.node_bin, max_nodes, 0); CLU_GROW(a.parent, max_nodes, 0); CLU_GROW(a.rflag, max_nodes, 0); CLU_GROW(a.cid, max_nodes, 0);
-        CLU_GROW(a.nbins, max_nodes, 0); CLU_GROW(a.first_bin, max_nodes, 0); CLU_GROW(a.seg_start, max_nodes, 0);
-        CLU_GROW(a.seg_end, max_nodes, 0); CLU_GROW(a.ucnt, max_nodes, 0); CLU_GROW(a.ubase, max_nodes, 0); CLU_GROW(a.wq, max_nodes, 0);
-        CLU_GROW(a.mean, max_nodes * 3, 0); CLU_GROW(a.ckey, max_nodes, 0); CLU_GROW(a.ckey2, max_nodes, 0); CLU_GROW(a.cval, max_nodes, 0);
-        CLU_GROW(a.cval2, max_nodes, 0); CLU_GROW(a.rank_of, max_nodes, 0);
-        c->cap_nodes = max_nodes;
-    }
-    if (units > c->cap_units) {
-        CLU_GROW(a.part, units * 6, 0); CLU_GROW(a.upart, units, 0);
-        c->cap_units = units;
-    }
-    if (K > c->cap_out || !a.out) {
-        CLU_GROW(a.out, K, 0);
-        if (c->h_out) { (void)hipHostFree(c->h_out); c->h_out = nullptr; }
-        HIPCHK(h, hipHostMalloc((void **)&c->h_out, (size_t)std::max<int64_t>(K, 1) * sizeof(mcl_cluster_t)));
-        c->cap_out = std::max<int64_t>(K, 1);
-    }
-    if (!a.hdr) CLU_GROW(a.hdr, 1, 0);
-    if (!c->h_hdr) HIPCHK(h, hipHostMalloc((void **)&c->h_hdr, sizeof(Header)));
+    const size_t sn = (size_t)std::max<int64_t>(n, 1), sm = (size_t)std::max<int64_t>(max_nodes, 1), sw = (size_t)std::max<int64_t>(nwords, 1);
+    const size_t su = (size_t)std::max<int64_t>((n + kChunk - 1) / kChunk + max_nodes, 1), sk = (size_t)std::max<int64_t>(K, 1);
+#define CLU_BUF(field, want) do { MCL_TRY(c->field.reserve(h, want)); a.field = c->field; } while (0)
+    CLU_BUF(bm, sw); CLU_BUF(wpref, sw);
+    CLU_BUF(pbin, sn); CLU_BUF(key, sn); CLU_BUF(val, sn); CLU_BUF(key2, sn); CLU_BUF(val2, sn); CLU_BUF(label, sn);
+    CLU_BUF(node_bin, sm); CLU_BUF(parent, sm); CLU_BUF(rflag, sm); CLU_BUF(cid, sm); CLU_BUF(nbins, sm); CLU_BUF(first_bin, sm);
+    CLU_BUF(seg_start, sm); CLU_BUF(seg_end, sm); CLU_BUF(ucnt, sm); CLU_BUF(ubase, sm); CLU_BUF(wq, sm); CLU_BUF(mean, sm * 3);
+    CLU_BUF(ckey, sm); CLU_BUF(ckey2, sm); CLU_BUF(cval, sm); CLU_BUF(cval2, sm); CLU_BUF(rank_of, sm);
+    CLU_BUF(part, su * 6); CLU_BUF(upart, su);
+    CLU_BUF(out, sk); CLU_BUF(hdr, 1);
+#undef CLU_BUF
+    MCL_TRY(c->h_out.reserve(h, sk));
+    MCL_TRY(c->h_hdr.reserve(h, 1));
     // rocPRIM's scratch: the largest of the two scans and the two sorts at these sizes
     size_t need = 0, b = 0;
     HIPCHK(h, rocprim::exclusive_scan(nullptr, b, rocprim::make_transform_iterator(a.bm, Popc{}), a.wpref, 0u, (size_t)nwords,
@@ -416,12 +378,7 @@ int cluster_alloc(mcl_engine *h, mcl_cluster *c, int64_t n, int64_t max_nodes, i
     need = std::max(need, b);
     HIPCHK(h, rocprim::radix_sort_pairs(nullptr, b, a.ckey, a.ckey2, a.cval, a.cval2, (size_t)max_nodes, 0, 64, h->stream));
     need = std::max(need, b);
-    if (need > c->cap_tmp || !c->tmp) {
-        if (c->tmp) { (void)hipFree(c->tmp); c->tmp = nullptr; c->cap_tmp = 0; }
-        HIPCHK(h, hipMalloc(&c->tmp, std::max<size_t>(need, 16)));
-        c->cap_tmp = std::max<size_t>(need, 16);
-    }
-    return MCL_OK;
+    return c->tmp.reserve(h, std::max<size_t>(need, 16));
 }
 
 unsigned grid_of(const mcl_engine *h, int64_t threads)
@@ -480,10 +437,10 @@ int mcl_pose_clusters(mcl_engine_t *h, const mcl_cluster_config_t *cfg, int32_t 
     c->labels_valid = false;
     const int64_t n = h->N, grid_bins = (int64_t)bits - 1;       // (the outside bin has no bit)
     const int64_t max_nodes = std::min<int64_t>(n, grid_bins), nwords = (grid_bins + 31) / 32;
-    int rc = cluster_alloc(h, c, n, max_nodes, nwords, max_clusters);
+    Args a{};
+    int rc = cluster_alloc(h, c, n, max_nodes, nwords, max_clusters, a);
     if (rc) return rc;
 
-    Args &a = c->a;
     const int cur = h->cur;
     a.x = h->d_x[cur]; a.y = h->d_y[cur]; a.th = h->d_th[cur]; a.q = h->d_q; a.n = n;
     a.kb = mcl_host::kld_args_of(&kc, nx, ny, h->ox, h->oy);
@@ -494,28 +451,28 @@ int mcl_pose_clusters(mcl_engine_t *h, const mcl_cluster_config_t *cfg, int32_t 
     HIPCHK(h, hipMemsetAsync(a.nbins, 0, (size_t)max_nodes * sizeof(uint32_t), h->stream));
     HIPCHK(h, hipMemsetAsync(a.hdr, 0, sizeof(Header), h->stream));
 
-    size_t tb = c->cap_tmp;
+    size_t tb = c->tmp.cap;
     CLU_LAUNCH(k_clu_bin, (unsigned)((n + kThreads - 1) / kThreads));
-    HIPCHK(h, rocprim::exclusive_scan(c->tmp, tb, rocprim::make_transform_iterator(a.bm, Popc{}), a.wpref, 0u, (size_t)nwords,
+    HIPCHK(h, rocprim::exclusive_scan(c->tmp.p, tb, rocprim::make_transform_iterator(a.bm, Popc{}), a.wpref, 0u, (size_t)nwords,
                                       rocprim::plus<uint32_t>(), h->stream));
     CLU_LAUNCH(k_clu_nodes, grid_of(h, nwords));
     CLU_LAUNCH(k_clu_union, grid_of(h, max_nodes));
     CLU_LAUNCH(k_clu_compress, grid_of(h, max_nodes));
-    tb = c->cap_tmp;
-    HIPCHK(h, rocprim::exclusive_scan(c->tmp, tb, a.rflag, a.cid, 0u, (size_t)max_nodes, rocprim::plus<uint32_t>(), h->stream));
+    tb = c->tmp.cap;
+    HIPCHK(h, rocprim::exclusive_scan(c->tmp.p, tb, a.rflag, a.cid, 0u, (size_t)max_nodes, rocprim::plus<uint32_t>(), h->stream));
     CLU_LAUNCH(k_clu_key, grid_of(h, n));
     CLU_LAUNCH(k_clu_nbins, grid_of(h, max_nodes));
-    tb = c->cap_tmp;
-    HIPCHK(h, rocprim::radix_sort_pairs(c->tmp, tb, a.key, a.key2, a.val, a.val2, (size_t)n, 0, bit_width((uint64_t)max_nodes), h->stream));
+    tb = c->tmp.cap;
+    HIPCHK(h, rocprim::radix_sort_pairs(c->tmp.p, tb, a.key, a.key2, a.val, a.val2, (size_t)n, 0, bit_width((uint64_t)max_nodes), h->stream));
     CLU_LAUNCH(k_clu_seg, grid_of(h, n));
     CLU_LAUNCH(k_clu_ucnt, grid_of(h, max_nodes));
-    tb = c->cap_tmp;
-    HIPCHK(h, rocprim::exclusive_scan(c->tmp, tb, a.ucnt, a.ubase, 0u, (size_t)max_nodes, rocprim::plus<uint32_t>(), h->stream));
+    tb = c->tmp.cap;
+    HIPCHK(h, rocprim::exclusive_scan(c->tmp.p, tb, a.ucnt, a.ubase, 0u, (size_t)max_nodes, rocprim::plus<uint32_t>(), h->stream));
     const int64_t units = (n + kChunk - 1) / kChunk + max_nodes;
     CLU_LAUNCH(k_clu_pass1, grid_of(h, units * 64));
     CLU_LAUNCH(k_clu_comb1, grid_of(h, max_nodes * 64));
-    tb = c->cap_tmp;
-    HIPCHK(h, rocprim::radix_sort_pairs(c->tmp, tb, a.ckey, a.ckey2, a.cval, a.cval2, (size_t)max_nodes, 0, 64, h->stream));
+    tb = c->tmp.cap;
+    HIPCHK(h, rocprim::radix_sort_pairs(c->tmp.p, tb, a.ckey, a.ckey2, a.cval, a.cval2, (size_t)max_nodes, 0, 64, h->stream));
     CLU_LAUNCH(k_clu_rank, grid_of(h, max_nodes));
     CLU_LAUNCH(k_clu_label, grid_of(h, n));
     if (max_clusters > 0) {
@@ -546,7 +503,7 @@ int mcl_get_cluster_labels(mcl_engine_t *h, int32_t *labels, int64_t n)
         return fail(h, MCL_ERR_NOT_READY, "clusters: no clustering of the current particle set (call mcl_pose_clusters first)");
     if (!labels || n != h->N) return fail(h, MCL_ERR_INVALID_ARG, "clusters: labels must hold N entries");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipMemcpyAsync(labels, c->a.label, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(labels, c->label, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MCL_OK;
 }

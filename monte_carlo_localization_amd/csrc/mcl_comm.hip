@@ -72,17 +72,15 @@ static RcclApi &rccl_api()
 struct mcl_comm {
     ncclComm_t comm = nullptr;
     int n_ranks = 0, rank = 0;
-    unsigned char *d_chunk_local = nullptr, *d_chunk_all = nullptr;     // the lists: this shard's chunk, every shard's
-    size_t chunk_capacity = 0;                                           // entries per chunk the buffers hold
-    double *d_red = nullptr;                                             // [0] MAX exchange | [1 .. k] SUM exchange | [1 + k] error word (ranks that failed)
-    double *h_red = nullptr;                                             // pinned copy of it
+    DevBuf<unsigned char> d_chunk_local, d_chunk_all;                    // the lists: this shard's chunk, every shard's
+    DevBuf<double> d_red;                                                // [0] MAX exchange | [1 .. k] SUM exchange | [1 + k] error word (ranks that failed)
+    HostBuf<double> h_red;                                               // pinned copy of it
     uint64_t bytes_received = 0, bytes_payload = 0;                      // of the last update's list exchange
     int host_waits = 0;
     // dense exchange (an update without lists: the first after the particles were set): every shard's fixed-point weights,
     // their global CDF and every shard's packed records; allocated when first needed
-    uint64_t *d_qall = nullptr, *d_cdfall = nullptr;
-    double4 *d_recall = nullptr;
-    size_t dense_capacity = 0;                                           // particles (all shards) the three arrays hold
+    DevBuf<uint64_t> d_qall, d_cdfall;                                   // (particles of all shards)
+    DevBuf<double4> d_recall;
     bool last_dense = false, last_kept = false;
     bool vec_valid = false;                                              // vec holds the sums of an update of the current particle set
     uint64_t dense_weights_bytes = 0, dense_records_bytes = 0;
@@ -121,13 +119,6 @@ void comm_free(mcl_comm *c)
 {
     if (!c) return;
     if (c->comm && rccl_api().CommDestroy) (void)rccl_api().CommDestroy(c->comm);        // (an aborted communicator is gone already: comm == nullptr)
-    if (c->d_chunk_local) (void)hipFree(c->d_chunk_local);
-    if (c->d_chunk_all) (void)hipFree(c->d_chunk_all);
-    if (c->d_red) (void)hipFree(c->d_red);
-    if (c->h_red) (void)hipHostFree(c->h_red);
-    if (c->d_qall) (void)hipFree(c->d_qall);
-    if (c->d_cdfall) (void)hipFree(c->d_cdfall);
-    if (c->d_recall) (void)hipFree(c->d_recall);
     delete c;
 }
 
@@ -240,7 +231,7 @@ int mcl_comm_create(mcl_engine_t *h, const unsigned char id[128], int32_t n_rank
     const ncclResult_t r = api.CommInitRank(&c->comm, n_ranks, u, rank);          // collective: every rank is in this call
     if (r != ncclSuccess) { c->comm = nullptr; comm_free(c); return fail(h, MCL_ERR_HIP, std::string("ncclCommInitRank: ") + api.GetErrorString(r)); }
     const size_t words = 1 + 5 + 3 * (size_t)n_ranks + 2 + 1;                     // MAX | summed vector | error word
-    if (hipMalloc(&c->d_red, words * 8) != hipSuccess || hipHostMalloc(&c->h_red, words * 8) != hipSuccess) {
+    if (c->d_red.reserve(h, words) != MCL_OK || c->h_red.reserve(h, words) != MCL_OK) {
         comm_free(c);
         return fail(h, MCL_ERR_HIP, "mcl_comm_create: allocation failed");
     }
@@ -260,8 +251,8 @@ int mcl_comm_selftest(mcl_engine_t *h)
     RcclApi &api = rccl_api();
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const int G = c->n_ranks;
-    unsigned char *d_buf = nullptr;
-    HIPCHK(h, hipMalloc(&d_buf, 64 * (size_t)(G + 1)));
+    DevBuf<unsigned char> d_buf;
+    MCL_TRY(d_buf.reserve(h, 64 * (size_t)(G + 1)));
     unsigned char mine[64];
     for (int i = 0; i < 64; ++i) mine[i] = (unsigned char)(c->rank * 7 + i);
     double two[2] = {(double)c->rank, 1.0};
@@ -283,8 +274,7 @@ int mcl_comm_selftest(mcl_engine_t *h)
         return MCL_OK;
     };
     const int rc = run();
-    (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(d_buf);
+    (void)hipStreamSynchronize(h->stream);               // (before d_buf goes)
     return rc;
 }
 
@@ -363,16 +353,13 @@ static int comm_gather_lists(mcl_engine_t *h, const int64_t *counts, CommLocal &
     for (int r = 0; r < G; ++r) { longest = std::max(longest, counts[r]); listed += counts[r]; }
     const int64_t entries = std::max<int64_t>(64, (longest + 63) & ~(int64_t)63);
     c->gathered = false;
-    if ((size_t)entries > c->chunk_capacity) {
+    if ((size_t)entries * kCompactEntryBytes * (size_t)G > c->d_chunk_all.cap) {       // (reserved last: it stands for both)
         // (without buffers of the agreed size this rank cannot take part in the all-gather: a hard failure)
         bool ok = hipStreamSynchronize(h->stream) == hipSuccess;
-        if (c->d_chunk_local) (void)hipFree(c->d_chunk_local);
-        if (c->d_chunk_all) (void)hipFree(c->d_chunk_all);
-        c->d_chunk_local = c->d_chunk_all = nullptr; c->chunk_capacity = 0;
+        c->d_chunk_local.drop(); c->d_chunk_all.drop();
         const size_t cap = (size_t)entries + (size_t)entries / 4;            // lists breathe from update to update
-        ok = ok && hipMalloc(&c->d_chunk_local, cap * kCompactEntryBytes) == hipSuccess && hipMalloc(&c->d_chunk_all, cap * kCompactEntryBytes * (size_t)G) == hipSuccess;
+        ok = ok && c->d_chunk_local.reserve(h, cap * kCompactEntryBytes) == MCL_OK && c->d_chunk_all.reserve(h, cap * kCompactEntryBytes * (size_t)G) == MCL_OK;
         if (!ok) { comm_abort(h, "alloc"); return fail(h, MCL_ERR_HIP, "mcl_comm_update: no memory for the list exchange (communicator aborted)"); }
-        c->chunk_capacity = cap;
     }
     if (!loc.bad()) loc.note(h, export_compact_launch(h, c->d_chunk_local, entries, h->cfg.device, h->stream));
     NCCLCHK(h, api.AllGather(c->d_chunk_local, c->d_chunk_all, (size_t)entries * kCompactEntryBytes, ncclChar, c->comm, h->stream));
@@ -414,26 +401,15 @@ static int comm_resample_dense(mcl_engine_t *h, const double action[3], CommLoca
     RcclApi &api = rccl_api();
     const int G = c->n_ranks;
     const int64_t n = h->N, nt = n * G;
-    if ((size_t)nt > c->dense_capacity) {
+    if ((size_t)nt > c->d_recall.cap) {                                  // (reserved last: it stands for the three)
         bool ok = hipStreamSynchronize(h->stream) == hipSuccess;
-        if (c->d_qall) (void)hipFree(c->d_qall);
-        if (c->d_cdfall) (void)hipFree(c->d_cdfall);
-        if (c->d_recall) (void)hipFree(c->d_recall);
-        c->d_qall = c->d_cdfall = nullptr; c->d_recall = nullptr; c->dense_capacity = 0;
-        ok = ok && hipMalloc(&c->d_qall, (size_t)nt * 8) == hipSuccess && hipMalloc(&c->d_cdfall, (size_t)nt * 8) == hipSuccess &&
-             hipMalloc(&c->d_recall, (size_t)nt * sizeof(double4)) == hipSuccess;
+        c->d_qall.drop(); c->d_cdfall.drop(); c->d_recall.drop();
+        ok = ok && c->d_qall.reserve(h, (size_t)nt) == MCL_OK && c->d_cdfall.reserve(h, (size_t)nt) == MCL_OK &&
+             c->d_recall.reserve(h, (size_t)nt) == MCL_OK;
         if (!ok) { comm_abort(h, "alloc"); return fail(h, MCL_ERR_HIP, "mcl_comm_update: no memory for the dense exchange (communicator aborted)"); }
-        c->dense_capacity = (size_t)nt;
     }
-    if (!loc.bad() && (size_t)nt / mcl::kScanTile + 2 > h->blocktot_capacity) {          // spine scratch of the scan, sized for one shard so far
-        graph_reset(h);
-        bool ok = hipStreamSynchronize(h->stream) == hipSuccess;
-        dfree(h->d_blocktot);
-        h->blocktot_capacity = 0;
-        ok = ok && hipMalloc(&h->d_blocktot, ((size_t)nt / mcl::kScanTile + 2) * 8) == hipSuccess;
-        if (ok) h->blocktot_capacity = (size_t)nt / mcl::kScanTile + 2;
-        else loc.note(h, fail(h, MCL_ERR_HIP, "mcl_comm_update: no memory for the scan of the whole set"));
-    }
+    if (!loc.bad() && reserve_scan_spine(h, nt) != MCL_OK)                 // (sized for one shard so far)
+        loc.note(h, fail(h, MCL_ERR_HIP, "mcl_comm_update: no memory for the scan of the whole set"));
     const int cur = h->cur;
     if (!loc.bad() && !h->pack_valid[cur]) {
         launch_pack_records(h->stream, h->d_x[cur], h->d_y[cur], h->d_th[cur], n, h->d_pack[cur]);

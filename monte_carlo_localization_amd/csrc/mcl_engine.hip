@@ -31,18 +31,11 @@ thread_local std::string g_create_error;
 
 int ensure_lt(mcl_engine *h)
 {
-    size_t need = (size_t)(h->P + 1) * h->bpad;
-    if (need > h->lt_capacity) {
-        dfree(h->d_Lt);
-        HIPCHK(h, hipMalloc(&h->d_Lt, 2 * need * sizeof(float)));      // [Lt | Lt with the rows reversed (k_rays_cell)]
-        h->lt_capacity = need;
-    }
+    MCL_TRY(h->d_Lt.reserve(h, 2 * (size_t)(h->P + 1) * h->bpad));     // [Lt | Lt with the rows reversed (k_rays_cell)]
     h->ltd_cols = (h->B + 2 * h->beam_margin + 64) & ~63;              // beam j in column j + beam_margin; at least one all-zero column after the last beam
     const size_t need_d = (size_t)mcl::sweep_table_rows(h->P) * h->ltd_cols;
-    if (need_d > h->ltd_capacity) {
-        dfree(h->d_Ltd);
-        HIPCHK(h, hipMalloc(&h->d_Ltd, need_d * sizeof(double)));
-        h->ltd_capacity = need_d;
+    if (need_d > h->d_Ltd.cap) {
+        MCL_TRY(h->d_Ltd.reserve(h, need_d));
         h->ltd_ready = false;
     }
     return MCL_OK;
@@ -131,19 +124,13 @@ int64_t max_sweep_units(int64_t n) { return (n + mcl::kSwUnit - 1) / mcl::kSwUni
 int launch_sweep_plan(mcl_engine *h, int64_t n, int nwg, int g, bool hybrid)
 {
     const int ngroups = mcl::kWedges / g;
-    const size_t need = (size_t)max_sweep_units(n) * ngroups;
-    if (need > h->items_capacity) {
-        dfree(h->d_items); dfree(h->d_centres);
-        h->items_capacity = 0;
-        HIPCHK(h, hipMalloc(&h->d_items, need * sizeof(int4)));
-        HIPCHK(h, hipMalloc(&h->d_centres, (size_t)max_sweep_units(n) * sizeof(int4)));
-        h->items_capacity = need;
-    }
-    if (!h->d_nitems) HIPCHK(h, hipMalloc(&h->d_nitems, sizeof(int)));
+    MCL_TRY(h->d_items.reserve(h, (size_t)max_sweep_units(n) * ngroups));
+    MCL_TRY(h->d_centres.reserve(h, (size_t)max_sweep_units(n)));
+    MCL_TRY(h->d_nitems.reserve(h, 1));
     const int play = sweep_play(h, hybrid);                             // cells a window leaves for the particles of an item
     // (EV_K0 = the stop event of the kernel before the ray kernel, EV_K1 = the ray kernel's own: its duration, dispatch included, at no cost)
-    hipExtLaunchKernelGGL(mcl::k_sweep_plan, dim3(1), dim3(1024), mcl::kPlanLds, h->stream, nullptr, h->ev[EV_K0], 0, h->d_unit_sums, h->d_nunits, ngroups, nwg,
-                          (double)(play / 2 - 1), h->env_sw_guide > 0 ? h->env_sw_guide : (h->sweep_global ? 3 : 2), h->d_items, h->d_centres, h->d_nitems);
+    hipExtLaunchKernelGGL(mcl::k_sweep_plan, dim3(1), dim3(1024), mcl::kPlanLds, h->stream, nullptr, h->ev[EV_K0], 0, h->d_unit_sums.p, h->d_nunits.p, ngroups, nwg,
+                          (double)(play / 2 - 1), h->env_sw_guide > 0 ? h->env_sw_guide : (h->sweep_global ? 3 : 2), h->d_items.p, h->d_centres.p, h->d_nitems.p);
     HIPCHK(h, hipGetLastError());
     return MCL_OK;
 }
@@ -221,7 +208,7 @@ SortTiles sort_tiles(const mcl_engine *h)
 int launch_far_windowed(mcl_engine *h, const mcl::RayArgs &a, int64_t n, bool count)
 {
     const unsigned nb = (unsigned)((n + mcl::kFarTile - 1) / mcl::kFarTile);
-    const uint32_t *flags32 = reinterpret_cast<const uint32_t *>(h->d_far);
+    const uint32_t *flags32 = reinterpret_cast<const uint32_t *>(h->d_far.p);
     hipLaunchKernelGGL(mcl::k_far_count, dim3(nb), dim3(256), 0, h->stream, flags32, n, a.far_count, h->d_far_cnt);
     hipLaunchKernelGGL(mcl::k_far_spine, dim3(1), dim3(1024), 0, h->stream, h->d_far_cnt, (int)nb, a.far_count);
     hipLaunchKernelGGL(mcl::k_far_scatter, dim3(nb), dim3(256), 0, h->stream, flags32, n, a.far_count, h->d_far_cnt, h->d_far_sorted);
@@ -251,15 +238,12 @@ int launch_rays(mcl_engine *h, const double *x, const double *y, const double *t
     if (h->cfg.keep_ray_steps) {
         // one byte per step index up to 255 px of range, two beyond (allocated here: both the map and the beam set size it)
         const size_t need = (size_t)h->cap * h->B * (h->P > 255 ? 2 : 1);
-        if (need > h->steps_capacity) {
+        if (need > h->d_steps.cap) {
             if (h->capturing) return fail(h, MCL_ERR_HIP, "step buffer missing during capture (internal)");
             graph_reset(h);
-            dfree(h->d_steps);
-            h->steps_capacity = 0;
-            HIPCHK(h, hipMalloc(&h->d_steps, need));
-            h->steps_capacity = need;
+            MCL_TRY(h->d_steps.reserve(h, need));
         }
-        if (h->P > 255) a.steps16 = reinterpret_cast<uint16_t *>(h->d_steps);
+        if (h->P > 255) a.steps16 = reinterpret_cast<uint16_t *>(h->d_steps.p);
         else a.steps = h->d_steps;
     }
     a.grid = h->d_grid; a.W = h->W; a.H = h->H;
@@ -329,16 +313,8 @@ int launch_rays(mcl_engine *h, const double *x, const double *y, const double *t
         const unsigned long long seg_div = 256;
         unsigned long long segcap = std::max<unsigned long long>(2048, (rays_per_seg / seg_div + 7) & ~7ull);
         if ((unsigned long long)n * h->B <= (4ull << 20)) segcap = (2 * rays_per_seg + 7) & ~7ull;   // small launch: room for every ray
-        if ((unsigned long long)nseg * segcap > h->fix_alloc) {
-            dfree(h->d_fix_list);
-            HIPCHK(h, hipMalloc(&h->d_fix_list, (size_t)nseg * segcap * 8));
-            h->fix_alloc = (unsigned long long)nseg * segcap;
-        }
-        if ((size_t)nseg > h->fix_count_alloc) {
-            dfree(h->d_fix_count);
-            HIPCHK(h, hipMalloc(&h->d_fix_count, (size_t)nseg * 64));
-            h->fix_count_alloc = nseg;
-        }
+        MCL_TRY(h->d_fix_list.reserve(h, (size_t)nseg * segcap));
+        MCL_TRY(h->d_fix_count.reserve(h, (size_t)nseg * 8));
         h->fix_cap = segcap;
         h->fix_segments = nseg;
         a.qr = cell ? nullptr : h->d_qr;
@@ -351,7 +327,7 @@ int launch_rays(mcl_engine *h, const double *x, const double *y, const double *t
         a.logw = h->d_logw_acc;
         {   // per-particle constants; the same pass zeroes the stage's scratch (partial sums are added atomically)
             mcl::PrepClear clr{};
-            clr.logw_acc = h->d_logw_acc; clr.far_flags = reinterpret_cast<uint32_t *>(h->d_far);
+            clr.logw_acc = h->d_logw_acc; clr.far_flags = reinterpret_cast<uint32_t *>(h->d_far.p);
             clr.fix_count = h->d_fix_count; clr.fix_words = nseg * 8; clr.fix_over = h->d_fix_over; clr.exact_count = h->d_result + 14;
             if (sweep) clr.far_count = h->d_result + 15;
             const bool stale_layout = cell && h->layout_stale_used;      // d_bbox / d_tilemap hold the layout to order by: not remade
@@ -393,23 +369,16 @@ int launch_rays(mcl_engine *h, const double *x, const double *y, const double *t
             // 4M x 1081 6.57 -> 6.47 ms per update; below, its fixed cost of a dozen launches loses (2M +0.03, 262 144 +0.05 ms).
             const bool radix = h->env_sort_radix >= 0 ? h->env_sort_radix != 0 : n >= 3000000;
             if (radix) {
-                if (!h->d_skey2) {
-                    HIPCHK(h, hipMalloc(&h->d_skey2, (size_t)h->cap * 4));
-                    HIPCHK(h, hipMalloc(&h->d_sval2, (size_t)h->cap * 4));
-                }
+                MCL_TRY(h->d_skey2.reserve(h, (size_t)h->cap));
+                MCL_TRY(h->d_sval2.reserve(h, (size_t)h->cap));
                 size_t tb = 0;
-                HIPCHK(h, rocprim::radix_sort_pairs(nullptr, tb, h->d_skey, h->d_skey2, h->d_srank, h->d_sval2, (size_t)n, 0, mcl::kSortKeyLog2, h->stream));
-                if (tb > h->sort_tmp_bytes) {
-                    dfree(h->d_sort_tmp);
-                    h->sort_tmp_bytes = 0;
-                    HIPCHK(h, hipMalloc(&h->d_sort_tmp, tb));
-                    h->sort_tmp_bytes = tb;
-                }
+                HIPCHK(h, rocprim::radix_sort_pairs(nullptr, tb, h->d_skey.p, h->d_skey2.p, h->d_srank.p, h->d_sval2.p, (size_t)n, 0, mcl::kSortKeyLog2, h->stream));
+                MCL_TRY(h->d_sort_tmp.reserve(h, tb));
                 if (!(stale_layout && h->keys_done))       // (else the resampling kernel wrote the pairs)
                     hipLaunchKernelGGL(mcl::k_sort_keys, dim3(nb256), dim3(256), 0, h->stream, h->d_pc, th, n, h->Wp, h->Hp, h->d_bbox, h->d_skey, h->d_srank,
                                        h->d_tilemap, ntx_abs);
-                tb = h->sort_tmp_bytes;
-                HIPCHK(h, rocprim::radix_sort_pairs(h->d_sort_tmp, tb, h->d_skey, h->d_skey2, h->d_srank, h->d_sval2, (size_t)n, 0, mcl::kSortKeyLog2, h->stream));
+                tb = h->d_sort_tmp.cap;
+                HIPCHK(h, rocprim::radix_sort_pairs(h->d_sort_tmp.p, tb, h->d_skey.p, h->d_skey2.p, h->d_srank.p, h->d_sval2.p, (size_t)n, 0, mcl::kSortKeyLog2, h->stream));
                 hipLaunchKernelGGL(mcl::k_sort_gather, dim3(nb256), dim3(256), 0, h->stream, h->d_pc, th, n, h->d_sval2, h->d_pcs, h->d_ths, h->d_perm,
                                    sweep ? h->d_skey2 : (const uint32_t *)nullptr, h->d_bbox, h->d_cut_start, h->d_cut_end);
             } else {
@@ -424,14 +393,9 @@ int launch_rays(mcl_engine *h, const double *x, const double *y, const double *t
                 // units of the sorted order (cut at tile borders when the set is ordered by whole tiles), from the bucket
                 // offsets the scatter has just used -- before they are cleared
                 const size_t mu = (size_t)max_sweep_units(n);
-                if (mu > h->unit_sums_capacity) {
-                    dfree(h->d_unit_sums); dfree(h->d_unit_begin);
-                    h->unit_sums_capacity = 0;
-                    HIPCHK(h, hipMalloc(&h->d_unit_sums, mu * 2 * sizeof(double4)));
-                    HIPCHK(h, hipMalloc(&h->d_unit_begin, (mu + 1) * sizeof(uint32_t)));
-                    h->unit_sums_capacity = mu;
-                }
-                if (!h->d_nunits) HIPCHK(h, hipMalloc(&h->d_nunits, sizeof(int)));
+                MCL_TRY(h->d_unit_sums.reserve(h, mu * 2));
+                MCL_TRY(h->d_unit_begin.reserve(h, mu + 1));
+                MCL_TRY(h->d_nunits.reserve(h, 1));
                 hipLaunchKernelGGL(mcl::k_unit_table, dim3(1), dim3(1024), 0, h->stream, h->d_bbox, n, h->d_hist, h->d_histpart, h->d_tile_used,
                                    radix ? h->d_cut_start : (uint32_t *)nullptr, h->d_cut_end, h->d_unit_begin, h->d_nunits, (int)mu);
             }
@@ -441,11 +405,7 @@ int launch_rays(mcl_engine *h, const double *x, const double *y, const double *t
                 hipLaunchKernelGGL(mcl::k_unit_sums, dim3((unsigned)std::min<int64_t>(max_sweep_units(n), (n + mcl::kSwUnit - 1) / mcl::kSwUnit + 256)), dim3(256), 0, h->stream, h->d_pcs, h->d_unit_begin, h->d_nunits,
                                    h->d_unit_sums, radix ? (uint32_t *)nullptr : h->d_hist, h->d_tile_used, nparts);
             } else {
-                if ((size_t)nsl > h->slice_mean_capacity) {
-                    dfree(h->d_slice_mean);
-                    HIPCHK(h, hipMalloc(&h->d_slice_mean, (size_t)nsl * sizeof(double2)));
-                    h->slice_mean_capacity = nsl;
-                }
+                MCL_TRY(h->d_slice_mean.reserve(h, (size_t)nsl));
                 hipLaunchKernelGGL(mcl::k_slice_means, dim3((unsigned)nsl), dim3(256), 0, h->stream, h->d_pcs, n, (n + nsl - 1) / nsl, h->d_slice_mean);
             }
             a.pcs = h->d_pcs; a.ths = h->d_ths; a.perm = h->d_perm; a.slice_mean = h->d_slice_mean;
@@ -464,11 +424,9 @@ int launch_rays(mcl_engine *h, const double *x, const double *y, const double *t
             a.beam_csi = h->d_beam_csi; a.beam_err = h->d_beam_err; a.rec_k = 2.0 * h->rec_c;
             a.distg = h->d_distg; a.distg_stride = h->distg_stride; a.distg_pitch = h->distg_pitch;
             a.items = h->d_items; a.centres = h->d_centres; a.nitems = 0; a.nitems_ptr = h->d_nitems; a.unit_sums = h->d_unit_sums; a.unit_begin = h->d_unit_begin; a.slot_space = 1;
-            if (!h->d_far_list) {
-                HIPCHK(h, hipMalloc(&h->d_far_list, (size_t)h->cap * sizeof(uint32_t)));
-                HIPCHK(h, hipMalloc(&h->d_far_sorted, (size_t)h->cap * sizeof(uint32_t)));
-                HIPCHK(h, hipMalloc(&h->d_far_cnt, ((size_t)h->cap / mcl::kFarTile + 2) * sizeof(uint32_t)));
-            }
+            MCL_TRY(h->d_far_list.reserve(h, (size_t)h->cap));
+            MCL_TRY(h->d_far_sorted.reserve(h, (size_t)h->cap));
+            MCL_TRY(h->d_far_cnt.reserve(h, (size_t)h->cap / mcl::kFarTile + 2));
             // the windowed far pass (four launches that stand down on the device when little is flagged) is only launched when
             // there is reason to expect work for it: the previous ray stage flagged a fair number of slots, or the particle set
             // is fresh (set / initialised since).  A misjudgement costs time, never results: without it k_rays_far takes all.
@@ -491,9 +449,9 @@ int launch_rays(mcl_engine *h, const double *x, const double *y, const double *t
         size_t qlds = sweep ? (sweep_glob ? 0 : (size_t)mcl::kSwWinBytes) + (sweep_rec ? (size_t)h->ltd_cols * 8 : 0) : (size_t)h->qside * h->qside;
         h->last_sweep_global = sweep_glob ? 1 : (sweep_hyb ? 2 : 0); h->last_sweep_rec = sweep_rec ? 1 : 0; h->last_sweep_pairs = (sweep_rec && (sweep_glob || sweep_pairs)) ? 1 : 0;
         dim3 qg((unsigned)nseg);   // persistent: 2 workgroups per CU
-        unsigned long long *d_dbg = nullptr;
+        DevBuf<unsigned long long> d_dbg;
         const char *dbgpath = h->env_debug_wg.empty() ? nullptr : h->env_debug_wg.c_str();
-        if (dbgpath) { HIPCHK(h, hipMalloc(&d_dbg, (size_t)qg.x * 32)); HIPCHK(h, hipMemset(d_dbg, 0, (size_t)qg.x * 32)); a.dbg = d_dbg; }
+        if (dbgpath) { MCL_TRY(d_dbg.reserve(h, (size_t)qg.x * 4)); HIPCHK(h, hipMemset(d_dbg, 0, (size_t)qg.x * 32)); a.dbg = d_dbg; }
         // k_rays_far is bound by global-memory latency: 4 workgroups per CU worth of blocks (2 resident at a time)
         dim3 gfar((unsigned)std::max<int64_t>(1, std::min<int64_t>(4 * (int64_t)h->num_cu, (n + 15) / 16)));
         const int fix_split = std::max(1, std::min(16, (8 * h->num_cu) / std::max(nseg, 1)));   // ~8 workgroups of k_rays_fix per CU (2 .. 16 per segment: no difference, round 4)
@@ -534,8 +492,8 @@ int launch_rays(mcl_engine *h, const double *x, const double *y, const double *t
         if (sweep) {
             // the slot accumulators (k_rays_sweep's per-wedge sums + what the far / fix / exact kernels added) -> d_logw in particle
             // order, the per-workgroup maxima, and the overflow flag of the fix-up lists (k_fix_overflow's job for the other kernels)
-            hipExtLaunchKernelGGL(mcl::k_combine_logw, dim3(mcl::kRedBlocks), dim3(256), 0, h->stream, nullptr, h->ev[EV_RAYS], 0, n, h->d_perm, h->d_logw_acc,
-                                  h->d_logw, h->d_maxpart, h->d_fix_count, nseg, segcap, h->d_fix_over);
+            hipExtLaunchKernelGGL(mcl::k_combine_logw, dim3(mcl::kRedBlocks), dim3(256), 0, h->stream, nullptr, h->ev[EV_RAYS], 0, n, h->d_perm.p, h->d_logw_acc.p,
+                                  h->d_logw.p, h->d_maxpart.p, h->d_fix_count.p, nseg, segcap, h->d_fix_over);
             h->ev_rays_bound = true;               // (the stage's last kernel: EV_RAYS is its stop event)
             h->max_partials_ready = true;
         } else {
@@ -547,7 +505,6 @@ int launch_rays(mcl_engine *h, const double *x, const double *y, const double *t
             HIPCHK(h, hipStreamSynchronize(h->stream));
             HIPCHK(h, hipMemcpy(hd.data(), d_dbg, hd.size() * 8, hipMemcpyDeviceToHost));
             if (FILE *f = fopen(dbgpath, "wb")) { fwrite(hd.data(), 8, hd.size(), f); fclose(f); }
-            (void)hipFree(d_dbg);
         }
         h->last_quad = true;
     } else if (count) {
@@ -611,7 +568,7 @@ int sensor_and_weights(mcl_engine *h, const double *d_global_max, bool defer_sum
         if (!h->cfg.keep_ray_steps) return fail(h, MCL_ERR_UNSUPPORTED, "weight_mode PRODUCT needs keep_ray_steps");
         int64_t n = h->N;
         hipLaunchKernelGGL(mcl::k_product_weights, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->P > 255 ? (const uint8_t *)nullptr : h->d_steps,
-                           h->P > 255 ? reinterpret_cast<const uint16_t *>(h->d_steps) : (const uint16_t *)nullptr, h->d_obs_idx, n, h->B, h->d_table, h->P + 1, 1.0 / h->cfg.squash_factor, h->d_w);
+                           h->P > 255 ? reinterpret_cast<const uint16_t *>(h->d_steps.p) : (const uint16_t *)nullptr, h->d_obs_idx, n, h->B, h->d_table, h->P + 1, 1.0 / h->cfg.squash_factor, h->d_w);
         HIPCHK(h, hipGetLastError());
         return weight_stats(h, false, nullptr, defer_sums);
     }
@@ -652,17 +609,9 @@ int kld_alloc(mcl_engine *h)
     if (!h->kld_on || !h->have_map) return MCL_OK;
     const size_t words = (size_t)((h->kld_bits + 31) / 32);
     const size_t list = (size_t)std::min<uint64_t>((uint64_t)h->cap, h->kld_bits);
-    if (words > h->kld_bm_words) {
-        dfree(h->d_kld_bm); h->kld_bm_words = 0;
-        HIPCHK(h, hipMalloc(&h->d_kld_bm, words * sizeof(uint32_t)));
-        h->kld_bm_words = words;
-    }
-    if (list > h->kld_list_cap) {
-        dfree(h->d_kld_list); h->kld_list_cap = 0;
-        HIPCHK(h, hipMalloc(&h->d_kld_list, list * sizeof(uint32_t)));
-        h->kld_list_cap = list;
-    }
-    if (!h->d_kld_cnt) HIPCHK(h, hipMalloc(&h->d_kld_cnt, 2 * sizeof(unsigned int)));
+    MCL_TRY(h->d_kld_bm.reserve(h, words));
+    MCL_TRY(h->d_kld_list.reserve(h, list));
+    MCL_TRY(h->d_kld_cnt.reserve(h, 2));
     HIPCHK(h, hipMemsetAsync(h->d_kld_bm, 0, words * sizeof(uint32_t), h->stream));
     HIPCHK(h, hipMemsetAsync(h->d_kld_cnt, 0, 2 * sizeof(unsigned int), h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -715,20 +664,19 @@ int lf_build(mcl_engine *h)
     while (reach > 0 && (reach - 1) * (reach - 1) >= K) --reach;
     lf_table(h->cfg, h->lf, h->res, K, h->lf_tab);
     h->lf_K = -1;                                                         // until both buffers hold this map's
-    dfree(h->d_lf_D); dfree(h->d_lf_tab);
+    h->d_lf_D.drop(); h->d_lf_tab.drop();
     const size_t cells = (size_t)h->W * h->H;
-    HIPCHK(h, hipMalloc(&h->d_lf_D, cells * sizeof(uint16_t)));
-    HIPCHK(h, hipMalloc(&h->d_lf_tab, h->lf_tab.size() * sizeof(float)));
-    uint16_t *d_g = nullptr;
-    HIPCHK(h, hipMalloc(&d_g, cells * sizeof(uint16_t)));
+    MCL_TRY(h->d_lf_D.reserve(h, cells));
+    MCL_TRY(h->d_lf_tab.reserve(h, h->lf_tab.size()));
+    DevBuf<uint16_t> d_g;
+    MCL_TRY(d_g.reserve(h, cells));
     const dim3 grid((unsigned)((cells + 255) / 256));
-    hipLaunchKernelGGL(mcl::k_lf_cols, grid, dim3(256), 0, h->stream, h->d_grid, h->W, h->H, reach, d_g);
-    hipLaunchKernelGGL(mcl::k_lf_rows, grid, dim3(256), 0, h->stream, d_g, h->W, h->H, reach, K, h->d_lf_D);
+    hipLaunchKernelGGL(mcl::k_lf_cols, grid, dim3(256), 0, h->stream, h->d_grid, h->W, h->H, reach, d_g.p);
+    hipLaunchKernelGGL(mcl::k_lf_rows, grid, dim3(256), 0, h->stream, d_g.p, h->W, h->H, reach, K, h->d_lf_D);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess)
         e = hipMemcpyAsync(h->d_lf_tab, h->lf_tab.data(), h->lf_tab.size() * sizeof(float), hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(d_g);
     if (e != hipSuccess) return fail(h, MCL_ERR_HIP, std::string("building the likelihood field: ") + hipGetErrorString(e));
     h->lf_K = K;
     return MCL_OK;
@@ -738,14 +686,8 @@ int lf_build(mcl_engine *h)
 // EV_QUERY / EV_K0 .. EV_K1 bracket the kernel (stage 3 and mcl_get_ray_kernel_ms).
 int launch_lfield(mcl_engine *h, const float *obs, int stride, int64_t n)
 {
-    if (h->lf_beams_cap < h->B) {
-        if (h->h_lf_beams) { (void)hipHostFree(h->h_lf_beams); h->h_lf_beams = nullptr; }
-        dfree(h->d_lf_beams);
-        h->lf_beams_cap = 0;
-        HIPCHK(h, hipHostMalloc(&h->h_lf_beams, (size_t)h->B * sizeof(double2)));
-        HIPCHK(h, hipMalloc(&h->d_lf_beams, (size_t)h->B * sizeof(double2)));
-        h->lf_beams_cap = h->B;
-    }
+    MCL_TRY(h->h_lf_beams.reserve(h, (size_t)h->B));
+    MCL_TRY(h->d_lf_beams.reserve(h, (size_t)h->B));
     const int nb = mcl_host::lf_used_beams(h, obs, stride, h->h_lf_beams);
     if (nb > 0)
         HIPCHK(h, hipMemcpyAsync(h->d_lf_beams, h->h_lf_beams, (size_t)nb * sizeof(double2), hipMemcpyHostToDevice, h->stream));
@@ -790,6 +732,17 @@ void mcl_host::graph_reset(mcl_engine *h)
     h->pc_ready = false;                    // whatever changed (map, beams, particles, a buffer): the ray stage makes its own constants
 }
 
+// mcl_update is not refused on an engine with a communicator or in a group, so such an engine can hold a captured graph too: a spine
+// that moves drops the graphs for every caller.  The stream is idle before its memory goes.
+int mcl_host::reserve_scan_spine(mcl_engine *h, int64_t n)
+{
+    const size_t need = (size_t)n / mcl::kScanTile + 2;
+    if (need <= h->d_blocktot.cap) return MCL_OK;
+    graph_reset(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return h->d_blocktot.reserve(h, need);
+}
+
 int mcl_host::scan_weights(mcl_engine *h, const uint64_t *d_q, uint64_t *d_cdf, int64_t n, uint64_t offset, uint64_t *d_total)
 {
     int nb = (int)((n + mcl::kScanTile - 1) / mcl::kScanTile);
@@ -808,15 +761,13 @@ int mcl_host::scan_weights(mcl_engine *h, const uint64_t *d_q, uint64_t *d_cdf, 
                        fold ? h->d_part : (const double *)nullptr, mcl::kRedBlocks, h->d_scalars);
     if (fold) h->sums_pending = false;
     const size_t nlead = (size_t)((n + 15) >> mcl::kLeaderShift) + 1;
-    if (nlead > h->leaders_capacity) {
+    if (nlead > h->d_leaders.cap) {
         graph_reset(h);                    // a captured update graph holds the old pointer
-        dfree(h->d_leaders);
-        HIPCHK(h, hipMalloc(&h->d_leaders, nlead * 8));
-        h->leaders_capacity = nlead;
+        MCL_TRY(h->d_leaders.reserve(h, nlead));
     }
     if (h->bind_sensor_event && own && !h->capturing) {          // the update's last kernel: EV_SENSOR is its stop event
-        hipExtLaunchKernelGGL(mcl::k_scan_final, dim3(nb), dim3(mcl::kScanThreads), 0, h->stream, nullptr, h->ev[EV_SENSOR], 0, d_q, n, h->d_blocktot, d_cdf,
-                              h->d_leaders, co);
+        hipExtLaunchKernelGGL(mcl::k_scan_final, dim3(nb), dim3(mcl::kScanThreads), 0, h->stream, nullptr, h->ev[EV_SENSOR], 0, d_q, n, h->d_blocktot.p, d_cdf,
+                              h->d_leaders.p, co);
         h->ev_sensor_bound = true; h->bind_sensor_event = false;
     } else {
         hipLaunchKernelGGL(mcl::k_scan_final, dim3(nb), dim3(mcl::kScanThreads), 0, h->stream, d_q, n, h->d_blocktot, d_cdf, h->d_leaders, co);
@@ -929,63 +880,63 @@ int mcl_create(const mcl_config_t *cfg, mcl_engine_t **out)
     CRT(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
     CRT(hipEventCreateWithFlags(&h->ev_obs, hipEventDisableTiming));
     for (int i = 0; i < EV_COUNT; ++i) CRT(hipEventCreate(&h->ev[i]));
-    const size_t nb = (size_t)h->cap * sizeof(double);
+#define CRB(buf, n) do { if ((buf).reserve(h, (n))) return bail(#buf); } while (0)
+    const size_t cap = (size_t)h->cap;
     for (int b = 0; b < 2; ++b) {
-        CRT(hipMalloc(&h->d_x[b], nb)); CRT(hipMalloc(&h->d_y[b], nb)); CRT(hipMalloc(&h->d_th[b], nb));
-        CRT(hipMalloc(&h->d_pack[b], (size_t)h->cap * sizeof(double4)));
+        CRB(h->d_x[b], cap); CRB(h->d_y[b], cap); CRB(h->d_th[b], cap);
+        CRB(h->d_pack[b], cap);
     }
-    CRT(hipMalloc(&h->d_w, nb)); CRT(hipMalloc(&h->d_logw, nb)); CRT(hipMalloc(&h->d_tmp, nb * 3));
-    CRT(hipMalloc(&h->d_logw_acc, nb));
-    CRT(hipMalloc(&h->d_carry[0], nb)); CRT(hipMalloc(&h->d_carry[1], nb));
-    CRT(hipMalloc(&h->d_q, (size_t)h->cap * 8)); CRT(hipMalloc(&h->d_cdf, (size_t)h->cap * 8));
-    h->blocktot_capacity = (size_t)h->cap / mcl::kScanTile + 2;
-    CRT(hipMalloc(&h->d_blocktot, h->blocktot_capacity * 8));
-    CRT(hipMalloc(&h->d_blockcnt, h->blocktot_capacity * 4));
+    CRB(h->d_w, cap); CRB(h->d_logw, cap); CRB(h->d_tmp, cap * 3);
+    CRB(h->d_logw_acc, cap);
+    CRB(h->d_carry[0], cap); CRB(h->d_carry[1], cap);
+    CRB(h->d_q, cap); CRB(h->d_cdf, cap);
+    CRB(h->d_blocktot, cap / mcl::kScanTile + 2);
+    CRB(h->d_blockcnt, cap / mcl::kScanTile + 2);
     h->compact_cap = std::max<int64_t>(4096, ((h->cap / 4 + 63) / 64) * 64);
-    CRT(hipMalloc(&h->d_ccdf, (size_t)h->compact_cap * 8));
-    CRT(hipMalloc(&h->d_ctop, ((size_t)h->compact_cap / 64 + 1) * 8));
-    CRT(hipMalloc(&h->d_cidx, (size_t)h->compact_cap * 4));
-    CRT(hipMalloc(&h->d_crec, (size_t)h->compact_cap * sizeof(double4)));
-    CRT(hipMalloc(&h->d_idx, (size_t)h->cap * 4));
-    CRT(hipMalloc(&h->d_part, (size_t)mcl::kRedBlocks * 8 * sizeof(double)));
-    CRT(hipMalloc(&h->d_maxpart, (size_t)mcl::kRedBlocks * sizeof(double)));
-    CRT(hipMalloc(&h->d_result, 32 * 8));
+    CRB(h->d_ccdf, (size_t)h->compact_cap);
+    CRB(h->d_ctop, (size_t)h->compact_cap / 64 + 1);
+    CRB(h->d_cidx, (size_t)h->compact_cap);
+    CRB(h->d_crec, (size_t)h->compact_cap);
+    CRB(h->d_idx, cap);
+    CRB(h->d_part, (size_t)mcl::kRedBlocks * 8);
+    CRB(h->d_maxpart, (size_t)mcl::kRedBlocks);
+    CRB(h->d_result, 32);
     CRT(hipMemset(h->d_result, 0, 32 * 8));
-    CRT(hipHostMalloc(&h->h_result, 48 * 8));
+    CRB(h->h_result, 48);
     std::memset(h->h_result, 0, 48 * 8);
-    h->d_scalars = reinterpret_cast<double *>(h->d_result);
+    h->d_scalars = reinterpret_cast<double *>(h->d_result.p);
     h->d_counters = h->d_result + 8;
     h->d_fix_over = h->d_result + 12;
-    CRT(hipMalloc(&h->d_exact_list, (size_t)kExactCap * 8));
-    CRT(hipMalloc(&h->d_inject, nb * 4));
-    CRT(hipMalloc(&h->d_pc, (size_t)h->cap * sizeof(double4)));
-    CRT(hipMalloc(&h->d_qr, (size_t)h->cap * sizeof(short4)));
-    CRT(hipMalloc(&h->d_far, (size_t)h->cap * 4));
-    CRT(hipMalloc(&h->d_pcs, (size_t)h->cap * sizeof(double4)));
-    CRT(hipMalloc(&h->d_ths, (size_t)h->cap * sizeof(double)));
-    CRT(hipMalloc(&h->d_perm, (size_t)h->cap * 4));
-    CRT(hipMalloc(&h->d_skey, (size_t)h->cap * 4));
-    CRT(hipMalloc(&h->d_srank, (size_t)h->cap * 4));
-    CRT(hipMalloc(&h->d_hist, (size_t)mcl::kSortBuckets * 4));
-    CRT(hipMalloc(&h->d_histpart, (size_t)(mcl::kSortKeySpace / mcl::kHistTile) * 4));
-    CRT(hipMalloc(&h->d_tile_used, (size_t)(mcl::kSortKeySpace / mcl::kHistTile) * 4));
+    CRB(h->d_exact_list, (size_t)kExactCap);
+    CRB(h->d_inject, cap * 4);
+    CRB(h->d_pc, cap);
+    CRB(h->d_qr, cap);
+    CRB(h->d_far, cap * 4);
+    CRB(h->d_pcs, cap);
+    CRB(h->d_ths, cap);
+    CRB(h->d_perm, cap);
+    CRB(h->d_skey, cap);
+    CRB(h->d_srank, cap);
+    CRB(h->d_hist, (size_t)mcl::kSortBuckets);
+    CRB(h->d_histpart, (size_t)(mcl::kSortKeySpace / mcl::kHistTile));
+    CRB(h->d_tile_used, (size_t)(mcl::kSortKeySpace / mcl::kHistTile));
     CRT(hipMemset(h->d_hist, 0, (size_t)mcl::kSortBuckets * 4));          // kept all-zero between sorts (k_hist_clear)
     CRT(hipMemset(h->d_tile_used, 0, (size_t)(mcl::kSortKeySpace / mcl::kHistTile) * 4));
-    CRT(hipMalloc(&h->d_bbox, 8 * sizeof(int)));
-    CRT(hipMalloc(&h->d_bbox_nx, 8 * sizeof(int)));
-    CRT(hipMalloc(&h->d_tilemap_nx, (size_t)mcl::kSortMaxTiles * sizeof(int)));
-    CRT(hipMalloc(&h->d_tilemark_nx, (size_t)mcl::kSortMaxTiles * sizeof(int)));
+    CRB(h->d_bbox, 8);
+    CRB(h->d_bbox_nx, 8);
+    CRB(h->d_tilemap_nx, (size_t)mcl::kSortMaxTiles);
+    CRB(h->d_tilemark_nx, (size_t)mcl::kSortMaxTiles);
     CRT(hipMemset(h->d_tilemark_nx, 0, (size_t)mcl::kSortMaxTiles * sizeof(int)));
     CRT(hipEventCreateWithFlags(&h->ev_children, hipEventDisableTiming));
     CRT(hipEventCreateWithFlags(&h->ev_layout, hipEventDisableTiming));
     CRT(hipEventCreateWithFlags(&h->ev_ext_in, hipEventDisableTiming));
     CRT(hipEventCreateWithFlags(&h->ev_ext_out, hipEventDisableTiming));
-    CRT(hipMalloc(&h->d_cut_start, (size_t)mcl::kSwMaxCuts * sizeof(uint32_t)));
-    CRT(hipMalloc(&h->d_cut_end, (size_t)mcl::kSwMaxCuts * sizeof(uint32_t)));
+    CRB(h->d_cut_start, (size_t)mcl::kSwMaxCuts);
+    CRB(h->d_cut_end, (size_t)mcl::kSwMaxCuts);
     CRT(hipMemset(h->d_cut_start, 0, (size_t)mcl::kSwMaxCuts * sizeof(uint32_t)));
     CRT(hipMemset(h->d_cut_end, 0, (size_t)mcl::kSwMaxCuts * sizeof(uint32_t)));
-    CRT(hipMalloc(&h->d_tilemap, (size_t)mcl::kSortMaxTiles * sizeof(int)));
-    CRT(hipMalloc(&h->d_tilemark, (size_t)mcl::kSortMaxTiles * sizeof(int)));
+    CRB(h->d_tilemap, (size_t)mcl::kSortMaxTiles);
+    CRB(h->d_tilemark, (size_t)mcl::kSortMaxTiles);
     CRT(hipMemset(h->d_tilemark, 0, (size_t)mcl::kSortMaxTiles * sizeof(int)));
     CRT(hipMemset(h->d_fix_over, 0, 16));
     CRT(hipMemset(h->d_scalars, 0, 8 * sizeof(double)));
@@ -1050,6 +1001,7 @@ int mcl_create(const mcl_config_t *cfg, mcl_engine_t **out)
                             static_lds_is(reinterpret_cast<const void *>(&mcl::k_rays_skip<4, false>), 0);
         (void)hipGetLastError();
     }
+#undef CRB
 #undef CRT
     *out = h;
     return MCL_OK;
@@ -1059,25 +1011,14 @@ void mcl_destroy(mcl_engine_t *h)
 {
     if (!h) return;
     (void)hipSetDevice(h->cfg.device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);           // both, before anything is released
+    if (h->stream2) (void)hipStreamSynchronize(h->stream2);
     if (h->comm) { comm_free(h->comm); h->comm = nullptr; }
     if (h->clu) { cluster_free(h->clu); h->clu = nullptr; }
     if (h->qry) { query_free(h->qry); h->qry = nullptr; }
     if (h->srch) { search_free(h->srch); h->srch = nullptr; }
     if (h->rfn) { refine_free(h->rfn); h->rfn = nullptr; }
     graph_reset(h);
-    for (int b = 0; b < 2; ++b) { dfree(h->d_x[b]); dfree(h->d_y[b]); dfree(h->d_th[b]); }
-    dfree(h->d_w); dfree(h->d_logw); dfree(h->d_tmp); dfree(h->d_logw_acc); dfree(h->d_carry[0]); dfree(h->d_carry[1]); dfree(h->d_q); dfree(h->d_cdf); dfree(h->d_blocktot); dfree(h->d_bm); dfree(h->d_bm_pop); dfree(h->d_bm_pref);
-    dfree(h->d_gcdf); dfree(h->d_gtop);
-    dfree(h->d_kld_bm); dfree(h->d_kld_list); dfree(h->d_kld_cnt); dfree(h->d_recov_cnt);
-    dfree(h->d_blockcnt); dfree(h->d_ccdf); dfree(h->d_ctop); dfree(h->d_cidx); dfree(h->d_crec);
-    dfree(h->d_idx); dfree(h->d_steps); dfree(h->d_part); dfree(h->d_maxpart); dfree(h->d_result); if (h->h_result) { (void)hipHostFree(h->h_result); h->h_result = nullptr; } dfree(h->d_inject); dfree(h->d_pc); dfree(h->d_qr); dfree(h->d_far); dfree(h->d_far_list); dfree(h->d_far_sorted); dfree(h->d_far_cnt); dfree(h->d_pcs); dfree(h->d_ths); dfree(h->d_distw); dfree(h->d_distg); dfree(h->d_leaders); dfree(h->d_pack[0]); dfree(h->d_pack[1]); dfree(h->d_perm); dfree(h->d_skey); dfree(h->d_srank); dfree(h->d_skey2); dfree(h->d_sval2); dfree(h->d_sort_tmp); dfree(h->d_hist); dfree(h->d_histpart); dfree(h->d_tile_used); dfree(h->d_bbox); dfree(h->d_cut_start); dfree(h->d_cut_end); dfree(h->d_tilemap); dfree(h->d_tilemark); dfree(h->d_slice_mean); dfree(h->d_fix_list); dfree(h->d_fix_count); dfree(h->d_exact_list);
-    dfree(h->d_grid); dfree(h->d_dist); dfree(h->d_dist4); dfree(h->d_L); dfree(h->d_table);
-    dfree(h->d_lf_D); dfree(h->d_lf_tab); dfree(h->d_lf_beams);
-    if (h->h_lf_beams) (void)hipHostFree(h->h_lf_beams);
-    for (int q = 0; q < 4; ++q) dfree(h->d_distq[q]);
-    dfree(h->d_angle); dfree(h->d_beam_cs); dfree(h->d_beam_csx); dfree(h->d_beam_csxg); dfree(h->d_beam_csi); dfree(h->d_beam_err); dfree(h->d_obs_idx); dfree(h->d_Lt); dfree(h->d_Ltd); dfree(h->d_items); dfree(h->d_centres); dfree(h->d_nitems); dfree(h->d_unit_sums); dfree(h->d_unit_begin); dfree(h->d_nunits); dfree(h->d_obs); dfree(h->d_free);
-    if (h->h_obs) (void)hipHostFree(h->h_obs);
     for (int i = 0; i < EV_COUNT; ++i)
         if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
     if (h->ev_obs) (void)hipEventDestroy(h->ev_obs);
@@ -1085,10 +1026,9 @@ void mcl_destroy(mcl_engine_t *h)
     if (h->ev_layout) (void)hipEventDestroy(h->ev_layout);
     if (h->ev_ext_in) (void)hipEventDestroy(h->ev_ext_in);
     if (h->ev_ext_out) (void)hipEventDestroy(h->ev_ext_out);
-    dfree(h->d_bbox_nx); dfree(h->d_tilemap_nx); dfree(h->d_tilemark_nx);
-    if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); }
+    if (h->stream2) (void)hipStreamDestroy(h->stream2);
     if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;                            // (every buffer goes with it)
 }
 
 int mcl_set_map(mcl_engine_t *h, const int8_t *data, uint32_t width, uint32_t height, float resolution, double origin_x,
@@ -1136,19 +1076,19 @@ int mcl_set_map(mcl_engine_t *h, const int8_t *data, uint32_t width, uint32_t he
     std::vector<uint8_t> dist;
     build_distance_field(data, h->W, h->H, h->Wp, h->Hp, h->Wps, dist);
     h->have_map = false;                 // until every buffer below exists again: a failure leaves "map not set", never dangling pointers
-    dfree(h->d_grid); dfree(h->d_dist); dfree(h->d_dist4); dfree(h->d_L); dfree(h->d_table);
-    for (int q = 0; q < 4; ++q) dfree(h->d_distq[q]);
-    HIPCHK(h, hipMalloc(&h->d_grid, (size_t)h->W * h->H));
-    HIPCHK(h, hipMalloc(&h->d_dist, dist.size()));
-    HIPCHK(h, hipMalloc(&h->d_L, L.size() * sizeof(float)));
-    HIPCHK(h, hipMalloc(&h->d_table, h->table.size() * sizeof(double)));
+    h->d_grid.drop(); h->d_dist.drop(); h->d_dist4.drop(); h->d_L.drop(); h->d_table.drop();     // drop + reserve: the exact size
+    for (int q = 0; q < 4; ++q) h->d_distq[q].drop();
+    MCL_TRY(h->d_grid.reserve(h, (size_t)h->W * h->H));
+    MCL_TRY(h->d_dist.reserve(h, dist.size()));
+    MCL_TRY(h->d_L.reserve(h, L.size()));
+    MCL_TRY(h->d_table.reserve(h, h->table.size()));
     HIPCHK(h, hipMemcpy(h->d_grid, data, (size_t)h->W * h->H, hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(h->d_dist, dist.data(), dist.size(), hipMemcpyHostToDevice));
     {
         std::vector<uint8_t> d4(dist.size() / 2);          // Wps is a multiple of 8
         for (size_t k = 0; k < d4.size(); ++k)
             d4[k] = (uint8_t)(std::min<int>(dist[2 * k], 15) | (std::min<int>(dist[2 * k + 1], 15) << 4));
-        HIPCHK(h, hipMalloc(&h->d_dist4, d4.size()));
+        MCL_TRY(h->d_dist4.reserve(h, d4.size()));
         HIPCHK(h, hipMemcpy(h->d_dist4, d4.data(), d4.size(), hipMemcpyHostToDevice));
     }
     if (want_wedges) {
@@ -1156,22 +1096,22 @@ int mcl_set_map(mcl_engine_t *h, const int8_t *data, uint32_t width, uint32_t he
         std::vector<uint8_t> dq;
         for (int q = 0; q < 4; ++q) {
             build_directional_field(data, h->W, h->H, h->Wp, h->Hp, h->Wps, qsx[q], qsy[q], dq);
-            HIPCHK(h, hipMalloc(&h->d_distq[q], dq.size()));
+            MCL_TRY(h->d_distq[q].reserve(h, dq.size()));
             HIPCHK(h, hipMemcpy(h->d_distq[q], dq.data(), dq.size(), hipMemcpyHostToDevice));
         }
     }
-    dfree(h->d_distw); dfree(h->d_distg);
+    h->d_distw.drop(); h->d_distg.drop();
     if (want_wedges) {
         // wedge fields for k_rays_cell (mcl_wedge.h), built on the device from the isotropic field's stop cells
         const size_t fsz = (size_t)h->Hp * h->Wps, ncell = (size_t)h->Hp * h->Wp;
-        int32_t *d_nxt = nullptr, *d_prv = nullptr;
-        mcl::WedgeRow *d_rows = nullptr;
+        DevBuf<int32_t> d_nxt, d_prv;
+        DevBuf<mcl::WedgeRow> d_rows;
         std::vector<mcl::WedgeRow> rows(2 * mcl::kWedgeR + 1);
-        HIPCHK(h, hipMalloc(&h->d_distw, fsz * mcl::kWedges));
+        MCL_TRY(h->d_distw.reserve(h, fsz * mcl::kWedges));
         HIPCHK(h, hipMemsetAsync(h->d_distw, 0, fsz * mcl::kWedges, h->stream));   // same stream as the kernels that fill it
-        HIPCHK(h, hipMalloc(&d_nxt, ncell * 4));
-        HIPCHK(h, hipMalloc(&d_prv, ncell * 4));
-        HIPCHK(h, hipMalloc(&d_rows, rows.size() * sizeof(mcl::WedgeRow)));
+        MCL_TRY(d_nxt.reserve(h, ncell));
+        MCL_TRY(d_prv.reserve(h, ncell));
+        MCL_TRY(d_rows.reserve(h, rows.size()));
         hipLaunchKernelGGL(mcl::k_row_tables, dim3((h->Hp + 63) / 64), dim3(64), 0, h->stream, h->d_dist, h->Wp, h->Hp, h->Wps, d_nxt, d_prv);
         int rc_w = MCL_OK;
         for (int k = 0; k < mcl::kWedges && rc_w == MCL_OK; ++k) {
@@ -1182,7 +1122,6 @@ int mcl_set_map(mcl_engine_t *h, const int8_t *data, uint32_t width, uint32_t he
                                d_rows, h->d_distw + (size_t)k * fsz);
             if (hipStreamSynchronize(h->stream) != hipSuccess) rc_w = MCL_ERR_HIP;   // rows[] is reused by the next wedge
         }
-        (void)hipFree(d_nxt); (void)hipFree(d_prv); (void)hipFree(d_rows);
         if (rc_w != MCL_OK) return fail(h, rc_w, "building the wedge fields failed");
         if (h->sweep_global) {
             // the copies k_rays_sweep<.., GLOBAL> probes: every field mirrored for its quadrant, with a two-cell ring of stop bytes
@@ -1196,7 +1135,7 @@ int mcl_set_map(mcl_engine_t *h, const int8_t *data, uint32_t width, uint32_t he
             } else {
                 h->distg_pitch = gl.pitch;
                 h->distg_stride = gl.stride;
-                HIPCHK(h, hipMalloc(&h->d_distg, gl.alloc));
+                MCL_TRY(h->d_distg.reserve(h, gl.alloc));
                 HIPCHK(h, hipMemsetAsync(h->d_distg, 0xFF, gl.alloc, h->stream));
                 for (int k = 0; k < mcl::kWedges; ++k) {
                     const int q = k >> mcl::kWedgeShift;
@@ -1211,15 +1150,15 @@ int mcl_set_map(mcl_engine_t *h, const int8_t *data, uint32_t width, uint32_t he
     }
     HIPCHK(h, hipMemcpy(h->d_L, L.data(), L.size() * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(h->d_table, h->table.data(), h->table.size() * sizeof(double), hipMemcpyHostToDevice));
-    h->lt_capacity = 0; dfree(h->d_Lt); h->ltd_capacity = 0; dfree(h->d_Ltd); h->ltd_ready = false;
+    h->d_Lt.drop(); h->d_Ltd.drop(); h->ltd_ready = false;
     {   // free-space list for initialize_global (cpp:199-213, 411-421): row-major order of data == 0
         std::vector<uint32_t> fr;
         for (size_t i = 0; i < (size_t)h->W * h->H; ++i)
             if (data[i] == 0) fr.push_back((uint32_t)i);
-        dfree(h->d_free);
+        h->d_free.drop();
         h->n_free = fr.size();
         if (h->n_free) {
-            HIPCHK(h, hipMalloc(&h->d_free, fr.size() * sizeof(uint32_t)));
+            MCL_TRY(h->d_free.reserve(h, fr.size()));
             HIPCHK(h, hipMemcpy(h->d_free, fr.data(), fr.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         }
     }
@@ -1310,8 +1249,8 @@ int mcl_set_beam_angles(mcl_engine_t *h, const float *angles, int32_t n_beams)
         csx[i] = make_double2(std::cos(a), std::sin(a));
         csxg[i] = make_double2(std::cos(ac), std::sin(ac));
     }
-    dfree(h->d_angle); dfree(h->d_beam_cs); dfree(h->d_beam_csx); dfree(h->d_beam_csxg); dfree(h->d_obs_idx); dfree(h->d_obs);
-    dfree(h->d_beam_csi); dfree(h->d_beam_err);
+    h->d_angle.drop(); h->d_beam_cs.drop(); h->d_beam_csx.drop(); h->d_beam_csxg.drop(); h->d_obs_idx.drop(); h->d_obs.drop();
+    h->d_beam_csi.drop(); h->d_beam_err.drop();
     h->rec_ok = false;
     if (h->beam_margin > 0 && !getenv("MCL_SWEEP_NO_REC")) {
         // REC: the walk turns the direction by the grid increment instead of fetching it (mcl_rays_sweep.h).  Every beam must lie
@@ -1329,27 +1268,27 @@ int mcl_set_beam_angles(mcl_engine_t *h, const float *angles, int32_t n_beams)
             if (j >= 0 && j < n_beams && i < ecols) { err[i] = (double)angles[j] - ag; worst = std::max(worst, std::fabs(err[i])); }
         }
         if (worst <= 2e-6 && ncsx <= ecols + 8) {
-            HIPCHK(h, hipMalloc(&h->d_beam_csi, (size_t)ncsx * sizeof(double2)));
+            MCL_TRY(h->d_beam_csi.reserve(h, (size_t)ncsx));
             HIPCHK(h, hipMemcpy(h->d_beam_csi, csi.data(), (size_t)ncsx * sizeof(double2), hipMemcpyHostToDevice));
-            HIPCHK(h, hipMalloc(&h->d_beam_err, (size_t)ecols * sizeof(double)));
+            MCL_TRY(h->d_beam_err.reserve(h, (size_t)ecols));
             HIPCHK(h, hipMemcpy(h->d_beam_err, err.data(), (size_t)ecols * sizeof(double), hipMemcpyHostToDevice));
             h->rec_c = std::cos(inc); h->rec_s = std::sin(inc);
             h->rec_ok = true;
         }
     }
-    if (h->h_obs) { (void)hipHostFree(h->h_obs); h->h_obs = nullptr; }
-    HIPCHK(h, hipMalloc(&h->d_obs, (size_t)n_beams * sizeof(float)));
-    HIPCHK(h, hipHostMalloc(&h->h_obs, (size_t)n_beams * sizeof(float)));
-    HIPCHK(h, hipMalloc(&h->d_angle, (size_t)n_beams * sizeof(float)));
-    HIPCHK(h, hipMalloc(&h->d_beam_cs, (size_t)ncs * sizeof(double2)));
-    HIPCHK(h, hipMalloc(&h->d_obs_idx, (size_t)n_beams * sizeof(int32_t)));
+    h->h_obs.drop();
+    MCL_TRY(h->d_obs.reserve(h, (size_t)n_beams));
+    MCL_TRY(h->h_obs.reserve(h, (size_t)n_beams));
+    MCL_TRY(h->d_angle.reserve(h, (size_t)n_beams));
+    MCL_TRY(h->d_beam_cs.reserve(h, (size_t)ncs));
+    MCL_TRY(h->d_obs_idx.reserve(h, (size_t)n_beams));
     HIPCHK(h, hipMemcpy(h->d_angle, angles, (size_t)n_beams * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(h->d_beam_cs, cs.data(), (size_t)ncs * sizeof(double2), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMalloc(&h->d_beam_csx, (size_t)ncsx * sizeof(double2)));
+    MCL_TRY(h->d_beam_csx.reserve(h, (size_t)ncsx));
     HIPCHK(h, hipMemcpy(h->d_beam_csx, csx.data(), (size_t)ncsx * sizeof(double2), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMalloc(&h->d_beam_csxg, (size_t)ncsx * sizeof(double2)));
+    MCL_TRY(h->d_beam_csxg.reserve(h, (size_t)ncsx));
     HIPCHK(h, hipMemcpy(h->d_beam_csxg, csxg.data(), (size_t)ncsx * sizeof(double2), hipMemcpyHostToDevice));
-    h->lt_capacity = 0; dfree(h->d_Lt); h->ltd_capacity = 0; dfree(h->d_Ltd); h->ltd_ready = false;
+    h->d_Lt.drop(); h->d_Ltd.drop(); h->ltd_ready = false;
     h->B = n_beams;
     return MCL_OK;
 }
@@ -1541,7 +1480,7 @@ static void resample_ray_extras(mcl_engine *h, int64_t n, mcl::ResampleArgs &a, 
     const int rmode = choose_ray_mode(h, n, false);
     if (!(rmode == 2 || rmode >= 4)) return;
     a.pc_out = h->d_pc; a.ox = h->ox; a.oy = h->oy; a.res = h->res;
-    if (rmode >= 4) { a.clr_logw_acc = h->d_logw_acc; a.clr_far_flags = reinterpret_cast<uint32_t *>(h->d_far); }
+    if (rmode >= 4) { a.clr_logw_acc = h->d_logw_acc; a.clr_far_flags = reinterpret_cast<uint32_t *>(h->d_far.p); }
     h->pc_ready = true;
     // The ordering of the ray stage works from the layout (bounding box, occupied tiles) of the PREVIOUS update's children
     // when there is one: the set moves by a cell or so per update and the order only decides which rays share a wave.
@@ -2262,17 +2201,16 @@ int mcl_init_particles_mixture(mcl_engine_t *h, int32_t n_components, const doub
     }
     if (sum != n_total) return fail(h, MCL_ERR_INVALID_ARG, "mixture init: the counts must add up to n_total");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    mcl::MixComponent *d_comp = nullptr;
-    HIPCHK(h, hipMalloc(&d_comp, comp.size() * sizeof(mcl::MixComponent)));
+    DevBuf<mcl::MixComponent> d_comp;
+    MCL_TRY(d_comp.reserve(h, comp.size()));
     int rc = MCL_OK;
     if (hipMemcpy(d_comp, comp.data(), comp.size() * sizeof(mcl::MixComponent), hipMemcpyHostToDevice) != hipSuccess) rc = MCL_ERR_HIP;
     if (rc == MCL_OK) {
         const int c = h->cur;
         hipLaunchKernelGGL(mcl::k_init_mixture, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, d_comp, n_components, n,
                            first_global_index, (uint32_t)h->cfg.seed, (uint32_t)(h->cfg.seed >> 32), h->init_idx, h->d_x[c], h->d_y[c], h->d_th[c]);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) rc = MCL_ERR_HIP;   // (d_comp is freed below)
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) rc = MCL_ERR_HIP;
     }
-    (void)hipFree(d_comp);
     if (rc != MCL_OK) return fail(h, rc, "mixture init: uploading the components or the draw failed");
     return finish_init(h, n, n_total);
 }
@@ -2292,7 +2230,7 @@ int mcl_set_recovery(mcl_engine_t *h, const mcl_recovery_config_t *c)
     if (const char *why = recov_invalid(c)) return fail(h, MCL_ERR_INVALID_ARG, why);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (!h->d_recov_cnt) {
-        HIPCHK(h, hipMalloc(&h->d_recov_cnt, 2 * sizeof(unsigned int)));
+        MCL_TRY(h->d_recov_cnt.reserve(h, 2));
         HIPCHK(h, hipMemsetAsync(h->d_recov_cnt, 0, 2 * sizeof(unsigned int), h->stream));
     }
     h->recov = *c;
@@ -2464,21 +2402,10 @@ int mcl_stage_distinct_parents(mcl_engine_t *h, const int32_t *d_parent, int64_t
     if (n_total > MCL_MAX_TOTAL_PARTICLES) return fail(h, MCL_ERR_INVALID_ARG, "n_total exceeds MCL_MAX_TOTAL_PARTICLES");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const int64_t nwords = (n_total + 31) / 32;
-    if ((size_t)nwords > h->bm_capacity) {
-        dfree(h->d_bm); dfree(h->d_bm_pop); dfree(h->d_bm_pref);
-        h->bm_capacity = 0;
-        HIPCHK(h, hipMalloc(&h->d_bm, (size_t)nwords * 4));
-        HIPCHK(h, hipMalloc(&h->d_bm_pop, (size_t)nwords * 8));
-        HIPCHK(h, hipMalloc(&h->d_bm_pref, (size_t)nwords * 8));
-        h->bm_capacity = (size_t)nwords;
-    }
-    size_t need = (size_t)nwords / mcl::kScanTile + 2;
-    if (need > h->blocktot_capacity) {
-        graph_reset(h);
-        dfree(h->d_blocktot);
-        HIPCHK(h, hipMalloc(&h->d_blocktot, need * 8));
-        h->blocktot_capacity = need;
-    }
+    MCL_TRY(h->d_bm.reserve(h, (size_t)nwords));
+    MCL_TRY(h->d_bm_pop.reserve(h, (size_t)nwords));
+    MCL_TRY(h->d_bm_pref.reserve(h, (size_t)nwords));
+    MCL_TRY(reserve_scan_spine(h, nwords));
     HIPCHK(h, hipMemsetAsync(h->d_bm, 0, (size_t)nwords * 4, h->stream));
     hipLaunchKernelGGL(mcl::k_bm_mark, dim3((unsigned)((n_children + 255) / 256)), dim3(256), 0, h->stream, d_parent, n_children, n_total, h->d_bm);
     hipLaunchKernelGGL(mcl::k_bm_pop, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, h->stream, h->d_bm, nwords, h->d_bm_pop);
@@ -2677,13 +2604,8 @@ int mcl_host::stage_resample_compact_launch(mcl_engine_t *h, const void *d_chunk
     if (off == 0) return fail(h, MCL_ERR_INVALID_ARG, "the lists carry no weight");
     const size_t total = (size_t)n_shards * (size_t)chunk_entries;
     if (total >= (size_t)MCL_MAX_TOTAL_PARTICLES) return fail(h, MCL_ERR_INVALID_ARG, "gathered lists exceed 2^27 entries");
-    if (total > h->gcdf_capacity) {
-        dfree(h->d_gcdf); dfree(h->d_gtop);
-        h->gcdf_capacity = 0;
-        HIPCHK(h, hipMalloc(&h->d_gcdf, total * 8));
-        HIPCHK(h, hipMalloc(&h->d_gtop, (total / 64 + 1) * 8));
-        h->gcdf_capacity = total;
-    }
+    MCL_TRY(h->d_gcdf.reserve(h, total));
+    MCL_TRY(h->d_gtop.reserve(h, total / 64 + 1));
     m.gcdf = h->d_gcdf; m.gtop = h->d_gtop;
     hipLaunchKernelGGL(mcl::k_compact_merge, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, m);
     HIPCHK(h, hipGetLastError());
@@ -2965,13 +2887,7 @@ int mcl_scan_weights(mcl_engine_t *h, const uint64_t *d_q, uint64_t *d_cdf, int6
 {
     if (!h || !d_q || !d_cdf || n <= 0) return MCL_ERR_INVALID_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    size_t need = (size_t)n / mcl::kScanTile + 2;
-    if (need > h->blocktot_capacity) {   // spine scratch is sized for cap; grow it for gathered arrays
-        graph_reset(h);
-        dfree(h->d_blocktot);
-        HIPCHK(h, hipMalloc(&h->d_blocktot, need * 8));
-        h->blocktot_capacity = need;
-    }
+    MCL_TRY(reserve_scan_spine(h, n));     // (sized for cap at mcl_create; a gathered array may be longer)
     int rc = scan_weights(h, d_q, d_cdf, n, offset, nullptr);
     if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));

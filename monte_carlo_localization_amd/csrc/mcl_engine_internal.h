@@ -11,6 +11,7 @@
 //                    kernels and buffers, called outside the update)
 //   mcl_refine.hip   mcl_refine_poses: the score of a dense window around each seed pose, its best pose, mean and covariance (its
 //                    own kernels and buffers, called outside the update)
+//   mcl_buffers.h    Buf / DevBuf / HostBuf: every device and pinned buffer of the files above owns its memory through these
 // Only mcl_engine.hip includes the kernels (mcl_kernels.h); mcl_comm.hip and mcl_group.hip reach the few kernels they launch
 // through the launch_* functions below.  Every function declared here is defined once, under this name.
 #pragma once
@@ -25,6 +26,7 @@
 
 #include "mcl_types.h"
 #include "mcl_host_math.h"
+#include "mcl_buffers.h"
 
 enum { EV_START = 0, EV_RESAMPLE, EV_QUERY, EV_RAYS, EV_SENSOR, EV_K0, EV_K1, EV_COUNT };   // K0..K1 bracket the dominant kernel
 
@@ -66,37 +68,35 @@ struct mcl_engine {
     int W = 0, H = 0, P = 0, Wp = 0, Hp = 0, Wps = 0, tw_cells = 0;
     double res = 0, ox = 0, oy = 0;
     std::vector<double> table;          // (P+1)^2 column-major (d*(P+1)+r)
-    int8_t *d_grid = nullptr;
-    uint8_t *d_dist = nullptr;
-    uint8_t *d_dist4 = nullptr;         // nibble-packed copy of d_dist (k_rays_skip's LDS window is a straight copy of it)
-    uint8_t *d_distq[4]{};              // directional skip fields, one per quadrant (k_rays_quad / k_rays_far)
-    float *d_L = nullptr;               // [r_obs][d]
-    double *d_table = nullptr;          // double table (product mode)
+    DevBuf<int8_t> d_grid;
+    DevBuf<uint8_t> d_dist;
+    DevBuf<uint8_t> d_dist4;            // nibble-packed copy of d_dist (k_rays_skip's LDS window is a straight copy of it)
+    DevBuf<uint8_t> d_distq[4];         // directional skip fields, one per quadrant (k_rays_quad / k_rays_far)
+    DevBuf<float> d_L;                  // [r_obs][d]
+    DevBuf<double> d_table;             // double table (product mode)
 
     // beams
     int B = 0, bpad = 0;
     std::vector<float> angles;
-    float *d_angle = nullptr;
-    double2 *d_beam_cs = nullptr;
-    double2 *d_beam_csx = nullptr;      // k_rays_sweep's copy with virtual beams either side (set_beam_angles)
-    double2 *d_beam_csxg = nullptr;     // the same for the global-field form: a virtual beam repeats the first / last REAL beam
+    DevBuf<float> d_angle;
+    DevBuf<double2> d_beam_cs;
+    DevBuf<double2> d_beam_csx;         // k_rays_sweep's copy with virtual beams either side (set_beam_angles)
+    DevBuf<double2> d_beam_csxg;        // the same for the global-field form: a virtual beam repeats the first / last REAL beam
     // k_rays_sweep<.., REC> (an evenly spaced scan): directions of the grid angles a0 + j inc, every beam's offset from its grid angle
     // (one entry per table column), cos / sin of the increment; rec_ok: the scan qualifies
-    double2 *d_beam_csi = nullptr;
-    double *d_beam_err = nullptr;
+    DevBuf<double2> d_beam_csi;
+    DevBuf<double> d_beam_err;
     double rec_c = 1.0, rec_s = 0.0;
     bool rec_ok = false;
     int beam_pad = 0, beam_margin = 0;
-    int32_t *d_obs_idx = nullptr;
-    float *d_obs = nullptr;
-    float *h_obs = nullptr;             // pinned staging for the per-update scan
-    uint32_t *d_free = nullptr;         // linear indices of free cells (data == 0), row-major, cpp:199-213
+    DevBuf<int32_t> d_obs_idx;
+    DevBuf<float> d_obs;
+    HostBuf<float> h_obs;               // pinned staging for the per-update scan
+    DevBuf<uint32_t> d_free;            // linear indices of free cells (data == 0), row-major, cpp:199-213
     uint64_t n_free = 0;
     uint32_t init_idx = 0;
-    float *d_Lt = nullptr;
-    size_t lt_capacity = 0;
-    double *d_Ltd = nullptr;            // k_rays_sweep's fp64 table (mcl_rays_sweep.h), built per update when that kernel runs
-    size_t ltd_capacity = 0;
+    DevBuf<float> d_Lt;                 // [Lt | Lt with the rows reversed (k_rays_cell)]
+    DevBuf<double> d_Ltd;               // k_rays_sweep's fp64 table (mcl_rays_sweep.h), built per update when that kernel runs
     int ltd_cols = 0;
     bool ltd_ready = false;             // d_Ltd holds the table of the observation in d_obs_idx (cleared when a new scan is staged)
     bool sweep_layout_ok = false;       // k_rays_sweep's static LDS ends where its raw window offset (kQLdsBase) assumes
@@ -110,7 +110,7 @@ struct mcl_engine {
     bool quad_layout_ok = false, cell_layout_ok = false;   // the same for k_rays_quad / k_rays_cell
     bool skip_layout_ok = false;        // k_rays_skip has no static LDS (its window is addressed from LDS offset 0)
     // k_rays_sweep on the wedge fields in GLOBAL memory (ranges a 256-cell LDS window cannot hold; MCL_SWEEP_GLOBAL=1 forces it)
-    uint8_t *d_distg = nullptr;         // kWedges mirrored fields with a two-cell stop ring and a tail of stop rows each (k_ring_field)
+    DevBuf<uint8_t> d_distg;            // kWedges mirrored fields with a two-cell stop ring and a tail of stop rows each (k_ring_field)
     int distg_pitch = 0;                // row pitch
     size_t distg_stride = 0;            // bytes per field, tail included
     const char *distg_why_not = nullptr;     // why the global-field form of k_rays_sweep is not available for this map, if it is not
@@ -125,15 +125,13 @@ struct mcl_engine {
     bool prep_cache_valid = false, prep_folded = false;
     int64_t prep_cache_n = 0;
     bool max_partials_ready = false;    // k_combine_logw left the per-workgroup maxima of d_logw in d_part
-    int4 *d_items = nullptr;            // k_rays_sweep's work items (guided schedule), planned on the device every update
-    int4 *d_centres = nullptr;          // per run of units: window centre, first unit, units (k_sweep_plan)
-    size_t items_capacity = 0;
-    int *d_nitems = nullptr;            // number of work items (written by k_sweep_plan)
+    DevBuf<int4> d_items;               // k_rays_sweep's work items (guided schedule), planned on the device every update
+    DevBuf<int4> d_centres;             // per run of units: window centre, first unit, units (k_sweep_plan)
+    DevBuf<int> d_nitems;               // number of work items (written by k_sweep_plan)
     int64_t plan_n = 0;
-    double4 *d_unit_sums = nullptr;     // per unit of the sorted order: (sum px, sum py, count, -), bounding box
-    uint32_t *d_unit_begin = nullptr;   // first slot of every unit + one (k_unit_table)
-    int *d_nunits = nullptr;            // number of units of this update's sorted order
-    size_t unit_sums_capacity = 0;
+    DevBuf<double4> d_unit_sums;        // per unit of the sorted order: (sum px, sum py, count, -), bounding box
+    DevBuf<uint32_t> d_unit_begin;      // first slot of every unit + one (k_unit_table)
+    DevBuf<int> d_nunits;               // number of units of this update's sorted order
     // environment knobs, read once at mcl_create (0 / negative = default)
     int64_t env_cell_min = 0, env_cell_slice = 0;
     int env_qslices_per_cu = 0, env_qside = 0, env_sweep_g = 0;
@@ -142,10 +140,10 @@ struct mcl_engine {
     // particles
     int64_t cap = 0, N = 0;
     bool have_particles = false;
-    double *d_x[2]{}, *d_y[2]{}, *d_th[2]{};
+    DevBuf<double> d_x[2], d_y[2], d_th[2];
     int cur = 0;
-    double *d_w = nullptr, *d_logw = nullptr, *d_tmp = nullptr;   // tmp: cap*3 doubles
-    double *d_carry[2]{};               // logw - max of the last update (adaptive resampling: what a kept particle carries)
+    DevBuf<double> d_w, d_logw, d_tmp;   // tmp: cap*3 doubles
+    DevBuf<double> d_carry[2];          // logw - max of the last update (adaptive resampling: what a kept particle carries)
     int carry_idx = 0;                  // d_carry[carry_idx] is current; k_weights writes the other one
     bool carry_valid = false, carry_pending = false;
     bool resampled_last = true;
@@ -153,70 +151,66 @@ struct mcl_engine {
     hipGraphExec_t graph_exec[2] = {nullptr, nullptr};
     bool graph_warm = false;            // a regular update has run since the sizes / map / beams last changed
     bool capturing = false;
-    double *d_logw_acc = nullptr;       // k_rays_quad/far/fix accumulate here with atomics; k_gather_logw copies to d_logw
-    uint64_t *d_q = nullptr, *d_cdf = nullptr, *d_blocktot = nullptr;
-    uint32_t *d_bm = nullptr;           // mcl_stage_distinct_parents: bitmap over the global particle indices, its popcounts and their prefix
-    uint64_t *d_bm_pop = nullptr, *d_bm_pref = nullptr;
-    size_t bm_capacity = 0;
+    DevBuf<double> d_logw_acc;          // k_rays_quad/far/fix accumulate here with atomics; k_gather_logw copies to d_logw
+    DevBuf<uint64_t> d_q, d_cdf;
+    DevBuf<uint64_t> d_blocktot;        // the scan's spine (reserve_scan_spine)
+    DevBuf<uint32_t> d_bm;              // mcl_stage_distinct_parents: bitmap over the global particle indices, its popcounts and their prefix
+    DevBuf<uint64_t> d_bm_pop, d_bm_pref;
     // compact list of the particles with a non-zero fixed-point weight, written by the scan of d_q (mcl::CompactOut)
-    uint32_t *d_blockcnt = nullptr;     // per scan tile (blocktot_capacity entries)
-    uint64_t *d_ccdf = nullptr, *d_ctop = nullptr;
-    uint32_t *d_cidx = nullptr;
-    double4 *d_crec = nullptr;
+    DevBuf<uint32_t> d_blockcnt;        // per scan tile of the engine's own set (sized at mcl_create)
+    DevBuf<uint64_t> d_ccdf, d_ctop;
+    DevBuf<uint32_t> d_cidx;
+    DevBuf<double4> d_crec;
     int64_t compact_cap = 0;            // room in the list (cap / 4, at least 4096)
     int64_t compact_n = -1;             // entries of the list that describes d_cdf / the current particles; -1: none
     bool compact_pending = false;       // the last scan wrote a list; its length arrives with the next result read-back
     bool compact_used = false;          // the last resampling drew from a compact list
-    uint64_t *d_gcdf = nullptr, *d_gtop = nullptr;   // merged CDF of the shards' gathered lists (mcl_stage_resample_compact)
-    size_t gcdf_capacity = 0;
+    DevBuf<uint64_t> d_gcdf, d_gtop; // merged CDF of the shards' gathered lists (mcl_stage_resample_compact)
     int env_no_compact = 0;
-    uint64_t *d_leaders = nullptr;      // last CDF entry of every 16-entry group of the array d_blocktot describes
-    size_t leaders_capacity = 0;
-    double4 *d_pack[2]{};               // (x, y, theta, -) records of buffer 0/1, written by k_resample_motion
+    DevBuf<uint64_t> d_leaders;         // last CDF entry of every 16-entry group of the array d_blocktot describes
+    DevBuf<double4> d_pack[2];          // (x, y, theta, -) records of buffer 0/1, written by k_resample_motion
     bool pack_valid[2] = {false, false};
-    int32_t *d_idx = nullptr;
-    uint8_t *d_steps = nullptr;
-    size_t steps_capacity = 0, blocktot_capacity = 0;
+    DevBuf<int32_t> d_idx;
+    DevBuf<uint8_t> d_steps;
     const uint64_t *blocktot_for = nullptr;   // which CDF array d_blocktot currently describes
     int64_t blocktot_n = 0;
-    double *d_part = nullptr;           // kRedBlocks * 8: per-workgroup partial sums (k_weights)
-    double *d_maxpart = nullptr;        // kRedBlocks: per-workgroup maxima of d_logw (k_combine_logw / k_reduce_max)
+    DevBuf<double> d_part;              // kRedBlocks * 8: per-workgroup partial sums (k_weights)
+    DevBuf<double> d_maxpart;           // kRedBlocks: per-workgroup maxima of d_logw (k_combine_logw / k_reduce_max)
     bool sums_pending = false;          // k_weights left partial sums that the next scan's spine turns into scalars[1..7]
-    double *d_scalars = nullptr;        // 8
+    double *d_scalars = nullptr;        // 8 (a view into d_result, like the next two)
     unsigned long long *d_counters = nullptr;  // 4
-    double *d_inject = nullptr;         // cap*4 (normals + uniforms)
-    double4 *d_pc = nullptr;            // cap: per-particle constants for k_rays_skip / k_rays_quad
-    short4 *d_qr = nullptr;             // cap: per-particle quadrant ranges (k_rays_quad)
+    DevBuf<double> d_inject;            // cap*4 (normals + uniforms)
+    DevBuf<double4> d_pc;               // cap: per-particle constants for k_rays_skip / k_rays_quad
+    DevBuf<short4> d_qr;                // cap: per-particle quadrant ranges (k_rays_quad)
     bool quad_ok = false;               // beam angles monotone over less than a full turn
     int qside = 0;                      // k_rays_quad window side (0: not usable for this map)
-    unsigned long long *d_fix_list = nullptr, *d_fix_count = nullptr, *d_fix_over = nullptr;
-    unsigned long long *d_exact_list = nullptr;   // level-3 rays for k_rays_exact; its counter is word 14 of d_result
-    unsigned long long fix_cap = 0, fix_alloc = 0;
-    size_t fix_count_alloc = 0;
+    DevBuf<unsigned long long> d_fix_list, d_fix_count;      // d_fix_count: 8 words (64 bytes) per segment
+    unsigned long long *d_fix_over = nullptr;
+    DevBuf<unsigned long long> d_exact_list;     // level-3 rays for k_rays_exact; its counter is word 14 of d_result
+    unsigned long long fix_cap = 0;
     int fix_segments = 0;
-    uint8_t *d_far = nullptr;           // cap * 4 flags
-    uint32_t *d_far_list = nullptr;     // k_rays_sweep: slots with a flagged quadrant (cap entries, allocated on first use)
-    uint32_t *d_far_sorted = nullptr, *d_far_cnt = nullptr;   // the same in ascending order (k_far_*), per-2048-slot counts
+    DevBuf<uint8_t> d_far;              // cap * 4 flags
+    DevBuf<uint32_t> d_far_list;        // k_rays_sweep: slots with a flagged quadrant (cap entries, allocated on first use)
+    DevBuf<uint32_t> d_far_sorted, d_far_cnt;   // the same in ascending order (k_far_*), per-2048-slot counts
     // cell sort for k_rays_cell
-    double4 *d_pcs = nullptr;           // cap: pc in sorted order
-    double *d_ths = nullptr;            // cap: heading in sorted order
-    uint8_t *d_distw = nullptr;         // kWedges wedge fields for k_rays_cell, each Hp x Wps bytes
-    uint32_t *d_perm = nullptr, *d_skey = nullptr, *d_srank = nullptr;   // cap each
-    uint32_t *d_skey2 = nullptr, *d_sval2 = nullptr;   // MCL_SORT=radix: sorted keys / indices
-    void *d_sort_tmp = nullptr;
-    size_t sort_tmp_bytes = 0;
+    DevBuf<double4> d_pcs;              // cap: pc in sorted order
+    DevBuf<double> d_ths;               // cap: heading in sorted order
+    DevBuf<uint8_t> d_distw;            // kWedges wedge fields for k_rays_cell, each Hp x Wps bytes
+    DevBuf<uint32_t> d_perm, d_skey, d_srank;   // cap each
+    DevBuf<uint32_t> d_skey2, d_sval2;   // MCL_SORT=radix: sorted keys / indices
+    DevBuf<uint8_t> d_sort_tmp;         // rocPRIM's scratch, in bytes
     int env_sort_radix = -1;           // MCL_SORT=radix / hist forces one ordering path; default: by size
-    uint32_t *d_tile_used = nullptr;    // one mark per kHistTile buckets of the sort histogram: touched by this update's sort
-    uint32_t *d_hist = nullptr, *d_histpart = nullptr;                   // kSortBuckets, kSortBuckets / kHistTile
-    int *d_bbox = nullptr;              // 7: bounding box, occupied tiles, numbering in use, window play
-    uint32_t *d_cut_start = nullptr, *d_cut_end = nullptr;   // kSwMaxCuts each: where the buckets of a sparse set start / end in the radix-sorted order (zero between sorts)
+    DevBuf<uint32_t> d_tile_used;       // one mark per kHistTile buckets of the sort histogram: touched by this update's sort
+    DevBuf<uint32_t> d_hist, d_histpart;                   // kSortBuckets, kSortBuckets / kHistTile
+    DevBuf<int> d_bbox;                 // 7: bounding box, occupied tiles, numbering in use, window play
+    DevBuf<uint32_t> d_cut_start, d_cut_end;   // kSwMaxCuts each: where the buckets of a sparse set start / end in the radix-sorted order (zero between sorts)
     bool env_no_bucket_cuts = false;    // MCL_NO_BUCKET_CUTS: units on the plain grid of 1024 slots, sparse sets ordered by whole tiles (rounds 2-3 before the cuts)
-    int *d_tilemap = nullptr, *d_tilemark = nullptr;   // kSortMaxTiles each: tile of the map -> compact id; marks of the occupied tiles (zero between sorts)
+    DevBuf<int> d_tilemap, d_tilemark;   // kSortMaxTiles each: tile of the map -> compact id; marks of the occupied tiles (zero between sorts)
     // The ordering layout (bounding box, occupied tiles) of an update's children is made on the second stream right after the
     // resampling kernel and used by the NEXT update, whose resampling kernel then writes the sort keys itself: d_bbox / d_tilemap are
     // the layout in use, *_nx the one being made; swapped at the end of an update.  layout_valid: d_bbox describes the previous
     // update's children of this configuration (cleared by graph_reset: map, beams, particles set from outside).
-    int *d_bbox_nx = nullptr, *d_tilemap_nx = nullptr, *d_tilemark_nx = nullptr;
+    DevBuf<int> d_bbox_nx, d_tilemap_nx, d_tilemark_nx;
     hipEvent_t ev_children = nullptr, ev_layout = nullptr;
     hipEvent_t ev_ext_in = nullptr, ev_ext_out = nullptr;   // ordering against a caller's stream (mcl_stream_wait_external / mcl_external_wait_stream)
     bool stage_async_rays = false, stage_async_weights = false;
@@ -237,8 +231,7 @@ struct mcl_engine {
     bool env_comm_no_lists = false;     // MCL_COMM_NO_LISTS: mcl_comm_update takes the dense exchange on every update
     bool env_comm_no_pregather = false; // MCL_COMM_NO_PREGATHER: mcl_comm_update gathers the lists when it starts, not when the previous one ends
     mcl::PrepClear prep_passed{};       // what the resampling kernel was given to clear (prep_folded)
-    double2 *d_slice_mean = nullptr;    // one per slice of the sorted order
-    size_t slice_mean_capacity = 0;
+    DevBuf<double2> d_slice_mean;       // one per slice of the sorted order
     bool last_quad = false;             // the last ray stage ran k_rays_quad (overflow check pending)
     int last_mode = 0;                  // 1 march, 2 skip, 3 quad, 4 cell, 5 sweep
     unsigned long long result_seq = 0;  // stamps the result block a small update writes to pinned memory (h_result[kResultStamp])
@@ -246,8 +239,8 @@ struct mcl_engine {
     bool far_fresh = true;              // no ray stage has seen the current particle set yet (set / initialised since the last one)
     bool pc_ready = false;              // d_pc already holds the constants of the current particles (written by k_resample_motion)
     int reserved_cus = 0;               // CUs k_rays_quad's persistent grid leaves free (for RCCL kernels running beside it)
-    unsigned long long *d_result = nullptr;   // [0..7] scalars, [8..11] counters, [12..13] overflow flag + work counter: one D2H copy
-    unsigned long long *h_result = nullptr;   // pinned mirror of d_result
+    DevBuf<unsigned long long> d_result;      // [0..7] scalars, [8..11] counters, [12..13] overflow flag + work counter: one D2H copy
+    HostBuf<unsigned long long> h_result;     // pinned mirror of d_result
     double h_scalars[8]{};
     uint64_t q_total = 0;
     double global_sums[5]{};            // sum w, wx, wy, wsin, wcos actually used for outputs
@@ -268,9 +261,8 @@ struct mcl_engine {
     uint64_t kld_bits = 0;              // kld_nx * kld_ny * n_theta_bins + 1 (the outside bin)
     int64_t kld_n_next = 0;             // children the next mcl_update draws
     int64_t kld_bins_last = -1;         // bins the last update's draw occupied (-1: none counted)
-    uint32_t *d_kld_bm = nullptr, *d_kld_list = nullptr;
-    unsigned int *d_kld_cnt = nullptr;  // 2 counters
-    size_t kld_bm_words = 0, kld_list_cap = 0;
+    DevBuf<uint32_t> d_kld_bm, d_kld_list;
+    DevBuf<unsigned int> d_kld_cnt;     // 2 counters
     int kld_parity = 0;
     // recovery by injection (mcl_set_recovery): the averages S, F (NaN: unset) on the host; an injecting update
     // counts its injected children in d_recov_cnt[recov_parity] and zeroes the other counter.  recov_cnt_slot: the counter of the
@@ -278,7 +270,7 @@ struct mcl_engine {
     bool recov_on = false;
     mcl_recovery_config_t recov{};
     double recov_S = __builtin_nan(""), recov_F = __builtin_nan("");
-    unsigned int *d_recov_cnt = nullptr;     // 2 counters
+    DevBuf<unsigned int> d_recov_cnt;        // 2 counters
     int recov_parity = 0, recov_cnt_slot = -1;
     int64_t recov_injected = 0;
     // likelihood-field sensor model (mcl_set_likelihood_field): the field and table of the current map (lf_K < 0:
@@ -286,11 +278,11 @@ struct mcl_engine {
     bool lf_on = false, last_lf = false;
     mcl_likelihood_field_config_t lf{};
     int lf_K = -1;
-    uint16_t *d_lf_D = nullptr;
-    float *d_lf_tab = nullptr;
+    DevBuf<uint16_t> d_lf_D;
+    DevBuf<float> d_lf_tab;
     std::vector<float> lf_tab;
-    double2 *d_lf_beams = nullptr, *h_lf_beams = nullptr;
-    int lf_beams_cap = 0;
+    DevBuf<double2> d_lf_beams;
+    HostBuf<double2> h_lf_beams;
     std::vector<double2> beam_cs_host;  // (cos, sin) of every beam angle (set_beam_angles)
     // motion model (mcl_set_motion_model): REFERENCE, or an odometry model whose per-update scalars go to the
     // k_resample_odo* kernels as plain arguments
@@ -320,6 +312,8 @@ struct mcl_engine {
         }                                                                                        \
     } while (0)
 
+#define MCL_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
+
 // Where the parents of a staged resample come from.
 struct ParentSource {
     const double *px = nullptr, *py = nullptr, *pth = nullptr;     // gathered columns, n_parents entries each
@@ -341,15 +335,11 @@ namespace mcl_host {
 int fail(mcl_engine *h, int code, const char *msg);
 int fail(mcl_engine *h, int code, const std::string &msg);
 std::string &create_error();                 // what mcl_*_last_error(NULL) reports (thread-local)
-template <class T>
-inline void dfree(T *&p)
-{
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
 bool ready(mcl_engine *h, bool need_particles);
 float elapsed(hipEvent_t a, hipEvent_t b);
 void graph_reset(mcl_engine *h);
+// room in d_blocktot for the scan of n entries (scan_weights); a spine that moves drops the captured graphs and the layout
+int reserve_scan_spine(mcl_engine *h, int64_t n);
 int scan_weights(mcl_engine *h, const uint64_t *d_q, uint64_t *d_cdf, int64_t n, uint64_t offset, uint64_t *d_total);
 void unpack_result(mcl_engine *h);
 int layout_adopt(mcl_engine *h, int64_t n);

@@ -27,11 +27,10 @@ extern "C" {
 // ---------------------------------------------------------------------------------------------
 struct mcl_group {
     std::vector<mcl_engine *> eng;
-    std::vector<uint64_t *> d_qall, d_cdfall;      // per device: all shards' weights and their global CDF
-    std::vector<unsigned long long *> d_remote;    // per device, 4 words: children whose parent was fetched from a peer (last update) |
+    std::vector<DevBuf<uint64_t>> d_qall, d_cdfall;      // per device: all shards' weights and their global CDF
+    std::vector<DevBuf<unsigned long long>> d_remote;    // per device, 4 words: children whose parent was fetched from a peer (last update) |
                                                    // this shard's max log-weight | the maximum over the shards (doubles)
-    std::vector<unsigned char *> d_chunks;         // per device: every shard's compact parent list (grown on demand)
-    std::vector<size_t> chunks_capacity;
+    std::vector<DevBuf<unsigned char>> d_chunks;   // per device: every shard's compact parent list (grown on demand)
     std::vector<hipEvent_t> ev_ready, ev_children, ev_rays; // per device, see mcl_group_update
     bool compact_last = false;
     int64_t n_per = 0, n_total = 0;
@@ -74,16 +73,12 @@ void mcl_group_destroy(mcl_group_t *g)
     for (size_t d = 0; d < g->eng.size(); ++d) {
         if (!g->eng[d]) continue;
         (void)hipSetDevice(g->eng[d]->cfg.device);
-        if (d < g->d_qall.size() && g->d_qall[d]) (void)hipFree(g->d_qall[d]);
-        if (d < g->d_cdfall.size() && g->d_cdfall[d]) (void)hipFree(g->d_cdfall[d]);
-        if (d < g->d_remote.size() && g->d_remote[d]) (void)hipFree(g->d_remote[d]);
-        if (d < g->d_chunks.size() && g->d_chunks[d]) (void)hipFree(g->d_chunks[d]);
         if (d < g->ev_ready.size() && g->ev_ready[d]) (void)hipEventDestroy(g->ev_ready[d]);
         if (d < g->ev_children.size() && g->ev_children[d]) (void)hipEventDestroy(g->ev_children[d]);
         if (d < g->ev_rays.size() && g->ev_rays[d]) (void)hipEventDestroy(g->ev_rays[d]);
         mcl_destroy(g->eng[d]);
     }
-    delete g;
+    delete g;                                // (the per-device buffers go here, whichever device is current: hipFree finds and waits for the owning one)
 }
 
 int mcl_group_create(const mcl_config_t *cfg, const int32_t *devices, int32_t n_devices, mcl_group_t **out)
@@ -106,17 +101,16 @@ int mcl_group_create(const mcl_config_t *cfg, const int32_t *devices, int32_t n_
         e->in_group = true;                 // (KLD sampling is single-engine only: mcl_set_kld refuses this engine)
         g->eng.push_back(e);
     }
-    g->d_qall.assign(n_devices, nullptr); g->d_cdfall.assign(n_devices, nullptr); g->d_remote.assign(n_devices, nullptr);
-    g->d_chunks.assign(n_devices, nullptr); g->chunks_capacity.assign(n_devices, 0);
+    g->d_qall.resize(n_devices); g->d_cdfall.resize(n_devices); g->d_remote.resize(n_devices); g->d_chunks.resize(n_devices);
     g->ev_ready.assign(n_devices, nullptr); g->ev_children.assign(n_devices, nullptr); g->ev_rays.assign(n_devices, nullptr);
     const size_t cap_total = (size_t)cfg->max_particles * n_devices;
     for (int d = 0; d < n_devices; ++d) {
-        if (hipSetDevice(devices[d]) != hipSuccess || hipMalloc(&g->d_qall[d], cap_total * 8) != hipSuccess ||
-            hipMalloc(&g->d_cdfall[d], cap_total * 8) != hipSuccess || hipMalloc(&g->d_remote[d], 32) != hipSuccess ||
+        if (hipSetDevice(devices[d]) != hipSuccess || g->d_qall[d].reserve(nullptr, cap_total) != MCL_OK ||
+            g->d_cdfall[d].reserve(nullptr, cap_total) != MCL_OK || g->d_remote[d].reserve(nullptr, 4) != MCL_OK ||
             hipEventCreateWithFlags(&g->ev_ready[d], hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&g->ev_rays[d], hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&g->ev_children[d], hipEventDisableTiming) != hipSuccess) {
-            create_error() = "group buffers: hipMalloc failed";
+            create_error() = "group buffers: allocation failed";
             mcl_group_destroy(g);
             return MCL_ERR_HIP;
         }
@@ -299,11 +293,9 @@ int mcl_group_update(mcl_group_t *g, const double action[3], const float *obs, i
             rc = mcl_stage_keep(e, (int64_t)d * n, nt, action);
         } else if (compact) {
             const size_t need = (size_t)G * (size_t)centries * kCompactEntryBytes;
-            if (need > g->chunks_capacity[d]) {
-                if (g->d_chunks[d]) { GHIP(g, hipStreamSynchronize(e->stream)); (void)hipFree(g->d_chunks[d]); g->d_chunks[d] = nullptr; }
-                g->chunks_capacity[d] = 0;
-                GHIP(g, hipMalloc(&g->d_chunks[d], need));
-                g->chunks_capacity[d] = need;
+            if (need > g->d_chunks[d].cap) {
+                if (g->d_chunks[d]) GHIP(g, hipStreamSynchronize(e->stream));
+                if (g->d_chunks[d].reserve(e, need)) return gfail(g, MCL_ERR_HIP, e->err);
             }
             for (int s = 0; s < G; ++s) {
                 rc = export_compact_launch(g->eng[s], g->d_chunks[d] + (size_t)s * (size_t)centries * kCompactEntryBytes, centries, e->cfg.device, e->stream);
@@ -313,13 +305,8 @@ int mcl_group_update(mcl_group_t *g, const double action[3], const float *obs, i
         } else {
             for (int s = 0; s < G; ++s)
                 GHIP(g, hipMemcpyPeerAsync(g->d_qall[d] + (size_t)s * n, e->cfg.device, g->eng[s]->d_q, g->eng[s]->cfg.device, (size_t)n * 8, e->stream));
-            if ((size_t)nt / mcl::kScanTile + 2 > e->blocktot_capacity) {
-                graph_reset(e);                // a captured update graph of this engine holds the old pointer
-                GHIP(g, hipStreamSynchronize(e->stream));
-                dfree(e->d_blocktot);
-                GHIP(g, hipMalloc(&e->d_blocktot, ((size_t)nt / mcl::kScanTile + 2) * 8));
-                e->blocktot_capacity = (size_t)nt / mcl::kScanTile + 2;
-            }
+            rc = reserve_scan_spine(e, nt);
+            if (rc) return gfail(g, rc, e->err);
             rc = scan_weights(e, g->d_qall[d], g->d_cdfall[d], nt, 0, nullptr);
             if (rc) return gfail(g, rc, e->err);
             ParentSource src;

@@ -44,7 +44,7 @@ struct mcl_query {
 namespace {
 
 // room for K poses of B beams; ranges / the score's buffers only for a call that wants them.  (device_bytes counts what was ever
-// asked of hipMalloc: a diagnostic, mcl_get_query_counters.)
+// asked of the device: a diagnostic, mcl_get_query_counters.)
 int query_alloc(mcl_engine *h, mcl_query *q, size_t K, size_t B, bool want_ranges, bool score)
 {
     size_t *bytes = &q->device_bytes;

@@ -1,54 +1,18 @@
 // mcl_side_buffers.h -- what the host code of the three read-only side calls shares (mcl_query.hip, mcl_search.hip, mcl_refine.hip):
-// device and pinned buffers that own their memory, and the few steps more than one of the calls takes.  Host code only.
+// the owning buffer types (mcl_buffers.h) and the few steps more than one of the calls takes.  Host code only.
 #pragma once
 #include "mcl_engine_internal.h"
 #include "mcl_lfield_core.h"
 
 #include <cmath>
 
-#define SIDE_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
+#define SIDE_TRY(call) MCL_TRY(call)
 
 namespace mcl_side {
 
-// `cap` elements at `p`, freed with the buffer.  reserve: room for `want` elements -- nothing when they are there, else the old
-// memory is dropped and new asked for (the contents are not kept).  A failure is the engine's error (HIPCHK) and leaves cap 0.
-template <class T, class Mem>
-struct Buf {
-    T *p = nullptr;
-    size_t cap = 0;
-    Buf() = default;
-    Buf(const Buf &) = delete;
-    Buf &operator=(const Buf &) = delete;
-    ~Buf() { drop(); }
-    void drop()
-    {
-        if (p) Mem::release(p);
-        p = nullptr;
-        cap = 0;
-    }
-    // bytes: the caller's count of what was ever asked of the device (never reduced by a free)
-    int reserve(mcl_engine *h, size_t want, size_t *bytes = nullptr)
-    {
-        if (want <= cap) return MCL_OK;
-        drop();
-        SIDE_TRY(Mem::alloc(h, (void **)&p, want * sizeof(T)));
-        cap = want;
-        if (bytes) *bytes += want * sizeof(T);
-        return MCL_OK;
-    }
-    operator T *() const { return p; }
-    T *operator->() const { return p; }
-};
-struct DeviceMem {
-    static int alloc(mcl_engine *h, void **p, size_t n) { HIPCHK(h, hipMalloc(p, n)); return MCL_OK; }
-    static void release(void *p) { (void)hipFree(p); }
-};
-struct PinnedMem {
-    static int alloc(mcl_engine *h, void **p, size_t n) { HIPCHK(h, hipHostMalloc(p, n)); return MCL_OK; }
-    static void release(void *p) { (void)hipHostFree(p); }
-};
-template <class T> using DevBuf = Buf<T, DeviceMem>;
-template <class T> using HostBuf = Buf<T, PinnedMem>;       // pinned staging: not counted in any byte counter
+// the owning buffers (mcl_buffers.h) under the names the side calls use
+using ::DevBuf;
+using ::HostBuf;
 
 // The used beams of a scan (search S3, refine R2) at `out`, through the update's own rule: the readings of every beam_stride-th
 // beam, the others NaN (no contribution).  h_obs: B floats of staging.  Returns their number.
