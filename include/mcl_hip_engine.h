@@ -526,6 +526,56 @@ int mcl_global_search_streamed(mcl_engine_t *h, const mcl_search_config_t *c /* 
 int mcl_host_search_slabs(const mcl_search_config_t *c, const mcl_search_stream_config_t *sc, int64_t n_positions, int32_t n_scans,
                           int32_t *slab_headings, int32_t *n_slabs, uint64_t *bytes);
 
+/* ---- global search under the beam model, from a shared per-position ray table ------------------------------
+ * mcl_global_search ranks the lattice by the likelihood field, which ignores free space.  mcl_global_search_beam ranks the same
+ * lattice (S1 / S2) by the model every update weights particles with: E4's table sum over cast rays.  All headings of a lattice
+ * position share that position's rays when the scan is evenly spaced and the heading step is a multiple of its increment, so a
+ * position needs M rays where a pose-by-pose search casts n_headings * B; a pose's score is a sum of table entries.
+ *   B1 grid.  a_j = (double)angle_f32[j] of the beams last set.  For B >= 2: inc = (a_{B-1} - a_0) / (B - 1), M = llround(2 pi /
+ *     inc); for B = 1: M = n_headings.  delta = 6.283185307179586 / (double)M.  phi_m = phi_0 + (double)m * delta with phi_0 =
+ *     a_0 - 3.141592653589793, the product and the sum each rounded once.  s = M / n_headings.  The headings are S2's theta_k,
+ *     unchanged, so theta_k + a_0 + j delta is the grid angle of index m(k, j) = (k s + j) mod M.  Refused with
+ *     MCL_ERR_INVALID_ARG -- the message says which condition failed -- unless inc > 0, B <= M <= 16384, n_headings divides M,
+ *     and max_j |a_j - (a_0 + j delta)| <= 4e-6 rad (the 2e-6 of mcl_set_beam_angles' even-spacing rule and as much again for
+ *     the drift between inc and delta; a Hokuyo's 1081 angles give M = 1440 and 2.7e-7).  mcl_host_search_beam_grid is the one
+ *     function the engine calls for this; it needs no device.  It writes *max_dev whenever M could be formed, refused or not;
+ *     phi (NULL, or n_phi == M entries) receives the grid angles.
+ *   B2 ray table.  R[p][m] is E3's step of the ray from the lattice position (x_p, y_p) of S1 at the angle phi_m: bit for bit
+ *     what cast_ray returns for that (x, y, angle).  The host forms (cos phi_m, sin phi_m) in double and uploads both.  Level 2
+ *     is the update's fp64 walk on the isotropic skip field with its guard, with that direction and the pose query's origin
+ *     arithmetic; level 3 -- guard hits and debug_force_exact -- is the literal march with dx = cos phi_m * res taken from the
+ *     uploaded table, not from a device cosine, so its additions are cast_ray's additions.  Entries are 8 bits wide when
+ *     MAX_RANGE_PX <= 255, else 16.  Lattice positions are cell centres: a grid angle whose sine or cosine is +-0.5 puts every
+ *     second sample on a cell edge, and every such ray is level 3 -- far more than the 0.02 % of an update.
+ *   B3 score.  row_j is E2's table row of reading j; NaN, +-inf and readings out of range count as E4 counts them.  Beam j is
+ *     used iff j % beam_stride == 0.  score[k * n_positions + p] = sum over the used j, ascending, of
+ *     (double)L[row_j][R[p][(k s + j) mod M]], from +0.0, in order, in fp64, one lane per pose: finite or -inf, never NaN, never
+ *     -0.0.  With beam_stride 1 this is E4's log-weight of a particle at that pose whose beams lie on the grid angles.  It is
+ *     NOT bit for bit mcl_score_poses: the float angles sit up to 4e-6 rad off the grid, and a ray that grazes a corner may stop
+ *     a step apart (profiles/beam_search.md has the measured share of differing steps).
+ *   B4 hits and volume.  S5, S6 (stats[0..3]) and mcl_get_search_scores exactly as for mcl_global_search; n_positions *
+ *     n_headings < MCL_MAX_TOTAL_PARTICLES.
+ *   B5 tiles.  The table is made and consumed per tile of T positions: T is the largest multiple of 256 with T * M * (1 or 2
+ *     bytes) <= table_budget_bytes (0: 256 MiB), no larger than n_positions rounded up to a multiple of 256, and with T * M <=
+ *     2^31.  A budget below 256 positions' worth is refused (MCL_ERR_INVALID_ARG).  The volume and the hits do not depend on T.
+ *     stats[4..7] = {M, T, tiles, rays of the call the literal march decided}.  mcl_get_search_beam_table copies the LAST tile's
+ *     table, position-major (out[t * M + m], n == *n_positions * M) and widened to 16 bits, for tests and debugging; with out
+ *     NULL and n 0 it reports the tile's first position and position count alone.  MCL_ERR_NOT_READY before a beam search and
+ *     after mcl_set_map.
+ *   B6 where it works.  A map and beam angles (MCL_ERR_NOT_READY otherwise); the likelihood field may be on or off, the bits are
+ *     the same.  weight_mode LOG only (MCL_ERR_INVALID_ARG in PRODUCT mode).  Single engine only (MCL_ERR_UNSUPPORTED for an
+ *     engine with a communicator or in a device group).  Everything S8 refuses of the
+ *     config and the arguments is refused here.  Read-only as S7: buffers of the search only (mcl_get_search_bytes counts
+ *     them), none of the update's scratch, one host wait; every later update is bit-identical to one of an engine that never
+ *     searched.
+ *   Not here: a sequence or streamed form, refinement under the beam model, shards. */
+int mcl_global_search_beam(mcl_engine_t *h, const mcl_search_config_t *c /* NULL = the defaults */, const float *obs, int32_t n_beams,
+                           uint64_t table_budget_bytes /* 0 = 256 MiB */, int32_t max_hits, mcl_search_hit_t *hits, int64_t *n_hits,
+                           uint64_t stats[8]);
+int mcl_host_search_beam_grid(const float *angles, int32_t n_beams, int32_t n_headings, int32_t *M, int32_t *heading_step,
+                              double *delta, double *max_dev, double *phi /* M entries, or NULL */, size_t n_phi);
+int mcl_get_search_beam_table(mcl_engine_t *h, uint16_t *out, size_t n, int64_t *first_position, int64_t *n_positions);
+
 /* ---- pose refinement: a dense local window around each seed pose, scored against one scan (correlative scan matching on the
  *      likelihood field) ---------------------------------------------------------------------------------
  * A hit of mcl_global_search sits on the search's lattice, a cluster mean or an /initialpose is only roughly right.  For each of

@@ -49,5 +49,20 @@ constexpr uint64_t kSearchListHits = 65536;             // the running list is s
 SearchSlabPlan search_slab_bytes(int64_t n_positions, int32_t G);
 std::string search_slabs(const mcl_search_config_t *c, const mcl_search_stream_config_t *sc, int64_t n_positions, int32_t n_scans,
                          SearchSlabPlan &plan);
+// The search under the beam model (mcl_global_search_beam).  B1: the angle grid of a scan and a heading count
+// (phi_m = phi0 + m delta); search_beam_grid returns an empty string and fills `g`, or says which condition failed (max_dev is
+// filled whenever M could be formed).  B5: the tiles of a table of n_positions x M entries in a budget (0: the default).
+struct SearchBeamGrid {
+    int32_t M = 0, heading_step = 0;
+    double delta = 0.0, max_dev = 0.0, phi0 = 0.0;
+};
+std::string search_beam_grid(const float *angles, int n_beams, int n_headings, SearchBeamGrid &g);
+void search_beam_angles(const SearchBeamGrid &g, double *phi);          // g.M entries
+struct SearchBeamTiles {
+    int64_t T = 0, tiles = 0;               // positions per tile (a multiple of 256), tiles
+    int32_t entry_bytes = 0;                // 1: MAX_RANGE_PX <= 255, else 2
+};
+constexpr uint64_t kSearchBeamDefaultBudget = 256ull << 20;
+std::string search_beam_tiles(int64_t n_positions, int32_t M, int32_t max_range_px, uint64_t budget_bytes, SearchBeamTiles &t);
 const char *refine_invalid(const mcl_refine_config_t *c);
 }  // namespace mcl_host

@@ -458,6 +458,65 @@ void search_headings(int n_headings, double *theta)
     for (int64_t k = 0; k < n_headings; ++k) theta[k] = (double)(2 * k - (int64_t)n_headings) * step;
 }
 
+// ---- the search under the beam model (mcl_global_search_beam): the angle grid of B1 and the tiles of B5
+std::string search_beam_grid(const float *angles, int n_beams, int n_headings, SearchBeamGrid &g)
+{
+    constexpr double kTwoPi = 6.283185307179586, kPi = 3.141592653589793;
+    g = SearchBeamGrid{};
+    if (!angles || n_beams < 1) return "beam search: no beam angles";
+    if (n_headings < 1) return "beam search: n_headings must be >= 1";
+    const int64_t B = n_beams;
+    const double a0 = (double)angles[0];
+    int64_t M = n_headings;                                              // one beam: the headings are the grid
+    if (B >= 2) {
+        const double inc = ((double)angles[B - 1] - a0) / (double)(B - 1);
+        if (!(inc > 0.0)) return "beam search: the beam angles must ascend (increment (a_last - a_first) / (B - 1) > 0)";
+        const double turns = kTwoPi / inc;
+        if (!(turns < 16384.5)) return "beam search: the angle grid M = round(2 pi / increment) must be at most 16384";
+        M = std::llround(turns);
+    }
+    if (M > 16384) return "beam search: the angle grid M = round(2 pi / increment) must be at most 16384";
+    g.M = (int32_t)M;
+    g.delta = kTwoPi / (double)M;
+    g.phi0 = a0 - kPi;
+    double worst = 0.0;
+    bool finite = true;
+    for (int64_t j = 0; j < B; ++j) {
+        const double dev = std::fabs((double)angles[j] - (a0 + (double)j * g.delta));
+        if (!(dev == dev)) finite = false;
+        else if (dev > worst) worst = dev;
+    }
+    g.max_dev = finite ? worst : std::nan("");
+    if (B > M) return "beam search: more beams than grid angles (B <= M = round(2 pi / increment): the scan spans more than a turn)";
+    if (M % n_headings != 0) return "beam search: n_headings must divide the angle grid M = " + std::to_string(M);
+    g.heading_step = (int32_t)(M / n_headings);
+    if (!finite || !(worst <= 4e-6)) return "beam search: the beam angles are not evenly spaced on the grid of 2 pi / M (a deviation above 4e-6 rad)";
+    return std::string();
+}
+
+void search_beam_angles(const SearchBeamGrid &g, double *phi)
+{
+    for (int64_t m = 0; m < g.M; ++m) phi[m] = g.phi0 + (double)m * g.delta;
+}
+
+std::string search_beam_tiles(int64_t n_positions, int32_t M, int32_t max_range_px, uint64_t budget_bytes, SearchBeamTiles &t)
+{
+    t = SearchBeamTiles{};
+    if (n_positions < 1 || n_positions >= MCL_MAX_TOTAL_PARTICLES || M < 1 || M > 16384 || max_range_px < 1 || max_range_px > 65535)
+        return "beam search: no tile plan for these sizes";
+    t.entry_bytes = max_range_px <= 255 ? 1 : 2;
+    const uint64_t budget = budget_bytes ? budget_bytes : kSearchBeamDefaultBudget;
+    const uint64_t per_position = (uint64_t)M * (uint64_t)t.entry_bytes;
+    uint64_t T = budget / per_position / 256 * 256;
+    if (T < 256)
+        return "beam search: table_budget_bytes holds fewer than 256 positions' rays (" + std::to_string(256 * per_position) + " bytes needed)";
+    T = std::min<uint64_t>(T, ((uint64_t)n_positions + 255) / 256 * 256);       // no larger than the lattice
+    T = std::min<uint64_t>(T, (1ull << 31) / (uint64_t)M / 256 * 256);         // a tile's ray index stays below 2^31
+    t.T = (int64_t)T;
+    t.tiles = (n_positions + t.T - 1) / t.T;
+    return std::string();
+}
+
 // ---- the search over a scan sequence (mcl_global_search_sequence): what it refuses of rel, and SQ1
 const char *search_sequence_invalid(const double *rel, int n_scans)
 {
@@ -857,6 +916,21 @@ int mcl_host_search_sequence_offsets(const mcl_search_config_t *c, const double 
     std::vector<double> theta((size_t)c->n_headings);
     search_headings(c->n_headings, theta.data());
     search_sequence_offsets(c->n_headings, theta.data(), rel, n_scans, out);
+    return MCL_OK;
+}
+
+int mcl_host_search_beam_grid(const float *angles, int32_t n_beams, int32_t n_headings, int32_t *M, int32_t *heading_step, double *delta,
+                              double *max_dev, double *phi, size_t n_phi)
+{
+    SearchBeamGrid g;
+    const std::string why = search_beam_grid(angles, n_beams, n_headings, g);
+    if (max_dev) *max_dev = g.max_dev;                                  // (what was measured, refused or not)
+    if (!why.empty()) return MCL_ERR_INVALID_ARG;
+    if (phi && n_phi != (size_t)g.M) return MCL_ERR_INVALID_ARG;
+    if (M) *M = g.M;
+    if (heading_step) *heading_step = g.heading_step;
+    if (delta) *delta = g.delta;
+    if (phi) search_beam_angles(g, phi);
     return MCL_OK;
 }
 

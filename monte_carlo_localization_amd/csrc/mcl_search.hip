@@ -18,7 +18,14 @@
 //              k_search_compact      (key, 64-bit index) of the flagged, in index order, behind the running list
 //              segmented radix sort  one segment, its end on the device: the list and the slab's candidates, stable
 //   (copy)     the counts and the first max_hits pairs of the list; one host wait
+// mcl_global_search_beam (§4.17) fills the same volume under the beam model, from a per-position ray table made in tiles:
+//   k_beam_rows          once: the table rows of the scan's used beams
+//   per tile:  k_beam_table        one lane per (position, grid angle): E3's step, flagged rays listed
+//              k_beam_table_exact  one wave per listed ray: the literal march
+//              k_beam_score        one lane per pose: the in-order sum of the rows' entries at the tile's steps
+//   then k_search_mark, the sort and the copies as above (search_finish)
 #include "mcl_search.h"
+#include "mcl_search_beam.h"
 #include "mcl_side_buffers.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -26,6 +33,7 @@
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <memory>
 
@@ -48,6 +56,13 @@ struct SlabBufs {
     size_t tmp_bytes = 0;                        // the two slab states and the segment's bounds
     SlabState *state = nullptr;                  // 2 (inside tmp)
     unsigned long long *seg = nullptr;           // 2 (inside tmp); set last: null until every buffer is there
+};
+
+// the ray table a beam search left on the device (B5): of which map, its shape, which positions (n = 0: none)
+struct BeamTable {
+    unsigned long long epoch = 0;
+    int32_t M = 0, entry_bytes = 0;
+    int64_t T = 0, first = 0, n = 0;
 };
 
 // the buffers of the search, kept between calls and grown with the lattice
@@ -87,6 +102,16 @@ struct mcl_search {
     std::unique_ptr<SlabBufs> slab;
     HostBuf<SlabState> h_state;
     HostBuf<uint64_t> h_idx;                    // kMaxHits
+    // the search under the beam model (§4.17): the grid's directions, a tile's ray table and its level-3 list, the scan and its rows
+    std::vector<double> bphi;                   // the grid angles the device's directions were made from
+    DevBuf<double2> d_bdir;
+    HostBuf<double2> h_bdir;
+    DevBuf<uint8_t> d_btab;                     // T x M entries of 1 or 2 bytes
+    DevBuf<uint32_t> d_blist;
+    DevBuf<mcl_sbeam::Header> d_bhdr;
+    HostBuf<mcl_sbeam::Header> h_bhdr;
+    DevBuf<float> d_bobs, d_lobs;
+    BeamTable btab;                             // what d_btab holds: the last tile of the last beam search
 };
 
 namespace {
@@ -192,9 +217,10 @@ double key_score(uint64_t key)
     return v;
 }
 
-// What every search checks before it touches the device: the arguments and the readiness (S8).  c receives the config in force.
+// What every search checks before it touches the device: the arguments and the readiness (S8; beam_model: B6, which asks for no
+// field).  c receives the config in force.
 int search_check(mcl_engine *h, const mcl_search_config_t *cfg, const void *obs, int32_t n_beams, int32_t max_hits,
-                 const mcl_search_hit_t *hits, const int64_t *n_hits, mcl_search_config_t &c)
+                 const mcl_search_hit_t *hits, const int64_t *n_hits, mcl_search_config_t &c, bool beam_model = false)
 {
     if (cfg) c = *cfg; else mcl_default_search_config(&c);
     if (const char *why = mcl_host::search_invalid(&c)) return fail(h, MCL_ERR_INVALID_ARG, why);
@@ -203,7 +229,7 @@ int search_check(mcl_engine *h, const mcl_search_config_t *cfg, const void *obs,
     if (max_hits > 0 && !hits) return fail(h, MCL_ERR_INVALID_ARG, "global search: hits is null");
     if (!h->have_map) return fail(h, MCL_ERR_NOT_READY, "global search: no map is set");
     if (h->B <= 0 || h->beam_cs_host.empty()) return fail(h, MCL_ERR_NOT_READY, "global search: no beam angles are set");
-    if (!h->lf_on || h->lf_K < 0 || !h->d_lf_D)
+    if (!beam_model && (!h->lf_on || h->lf_K < 0 || !h->d_lf_D))
         return fail(h, MCL_ERR_NOT_READY, "global search: the likelihood-field model is off (mcl_set_likelihood_field; the search reads its field and table)");
     if (n_beams != h->B) return fail(h, MCL_ERR_INVALID_ARG, "global search: n_beams does not match the beam angles");
     return MCL_OK;
@@ -506,6 +532,133 @@ int stream_finish(mcl_engine *h, mcl_search *s, const Stream &st, int nb, mcl_se
     return MCL_OK;
 }
 
+// ---- the search under the beam model (§4.17)
+// the directions of the grid angles on the device (formed and uploaded when the grid changed): the host's cos / sin, in double (B2)
+int beam_directions_upload(mcl_engine *h, mcl_search *s, const mcl_host::SearchBeamGrid &g)
+{
+    std::vector<double> phi((size_t)g.M);
+    mcl_host::search_beam_angles(g, phi.data());
+    if (phi == s->bphi) return MCL_OK;
+    s->bphi.clear();
+    SIDE_TRY(s->d_bdir.reserve(h, (size_t)g.M, &s->device_bytes));
+    SIDE_TRY(s->h_bdir.reserve(h, (size_t)g.M));
+    for (int32_t m = 0; m < g.M; ++m) s->h_bdir[m] = make_double2(std::cos(phi[(size_t)m]), std::sin(phi[(size_t)m]));
+    // on the engine's stream, from pinned staging: no host wait of its own (the staging is rewritten only by a later call,
+    // and every call ends in a host wait)
+    HIPCHK(h, hipMemcpyAsync(s->d_bdir, s->h_bdir, (size_t)g.M * sizeof(double2), hipMemcpyHostToDevice, h->stream));
+    s->bphi.swap(phi);
+    return MCL_OK;
+}
+
+// entries of a tile's level-3 list (B2): the share of rays that run along cell edges is near 1 in 180 on a Hokuyo's grid; room
+// for 1 in 64, at least 4096, and never more than the tile has rays
+size_t beam_list_entries(uint64_t tile_rays)
+{
+    return (size_t)std::min<uint64_t>(tile_rays, std::max<uint64_t>(4096, tile_rays / 64));
+}
+
+template <class E>
+int beam_tiles_run(mcl_engine *h, mcl_search *s, mcl_sbeam::Args &a, const mcl_host::SearchBeamTiles &tp)
+{
+    using namespace mcl_sbeam;
+    for (int64_t tile = 0; tile < tp.tiles; ++tile) {
+        a.pos0 = (int32_t)(tile * tp.T);
+        a.count = (int32_t)std::min<int64_t>(tp.T, s->n_pos - (int64_t)a.pos0);
+        a.blocks_per_row = (uint32_t)((a.count + mcl_sbeam::kThreads - 1) / mcl_sbeam::kThreads);
+        HIPCHK(h, hipMemsetAsync(&s->d_bhdr.p->listed, 0, sizeof(unsigned long long), h->stream));
+        hipLaunchKernelGGL(k_beam_table<E>, dim3((unsigned)((uint64_t)a.blocks_per_row * (uint64_t)a.M)), dim3(mcl_sbeam::kThreads), 0,
+                           h->stream, a);
+        HIPCHK(h, hipGetLastError());
+        // one wave per listed ray, as many as the list can hold (the count is read on the device)
+        const int64_t waves = (int64_t)std::min<unsigned long long>((unsigned long long)a.count * (unsigned long long)a.M, a.list_cap);
+        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, (int64_t)h->num_cu * 8));
+        hipLaunchKernelGGL(k_beam_table_exact<E>, dim3(grid), dim3(mcl_sbeam::kThreads), 0, h->stream, a);
+        HIPCHK(h, hipGetLastError());
+        hipLaunchKernelGGL(k_beam_score<E>, dim3((unsigned)((uint64_t)a.blocks_per_row * (uint64_t)a.n_head)), dim3(mcl_sbeam::kThreads), 0,
+                           h->stream, a);
+        HIPCHK(h, hipGetLastError());
+    }
+    return MCL_OK;
+}
+
+int search_beam(mcl_engine *h, const mcl_search_config_t *cfg, const float *obs, int32_t n_beams, uint64_t budget, int32_t max_hits,
+                mcl_search_hit_t *hits, int64_t *n_hits, uint64_t *stats)
+{
+    // B6 / B1 / B5: everything that can refuse the call, before anything is allocated for it
+    mcl_search_config_t c;
+    SIDE_TRY(search_check(h, cfg, obs, n_beams, max_hits, hits, n_hits, c, true));
+    if (h->cfg.weight_mode != MCL_WEIGHT_LOG) return fail(h, MCL_ERR_INVALID_ARG, "beam search: weight_mode LOG only");
+    if (h->comm || h->in_group)
+        return fail(h, MCL_ERR_UNSUPPORTED, "beam search: single-engine only: this engine has a communicator or belongs to a device group");
+    if (!h->d_L || !h->d_dist) return fail(h, MCL_ERR_NOT_READY, "beam search: the map's tables are not built");
+    mcl_host::SearchBeamGrid g;
+    const std::string why_grid = mcl_host::search_beam_grid(h->angles.data(), h->B, c.n_headings, g);
+    if (!why_grid.empty()) return fail(h, MCL_ERR_INVALID_ARG, why_grid);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (!h->srch) h->srch = new mcl_search();
+    mcl_search *s = h->srch;
+    SIDE_TRY(search_lattice_upload(h, s, c.stride_cells));
+    if (s->n_pos == 0) return fail(h, MCL_ERR_NOT_READY, "global search: the lattice has no free position on this map");
+    const int64_t n_poses = s->n_pos * (int64_t)c.n_headings;
+    if (n_poses >= MCL_MAX_TOTAL_PARTICLES)
+        return fail(h, MCL_ERR_INVALID_ARG, "global search: n_positions * n_headings must stay below 2^27 (a larger stride_cells or fewer headings)");
+    mcl_host::SearchBeamTiles tp;
+    const std::string why_tiles = mcl_host::search_beam_tiles(s->n_pos, g.M, h->P, budget, tp);
+    if (!why_tiles.empty()) return fail(h, MCL_ERR_INVALID_ARG, why_tiles);
+
+    // the buffers: the volume and its sort as every unstreamed search, then the beam search's own
+    const int B = h->B, tw = h->P + 1;
+    const int nb = (B + c.beam_stride - 1) / c.beam_stride;
+    SIDE_TRY(search_headings_upload(h, s, c.n_headings));
+    SIDE_TRY(search_alloc(h, s, (size_t)n_poses, (size_t)B));
+    s->volume.n = 0;                                             // until this volume is whole
+    s->btab.n = 0;
+    SIDE_TRY(beam_directions_upload(h, s, g));
+    const uint64_t tile_rays = (uint64_t)tp.T * (uint64_t)g.M;
+    SIDE_TRY(s->d_btab.reserve(h, (size_t)(tile_rays * (uint64_t)tp.entry_bytes), &s->device_bytes));
+    SIDE_TRY(s->d_blist.reserve(h, beam_list_entries(tile_rays), &s->device_bytes));
+    SIDE_TRY(s->d_bhdr.reserve(h, 1, &s->device_bytes));
+    SIDE_TRY(s->h_bhdr.reserve(h, 1));
+    SIDE_TRY(s->d_bobs.reserve(h, (size_t)B, &s->device_bytes));
+    SIDE_TRY(s->d_lobs.reserve(h, (size_t)nb * (size_t)tw, &s->device_bytes));
+
+    // the scan, the counters, the rows
+    std::memcpy(s->h_obs, obs, (size_t)B * sizeof(float));
+    HIPCHK(h, hipMemcpyAsync(s->d_bobs, s->h_obs, (size_t)B * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(s->d_count, 0, sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMemsetAsync(s->d_bhdr, 0, sizeof(mcl_sbeam::Header), h->stream));
+    mcl_sbeam::Args a{};
+    mcl::RayArgs &m = a.ray;
+    m.B = B; m.P = h->P;
+    m.grid = h->d_grid; m.W = h->W; m.H = h->H;
+    m.res = h->res; m.ox = h->ox; m.oy = h->oy;
+    m.dist = h->d_dist; m.Wp = h->Wp; m.Hp = h->Hp; m.Wps = h->Wps;
+    m.force_exact = h->cfg.debug_force_exact;
+    a.xy = s->d_xy; a.dir = s->d_bdir;
+    a.M = g.M; a.T = (int32_t)tp.T;
+    a.tab = s->d_btab;
+    a.list = s->d_blist; a.list_cap = (unsigned long long)beam_list_entries(tile_rays);
+    a.hdr = s->d_bhdr;
+    a.obs = s->d_bobs; a.B = B; a.beam_stride = c.beam_stride; a.nb = nb;
+    a.L = h->d_L; a.lobs = s->d_lobs;
+    a.n_pos = (int32_t)s->n_pos; a.n_head = c.n_headings; a.heading_step = g.heading_step;
+    a.score = s->d_score;
+    hipLaunchKernelGGL(mcl_sbeam::k_beam_rows, dim3((unsigned)(((uint64_t)nb * (uint64_t)tw + mcl_sbeam::kThreads - 1) / mcl_sbeam::kThreads)),
+                       dim3(mcl_sbeam::kThreads), 0, h->stream, a);
+    HIPCHK(h, hipGetLastError());
+    if (tp.entry_bytes == 1) SIDE_TRY(beam_tiles_run<uint8_t>(h, s, a, tp));
+    else SIDE_TRY(beam_tiles_run<uint16_t>(h, s, a, tp));
+    HIPCHK(h, hipMemcpyAsync(s->h_bhdr, s->d_bhdr, sizeof(mcl_sbeam::Header), hipMemcpyDeviceToHost, h->stream));
+    const SeqArgs q = search_args(h, s, c, nb, 1);
+    SIDE_TRY(search_finish(h, s, q.a, n_poses, max_hits, hits, n_hits));      // (the one host wait)
+    s->btab = {h->map_epoch, g.M, tp.entry_bytes, tp.T, (tp.tiles - 1) * tp.T, s->n_pos - (tp.tiles - 1) * tp.T};
+    if (stats) {
+        search_stats(stats, s, n_poses, nb);
+        stats[4] = (uint64_t)g.M; stats[5] = (uint64_t)tp.T; stats[6] = (uint64_t)tp.tiles; stats[7] = (uint64_t)s->h_bhdr->level3;
+    }
+    return MCL_OK;
+}
+
 }  // namespace
 
 void search_free(struct mcl_search *s) { delete s; }
@@ -551,6 +704,41 @@ int mcl_global_search_streamed(mcl_engine_t *h, const mcl_search_config_t *cfg, 
     SIDE_TRY(stream_begin(h, s, nb, n_scans, st));
     for (int t = 0; t < st.plan.n_slabs; ++t) SIDE_TRY(stream_slab(h, s, st, t));
     return stream_finish(h, s, st, nb, hits, n_hits, stats);
+}
+
+int mcl_global_search_beam(mcl_engine_t *h, const mcl_search_config_t *cfg, const float *obs, int32_t n_beams, uint64_t table_budget_bytes,
+                           int32_t max_hits, mcl_search_hit_t *hits, int64_t *n_hits, uint64_t stats[8])
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    return search_beam(h, cfg, obs, n_beams, table_budget_bytes, max_hits, hits, n_hits, stats);
+}
+
+int mcl_get_search_beam_table(mcl_engine_t *h, uint16_t *out, size_t n, int64_t *first_position, int64_t *n_positions)
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    const mcl_search *s = h->srch;
+    if (!s || s->btab.n == 0 || s->btab.epoch != h->map_epoch || !h->have_map)
+        return fail(h, MCL_ERR_NOT_READY, "no ray table: no beam search has run on this map");
+    const BeamTable &b = s->btab;
+    if (first_position) *first_position = b.first;
+    if (n_positions) *n_positions = b.n;
+    if (!out && n == 0) return MCL_OK;                                  // the shape alone
+    if (!out || n != (size_t)b.n * (size_t)b.M) return fail(h, MCL_ERR_INVALID_ARG, "the last tile's table has n_positions x M entries");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    // the tile's first b.n columns of every angle's row, then position-major and widened on the host
+    const size_t e = (size_t)b.entry_bytes, row = (size_t)b.n * e;
+    std::vector<uint8_t> raw(row * (size_t)b.M);
+    HIPCHK(h, hipMemcpy2DAsync(raw.data(), row, s->d_btab.p, (size_t)b.T * e, row, (size_t)b.M, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int64_t t = 0; t < b.n; ++t)
+        for (int32_t m = 0; m < b.M; ++m) {
+            const size_t i = (size_t)m * (size_t)b.n + (size_t)t;
+            uint16_t v;
+            if (e == 1) v = raw[i];
+            else std::memcpy(&v, &raw[2 * i], sizeof v);
+            out[(size_t)t * (size_t)b.M + (size_t)m] = v;
+        }
+    return MCL_OK;
 }
 
 int mcl_get_search_scores(mcl_engine_t *h, double *out, size_t n)

@@ -387,6 +387,10 @@ class ShardedFilter:
         dist.all_to_all_single(req_in, local, output_split_sizes=rcv, input_split_sizes=sc, group=self.group)
         reply = torch.empty((int(req_in.numel()), 4), dtype=torch.float64, device=self.device)
         self._records_at(req_in, reply)                                  # the records the other ranks asked this one for
+        if self._err is not None:
+            # a rank that has failed exported none, or not all: it answers with zeros, not with what the fresh buffer holds --
+            # its peers run their stages on the answer before the error word voids the update
+            reply.zero_()
         self._sync()
         dist.all_to_all_single(table, reply, output_split_sizes=sc, input_split_sizes=rcv, group=self.group)
         remote = k - sc[self.rank]

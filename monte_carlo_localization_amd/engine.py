@@ -51,6 +51,7 @@ EXPORTS = [
     "mcl_host_search_headings", "mcl_init_particles_mixture",
     "mcl_global_search_sequence", "mcl_host_search_sequence_offsets", "mcl_host_relative_poses",
     "mcl_default_search_stream_config", "mcl_global_search_streamed", "mcl_host_search_slabs",
+    "mcl_global_search_beam", "mcl_host_search_beam_grid", "mcl_get_search_beam_table",
     "mcl_default_refine_config", "mcl_refine_poses", "mcl_get_refine_scores", "mcl_get_refine_bytes", "mcl_host_refine_window",
     "mcl_host_refine_reduce",
     "mcl_default_recovery_config", "mcl_set_recovery", "mcl_get_recovery_state", "mcl_set_recovery_state", "mcl_host_recovery_step",
@@ -259,6 +260,11 @@ def load_library(legacy=False):
                                                    C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]
         lib.mcl_host_search_slabs.argtypes = [C.POINTER(SearchConfig), C.POINTER(SearchStreamConfig), C.c_int64, C.c_int32,
                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
+        lib.mcl_global_search_beam.argtypes = [C.c_void_p, C.POINTER(SearchConfig), C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, C.c_void_p,
+                                               C.POINTER(C.c_int64), C.c_void_p]
+        lib.mcl_host_search_beam_grid.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                  C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_size_t]
+        lib.mcl_get_search_beam_table.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         lib.mcl_default_refine_config.argtypes = [C.POINTER(RefineConfig)]
         lib.mcl_default_refine_config.restype = None
         lib.mcl_refine_poses.argtypes = [C.c_void_p, C.POINTER(RefineConfig), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
@@ -484,6 +490,27 @@ def host_search_headings(**fields) -> np.ndarray:
     if rc != MCL_OK:
         raise EngineError(f"mcl_host_search_headings rc={rc}", rc)
     return out
+
+
+def host_search_beam_grid(angles, n_headings=72) -> dict:
+    """The angle grid of a search under the beam model (mcl_host_search_beam_grid, rule B1; no device needed): {M, heading_step,
+    delta, max_dev, phi} -- the grid angles per turn, the grid steps between two headings, the grid's increment, the worst
+    deviation of a beam angle from its grid angle, and the M grid angles.  Raises EngineError (with .max_dev where it was
+    measured) when the scan and the heading count do not share a grid."""
+    a = _c(angles, np.float32)
+    lib = load_library()
+    M, s, d, dev = C.c_int32(), C.c_int32(), C.c_double(), C.c_double(float("nan"))
+    rc = lib.mcl_host_search_beam_grid(_p(a) if a.size else None, C.c_int32(a.size), C.c_int32(int(n_headings)), C.byref(M), C.byref(s),
+                                       C.byref(d), C.byref(dev), None, 0)
+    if rc != MCL_OK:
+        err = EngineError(f"mcl_host_search_beam_grid rc={rc}", rc)
+        err.max_dev = dev.value
+        raise err
+    phi = np.empty(M.value, np.float64)
+    rc = lib.mcl_host_search_beam_grid(_p(a), C.c_int32(a.size), C.c_int32(int(n_headings)), None, None, None, None, _p(phi), phi.size)
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_search_beam_grid rc={rc}", rc)
+    return dict(M=int(M.value), heading_step=int(s.value), delta=d.value, max_dev=dev.value, phi=phi)
 
 
 def _rel_rows(rel) -> np.ndarray:
@@ -1044,6 +1071,35 @@ class Engine:
         return hits[:min(n.value, hits.size)], dict(n_hits=n.value, n_positions=int(st[0]), n_poses=int(st[1]), used_beams=int(st[2]),
                                                     device_bytes=int(st[3]), slab_headings=int(st[4]), n_slabs=int(st[5]),
                                                     headings_scored=int(st[6]), candidates_compacted=int(st[7]))
+
+    def global_search_beam(self, obs, max_hits=16, table_budget_bytes=0, **fields):
+        """global_search under the beam model (mcl_global_search_beam): the lattice ranked by the table sum over
+        cast rays that every update weights particles with, from a per-position ray table shared by all headings.  The scan must
+        be evenly spaced and n_headings must divide its angle grid (host_search_beam_grid).  The likelihood field may be on or
+        off.  `table_budget_bytes` (0: 256 MiB) bounds the table: the lattice is walked in tiles of positions.  Returns (hits,
+        {n_hits, n_positions, n_poses, used_beams, device_bytes, grid_angles, tile_positions, n_tiles, level3_rays})."""
+        c = default_search_config(**fields)
+        o = _c(obs, np.float32)
+        hits = np.zeros(int(max_hits), SEARCH_HIT_DTYPE)
+        n, st = C.c_int64(), np.zeros(8, np.uint64)
+        self._chk(self.lib.mcl_global_search_beam(self._h, C.byref(c), _p(o), C.c_int32(o.size), C.c_uint64(int(table_budget_bytes)),
+                                                  C.c_int32(int(max_hits)), _p(hits) if hits.size else None, C.byref(n), _p(st)),
+                  "mcl_global_search_beam")
+        self._search_poses, self._search_beam_M = int(st[1]), int(st[4])
+        return hits[:min(n.value, hits.size)], dict(n_hits=n.value, n_positions=int(st[0]), n_poses=int(st[1]), used_beams=int(st[2]),
+                                                    device_bytes=int(st[3]), grid_angles=int(st[4]), tile_positions=int(st[5]),
+                                                    n_tiles=int(st[6]), level3_rays=int(st[7]))
+
+    def search_beam_table(self):
+        """The ray table of the last tile of the last global_search_beam (mcl_get_search_beam_table): (first_position, steps) with
+        steps of shape (n_positions_of_the_tile, M), uint16 -- E3's step from each position at each grid angle.  M is the
+        grid_angles this object's last global_search_beam reported (the C call takes the size and checks it)."""
+        first, cnt = C.c_int64(), C.c_int64()
+        self._chk(self.lib.mcl_get_search_beam_table(self._h, None, 0, C.byref(first), C.byref(cnt)), "mcl_get_search_beam_table")
+        M = getattr(self, "_search_beam_M", 0)
+        out = np.empty(cnt.value * M, np.uint16)
+        self._chk(self.lib.mcl_get_search_beam_table(self._h, _p(out), C.c_size_t(out.size), None, None), "mcl_get_search_beam_table")
+        return int(first.value), out.reshape(cnt.value, M)
 
     def search_scores(self, n_headings=None):
         """The score volume of the last global_search or global_search_sequence (mcl_get_search_scores): n_headings * n_positions doubles, heading-major;
