@@ -568,7 +568,7 @@ int mcl_host_search_slabs(const mcl_search_config_t *c, const mcl_search_stream_
  *     config and the arguments is refused here.  Read-only as S7: buffers of the search only (mcl_get_search_bytes counts
  *     them), none of the update's scratch, one host wait; every later update is bit-identical to one of an engine that never
  *     searched.
- *   Not here: a sequence or streamed form, refinement under the beam model, shards. */
+ *   Not here: a sequence or streamed form, shards.  (Refinement under the beam model: mcl_refine_poses_beam.) */
 int mcl_global_search_beam(mcl_engine_t *h, const mcl_search_config_t *c /* NULL = the defaults */, const float *obs, int32_t n_beams,
                            uint64_t table_budget_bytes /* 0 = 256 MiB */, int32_t max_hits, mcl_search_hit_t *hits, int64_t *n_hits,
                            uint64_t stats[8]);
@@ -617,7 +617,8 @@ int mcl_get_search_beam_table(mcl_engine_t *h, uint16_t *out, size_t n, int64_t 
  *     reserved != 0, n_win > 32768, M outside [1, 4096], M n_win >= MCL_MAX_TOTAL_PARTICLES, a null seeds / obs / out,
  *     n_beams != B, a seed with a non-finite component.  Seeds off the map or inside a wall are allowed and score like any pose.
  *     Single engine only (the likelihood field is).  Seeds that refine to the same maximum are not merged, and the window is not
- *     iterated: a caller re-centres and calls again if it wants to. */
+ *     iterated: a caller re-centres and calls again if it wants to.  The same window under the beam model, with the field on or
+ *     off: mcl_refine_poses_beam, below. */
 typedef struct {
     int32_t half_xy;                        /* >= 0, default 4: window columns / rows = 2 half_xy + 1                          */
     int32_t half_theta;                     /* >= 0, default 10: window headings = 2 half_theta + 1                            */
@@ -647,6 +648,41 @@ int mcl_get_refine_bytes(const mcl_engine_t *h, uint64_t *bytes);
 int mcl_host_refine_window(const mcl_refine_config_t *c, const double seed[3], float resolution, double *poses, size_t n_win);
 int mcl_host_refine_reduce(const mcl_refine_config_t *c, const double seed[3], float resolution, const double *scores, size_t n_win,
                            mcl_refine_result_t *out);
+
+/* ---- pose refinement under the beam model: the same window, every pose's beams cast and summed in one kernel --
+ * mcl_refine_poses ranks its window by the likelihood field, which ignores free space and which a node that runs the beam model
+ * -- the reference's only model, the engine's default -- never otherwise builds.  mcl_refine_poses_beam scores the same window by
+ * E4's table sum over cast rays, what every update of such a node weights particles with and what mcl_global_search_beam ranks
+ * its lattice by: search, refinement and seeding under one model.  The same config and result structs.
+ *   RB1 window.  R1, unchanged: the device forms the window poses from the seeds, multiply and add each rounded; no pose table
+ *     is uploaded.
+ *   RB2 rays.  For window pose w and beam j the step r(w, j) is Q1's: bit for bit what mcl_query_scans reports for that pose and
+ *     beam, and what cast_ray returns for (x, y, theta + (double)angle_f32[j]).  The device functions of the pose query: the
+ *     update's fp64 walk on the isotropic skip field with its guard, and the literal march where the guard says so, where the
+ *     pose is not sane, or with debug_force_exact.  These are the float beam angles, not B1's grid: no evenly-spaced-scan
+ *     condition.  No step is ever stored.
+ *   RB3 score.  row_j is E2's table row of reading j; every reading counts as E4 counts it (NaN, +-inf and out-of-range readings
+ *     have rows): nothing is masked, unlike R2.  Beam j is used iff j % beam_stride == 0.  The u-th used beam (u ascending with j)
+ *     belongs to lane u % 64; each lane adds its (double)L[row_j][r(w, j)] in ascending u from +0.0, and the 64 lane sums are
+ *     joined by the butterfly v += shfl_xor(v, off), off = 32, 16, ..., 1 (Q3's order).  With beam_stride 1 the score is bit for
+ *     bit mcl_score_poses(...).log_likelihood under the beam model for that pose and the same obs; with stride s, that of an
+ *     engine whose beam angles are angles[::s], given obs[::s].  Finite or -inf, never NaN.
+ *   RB4 records.  R3 and R4, unchanged; mcl_host_refine_reduce on the volume is the restatement.
+ *   RB5 memory and volume.  No step or range volume exists at any time: device memory is the seeds, the records, the M n_win
+ *     doubles of the volume, the scan and one table-row offset per beam, and a counter; it does not depend on M n_win B.
+ *     stats = {n_win, M n_win, used beams, bytes of device memory the refinement's buffers have asked for so far, rays cast
+ *     (= M n_win used beams), rays the literal march decided}; stats may be NULL.  mcl_get_refine_scores returns the volume of
+ *     the last refinement of either kind (one buffer, one tag), mcl_get_refine_bytes counts the buffers of both.
+ *   RB6 where it works.  A map and beam angles (MCL_ERR_NOT_READY otherwise); the likelihood field may be on or off, the bits are
+ *     the same: it reads neither the field nor its table.  weight_mode LOG only (MCL_ERR_INVALID_ARG in PRODUCT mode, as
+ *     mcl_score_poses).  Single engine only (MCL_ERR_UNSUPPORTED for an engine with a communicator or in a device group, as B6).
+ *     Everything R7 refuses of the config and the arguments is refused here with the same status, and everything R7 allows is
+ *     served: up to 2^27 - 1 window poses, a wave each, in launches of 2^22 poses.  Read-only as R6: none of the
+ *     update's scratch or staged observation, no captured graph dropped, one host wait at the end; every later update is
+ *     bit-identical to one of an engine that never refined.
+ *   Not here: a window that is iterated or re-centred, pruning of the window, shards. */
+int mcl_refine_poses_beam(mcl_engine_t *h, const mcl_refine_config_t *c /* NULL = the defaults */, const double *seeds_colmajor,
+                          int32_t M, const float *obs, int32_t n_beams, mcl_refine_result_t *out, uint64_t stats[6]);
 
 /* ---- recovery by random-particle injection (augmented MCL, Probabilistic Robotics Table 8.3; AMCL's recovery_alpha_slow /
  *      recovery_alpha_fast) -------------------------------------------------------------------------------

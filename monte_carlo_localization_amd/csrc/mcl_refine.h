@@ -1,10 +1,12 @@
-// mcl_refine.h -- the pose refinement (mcl_refine_poses): the likelihood-field score of every pose of a dense
-// window around each seed pose, and per seed the best pose, the weighted mean and the covariance of its window.  The arguments of
-// its kernels and the kernels themselves; only mcl_refine.hip includes it.  A score comes from the per-beam arithmetic of k_lfield
-// (mcl_lfield_core.h), so a window pose and a queried pose at the same place agree bit for bit.
+// mcl_refine.h -- the pose refinement (mcl_refine_poses; mcl_refine_poses_beam, §4.18): the score of every pose
+// of a dense window around each seed pose, and per seed the best pose, the weighted mean and the covariance of its window.  The
+// arguments of its kernels and the kernels themselves; only mcl_refine.hip includes it.  A likelihood-field score comes from the
+// per-beam arithmetic of k_lfield (mcl_lfield_core.h), a beam-model score from the ray functions of the update and the pose
+// query (mcl_ray_core.h), so a window pose and a queried pose at the same place agree bit for bit under either model.
 #pragma once
 #include "mcl_engine_internal.h"
 #include "mcl_lfield_core.h"
+#include "mcl_ray_core.h"
 #include "mcl_refine_core.h"
 
 namespace mcl_rf {
@@ -25,6 +27,38 @@ struct Args {
     double *score;                  // M x n_win: score[m * n_win + w]
     mcl_refine_result_t *out;       // M records
 };
+
+// what k_refine_beam_score counts (stats only: never part of a score)
+struct BeamHeader {
+    unsigned long long level3;      // rays the literal march decided
+};
+
+struct BeamArgs {
+    mcl::RayArgs ray;               // the map, P, the beam directions and angles, force_exact: what trace_fp64 and the march read
+    const double *seeds;            // M x 3 column-major
+    int32_t M;
+    Window win;
+    int32_t n_total;                // M * n_win (< 2^27)
+    int32_t pose0;                  // first pose of this launch of k_refine_beam_score (kPosesPerLaunch)
+    const float *obs;               // B readings
+    int32_t beam_stride, nb;        // nb = used beams: j = u * beam_stride, u < nb
+    uint32_t *row_base;             // per used beam: row_j * (P + 1), where its row of L starts (RB3)
+    const float *L;                 // [row][step], P + 1 columns: the engine's static table
+    double *score;                  // M x n_win
+    BeamHeader *hdr;
+};
+
+// Flagged lanes of a round from which every one of them marches its own ray (march_exact, 64 rays at once) instead of the wave
+// marching them one after the other (wave_march_exact).  The wave's march costs about 270 instruction slots per ray whatever its
+// length, a lane's about 60 per step of the longest flagged ray: they break even at (longest ray) / 4.5 flagged lanes, 9 to 50
+// for rays of 40 to 240 steps.  Measured on whole-wave rounds: any value from 1 to 32 gives the same time, 11
+// times shorter than the wave's march alone.
+constexpr int kLaneMarchMin = 16;
+
+// k_refine_beam_score: a wave per pose, so a workgroup holds four poses, and a launch at most 2^22 of them: 2^30 threads, below
+// the 2^32 threads a grid may have.  The 2^27 - 1 poses R7 allows take 32 launches on the stream.
+constexpr int kPosesPerBlock = kThreads / 64;
+constexpr int32_t kPosesPerLaunch = 1 << 22;
 
 // One lane per window pose i = m * n_win + w, ix fastest: the lanes of a wave are neighbouring sub-cell positions of one heading
 // (or of two, where a row of the window ends), so for one beam their end points fall into the same few cells of D.  The pose is
@@ -114,6 +148,117 @@ __global__ __launch_bounds__(kThreads) void k_refine_reduce(Args a)
         for (int k = 0; k < kSums; ++k) sums[k] = s_sum[k][0];
         const int32_t wc = (a.win.half_theta * a.win.nx + a.win.half_xy) * a.win.nx + a.win.half_xy;
         finish(a.win, a.seeds[m], a.seeds[(size_t)a.M + m], a.seeds[(size_t)2 * a.M + m], wb, sb, score[wc], sums, &a.out[m]);
+    }
+}
+
+// ---- under the beam model (RB1-RB6) ------------------------------------------------------------------------------------------
+
+// Once per call: where the table row (E2) of every used beam starts.  Every reading has a row: NaN, +-inf and readings out of
+// range land where E4 puts them.
+__global__ __launch_bounds__(kThreads) void k_refine_beam_rows(BeamArgs a)
+{
+    const int u = (int)(blockIdx.x * (uint32_t)kThreads + threadIdx.x);
+    if (u >= a.nb) return;
+    const int row = mcl::obs_index_of(a.obs[(size_t)u * a.beam_stride], a.ray.res, a.ray.P);
+    a.row_base[u] = (uint32_t)row * (uint32_t)(a.ray.P + 1);
+}
+
+// The literal march of cast_ray (cpp:611-650) by a whole wave, as k_query_exact does it: lane l accumulates `current += d` l + 1
+// times as the reference's single accumulator does (the same additions in the same order, so the same bits), then the 64 lanes
+// test 64 consecutive samples at once; the first stop wins.  Every argument is wave-uniform and all 64 lanes must be here.
+__device__ __forceinline__ int wave_march_exact(const mcl::RayArgs &m, double x, double y, double angle, int lane)
+{
+    const double dx = cos(angle) * m.res, dy = sin(angle) * m.res;
+    double cx = x, cy = y;
+    for (int t = 0; t <= lane; ++t) { cx += dx; cy += dy; }            // sample lane + 1 of the sequential accumulation
+    for (int s0 = 0; s0 < m.P; s0 += 64) {
+        const int step = s0 + lane;
+        bool hit = false;
+        if (step < m.P) {
+            const int gx = (int)((cx - m.ox) / m.res), gy = (int)((cy - m.oy) / m.res);
+            hit = gx < 0 || gx >= m.W || gy < 0 || gy >= m.H || m.grid[(size_t)gy * m.W + gx] > 50;
+        }
+        const unsigned long long hits = __ballot(hit);
+        if (hits) return s0 + (__ffsll((long long)hits) - 1);
+        for (int t = 0; t < 64; ++t) { cx += dx; cy += dy; }            // 64 samples further
+    }
+    return m.P;
+}
+
+// One WAVE per window pose i = m * n_win + w, four poses per workgroup; lane l takes the used beams u = l, l + 64, ... (RB3: Q3's
+// order).  The pose (R1), its constants, its start cell and the skip distance there are the same in all 64 lanes; neighbouring
+// lanes walk neighbouring beams from that cell, the pose query's access pattern.  A round: every lane walks its beam at level 2
+// (k_query_rays' arithmetic: fp64 positions on the isotropic field, the guard) and the lanes whose ray wants the literal march
+// are balloted.  Few of them: the wave marches them one after the other (wave_march_exact).  Many (kLaneMarchMin; a pose on a
+// cell edge flags all 64): each marches its own ray (march_exact).  Both are cast_ray's additions in its order.  Then every lane
+// gathers its table entry and adds it in fp64.  No step is ever stored.  The butterfly joins the 64 lane sums; lane 0 writes
+// the score.
+__global__ __launch_bounds__(kThreads) void k_refine_beam_score(BeamArgs a)
+{
+    const mcl::RayArgs &m = a.ray;
+    const int lane = threadIdx.x & 63;
+    // (the pose index from the block index, not from a global thread index: M * n_win waves may be 2^33 threads)
+    const int32_t i = a.pose0 + (int32_t)(blockIdx.x * (uint32_t)kPosesPerBlock + (threadIdx.x >> 6));
+    if (i >= a.n_total) return;                                         // (whole waves leave together)
+    const int32_t sm = i / a.win.n_win, w = i - sm * a.win.n_win;
+    int32_t dx, dy, dt;
+    offsets(a.win, w, dx, dy, dt);
+    const double x = coord(a.seeds[sm], dx, a.win.sx);
+    const double y = coord(a.seeds[(size_t)a.M + sm], dy, a.win.sx);
+    const double th = coord(a.seeds[(size_t)2 * a.M + sm], dt, a.win.st);
+    const double4 pci = mcl::particle_constants(x, y, th, m.ox, m.oy, m.res);
+    const bool sane = (pci.z > -200000.0) && (pci.z < 200000.0) && (pci.w > -200000.0) && (pci.w < 200000.0);
+    bool walk = sane && m.force_exact != 1;                             // (a ray bound for the march anyway needs no walk)
+    const double p0x = (pci.z + 1.0 + 262144.0) + mcl::kMagic, p0y = (pci.w + 1.0 + 262144.0) + mcl::kMagic;
+    const int base = mcl::kCellBase + 262144;
+    uint32_t amb0 = 0;
+    int s_first = 1;
+    if (walk) {
+        const uint32_t lox = (uint32_t)__double2loint(p0x), loy = (uint32_t)__double2loint(p0y);
+        const int cx = (__double2hiint(p0x) & 0xFFFFF) - base, cy = (__double2hiint(p0y) & 0xFFFFF) - base;
+        amb0 = lox < loy ? lox : loy;
+        const int d = ((unsigned)cx < (unsigned)m.Wp && (unsigned)cy < (unsigned)m.Hp) ? m.dist[(size_t)cy * m.Wps + cx] : 0;
+        s_first = d > 1 ? d : 1;
+        walk = amb0 >= mcl::kGuard;                                     // (a pose on a cell edge: the walk can only lower amb)
+    }
+    double acc = 0.0;
+    unsigned n3 = 0;
+    for (int u0 = 0; u0 < a.nb; u0 += 64) {
+        const int u = u0 + lane;
+        const bool live = u < a.nb;
+        const int j = live ? u * a.beam_stride : 0;
+        int r = m.P;
+        bool exact = false;
+        if (live) {
+            uint32_t amb = amb0;
+            if (walk) {
+                const double2 cs = m.beam_cs[j];
+                const double ux = pci.x * cs.x - pci.y * cs.y, uy = pci.y * cs.x + pci.x * cs.y;
+                unsigned np = 0;
+                r = mcl::trace_fp64<false, false>(m, nullptr, 0, base, p0x, p0y, ux, uy, s_first, amb, np);
+            }
+            exact = !walk || amb < mcl::kGuard;
+        }
+        unsigned long long todo = __ballot(exact);
+        const int n_exact = __popcll(todo);
+        n3 += (unsigned)n_exact;
+        if (n_exact >= kLaneMarchMin) {                              // (wave-uniform) many: every flagged lane marches its own ray
+            if (exact) r = mcl::march_exact(m, x, y, th + (double)m.beam_angle[j]);
+            todo = 0;
+        }
+        while (todo) {                                                  // (wave-uniform: every lane is in every march)
+            const int src = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const int jj = __shfl(j, src);
+            const int rr = wave_march_exact(m, x, y, th + (double)m.beam_angle[jj], lane);
+            if (lane == src) r = rr;
+        }
+        if (live) acc += (double)a.L[(size_t)a.row_base[u] + (size_t)r];
+    }
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);   // Q3's butterfly: every lane ends with the same bits
+    if (lane == 0) {
+        a.score[i] = acc;
+        if (n3) atomicAdd(&a.hdr->level3, (unsigned long long)n3);
     }
 }
 

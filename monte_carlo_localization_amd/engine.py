@@ -52,7 +52,7 @@ EXPORTS = [
     "mcl_global_search_sequence", "mcl_host_search_sequence_offsets", "mcl_host_relative_poses",
     "mcl_default_search_stream_config", "mcl_global_search_streamed", "mcl_host_search_slabs",
     "mcl_global_search_beam", "mcl_host_search_beam_grid", "mcl_get_search_beam_table",
-    "mcl_default_refine_config", "mcl_refine_poses", "mcl_get_refine_scores", "mcl_get_refine_bytes", "mcl_host_refine_window",
+    "mcl_default_refine_config", "mcl_refine_poses", "mcl_refine_poses_beam", "mcl_get_refine_scores", "mcl_get_refine_bytes", "mcl_host_refine_window",
     "mcl_host_refine_reduce",
     "mcl_default_recovery_config", "mcl_set_recovery", "mcl_get_recovery_state", "mcl_set_recovery_state", "mcl_host_recovery_step",
     "mcl_default_likelihood_field_config", "mcl_set_likelihood_field", "mcl_get_likelihood_field", "mcl_get_likelihood_table",
@@ -269,6 +269,7 @@ def load_library(legacy=False):
         lib.mcl_default_refine_config.restype = None
         lib.mcl_refine_poses.argtypes = [C.c_void_p, C.POINTER(RefineConfig), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                          C.c_void_p, C.c_void_p]
+        lib.mcl_refine_poses_beam.argtypes = list(lib.mcl_refine_poses.argtypes)
         lib.mcl_get_refine_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         lib.mcl_get_refine_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         lib.mcl_host_refine_window.argtypes = [C.POINTER(RefineConfig), C.c_void_p, C.c_float, C.c_void_p, C.c_size_t]
@@ -1135,8 +1136,29 @@ class Engine:
         self._refine_shape = (M, int(st[0]))
         return out, dict(n_win=int(st[0]), n_poses=int(st[1]), used_beams=int(st[2]), device_bytes=int(st[3]))
 
+    def refine_poses_beam(self, poses, obs, **fields):
+        """refine_poses under the beam model (mcl_refine_poses_beam): the same window, every pose scored by the
+        table sum over cast rays that every update weights particles with -- what score_poses returns with the likelihood field
+        off -- in one kernel that stores no ray.  The likelihood field may be on or off.  Returns (records, {n_win, n_poses,
+        used_beams, device_bytes, rays, level3_rays}).  The chain from one scan to a cloud, under one model:
+            hits, _ = e.global_search_beam(obs, beam_stride=10)
+            r, _ = e.refine_poses_beam(hits["pose"], obs)
+            e.init_particles_mixture(r["mean"], r["cov"], seed_counts(r["best_log_likelihood"], n))"""
+        c = default_refine_config(**fields)
+        p = self._query_poses(poses)
+        M = p.shape[1]
+        o = _c(obs, np.float32)
+        out = np.zeros(M, REFINE_DTYPE)
+        st = np.zeros(6, np.uint64)
+        self._chk(self.lib.mcl_refine_poses_beam(self._h, C.byref(c), _p(p) if M else None, C.c_int32(M), _p(o), C.c_int32(o.size),
+                                                 _p(out) if M else None, _p(st)), "mcl_refine_poses_beam")
+        self._refine_shape = (M, int(st[0]))
+        return out, dict(n_win=int(st[0]), n_poses=int(st[1]), used_beams=int(st[2]), device_bytes=int(st[3]), rays=int(st[4]),
+                         level3_rays=int(st[5]))
+
     def refine_scores(self):
-        """The score volume of the last refine_poses (mcl_get_refine_scores): (M, n_win) doubles, window index ix fastest."""
+        """The score volume of the last refine_poses or refine_poses_beam (mcl_get_refine_scores): (M, n_win) doubles, window index
+        ix fastest."""
         shape = getattr(self, "_refine_shape", None) or (1, 1)
         out = np.empty(shape, np.float64)
         self._chk(self.lib.mcl_get_refine_scores(self._h, _p(out), C.c_size_t(out.size)), "mcl_get_refine_scores")
