@@ -1771,21 +1771,14 @@ __global__ __launch_bounds__(256) void k_rays_fix(RayArgs a)
         }
         const double2 cs = a.beam_cs[j];
         const double ux = pci.x * cs.x - pci.y * cs.y, uy = pci.y * cs.x + pci.x * cs.y;
-        const bool sane = (pci.z > -200000.0) && (pci.z < 200000.0) && (pci.w > -200000.0) && (pci.w < 200000.0);
-        const double p0x = (pci.z + 1.0 + 262144.0) + kMagic, p0y = (pci.w + 1.0 + 262144.0) + kMagic;
-        const int base = kCellBase + 262144;
+        const RayOrigin o = ray_origin(a, pci.z, pci.w);
         int r = a.P;
-        uint32_t amb = 0;
+        uint32_t amb = o.amb0;
         unsigned np = 0;
-        if (sane) {
-            const uint32_t lox = (uint32_t)__double2loint(p0x), loy = (uint32_t)__double2loint(p0y);
-            const int cx = (__double2hiint(p0x) & 0xFFFFF) - base, cy = (__double2hiint(p0y) & 0xFFFFF) - base;
-            amb = lox < loy ? lox : loy;
-            int d = ((unsigned)cx < (unsigned)a.Wp && (unsigned)cy < (unsigned)a.Hp) ? (wfield ? wfield : a.dist)[(size_t)cy * a.Wps + cx] : 0;
-            if (wfield && d == 255) d = 0;
-            r = trace_fp64<false, COUNT>(a, nullptr, 0, base, p0x, p0y, ux, uy, d > 1 ? d : 1, amb, np, wfield, wfield != nullptr);
-        }
-        if (!sane || amb < kGuard || a.force_exact == 1) {
+        if (o.sane)
+            r = trace_fp64<false, COUNT>(a, nullptr, 0, kOriginBase, o.p0x, o.p0y, ux, uy, first_skip(a, o, wfield ? wfield : a.dist, wfield != nullptr),
+                                         amb, np, wfield, wfield != nullptr);
+        if (takes_literal_march(a, o.sane, amb)) {
             // level 3, the literal march: 207 dependent steps in one thread would set the duration of this kernel, so the
             // (few) rays that need it go to k_rays_exact, which gives each of them a whole wave
             if (a.exact_list) {
@@ -1808,9 +1801,7 @@ __global__ __launch_bounds__(256) void k_rays_fix(RayArgs a)
     }
 }
 
-// Level 3 for the rays k_rays_fix handed over: the literal march of cast_ray (cpp:611-650), one WAVE per ray.  Lane l
-// accumulates `current += d` l+1 times exactly as the reference's single accumulator does (same additions in the same
-// order, so the same bits), then the 64 lanes test 64 consecutive samples at once; the first stop wins.
+// Level 3 for the rays k_rays_fix handed over: the literal march of cast_ray (cpp:611-650), one WAVE per ray (wave_march_exact_dir).
 template <bool COUNT>
 __global__ __launch_bounds__(256) void k_rays_exact(RayArgs a)
 {
@@ -1831,20 +1822,7 @@ __global__ __launch_bounds__(256) void k_rays_exact(RayArgs a)
         const int j = (int)(e & 0xFFFF);
         const double angle = a.th[i] + (double)a.beam_angle[j];
         const double dx = cos(angle) * a.res, dy = sin(angle) * a.res;
-        double cx = a.x[i], cy = a.y[i];
-        for (int t = 0; t <= lane; ++t) { cx += dx; cy += dy; }        // sample lane + 1 of the sequential accumulation
-        int r = a.P;
-        for (int base = 0; base < a.P; base += 64) {
-            const int step = base + lane;
-            bool hit = false;
-            if (step < a.P) {
-                const int gx = (int)((cx - a.ox) / a.res), gy = (int)((cy - a.oy) / a.res);
-                hit = gx < 0 || gx >= a.W || gy < 0 || gy >= a.H || a.grid[(size_t)gy * a.W + gx] > 50;
-            }
-            const unsigned long long m = __ballot(hit);
-            if (m) { r = base + (__ffsll((long long)m) - 1); break; }
-            for (int t = 0; t < 64; ++t) { cx += dx; cy += dy; }        // 64 samples further
-        }
+        const int r = wave_march_exact_dir(a, a.x[i], a.y[i], dx, dy, lane);
         if (lane == 0) {
             atomicAdd(&a.logw[p], (double)a.Lt[(size_t)r * a.bpad + j]);
             if (a.steps || a.steps16) store_step(a, i, j, r);
@@ -1983,9 +1961,10 @@ __global__ __launch_bounds__(kRayThreads, 8) void k_rays_far(RayArgs a)
         if (lane == 0) ++cnt_off;
         const double4 pci = a.slot_space ? a.pcs[p] : a.pc[p];
         const double cth = pci.x, sth = pci.y, gpx = pci.z, gpy = pci.w;
+        // (ray_origin of mcl_ray_core.h written out, and the bits must match it: through the helper this kernel spills more VGPRs)
         const bool sane = (gpx > -200000.0) && (gpx < 200000.0) && (gpy > -200000.0) && (gpy < 200000.0);
         const double p0x = (gpx + 1.0 + 262144.0) + kMagic, p0y = (gpy + 1.0 + 262144.0) + kMagic;
-        const int base = kCellBase + 262144;
+        const int base = kOriginBase;
         uint32_t amb0 = 0;
         int cx0 = 0, cy0 = 0;
         bool in0 = false;
@@ -2020,7 +1999,7 @@ __global__ __launch_bounds__(kRayThreads, 8) void k_rays_far(RayArgs a)
                         double uy = sth * cs.x + cth * cs.y;
                         r = trace_fp64<false, COUNT>(a, nullptr, 0, base, p0x, p0y, ux, uy, s0, amb, np, field);
                     }
-                    if (!sane || amb < kGuard || a.force_exact == 1) {
+                    if (takes_literal_march(a, sane, amb)) {
                         r = march_exact(a, a.x[i], a.y[i], a.th[i] + (double)a.beam_angle[j]);
                         ++cnt_exact;
                     }

@@ -1,8 +1,9 @@
 // mcl_query.h -- the pose query (mcl_query_scans / mcl_score_poses): the expected scan of K poses that are not
 // particles, and how well a scan supports each of them.  The arguments of its kernels and the kernels themselves; only
-// mcl_query.hip includes it.  A ray's step index comes from the device functions of the update's own ray stage (mcl_ray_core.h:
-// particle_constants, trace_fp64 with its guard, march_exact), so a query and a particle at the same pose agree bit for bit.
+// mcl_query.hip includes it.  A ray's step index comes from the functions the update's own ray stage calls (mcl_ray_core.h), so a
+// query and a particle at the same pose agree bit for bit.
 #pragma once
+#include "mcl_device_math.h"
 #include "mcl_engine_internal.h"
 #include "mcl_ray_core.h"
 
@@ -13,11 +14,7 @@ constexpr int32_t kMaxPoses = 65536;
 constexpr unsigned long long kListCap = 1ull << 20;   // level-3 rays of a call that get a wave each (more: marched by their own lane)
 constexpr uint32_t kObsInvalid = 0x80000000u;          // flag of a beam that is not valid (Q4) beside its table row
 
-// what the kernels count; copied to the host at the end of a call
-struct Header {
-    unsigned long long listed;      // rays appended to the level-3 list (may exceed the capacity: those were marched inline)
-    unsigned long long level3;      // rays the literal march decided
-};
+using Header = mcl::Level3Header;   // what the kernels count; copied to the host at the end of a call
 
 struct Args {
     mcl::RayArgs ray;               // the map, P, B, the beam directions and angles, force_exact: what trace_fp64 / march_exact read
@@ -37,13 +34,6 @@ struct Args {
     int32_t tol_steps;
     mcl_pose_score_t *out;
 };
-
-// sum over the 64 lanes of a wave in a fixed pattern (every lane ends with the same bits)
-__device__ __forceinline__ double wave_sum(double v)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 __device__ __forceinline__ void store_ray(const Args &a, uint32_t ray, int r)
 {
@@ -65,39 +55,28 @@ __global__ __launch_bounds__(kThreads) void k_query_rays(Args a)
     const double4 pci = mcl::particle_constants(a.x[k], a.y[k], a.th[k], m.ox, m.oy, m.res);
     const double2 cs = m.beam_cs[j];
     const double ux = pci.x * cs.x - pci.y * cs.y, uy = pci.y * cs.x + pci.x * cs.y;
-    const bool sane = (pci.z > -200000.0) && (pci.z < 200000.0) && (pci.w > -200000.0) && (pci.w < 200000.0);
-    const double p0x = (pci.z + 1.0 + 262144.0) + mcl::kMagic, p0y = (pci.w + 1.0 + 262144.0) + mcl::kMagic;
-    const int base = mcl::kCellBase + 262144;
+    const mcl::RayOrigin o = mcl::ray_origin(m, pci.z, pci.w);
     int r = m.P;
-    uint32_t amb = 0;
+    uint32_t amb = o.amb0;
     unsigned np = 0;
-    if (sane) {
-        const uint32_t lox = (uint32_t)__double2loint(p0x), loy = (uint32_t)__double2loint(p0y);
-        const int cx = (__double2hiint(p0x) & 0xFFFFF) - base, cy = (__double2hiint(p0y) & 0xFFFFF) - base;
-        amb = lox < loy ? lox : loy;
-        const int d = ((unsigned)cx < (unsigned)m.Wp && (unsigned)cy < (unsigned)m.Hp) ? m.dist[(size_t)cy * m.Wps + cx] : 0;
-        r = mcl::trace_fp64<false, false>(m, nullptr, 0, base, p0x, p0y, ux, uy, d > 1 ? d : 1, amb, np);
-    }
-    if (!sane || amb < mcl::kGuard || m.force_exact == 1) {
-        const unsigned long long slot = atomicAdd(&a.hdr->listed, 1ull);
-        if (slot < a.list_cap) { a.list[slot] = ray; return; }
+    if (o.sane)
+        r = mcl::trace_fp64<false, false>(m, nullptr, 0, mcl::kOriginBase, o.p0x, o.p0y, ux, uy, mcl::first_skip(m, o, m.dist), amb, np);
+    if (mcl::takes_literal_march(m, o.sane, amb)) {
+        if (mcl::level3_append(a.hdr, a.list, a.list_cap, (unsigned long long)ray)) return;
         r = mcl::march_exact(m, a.x[k], a.y[k], a.th[k] + (double)m.beam_angle[j]);
         atomicAdd(&a.hdr->level3, 1ull);
     }
     store_ray(a, ray, r);
 }
 
-// Level 3 for the listed rays: the literal march of cast_ray (cpp:611-650), one WAVE per ray, as k_rays_exact does it.  Lane l
-// accumulates `current += d` l + 1 times exactly as the reference's single accumulator does (the same additions in the same
-// order, so the same bits), then the 64 lanes test 64 consecutive samples at once; the first stop wins.
+// Level 3 for the listed rays: the literal march of cast_ray (cpp:611-650), one WAVE per ray (mcl::wave_march_exact_dir).
 __global__ __launch_bounds__(kThreads) void k_query_exact(Args a)
 {
     const mcl::RayArgs &m = a.ray;
     const int lane = threadIdx.x & 63;
     const unsigned long long wave_id = ((unsigned long long)blockIdx.x * kThreads + threadIdx.x) >> 6;
     const unsigned long long nwaves = ((unsigned long long)gridDim.x * kThreads) >> 6;
-    unsigned long long n = a.hdr->listed;              // (an earlier kernel's atomics: plain loads see them)
-    if (n > a.list_cap) n = a.list_cap;
+    const unsigned long long n = mcl::level3_listed(a.hdr, a.list_cap);
     unsigned long long done = 0;
     for (unsigned long long e = wave_id; e < n; e += nwaves) {
         const uint32_t ray = (uint32_t)a.list[e];
@@ -105,20 +84,7 @@ __global__ __launch_bounds__(kThreads) void k_query_exact(Args a)
         const int j = (int)(ray - k * (uint32_t)m.B);
         const double angle = a.th[k] + (double)m.beam_angle[j];
         const double dx = cos(angle) * m.res, dy = sin(angle) * m.res;
-        double cx = a.x[k], cy = a.y[k];
-        for (int t = 0; t <= lane; ++t) { cx += dx; cy += dy; }        // sample lane + 1 of the sequential accumulation
-        int r = m.P;
-        for (int s0 = 0; s0 < m.P; s0 += 64) {
-            const int step = s0 + lane;
-            bool hit = false;
-            if (step < m.P) {
-                const int gx = (int)((cx - m.ox) / m.res), gy = (int)((cy - m.oy) / m.res);
-                hit = gx < 0 || gx >= m.W || gy < 0 || gy >= m.H || m.grid[(size_t)gy * m.W + gx] > 50;
-            }
-            const unsigned long long hits = __ballot(hit);
-            if (hits) { r = s0 + (__ffsll((long long)hits) - 1); break; }
-            for (int t = 0; t < 64; ++t) { cx += dx; cy += dy; }        // 64 samples further
-        }
+        const int r = mcl::wave_march_exact_dir(m, a.x[k], a.y[k], dx, dy, lane);
         if (lane == 0) { store_ray(a, ray, r); ++done; }
     }
     if (lane == 0 && done) atomicAdd(&a.hdr->level3, done);
@@ -162,7 +128,7 @@ __global__ __launch_bounds__(kThreads) void k_query_score(Args a)
         n_agree += __popcll(__ballot(agree));
         n_miss += __popcll(__ballot(miss));
     }
-    acc = wave_sum(acc);
+    acc = mcl::wave_sum(acc);
     if (lane == 0) {
         mcl_pose_score_t s;
         s.log_likelihood = a.lf_logw ? a.lf_logw[k] : acc;

@@ -88,13 +88,7 @@ int query_cast(mcl_engine *h, mcl_query *q, Args &a, const double *poses, int32_
     std::memcpy(q->h_pose, poses, (size_t)3 * K * sizeof(double));
     HIPCHK(h, hipMemcpyAsync(q->d_pose, q->h_pose, (size_t)3 * K * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemsetAsync(q->d_hdr, 0, sizeof(Header), h->stream));
-    mcl::RayArgs &m = a.ray;
-    m.B = h->B; m.P = h->P;
-    m.beam_cs = h->d_beam_cs; m.beam_angle = h->d_angle;
-    m.grid = h->d_grid; m.W = h->W; m.H = h->H;
-    m.res = h->res; m.ox = h->ox; m.oy = h->oy;
-    m.dist = h->d_dist; m.Wp = h->Wp; m.Hp = h->Hp; m.Wps = h->Wps;
-    m.force_exact = h->cfg.debug_force_exact;
+    fill_ray_args(h, a.ray);
     a.x = q->d_pose; a.y = q->d_pose + K; a.th = q->d_pose + 2 * (size_t)K;
     a.K = K;
     a.steps = q->d_steps;
@@ -105,10 +99,9 @@ int query_cast(mcl_engine *h, mcl_query *q, Args &a, const double *poses, int32_
     const int64_t rays = (int64_t)K * h->B;
     hipLaunchKernelGGL(k_query_rays, dim3((unsigned)((rays + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream, a);
     HIPCHK(h, hipGetLastError());
-    // one wave per listed ray, as many as the list can hold at this size (the count is read on the device)
-    const int64_t waves = std::min<int64_t>(rays, (int64_t)q->d_list.cap);
-    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, (int64_t)h->num_cu * 8));
-    hipLaunchKernelGGL(k_query_exact, dim3(grid), dim3(kThreads), 0, h->stream, a);
+    // one wave per listed ray, as many as the list can hold at this size
+    const unsigned grid_exact = level3_grid(h, std::min<int64_t>(rays, (int64_t)q->d_list.cap));
+    hipLaunchKernelGGL(k_query_exact, dim3(grid_exact), dim3(kThreads), 0, h->stream, a);
     HIPCHK(h, hipGetLastError());
     return MCL_OK;
 }

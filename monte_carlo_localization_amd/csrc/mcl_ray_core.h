@@ -1,6 +1,8 @@
-// mcl_ray_core.h -- the device functions that decide a ray's step index (E3) and an observation's table row (E2), with the
-// arguments they read: what the update's ray kernels (mcl_kernels.h) and the pose query (mcl_query.h) share, so that both give
-// the same bits.  No kernels here: every translation unit with device code may include it.
+// mcl_ray_core.h -- the one statement of what decides a ray's step index (E3) at levels 2 and 3, and an observation's table row
+// (E2): the arguments, the origin set-up of the fp64 walk, the walk, the rule that sends a ray to the literal march, that march
+// by a lane and by a wave, and the list of rays waiting for it.  The update's ray kernels (mcl_kernels.h) and the side calls
+// (mcl_query.h, mcl_search_beam.h, mcl_refine.h) call these functions, so a particle and a queried pose at the same place get
+// the same bits.  Device functions only, no kernels: every translation unit with device code may include it.
 #pragma once
 #include "mcl_types.h"
 
@@ -104,12 +106,19 @@ struct RayArgs {
     int force_exact;
 };
 
-// literal restatement of cast_ray (cpp:611-650) on the int8 grid; returns the step index
-// (0..P-1) or P for "no hit within MAX_RANGE_PX samples".
-__device__ __forceinline__ int march_exact(const RayArgs &a, double x, double y, double angle)
+// the fp64 positions of levels 2 and 3 (the three precision levels are described at k_rays_skip, mcl_kernels.h)
+// fp64 fixed-point extraction: t = p + kMagic puts floor(p)+2^19 in the low 20 bits of the high
+// dword and the fraction (2^-32 units, biased by +4) in the low dword; lo < kGuard <=> within 2^-30 px.
+constexpr double kMagic = 1572864.0 + 0x1p-30;   // 1.5 * 2^20 + 2^-30
+constexpr uint32_t kGuard = 8u;
+constexpr int kCellBase = 1 << 19;
+
+// Level 3: the literal restatement of cast_ray (cpp:611-650) on the int8 grid, with its per-step displacement given; returns the
+// step index (0..P-1) or P for "no hit within MAX_RANGE_PX samples".  The displacement form exists for directions the host
+// formed (the global search under the beam model, rule B2): the products of the host's cosine and sine with the resolution,
+// so the additions are the oracle's additions.
+__device__ __forceinline__ int march_exact_dir(const RayArgs &a, double x, double y, double dx, double dy)
 {
-    double dx = cos(angle) * a.res;
-    double dy = sin(angle) * a.res;
     double cx = x, cy = y;
     for (int step = 0; step < a.P; ++step) {
         cx += dx;
@@ -122,12 +131,34 @@ __device__ __forceinline__ int march_exact(const RayArgs &a, double x, double y,
     return a.P;
 }
 
-// the fp64 positions of levels 2 and 3 (the three precision levels are described at k_rays_skip, mcl_kernels.h)
-// fp64 fixed-point extraction: t = p + kMagic puts floor(p)+2^19 in the low 20 bits of the high
-// dword and the fraction (2^-32 units, biased by +4) in the low dword; lo < kGuard <=> within 2^-30 px.
-constexpr double kMagic = 1572864.0 + 0x1p-30;   // 1.5 * 2^20 + 2^-30
-constexpr uint32_t kGuard = 8u;
-constexpr int kCellBase = 1 << 19;
+// the same with the cosine and the sine of an angle taken on the device
+__device__ __forceinline__ int march_exact(const RayArgs &a, double x, double y, double angle)
+{
+    return march_exact_dir(a, x, y, cos(angle) * a.res, sin(angle) * a.res);
+}
+
+// The same march by a whole WAVE.  Lane l accumulates `current += d` l + 1 times exactly as the reference's single accumulator
+// does (the same additions in the same order, so the same bits), then the 64 lanes test 64 consecutive samples at once; the
+// first stop wins.  Every argument but `lane` is wave-uniform and all 64 lanes must be here; every lane gets the result.  (Only
+// the displacement form: a caller with an angle forms cos(angle) * res, sin(angle) * res BEFORE it loads x and y, which
+// otherwise stay in registers across the cosine and the sine.)
+__device__ __forceinline__ int wave_march_exact_dir(const RayArgs &a, double x, double y, double dx, double dy, int lane)
+{
+    double cx = x, cy = y;
+    for (int t = 0; t <= lane; ++t) { cx += dx; cy += dy; }            // sample lane + 1 of the sequential accumulation
+    for (int s0 = 0; s0 < a.P; s0 += 64) {
+        const int step = s0 + lane;
+        bool hit = false;
+        if (step < a.P) {
+            const int gx = (int)((cx - a.ox) / a.res), gy = (int)((cy - a.oy) / a.res);
+            hit = gx < 0 || gx >= a.W || gy < 0 || gy >= a.H || a.grid[(size_t)gy * a.W + gx] > 50;
+        }
+        const unsigned long long hits = __ballot(hit);
+        if (hits) return s0 + (__ffsll((long long)hits) - 1);
+        for (int t = 0; t < 64; ++t) { cx += dx; cy += dy; }            // 64 samples further
+    }
+    return a.P;
+}
 
 // fp64 skipping march of one ray, on the LDS nibble window (LDSWIN) or on the global byte field.
 template <bool LDSWIN, bool COUNT>
@@ -161,6 +192,65 @@ __device__ __forceinline__ int trace_fp64(const RayArgs &a, const unsigned char 
         if (s > a.P) break;
     }
     return r;
+}
+
+// Where the fp64 walk of a ray from pixel position (px, py) starts: padded global coordinates shifted by 2^18, so `base` of
+// trace_fp64 is kOriginBase.  Outside the window of +-200000 px (NaN included) the position is not `sane`: the ray is marched
+// literally, amb0 is 0, `inside` is false and the cell means nothing.  (No branch on `sane` here: k_rays_fix keeps its registers.)
+constexpr int kOriginBase = kCellBase + 262144;
+struct RayOrigin {
+    double p0x, p0y;               // the position as trace_fp64 takes it
+    uint32_t amb0;                 // min of the two fractions: what the walk's `amb` starts from
+    int cx, cy;                    // the start cell in the padded field
+    bool sane, inside;             // inside: the start cell lies in the padded field
+};
+__device__ __forceinline__ RayOrigin ray_origin(const RayArgs &a, double px, double py)
+{
+    RayOrigin o;
+    o.sane = (px > -200000.0) && (px < 200000.0) && (py > -200000.0) && (py < 200000.0);
+    o.p0x = (px + 1.0 + 262144.0) + kMagic; o.p0y = (py + 1.0 + 262144.0) + kMagic;
+    const uint32_t lox = (uint32_t)__double2loint(o.p0x), loy = (uint32_t)__double2loint(o.p0y);
+    o.cx = (__double2hiint(o.p0x) & 0xFFFFF) - kOriginBase; o.cy = (__double2hiint(o.p0y) & 0xFFFFF) - kOriginBase;
+    o.amb0 = o.sane ? (lox < loy ? lox : loy) : 0u;
+    o.inside = o.sane && (unsigned)o.cx < (unsigned)a.Wp && (unsigned)o.cy < (unsigned)a.Hp;
+    return o;
+}
+
+// the first sample of the walk (trace_fp64's s0): the skip the caller's own field allows at the start cell, at least 1
+__device__ __forceinline__ int first_skip(const RayArgs &a, const RayOrigin &o, const uint8_t *field, bool wedge_coded = false)
+{
+    int d = o.inside ? field[(size_t)o.cy * a.Wps + o.cx] : 0;
+    if (wedge_coded && d == 255) d = 0;
+    return d > 1 ? d : 1;
+}
+
+// this ray takes the literal march: `amb` is what the walk left (the origin's amb0 where none ran)
+__device__ __forceinline__ bool takes_literal_march(const RayArgs &a, bool sane, uint32_t amb)
+{
+    return !sane || amb < kGuard || a.force_exact == 1;
+}
+
+// The side calls' list of rays waiting for the literal march, a wave each.  E: the entry, a ray index of the call.
+struct Level3Header {
+    unsigned long long listed;      // rays appended to the list (may exceed its capacity: those were marched inline)
+    unsigned long long level3;      // rays the literal march decided
+};
+
+// true: the ray is on the list.  false: the list is full, the lane marches its ray itself and counts it in level3.
+template <class E>
+__device__ __forceinline__ bool level3_append(Level3Header *hdr, E *list, unsigned long long cap, E ray)
+{
+    const unsigned long long slot = atomicAdd(&hdr->listed, 1ull);
+    if (slot >= cap) return false;
+    list[slot] = ray;
+    return true;
+}
+
+// entries on the list, for a later kernel (an earlier kernel's atomics: plain loads see them)
+__device__ __forceinline__ unsigned long long level3_listed(const Level3Header *hdr, unsigned long long cap)
+{
+    const unsigned long long n = hdr->listed;
+    return n > cap ? cap : n;
 }
 
 }  // namespace mcl

@@ -1,9 +1,10 @@
 // mcl_refine.h -- the pose refinement (mcl_refine_poses; mcl_refine_poses_beam, §4.18): the score of every pose
 // of a dense window around each seed pose, and per seed the best pose, the weighted mean and the covariance of its window.  The
 // arguments of its kernels and the kernels themselves; only mcl_refine.hip includes it.  A likelihood-field score comes from the
-// per-beam arithmetic of k_lfield (mcl_lfield_core.h), a beam-model score from the ray functions of the update and the pose
-// query (mcl_ray_core.h), so a window pose and a queried pose at the same place agree bit for bit under either model.
+// per-beam arithmetic of k_lfield (mcl_lfield_core.h), a beam-model score from the ray functions the update and the pose
+// query call (mcl_ray_core.h), so a window pose and a queried pose at the same place agree bit for bit under either model.
 #pragma once
+#include "mcl_device_math.h"
 #include "mcl_engine_internal.h"
 #include "mcl_lfield_core.h"
 #include "mcl_ray_core.h"
@@ -49,7 +50,7 @@ struct BeamArgs {
 };
 
 // Flagged lanes of a round from which every one of them marches its own ray (march_exact, 64 rays at once) instead of the wave
-// marching them one after the other (wave_march_exact).  The wave's march costs about 270 instruction slots per ray whatever its
+// marching them one after the other (mcl::wave_march_exact_dir).  The wave's march costs about 270 instruction slots per ray whatever its
 // length, a lane's about 60 per step of the longest flagged ray: they break even at (longest ray) / 4.5 flagged lanes, 9 to 50
 // for rays of 40 to 240 steps.  Measured on whole-wave rounds: any value from 1 to 32 gives the same time, 11
 // times shorter than the wave's march alone.
@@ -163,34 +164,12 @@ __global__ __launch_bounds__(kThreads) void k_refine_beam_rows(BeamArgs a)
     a.row_base[u] = (uint32_t)row * (uint32_t)(a.ray.P + 1);
 }
 
-// The literal march of cast_ray (cpp:611-650) by a whole wave, as k_query_exact does it: lane l accumulates `current += d` l + 1
-// times as the reference's single accumulator does (the same additions in the same order, so the same bits), then the 64 lanes
-// test 64 consecutive samples at once; the first stop wins.  Every argument is wave-uniform and all 64 lanes must be here.
-__device__ __forceinline__ int wave_march_exact(const mcl::RayArgs &m, double x, double y, double angle, int lane)
-{
-    const double dx = cos(angle) * m.res, dy = sin(angle) * m.res;
-    double cx = x, cy = y;
-    for (int t = 0; t <= lane; ++t) { cx += dx; cy += dy; }            // sample lane + 1 of the sequential accumulation
-    for (int s0 = 0; s0 < m.P; s0 += 64) {
-        const int step = s0 + lane;
-        bool hit = false;
-        if (step < m.P) {
-            const int gx = (int)((cx - m.ox) / m.res), gy = (int)((cy - m.oy) / m.res);
-            hit = gx < 0 || gx >= m.W || gy < 0 || gy >= m.H || m.grid[(size_t)gy * m.W + gx] > 50;
-        }
-        const unsigned long long hits = __ballot(hit);
-        if (hits) return s0 + (__ffsll((long long)hits) - 1);
-        for (int t = 0; t < 64; ++t) { cx += dx; cy += dy; }            // 64 samples further
-    }
-    return m.P;
-}
-
 // One WAVE per window pose i = m * n_win + w, four poses per workgroup; lane l takes the used beams u = l, l + 64, ... (RB3: Q3's
 // order).  The pose (R1), its constants, its start cell and the skip distance there are the same in all 64 lanes; neighbouring
 // lanes walk neighbouring beams from that cell, the pose query's access pattern.  A round: every lane walks its beam at level 2
 // (k_query_rays' arithmetic: fp64 positions on the isotropic field, the guard) and the lanes whose ray wants the literal march
-// are balloted.  Few of them: the wave marches them one after the other (wave_march_exact).  Many (kLaneMarchMin; a pose on a
-// cell edge flags all 64): each marches its own ray (march_exact).  Both are cast_ray's additions in its order.  Then every lane
+// are balloted.  Few of them: the wave marches them one after the other (mcl::wave_march_exact_dir).  Many (kLaneMarchMin; a pose on
+// a cell edge flags all 64): each marches its own ray (mcl::march_exact).  Both are cast_ray's additions in its order.  Then every lane
 // gathers its table entry and adds it in fp64.  No step is ever stored.  The butterfly joins the 64 lane sums; lane 0 writes
 // the score.
 __global__ __launch_bounds__(kThreads) void k_refine_beam_score(BeamArgs a)
@@ -207,20 +186,10 @@ __global__ __launch_bounds__(kThreads) void k_refine_beam_score(BeamArgs a)
     const double y = coord(a.seeds[(size_t)a.M + sm], dy, a.win.sx);
     const double th = coord(a.seeds[(size_t)2 * a.M + sm], dt, a.win.st);
     const double4 pci = mcl::particle_constants(x, y, th, m.ox, m.oy, m.res);
-    const bool sane = (pci.z > -200000.0) && (pci.z < 200000.0) && (pci.w > -200000.0) && (pci.w < 200000.0);
-    bool walk = sane && m.force_exact != 1;                             // (a ray bound for the march anyway needs no walk)
-    const double p0x = (pci.z + 1.0 + 262144.0) + mcl::kMagic, p0y = (pci.w + 1.0 + 262144.0) + mcl::kMagic;
-    const int base = mcl::kCellBase + 262144;
-    uint32_t amb0 = 0;
-    int s_first = 1;
-    if (walk) {
-        const uint32_t lox = (uint32_t)__double2loint(p0x), loy = (uint32_t)__double2loint(p0y);
-        const int cx = (__double2hiint(p0x) & 0xFFFFF) - base, cy = (__double2hiint(p0y) & 0xFFFFF) - base;
-        amb0 = lox < loy ? lox : loy;
-        const int d = ((unsigned)cx < (unsigned)m.Wp && (unsigned)cy < (unsigned)m.Hp) ? m.dist[(size_t)cy * m.Wps + cx] : 0;
-        s_first = d > 1 ? d : 1;
-        walk = amb0 >= mcl::kGuard;                                     // (a pose on a cell edge: the walk can only lower amb)
-    }
+    const mcl::RayOrigin o = mcl::ray_origin(m, pci.z, pci.w);
+    // (a ray bound for the march anyway needs no walk; from a pose on a cell edge the walk can only lower amb)
+    const bool walk = !mcl::takes_literal_march(m, o.sane, o.amb0);
+    const int s_first = mcl::first_skip(m, o, m.dist);
     double acc = 0.0;
     unsigned n3 = 0;
     for (int u0 = 0; u0 < a.nb; u0 += 64) {
@@ -230,14 +199,14 @@ __global__ __launch_bounds__(kThreads) void k_refine_beam_score(BeamArgs a)
         int r = m.P;
         bool exact = false;
         if (live) {
-            uint32_t amb = amb0;
+            uint32_t amb = o.amb0;
             if (walk) {
                 const double2 cs = m.beam_cs[j];
                 const double ux = pci.x * cs.x - pci.y * cs.y, uy = pci.y * cs.x + pci.x * cs.y;
                 unsigned np = 0;
-                r = mcl::trace_fp64<false, false>(m, nullptr, 0, base, p0x, p0y, ux, uy, s_first, amb, np);
+                r = mcl::trace_fp64<false, false>(m, nullptr, 0, mcl::kOriginBase, o.p0x, o.p0y, ux, uy, s_first, amb, np);
             }
-            exact = !walk || amb < mcl::kGuard;
+            exact = mcl::takes_literal_march(m, o.sane, amb);
         }
         unsigned long long todo = __ballot(exact);
         const int n_exact = __popcll(todo);
@@ -250,12 +219,13 @@ __global__ __launch_bounds__(kThreads) void k_refine_beam_score(BeamArgs a)
             const int src = __ffsll((long long)todo) - 1;
             todo &= todo - 1;
             const int jj = __shfl(j, src);
-            const int rr = wave_march_exact(m, x, y, th + (double)m.beam_angle[jj], lane);
+            const double angle = th + (double)m.beam_angle[jj];
+            const int rr = mcl::wave_march_exact_dir(m, x, y, cos(angle) * m.res, sin(angle) * m.res, lane);
             if (lane == src) r = rr;
         }
         if (live) acc += (double)a.L[(size_t)a.row_base[u] + (size_t)r];
     }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);   // Q3's butterfly: every lane ends with the same bits
+    acc = mcl::wave_sum(acc);                                             // Q3's butterfly: every lane ends with the same bits
     if (lane == 0) {
         a.score[i] = acc;
         if (n3) atomicAdd(&a.hdr->level3, (unsigned long long)n3);

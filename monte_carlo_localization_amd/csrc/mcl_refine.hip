@@ -164,12 +164,7 @@ int mcl_refine_poses_beam(mcl_engine_t *h, const mcl_refine_config_t *cfg, const
     mcl_refine_config_t c;
     // arguments, then where it works, then readiness (RB6)
     SIDE_TRY(refine_args(h, cfg, seeds_colmajor, M, obs, out, c));
-    if (h->cfg.weight_mode != MCL_WEIGHT_LOG) return fail(h, MCL_ERR_INVALID_ARG, "refine (beam model): weight_mode LOG only");
-    if (h->comm || h->in_group)
-        return fail(h, MCL_ERR_UNSUPPORTED, "refine (beam model): single-engine only: this engine has a communicator or belongs to a device group");
-    if (!h->have_map) return fail(h, MCL_ERR_NOT_READY, "refine (beam model): no map is set");
-    if (h->B <= 0 || !h->d_beam_cs || !h->d_angle) return fail(h, MCL_ERR_NOT_READY, "refine (beam model): no beam angles are set");
-    if (!h->d_L || !h->d_dist || !h->d_grid) return fail(h, MCL_ERR_NOT_READY, "refine (beam model): the map's tables are not built");
+    SIDE_TRY(beam_model_check(h, "refine (beam model)", true));
     if (n_beams != h->B) return fail(h, MCL_ERR_INVALID_ARG, "refine: n_beams does not match the beam angles");
     const Window win = window_of(c, h->res);
     const int64_t n_poses = (int64_t)M * win.n_win;
@@ -189,13 +184,7 @@ int mcl_refine_poses_beam(mcl_engine_t *h, const mcl_refine_config_t *cfg, const
     HIPCHK(h, hipMemsetAsync(r->d_hdr, 0, sizeof(BeamHeader), h->stream));
 
     BeamArgs b{};
-    mcl::RayArgs &m = b.ray;
-    m.B = B; m.P = h->P;
-    m.beam_cs = h->d_beam_cs; m.beam_angle = h->d_angle;
-    m.grid = h->d_grid; m.W = h->W; m.H = h->H;
-    m.res = h->res; m.ox = h->ox; m.oy = h->oy;
-    m.dist = h->d_dist; m.Wp = h->Wp; m.Hp = h->Hp; m.Wps = h->Wps;
-    m.force_exact = h->cfg.debug_force_exact;
+    fill_ray_args(h, b.ray);
     b.seeds = r->d_seeds; b.M = M; b.win = win; b.n_total = (int32_t)n_poses;
     b.obs = r->d_obs; b.beam_stride = c.beam_stride; b.nb = nb;
     b.row_base = r->d_row_base; b.L = h->d_L;

@@ -569,10 +569,9 @@ int beam_tiles_run(mcl_engine *h, mcl_search *s, mcl_sbeam::Args &a, const mcl_h
         hipLaunchKernelGGL(k_beam_table<E>, dim3((unsigned)((uint64_t)a.blocks_per_row * (uint64_t)a.M)), dim3(mcl_sbeam::kThreads), 0,
                            h->stream, a);
         HIPCHK(h, hipGetLastError());
-        // one wave per listed ray, as many as the list can hold (the count is read on the device)
-        const int64_t waves = (int64_t)std::min<unsigned long long>((unsigned long long)a.count * (unsigned long long)a.M, a.list_cap);
-        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, (int64_t)h->num_cu * 8));
-        hipLaunchKernelGGL(k_beam_table_exact<E>, dim3(grid), dim3(mcl_sbeam::kThreads), 0, h->stream, a);
+        // one wave per listed ray, as many as the list can hold
+        const unsigned grid_exact = level3_grid(h, (int64_t)std::min<unsigned long long>((unsigned long long)a.count * (unsigned long long)a.M, a.list_cap));
+        hipLaunchKernelGGL(k_beam_table_exact<E>, dim3(grid_exact), dim3(mcl_sbeam::kThreads), 0, h->stream, a);
         HIPCHK(h, hipGetLastError());
         hipLaunchKernelGGL(k_beam_score<E>, dim3((unsigned)((uint64_t)a.blocks_per_row * (uint64_t)a.n_head)), dim3(mcl_sbeam::kThreads), 0,
                            h->stream, a);
@@ -587,10 +586,7 @@ int search_beam(mcl_engine *h, const mcl_search_config_t *cfg, const float *obs,
     // B6 / B1 / B5: everything that can refuse the call, before anything is allocated for it
     mcl_search_config_t c;
     SIDE_TRY(search_check(h, cfg, obs, n_beams, max_hits, hits, n_hits, c, true));
-    if (h->cfg.weight_mode != MCL_WEIGHT_LOG) return fail(h, MCL_ERR_INVALID_ARG, "beam search: weight_mode LOG only");
-    if (h->comm || h->in_group)
-        return fail(h, MCL_ERR_UNSUPPORTED, "beam search: single-engine only: this engine has a communicator or belongs to a device group");
-    if (!h->d_L || !h->d_dist) return fail(h, MCL_ERR_NOT_READY, "beam search: the map's tables are not built");
+    SIDE_TRY(beam_model_check(h, "beam search", false));        // (search_check has asked for the map and the beam angles)
     mcl_host::SearchBeamGrid g;
     const std::string why_grid = mcl_host::search_beam_grid(h->angles.data(), h->B, c.n_headings, g);
     if (!why_grid.empty()) return fail(h, MCL_ERR_INVALID_ARG, why_grid);
@@ -628,12 +624,7 @@ int search_beam(mcl_engine *h, const mcl_search_config_t *cfg, const float *obs,
     HIPCHK(h, hipMemsetAsync(s->d_count, 0, sizeof(unsigned long long), h->stream));
     HIPCHK(h, hipMemsetAsync(s->d_bhdr, 0, sizeof(mcl_sbeam::Header), h->stream));
     mcl_sbeam::Args a{};
-    mcl::RayArgs &m = a.ray;
-    m.B = B; m.P = h->P;
-    m.grid = h->d_grid; m.W = h->W; m.H = h->H;
-    m.res = h->res; m.ox = h->ox; m.oy = h->oy;
-    m.dist = h->d_dist; m.Wp = h->Wp; m.Hp = h->Hp; m.Wps = h->Wps;
-    m.force_exact = h->cfg.debug_force_exact;
+    fill_ray_args(h, a.ray);
     a.xy = s->d_xy; a.dir = s->d_bdir;
     a.M = g.M; a.T = (int32_t)tp.T;
     a.tab = s->d_btab;

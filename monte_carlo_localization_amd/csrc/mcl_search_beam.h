@@ -2,9 +2,8 @@
 // include/mcl_hip_engine.h): the arguments of its kernels and the kernels themselves; only mcl_search.hip includes it.  All
 // headings of a lattice position share that position's rays: a tile of T positions gets a table R[m * T + t] of E3's step at
 // the M grid angles (k_beam_table, k_beam_table_exact), and a pose's score is a sum of table entries of the scan's rows
-// (k_beam_rows, k_beam_score).  A step comes from the device functions of the update's ray stage (mcl_ray_core.h: trace_fp64
-// with its guard) and, at level 3, from the literal march with the direction the host formed, so a table entry is bit for
-// bit cast_ray's step at that origin and grid angle.
+// (k_beam_rows, k_beam_score).  A step comes from the functions the update's ray stage calls (mcl_ray_core.h), at level 3 with
+// the direction the host formed (B2), so a table entry is bit for bit cast_ray's step at that origin and grid angle.
 #pragma once
 #include "mcl_engine_internal.h"
 #include "mcl_ray_core.h"
@@ -13,11 +12,7 @@ namespace mcl_sbeam {
 
 constexpr int kThreads = 256;
 
-// what the table kernels count
-struct Header {
-    unsigned long long listed;      // this tile's flagged rays (may exceed the list's capacity: those were marched inline)
-    unsigned long long level3;      // this call's rays the literal march decided
-};
+using Header = mcl::Level3Header;   // what the table kernels count: `listed` of this tile, `level3` of the whole call
 
 struct Args {
     mcl::RayArgs ray;               // the map, P, force_exact: what trace_fp64 and the march read
@@ -40,26 +35,9 @@ struct Args {
     double *score;                  // n_head x n_pos
 };
 
-// cast_ray's march (cpp:611-650) with its per-step displacement given: march_exact of mcl_ray_core.h takes the cosine and the
-// sine of an angle on the device, this one takes the products the host's cosine and sine give (B2), so the additions are the
-// oracle's additions.
-__device__ __forceinline__ int march_exact_dir(const mcl::RayArgs &a, double x, double y, double dx, double dy)
-{
-    double cx = x, cy = y;
-    for (int step = 0; step < a.P; ++step) {
-        cx += dx;
-        cy += dy;
-        const int gx = (int)((cx - a.ox) / a.res);
-        const int gy = (int)((cy - a.oy) / a.res);
-        if (gx < 0 || gx >= a.W || gy < 0 || gy >= a.H) return step;
-        if (a.grid[(size_t)gy * a.W + gx] > 50) return step;
-    }
-    return a.P;
-}
-
 // One lane per (tile position t, angle m), a workgroup = 256 consecutive positions at ONE angle: a wave is 64 neighbouring
 // origins with one direction, so its rays are near-identical and its store is 64 consecutive entries.  Levels 2 and 3 as
-// k_query_rays runs them, with the query's origin arithmetic and the uploaded direction.  Flagged rays go to the list
+// k_query_rays runs them, with the uploaded direction.  Flagged rays go to the list
 // (k_beam_table_exact gives each a wave); beyond its capacity the lane marches itself.
 template <class E>
 __global__ __launch_bounds__(kThreads) void k_beam_table(Args a)
@@ -70,33 +48,22 @@ __global__ __launch_bounds__(kThreads) void k_beam_table(Args a)
     if (mi >= (uint32_t)a.M || t >= (uint32_t)a.count) return;
     const double2 q = a.xy[(size_t)a.pos0 + t];
     const double2 u = a.dir[mi];
-    const double px = (q.x - m.ox) / m.res, py = (q.y - m.oy) / m.res;
-    const bool sane = (px > -200000.0) && (px < 200000.0) && (py > -200000.0) && (py < 200000.0);
-    const double p0x = (px + 1.0 + 262144.0) + mcl::kMagic, p0y = (py + 1.0 + 262144.0) + mcl::kMagic;
-    const int base = mcl::kCellBase + 262144;
+    const mcl::RayOrigin o = mcl::ray_origin(m, (q.x - m.ox) / m.res, (q.y - m.oy) / m.res);
     int r = m.P;
-    uint32_t amb = 0;
+    uint32_t amb = o.amb0;
     unsigned np = 0;
-    if (sane && m.force_exact != 1) {                      // (a ray bound for the list anyway needs no walk)
-        const uint32_t lox = (uint32_t)__double2loint(p0x), loy = (uint32_t)__double2loint(p0y);
-        const int cx = (__double2hiint(p0x) & 0xFFFFF) - base, cy = (__double2hiint(p0y) & 0xFFFFF) - base;
-        amb = lox < loy ? lox : loy;
-        const int d = ((unsigned)cx < (unsigned)m.Wp && (unsigned)cy < (unsigned)m.Hp) ? m.dist[(size_t)cy * m.Wps + cx] : 0;
-        r = mcl::trace_fp64<false, false>(m, nullptr, 0, base, p0x, p0y, u.x, u.y, d > 1 ? d : 1, amb, np);
-    }
+    if (o.sane && m.force_exact != 1)                      // (a ray bound for the list anyway needs no walk)
+        r = mcl::trace_fp64<false, false>(m, nullptr, 0, mcl::kOriginBase, o.p0x, o.p0y, u.x, u.y, mcl::first_skip(m, o, m.dist), amb, np);
     const uint32_t ray = mi * (uint32_t)a.T + t;
-    if (!sane || amb < mcl::kGuard || m.force_exact == 1) {
-        const unsigned long long slot = atomicAdd(&a.hdr->listed, 1ull);
-        if (slot < a.list_cap) { a.list[slot] = ray; return; }
-        r = march_exact_dir(m, q.x, q.y, u.x * m.res, u.y * m.res);
+    if (mcl::takes_literal_march(m, o.sane, amb)) {
+        if (mcl::level3_append(a.hdr, a.list, a.list_cap, ray)) return;
+        r = mcl::march_exact_dir(m, q.x, q.y, u.x * m.res, u.y * m.res);
         atomicAdd(&a.hdr->level3, 1ull);
     }
     static_cast<E *>(a.tab)[ray] = (E)r;
 }
 
-// Level 3 for the listed rays: one WAVE per ray, as k_query_exact does it.  Lane l accumulates `current += d` l + 1 times as
-// the reference's single accumulator does (the same additions in the same order), then the 64 lanes test 64 consecutive
-// samples at once; the first stop wins.
+// Level 3 for the listed rays: one WAVE per ray (mcl::wave_march_exact_dir).
 template <class E>
 __global__ __launch_bounds__(kThreads) void k_beam_table_exact(Args a)
 {
@@ -104,32 +71,17 @@ __global__ __launch_bounds__(kThreads) void k_beam_table_exact(Args a)
     const int lane = threadIdx.x & 63;
     const unsigned long long wave_id = ((unsigned long long)blockIdx.x * kThreads + threadIdx.x) >> 6;
     const unsigned long long nwaves = ((unsigned long long)gridDim.x * kThreads) >> 6;
-    unsigned long long n = a.hdr->listed;              // (an earlier kernel's atomics: plain loads see them)
-    if (n > a.list_cap) n = a.list_cap;
+    const unsigned long long n = mcl::level3_listed(a.hdr, a.list_cap);
     unsigned long long done = 0;
     for (unsigned long long e = wave_id; e < n; e += nwaves) {
         const uint32_t ray = a.list[e];
         const uint32_t mi = ray / (uint32_t)a.T, t = ray - mi * (uint32_t)a.T;
         // (never taken: the list holds what k_beam_table put there.  `ray` is the same in all 64 lanes, so the wave leaves the
-        //  iteration together and every __ballot below sees the whole wave)
+        //  iteration together and the march below has the whole wave)
         if (mi >= (uint32_t)a.M || t >= (uint32_t)a.count) continue;
         const double2 q = a.xy[(size_t)a.pos0 + t];
         const double2 u = a.dir[mi];
-        const double dx = u.x * m.res, dy = u.y * m.res;
-        double cx = q.x, cy = q.y;
-        for (int i = 0; i <= lane; ++i) { cx += dx; cy += dy; }          // sample lane + 1 of the sequential accumulation
-        int r = m.P;
-        for (int s0 = 0; s0 < m.P; s0 += 64) {
-            const int step = s0 + lane;
-            bool hit = false;
-            if (step < m.P) {
-                const int gx = (int)((cx - m.ox) / m.res), gy = (int)((cy - m.oy) / m.res);
-                hit = gx < 0 || gx >= m.W || gy < 0 || gy >= m.H || m.grid[(size_t)gy * m.W + gx] > 50;
-            }
-            const unsigned long long hits = __ballot(hit);
-            if (hits) { r = s0 + (__ffsll((long long)hits) - 1); break; }
-            for (int i = 0; i < 64; ++i) { cx += dx; cy += dy; }         // 64 samples further
-        }
+        const int r = mcl::wave_march_exact_dir(m, q.x, q.y, u.x * m.res, u.y * m.res, lane);
         if (lane == 0) { static_cast<E *>(a.tab)[ray] = (E)r; ++done; }
     }
     if (lane == 0 && done) atomicAdd(&a.hdr->level3, done);

@@ -3,7 +3,9 @@
 #pragma once
 #include "mcl_engine_internal.h"
 #include "mcl_lfield_core.h"
+#include "mcl_ray_core.h"
 
+#include <algorithm>
 #include <cmath>
 
 #define SIDE_TRY(call) MCL_TRY(call)
@@ -26,6 +28,40 @@ inline int stage_used_beams(const mcl_engine *h, int beam_stride, const float *o
 inline size_t lf_lds_bytes(const mcl_engine *h)
 {
     return h->lf_K < mcl::kLfLdsEntries ? (size_t)(h->lf_K + 1) * sizeof(float) : 0;
+}
+
+// What the ray functions (mcl_ray_core.h) read of the engine: the map, P, the beams, force_exact.  The rest of `m` stays as it is.
+inline void fill_ray_args(const mcl_engine *h, mcl::RayArgs &m)
+{
+    m.B = h->B; m.P = h->P;
+    m.beam_cs = h->d_beam_cs; m.beam_angle = h->d_angle;
+    m.grid = h->d_grid; m.W = h->W; m.H = h->H;
+    m.res = h->res; m.ox = h->ox; m.oy = h->oy;
+    m.dist = h->d_dist; m.Wp = h->Wp; m.Hp = h->Hp; m.Wps = h->Wps;
+    m.force_exact = h->cfg.debug_force_exact;
+}
+
+// workgroups (of 4 waves) of a kernel that gives every listed level-3 ray a wave, for a list that holds at most `waves` rays
+// (the count is read on the device)
+inline unsigned level3_grid(const mcl_engine *h, int64_t waves)
+{
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, (int64_t)h->num_cu * 8));
+}
+
+// What refuses a call under the beam model after its arguments (B6 / RB6): where it works, then readiness.  `who` opens every
+// message.  map_and_beams: false where the call's own argument check has asked for the map and the beam angles already.
+inline int beam_model_check(mcl_engine *h, const std::string &who, bool map_and_beams)
+{
+    using mcl_host::fail;
+    if (h->cfg.weight_mode != MCL_WEIGHT_LOG) return fail(h, MCL_ERR_INVALID_ARG, who + ": weight_mode LOG only");
+    if (h->comm || h->in_group)
+        return fail(h, MCL_ERR_UNSUPPORTED, who + ": single-engine only: this engine has a communicator or belongs to a device group");
+    if (map_and_beams) {
+        if (!h->have_map) return fail(h, MCL_ERR_NOT_READY, who + ": no map is set");
+        if (h->B <= 0 || !h->d_beam_cs || !h->d_angle) return fail(h, MCL_ERR_NOT_READY, who + ": no beam angles are set");
+    }
+    if (!h->d_L || !h->d_dist || !h->d_grid) return fail(h, MCL_ERR_NOT_READY, who + ": the map's tables are not built");
+    return MCL_OK;
 }
 
 // the score volume a call left on the device: of which map, how many poses (0: none)

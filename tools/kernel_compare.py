@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """usage: tools/kernel_compare.py <parent tree> <change tree>
 Per translation unit of both libraries (the objects build() leaves in csrc/_build/<lib>/): the gfx950 code object is taken out of
-the offload bundle, disassembled and split per kernel; metadata (llvm-readelf --notes) and ISA are compared kernel by kernel."""
+the offload bundle, disassembled and split per kernel; metadata (llvm-readelf --notes) and ISA are compared kernel by kernel.
+A kernel that only moved (another kernel of its unit changed its size) is counted apart from one whose code or metadata differs."""
 import glob
 import os
 import re
@@ -48,16 +49,24 @@ def read_kernels(tmp):
     for m in re.finditer(r"^[0-9a-f]+ <([^>]+)>:\n(.*?)(?=^\n?[0-9a-f]+ <|\Z)", dis, re.S | re.M):
         isa[m.group(1)] = m.group(2)
     return meta, isa
+def unplaced(text):
+    """a kernel's disassembly, instruction words included, without the addresses (every instruction's, and the branch targets
+    llvm-objdump resolves)"""
+    return re.sub(r"// [0-9A-F]+:", "//", re.sub(r" <[^>]+>$", "", text, flags=re.M))
 parent, change = sys.argv[1:3]
-tot = [0, 0, 0]
+tot = [0, 0, 0, 0]
 for lib in ("libmcl_hip_engine.so", "libmcl_hip_engine_legacy.so"):
     for o in sorted(glob.glob(f"{change}/monte_carlo_localization_amd/csrc/_build/{lib}/*.o")):
         tu = os.path.basename(o)
         cp, mp, ip = kernels(f"{parent}/monte_carlo_localization_amd/csrc/_build/{lib}/{tu}")
         cc, mc, ic = kernels(o)
         differ = [k for k in sorted(set(mp) | set(mc)) if mp.get(k) != mc.get(k) or ip.get(k) != ic.get(k) or k not in ip]
-        print(f"{lib:30s} {tu:18s} kernels parent {len(mp):3d} change {len(mc):3d}  differing {len(differ)}  code object bytes {'equal' if cp == cc else 'differ'}")
+        # a kernel behind one that changed its size: the same metadata and instruction words at another address
+        moved = [k for k in differ if mp.get(k) == mc.get(k) and k in ip and k in ic and unplaced(ip[k]) == unplaced(ic[k])]
+        print(f"{lib:30s} {tu:18s} kernels parent {len(mp):3d} change {len(mc):3d}  differing {len(differ) - len(moved)}  moved only {len(moved)}"
+              f"  code object bytes {'equal' if cp == cc else 'differ'}")
         for k in differ:
-            print("    DIFFERS:", k)
-        tot = [tot[0] + len(mp), tot[1] + len(mc), tot[2] + len(differ)]
-print(f"total: parent {tot[0]} kernels, change {tot[1]}, differing {tot[2]}")
+            if k not in moved:
+                print("    DIFFERS:", k)
+        tot = [tot[0] + len(mp), tot[1] + len(mc), tot[2] + len(differ) - len(moved), tot[3] + len(moved)]
+print(f"total: parent {tot[0]} kernels, change {tot[1]}, differing {tot[2]}, moved only {tot[3]}")
