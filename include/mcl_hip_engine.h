@@ -725,6 +725,40 @@ int mcl_set_recovery_state(mcl_engine_t *h, const double state[2]);
  * denom that is not > 0 or n_beams < 1. */
 int mcl_host_recovery_step(const mcl_recovery_config_t *c, const double in[2], int32_t reset, double max_logw, double sum_w,
                            double denom, int32_t n_beams, double out[2], double *p_next);
+/* The proposal of an injecting update (sensor resetting, Lenser & Veloso 2000): a Gaussian mixture -- the hits of
+ * mcl_global_search* refined by mcl_refine_poses*, say -- from which the next injecting update draws its injected children instead
+ * of from the free cells.  Off by default.
+ *   P1 components.  1 <= M <= 4096.  means: M x 3, finite.  covs: M x 9 row-major, each by G1 of mcl_init_particles_gaussian (the
+ *     same function: symmetric, positive semi-definite, zero pivots allowed).  weights: M, finite and >= 0, with an in-order double
+ *     sum s_M that is finite and > 0; NULL = all 1.  n_components = 0 clears the proposal (the other pointers are not read).
+ *     MCL_ERR_INVALID_ARG otherwise, the message naming the component; nothing changes then.
+ *   P2 thresholds.  s_k = the in-order double prefix sum of the weights; t_k = (uint64)floor((s_k / s_M) * 2^53) for k < M - 1,
+ *     t_{M-1} = 2^53.  The component of an injected child is the first k with pick < t_k, pick = bits53(v2, v3) of stream 8 (the
+ *     53 bits the uniform rule turns into a free cell).  A zero-weight component has an empty range and is never drawn.  The
+ *     device searches [0, M - 1] whatever the uploaded words hold.
+ *   P3 pose.  Child g of update u draws n0, n1 from Philox stream 10 and n2 from stream 11, counter (g, u, stream) as streams 8 / 9,
+ *     by G1's Box-Muller (u1 = (bits53(v0, v1) + 1) 2^-53, u2 = bits53(v2, v3) 2^-53; n0 = r cos(2 pi u2), n1 = r sin(2 pi u2) with
+ *     r = sqrt(-2 log u1); n2 the cosine branch of stream 11).  With the component's mean (mx, my, mt) and factor L:
+ *     x = mx + L00 n0; y = my + (L10 n0 + L11 n1); theta = normalize_angle(mt + (L20 n0 + L21 n1 + L22 n2)).  Stream 9 is not drawn.
+ *   P4 what does not change.  Which children are injected (coin < T, the same T), that an injected child skips the parent search
+ *     and the motion model, reports parent -1, is the sample KLD counts and is counted in injected_last; how the update plans its
+ *     ray stage; every non-injected child, bit for bit.
+ *   P5 one shot.  The first resampling update that runs with T > 0 consumes the proposal: the update after it injects from the free
+ *     cells again, so a proposal made from an old scan is never drawn from at a later kidnap.  Updates with T = 0, updates that keep
+ *     their particles and mcl_sensor_update leave it in place; mcl_set_map clears it; setting or initialising particles, the beams
+ *     or the recovery config does not.  Setting it changes neither S nor F and drops no captured graph.
+ *   P6 free cells.  An injecting update with a proposal in place needs no free cell (MCL_ERR_NOT_READY is the uniform rule's).
+ *   P7 MCL_ERR_UNSUPPORTED for an engine with a communicator or in a device group and for weight_mode PRODUCT, as mcl_set_recovery.
+ *     It may be set while recovery is off; it is then never consumed. */
+int mcl_set_recovery_proposal(mcl_engine_t *h, int32_t n_components, const double *means /* M x 3 */,
+                              const double *covs /* M x 9, row-major */, const double *weights /* M, NULL = all equal */);
+/* the proposal in place: *n_components (0: none), its thresholds (M words) and factors (M x 9: mean x, y, theta, L00 L10 L11 L20
+ * L21 L22).  Any output may be NULL. */
+int mcl_get_recovery_proposal(const mcl_engine_t *h, int32_t *n_components, uint64_t *thresholds, double *factors);
+/* P1 / P2 on the host, without a device: the one function the engine itself calls to form what it uploads.  thresholds and
+ * factors may be NULL (the arguments are then only checked).  MCL_ERR_INVALID_ARG as P1, and for n_components = 0. */
+int mcl_host_recovery_proposal(int32_t n_components, const double *means, const double *covs, const double *weights,
+                               uint64_t *thresholds, double *factors);
 
 /* ---- likelihood-field ("endpoint") sensor model (Probabilistic Robotics §6.4; AMCL's laser_model_type likelihood_field;
  *      DESIGN.md §4.10) ---------------------------------------------------------------------------------------------------

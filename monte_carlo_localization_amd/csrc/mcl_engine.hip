@@ -1045,6 +1045,7 @@ int mcl_set_map(mcl_engine_t *h, const int8_t *data, uint32_t width, uint32_t he
     graph_reset(h);
     if (!(resolution > 0.0f)) return fail(h, MCL_ERR_INVALID_ARG, "invalid map resolution");   // cpp:236-240
     recov_unset(h);
+    h->mix_n = 0;                           // a proposal belongs to the map its scan was matched against
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const double res = (double)resolution;                    // cpp:191
     const int P = (int)(h->cfg.max_range_m / res);            // cpp:195
@@ -1576,24 +1577,25 @@ static bool odo_args_of(const mcl_engine *h, const double action[3], mcl::OdoArg
     return true;
 }
 
-// The resampling kernel of an update: one of eight entry points, [odometry model][KLD][recovery]; the arguments follow
-// ResampleArgs in that order of the ones that are present (kld, rec, odo: null = absent).  timed: EV_RESAMPLE is the kernel's
-// stop event.
+// The resampling kernel of an update: one of twelve entry points, [odometry model][KLD][injection: none | uniform | mixture]; the
+// arguments follow ResampleArgs in that order of the ones that are present (kld, rec or mix -- never both --, odo: null = absent).
+// timed: EV_RESAMPLE is the kernel's stop event.
 static void launch_resample(mcl_engine *h, dim3 grid, size_t lds, bool timed, mcl::ResampleArgs &a, mcl::KldArgs *kld, mcl::RecArgs *rec,
-                            mcl::OdoArgs *odo)
+                            mcl::MixArgs *mix, mcl::OdoArgs *odo)
 {
-    static const void *const entry[2][2][2] = {
-        {{(const void *)mcl::k_resample_motion, (const void *)mcl::k_resample_motion_rec},
-         {(const void *)mcl::k_resample_motion_kld, (const void *)mcl::k_resample_motion_kld_rec}},
-        {{(const void *)mcl::k_resample_odo, (const void *)mcl::k_resample_odo_rec},
-         {(const void *)mcl::k_resample_odo_kld, (const void *)mcl::k_resample_odo_kld_rec}}};
+    static const void *const entry[2][2][3] = {
+        {{(const void *)mcl::k_resample_motion, (const void *)mcl::k_resample_motion_rec, (const void *)mcl::k_resample_motion_mix},
+         {(const void *)mcl::k_resample_motion_kld, (const void *)mcl::k_resample_motion_kld_rec, (const void *)mcl::k_resample_motion_kld_mix}},
+        {{(const void *)mcl::k_resample_odo, (const void *)mcl::k_resample_odo_rec, (const void *)mcl::k_resample_odo_mix},
+         {(const void *)mcl::k_resample_odo_kld, (const void *)mcl::k_resample_odo_kld_rec, (const void *)mcl::k_resample_odo_kld_mix}}};
     void *args[4];
     int na = 0;
     args[na++] = &a;
     if (kld) args[na++] = kld;
     if (rec) args[na++] = rec;
+    if (mix) args[na++] = mix;
     if (odo) args[na++] = odo;
-    const void *fn = entry[odo ? 1 : 0][kld ? 1 : 0][rec ? 1 : 0];
+    const void *fn = entry[odo ? 1 : 0][kld ? 1 : 0][mix ? 2 : (rec ? 1 : 0)];
     if (timed) {
         (void)hipExtLaunchKernel(fn, grid, dim3(256), args, lds, h->stream, nullptr, h->ev[EV_RESAMPLE], 0);
         h->ev_resample_bound = true;
@@ -1607,7 +1609,7 @@ struct Update {
     const double *action; const float *obs; int obs_stride; const double *uniforms; bool resample_and_move;
     std::chrono::steady_clock::time_point t0;
     int64_t n_par, n;                   // parents; children: every stage after the resampling kernel runs on them
-    bool kld, keep, rec;                // KLD sizes this draw | adaptive resampling keeps the set | the injecting kernel runs
+    bool kld, keep, rec, mix;           // KLD sizes this draw | adaptive resampling keeps the set | the injecting kernel runs | ... from the proposal
     uint64_t rec_thr; double prev_sum_w;
     bool tiny, graph_ok;                // the tail: one workgroup | the captured graph | (neither) launch by launch
     mcl::KldArgs kld_cur; bool obs_early;   // (resampling launch) the bins the tiny tail clears | the scan's tables are built on the second stream
@@ -1634,7 +1636,8 @@ static int plan_update(mcl_engine *h, Update &u)
     u.prev_sum_w = h->h_scalars[1];
     u.rec_thr = (h->recov_on && u.resample_and_move && !u.keep) ? recov_threshold(recov_p(h->recov_S, h->recov_F)) : 0;
     u.rec = u.rec_thr > 0;
-    if (u.rec && h->n_free == 0) return fail(h, MCL_ERR_NOT_READY, "recovery: the map has no free cell to inject particles into");
+    u.mix = u.rec && h->mix_n > 0;          // a proposal in place (mcl_set_recovery_proposal): the injected children come from it
+    if (u.rec && !u.mix && h->n_free == 0) return fail(h, MCL_ERR_NOT_READY, "recovery: the map has no free cell to inject particles into");
     // Small updates are launch-bound (about twenty launches for ~0.06 ms of kernels): once a regular update has run with these sizes
     // (graph_warm: every buffer exists) on the k_rays_skip path, one of two short tails takes its place.  Eligibility is a pure function
     // of the configuration and the sizes (choose_ray_mode), never of what the previous update happened to run: k_rays_skip chosen
@@ -1691,10 +1694,16 @@ static int launch_update_resample(mcl_engine *h, Update &u, const double *d_norm
     h->ev_resample_bound = false;
     const dim3 grid((unsigned)((n + 255) / 256));
     mcl::RecArgs rec_args{};
+    mcl::MixArgs mix_args{};
     if (u.rec) {
         rec_args.thr = u.rec_thr; rec_args.free_cells = h->d_free; rec_args.n_free = h->n_free; rec_args.W = h->W;
         rec_args.res = h->res; rec_args.ox = h->ox; rec_args.oy = h->oy;
         rec_args.count = h->d_recov_cnt + h->recov_parity; rec_args.count_next = h->d_recov_cnt + (h->recov_parity ^ 1);
+        if (u.mix) {
+            mix_args.thr = u.rec_thr; mix_args.thresholds = h->d_mix_thr; mix_args.factors = h->d_mix_fac; mix_args.n_comp = h->mix_n;
+            mix_args.count = rec_args.count; mix_args.count_next = rec_args.count_next;
+            h->mix_n = 0;                   // one shot (P5): the next injecting update draws from free space again
+        }
         h->recov_cnt_slot = h->recov_parity; h->recov_injected = -1;
         h->recov_parity ^= 1;
     }
@@ -1710,7 +1719,8 @@ static int launch_update_resample(mcl_engine *h, Update &u, const double *d_norm
     // (the motion model's scalars are plain arguments of this launch, which is outside the captured graph and the tail)
     mcl::OdoArgs odo_cur{};
     const bool odo = odo_args_of(h, u.action, odo_cur);
-    launch_resample(h, grid, cdf_lds, !u.tiny && !h->capturing, a, u.kld ? &u.kld_cur : nullptr, u.rec ? &rec_args : nullptr, odo ? &odo_cur : nullptr);
+    launch_resample(h, grid, cdf_lds, !u.tiny && !h->capturing, a, u.kld ? &u.kld_cur : nullptr, u.rec && !u.mix ? &rec_args : nullptr,
+                    u.mix ? &mix_args : nullptr, odo ? &odo_cur : nullptr);
     if (u.kld && !u.tiny) {
         const int64_t most = std::min<int64_t>(n, (int64_t)h->kld_bits);
         hipLaunchKernelGGL(mcl::k_kld_clear, dim3((unsigned)std::min<int64_t>((most + 255) / 256, 1024)), dim3(256), 0, h->stream, u.kld_cur);
@@ -2270,6 +2280,44 @@ int mcl_set_recovery_state(mcl_engine_t *h, const double state[2])
     return MCL_OK;
 }
 
+// ---- the proposal of the next injecting update (the header's P1-P7)
+int mcl_set_recovery_proposal(mcl_engine_t *h, int32_t n_components, const double *means, const double *covs, const double *weights)
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    if (n_components == 0) { h->mix_n = 0; return MCL_OK; }
+    if (h->comm || h->in_group)
+        return fail(h, MCL_ERR_UNSUPPORTED, "recovery is single-engine only: this engine has a communicator or belongs to a device group");
+    if (h->cfg.weight_mode != MCL_WEIGHT_LOG) return fail(h, MCL_ERR_UNSUPPORTED, "recovery needs weight_mode LOG");
+    if (n_components < 0 || n_components > kRecovProposalMax)
+        return fail(h, MCL_ERR_INVALID_ARG, "recovery proposal: n_components must be in [0, 4096]");
+    const size_t M = (size_t)n_components;
+    std::vector<uint64_t> thr(M);
+    std::vector<double> fac(9 * M);
+    const std::string why = recov_proposal(n_components, means, covs, weights, thr.data(), fac.data());
+    if (!why.empty()) return fail(h, MCL_ERR_INVALID_ARG, why);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    // behind whatever the stream still runs (an update's kernel may be reading the previous proposal); the buffers only ever grow
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->mix_n = 0;
+    MCL_TRY(h->d_mix_thr.reserve(h, M));
+    MCL_TRY(h->d_mix_fac.reserve(h, 9 * M));
+    HIPCHK(h, hipMemcpy(h->d_mix_thr, thr.data(), M * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->d_mix_fac, fac.data(), 9 * M * sizeof(double), hipMemcpyHostToDevice));
+    h->mix_thr.swap(thr); h->mix_fac.swap(fac);
+    h->mix_n = n_components;
+    return MCL_OK;
+}
+
+int mcl_get_recovery_proposal(const mcl_engine_t *h, int32_t *n_components, uint64_t *thresholds, double *factors)
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    if (n_components) *n_components = h->mix_n;
+    const size_t M = (size_t)h->mix_n;
+    if (thresholds && M) std::memcpy(thresholds, h->mix_thr.data(), M * sizeof(uint64_t));
+    if (factors && M) std::memcpy(factors, h->mix_fac.data(), 9 * M * sizeof(double));
+    return MCL_OK;
+}
+
 int mcl_set_likelihood_field(mcl_engine_t *h, const mcl_likelihood_field_config_t *c)
 {
     if (!h) return MCL_ERR_INVALID_ARG;
@@ -2486,7 +2534,7 @@ int mcl_host::stage_resample_launch(mcl_engine_t *h, const ParentSource &src, co
     mcl::OdoArgs odo_cur{};
     const bool odo = !index_only && odo_args_of(h, action, odo_cur);       // (an index-only pass moves nothing)
     const bool bound_before = h->ev_resample_bound;
-    launch_resample(h, dim3((unsigned)((n + 255) / 256)), 0, !index_only, a, nullptr, nullptr, odo ? &odo_cur : nullptr);
+    launch_resample(h, dim3((unsigned)((n + 255) / 256)), 0, !index_only, a, nullptr, nullptr, nullptr, odo ? &odo_cur : nullptr);
     h->ev_resample_bound = bound_before;               // (the staged flow reads EV_RESAMPLE itself)
     HIPCHK(h, hipGetLastError());
     if (a.pc_out) { const int rc_l = layout_mark(h, n); if (rc_l) return rc_l; }

@@ -273,6 +273,14 @@ struct mcl_engine {
     DevBuf<unsigned int> d_recov_cnt;        // 2 counters
     int recov_parity = 0, recov_cnt_slot = -1;
     int64_t recov_injected = 0;
+    // the proposal the next injecting update draws its injected children from (mcl_set_recovery_proposal): mix_n
+    // components (0: none -- the free cells), as uploaded (thresholds, 9 doubles per component) and the host's copy of both for
+    // the getter.  Allocated by the first call that sets one.
+    int32_t mix_n = 0;
+    std::vector<uint64_t> mix_thr;
+    std::vector<double> mix_fac;
+    DevBuf<uint64_t> d_mix_thr;
+    DevBuf<double> d_mix_fac;
     // likelihood-field sensor model (mcl_set_likelihood_field): the field and table of the current map (lf_K < 0:
     // not built), the used beams of an update's scan staged in pinned memory; last_lf: the last log-weights came from k_lfield
     bool lf_on = false, last_lf = false;

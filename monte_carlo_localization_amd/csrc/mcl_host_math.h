@@ -23,6 +23,10 @@ double recov_likelihood(const mcl_recovery_config_t &c, double max_logw, double 
 void recov_fold(const mcl_recovery_config_t &c, double &S, double &F, double l);
 double recov_p(double S, double F);
 uint64_t recov_threshold(double p);
+// the proposal of an injecting update (P1 / P2): thresholds (M words) and factors (9 doubles per component), either may be null;
+// empty when the arguments are fine, else why not (the component named)
+constexpr int32_t kRecovProposalMax = 4096;
+std::string recov_proposal(int32_t M, const double *means, const double *covs, const double *weights, uint64_t *thresholds, double *factors);
 const char *lf_invalid(const mcl_likelihood_field_config_t *c);
 int lf_cap(const mcl_likelihood_field_config_t *c, float resolution);
 void lf_table(const mcl_config_t &cfg, const mcl_likelihood_field_config_t &c, double res, int K, std::vector<float> &t);

@@ -645,6 +645,37 @@ const char *gaussian_factor(const double cov[9], double L[6])
     return nullptr;
 }
 
+// P1 / P2 of mcl_set_recovery_proposal: every component checked (its covariance by G1's own function), then the thresholds
+// t_k = floor((s_k / s_M) 2^53) of the in-order prefix sums, the last one 2^53.  Nothing is written unless everything is fine.
+std::string recov_proposal(int32_t M, const double *means, const double *covs, const double *weights, uint64_t *thresholds, double *factors)
+{
+    if (M < 1 || M > kRecovProposalMax) return "recovery proposal: n_components must be in [1, 4096]";
+    if (!means || !covs) return "recovery proposal: null means or covariances";
+    double total = 0.0;
+    for (int32_t c = 0; c < M; ++c) {
+        const std::string who = "recovery proposal, component " + std::to_string(c) + ": ";
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(means[3 * (size_t)c + k])) return who + "the mean must be finite";
+        double L[6];
+        if (const char *why = gaussian_factor(covs + 9 * (size_t)c, L)) return who + why;
+        const double w = weights ? weights[c] : 1.0;
+        if (!std::isfinite(w) || w < 0.0) return who + "the weight must be finite and >= 0";
+        total += w;
+    }
+    if (!std::isfinite(total) || !(total > 0.0)) return "recovery proposal: the sum of the weights must be finite and > 0";
+    double s = 0.0;
+    for (int32_t c = 0; c < M; ++c) {
+        s += weights ? weights[c] : 1.0;
+        if (thresholds) thresholds[c] = c == M - 1 ? (1ull << 53) : (uint64_t)std::floor((s / total) * 9007199254740992.0);
+        if (factors) {
+            double *f = factors + 9 * (size_t)c;
+            for (int k = 0; k < 3; ++k) f[k] = means[3 * (size_t)c + k];
+            (void)gaussian_factor(covs + 9 * (size_t)c, f + 3);
+        }
+    }
+    return std::string();
+}
+
 }  // namespace mcl_host
 
 using namespace mcl_host;
@@ -827,6 +858,12 @@ void mcl_default_recovery_config(mcl_recovery_config_t *c)
     if (!c) return;
     *c = mcl_recovery_config_t{};
     c->alpha_slow = 0.001; c->alpha_fast = 0.1; c->per_beam = 1;
+}
+
+int mcl_host_recovery_proposal(int32_t n_components, const double *means, const double *covs, const double *weights,
+                               uint64_t *thresholds, double *factors)
+{
+    return recov_proposal(n_components, means, covs, weights, thresholds, factors).empty() ? MCL_OK : MCL_ERR_INVALID_ARG;
 }
 
 int mcl_host_recovery_step(const mcl_recovery_config_t *c, const double in[2], int32_t reset, double max_logw, double sum_w,

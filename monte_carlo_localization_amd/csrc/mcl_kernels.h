@@ -312,11 +312,46 @@ struct RecArgs {
     unsigned int *count_next;         // the other counter, zeroed for the next injecting update
 };
 
+// The same injection from a pose mixture (mcl_set_recovery_proposal; the header's P2 / P3): the _mix kernels.  Which
+// children are injected is the _rec kernels' rule (the same coin against the same threshold); an injected child's component is the
+// first k with pick < thresholds[k], searched over [0, n_comp - 1] whatever the words hold, and its pose is G1's with the normals
+// of streams 10 / 11.
+struct MixArgs {
+    uint64_t thr;                     // injection threshold, > 0
+    const uint64_t *thresholds;       // n_comp words, non-decreasing, the last one 2^53
+    const double *factors;            // 9 doubles per component: mean x, y, theta, L00 L10 L11 L20 L21 L22
+    int n_comp;                       // >= 1
+    unsigned int *count;              // += injected children of this update
+    unsigned int *count_next;         // the other counter, zeroed for the next injecting update
+};
+
+// three standard normals of (g, counter): Box-Muller on Philox stream s_pair (n0, n1) and stream s_one (n2), as k_init_pose draws
+__device__ __forceinline__ void normals3(uint64_t g, uint32_t counter, uint32_t s_pair, uint32_t s_one, uint32_t seed_lo, uint32_t seed_hi,
+                                         double &n0, double &n1, double &n2)
+{
+    const double TWO_M53 = 1.0 / 9007199254740992.0;
+    const double TWO_PI = 2.0 * 3.14159265358979323846;
+    u32x4 o = philox4x32((uint32_t)g, counter, s_pair, (uint32_t)(g >> 32), seed_lo, seed_hi);
+    double u1 = (double)(bits53(o.v[0], o.v[1]) + 1) * TWO_M53;
+    double u2 = (double)bits53(o.v[2], o.v[3]) * TWO_M53;
+    double rad = sqrt(-2.0 * log(u1));
+    n0 = rad * cos(TWO_PI * u2);
+    n1 = rad * sin(TWO_PI * u2);
+    o = philox4x32((uint32_t)g, counter, s_one, (uint32_t)(g >> 32), seed_lo, seed_hi);
+    u1 = (double)(bits53(o.v[0], o.v[1]) + 1) * TWO_M53;
+    u2 = (double)bits53(o.v[2], o.v[3]) * TWO_M53;
+    n2 = sqrt(-2.0 * log(u1)) * cos(TWO_PI * u2);
+}
+
+// REC: 0 no injection, kRecUniform from the free cells (RecArgs), kRecMixture from the pose mixture (MixArgs)
+constexpr int kRecUniform = 1, kRecMixture = 2;
+
 // ODO: the odometry motion models (mcl_set_motion_model): the child moves by odo_step (mcl_motion.h) with the same
 // three normals instead of by the reference's arc and map-frame noise; everything else is the kernel without it.
-template <bool KLD, bool REC, bool ODO = false>
+template <bool KLD, int REC, bool ODO = false>
 __device__ __forceinline__ void resample_motion_body(const ResampleArgs &a, const KldArgs &k, const RecArgs &r,
-                                                     [[maybe_unused]] const OdoArgs &od = OdoArgs{})
+                                                     [[maybe_unused]] const OdoArgs &od = OdoArgs{},
+                                                     [[maybe_unused]] const MixArgs &mx = MixArgs{})
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char resample_lds[];
     int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -333,12 +368,32 @@ __device__ __forceinline__ void resample_motion_body(const ResampleArgs &a, cons
         __syncthreads();
         cdf = c_sh;
     }
-    if constexpr (REC) { if (m == 0) *r.count_next = 0u; }
+    if constexpr (REC == kRecUniform) { if (m == 0) *r.count_next = 0u; }
+    if constexpr (REC == kRecMixture) { if (m == 0) *mx.count_next = 0u; }
     if (m >= a.n_children) return;
     uint64_t g = (uint64_t)(a.child_first + m);
-    [[maybe_unused]] bool inj = false;        // (REC: this child is a drawn free-space pose)
+    [[maybe_unused]] bool inj = false;        // (REC: this child is a drawn free-space pose, or one drawn from the mixture)
     [[maybe_unused]] double ix = 0.0, iy = 0.0, ith = 0.0;
-    if constexpr (REC) {
+    if constexpr (REC == kRecMixture) {
+        const u32x4 o = philox4x32((uint32_t)g, a.update_idx, 8u, (uint32_t)(g >> 32), a.seed_lo, a.seed_hi);
+        inj = bits53(o.v[0], o.v[1]) < mx.thr;
+        if (inj) {
+            const uint64_t pick = bits53(o.v[2], o.v[3]);
+            int lo = 0, len = mx.n_comp - 1;             // the first k in [0, M - 2] with pick < t_k, else M - 1: never outside [0, M - 1]
+            while (len > 0) {
+                const int half = len >> 1, mid = lo + half;
+                if (!(pick < mx.thresholds[mid])) { lo = mid + 1; len = len - half - 1; }
+                else len = half;
+            }
+            const double *f = mx.factors + 9 * (size_t)lo;
+            double n0, n1, n2;
+            normals3(g, a.update_idx, 10u, 11u, a.seed_lo, a.seed_hi, n0, n1, n2);
+            ix = f[0] + f[3] * n0;                                       // G1
+            iy = f[1] + (f[4] * n0 + f[5] * n1);
+            ith = normalize_angle(f[2] + (f[6] * n0 + f[7] * n1 + f[8] * n2));
+        }
+    }
+    if constexpr (REC == kRecUniform) {
         u32x4 o = philox4x32((uint32_t)g, a.update_idx, 8u, (uint32_t)(g >> 32), a.seed_lo, a.seed_hi);
         inj = bits53(o.v[0], o.v[1]) < r.thr;
         if (inj) {
@@ -543,10 +598,11 @@ __device__ __forceinline__ void resample_motion_body(const ResampleArgs &a, cons
     }
     if (a.clr_logw_acc) a.clr_logw_acc[m] = 0.0;
     if (a.clr_far_flags) a.clr_far_flags[m] = 0u;
-    if constexpr (REC) {
+    if constexpr (REC != 0) {
         // the injected children of the wave: one atomic
         const unsigned long long injm = __ballot(inj);
-        if (injm && (threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) atomicAdd(r.count, (unsigned int)__popcll(injm));
+        unsigned int *const count = REC == kRecMixture ? mx.count : r.count;
+        if (injm && (threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) atomicAdd(count, (unsigned int)__popcll(injm));
     }
     if constexpr (KLD) {
         // the parent's pose (a kept update: the particle's own), after the child's stores (the marking's dependent loads and
@@ -575,17 +631,22 @@ __device__ __forceinline__ void resample_motion_body(const ResampleArgs &a, cons
     }
 }
 
-__global__ __launch_bounds__(256) void k_resample_motion(ResampleArgs a) { resample_motion_body<false, false>(a, KldArgs{}, RecArgs{}); }
+__global__ __launch_bounds__(256) void k_resample_motion(ResampleArgs a) { resample_motion_body<false, 0>(a, KldArgs{}, RecArgs{}); }
 // the same with the KLD bin marking (a separate instantiation: the kernel without it is the one above, unchanged)
-__global__ __launch_bounds__(256) void k_resample_motion_kld(ResampleArgs a, KldArgs k) { resample_motion_body<true, false>(a, k, RecArgs{}); }
+__global__ __launch_bounds__(256) void k_resample_motion_kld(ResampleArgs a, KldArgs k) { resample_motion_body<true, 0>(a, k, RecArgs{}); }
 // the two with recovery injection (launched only for an update whose threshold is > 0)
-__global__ __launch_bounds__(256) void k_resample_motion_rec(ResampleArgs a, RecArgs r) { resample_motion_body<false, true>(a, KldArgs{}, r); }
-__global__ __launch_bounds__(256) void k_resample_motion_kld_rec(ResampleArgs a, KldArgs k, RecArgs r) { resample_motion_body<true, true>(a, k, r); }
+__global__ __launch_bounds__(256) void k_resample_motion_rec(ResampleArgs a, RecArgs r) { resample_motion_body<false, kRecUniform>(a, KldArgs{}, r); }
+__global__ __launch_bounds__(256) void k_resample_motion_kld_rec(ResampleArgs a, KldArgs k, RecArgs r) { resample_motion_body<true, kRecUniform>(a, k, r); }
 // the four with an odometry motion model (DIFF / OMNI: one instantiation each, the model is a wave-uniform branch in odo_step)
-__global__ __launch_bounds__(256) void k_resample_odo(ResampleArgs a, OdoArgs o) { resample_motion_body<false, false, true>(a, KldArgs{}, RecArgs{}, o); }
-__global__ __launch_bounds__(256) void k_resample_odo_kld(ResampleArgs a, KldArgs k, OdoArgs o) { resample_motion_body<true, false, true>(a, k, RecArgs{}, o); }
-__global__ __launch_bounds__(256) void k_resample_odo_rec(ResampleArgs a, RecArgs r, OdoArgs o) { resample_motion_body<false, true, true>(a, KldArgs{}, r, o); }
-__global__ __launch_bounds__(256) void k_resample_odo_kld_rec(ResampleArgs a, KldArgs k, RecArgs r, OdoArgs o) { resample_motion_body<true, true, true>(a, k, r, o); }
+__global__ __launch_bounds__(256) void k_resample_odo(ResampleArgs a, OdoArgs o) { resample_motion_body<false, 0, true>(a, KldArgs{}, RecArgs{}, o); }
+__global__ __launch_bounds__(256) void k_resample_odo_kld(ResampleArgs a, KldArgs k, OdoArgs o) { resample_motion_body<true, 0, true>(a, k, RecArgs{}, o); }
+__global__ __launch_bounds__(256) void k_resample_odo_rec(ResampleArgs a, RecArgs r, OdoArgs o) { resample_motion_body<false, kRecUniform, true>(a, KldArgs{}, r, o); }
+__global__ __launch_bounds__(256) void k_resample_odo_kld_rec(ResampleArgs a, KldArgs k, RecArgs r, OdoArgs o) { resample_motion_body<true, kRecUniform, true>(a, k, r, o); }
+// the four that inject from the pose mixture (launched only for an injecting update with a proposal in place)
+__global__ __launch_bounds__(256) void k_resample_motion_mix(ResampleArgs a, MixArgs x) { resample_motion_body<false, kRecMixture>(a, KldArgs{}, RecArgs{}, OdoArgs{}, x); }
+__global__ __launch_bounds__(256) void k_resample_motion_kld_mix(ResampleArgs a, KldArgs k, MixArgs x) { resample_motion_body<true, kRecMixture>(a, k, RecArgs{}, OdoArgs{}, x); }
+__global__ __launch_bounds__(256) void k_resample_odo_mix(ResampleArgs a, MixArgs x, OdoArgs o) { resample_motion_body<false, kRecMixture, true>(a, KldArgs{}, RecArgs{}, o, x); }
+__global__ __launch_bounds__(256) void k_resample_odo_kld_mix(ResampleArgs a, KldArgs k, MixArgs x, OdoArgs o) { resample_motion_body<true, kRecMixture, true>(a, k, RecArgs{}, o, x); }
 
 // The shards' compact lists, gathered as chunks ([ccdf | crec | cidx], ccap entries each), become ONE searchable CDF: chunk r's
 // column plus the fixed-point total of the shards before it, its unused tail turned into a plateau at the shard's end value
@@ -698,18 +759,7 @@ __global__ __launch_bounds__(256) void k_init_pose(double px, double py, double 
 __device__ __forceinline__ void init_normals(uint64_t g, uint32_t init_idx, uint32_t seed_lo, uint32_t seed_hi, double &n0, double &n1,
                                              double &n2)
 {
-    const double TWO_M53 = 1.0 / 9007199254740992.0;
-    const double TWO_PI = 2.0 * 3.14159265358979323846;
-    u32x4 o = philox4x32((uint32_t)g, init_idx, 5u, (uint32_t)(g >> 32), seed_lo, seed_hi);
-    double u1 = (double)(bits53(o.v[0], o.v[1]) + 1) * TWO_M53;
-    double u2 = (double)bits53(o.v[2], o.v[3]) * TWO_M53;
-    double rad = sqrt(-2.0 * log(u1));
-    n0 = rad * cos(TWO_PI * u2);
-    n1 = rad * sin(TWO_PI * u2);
-    o = philox4x32((uint32_t)g, init_idx, 6u, (uint32_t)(g >> 32), seed_lo, seed_hi);
-    u1 = (double)(bits53(o.v[0], o.v[1]) + 1) * TWO_M53;
-    u2 = (double)bits53(o.v[2], o.v[3]) * TWO_M53;
-    n2 = sqrt(-2.0 * log(u1)) * cos(TWO_PI * u2);
+    normals3(g, init_idx, 5u, 6u, seed_lo, seed_hi, n0, n1, n2);
 }
 
 // mcl_init_particles_gaussian (G1): k_init_pose's draw with the lower Cholesky factor of the covariance as six scalars

@@ -55,6 +55,7 @@ EXPORTS = [
     "mcl_default_refine_config", "mcl_refine_poses", "mcl_refine_poses_beam", "mcl_get_refine_scores", "mcl_get_refine_bytes", "mcl_host_refine_window",
     "mcl_host_refine_reduce",
     "mcl_default_recovery_config", "mcl_set_recovery", "mcl_get_recovery_state", "mcl_set_recovery_state", "mcl_host_recovery_step",
+    "mcl_set_recovery_proposal", "mcl_get_recovery_proposal", "mcl_host_recovery_proposal",
     "mcl_default_likelihood_field_config", "mcl_set_likelihood_field", "mcl_get_likelihood_field", "mcl_get_likelihood_table",
     "mcl_host_likelihood_field", "mcl_host_likelihood_table",
     "mcl_default_motion_config", "mcl_set_motion_model", "mcl_get_motion_model", "mcl_host_motion_scalars", "mcl_host_motion_sample",
@@ -283,6 +284,9 @@ def load_library(legacy=False):
         lib.mcl_set_recovery_state.argtypes = [C.c_void_p, C.c_void_p]
         lib.mcl_host_recovery_step.argtypes = [C.POINTER(RecoveryConfig), C.c_void_p, C.c_int32, C.c_double, C.c_double,
                                                C.c_double, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]
+        lib.mcl_set_recovery_proposal.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.mcl_get_recovery_proposal.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]
+        lib.mcl_host_recovery_proposal.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mcl_default_likelihood_field_config.argtypes = [C.POINTER(LikelihoodFieldConfig)]
         lib.mcl_default_likelihood_field_config.restype = None
         lib.mcl_set_likelihood_field.argtypes = [C.c_void_p, C.POINTER(LikelihoodFieldConfig)]
@@ -348,6 +352,41 @@ def host_recovery_step(cfg: RecoveryConfig, S, F, reset, max_logw, sum_w, denom,
     if rc != MCL_OK:
         raise EngineError(f"mcl_host_recovery_step rc={rc}", rc)
     return out[0], out[1], p.value
+
+
+def _proposal_arrays(means, covs, weights):
+    """(M, means, covs, weights or None) as the C calls take them; ValueError for shapes that are not (M, 3) / (M, 3, 3) or (M, 9) / (M,)"""
+    m = _c(np.atleast_2d(np.asarray(means, np.float64)), np.float64)
+    c = _c(covs, np.float64)
+    if m.ndim != 2 or m.shape[1] != 3 or c.size != 9 * m.shape[0]:
+        raise ValueError("means must be (M, 3) and covs (M, 3, 3)")
+    w = None
+    if weights is not None:
+        w = _c(weights, np.float64).ravel()
+        if w.size != m.shape[0]:
+            raise ValueError("weights must have one entry per component")
+    return m.shape[0], m, c, w
+
+
+def host_recovery_proposal(means, covs, weights=None):
+    """What Engine.set_recovery_proposal uploads for a mixture (mcl_host_recovery_proposal, rules P1 / P2; no device needed):
+    (thresholds, factors) -- M uint64 and (M, 9) doubles (mean x, y, theta, L00 L10 L11 L20 L21 L22).  A refused mixture raises
+    EngineError; the message names the first component that is refused on its own."""
+    M, m, c, w = _proposal_arrays(means, covs, weights)
+    thr, fac = np.zeros(M, np.uint64), np.zeros((M, 9), np.float64)
+    lib = load_library()
+    rc = lib.mcl_host_recovery_proposal(C.c_int32(M), _p(m) if M else None, _p(c) if M else None, _p(w) if w is not None else None,
+                                        _p(thr) if M else None, _p(fac) if M else None)
+    if rc != MCL_OK:
+        c9 = c.reshape(M, 9) if M else c
+        one = np.ones(1)
+        for k in range(M if M <= 4096 else 0):
+            wk = _c([w[k]], np.float64) if w is not None and w[k] != 0.0 else one     # (a zero weight alone is only an empty sum)
+            mk, ck = _c(m[k], np.float64), _c(c9[k], np.float64)
+            if lib.mcl_host_recovery_proposal(C.c_int32(1), _p(mk), _p(ck), _p(wk), None, None) != MCL_OK:
+                raise EngineError(f"mcl_host_recovery_proposal rc={rc}: component {k} is refused", rc)
+        raise EngineError(f"mcl_host_recovery_proposal rc={rc}: n_components or the sum of the weights is refused", rc)
+    return thr, fac
 
 
 def default_likelihood_field_config(**over) -> LikelihoodFieldConfig:
@@ -745,6 +784,7 @@ class Engine:
         self._chk(self.lib.mcl_set_map(self._h, _p(g), C.c_uint32(W), C.c_uint32(H), C.c_float(np.float32(resolution)),
                                        C.c_double(origin_x), C.c_double(origin_y)), "mcl_set_map")
         self.map_shape = (H, W)
+        self.map_resolution = float(np.float32(resolution))
 
     @property
     def max_range_px(self) -> int:
@@ -911,6 +951,64 @@ class Engine:
         """Sets the averages (NaN = unset): restores a saved state, or forces the p of the next update."""
         st = (C.c_double * 2)(S, F)
         self._chk(self.lib.mcl_set_recovery_state(self._h, st), "mcl_set_recovery_state")
+
+    # -- the proposal of an injecting update (sensor resetting; DESIGN.md §4.19)
+    def set_recovery_proposal(self, means, covs=None, weights=None):
+        """The Gaussian mixture the next injecting update draws its injected children from (mcl_set_recovery_proposal): means
+        (M, 3), covs (M, 3, 3), weights (M,) or None for equal ones.  means=None clears it (free cells again).  One shot: the first
+        resampling update that injects consumes it."""
+        if means is None:
+            self._chk(self.lib.mcl_set_recovery_proposal(self._h, C.c_int32(0), None, None, None), "mcl_set_recovery_proposal")
+            return
+        M, m, c, w = _proposal_arrays(means, covs, weights)
+        if M == 0:
+            raise ValueError("a proposal needs at least one component (None clears it)")
+        self._chk(self.lib.mcl_set_recovery_proposal(self._h, C.c_int32(M), _p(m), _p(c), _p(w) if w is not None else None),
+                  "mcl_set_recovery_proposal")
+
+    def recovery_proposal(self):
+        """The proposal in place (mcl_get_recovery_proposal): (thresholds, factors) as host_recovery_proposal returns them, or None."""
+        n = C.c_int32()
+        self._chk(self.lib.mcl_get_recovery_proposal(self._h, C.byref(n), None, None), "mcl_get_recovery_proposal")
+        if n.value == 0:
+            return None
+        thr, fac = np.zeros(n.value, np.uint64), np.zeros((n.value, 9), np.float64)
+        self._chk(self.lib.mcl_get_recovery_proposal(self._h, None, _p(thr), _p(fac)), "mcl_get_recovery_proposal")
+        return thr, fac
+
+    def propose_from_scan(self, obs, max_hits=16, refine=True, weights="equal", cov=None, refine_fields=None, **search_fields):
+        """Sets the proposal from where the scan `obs` fits the map: the search of the sensor model in use (global_search +
+        refine_poses with the likelihood field on, else global_search_beam + refine_poses_beam; the model is never switched and an
+        error of the search propagates), hits at -inf dropped, one component per hit from the refined mean and covariance.
+        refine=False: the hit poses with the covariance `cov` (default: one lattice step, diag((stride_cells res)^2 twice,
+        (2 pi / n_headings)^2)).  weights: "equal" (the default: the same update's sensor model ranks the components anyway, and
+        with a thousand beams exp(ll - max) gives everything to one hit) or "likelihood" (seed_counts' shares).  No hit left:
+        the proposal is cleared.  Returns the hits.  `search_fields` override mcl_default_search_config, `refine_fields`
+        mcl_default_refine_config.
+            if e.recovery_state()[2] > 0: e.propose_from_scan(scan)
+            e.update(action, scan)"""
+        if weights not in ("equal", "likelihood"):
+            raise ValueError('weights must be "equal" or "likelihood"')
+        lf = self.lib.mcl_get_likelihood_table(self._h, None, C.c_size_t(0), None) == MCL_OK
+        hits, _ = (self.global_search if lf else self.global_search_beam)(obs, max_hits=max_hits, **search_fields)
+        hits = hits[np.isfinite(hits["log_likelihood"])]
+        if hits.size == 0:
+            self.set_recovery_proposal(None)
+            return hits
+        ll = hits["log_likelihood"]
+        if refine:
+            r, _ = (self.refine_poses if lf else self.refine_poses_beam)(hits["pose"], obs, **(refine_fields or {}))
+            means, covs, ll = r["mean"], r["cov"], r["best_log_likelihood"]
+        else:
+            means = hits["pose"]
+            if cov is None:
+                sc = default_search_config(**search_fields)
+                res = getattr(self, "map_resolution", 0.0)
+                cov = np.diag([(sc.stride_cells * res) ** 2, (sc.stride_cells * res) ** 2, (2.0 * np.pi / sc.n_headings) ** 2])
+            covs = np.broadcast_to(_c(cov, np.float64).reshape(3, 3), (hits.size, 3, 3))
+        w = seed_counts(ll, 1 << 30).astype(np.float64) if weights == "likelihood" else None
+        self.set_recovery_proposal(means, covs, w)
+        return hits
 
     # -- likelihood-field sensor model (off by default; DESIGN.md §4.10)
     def set_likelihood_field(self, on=True, **fields):
