@@ -11,6 +11,8 @@ import math
 
 import numpy as np
 
+from side_geometries import odd_scan, perturbed_scan, scan_at  # noqa: F401  (the fixture's helpers, shared by geometry)
+
 RES = np.float32(0.05)
 OX, OY = -3.0, -2.25
 MAX_RANGE = 12.0
@@ -41,26 +43,6 @@ def angles(orc, B):
     """B beams over the Hokuyo's 270 degrees (B = 1: the first of them)"""
     full = orc.beam_angles()
     return full[np.linspace(0, full.size - 1, B).round().astype(int)].copy() if B > 1 else full[:1].copy()
-
-
-def scan_at(orc, om, ang, pose):
-    a = float(pose[2]) + ang.astype(np.float64)
-    return orc.cast_many(om, np.full(a.size, pose[0]), np.full(a.size, pose[1]), a)[0].astype(np.float32)
-
-
-def odd_scan(scan):
-    """the scan with readings that must not count (NaN, +-inf, negative, max range and beyond) and one that must (0)"""
-    s = scan.copy()
-    for j, v in ((3, np.nan), (10, np.inf), (11, -np.inf), (17, -0.5), (23, MAX_RANGE), (29, MAX_RANGE + 1.0), (31, 0.0)):
-        if j < s.size:
-            s[j] = v
-    return s
-
-
-def perturbed_scan(orc, om, ang, pose):
-    """ranges cast by the oracle from `pose`, moved by about a millimetre (fixed seed): end points off the cell edges"""
-    scan = scan_at(orc, om, ang, pose)
-    return (scan + np.random.default_rng(7).uniform(0.0005, 0.0015, scan.size).astype(np.float32)).astype(np.float32)
 
 
 # The seed of fixtures (a) and (b): the pose of the stride-2 search lattice at cell (col 25, row 15) -- free, in the asymmetric

@@ -8,7 +8,9 @@ import numpy as np
 import pytest
 
 import lfield_ref as lr
+import side_geometries as sg
 from conftest import make_engine, tracking_cloud
+from side_geometries import lattice, odd_scan, scan_at  # noqa: F401  (the helpers these tests defined, now by geometry)
 
 pytestmark = pytest.mark.gpu
 
@@ -55,34 +57,10 @@ def angles(orc, B):
     return full[np.linspace(0, full.size - 1, B).round().astype(int)].copy() if B > 1 else full[:1].copy()
 
 
-def scan_at(orc, om, ang, pose):
-    a = float(pose[2]) + ang.astype(np.float64)
-    return orc.cast_many(om, np.full(a.size, pose[0]), np.full(a.size, pose[1]), a)[0].astype(np.float32)
-
-
-def odd_scan(scan):
-    """the scan with readings that must not count (NaN, +-inf, negative, max range and beyond) and one that must (0)"""
-    s = scan.copy()
-    for j, v in ((3, np.nan), (10, np.inf), (11, -np.inf), (17, -0.5), (23, MAX_RANGE), (29, MAX_RANGE + 1.0), (31, 0.0)):
-        if j < s.size:
-            s[j] = v
-    return s
-
-
 def lf_engine(engine_mod, m, ang, n=64, **lf_fields):
     e = make_engine(engine_mod, m, ang, n)
     e.set_likelihood_field(True, **lf_fields)
     return e
-
-
-def lattice(engine_mod, m, stride, n_head):
-    """(cells, xy, theta, poses): the lattice of S1 / S2 and its poses (n_head * n_pos, 3) in index order"""
-    cells, xy = engine_mod.host_search_lattice(m.data, m.resolution, m.origin_x, m.origin_y, stride_cells=stride)
-    theta = engine_mod.host_search_headings(n_headings=n_head)
-    poses = np.empty((n_head, cells.size, 3))
-    poses[:, :, :2] = xy[None]
-    poses[:, :, 2] = theta[:, None]
-    return cells, xy, theta, poses.reshape(-1, 3)
 
 
 def score_all(e, poses, obs):
@@ -132,8 +110,7 @@ def test_volume_is_score_poses(engine_mod, orc, small, small_oracle, stride, n_h
 # ---- 2. the volume against the independent statement
 def perturbed_scan(orc, om, ang):
     """ranges cast by the oracle from a known pose, moved by about a millimetre (fixed seed): end points off the cell edges"""
-    scan = scan_at(orc, om, ang, TRUE_POSE)
-    return (scan + np.random.default_rng(7).uniform(0.0005, 0.0015, scan.size).astype(np.float32)).astype(np.float32)
+    return sg.perturbed_scan(orc, om, ang, TRUE_POSE)
 
 
 def test_volume_is_the_restatement(engine_mod, orc, small, small_oracle):
@@ -155,30 +132,8 @@ def test_volume_is_the_restatement(engine_mod, orc, small, small_oracle):
 
 # ---- 3. the hits are S5
 def hits_ref(V, cells, stride, nms):
-    """S5 restated: the candidates' pose indices, best first.  V: (n_head, n_pos)"""
-    n_head, n_pos = V.shape
-    h0 = stride // 2
-    cells = cells.astype(np.int64)
-    ix, iy = (cells % W - h0) // stride, (cells // W - h0) // stride
-    nx, ny = (W - 1 - h0) // stride + 1, (H - 1 - h0) // stride + 1
-    pmap = np.full((ny + 2, nx + 2), -1, np.int64)           # a ring of "no position" around the lattice
-    pmap[iy + 1, ix + 1] = np.arange(n_pos)
-    idx = np.arange(n_head * n_pos).reshape(n_head, n_pos)
-    cand = V > -np.inf
-    if nms:
-        for dk in (-1, 0, 1):
-            kk = (np.arange(n_head) + dk) % n_head
-            for dy in (-1, 0, 1):
-                for dx in (-1, 0, 1):
-                    q = pmap[iy + 1 + dy, ix + 1 + dx]
-                    there = q >= 0
-                    qq = np.where(there, q, 0)
-                    Vn, jn = V[kk][:, qq], idx[kk][:, qq]
-                    is_nb = there[None, :] & (jn != idx)
-                    better = (V > Vn) | ((V == Vn) & (idx < jn))
-                    cand &= ~is_nb | better
-    c = idx[cand]
-    return c[np.lexsort((c, -V[cand]))]
+    """S5 restated on the 120 x 90 lattice of these tests: the candidates' pose indices, best first.  V: (n_head, n_pos)"""
+    return sg.hits_ref(SmallMap(), V, cells, stride, nms)
 
 
 def check_hits(engine_mod, e, small, obs, stride, n_head, nms, max_hits, beam_stride=1):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import lfield_ref as lr
+import side_geometries as sg
 from conftest import make_engine, tracking_cloud
 
 pytestmark = pytest.mark.gpu
@@ -97,18 +98,14 @@ def poses_for(m, K, seed=1):
     return p
 
 
-def scan_at(orc, om, ang, pose):
-    a = float(pose[2]) + ang.astype(np.float64)
-    return orc.cast_many(om, np.full(a.size, pose[0]), np.full(a.size, pose[1]), a)[0]
+scan_at = sg.scan_at
 
 
 def odd_scan(scan, P, res):
     """the scan with readings that are not valid (NaN, +-inf, max range and beyond) and some that are (negative: row 0)"""
-    s = scan.copy()
-    put = ((3, np.nan), (10, np.inf), (11, -np.inf), (17, -0.5), (23, MAX_RANGE), (29, MAX_RANGE + 1.0), (31, 0.0), (37, P * res))
-    for j, v in put:
-        if j < s.size:
-            s[j] = v
+    s = sg.odd_scan(scan, MAX_RANGE)
+    if 37 < s.size:
+        s[37] = P * res
     return s
 
 

@@ -10,6 +10,7 @@ import pytest
 
 import lfield_ref as lr
 import refine_ref as rr
+import side_geometries as sg
 from conftest import make_engine, tracking_cloud
 
 pytestmark = pytest.mark.gpu
@@ -37,11 +38,8 @@ def bits(a):
 
 def window_scores(engine_mod, e, seeds, obs, beam_stride=1, **fields):
     """mcl_score_poses on the window poses of mcl_host_refine_window: (M, n_win), the readings of the unused beams NaN (R2)"""
-    masked = np.asarray(obs, np.float32).copy()
-    masked[np.arange(masked.size) % beam_stride != 0] = np.nan
-    poses = np.concatenate([engine_mod.host_refine_window(s, rr.RES, **fields) for s in seeds])
-    ll = np.concatenate([e.score_poses(poses[s:s + 65536], masked)["log_likelihood"] for s in range(0, len(poses), 65536)])
-    return ll.reshape(len(seeds), -1), masked
+    ll, scored, _ = sg.window_scores(engine_mod, e, rr.SmallMap(), seeds, obs, beam_stride, **fields)
+    return ll, scored
 
 
 # ---- 1. the volume is mcl_score_poses, bit for bit; 3. the records are the host restatement's

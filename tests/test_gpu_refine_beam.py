@@ -10,6 +10,7 @@ import pytest
 
 import refine_beam_ref as rb
 import refine_ref as rr
+import side_geometries as sg
 from conftest import make_engine, tracking_cloud
 
 pytestmark = pytest.mark.gpu
@@ -32,12 +33,8 @@ def bits(a):
 def window_scores(engine_mod, e, seeds, obs, **fields):
     """mcl_score_poses (the field off: the beam model) on the window poses of mcl_host_refine_window, in chunks of <= 65536:
     (M, n_win) log-likelihoods and the rays the literal march decided, summed over the chunks"""
-    poses = np.concatenate([engine_mod.host_refine_window(s, rr.RES, **fields) for s in np.atleast_2d(seeds)])
-    ll, level3 = [], 0
-    for s in range(0, len(poses), 65536):
-        ll.append(e.score_poses(poses[s:s + 65536], obs)["log_likelihood"])
-        level3 += e.query_counters()["level3_rays"]
-    return np.concatenate(ll).reshape(len(np.atleast_2d(seeds)), -1), level3
+    ll, _, level3 = sg.window_scores(engine_mod, e, rr.SmallMap(), seeds, obs, **fields)
+    return ll, level3
 
 
 def check_records(engine_mod, r, seeds, want, **fields):

@@ -8,6 +8,7 @@ import pytest
 
 import beam_search_ref as br
 from conftest import make_engine, tracking_cloud
+from side_geometries import odd_scan
 
 pytestmark = pytest.mark.gpu
 
@@ -40,15 +41,6 @@ def angles(orc, B):
     """B beams of the Hokuyo's 1081, evenly spaced over its 270 degrees (B = 1: the first)"""
     full = orc.beam_angles()
     return full[::1080 // (B - 1)].copy() if B > 1 else full[:1].copy()
-
-
-def odd_scan(scan):
-    """the scan with readings that land in the table's edge rows (NaN, +-inf, negative, max range and beyond, 0)"""
-    s = scan.copy()
-    for j, v in ((3, np.nan), (10, np.inf), (11, -np.inf), (17, -0.5), (23, MAX_RANGE), (29, MAX_RANGE + 1.0), (31, 0.0)):
-        if j < s.size:
-            s[j] = v
-    return s
 
 
 def bits(a):

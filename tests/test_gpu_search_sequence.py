@@ -11,36 +11,11 @@ import pytest
 
 import lfield_ref as lr
 from conftest import tracking_cloud
+from side_geometries import compose, masked, scan_poses
 from test_gpu_global_search import (H, MAX_RANGE, OX, OY, RES, TRUE_POSE, W, SmallMap, angles, bits, expect, hits_ref, lattice, lf_engine,
                                     odd_scan, scan_at, score_all, small, small_oracle)  # noqa: F401  (small, small_oracle: fixtures)
 
 pytestmark = pytest.mark.gpu
-
-
-def compose(a, r):
-    """the pose r, given in the frame of the pose a, in the map frame"""
-    c, s = np.cos(a[2]), np.sin(a[2])
-    return (a[0] + c * r[0] - s * r[1], a[1] + s * r[0] + c * r[1], a[2] + r[2])
-
-
-def scan_poses(engine_mod, m, rel, stride, n_head):
-    """SQ2 in numpy: (S, n_head * n_pos, 3), the pose of every scan at every lattice pose in index order -- one IEEE add per
-    coordinate of the lattice tables and the host's offsets table, so the bits are the device's"""
-    cells, xy, theta, _ = lattice(engine_mod, m, stride, n_head)
-    off = engine_mod.host_search_sequence_offsets(rel, n_headings=n_head)             # (n_head, S, 3)
-    S = off.shape[1]
-    out = np.empty((S, n_head, cells.size, 3))
-    for s in range(S):
-        out[s, :, :, 0] = xy[None, :, 0] + off[:, s, 0][:, None]
-        out[s, :, :, 1] = xy[None, :, 1] + off[:, s, 1][:, None]
-        out[s, :, :, 2] = off[:, s, 2][:, None]
-    return out.reshape(S, -1, 3)
-
-
-def masked(scan, beam_stride):
-    m = np.array(scan, np.float32)
-    m[np.arange(m.size) % beam_stride != 0] = np.nan
-    return m
 
 
 def fold(accs):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import make_engine, tracking_cloud
+from side_geometries import compose, odd_scan, scan_at  # noqa: F401  (imported from here by other tests too)
 
 pytestmark = pytest.mark.gpu
 
@@ -52,20 +53,6 @@ def angles(orc, B):
     return full[np.linspace(0, full.size - 1, B).round().astype(int)].copy()
 
 
-def scan_at(orc, om, ang, pose):
-    a = float(pose[2]) + ang.astype(np.float64)
-    return orc.cast_many(om, np.full(a.size, pose[0]), np.full(a.size, pose[1]), a)[0].astype(np.float32)
-
-
-def odd_scan(scan):
-    """the scan with readings that must not count (NaN, +-inf, negative, max range and beyond) and one that must (0)"""
-    s = scan.copy()
-    for j, v in ((3, np.nan), (10, np.inf), (11, -np.inf), (17, -0.5), (23, MAX_RANGE), (29, MAX_RANGE + 1.0), (31, 0.0)):
-        if j < s.size:
-            s[j] = v
-    return s
-
-
 def lf_engine(engine_mod, m, ang, n=64):
     e = make_engine(engine_mod, m, ang, n)
     e.set_likelihood_field(True)
@@ -74,11 +61,6 @@ def lf_engine(engine_mod, m, ang, n=64):
 
 def bits(a):
     return np.ascontiguousarray(a, np.float64).view(np.uint64)
-
-
-def compose(a, r):
-    c, s = np.cos(a[2]), np.sin(a[2])
-    return (a[0] + c * r[0] - s * r[1], a[1] + s * r[0] + c * r[1], a[2] + r[2])
 
 
 TRUE_POSE = (OX + 25.5 * 0.05, OY + 15.5 * 0.05, 0.4)
