@@ -576,6 +576,68 @@ int mcl_host_search_beam_grid(const float *angles, int32_t n_beams, int32_t n_he
                               double *delta, double *max_dev, double *phi /* M entries, or NULL */, size_t n_phi);
 int mcl_get_search_beam_table(mcl_engine_t *h, uint16_t *out, size_t n, int64_t *first_position, int64_t *n_positions);
 
+/* ---- global search with exact pruning: bound blocks of poses, score the survivors ---------------------------
+ * mcl_global_search scores every lattice pose with every used beam.  mcl_global_search_pruned reports the same hits -- pose,
+ * log_likelihood bits and index, nms included -- from the blocks of poses an upper bound cannot rule out, and keeps no volume.
+ * The lattice, the headings, the used beams, the score and the order of the hits are S1 - S5's.  With S = block, n = n_headings:
+ *   P1 blocks.  The lattice grid (iy, ix) of S1 is cut into S x S blocks: block (by, bx) holds the lattice cells iy in [by S,
+ *     by S + S), ix in [bx S, bx S + S) that the lattice has.  A block is live iff it holds at least one position; the live blocks
+ *     are numbered b = 0 ... in row-major order of (by, bx).  A pair is (live block b, heading k), numbered k * n_blocks + b.
+ *     mcl_host_search_blocks is the plan without a device: n_blocks, the block grid nbx x nby, w of P2 and, per live block,
+ *     (bx, by, positions in it).
+ *   P2 pooled field and bound table.  w = (S - 1) * stride_cells + 2.  Dp[y][x], for low corners -(w - 1) <= x <= W - 1 and
+ *     -(w - 1) <= y <= H - 1, is the minimum of D' over the w x w window of cells whose low corner is (x, y); D' is the field D
+ *     of LF1 inside the map and K outside (a window wholly off the map in either axis is K).  Ub[k] = max over j >= k of Lf[j],
+ *     0 <= k <= K, formed on the host from the engine's table: no monotonicity of Lf is assumed.  Dp is built on the device by
+ *     two separable passes (rows, then columns) and kept per (map, field, w).  mcl_host_lf_pool (out[(y + w - 1) * (W + w - 1) +
+ *     (x + w - 1)], n == (W + w - 1) * (H + w - 1)) and mcl_host_search_bound_table (K + 1 entries) restate both on the host.
+ *   P3 the bound of a pair.  (px_lo, py_lo) and (px_hi, py_hi) are LF4's cell coordinates of S1's cell centres of the block's
+ *     first and last lattice column and row (the last clipped to the lattice).  For each used beam, in S3's order, the end point's
+ *     cell of LF4 -- the two nested fmas and the floors -- is evaluated at both corners: (lx, ly) and (hx, hy).  Both are
+ *     monotone in px and py, so the end point's cell of every pose of the block lies in [lx, hx] x [ly, hy].  If hx - lx < w and
+ *     hy - ly < w the beam's term is Ub[Dp[ly][lx]] (Ub[K] where (lx, ly) is outside Dp's range); otherwise it is Ub[0] and the
+ *     term is counted as a guard fallback (in real arithmetic hi - lo <= (S - 1) stride_cells + 1, so this is not expected).  U
+ *     is the in-order fp64 sum of the terms widened to double, from +0.0.  Every term is >= the term of every pose of the block
+ *     and rounded addition is monotone, so U >= the score of every pose of the block, compared as doubles, -inf included.
+ *     mcl_get_search_bounds copies U in pair order after a call (n == n * n_blocks); MCL_ERR_NOT_READY before one and after
+ *     mcl_set_map.
+ *   P4 rounds.  The pairs are ranked by U descending, ties by pair number.  Round 1 scores the ranks [0, n_1), n_1 =
+ *     min(first_pairs, pairs); first_pairs = 0 stands for max(1024, pairs / 64).  After a round the scored poses are marked by
+ *     S5's rule, a neighbour in an unscored pair counting as worse; c is the score of the max_hits-th best of these provisional
+ *     candidates (-inf when there are fewer) and t the U of the first unscored pair.  The call stops when nothing is unscored or
+ *     c > t: every unscored pose scores <= t, so the max_hits best provisional candidates are candidates of the whole volume and
+ *     no unscored pose is better than any of them, ties included.  Otherwise the next round scores up to n_{r+1} = max(j,
+ *     min(2 n_r, pairs)): with fewer than max_hits candidates there is no c yet and j = 0 (the doubling alone); else j is the
+ *     first rank with U < c, pairs when no rank has one.  The last possible round has scored everything.
+ *     mcl_host_search_prune_next is this schedule on the host (n_scored = 0: n_1; first_below_c: j).
+ *   P5 result.  hits[0 .. min(max_hits, C)) are exactly the first entries mcl_global_search reports for the same config and
+ *     scan, C the candidates of the whole volume; *n_hits is the number WRITTEN: the total candidate count of S5 is not known
+ *     without the whole volume.  max_hits = 0 is refused (MCL_ERR_INVALID_ARG): the call would have nothing to do.
+ *   P6 where it works.  As S8 (the likelihood-field model ON, single engine only), one scan.  MCL_ERR_INVALID_ARG also for block
+ *     outside {2, 4, 8}, first_pairs < 0, reserved != 0, pairs * S * S >= 2^31.  Read-only as S7: buffers of its own
+ *     (mcl_get_search_bytes counts them), none of the update's; one host wait per round.  The score volume of an earlier
+ *     mcl_global_search stays as it was.  Every later update and search is bit-identical to one of an engine that never called it.
+ *   stats = {n_positions, poses of the lattice, used beams, bytes of device memory this call's own buffers have asked for so far
+ *     (the pooled field, the block tables, U, the sort buffers over the pairs, the slot map, the store of scores and its sort
+ *     buffers), pairs, pairs scored, rounds, guard fallbacks}; stats may be NULL. */
+typedef struct {
+    int32_t block;                          /* S: 2, 4 or 8, default 8 (S * S <= 64: one wave scores one block)               */
+    int32_t first_pairs;                    /* >= 0, default 0 = max(1024, pairs / 64)                                         */
+    int32_t reserved[6];                    /* must be 0                                                                      */
+} mcl_search_prune_config_t;
+void mcl_default_search_prune_config(mcl_search_prune_config_t *c);
+int mcl_global_search_pruned(mcl_engine_t *h, const mcl_search_config_t *c /* NULL = the defaults */,
+                             const mcl_search_prune_config_t *pc /* NULL = the defaults */, const float *obs, int32_t n_beams,
+                             int32_t max_hits, mcl_search_hit_t *hits, int64_t *n_hits, uint64_t stats[8]);
+int mcl_get_search_bounds(mcl_engine_t *h, double *out, size_t n);
+/* P1 / P2 / P4 on the host, without a device.  blocks: n x 3 (bx, by, positions) when given, n must then equal *n_blocks. */
+int mcl_host_search_blocks(const mcl_search_config_t *c, const mcl_search_prune_config_t *pc, const int8_t *data, uint32_t width,
+                           uint32_t height, int32_t *n_blocks, int32_t *w, int32_t *nbx, int32_t *nby, int32_t *blocks, size_t n);
+int mcl_host_lf_pool(const uint16_t *D, uint32_t width, uint32_t height, int32_t K, int32_t w, uint16_t *out, size_t n);
+int mcl_host_search_bound_table(const float *lf, int32_t K, float *ub /* K + 1 entries */);
+int mcl_host_search_prune_next(const mcl_search_prune_config_t *pc, int64_t pairs, int64_t n_scored, int64_t first_below_c,
+                               int64_t *n_next);
+
 /* ---- pose refinement: a dense local window around each seed pose, scored against one scan (correlative scan matching on the
  *      likelihood field) ---------------------------------------------------------------------------------
  * A hit of mcl_global_search sits on the search's lattice, a cluster mean or an /initialpose is only roughly right.  For each of

@@ -664,6 +664,7 @@ int lf_build(mcl_engine *h)
     while (reach > 0 && (reach - 1) * (reach - 1) >= K) --reach;
     lf_table(h->cfg, h->lf, h->res, K, h->lf_tab);
     h->lf_K = -1;                                                         // until both buffers hold this map's
+    h->lf_epoch++;
     h->d_lf_D.drop(); h->d_lf_tab.drop();
     const size_t cells = (size_t)h->W * h->H;
     MCL_TRY(h->d_lf_D.reserve(h, cells));

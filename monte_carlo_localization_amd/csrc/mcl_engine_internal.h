@@ -286,6 +286,7 @@ struct mcl_engine {
     bool lf_on = false, last_lf = false;
     mcl_likelihood_field_config_t lf{};
     int lf_K = -1;
+    unsigned long long lf_epoch = 0;    // counts the fields built (what the pruned search pools belongs to one of them)
     DevBuf<uint16_t> d_lf_D;
     DevBuf<float> d_lf_tab;
     std::vector<float> lf_tab;

@@ -68,5 +68,17 @@ struct SearchBeamTiles {
 };
 constexpr uint64_t kSearchBeamDefaultBudget = 256ull << 20;
 std::string search_beam_tiles(int64_t n_positions, int32_t M, int32_t max_range_px, uint64_t budget_bytes, SearchBeamTiles &t);
+// The search with exact pruning (mcl_global_search_pruned).  P1: the live blocks of a lattice (its pmap, ny x nx)
+// in row-major order of (by, bx); P2: w, the pooled field and the bound table; P4: the round schedule.
+struct SearchBlocks {
+    int32_t S = 0, w = 0, nbx = 0, nby = 0, n_blocks = 0;
+    std::vector<int32_t> blk;               // 3 per live block: bx, by, positions in it
+    std::vector<int32_t> bmap;              // nby x nbx: (by, bx) -> live block, -1: none
+};
+const char *search_prune_invalid(const mcl_search_config_t *c, const mcl_search_prune_config_t *pc);
+void search_blocks(int S, int stride, const int32_t *pmap, int nx, int ny, SearchBlocks &out);
+void lf_pool(const uint16_t *D, int W, int H, int K, int w, uint16_t *out);             // (H + w - 1) x (W + w - 1)
+void search_bound_table(const float *lf, int K, float *ub);                             // K + 1 entries
+int64_t search_prune_next(const mcl_search_prune_config_t &pc, int64_t pairs, int64_t n_scored, int64_t first_below_c);
 const char *refine_invalid(const mcl_refine_config_t *c);
 }  // namespace mcl_host

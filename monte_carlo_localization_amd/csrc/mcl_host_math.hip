@@ -598,6 +598,76 @@ std::string search_slabs(const mcl_search_config_t *c, const mcl_search_stream_c
     return std::string();
 }
 
+// ---- the search with exact pruning (mcl_global_search_pruned): the blocks of P1, the pooled field and the bound
+// table of P2, the rounds of P4
+const char *search_prune_invalid(const mcl_search_config_t *c, const mcl_search_prune_config_t *pc)
+{
+    if (pc->block != 2 && pc->block != 4 && pc->block != 8) return "pruned search: block must be 2, 4 or 8";
+    if (pc->first_pairs < 0) return "pruned search: first_pairs must be >= 0";
+    for (int i = 0; i < 6; ++i)
+        if (pc->reserved[i] != 0) return "pruned search: reserved must be 0";
+    if ((int64_t)(pc->block - 1) * (int64_t)c->stride_cells + 2 > 65536) return "pruned search: the window (block - 1) * stride_cells + 2 must be at most 65536 cells";
+    return nullptr;
+}
+
+void search_blocks(int S, int stride, const int32_t *pmap, int nx, int ny, SearchBlocks &out)
+{
+    out = SearchBlocks{};
+    out.S = S;
+    out.w = (S - 1) * stride + 2;
+    out.nbx = (nx + S - 1) / S;
+    out.nby = (ny + S - 1) / S;
+    out.bmap.assign((size_t)out.nbx * (size_t)out.nby, -1);
+    for (int by = 0; by < out.nby; ++by)
+        for (int bx = 0; bx < out.nbx; ++bx) {
+            int32_t held = 0;
+            for (int iy = by * S; iy < std::min(ny, by * S + S); ++iy)
+                for (int ix = bx * S; ix < std::min(nx, bx * S + S); ++ix)
+                    if (pmap[(size_t)iy * (size_t)nx + (size_t)ix] >= 0) ++held;
+            if (!held) continue;
+            out.bmap[(size_t)by * (size_t)out.nbx + (size_t)bx] = out.n_blocks++;
+            out.blk.push_back(bx); out.blk.push_back(by); out.blk.push_back(held);
+        }
+}
+
+// rows, then columns, as the device's two passes
+void lf_pool(const uint16_t *D, int W, int H, int K, int w, uint16_t *out)
+{
+    const int Wp = W + w - 1, Hp = H + w - 1;
+    std::vector<uint16_t> R((size_t)Wp * (size_t)H);
+    for (int y = 0; y < H; ++y)
+        for (int xs = 0; xs < Wp; ++xs) {
+            int best = K;
+            for (int x = std::max(0, xs - (w - 1)); x <= std::min(W - 1, xs); ++x) best = std::min(best, (int)D[(size_t)y * W + x]);
+            R[(size_t)y * Wp + xs] = (uint16_t)best;
+        }
+    for (int ys = 0; ys < Hp; ++ys)
+        for (int xs = 0; xs < Wp; ++xs) {
+            int best = K;
+            for (int y = std::max(0, ys - (w - 1)); y <= std::min(H - 1, ys); ++y) best = std::min(best, (int)R[(size_t)y * Wp + xs]);
+            out[(size_t)ys * Wp + xs] = (uint16_t)best;
+        }
+}
+
+void search_bound_table(const float *lf, int K, float *ub)
+{
+    float m = lf[K];
+    for (int k = K; k >= 0; --k) {
+        if (lf[k] > m) m = lf[k];
+        ub[k] = m;
+    }
+}
+
+int64_t search_prune_next(const mcl_search_prune_config_t &pc, int64_t pairs, int64_t n_scored, int64_t first_below_c)
+{
+    if (n_scored <= 0) {
+        const int64_t first = pc.first_pairs > 0 ? (int64_t)pc.first_pairs : std::max<int64_t>(1024, pairs / 64);
+        return std::min(first, pairs);
+    }
+    const int64_t twice = n_scored > pairs / 2 ? pairs : std::min(2 * n_scored, pairs);
+    return std::max(std::min(first_below_c, pairs), twice);
+}
+
 // ---- the pose refinement (mcl_refine_poses): its config check (R7)
 const char *refine_invalid(const mcl_refine_config_t *c)
 {
@@ -988,6 +1058,62 @@ int mcl_host_search_slabs(const mcl_search_config_t *c, const mcl_search_stream_
     if (slab_headings) *slab_headings = plan.G;
     if (n_slabs) *n_slabs = plan.n_slabs;
     if (bytes) *bytes = plan.bytes;
+    return MCL_OK;
+}
+
+void mcl_default_search_prune_config(mcl_search_prune_config_t *c)
+{
+    if (!c) return;
+    *c = mcl_search_prune_config_t{};
+    c->block = 8; c->first_pairs = 0;
+}
+
+int mcl_host_search_blocks(const mcl_search_config_t *c, const mcl_search_prune_config_t *pc, const int8_t *data, uint32_t width,
+                           uint32_t height, int32_t *n_blocks, int32_t *w, int32_t *nbx, int32_t *nby, int32_t *blocks, size_t n)
+{
+    mcl_search_prune_config_t d;
+    mcl_default_search_prune_config(&d);
+    if (!pc) pc = &d;
+    if (!c || search_invalid(c) || search_prune_invalid(c, pc) || !data || width == 0 || height == 0 || width > 200000 || height > 200000)
+        return MCL_ERR_INVALID_ARG;
+    std::vector<int32_t> pmap;
+    int nx = 0, ny = 0;
+    search_lattice(c->stride_cells, data, (int)width, (int)height, 1.0, 0.0, 0.0, nullptr, nullptr, nullptr, &pmap, nx, ny);
+    SearchBlocks b;
+    search_blocks(pc->block, c->stride_cells, pmap.data(), nx, ny, b);
+    if (n_blocks) *n_blocks = b.n_blocks;
+    if (w) *w = b.w;
+    if (nbx) *nbx = b.nbx;
+    if (nby) *nby = b.nby;
+    if (!blocks) return MCL_OK;
+    if (n != (size_t)b.n_blocks) return MCL_ERR_INVALID_ARG;
+    if (n) std::memcpy(blocks, b.blk.data(), n * 3 * sizeof(int32_t));
+    return MCL_OK;
+}
+
+int mcl_host_lf_pool(const uint16_t *D, uint32_t width, uint32_t height, int32_t K, int32_t w, uint16_t *out, size_t n)
+{
+    if (!D || !out || width == 0 || height == 0 || width > 200000 || height > 200000 || K < 0 || K > 65535 || w < 1 || w > 65536 ||
+        n != ((size_t)width + (size_t)w - 1) * ((size_t)height + (size_t)w - 1))
+        return MCL_ERR_INVALID_ARG;
+    lf_pool(D, (int)width, (int)height, K, w, out);
+    return MCL_OK;
+}
+
+int mcl_host_search_bound_table(const float *lf, int32_t K, float *ub)
+{
+    if (!lf || !ub || K < 0 || K > 65535) return MCL_ERR_INVALID_ARG;
+    search_bound_table(lf, K, ub);
+    return MCL_OK;
+}
+
+int mcl_host_search_prune_next(const mcl_search_prune_config_t *pc, int64_t pairs, int64_t n_scored, int64_t first_below_c, int64_t *n_next)
+{
+    mcl_search_prune_config_t d;
+    mcl_default_search_prune_config(&d);
+    if (!pc) pc = &d;
+    if (!n_next || pairs < 1 || n_scored < 0 || n_scored > pairs || first_below_c < 0 || pc->first_pairs < 0) return MCL_ERR_INVALID_ARG;
+    *n_next = search_prune_next(*pc, pairs, n_scored, first_below_c);
     return MCL_OK;
 }
 

@@ -24,8 +24,18 @@
 //              k_beam_table_exact  one wave per listed ray: the literal march
 //              k_beam_score        one lane per pose: the in-order sum of the rows' entries at the tile's steps
 //   then k_search_mark, the sort and the copies as above (search_finish)
+// mcl_global_search_pruned (§4.20) reports mcl_global_search's hits from the blocks of poses a bound cannot rule out:
+//   (once per map, field, w)   k_lf_pool_rows, k_lf_pool_cols: the pooled field Dp
+//   k_search_bound        one lane per (block, heading) pair: U
+//   radix sort            the pairs, U descending, ties by pair; k_search_rank: the slot map
+//   per round: k_search_score_block  one wave per pair of the round's ranks: its S x S scores into the store
+//              k_search_mark_block   S5 over the scored pairs, an unscored neighbour counting as worse
+//              two radix sorts       the store's entries by index, then stably by key: the candidates, best first
+//              k_search_decide       c, stop or not, the first rank below c
+//              (copy)                the round's state and the first max_hits entries; the round's one host wait
 #include "mcl_search.h"
 #include "mcl_search_beam.h"
+#include "mcl_search_pruned.h"
 #include "mcl_side_buffers.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -63,6 +73,34 @@ struct BeamTable {
     unsigned long long epoch = 0;
     int32_t M = 0, entry_bytes = 0;
     int64_t T = 0, first = 0, n = 0;
+};
+
+// the buffers of a pruned search (§4.20), kept between calls: the pooled field of one (map, field, w), the block tables of one
+// (lattice, S), the bounds of the last call, the store of scores and its sort buffers (grown by rounds, never beyond the volume)
+struct PruneBufs {
+    size_t bytes = 0;                            // what these buffers have asked of the device so far
+    unsigned long long pool_map = 0, pool_lf = 0;
+    int pool_w = 0;                              // 0: no pooled field
+    DevBuf<uint16_t> d_R, d_Dp;                  // the row pass's output, Dp
+    DevBuf<float> d_ub;
+    unsigned long long blk_epoch = 0;            // lattice_epoch of the block tables (0: none)
+    int blk_stride = 0, blk_S = 0;
+    mcl_host::SearchBlocks plan;
+    DevBuf<double4> d_corner;
+    DevBuf<int2> d_blk;
+    DevBuf<int32_t> d_bmap;
+    DevBuf<double> d_U;
+    DevBuf<uint64_t> d_ukey[2];
+    DevBuf<uint32_t> d_upair[2], d_rank;
+    Volume bounds;                               // what d_U holds: of which map, how many pairs
+    DevBuf<double> store;
+    DevBuf<uint64_t> ckey[2];
+    DevBuf<uint32_t> cval[2];
+    DevBuf<char> tmp;                            // the sorts' scratch
+    DevBuf<unsigned long long> d_guard;
+    HostBuf<unsigned long long> h_guard;
+    DevBuf<mcl_prune::Round> d_round;
+    HostBuf<mcl_prune::Round> h_round;
 };
 
 // the buffers of the search, kept between calls and grown with the lattice
@@ -112,6 +150,8 @@ struct mcl_search {
     HostBuf<mcl_sbeam::Header> h_bhdr;
     DevBuf<float> d_bobs, d_lobs;
     BeamTable btab;                             // what d_btab holds: the last tile of the last beam search
+    // the search with exact pruning (§4.20)
+    std::unique_ptr<PruneBufs> prune;
 };
 
 namespace {
@@ -650,6 +690,229 @@ int search_beam(mcl_engine *h, const mcl_search_config_t *cfg, const float *obs,
     return MCL_OK;
 }
 
+
+// ---- the search with exact pruning (§4.20)
+// P1 on the device: the block tables of this lattice at this S (formed and uploaded when either changed).  A block's corners are
+// S1's cell centres of its first and last lattice column and row, the expressions of search_lattice.
+int prune_blocks_upload(mcl_engine *h, mcl_search *s, PruneBufs &pb, int stride, int S)
+{
+    if (pb.blk_epoch == s->lattice_epoch && pb.blk_stride == stride && pb.blk_S == S) return MCL_OK;
+    pb.blk_epoch = 0;
+    std::vector<int32_t> pmap((size_t)s->nx * (size_t)s->ny);
+    HIPCHK(h, hipMemcpy(pmap.data(), s->d_pmap, pmap.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    mcl_host::search_blocks(S, stride, pmap.data(), s->nx, s->ny, pb.plan);
+    const mcl_host::SearchBlocks &b = pb.plan;
+    const size_t n = (size_t)b.n_blocks;
+    std::vector<double4> corner(n);
+    std::vector<int2> blk(n);
+    const int64_t h0 = stride / 2;
+    for (size_t i = 0; i < n; ++i) {
+        const int bx = b.blk[3 * i], by = b.blk[3 * i + 1];
+        const int64_t c0 = h0 + (int64_t)bx * S * stride, c1 = h0 + (int64_t)std::min(bx * S + S - 1, s->nx - 1) * stride;
+        const int64_t r0 = h0 + (int64_t)by * S * stride, r1 = h0 + (int64_t)std::min(by * S + S - 1, s->ny - 1) * stride;
+        corner[i] = make_double4(h->ox + ((double)c0 + 0.5) * h->res, h->oy + ((double)r0 + 0.5) * h->res,
+                                 h->ox + ((double)c1 + 0.5) * h->res, h->oy + ((double)r1 + 0.5) * h->res);
+        blk[i] = make_int2(bx, by);
+    }
+    SIDE_TRY(pb.d_corner.reserve(h, n, &pb.bytes));
+    SIDE_TRY(pb.d_blk.reserve(h, n, &pb.bytes));
+    SIDE_TRY(pb.d_bmap.reserve(h, b.bmap.size(), &pb.bytes));
+    HIPCHK(h, hipMemcpy(pb.d_corner, corner.data(), n * sizeof(double4), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(pb.d_blk, blk.data(), n * sizeof(int2), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(pb.d_bmap, b.bmap.data(), b.bmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    pb.blk_epoch = s->lattice_epoch;
+    pb.blk_stride = stride;
+    pb.blk_S = S;
+    return MCL_OK;
+}
+
+// P2 on the device: Ub and the pooled field of this map's field at this w (made when any of the three changed)
+int prune_pool(mcl_engine *h, PruneBufs &pb, int w)
+{
+    if (pb.pool_w == w && pb.pool_map == h->map_epoch && pb.pool_lf == h->lf_epoch) return MCL_OK;
+    pb.pool_w = 0;
+    const int K = h->lf_K;
+    std::vector<float> ub((size_t)K + 1);
+    mcl_host::search_bound_table(h->lf_tab.data(), K, ub.data());
+    const size_t Wp = (size_t)h->W + (size_t)w - 1, Hp = (size_t)h->H + (size_t)w - 1;
+    SIDE_TRY(pb.d_ub.reserve(h, ub.size(), &pb.bytes));
+    SIDE_TRY(pb.d_R.reserve(h, Wp * (size_t)h->H, &pb.bytes));
+    SIDE_TRY(pb.d_Dp.reserve(h, Wp * Hp, &pb.bytes));
+    HIPCHK(h, hipMemcpy(pb.d_ub, ub.data(), ub.size() * sizeof(float), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(mcl_prune::k_lf_pool_rows, dim3((unsigned)((Wp * (size_t)h->H + 255) / 256)), dim3(256), 0, h->stream, h->d_lf_D.p, h->W,
+                       h->H, K, w, pb.d_R.p);
+    hipLaunchKernelGGL(mcl_prune::k_lf_pool_cols, dim3((unsigned)((Wp * Hp + 255) / 256)), dim3(256), 0, h->stream, pb.d_R.p, h->W, h->H, K, w,
+                       pb.d_Dp.p);
+    HIPCHK(h, hipGetLastError());
+    pb.pool_map = h->map_epoch;
+    pb.pool_lf = h->lf_epoch;
+    pb.pool_w = w;
+    return MCL_OK;
+}
+
+// room in the store and its sort buffers for `want` entries, the first `keep` entries of the store kept
+int prune_grow(mcl_engine *h, PruneBufs &pb, size_t keep, size_t want)
+{
+    if (want > pb.store.cap) {
+        DevBuf<double> bigger;
+        SIDE_TRY(bigger.reserve(h, want, &pb.bytes));
+        if (keep) HIPCHK(h, hipMemcpyAsync(bigger, pb.store, keep * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));                 // before the old store goes
+        pb.store = std::move(bigger);
+    }
+    for (int i = 0; i < 2; ++i) {
+        SIDE_TRY(pb.ckey[i].reserve(h, want, &pb.bytes));
+        SIDE_TRY(pb.cval[i].reserve(h, want, &pb.bytes));
+    }
+    return MCL_OK;
+}
+
+// adds what a call's own buffers have asked for to the search's byte count, however the call ends
+struct PruneBytes {
+    mcl_search *s;
+    PruneBufs &pb;
+    size_t before;
+    ~PruneBytes() { s->device_bytes += pb.bytes - before; }
+};
+
+int search_pruned(mcl_engine *h, const mcl_search_config_t *cfg, const mcl_search_prune_config_t *pcfg, const float *obs, int32_t n_beams,
+                  int32_t max_hits, mcl_search_hit_t *hits, int64_t *n_hits, uint64_t *stats)
+{
+    // P6: everything that can refuse the call, before anything is allocated for it
+    mcl_search_config_t c;
+    SIDE_TRY(search_check(h, cfg, obs, n_beams, max_hits, hits, n_hits, c));
+    if (max_hits == 0) return fail(h, MCL_ERR_INVALID_ARG, "pruned search: max_hits must be >= 1 (with no hit to report the call has nothing to do)");
+    mcl_search_prune_config_t pc;
+    if (pcfg) pc = *pcfg; else mcl_default_search_prune_config(&pc);
+    if (const char *why = mcl_host::search_prune_invalid(&c, &pc)) return fail(h, MCL_ERR_INVALID_ARG, why);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (!h->srch) h->srch = new mcl_search();
+    mcl_search *s = h->srch;
+    SIDE_TRY(search_lattice_upload(h, s, c.stride_cells));
+    if (s->n_pos == 0) return fail(h, MCL_ERR_NOT_READY, "global search: the lattice has no free position on this map");
+    const int64_t n_poses = s->n_pos * (int64_t)c.n_headings;
+    if (n_poses >= MCL_MAX_TOTAL_PARTICLES)
+        return fail(h, MCL_ERR_INVALID_ARG, "global search: n_positions * n_headings must stay below 2^27 (a larger stride_cells or fewer headings)");
+    SIDE_TRY(search_headings_upload(h, s, c.n_headings));
+    SIDE_TRY(search_alloc_scan(h, s, (size_t)h->B));
+    if (!s->prune) s->prune.reset(new PruneBufs());
+    PruneBufs &pb = *s->prune;
+    const PruneBytes count_bytes{s, pb, pb.bytes};
+    pb.bounds.n = 0;                                             // until this call's bounds are whole
+    const int S = pc.block;
+    const uint64_t SS = (uint64_t)(S * S);
+    SIDE_TRY(prune_blocks_upload(h, s, pb, c.stride_cells, S));
+    const int64_t n_pairs = (int64_t)pb.plan.n_blocks * (int64_t)c.n_headings;
+    if ((uint64_t)n_pairs * SS >= (1ull << 31))
+        return fail(h, MCL_ERR_INVALID_ARG, "pruned search: pairs * block * block must stay below 2^31 (a smaller block, a larger stride_cells or fewer headings)");
+    SIDE_TRY(prune_pool(h, pb, pb.plan.w));
+    SIDE_TRY(pb.d_U.reserve(h, (size_t)n_pairs, &pb.bytes));
+    for (int i = 0; i < 2; ++i) {
+        SIDE_TRY(pb.d_ukey[i].reserve(h, (size_t)n_pairs, &pb.bytes));
+        SIDE_TRY(pb.d_upair[i].reserve(h, (size_t)n_pairs, &pb.bytes));
+    }
+    SIDE_TRY(pb.d_rank.reserve(h, (size_t)n_pairs, &pb.bytes));
+    SIDE_TRY(pb.d_guard.reserve(h, 1, &pb.bytes));
+    SIDE_TRY(pb.h_guard.reserve(h, 1));
+    SIDE_TRY(pb.d_round.reserve(h, 1, &pb.bytes));
+    SIDE_TRY(pb.h_round.reserve(h, 1));
+
+    // the scan; the bounds, their order, the slot map
+    const int nb = stage_used_beams(h, c.beam_stride, obs, s->h_obs, s->h_beams);
+    if (nb > 0) HIPCHK(h, hipMemcpyAsync(s->d_beams, s->h_beams, (size_t)nb * sizeof(double2), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(pb.d_guard, 0, sizeof(unsigned long long), h->stream));
+    mcl_prune::Args a{};
+    a.xy = s->d_xy; a.pmap = s->d_pmap; a.theta = s->d_theta;
+    a.n_pos = (int32_t)s->n_pos; a.n_head = c.n_headings; a.nx = s->nx; a.ny = s->ny;
+    a.S = S; a.n_blocks = pb.plan.n_blocks; a.nbx = pb.plan.nbx;
+    a.n_pairs = (uint32_t)n_pairs;
+    a.groups_per_heading = (uint32_t)((pb.plan.n_blocks + kThreads - 1) / kThreads);
+    a.corner = pb.d_corner; a.blk = pb.d_blk; a.bmap = pb.d_bmap;
+    a.beams = s->d_beams; a.nb = nb;
+    a.D = h->d_lf_D; a.W = h->W; a.H = h->H;
+    a.ox = h->ox; a.oy = h->oy; a.inv_res = 1.0 / h->res;
+    a.lf = h->d_lf_tab; a.ub = pb.d_ub; a.K = h->lf_K;
+    a.Dp = pb.d_Dp; a.w = pb.plan.w;
+    a.U = pb.d_U; a.ukey = pb.d_ukey[0]; a.upair = pb.d_upair[0];
+    a.ukey_sorted = pb.d_ukey[1]; a.pair_sorted = pb.d_upair[1]; a.rank = pb.d_rank;
+    a.guard = pb.d_guard;
+    a.nms = c.nms;
+    a.count = s->d_count;
+    a.max_hits = (uint32_t)max_hits;
+    a.round = pb.d_round;
+    const size_t lds = lf_lds_bytes(h);
+    const dim3 grid_bound((unsigned)((uint64_t)a.groups_per_heading * (uint64_t)c.n_headings));
+    if (lds) hipLaunchKernelGGL(mcl_prune::k_search_bound<true>, grid_bound, dim3(kThreads), lds, h->stream, a);
+    else hipLaunchKernelGGL(mcl_prune::k_search_bound<false>, grid_bound, dim3(kThreads), 0, h->stream, a);
+    HIPCHK(h, hipGetLastError());
+    size_t tb = 0;
+    HIPCHK(h, rocprim::radix_sort_pairs(nullptr, tb, pb.d_ukey[0].p, pb.d_ukey[1].p, pb.d_upair[0].p, pb.d_upair[1].p, (size_t)n_pairs, 0, 64, h->stream));
+    SIDE_TRY(pb.tmp.reserve(h, std::max<size_t>(tb, 16), &pb.bytes));
+    tb = pb.tmp.cap;
+    HIPCHK(h, rocprim::radix_sort_pairs(pb.tmp.p, tb, pb.d_ukey[0].p, pb.d_ukey[1].p, pb.d_upair[0].p, pb.d_upair[1].p, (size_t)n_pairs, 0, 64, h->stream));
+    hipLaunchKernelGGL(mcl_prune::k_search_rank, dim3((unsigned)((n_pairs + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream, a);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(pb.h_guard, pb.d_guard, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+
+    // P4: the rounds
+    unsigned index_bits = 1;
+    while (((int64_t)1 << index_bits) < n_poses) ++index_bits;
+    int64_t n_scored = 0, next = mcl_host::search_prune_next(pc, n_pairs, 0, 0), rounds = 0;
+    size_t top = 0;
+    for (;;) {
+        const size_t entries = (size_t)((uint64_t)next * SS);
+        SIDE_TRY(prune_grow(h, pb, (size_t)((uint64_t)n_scored * SS), entries));
+        size_t tb1 = 0, tb2 = 0;
+        HIPCHK(h, rocprim::radix_sort_pairs(nullptr, tb1, pb.cval[0].p, pb.cval[1].p, pb.ckey[0].p, pb.ckey[1].p, entries, 0, index_bits, h->stream));
+        HIPCHK(h, rocprim::radix_sort_pairs(nullptr, tb2, pb.ckey[1].p, pb.ckey[0].p, pb.cval[1].p, pb.cval[0].p, entries, 0, 64, h->stream));
+        SIDE_TRY(pb.tmp.reserve(h, std::max(tb1, tb2), &pb.bytes));
+        a.store = pb.store; a.ckey = pb.ckey[0]; a.cval = pb.cval[0];
+        a.r0 = (uint32_t)n_scored; a.r1 = (uint32_t)next; a.n_scored = (uint32_t)next;
+        const dim3 grid_score((unsigned)((next - n_scored + kThreads / 64 - 1) / (kThreads / 64)));
+        if (lds) hipLaunchKernelGGL(mcl_prune::k_search_score_block<true>, grid_score, dim3(kThreads), lds, h->stream, a);
+        else hipLaunchKernelGGL(mcl_prune::k_search_score_block<false>, grid_score, dim3(kThreads), 0, h->stream, a);
+        HIPCHK(h, hipGetLastError());
+        n_scored = next;
+        ++rounds;
+        HIPCHK(h, hipMemsetAsync(s->d_count, 0, sizeof(unsigned long long), h->stream));
+        hipLaunchKernelGGL(mcl_prune::k_search_mark_block, dim3((unsigned)((entries + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream, a);
+        HIPCHK(h, hipGetLastError());
+        // the entries by index, then stably by key: the candidates first, best first, ties by index (S5)
+        tb = pb.tmp.cap;
+        HIPCHK(h, rocprim::radix_sort_pairs(pb.tmp.p, tb, pb.cval[0].p, pb.cval[1].p, pb.ckey[0].p, pb.ckey[1].p, entries, 0, index_bits, h->stream));
+        tb = pb.tmp.cap;
+        HIPCHK(h, rocprim::radix_sort_pairs(pb.tmp.p, tb, pb.ckey[1].p, pb.ckey[0].p, pb.cval[1].p, pb.cval[0].p, entries, 0, 64, h->stream));
+        hipLaunchKernelGGL(mcl_prune::k_search_decide, dim3(1), dim3(64), 0, h->stream, a);
+        HIPCHK(h, hipGetLastError());
+        top = std::min<size_t>((size_t)max_hits, entries);
+        HIPCHK(h, hipMemcpyAsync(s->h_key, pb.ckey[0], top * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(s->h_val, pb.cval[0], top * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(s->h_count, s->d_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(pb.h_round, pb.d_round, sizeof(mcl_prune::Round), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));               // the round's one host wait
+        if (pb.h_round->stop) break;
+        next = mcl_host::search_prune_next(pc, n_pairs, n_scored, (int64_t)pb.h_round->next);
+    }
+    pb.bounds = {h->map_epoch, n_pairs};
+    // P5: the first min(max_hits, candidates) entries; a stop with pairs left unscored has at least max_hits of them
+    const int64_t m = std::min<int64_t>((int64_t)top, (int64_t)*s->h_count);
+    for (int64_t r = 0; r < m; ++r) {
+        const int64_t i = (int64_t)s->h_val[r];
+        const int64_t k = i / s->n_pos, p = i - k * s->n_pos;
+        hits[r].pose[0] = s->xy[(size_t)2 * p];
+        hits[r].pose[1] = s->xy[(size_t)2 * p + 1];
+        hits[r].pose[2] = s->theta[(size_t)k];
+        hits[r].log_likelihood = key_score(s->h_key[r]);
+        hits[r].index = i;
+    }
+    *n_hits = m;
+    if (stats) {
+        stats[0] = (uint64_t)s->n_pos; stats[1] = (uint64_t)n_poses; stats[2] = (uint64_t)nb; stats[3] = (uint64_t)pb.bytes;
+        stats[4] = (uint64_t)n_pairs; stats[5] = (uint64_t)n_scored; stats[6] = (uint64_t)rounds; stats[7] = (uint64_t)*pb.h_guard;
+    }
+    return MCL_OK;
+}
+
 }  // namespace
 
 void search_free(struct mcl_search *s) { delete s; }
@@ -730,6 +993,21 @@ int mcl_get_search_beam_table(mcl_engine_t *h, uint16_t *out, size_t n, int64_t 
             out[(size_t)t * (size_t)b.M + (size_t)m] = v;
         }
     return MCL_OK;
+}
+
+int mcl_global_search_pruned(mcl_engine_t *h, const mcl_search_config_t *cfg, const mcl_search_prune_config_t *pcfg, const float *obs,
+                             int32_t n_beams, int32_t max_hits, mcl_search_hit_t *hits, int64_t *n_hits, uint64_t stats[8])
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    return search_pruned(h, cfg, pcfg, obs, n_beams, max_hits, hits, n_hits, stats);
+}
+
+int mcl_get_search_bounds(mcl_engine_t *h, double *out, size_t n)
+{
+    if (!h || !out) return MCL_ERR_INVALID_ARG;
+    const PruneBufs *pb = h->srch ? h->srch->prune.get() : nullptr;
+    return read_volume(h, pb ? &pb->bounds : nullptr, pb ? pb->d_U.p : nullptr, out, n, "no bounds: no pruned search has run on this map",
+                       "the bounds have n_headings x n_blocks entries");
 }
 
 int mcl_get_search_scores(mcl_engine_t *h, double *out, size_t n)

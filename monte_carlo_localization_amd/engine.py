@@ -52,6 +52,8 @@ EXPORTS = [
     "mcl_global_search_sequence", "mcl_host_search_sequence_offsets", "mcl_host_relative_poses",
     "mcl_default_search_stream_config", "mcl_global_search_streamed", "mcl_host_search_slabs",
     "mcl_global_search_beam", "mcl_host_search_beam_grid", "mcl_get_search_beam_table",
+    "mcl_default_search_prune_config", "mcl_global_search_pruned", "mcl_get_search_bounds", "mcl_host_search_blocks", "mcl_host_lf_pool",
+    "mcl_host_search_bound_table", "mcl_host_search_prune_next",
     "mcl_default_refine_config", "mcl_refine_poses", "mcl_refine_poses_beam", "mcl_get_refine_scores", "mcl_get_refine_bytes", "mcl_host_refine_window",
     "mcl_host_refine_reduce",
     "mcl_default_recovery_config", "mcl_set_recovery", "mcl_get_recovery_state", "mcl_set_recovery_state", "mcl_host_recovery_step",
@@ -145,6 +147,11 @@ class SearchConfig(C.Structure):
 class SearchStreamConfig(C.Structure):
     """mcl_search_stream_config_t: the memory budget and the slab of a streamed search (Engine.global_search_streamed)."""
     _fields_ = [("budget_bytes", C.c_uint64), ("slab_headings", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+class SearchPruneConfig(C.Structure):
+    """mcl_search_prune_config_t: the block side and the first round of a pruned search (Engine.global_search_pruned)."""
+    _fields_ = [("block", C.c_int32), ("first_pairs", C.c_int32), ("reserved", C.c_int32 * 6)]
 
 
 # the numpy view of an array of mcl_search_hit_t (Engine.global_search)
@@ -266,6 +273,17 @@ def load_library(legacy=False):
         lib.mcl_host_search_beam_grid.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                                   C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_size_t]
         lib.mcl_get_search_beam_table.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        lib.mcl_default_search_prune_config.argtypes = [C.POINTER(SearchPruneConfig)]
+        lib.mcl_default_search_prune_config.restype = None
+        lib.mcl_global_search_pruned.argtypes = [C.c_void_p, C.POINTER(SearchConfig), C.POINTER(SearchPruneConfig), C.c_void_p, C.c_int32,
+                                                 C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]
+        lib.mcl_get_search_bounds.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.mcl_host_search_blocks.argtypes = [C.POINTER(SearchConfig), C.POINTER(SearchPruneConfig), C.c_void_p, C.c_uint32, C.c_uint32,
+                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                               C.c_void_p, C.c_size_t]
+        lib.mcl_host_lf_pool.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t]
+        lib.mcl_host_search_bound_table.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        lib.mcl_host_search_prune_next.argtypes = [C.POINTER(SearchPruneConfig), C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
         lib.mcl_default_refine_config.argtypes = [C.POINTER(RefineConfig)]
         lib.mcl_default_refine_config.restype = None
         lib.mcl_refine_poses.argtypes = [C.c_void_p, C.POINTER(RefineConfig), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
@@ -501,6 +519,72 @@ def host_search_slabs(n_positions, n_scans=1, budget_bytes=0, slab_headings=0, s
     if rc != MCL_OK:
         raise EngineError(f"mcl_host_search_slabs rc={rc}", rc)
     return int(G.value), int(ns.value), int(b.value)
+
+
+def search_prune_config(block=0, first_pairs=0, reserved=(0, 0, 0, 0, 0, 0)) -> SearchPruneConfig:
+    """mcl_search_prune_config_t: block 0 is the default block side (mcl_default_search_prune_config's), first_pairs 0 the default
+    first round (max(1024, pairs / 64))."""
+    c = SearchPruneConfig()
+    load_library().mcl_default_search_prune_config(C.byref(c))
+    if block:
+        c.block = int(block)
+    c.first_pairs = int(first_pairs)
+    c.reserved[:] = [int(v) for v in reserved]
+    return c
+
+
+def host_search_blocks(grid, block=0, **fields) -> dict:
+    """The block plan of a pruned search over a map (mcl_host_search_blocks, rules P1 / P2; no device needed): {n_blocks, w, nbx,
+    nby, blocks} -- the live blocks, the window of the pooled field, the block grid, and per live block (bx, by, positions in it)
+    in the order of the pair numbering: pair = k * n_blocks + b.  `fields` override mcl_default_search_config."""
+    g = _c(grid, np.int8)
+    H, W = g.shape
+    c, pc = default_search_config(**fields), search_prune_config(block)
+    lib = load_library()
+    n, w, nbx, nby = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+    args = (C.byref(c), C.byref(pc), _p(g), W, H, C.byref(n), C.byref(w), C.byref(nbx), C.byref(nby))
+    rc = lib.mcl_host_search_blocks(*args, None, 0)
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_search_blocks rc={rc}", rc)
+    blocks = np.empty((n.value, 3), np.int32)
+    if n.value:
+        rc = lib.mcl_host_search_blocks(*args, _p(blocks), n.value)
+        if rc != MCL_OK:
+            raise EngineError(f"mcl_host_search_blocks rc={rc}", rc)
+    return dict(n_blocks=n.value, w=w.value, nbx=nbx.value, nby=nby.value, blocks=blocks)
+
+
+def host_lf_pool(D, K, w) -> np.ndarray:
+    """The pooled field Dp of a likelihood field D (mcl_host_lf_pool, rule P2; no device needed): shape (H + w - 1, W + w - 1),
+    uint16; out[y + w - 1, x + w - 1] is the minimum over the w x w window with low corner (x, y), cells off the map counting K."""
+    d = _c(D, np.uint16)
+    H, W = d.shape
+    out = np.empty((H + int(w) - 1, W + int(w) - 1), np.uint16)
+    rc = load_library().mcl_host_lf_pool(_p(d), W, H, C.c_int32(int(K)), C.c_int32(int(w)), _p(out), out.size)
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_lf_pool rc={rc}", rc)
+    return out
+
+
+def host_search_bound_table(lf) -> np.ndarray:
+    """Ub[k] = max over j >= k of Lf[j] (mcl_host_search_bound_table, rule P2; no device needed): K + 1 float32 entries."""
+    t = _c(lf, np.float32)
+    out = np.empty_like(t)
+    rc = load_library().mcl_host_search_bound_table(_p(t), C.c_int32(t.size - 1), _p(out))
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_search_bound_table rc={rc}", rc)
+    return out
+
+
+def host_search_prune_next(pairs, n_scored, first_below_c=0, first_pairs=0) -> int:
+    """The round schedule of a pruned search (mcl_host_search_prune_next, rule P4; no device needed): how many ranks have scores
+    after the next round; n_scored = 0 gives the first round."""
+    pc, out = search_prune_config(0, first_pairs), C.c_int64()
+    rc = load_library().mcl_host_search_prune_next(C.byref(pc), C.c_int64(int(pairs)), C.c_int64(int(n_scored)),
+                                                   C.c_int64(int(first_below_c)), C.byref(out))
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_search_prune_next rc={rc}", rc)
+    return out.value
 
 
 def host_search_lattice(grid, resolution, origin_x, origin_y, **fields):
@@ -976,7 +1060,8 @@ class Engine:
         self._chk(self.lib.mcl_get_recovery_proposal(self._h, None, _p(thr), _p(fac)), "mcl_get_recovery_proposal")
         return thr, fac
 
-    def propose_from_scan(self, obs, max_hits=16, refine=True, weights="equal", cov=None, refine_fields=None, **search_fields):
+    def propose_from_scan(self, obs, max_hits=16, refine=True, weights="equal", cov=None, refine_fields=None, pruned=False,
+                          **search_fields):
         """Sets the proposal from where the scan `obs` fits the map: the search of the sensor model in use (global_search +
         refine_poses with the likelihood field on, else global_search_beam + refine_poses_beam; the model is never switched and an
         error of the search propagates), hits at -inf dropped, one component per hit from the refined mean and covariance.
@@ -984,13 +1069,16 @@ class Engine:
         (2 pi / n_headings)^2)).  weights: "equal" (the default: the same update's sensor model ranks the components anyway, and
         with a thousand beams exp(ll - max) gives everything to one hit) or "likelihood" (seed_counts' shares).  No hit left:
         the proposal is cleared.  Returns the hits.  `search_fields` override mcl_default_search_config, `refine_fields`
-        mcl_default_refine_config.
+        mcl_default_refine_config.  pruned=True (likelihood field only): the same hits from global_search_pruned.
             if e.recovery_state()[2] > 0: e.propose_from_scan(scan)
             e.update(action, scan)"""
         if weights not in ("equal", "likelihood"):
             raise ValueError('weights must be "equal" or "likelihood"')
         lf = self.lib.mcl_get_likelihood_table(self._h, None, C.c_size_t(0), None) == MCL_OK
-        hits, _ = (self.global_search if lf else self.global_search_beam)(obs, max_hits=max_hits, **search_fields)
+        if pruned and not lf:
+            raise EngineError("propose_from_scan: pruned=True needs the likelihood-field model (global_search_pruned)", MCL_ERR_NOT_READY)
+        search = self.global_search_pruned if pruned else self.global_search if lf else self.global_search_beam
+        hits, _ = search(obs, max_hits=max_hits, **search_fields)
         hits = hits[np.isfinite(hits["log_likelihood"])]
         if hits.size == 0:
             self.set_recovery_proposal(None)
@@ -1115,6 +1203,30 @@ class Engine:
         self._search_poses = int(st[1])
         return hits[:min(n.value, hits.size)], dict(n_hits=n.value, n_positions=int(st[0]), n_poses=int(st[1]), used_beams=int(st[2]),
                                                     device_bytes=int(st[3]))
+
+    def global_search_pruned(self, obs, max_hits=16, block=0, first_pairs=0, prune_reserved=(0, 0, 0, 0, 0, 0), **fields):
+        """global_search's hits from the blocks of poses an upper bound cannot rule out (mcl_global_search_pruned):
+        the same structured array, bit for bit, without the score volume.  block: lattice positions per block side (2, 4 or 8; 0:
+        the default), first_pairs: the (block, heading) pairs the first round scores (0: the default).  n_hits is the number of
+        hits written, not the candidates of the volume.  Returns (hits, {n_hits, n_positions, n_poses, used_beams, device_bytes,
+        pairs, pairs_scored, rounds, guard_fallbacks})."""
+        c, pc = default_search_config(**fields), search_prune_config(block, first_pairs, prune_reserved)
+        o = _c(obs, np.float32)
+        hits = np.zeros(int(max_hits), SEARCH_HIT_DTYPE)
+        n, st = C.c_int64(), np.zeros(8, np.uint64)
+        self._chk(self.lib.mcl_global_search_pruned(self._h, C.byref(c), C.byref(pc), _p(o), C.c_int32(o.size), C.c_int32(int(max_hits)),
+                                                    _p(hits) if hits.size else None, C.byref(n), _p(st)), "mcl_global_search_pruned")
+        self._search_pairs = int(st[4])
+        return hits[:n.value], dict(n_hits=n.value, n_positions=int(st[0]), n_poses=int(st[1]), used_beams=int(st[2]),
+                                    device_bytes=int(st[3]), pairs=int(st[4]), pairs_scored=int(st[5]), rounds=int(st[6]),
+                                    guard_fallbacks=int(st[7]))
+
+    def search_bounds(self):
+        """The bounds U of the last global_search_pruned (mcl_get_search_bounds): one double per (block, heading) pair, pair =
+        k * n_blocks + b in host_search_blocks' order.  Raises before a pruned search and after set_map."""
+        out = np.empty(getattr(self, "_search_pairs", 0) or 1, np.float64)
+        self._chk(self.lib.mcl_get_search_bounds(self._h, _p(out), C.c_size_t(out.size)), "mcl_get_search_bounds")
+        return out
 
     def global_search_sequence(self, scans, rel, max_hits=16, **fields):
         """global_search over a sequence of scans joined by odometry (mcl_global_search_sequence): every lattice
