@@ -9,7 +9,9 @@ the coordinates, the content.
   Geometry        data, resolution, origin_x, origin_y, max_range_m, name; its true pose, its 64 query poses, its seeds of the
                   refinement, its scan
   family()        the members by name (built once, from fixed seeds)
-  lattice ...     the helpers the side-call tests kept as module-level functions bound to W, H, OX, OY"""
+  lattice ...     the helpers the side-call tests kept as module-level functions bound to W, H, OX, OY
+  cloud_around .. what the tests of the filter's own stages share: clouds with their spread in cells, the oracle's world-to-cell
+                  rule, the KLD bin grids and the poses that straddle their edges"""
 import math
 
 import numpy as np
@@ -318,6 +320,103 @@ def lf_mismatches(got, want, alts):
         if not (int(i) in alts and got[i] in alts[int(i)]):
             bad.append((int(i), float(got[i]), float(want[i])))
     return bad
+
+
+# ---- what the tests of the filter's own stages share (tests/test_update_geometries_host.py, test_gpu_update_geometries.py)
+def wrap(th):
+    return (th + np.pi) % (2 * np.pi) - np.pi
+
+
+def cloud_around(g, rng, n, pose=None, sig_cells=(4.0, 4.0), sig_theta=0.3):
+    """(3, n): a tracking cloud around `pose` (default: the true pose) with its spread in cells; on a map of a few cells part of
+    it lies in walls and off the map (cloud_shares says how much)"""
+    pose = g.true_pose if pose is None else pose
+    p = np.empty((3, n))
+    p[0] = pose[0] + rng.normal(0, sig_cells[0] * g.res, n)
+    p[1] = pose[1] + rng.normal(0, sig_cells[1] * g.res, n)
+    p[2] = wrap(pose[2] + rng.normal(0, sig_theta, n))
+    return p
+
+
+def global_cloud(g, rng, n, off=0.05):
+    """(3, n): uniform over the map, the first `off` of the set up to two cells outside its border instead"""
+    p = np.empty((3, n))
+    p[0] = g.origin_x + rng.uniform(0, g.W, n) * g.res
+    p[1] = g.origin_y + rng.uniform(0, g.H, n) * g.res
+    p[2] = rng.uniform(-np.pi, np.pi, n)
+    k = int(n * off)
+    side = rng.integers(0, 4, k)
+    d = rng.uniform(0.0, 2.0, k) * g.res
+    p[0, :k] = np.where(side == 0, g.origin_x - d, np.where(side == 1, g.origin_x + g.W * g.res + d, p[0, :k]))
+    p[1, :k] = np.where(side == 2, g.origin_y - d, np.where(side == 3, g.origin_y + g.H * g.res + d, p[1, :k]))
+    return p
+
+
+def oracle_cells(om, x, y):
+    """(col, row) of world points under the oracle's own rule, the truncation of cast_ray (mcl_oracle.c: (int)((cx - origin_x) /
+    resolution)), with the oracle map's own doubles"""
+    with np.errstate(invalid="ignore"):
+        col = np.trunc((np.asarray(x, np.float64) - om.origin_x) / om.resolution)
+        row = np.trunc((np.asarray(y, np.float64) - om.origin_y) / om.resolution)
+    return col.astype(np.int64), row.astype(np.int64)
+
+
+def cloud_shares(om, p):
+    """(share of the poses in occupied cells, share off the map) under oracle_cells"""
+    col, row = oracle_cells(om, p[0], p[1])
+    off = (col < 0) | (col >= om.width) | (row < 0) | (row >= om.height) | (p[0] < om.origin_x) | (p[1] < om.origin_y)
+    wall = np.zeros(off.shape, bool)
+    wall[~off] = om.grid[row[~off], col[~off]] > 50
+    return float(wall.mean()), float(off.mean())
+
+
+def mirrored_pose(g):
+    """the true pose mirrored through the map's centre, moved to the centre of the nearest free cell that is not the true cell
+    (on one_free there is none: the true pose turned by pi)"""
+    rows, cols = np.nonzero(g.data == 0)
+    keep = (cols != g.true_cell[0]) | (rows != g.true_cell[1])
+    if not keep.any():
+        return (g.true_pose[0], g.true_pose[1], float(wrap(g.true_pose[2] + np.pi)))
+    rows, cols = rows[keep], cols[keep]
+    mc, mr = g.W - 1 - g.true_cell[0], g.H - 1 - g.true_cell[1]
+    k = int(np.argmin((cols - mc) ** 2 + (rows - mr) ** 2))
+    return g.at(cols[k] + 0.5, rows[k] + 0.5, float(wrap(g.true_pose[2] + np.pi)))
+
+
+def kld_forms(g):
+    """name -> the bin fields of the three bin grids the tests use: the default 0.5 m, bins of one cell, bins larger than the map"""
+    return dict(default={}, cell=dict(bin_x_m=g.res, bin_y_m=g.res), huge=dict(bin_x_m=2.0 * max(g.W, g.H) * g.res, bin_y_m=2.0 * max(g.W, g.H) * g.res))
+
+
+def kld_grid(g, k):
+    """(nx, ny) of the bin grid: ceil(W res / bin) per axis, in the header's arithmetic"""
+    return int(np.ceil(np.float64(g.W) * np.float64(g.res) / np.float64(k.bin_x_m))), int(np.ceil(np.float64(g.H) * np.float64(g.res) / np.float64(k.bin_y_m)))
+
+
+def edge_poses(g, k, rng, n=2000):
+    """(3, n): poses straddling every edge of the map and of the bin grid by +-1 ulp and +-1 bin in one coordinate, the other
+    anywhere from a bin outside to a bin outside, headings anywhere in +-2 turns with the turn's ends among them"""
+    nx, ny = kld_grid(g, k)
+    bx, by = float(k.bin_x_m), float(k.bin_y_m)
+
+    def around(edges, b):
+        out = []
+        for e in edges:
+            out += [e, np.nextafter(e, -np.inf), np.nextafter(e, np.inf), e - b, e + b]
+        return np.array(out)
+    ex = around([g.origin_x, g.origin_x + g.W * g.res, g.origin_x + nx * bx], bx)
+    ey = around([g.origin_y, g.origin_y + g.H * g.res, g.origin_y + ny * by], by)
+    p = np.empty((3, n))
+    p[0] = rng.uniform(g.origin_x - bx, g.origin_x + nx * bx + bx, n)
+    p[1] = rng.uniform(g.origin_y - by, g.origin_y + ny * by + by, n)
+    p[2] = rng.uniform(-4 * np.pi, 4 * np.pi, n)
+    which = rng.integers(0, 3, n)                               # x on an edge, y on an edge, both
+    onx, ony = which != 1, which != 0
+    p[0, onx] = ex[np.arange(int(onx.sum())) % ex.size]
+    p[1, ony] = ey[(np.arange(int(ony.sum())) // 3) % ey.size]
+    ends = np.array([np.pi, -np.pi, np.nextafter(np.pi, 0), np.nextafter(-np.pi, 0), 3 * np.pi, 0.0])
+    p[2, ::7] = ends[np.arange(p[2, ::7].size) % ends.size]
+    return p
 
 
 # ---- the family

@@ -326,6 +326,7 @@ def test_an_update_after_every_side_call_is_that_of_a_fresh_engine(cx, field):
         a.global_search(cx.obs, max_hits=4, **f)
         a.global_search_sequence(np.stack([cx.earlier, cx.obs]), cx.rel, max_hits=4, **f)
         a.global_search_streamed(cx.obs, max_hits=4, slab_headings=2, **f)
+        a.global_search_pruned(cx.obs, max_hits=4, block=4, first_pairs=3, **f)
         a.refine_poses(g.seeds, cx.obs, **g.window_fields)
     for e in (a, b):
         e.update((g.res, 0.0, 0.01), scan)
