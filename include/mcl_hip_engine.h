@@ -943,6 +943,15 @@ int mcl_host_skip_field_dir(const int8_t *data, uint32_t width, uint32_t height,
  * [2*pi*k/MCL_WEDGES, 2*pi*(k+1)/MCL_WEDGES]); the fields MCL_RAYS_CELL stages in LDS. */
 #define MCL_WEDGES 16
 int mcl_host_skip_field_wedge(const int8_t *data, uint32_t width, uint32_t height, int32_t wedge, uint8_t *out, size_t n);
+/* The wedge field under the tight rule, which is what mcl_set_map builds for the ray kernels: a stop cell bounds the jump by the
+ * distance from the origin to the part of its offset square that lies INSIDE the (closed) wedge, not by the distance between the
+ * two cell squares (csrc/mcl_wedge.h has the argument and the margins).  Never smaller than mcl_host_skip_field_wedge, 0 in the
+ * same cells.  MCL_WEDGE_METRIC=0 in the environment of mcl_set_map keeps the Euclidean rule on the device (an A/B switch). */
+int mcl_host_skip_field_wedge_tight(const int8_t *data, uint32_t width, uint32_t height, int32_t wedge, uint8_t *out, size_t n);
+/* What the tight rule allows per stop-cell offset: for (ox, oy) in [-255, 255]^2, row-major in oy then ox (n = 511 * 511),
+ * values[] = the uncapped skip a stop at that offset permits and reachable[] = 1 where the field search counts the offset as
+ * reachable in this wedge.  Host only; for tests and tools. */
+int mcl_host_wedge_tight_table(int32_t wedge, int32_t *values, uint8_t *reachable, size_t n);
 /* Layout of the copies of the wedge fields that the global-field form of the ray kernel (ranges beyond 243 px) probes in place:
  * out = [usable (0 / 1), row pitch, rows per field (ringed grid + tail of stop rows), bytes per field, bytes of the allocation,
  * the largest byte offset a walk can form].  The kernel addresses the allocation from its start with offsets >= 0; a walk

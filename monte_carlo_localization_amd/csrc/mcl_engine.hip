@@ -1115,12 +1115,20 @@ int mcl_set_map(mcl_engine_t *h, const int8_t *data, uint32_t width, uint32_t he
         MCL_TRY(d_prv.reserve(h, ncell));
         MCL_TRY(d_rows.reserve(h, rows.size()));
         hipLaunchKernelGGL(mcl::k_row_tables, dim3((h->Hp + 63) / 64), dim3(64), 0, h->stream, h->d_dist, h->Wp, h->Hp, h->Wps, d_nxt, d_prv);
+        // the tight rule of mcl_wedge.h (jumps bounded by the distance travelled inside the wedge); MCL_WEDGE_METRIC=0 keeps the
+        // Euclidean rule: the same binary with either field, for A/B measurements (read here, so a process can build both)
+        const char *env_metric = getenv("MCL_WEDGE_METRIC");
+        const bool tight = !(env_metric && atoi(env_metric) == 0);
         int rc_w = MCL_OK;
         for (int k = 0; k < mcl::kWedges && rc_w == MCL_OK; ++k) {
             mcl::wedge_rows(k, rows.data());
             if (hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(mcl::WedgeRow), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
                 hipStreamSynchronize(h->stream) != hipSuccess) { rc_w = MCL_ERR_HIP; break; }
-            hipLaunchKernelGGL(mcl::k_wedge_field, dim3((h->Wp + 255) / 256, h->Hp), dim3(256), 0, h->stream, d_nxt, d_prv, h->Wp, h->Hp, h->Wps,
+            if (tight)
+                hipLaunchKernelGGL(mcl::k_wedge_field_tight, dim3((h->Wp + 255) / 256, h->Hp), dim3(256), 0, h->stream, d_nxt, d_prv, h->Wp, h->Hp, h->Wps,
+                                   d_rows, mcl::wedge_cone(k), h->d_distw + (size_t)k * fsz);
+            else
+                hipLaunchKernelGGL(mcl::k_wedge_field, dim3((h->Wp + 255) / 256, h->Hp), dim3(256), 0, h->stream, d_nxt, d_prv, h->Wp, h->Hp, h->Wps,
                                d_rows, h->d_distw + (size_t)k * fsz);
             if (hipStreamSynchronize(h->stream) != hipSuccess) rc_w = MCL_ERR_HIP;   // rows[] is reused by the next wedge
         }

@@ -789,7 +789,36 @@ int mcl_host_skip_field_dir(const int8_t *data, uint32_t width, uint32_t height,
     return MCL_OK;
 }
 
+static int host_wedge_field(const int8_t *data, uint32_t width, uint32_t height, int32_t wedge, uint8_t *out, size_t n, bool tight);
+
 int mcl_host_skip_field_wedge(const int8_t *data, uint32_t width, uint32_t height, int32_t wedge, uint8_t *out, size_t n)
+{
+    return host_wedge_field(data, width, height, wedge, out, n, false);
+}
+
+int mcl_host_skip_field_wedge_tight(const int8_t *data, uint32_t width, uint32_t height, int32_t wedge, uint8_t *out, size_t n)
+{
+    return host_wedge_field(data, width, height, wedge, out, n, true);
+}
+
+int mcl_host_wedge_tight_table(int32_t wedge, int32_t *values, uint8_t *reachable, size_t n)
+{
+    const int S = 2 * mcl::kWedgeR + 1;
+    if (wedge < 0 || wedge >= mcl::kWedges || !values || !reachable || n != (size_t)S * S) return MCL_ERR_INVALID_ARG;
+    std::vector<mcl::WedgeRow> rows(S);
+    mcl::wedge_rows(wedge, rows.data());
+    const mcl::WedgeCone cone = mcl::wedge_cone(wedge);
+    for (int oy = -mcl::kWedgeR; oy <= mcl::kWedgeR; ++oy)
+        for (int ox = -mcl::kWedgeR; ox <= mcl::kWedgeR; ++ox) {
+            const size_t i = (size_t)(oy + mcl::kWedgeR) * S + (size_t)(ox + mcl::kWedgeR);
+            const mcl::WedgeRow r = rows[oy + mcl::kWedgeR];
+            reachable[i] = (ox >= r.xa && ox <= r.xb) ? 1 : 0;
+            values[i] = mcl::wedge_tight_value(cone, ox, oy);
+        }
+    return MCL_OK;
+}
+
+static int host_wedge_field(const int8_t *data, uint32_t width, uint32_t height, int32_t wedge, uint8_t *out, size_t n, bool tight)
 {
     if (!data || !out || width == 0 || height == 0 || wedge < 0 || wedge >= mcl::kWedges || n != (size_t)(width + 1) * (height + 1))
         return MCL_ERR_INVALID_ARG;
@@ -804,8 +833,11 @@ int mcl_host_skip_field_wedge(const int8_t *data, uint32_t width, uint32_t heigh
     }
     std::vector<mcl::WedgeRow> rows(2 * mcl::kWedgeR + 1);
     mcl::wedge_rows(wedge, rows.data());
+    const mcl::WedgeCone cone = mcl::wedge_cone(wedge);
     for (int y = 0; y < Hp; ++y)
-        for (int x = 0; x < Wp; ++x) out[(size_t)y * Wp + x] = (uint8_t)mcl::wedge_skip_cell(nxt.data(), prv.data(), Wp, Hp, x, y, rows.data());
+        for (int x = 0; x < Wp; ++x)
+            out[(size_t)y * Wp + x] = (uint8_t)(tight ? mcl::wedge_skip_cell_tight(nxt.data(), prv.data(), Wp, Hp, x, y, rows.data(), cone)
+                                                      : mcl::wedge_skip_cell(nxt.data(), prv.data(), Wp, Hp, x, y, rows.data()));
     return MCL_OK;
 }
 

@@ -1344,6 +1344,16 @@ __global__ __launch_bounds__(256) void k_wedge_field(const int32_t *__restrict__
     out[(size_t)y * Wps + x] = (uint8_t)(v == 0 ? 255 : (v > 127 ? 127 : v));
 }
 
+// the same field under the tight rule (mcl_wedge.h: the distance travelled inside the wedge), the same encoding
+__global__ __launch_bounds__(256) void k_wedge_field_tight(const int32_t *__restrict__ nxt, const int32_t *__restrict__ prv, int Wp, int Hp, int Wps,
+                                                          const WedgeRow *__restrict__ rows, WedgeCone cone, uint8_t *__restrict__ out)
+{
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= Wp || y >= Hp) return;
+    const int v = wedge_skip_cell_tight(nxt, prv, Wp, Hp, x, y, rows, cone);
+    out[(size_t)y * Wps + x] = (uint8_t)(v == 0 ? 255 : (v > 127 ? 127 : v));
+}
+
 // ---- cell sort: particles ordered by (32x32 tile, cell in tile, heading) ---------------------------------
 //
 // k_rays_cell gives every LANE one particle and walks that particle's beams; the 64 lanes of a wave then trace

@@ -43,7 +43,7 @@ EXPORTS = [
     "mcl_stream_wait_external", "mcl_external_wait_stream", "mcl_export_compact_async", "mcl_stage_resample_compact_async",
     "mcl_stage_rays_async", "mcl_stage_weights_async", "mcl_stage_complete", "mcl_stage_keep",
     "mcl_comm_available", "mcl_comm_unique_id", "mcl_comm_create", "mcl_comm_destroy", "mcl_comm_update", "mcl_comm_stats", "mcl_comm_set_lists", "mcl_comm_get_vector", "mcl_comm_last_exchange", "mcl_comm_selftest",
-    "mcl_host_sweep_global_layout", "mcl_get_ray_kernel_variant",
+    "mcl_host_sweep_global_layout", "mcl_get_ray_kernel_variant", "mcl_host_skip_field_wedge_tight", "mcl_host_wedge_tight_table",
     "mcl_default_kld_config", "mcl_set_kld", "mcl_get_particle_count", "mcl_get_kld_state", "mcl_host_kld_bins", "mcl_host_kld_target",
     "mcl_default_cluster_config", "mcl_pose_clusters", "mcl_get_cluster_labels",
     "mcl_query_scans", "mcl_score_poses", "mcl_get_query_counters",
@@ -814,6 +814,31 @@ def host_skip_field_wedge(grid, wedge: int) -> np.ndarray:
     if rc != MCL_OK:
         raise EngineError(f"mcl_host_skip_field_wedge rc={rc}")
     return out
+
+
+def host_skip_field_wedge_tight(grid, wedge: int) -> np.ndarray:
+    """The wedge field under the tight rule (jumps bounded by the distance travelled inside the wedge): what set_map builds."""
+    g = _c(grid, np.int8)
+    H, W = g.shape
+    out = np.empty((H + 1, W + 1), np.uint8)
+    rc = load_library().mcl_host_skip_field_wedge_tight(_p(g), C.c_uint32(W), C.c_uint32(H), C.c_int32(wedge), _p(out), C.c_size_t(out.size))
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_skip_field_wedge_tight rc={rc}")
+    return out
+
+
+WEDGE_R = 255
+
+
+def host_wedge_tight_table(wedge: int):
+    """(values, reachable), each (511, 511) indexed [oy + 255, ox + 255]: the uncapped skip a stop cell at that offset allows
+    under the tight rule, and whether the field search counts the offset as reachable in this wedge."""
+    S = 2 * WEDGE_R + 1
+    val, reach = np.empty((S, S), np.int32), np.empty((S, S), np.uint8)
+    rc = load_library().mcl_host_wedge_tight_table(C.c_int32(wedge), _p(val), _p(reach), C.c_size_t(val.size))
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_wedge_tight_table rc={rc}")
+    return val, reach.astype(bool)
 
 
 def host_skip_field_dir(grid, quadrant: int) -> np.ndarray:
