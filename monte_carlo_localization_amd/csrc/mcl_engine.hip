@@ -77,11 +77,13 @@ int fetch_scalars(mcl_engine *h)
     return MCL_OK;
 }
 
-// Work items of k_rays_sweep: made on the device from this update's unit statistics (k_sweep_plan, mcl_rays_sweep.h);
-// the host only sizes the list (every unit on its own, once per wedge group, is the longest it can get).
-// upper bound on the units of n sorted particles: the plain grid plus one cut per bucket of a sparse set (mcl::k_unit_table)
-// cells the particles of one k_rays_sweep work item may spread over (per axis): what the 256-cell LDS window leaves beside a
-// ray's reach, or -- on the global wedge fields -- the span of the cell field minus the reach on both sides
+// ---- ray modes: choose_ray_mode's answers are the public MCL_RAYS_* enumerators (0: the configured kernel cannot run); what the
+// host code asks of one
+bool mode_work_lists(int mode) { return mode == MCL_RAYS_QUAD || mode == MCL_RAYS_CELL || mode == MCL_RAYS_SWEEP; }   // quadrant / wedge windows + fix-up lists
+bool mode_orders(int mode) { return mode == MCL_RAYS_CELL || mode == MCL_RAYS_SWEEP; }       // cell-sorted particles, one particle per lane
+bool mode_sweep(int mode) { return mode == MCL_RAYS_SWEEP; }
+bool mode_fills_pc(int mode) { return mode != 0 && mode != MCL_RAYS_MARCH; }                // every kernel but the literal march works from d_pc
+
 // The hybrid form of k_rays_sweep (ranges beyond the LDS window: the walk leaves the window into the global wedge fields where a
 // ray is that long): for evenly spaced scans (the turned-direction walk), when both sets of fields exist.  MCL_SWEEP_HYBRID=0:
 // the global-field form alone, as in round 4.
@@ -112,6 +114,8 @@ bool sweep_hybrid_decide(mcl_engine *h)
     return true;
 }
 
+// cells the particles of one k_rays_sweep work item may spread over (per axis): what the 256-cell LDS window leaves beside a
+// ray's reach, or -- on the global wedge fields -- the span of the cell field minus the reach on both sides
 int sweep_play(const mcl_engine *h, bool hybrid)
 {
     if (hybrid) return mcl::kSwSide - (mcl::kSwHybReach + 2) - 3;
@@ -119,8 +123,17 @@ int sweep_play(const mcl_engine *h, bool hybrid)
     return mcl::kSwSide - (h->P + 2) - 3;
 }
 
+// the window play the units of a layout are cut for and k_sweep_plan works with (0: no windowed kernel; -1: no cuts at all, MCL_NO_BUCKET_CUTS)
+int unit_play(const mcl_engine *h, int mode, bool hybrid)
+{
+    return h->env_no_bucket_cuts ? -1 : (mode_sweep(mode) ? sweep_play(h, hybrid) : 0);
+}
+
+// upper bound on the units of n sorted particles: the plain grid plus one cut per bucket of a sparse set (mcl::k_unit_table)
 int64_t max_sweep_units(int64_t n) { return (n + mcl::kSwUnit - 1) / mcl::kSwUnit + mcl::kSwMaxCuts + 2; }
 
+// Work items of k_rays_sweep: made on the device from this update's unit statistics (k_sweep_plan, mcl_rays_sweep.h);
+// the host only sizes the list (every unit on its own, once per wedge group, is the longest it can get).
 int launch_sweep_plan(mcl_engine *h, int64_t n, int nwg, int g, bool hybrid)
 {
     const int ngroups = mcl::kWedges / g;
@@ -135,7 +148,7 @@ int launch_sweep_plan(mcl_engine *h, int64_t n, int nwg, int g, bool hybrid)
     return MCL_OK;
 }
 
-// Which ray kernel a launch over n particles takes: 1 march, 2 skip, 3 quad, 4 cell, 5 sweep; 0 = the configured kernel
+// Which ray kernel a launch over n particles takes, as its MCL_RAYS_* enumerator (MARCH .. SWEEP); 0 = the configured kernel
 // cannot run with this map / beam set.  A pure function of the configuration, the map, the beam set and n, so that
 // callers (graph eligibility, table building, mcl_get_planned_ray_kernel) can ask before anything is launched.  *why, when
 // given, receives a static sentence saying what decided (the kernels that address their LDS window from a raw offset are
@@ -145,20 +158,20 @@ int choose_ray_mode(const mcl_engine *h, int64_t n, bool force_skip, const char 
     const char *dummy;
     const char *&w = why ? *why : dummy;
     const int rk = h->cfg.ray_kernel;
-    if (rk == MCL_RAYS_MARCH) { w = "configured: MCL_RAYS_MARCH"; return 1; }
+    if (rk == MCL_RAYS_MARCH) { w = "configured: MCL_RAYS_MARCH"; return MCL_RAYS_MARCH; }
     // k_rays_skip without its LDS layout (never seen): the literal march, same results
     if (rk == MCL_RAYS_SKIP || force_skip) {
-        if (!h->skip_layout_ok) { w = "k_rays_skip's LDS layout check failed at mcl_create: literal march"; return 1; }
+        if (!h->skip_layout_ok) { w = "k_rays_skip's LDS layout check failed at mcl_create: literal march"; return MCL_RAYS_MARCH; }
         w = force_skip ? "fix-up list overflow: the stage is re-run with k_rays_skip" : "configured: MCL_RAYS_SKIP";
-        return 2;
+        return MCL_RAYS_SKIP;
     }
     const char *no_windows = nullptr;                        // why the windowed kernels (quad / cell / sweep) are out, if they are
     if (!h->quad_ok) no_windows = "beam angles are not monotone over less than a turn (or more than 16383 beams): the windowed kernels need contiguous beam ranges per direction wedge";
     else if (h->qside <= 0) no_windows = "MAX_RANGE_PX leaves less than 32 cells of play in a 280-cell byte window: the windowed kernels cannot hold a ray";
     [[maybe_unused]] const bool windows_ok = no_windows == nullptr;           // monotone beams over less than a turn, room for a byte window
 #ifdef MCL_LEGACY_RAY_KERNELS
-    if (rk == MCL_RAYS_QUAD) { w = windows_ok && h->quad_layout_ok ? "configured: MCL_RAYS_QUAD" : (no_windows ? no_windows : "k_rays_quad's LDS layout check failed"); return windows_ok && h->quad_layout_ok ? 3 : 0; }
-    if (rk == MCL_RAYS_CELL) { w = windows_ok && h->cell_layout_ok ? "configured: MCL_RAYS_CELL" : (no_windows ? no_windows : "k_rays_cell's LDS layout check failed"); return windows_ok && h->cell_layout_ok ? 4 : 0; }
+    if (rk == MCL_RAYS_QUAD) { w = windows_ok && h->quad_layout_ok ? "configured: MCL_RAYS_QUAD" : (no_windows ? no_windows : "k_rays_quad's LDS layout check failed"); return windows_ok && h->quad_layout_ok ? MCL_RAYS_QUAD : 0; }
+    if (rk == MCL_RAYS_CELL) { w = windows_ok && h->cell_layout_ok ? "configured: MCL_RAYS_CELL" : (no_windows ? no_windows : "k_rays_cell's LDS layout check failed"); return windows_ok && h->cell_layout_ok ? MCL_RAYS_CELL : 0; }
 #else
     // k_rays_quad / k_rays_cell, the predecessors of k_rays_sweep, are not part of this library (csrc/mcl_rays_legacy.h, a build
     // flag; the tests load libmcl_hip_engine_legacy.so for them)
@@ -173,7 +186,7 @@ int choose_ray_mode(const mcl_engine *h, int64_t n, bool force_skip, const char 
         else if (!h->sweep_layout_ok) no_sweep = "k_rays_sweep's LDS layout check failed at mcl_create";
     }
     const bool sweep_ok = no_sweep == nullptr;
-    if (rk == MCL_RAYS_SWEEP) { w = sweep_ok ? "configured: MCL_RAYS_SWEEP" : no_sweep; return sweep_ok ? 5 : 0; }
+    if (rk == MCL_RAYS_SWEEP) { w = sweep_ok ? "configured: MCL_RAYS_SWEEP" : no_sweep; return sweep_ok ? MCL_RAYS_SWEEP : 0; }
     // AUTO: one particle per lane on cell-sorted particles pays once there are enough particles to fill the machine
     // with 64-particle groups and enough rays to amortise the sort (measured, wall ms skip / quad / cell:
     // 4096 x 1081 0.16/0.28/0.40, 65536 x 1081 0.55/0.56/0.44, 65536 x 61 0.21/0.33/0.25, 262144 x 61 0.47/0.76/0.40);
@@ -184,14 +197,14 @@ int choose_ray_mode(const mcl_engine *h, int64_t n, bool force_skip, const char 
         w = sweep_hybrid(h) ? "AUTO: at least 65536 particles and 2^23 rays, evenly spaced beams; MAX_RANGE_PX > 243 (or MCL_SWEEP_GLOBAL): k_rays_sweep walks in LDS windows and goes on in the wedge fields in global memory where a ray leaves its window"
           : h->sweep_global ? "AUTO: at least 65536 particles and 2^23 rays, monotone beams; MAX_RANGE_PX > 243 (or MCL_SWEEP_GLOBAL): k_rays_sweep probes the wedge fields in global memory"
                             : "AUTO: at least 65536 particles and 2^23 rays, monotone beams, MAX_RANGE_PX <= 243";
-        return 5;
+        return MCL_RAYS_SWEEP;
     }
 #ifdef MCL_LEGACY_RAY_KERNELS
-    if (big && windows_ok && h->cell_layout_ok) { w = no_sweep; return 4; }
+    if (big && windows_ok && h->cell_layout_ok) { w = no_sweep; return MCL_RAYS_CELL; }
 #endif
-    if (!h->skip_layout_ok) { w = "k_rays_skip's LDS layout check failed at mcl_create: literal march"; return 1; }
+    if (!h->skip_layout_ok) { w = "k_rays_skip's LDS layout check failed at mcl_create: literal march"; return MCL_RAYS_MARCH; }
     w = !big ? "AUTO: fewer than 65536 particles or 2^23 rays: the self-contained k_rays_skip is the quickest" : no_sweep;
-    return 2;
+    return MCL_RAYS_SKIP;
 }
 
 // The ordering's tiles over the padded map: occupied tiles are numbered compactly when the map has at most kSortMaxTiles of them
@@ -200,6 +213,23 @@ SortTiles sort_tiles(const mcl_engine *h)
 {
     const int ntx_abs = ((h->Wp * mcl::kSortSub - 1) >> 5) + 1, nty_abs = ((h->Hp * mcl::kSortSub - 1) >> 5) + 1;
     return {ntx_abs, nty_abs, (int64_t)ntx_abs * nty_abs <= mcl::kSortMaxTiles};
+}
+
+// Two ways to the same kind of order (which lanes share a wave; never results).  Counting sort with per-XCD
+// histograms: one returning L2 atomic per particle (~1 per clock and XCD) + a scatter.  From 3M particles a radix
+// sort of (key, index) pairs is quicker -- keys only, rocPRIM's device sort (a plain library sort), then a gather:
+// 4M x 1081 6.57 -> 6.47 ms per update; below, its fixed cost of a dozen launches loses (2M +0.03, 262 144 +0.05 ms).
+bool sort_radix(const mcl_engine *h, int64_t n) { return h->env_sort_radix >= 0 ? h->env_sort_radix != 0 : n >= 3000000; }
+
+// The layout the ordering works from, on `stream`: the bounding box of the particles in d_pc (every 16th of a large set), and
+// the occupied tiles of the map numbered compactly when the map has at most kSortMaxTiles of them (bbox[5] says so)
+void launch_layout(mcl_engine *h, hipStream_t stream, int64_t n, int *bbox, int *tilemark, int *tilemap)
+{
+    const auto [ntx_abs, nty_abs, tiles_ok] = sort_tiles(h);
+    const int bstride = n >= (1 << 20) ? 16 : 1;
+    hipLaunchKernelGGL(mcl::k_cell_bbox, dim3((unsigned)std::min<int64_t>((n / bstride + 255) / 256, 128)), dim3(256), 0, stream, h->d_pc, n,
+                       bstride, h->Wp, h->Hp, bbox, tiles_ok ? tilemark : (int *)nullptr, ntx_abs);
+    if (tiles_ok) hipLaunchKernelGGL(mcl::k_tile_compact, dim3(1), dim3(1024), 0, stream, bbox, tilemark, tilemap, ntx_abs * nty_abs);
 }
 
 // The windowed pass over what k_rays_sweep's windows did not fit (k_rays_skip<.., FAR>): ordered list of the flagged slots,
@@ -220,7 +250,109 @@ int launch_far_windowed(mcl_engine *h, const mcl::RayArgs &a, int64_t n, bool co
     return MCL_OK;
 }
 
-int launch_rays(mcl_engine *h, const double *x, const double *y, const double *th, int64_t n, bool force_skip = false, bool direct_table = false)
+// ---- the ray stage: plan_rays decides, launch_rays launches in phases that read the plan
+// Everything a launch decides before or between its kernels.  Filled by plan_rays with arithmetic on the engine's state: no
+// runtime call, nothing reserved.
+struct RayPlan {
+    int mode = 0;                                           // choose_ray_mode's answer (0: cannot run)
+    bool lists = false, ordered = false, sweep = false;     // mode_work_lists / mode_orders / mode_sweep of it
+    bool count = false;                                     // debug_count_probes: the COUNT instantiations
+    bool timed = false;                                     // without work lists: EV_K0 / EV_K1 recorded around the kernel
+    int R = 1;                                              // k_rays_skip: rays per lane
+    int grid = 1;                                           // k_rays_march / k_rays_skip: workgroups
+    size_t lds = 0;                                         // ... and the nibble window of k_rays_skip
+    int nsl = 1, items_per_slice = 4, sweep_g = 1;          // slices (units for k_rays_sweep), work items per slice, wedges per item
+    int nseg = 1, fix_split = 1;                            // persistent workgroups = fix-up list segments; k_rays_fix workgroups per segment
+    unsigned long long segcap = 0;                          // entries per segment
+    unsigned gfar = 1;                                      // k_rays_far's grid
+    bool hyb = false, glob = false, rec = false, pairs = false;   // the form of k_rays_sweep
+    size_t qlds = 0;                                        // LDS of the kernel with work lists
+    bool far_windowed = false, radix = false, stale_layout = false;
+};
+
+// Slices, list segments and grids of the kernels with work lists (quad, cell, sweep)
+void plan_work_lists(const mcl_engine *h, int64_t n, RayPlan &p)
+{
+    // item granularity: 32 slices per CU (measured best at 4M: 4/8/16/32/64 -> 22.1/20.2/19.7/19.6/20.2 ms), but at
+    // least 256 particles per slice so that the 78 KB window load stays amortised
+    const int spc = h->env_qslices_per_cu > 0 ? h->env_qslices_per_cu : 32;
+    p.nsl = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)spc * h->num_cu, (n + 255) / 256));
+    if (p.ordered) {
+        // k_rays_cell: a slice is a run of the sorted order; 2048 particles = two 64-particle groups per wave.  Longer
+        // slices amortise the window load better, shorter ones balance the persistent workgroups better
+        // (measured at 4M: 1024/2048/4096/8192/16384 -> 8.59/8.04/7.86/7.96/8.64 ms; at 256k: 2048/4096 -> 0.68/0.79 ms)
+        int64_t slice_len = h->env_cell_slice > 0 ? std::max<int64_t>(64, h->env_cell_slice) : (n >= (1 << 21) ? 4096 : 2048);
+        p.nsl = (int)std::max<int64_t>(1, (n + slice_len - 1) / slice_len);
+    }
+    if (p.sweep) {
+        // k_rays_sweep: a work item is (run of 1024-particle units, G wedges); the G wedges of a group share one
+        // partial-sum array.  G = 2 (measured at 4M x 1081, ray kernel / update ms, same device: G = 1 6.50 / 7.87,
+        // 2 6.54 / 7.86, 4 6.69 / 7.97, 8 6.99 / 8.27, 16 7.62 / 8.90: a longer item is a longer tail); G = 1 up to 2M
+        // particles, where the finer items balance better than the sixteen partial-sum arrays cost (262 144 x 1081:
+        // 0.58 / 0.80 -> 0.53 / 0.77, 1M: 1.72 / 2.13 -> 1.63 / 2.07; at 4M G = 1 and 2 are level).
+        // Round 3: with the per-wedge sums added atomically (no partial-sum array per group) G = 1 wins at every size
+        // (4M x 1081, ms per update G = 1 / 2 / 4: 6.80 / 6.91 / 7.08; levine stand-in 7.89 / 8.00 / 8.24)
+        p.sweep_g = h->env_sweep_g > 0 ? h->env_sweep_g : 1;
+        if (p.sweep_g > mcl::kWedges || (mcl::kWedges % p.sweep_g) != 0) p.sweep_g = 1;
+        p.nsl = (int)((n + mcl::kSwUnit - 1) / mcl::kSwUnit);
+    }
+    p.items_per_slice = p.sweep ? mcl::kWedges / p.sweep_g : (p.ordered ? mcl::kWedges : 4);
+    const int max_wg = 2 * (h->num_cu - h->reserved_cus);             // persistent: 2 workgroups per CU
+    p.nseg = (int)std::min<int64_t>(max_wg, p.items_per_slice * (int64_t)p.nsl);   // one segment per persistent workgroup
+    // work list for undecided rays (~0.06 % of the rays in practice): one segment per persistent workgroup of
+    // k_rays_quad with room for 1/256 of that workgroup's share of the rays (at least 2048 entries)
+    // (both forms of k_rays_sweep work with 32 fractional bits: a walk of ~70 rays is handed over once in several thousand)
+    const unsigned long long rays_per_seg = (unsigned long long)n * h->B / p.nseg + 64, seg_div = 256;
+    p.segcap = std::max<unsigned long long>(2048, (rays_per_seg / seg_div + 7) & ~7ull);
+    if ((unsigned long long)n * h->B <= (4ull << 20)) p.segcap = (2 * rays_per_seg + 7) & ~7ull;   // small launch: room for every ray
+    // k_rays_far is bound by global-memory latency: 4 workgroups per CU worth of blocks (2 resident at a time)
+    p.gfar = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4 * (int64_t)h->num_cu, (n + 15) / 16));
+    p.fix_split = std::max(1, std::min(16, (8 * h->num_cu) / std::max(p.nseg, 1)));   // ~8 workgroups of k_rays_fix per CU (2 .. 16 per segment: no difference, round 4)
+}
+
+// Which form of k_rays_sweep THIS update takes, and whether the windowed far pass goes with it
+void plan_sweep_form(mcl_engine *h, RayPlan &p)
+{
+    p.hyb = sweep_hybrid_decide(h);                    // LDS windows as far as they reach, the global fields beyond
+    p.glob = h->sweep_global && !p.hyb;                // probes in global memory: no window in LDS
+    // REC: the walk turns the beam direction by the scan's increment instead of fetching it (evenly spaced scans; the beams'
+    // offsets from the grid sit in LDS behind the window: 8 bytes per table column)
+    // (... as long as two workgroups still fit a CU's 160 KB: up to ~1800 table columns; more beams than that fetch their directions)
+    p.rec = h->rec_ok && h->sweep_rec_layout_ok && h->d_beam_err != nullptr && (size_t)mcl::kSwWinBytes + (size_t)h->ltd_cols * 8 <= 80 * 1024 - 64;
+    // the windowed far pass (four launches that stand down on the device when little is flagged) is only launched when
+    // there is reason to expect work for it: the previous ray stage flagged a fair number of slots, or the particle set
+    // is fresh (set / initialised since).  A misjudgement costs time, never results: without it k_rays_far takes all.
+    p.far_windowed = sweep_far_expected(h);
+    // PAIRS (two rays per lane) where the walk waits for memory: always in the global-field form; in LDS windows for a set
+    // that was set / initialised since the last update (the spread cloud of a re-localisation: -11 % on its first update, where
+    // the tracking cloud gains nothing and the levine stand-in loses 2 %); MCL_SWEEP_PAIRS=0 / 1 overrides
+    p.pairs = p.rec && !p.hyb && (h->env_sweep_pairs >= 0 ? h->env_sweep_pairs != 0 : (p.glob || p.far_windowed));
+    p.qlds = (p.glob ? 0 : (size_t)mcl::kSwWinBytes) + (p.rec ? (size_t)h->ltd_cols * 8 : 0);
+}
+
+// The one piece of state written here is the hybrid's back-off (sweep_hybrid_decide, once per launch that takes k_rays_sweep);
+// the other two a decision leaves behind, far_fresh and last_sweep_*, are written by launch_rays where its reservations are through.
+RayPlan plan_rays(mcl_engine *h, int64_t n, bool force_skip, bool direct_table)
+{
+    RayPlan p;
+    p.mode = choose_ray_mode(h, n, force_skip);
+    p.lists = mode_work_lists(p.mode); p.ordered = mode_orders(p.mode); p.sweep = mode_sweep(p.mode);
+    p.count = h->cfg.debug_count_probes != 0;
+    p.R = h->cfg.rays_per_lane > 0 ? h->cfg.rays_per_lane : 1;   // measured on MI355X: the kernel is VALU-issue-bound, extra chains per lane only add idle slots
+    p.grid = (int)std::max<int64_t>(1, std::min<int64_t>(h->num_cu, (n + 15) / 16));
+    p.lds = (size_t)h->tw_cells * h->tw_cells / 2;
+    p.timed = !p.lists && !h->capturing && !direct_table;
+    if (!p.lists) return p;
+    plan_work_lists(h, n, p);
+    if (p.sweep) plan_sweep_form(h, p);
+    else p.qlds = (size_t)h->qside * h->qside;
+    p.stale_layout = p.ordered && h->layout_stale_used;      // d_bbox / d_tilemap hold the layout to order by: not remade
+    p.radix = p.ordered && sort_radix(h, n);
+    return p;
+}
+
+// Phase 1: what a ray kernel is given whatever its kind (the work lists and the ordering add theirs once they are reserved)
+mcl::RayArgs ray_args(const mcl_engine *h, const double *x, const double *y, const double *th, int64_t n, bool direct_table)
 {
     mcl::RayArgs a{};
     a.x = x; a.y = y; a.th = th; a.n = n;
@@ -230,22 +362,9 @@ int launch_rays(mcl_engine *h, const double *x, const double *y, const double *t
     a.Ltr = h->d_Lt + (size_t)(h->P + 1) * h->bpad;
     a.beam_a0 = h->B > 0 ? (double)h->angles[0] : 0.0;
     a.beam_alast = h->B > 0 ? (double)h->angles[h->B - 1] : 0.0;
-    {
-        const double span = h->B > 1 ? (double)h->angles[h->B - 1] - (double)h->angles[0] : 0.0;
-        a.beam_inv_inc = span > 0.0 ? (double)(h->B - 1) / span : 0.0;
-    }
+    const double span = h->B > 1 ? (double)h->angles[h->B - 1] - (double)h->angles[0] : 0.0;
+    a.beam_inv_inc = span > 0.0 ? (double)(h->B - 1) / span : 0.0;
     a.logw = h->d_logw;
-    if (h->cfg.keep_ray_steps) {
-        // one byte per step index up to 255 px of range, two beyond (allocated here: both the map and the beam set size it)
-        const size_t need = (size_t)h->cap * h->B * (h->P > 255 ? 2 : 1);
-        if (need > h->d_steps.cap) {
-            if (h->capturing) return fail(h, MCL_ERR_HIP, "step buffer missing during capture (internal)");
-            graph_reset(h);
-            MCL_TRY(h->d_steps.reserve(h, need));
-        }
-        if (h->P > 255) a.steps16 = reinterpret_cast<uint16_t *>(h->d_steps.p);
-        else a.steps = h->d_steps;
-    }
     a.grid = h->d_grid; a.W = h->W; a.H = h->H;
     a.res = h->res; a.ox = h->ox; a.oy = h->oy;
     if (direct_table) { a.Ldirect = h->d_L; a.obs_idx = h->d_obs_idx; }       // small updates: no per-update table (do_update)
@@ -254,271 +373,281 @@ int launch_rays(mcl_engine *h, const double *x, const double *y, const double *t
     a.tw_cells = h->tw_cells;
     a.counters = h->d_counters;
     a.force_exact = h->cfg.debug_force_exact;
-    h->last_quad = false;
-    h->last_lf = false;
-    h->max_partials_ready = false;
-    const int mode = choose_ray_mode(h, n, force_skip);
-    if (mode == 0) return fail(h, MCL_ERR_UNSUPPORTED, "MCL_RAYS_QUAD / MCL_RAYS_CELL / MCL_RAYS_SWEEP not usable with this map / beam set");
-    const bool windows = mode >= 3;                 // quadrant / wedge windows + work lists
-    const bool cell = mode >= 4;                    // cell-sorted particles, one particle per lane
-    const bool sweep = mode == 5;
-    int64_t want = (n + 15) / 16;
-    int grid = (int)std::max<int64_t>(1, std::min<int64_t>(h->num_cu, want));
-    if (mode == 2 && !h->pc_ready)             // (an update's resampling kernel has already left them in d_pc otherwise)
-        hipLaunchKernelGGL(mcl::k_particle_prep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, x, y, th, n, h->ox, h->oy,
-                           h->res, h->d_pc, h->d_angle, h->B, (short4 *)nullptr, mcl::PrepClear{});
-    const bool count = h->cfg.debug_count_probes != 0;
-    size_t lds = (size_t)h->tw_cells * h->tw_cells / 2;
-    dim3 g(grid), b(mcl::kRayThreads);
-    int R = h->cfg.rays_per_lane;
-    if (R <= 0) R = 1;   // measured on MI355X: the kernel is VALU-issue-bound, extra chains per lane only add idle slots
-    if (!windows && !h->capturing && !direct_table) HIPCHK(h, hipEventRecord(h->ev[EV_K0], h->stream));
-    if (mode == 1) {
-        if (count) hipLaunchKernelGGL((mcl::k_rays_march<true>), g, b, 0, h->stream, a);
-        else hipLaunchKernelGGL((mcl::k_rays_march<false>), g, b, 0, h->stream, a);
-    } else if (windows) {
-        // work list for undecided rays (~0.06 % of the rays in practice): one segment per persistent workgroup of
-        // k_rays_quad with room for 1/256 of that workgroup's share of the rays (at least 2048 entries)
-        // item granularity: 32 slices per CU (measured best at 4M: 4/8/16/32/64 -> 22.1/20.2/19.7/19.6/20.2 ms), but at
-        // least 256 particles per slice so that the 78 KB window load stays amortised
-        const int spc = h->env_qslices_per_cu > 0 ? h->env_qslices_per_cu : 32;
-        int nsl = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)spc * h->num_cu, (n + 255) / 256));
-        int sweep_g = 1;
-        const bool sweep_hyb_now = sweep && sweep_hybrid_decide(h);      // k_rays_sweep's hybrid form for THIS update
-        if (cell) {
-            // k_rays_cell: a slice is a run of the sorted order; 2048 particles = two 64-particle groups per wave.  Longer
-            // slices amortise the window load better, shorter ones balance the persistent workgroups better
-            // (measured at 4M: 1024/2048/4096/8192/16384 -> 8.59/8.04/7.86/7.96/8.64 ms; at 256k: 2048/4096 -> 0.68/0.79 ms)
-            int64_t slice_len = h->env_cell_slice > 0 ? std::max<int64_t>(64, h->env_cell_slice) : (n >= (1 << 21) ? 4096 : 2048);
-            nsl = (int)std::max<int64_t>(1, (n + slice_len - 1) / slice_len);
-        }
-        const int max_wg = 2 * (h->num_cu - h->reserved_cus);             // persistent: 2 workgroups per CU
-        if (sweep) {
-            // k_rays_sweep: a work item is (run of 1024-particle units, G wedges); the G wedges of a group share one
-            // partial-sum array.  G = 2 (measured at 4M x 1081, ray kernel / update ms, same device: G = 1 6.50 / 7.87,
-            // 2 6.54 / 7.86, 4 6.69 / 7.97, 8 6.99 / 8.27, 16 7.62 / 8.90: a longer item is a longer tail); G = 1 up to 2M
-            // particles, where the finer items balance better than the sixteen partial-sum arrays cost (262 144 x 1081:
-            // 0.58 / 0.80 -> 0.53 / 0.77, 1M: 1.72 / 2.13 -> 1.63 / 2.07; at 4M G = 1 and 2 are level).
-            const int64_t M = (n + mcl::kSwUnit - 1) / mcl::kSwUnit;
-            // Round 3: with the per-wedge sums added atomically (no partial-sum array per group) G = 1 wins at every size
-            // (4M x 1081, ms per update G = 1 / 2 / 4: 6.80 / 6.91 / 7.08; levine stand-in 7.89 / 8.00 / 8.24)
-            sweep_g = h->env_sweep_g > 0 ? h->env_sweep_g : 1;
-            if (sweep_g > mcl::kWedges || (mcl::kWedges % sweep_g) != 0) sweep_g = 1;
-            nsl = (int)M;
-        }
-        const int items_per_slice = sweep ? mcl::kWedges / sweep_g : (cell ? mcl::kWedges : 4);
-        const int nseg = (int)std::min<int64_t>(max_wg, items_per_slice * (int64_t)nsl);   // one segment per persistent workgroup
-        unsigned long long rays_per_seg = (unsigned long long)n * h->B / nseg + 64;
-        // (both forms of k_rays_sweep work with 32 fractional bits: a walk of ~70 rays is handed over once in several thousand)
-        const unsigned long long seg_div = 256;
-        unsigned long long segcap = std::max<unsigned long long>(2048, (rays_per_seg / seg_div + 7) & ~7ull);
-        if ((unsigned long long)n * h->B <= (4ull << 20)) segcap = (2 * rays_per_seg + 7) & ~7ull;   // small launch: room for every ray
-        MCL_TRY(h->d_fix_list.reserve(h, (size_t)nseg * segcap));
-        MCL_TRY(h->d_fix_count.reserve(h, (size_t)nseg * 8));
-        h->fix_cap = segcap;
-        h->fix_segments = nseg;
-        a.qr = cell ? nullptr : h->d_qr;
-        a.qside = sweep ? mcl::kSwSide : h->qside;
-        a.nslices = nsl;
-        a.fix_list = h->d_fix_list; a.fix_count = h->d_fix_count; a.fix_cap = h->fix_cap; a.fix_segments = nseg;
-        a.exact_list = h->d_exact_list; a.exact_count = h->d_result + 14; a.exact_cap = kExactCap;
-        a.far_flags = h->d_far;
-        a.work_counter = h->d_fix_over + 1;                // second word of the 16-byte scratch block
-        a.logw = h->d_logw_acc;
-        {   // per-particle constants; the same pass zeroes the stage's scratch (partial sums are added atomically)
-            mcl::PrepClear clr{};
-            clr.logw_acc = h->d_logw_acc; clr.far_flags = reinterpret_cast<uint32_t *>(h->d_far.p);
-            clr.fix_count = h->d_fix_count; clr.fix_words = nseg * 8; clr.fix_over = h->d_fix_over; clr.exact_count = h->d_result + 14;
-            if (sweep) clr.far_count = h->d_result + 15;
-            const bool stale_layout = cell && h->layout_stale_used;      // d_bbox / d_tilemap hold the layout to order by: not remade
-            if (cell && !stale_layout) clr.bbox = h->d_bbox;          // (the histogram is left all-zero by k_hist_clear of the previous sort)
-            // the window play k_sweep_plan works with (0: no windowed kernel; -1: no cuts at all, MCL_NO_BUCKET_CUTS)
-            clr.bbox_play = h->env_no_bucket_cuts ? -1 : (sweep ? sweep_play(h, sweep_hyb_now) : 0);
-            if (cell && h->pc_ready) {         // the resampling kernel left the constants and zeroed the per-particle scratch
-                clr.logw_acc = nullptr; clr.far_flags = nullptr;
-                // ... and, from the second update of a configuration on, the few words that are not per particle as well
-                const mcl::PrepClear &pc0 = h->prep_passed;
-                const bool done = h->prep_folded && clr.fix_count == pc0.fix_count && clr.fix_words == pc0.fix_words &&
-                                  clr.fix_over == pc0.fix_over && clr.exact_count == pc0.exact_count && clr.far_count == pc0.far_count &&
-                                  clr.bbox == pc0.bbox && clr.bbox_play == pc0.bbox_play && !clr.hist && !pc0.hist;
-                if (!done) hipLaunchKernelGGL(mcl::k_prep_small, dim3(1), dim3(256), 0, h->stream, clr);
-                if (!h->capturing) { h->prep_cache = clr; h->prep_cache_valid = true; h->prep_cache_n = n; }
-            } else {
-                hipLaunchKernelGGL(mcl::k_particle_prep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, x, y, th, n, h->ox, h->oy,
-                                   h->res, h->d_pc, h->d_angle, h->B, cell ? (short4 *)nullptr : h->d_qr, clr);
-            }
-        }
-        if (cell) {
-            // order the particles by (tile, cell, heading): bounding box -> bucket histogram (the atomic's return value
-            // is the rank inside the bucket) -> exclusive scan -> scatter of pc / qr / index
-            const unsigned nb256 = (unsigned)((n + 255) / 256);
-            const int nparts = (int)(mcl::kSortKeySpace / mcl::kHistTile);
-            const int bstride = n >= (1 << 20) ? 16 : 1;
-            // occupied tiles of the map are numbered compactly when the map has at most kSortMaxTiles of them (bbox[5] says so)
-            const auto [ntx_abs, nty_abs, tiles_ok] = sort_tiles(h);
-            const bool stale_layout = h->layout_stale_used;
-            if (!stale_layout) {
-                hipLaunchKernelGGL(mcl::k_cell_bbox, dim3((unsigned)std::min<int64_t>((n / bstride + 255) / 256, 128)), dim3(256), 0,
-                                   h->stream, h->d_pc, n, bstride, h->Wp, h->Hp, h->d_bbox, tiles_ok ? h->d_tilemark : (int *)nullptr, ntx_abs);
-                if (tiles_ok)
-                    hipLaunchKernelGGL(mcl::k_tile_compact, dim3(1), dim3(1024), 0, h->stream, h->d_bbox, h->d_tilemark, h->d_tilemap, ntx_abs * nty_abs);
-            }
-            // Two ways to the same kind of order (which lanes share a wave; never results).  Counting sort with per-XCD
-            // histograms: one returning L2 atomic per particle (~1 per clock and XCD) + a scatter.  From 3M particles a radix
-            // sort of (key, index) pairs is quicker -- keys only, rocPRIM's device sort (a plain library sort), then a gather:
-            // 4M x 1081 6.57 -> 6.47 ms per update; below, its fixed cost of a dozen launches loses (2M +0.03, 262 144 +0.05 ms).
-            const bool radix = h->env_sort_radix >= 0 ? h->env_sort_radix != 0 : n >= 3000000;
-            if (radix) {
-                MCL_TRY(h->d_skey2.reserve(h, (size_t)h->cap));
-                MCL_TRY(h->d_sval2.reserve(h, (size_t)h->cap));
-                size_t tb = 0;
-                HIPCHK(h, rocprim::radix_sort_pairs(nullptr, tb, h->d_skey.p, h->d_skey2.p, h->d_srank.p, h->d_sval2.p, (size_t)n, 0, mcl::kSortKeyLog2, h->stream));
-                MCL_TRY(h->d_sort_tmp.reserve(h, tb));
-                if (!(stale_layout && h->keys_done))       // (else the resampling kernel wrote the pairs)
-                    hipLaunchKernelGGL(mcl::k_sort_keys, dim3(nb256), dim3(256), 0, h->stream, h->d_pc, th, n, h->Wp, h->Hp, h->d_bbox, h->d_skey, h->d_srank,
-                                       h->d_tilemap, ntx_abs);
-                tb = h->d_sort_tmp.cap;
-                HIPCHK(h, rocprim::radix_sort_pairs(h->d_sort_tmp.p, tb, h->d_skey.p, h->d_skey2.p, h->d_srank.p, h->d_sval2.p, (size_t)n, 0, mcl::kSortKeyLog2, h->stream));
-                hipLaunchKernelGGL(mcl::k_sort_gather, dim3(nb256), dim3(256), 0, h->stream, h->d_pc, th, n, h->d_sval2, h->d_pcs, h->d_ths, h->d_perm,
-                                   sweep ? h->d_skey2 : (const uint32_t *)nullptr, h->d_bbox, h->d_cut_start, h->d_cut_end);
-            } else {
-            hipLaunchKernelGGL(mcl::k_sort_hist, dim3(nb256), dim3(256), 0, h->stream, h->d_pc, th, n, h->Wp, h->Hp, h->d_bbox, h->d_hist,
-                               h->d_skey, h->d_srank, h->d_tile_used, h->d_tilemap, ntx_abs);
-            hipLaunchKernelGGL(mcl::k_hist_partials, dim3(nparts), dim3(256), 0, h->stream, h->d_hist, h->d_histpart, h->d_tile_used);
-            hipLaunchKernelGGL(mcl::k_hist_final, dim3(nparts), dim3(256), 0, h->stream, h->d_hist, h->d_histpart, h->d_tile_used);
-            hipLaunchKernelGGL(mcl::k_sort_scatter, dim3(nb256), dim3(256), 0, h->stream, h->d_pc, th, n, h->d_skey, h->d_srank,
-                               h->d_hist, h->d_pcs, h->d_ths, h->d_perm);
-            }
-            if (sweep) {
-                // units of the sorted order (cut at tile borders when the set is ordered by whole tiles), from the bucket
-                // offsets the scatter has just used -- before they are cleared
-                const size_t mu = (size_t)max_sweep_units(n);
-                MCL_TRY(h->d_unit_sums.reserve(h, mu * 2));
-                MCL_TRY(h->d_unit_begin.reserve(h, mu + 1));
-                MCL_TRY(h->d_nunits.reserve(h, 1));
-                hipLaunchKernelGGL(mcl::k_unit_table, dim3(1), dim3(1024), 0, h->stream, h->d_bbox, n, h->d_hist, h->d_histpart, h->d_tile_used,
-                                   radix ? h->d_cut_start : (uint32_t *)nullptr, h->d_cut_end, h->d_unit_begin, h->d_nunits, (int)mu);
-            }
-            if (!radix && !sweep) hipLaunchKernelGGL(mcl::k_hist_clear, dim3(nparts), dim3(256), 0, h->stream, h->d_hist, h->d_tile_used);
-            if (sweep) {
-                // (... and, after a counting sort, the histogram's used tiles back to zero: k_hist_clear's work)
-                hipLaunchKernelGGL(mcl::k_unit_sums, dim3((unsigned)std::min<int64_t>(max_sweep_units(n), (n + mcl::kSwUnit - 1) / mcl::kSwUnit + 256)), dim3(256), 0, h->stream, h->d_pcs, h->d_unit_begin, h->d_nunits,
-                                   h->d_unit_sums, radix ? (uint32_t *)nullptr : h->d_hist, h->d_tile_used, nparts);
-            } else {
-                MCL_TRY(h->d_slice_mean.reserve(h, (size_t)nsl));
-                hipLaunchKernelGGL(mcl::k_slice_means, dim3((unsigned)nsl), dim3(256), 0, h->stream, h->d_pcs, n, (n + nsl - 1) / nsl, h->d_slice_mean);
-            }
-            a.pcs = h->d_pcs; a.ths = h->d_ths; a.perm = h->d_perm; a.slice_mean = h->d_slice_mean;
-            a.distw = h->d_distw; a.distw_stride = (size_t)h->Hp * h->Wps;
-        }
-        // the tables of this update's scan were built on the second stream beside the resampling and the ordering: from here on they are read
-        if (h->obs_wait_pending) { h->obs_wait_pending = false; HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_obs, 0)); }
-        if (sweep) {
-            if (!h->d_Ltd) return fail(h, MCL_ERR_HIP, "k_rays_sweep: table not allocated (internal)");
-            if (!h->ltd_ready) build_ltd(h);          // a caller whose table decision was made for another particle count
-            const int rc_plan = launch_sweep_plan(h, n, nseg, sweep_g, sweep_hyb_now);
-            if (rc_plan) return rc_plan;
-            a.sweep_g = sweep_g; a.Ltd = h->d_Ltd; a.ltd_cols = h->ltd_cols;
-            a.split16 = h->env_sw_split16 >= 0 ? h->env_sw_split16 : 0;
-            a.beam_csx = h->sweep_global ? h->d_beam_csxg : h->d_beam_csx; a.beam_pad = h->beam_pad; a.beam_margin = h->beam_margin;
-            a.beam_csi = h->d_beam_csi; a.beam_err = h->d_beam_err; a.rec_k = 2.0 * h->rec_c;
-            a.distg = h->d_distg; a.distg_stride = h->distg_stride; a.distg_pitch = h->distg_pitch;
-            a.items = h->d_items; a.centres = h->d_centres; a.nitems = 0; a.nitems_ptr = h->d_nitems; a.unit_sums = h->d_unit_sums; a.unit_begin = h->d_unit_begin; a.slot_space = 1;
-            MCL_TRY(h->d_far_list.reserve(h, (size_t)h->cap));
-            MCL_TRY(h->d_far_sorted.reserve(h, (size_t)h->cap));
-            MCL_TRY(h->d_far_cnt.reserve(h, (size_t)h->cap / mcl::kFarTile + 2));
-            // the windowed far pass (four launches that stand down on the device when little is flagged) is only launched when
-            // there is reason to expect work for it: the previous ray stage flagged a fair number of slots, or the particle set
-            // is fresh (set / initialised since).  A misjudgement costs time, never results: without it k_rays_far takes all.
-            a.far_sorted = h->d_far_sorted;
-            a.far_windowed = sweep_far_expected(h) ? 1 : 0;
-            h->far_fresh = false;
-            a.far_list = h->d_far_list; a.far_count = h->d_result + 15;      // word 15 of the result block, zeroed below
-        }
-        const bool sweep_hyb = sweep && sweep_hyb_now;          // LDS windows as far as they reach, the global fields beyond
-        const bool sweep_glob = sweep && h->sweep_global && !sweep_hyb;       // probes in global memory: no window in LDS
-        // REC: the walk turns the beam direction by the scan's increment instead of fetching it (evenly spaced scans; the beams'
-        // offsets from the grid sit in LDS behind the window: 8 bytes per table column)
-        // (... as long as two workgroups still fit a CU's 160 KB: up to ~1800 table columns; more beams than that fetch their directions)
-        const bool sweep_rec = sweep && h->rec_ok && h->sweep_rec_layout_ok && h->d_beam_err != nullptr &&
-                               (size_t)mcl::kSwWinBytes + (size_t)h->ltd_cols * 8 <= 80 * 1024 - 64;
-        // PAIRS (two rays per lane) where the walk waits for memory: always in the global-field form; in LDS windows for a set
-        // that was set / initialised since the last update (the spread cloud of a re-localisation: -11 % on its first update, where
-        // the tracking cloud gains nothing and the levine stand-in loses 2 %); MCL_SWEEP_PAIRS=0 / 1 overrides
-        const bool sweep_pairs = sweep_rec && !sweep_hyb && (h->env_sweep_pairs >= 0 ? h->env_sweep_pairs != 0 : (sweep_glob || a.far_windowed != 0));
-        size_t qlds = sweep ? (sweep_glob ? 0 : (size_t)mcl::kSwWinBytes) + (sweep_rec ? (size_t)h->ltd_cols * 8 : 0) : (size_t)h->qside * h->qside;
-        h->last_sweep_global = sweep_glob ? 1 : (sweep_hyb ? 2 : 0); h->last_sweep_rec = sweep_rec ? 1 : 0; h->last_sweep_pairs = (sweep_rec && (sweep_glob || sweep_pairs)) ? 1 : 0;
-        dim3 qg((unsigned)nseg);   // persistent: 2 workgroups per CU
-        DevBuf<unsigned long long> d_dbg;
-        const char *dbgpath = h->env_debug_wg.empty() ? nullptr : h->env_debug_wg.c_str();
-        if (dbgpath) { MCL_TRY(d_dbg.reserve(h, (size_t)qg.x * 4)); HIPCHK(h, hipMemset(d_dbg, 0, (size_t)qg.x * 32)); a.dbg = d_dbg; }
-        // k_rays_far is bound by global-memory latency: 4 workgroups per CU worth of blocks (2 resident at a time)
-        dim3 gfar((unsigned)std::max<int64_t>(1, std::min<int64_t>(4 * (int64_t)h->num_cu, (n + 15) / 16)));
-        const int fix_split = std::max(1, std::min(16, (8 * h->num_cu) / std::max(nseg, 1)));   // ~8 workgroups of k_rays_fix per CU (2 .. 16 per segment: no difference, round 4)
-        if (!sweep) HIPCHK(h, hipEventRecord(h->ev[EV_K0], h->stream));
-        if (count) {
-            if (sweep_hyb) hipExtLaunchKernelGGL((mcl::k_rays_sweep<true, false, true, false, true>), qg, b, qlds, h->stream, nullptr, h->ev[EV_K1], 0, a);
-            else if (sweep_glob && sweep_rec) hipExtLaunchKernelGGL((mcl::k_rays_sweep<true, true, true, true>), qg, b, qlds, h->stream, nullptr, h->ev[EV_K1], 0, a);
-            else if (sweep_glob) hipExtLaunchKernelGGL((mcl::k_rays_sweep<true, true>), qg, b, qlds, h->stream, nullptr, h->ev[EV_K1], 0, a);
-            else if (sweep && sweep_rec && sweep_pairs) hipExtLaunchKernelGGL((mcl::k_rays_sweep<true, false, true, true>), qg, b, qlds, h->stream, nullptr, h->ev[EV_K1], 0, a);
-            else if (sweep && sweep_rec) hipExtLaunchKernelGGL((mcl::k_rays_sweep<true, false, true>), qg, b, qlds, h->stream, nullptr, h->ev[EV_K1], 0, a);
-            else if (sweep) hipExtLaunchKernelGGL((mcl::k_rays_sweep<true>), qg, b, qlds, h->stream, nullptr, h->ev[EV_K1], 0, a);
-#ifdef MCL_LEGACY_RAY_KERNELS
-            else if (cell) hipLaunchKernelGGL((mcl::k_rays_cell<true>), qg, b, qlds, h->stream, a);
-            else hipLaunchKernelGGL((mcl::k_rays_quad<true>), qg, b, qlds, h->stream, a);
-#endif
-            if (!sweep) HIPCHK(h, hipEventRecord(h->ev[EV_K1], h->stream));
-            if (sweep && a.far_windowed) { const int rcw = launch_far_windowed(h, a, n, true); if (rcw) return rcw; }
-            hipLaunchKernelGGL((mcl::k_rays_far<true>), gfar, b, 0, h->stream, a);
-            hipLaunchKernelGGL((mcl::k_rays_fix<true>), dim3(nseg * fix_split), dim3(256), 0, h->stream, a);
-            hipLaunchKernelGGL((mcl::k_rays_exact<true>), dim3(2 * h->num_cu), dim3(256), 0, h->stream, a);
-        } else {
-            if (sweep_hyb) hipExtLaunchKernelGGL((mcl::k_rays_sweep<false, false, true, false, true>), qg, b, qlds, h->stream, nullptr, h->ev[EV_K1], 0, a);
-            else if (sweep_glob && sweep_rec) hipExtLaunchKernelGGL((mcl::k_rays_sweep<false, true, true, true>), qg, b, qlds, h->stream, nullptr, h->ev[EV_K1], 0, a);
-            else if (sweep_glob) hipExtLaunchKernelGGL((mcl::k_rays_sweep<false, true>), qg, b, qlds, h->stream, nullptr, h->ev[EV_K1], 0, a);
-            else if (sweep && sweep_rec && sweep_pairs) hipExtLaunchKernelGGL((mcl::k_rays_sweep<false, false, true, true>), qg, b, qlds, h->stream, nullptr, h->ev[EV_K1], 0, a);
-            else if (sweep && sweep_rec) hipExtLaunchKernelGGL((mcl::k_rays_sweep<false, false, true>), qg, b, qlds, h->stream, nullptr, h->ev[EV_K1], 0, a);
-            else if (sweep) hipExtLaunchKernelGGL((mcl::k_rays_sweep<false>), qg, b, qlds, h->stream, nullptr, h->ev[EV_K1], 0, a);
-#ifdef MCL_LEGACY_RAY_KERNELS
-            else if (cell) hipLaunchKernelGGL((mcl::k_rays_cell<false>), qg, b, qlds, h->stream, a);
-            else hipLaunchKernelGGL((mcl::k_rays_quad<false>), qg, b, qlds, h->stream, a);
-#endif
-            if (!sweep) HIPCHK(h, hipEventRecord(h->ev[EV_K1], h->stream));
-            if (sweep && a.far_windowed) { const int rcw = launch_far_windowed(h, a, n, false); if (rcw) return rcw; }
-            hipLaunchKernelGGL((mcl::k_rays_far<false>), gfar, b, 0, h->stream, a);
-            hipLaunchKernelGGL((mcl::k_rays_fix<false>), dim3(nseg * fix_split), dim3(256), 0, h->stream, a);
-            hipLaunchKernelGGL((mcl::k_rays_exact<false>), dim3(2 * h->num_cu), dim3(256), 0, h->stream, a);
-        }
-        if (sweep) {
-            // the slot accumulators (k_rays_sweep's per-wedge sums + what the far / fix / exact kernels added) -> d_logw in particle
-            // order, the per-workgroup maxima, and the overflow flag of the fix-up lists (k_fix_overflow's job for the other kernels)
-            hipExtLaunchKernelGGL(mcl::k_combine_logw, dim3(mcl::kRedBlocks), dim3(256), 0, h->stream, nullptr, h->ev[EV_RAYS], 0, n, h->d_perm.p, h->d_logw_acc.p,
-                                  h->d_logw.p, h->d_maxpart.p, h->d_fix_count.p, nseg, segcap, h->d_fix_over);
-            h->ev_rays_bound = true;               // (the stage's last kernel: EV_RAYS is its stop event)
-            h->max_partials_ready = true;
-        } else {
-            hipLaunchKernelGGL(mcl::k_fix_overflow, dim3(1), dim3(256), 0, h->stream, h->d_fix_count, nseg, segcap, h->d_fix_over);
-            hipLaunchKernelGGL(mcl::k_gather_logw, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d_logw_acc, n, h->d_logw);
-        }
-        if (d_dbg) {
-            std::vector<unsigned long long> hd((size_t)qg.x * 4);
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            HIPCHK(h, hipMemcpy(hd.data(), d_dbg, hd.size() * 8, hipMemcpyDeviceToHost));
-            if (FILE *f = fopen(dbgpath, "wb")) { fwrite(hd.data(), 8, hd.size(), f); fclose(f); }
-        }
-        h->last_quad = true;
-    } else if (count) {
-        hipLaunchKernelGGL((mcl::k_rays_skip<1, true>), g, b, lds, h->stream, a);
+    return a;
+}
+
+// Phase 2 (keep_ray_steps): one byte per step index up to 255 px of range, two beyond (allocated here: both the map and the beam set size it)
+int ray_step_buffer(mcl_engine *h, mcl::RayArgs &a)
+{
+    if (!h->cfg.keep_ray_steps) return MCL_OK;
+    const size_t need = (size_t)h->cap * h->B * (h->P > 255 ? 2 : 1);
+    if (need > h->d_steps.cap) {
+        if (h->capturing) return fail(h, MCL_ERR_HIP, "step buffer missing during capture (internal)");
+        graph_reset(h);
+        MCL_TRY(h->d_steps.reserve(h, need));
+    }
+    if (h->P > 255) a.steps16 = reinterpret_cast<uint16_t *>(h->d_steps.p);
+    else a.steps = h->d_steps;
+    return MCL_OK;
+}
+
+// Phase 3a (work lists): the fix-up lists, one segment per persistent workgroup, and what the kernels are told of them
+int ray_fix_lists(mcl_engine *h, const RayPlan &p, mcl::RayArgs &a)
+{
+    MCL_TRY(h->d_fix_list.reserve(h, (size_t)p.nseg * p.segcap));
+    MCL_TRY(h->d_fix_count.reserve(h, (size_t)p.nseg * 8));
+    h->fix_cap = p.segcap;
+    h->fix_segments = p.nseg;
+    a.qr = p.ordered ? nullptr : h->d_qr;
+    a.qside = p.sweep ? mcl::kSwSide : h->qside;
+    a.nslices = p.nsl;
+    a.fix_list = h->d_fix_list; a.fix_count = h->d_fix_count; a.fix_cap = h->fix_cap; a.fix_segments = p.nseg;
+    a.exact_list = h->d_exact_list; a.exact_count = h->d_result + 14; a.exact_cap = kExactCap;
+    a.far_flags = h->d_far;
+    a.work_counter = h->d_fix_over + 1;                // second word of the 16-byte scratch block
+    a.logw = h->d_logw_acc;
+    return MCL_OK;
+}
+
+// Phase 3: per-particle constants.  With work lists the same pass zeroes the stage's scratch (partial sums are added atomically);
+// k_rays_skip only wants the constants, and an update's resampling kernel has usually left them in d_pc already.
+void ray_prep(mcl_engine *h, const RayPlan &p, const mcl::RayArgs &a)
+{
+    const dim3 grid((unsigned)((a.n + 255) / 256));
+    if (!p.lists) {
+        if (p.mode == MCL_RAYS_SKIP && !h->pc_ready)
+            hipLaunchKernelGGL(mcl::k_particle_prep, grid, dim3(256), 0, h->stream, a.x, a.y, a.th, a.n, h->ox, h->oy, h->res, h->d_pc, h->d_angle, h->B,
+                               (short4 *)nullptr, mcl::PrepClear{});
+        return;
+    }
+    mcl::PrepClear clr{};
+    clr.logw_acc = h->d_logw_acc; clr.far_flags = reinterpret_cast<uint32_t *>(h->d_far.p);
+    clr.fix_count = h->d_fix_count; clr.fix_words = p.nseg * 8; clr.fix_over = h->d_fix_over; clr.exact_count = h->d_result + 14;
+    if (p.sweep) clr.far_count = h->d_result + 15;
+    if (p.ordered && !p.stale_layout) clr.bbox = h->d_bbox;          // (the histogram is left all-zero by k_hist_clear of the previous sort)
+    clr.bbox_play = unit_play(h, p.mode, p.hyb);
+    if (p.ordered && h->pc_ready) {         // the resampling kernel left the constants and zeroed the per-particle scratch
+        clr.logw_acc = nullptr; clr.far_flags = nullptr;
+        // ... and, from the second update of a configuration on, the few words that are not per particle as well
+        const mcl::PrepClear &pc0 = h->prep_passed;
+        const bool done = h->prep_folded && clr.fix_count == pc0.fix_count && clr.fix_words == pc0.fix_words &&
+                          clr.fix_over == pc0.fix_over && clr.exact_count == pc0.exact_count && clr.far_count == pc0.far_count &&
+                          clr.bbox == pc0.bbox && clr.bbox_play == pc0.bbox_play && !clr.hist && !pc0.hist;
+        if (!done) hipLaunchKernelGGL(mcl::k_prep_small, dim3(1), dim3(256), 0, h->stream, clr);
+        if (!h->capturing) { h->prep_cache = clr; h->prep_cache_valid = true; h->prep_cache_n = a.n; }
     } else {
-        switch (R) {
-        case 1: hipLaunchKernelGGL((mcl::k_rays_skip<1, false>), g, b, lds, h->stream, a); break;
-        case 2: hipLaunchKernelGGL((mcl::k_rays_skip<2, false>), g, b, lds, h->stream, a); break;
-        case 3: hipLaunchKernelGGL((mcl::k_rays_skip<3, false>), g, b, lds, h->stream, a); break;
-        default: hipLaunchKernelGGL((mcl::k_rays_skip<4, false>), g, b, lds, h->stream, a); break;
+        hipLaunchKernelGGL(mcl::k_particle_prep, grid, dim3(256), 0, h->stream, a.x, a.y, a.th, a.n, h->ox, h->oy, h->res, h->d_pc, h->d_angle, h->B,
+                           p.ordered ? (short4 *)nullptr : h->d_qr, clr);
+    }
+}
+
+// Phase 7 for MCL_RAYS_MARCH.  (Up here, and k_rays_skip's launch in ray_kernel below: the compiler lays a unit's kernels out in the
+// order their instantiations are first named, and the names of this file keep the order they always had -- march, the library
+// sort, the kernels with work lists, skip -- so that a change of the host code leaves the code object byte for byte as it was.)
+void ray_kernel_march(mcl_engine *h, const RayPlan &p, const mcl::RayArgs &a)
+{
+    if (p.count) hipLaunchKernelGGL((mcl::k_rays_march<true>), dim3(p.grid), dim3(mcl::kRayThreads), 0, h->stream, a);
+    else hipLaunchKernelGGL((mcl::k_rays_march<false>), dim3(p.grid), dim3(mcl::kRayThreads), 0, h->stream, a);
+}
+
+// Phase 4 (cell, sweep): order the particles by (tile, cell, heading): bounding box -> bucket histogram (the atomic's return
+// value is the rank inside the bucket) -> exclusive scan -> scatter of pc / qr / index; or (sort_radix) a library sort of
+// (key, index) pairs and a gather
+int ray_order(mcl_engine *h, const RayPlan &p, const mcl::RayArgs &a)
+{
+    const int64_t n = a.n;
+    const unsigned nb256 = (unsigned)((n + 255) / 256);
+    const int nparts = (int)(mcl::kSortKeySpace / mcl::kHistTile);
+    const int ntx_abs = sort_tiles(h).ntx_abs;
+    if (!p.stale_layout) launch_layout(h, h->stream, n, h->d_bbox, h->d_tilemark, h->d_tilemap);
+    if (!p.radix) {
+        hipLaunchKernelGGL(mcl::k_sort_hist, dim3(nb256), dim3(256), 0, h->stream, h->d_pc, a.th, n, h->Wp, h->Hp, h->d_bbox, h->d_hist,
+                           h->d_skey, h->d_srank, h->d_tile_used, h->d_tilemap, ntx_abs);
+        hipLaunchKernelGGL(mcl::k_hist_partials, dim3(nparts), dim3(256), 0, h->stream, h->d_hist, h->d_histpart, h->d_tile_used);
+        hipLaunchKernelGGL(mcl::k_hist_final, dim3(nparts), dim3(256), 0, h->stream, h->d_hist, h->d_histpart, h->d_tile_used);
+        hipLaunchKernelGGL(mcl::k_sort_scatter, dim3(nb256), dim3(256), 0, h->stream, h->d_pc, a.th, n, h->d_skey, h->d_srank,
+                           h->d_hist, h->d_pcs, h->d_ths, h->d_perm);
+        return MCL_OK;
+    }
+    MCL_TRY(h->d_skey2.reserve(h, (size_t)h->cap));
+    MCL_TRY(h->d_sval2.reserve(h, (size_t)h->cap));
+    size_t tb = 0;
+    HIPCHK(h, rocprim::radix_sort_pairs(nullptr, tb, h->d_skey.p, h->d_skey2.p, h->d_srank.p, h->d_sval2.p, (size_t)n, 0, mcl::kSortKeyLog2, h->stream));
+    MCL_TRY(h->d_sort_tmp.reserve(h, tb));
+    if (!(p.stale_layout && h->keys_done))       // (else the resampling kernel wrote the pairs)
+        hipLaunchKernelGGL(mcl::k_sort_keys, dim3(nb256), dim3(256), 0, h->stream, h->d_pc, a.th, n, h->Wp, h->Hp, h->d_bbox, h->d_skey, h->d_srank,
+                           h->d_tilemap, ntx_abs);
+    tb = h->d_sort_tmp.cap;
+    HIPCHK(h, rocprim::radix_sort_pairs(h->d_sort_tmp.p, tb, h->d_skey.p, h->d_skey2.p, h->d_srank.p, h->d_sval2.p, (size_t)n, 0, mcl::kSortKeyLog2, h->stream));
+    hipLaunchKernelGGL(mcl::k_sort_gather, dim3(nb256), dim3(256), 0, h->stream, h->d_pc, a.th, n, h->d_sval2, h->d_pcs, h->d_ths, h->d_perm,
+                       p.sweep ? h->d_skey2 : (const uint32_t *)nullptr, h->d_bbox, h->d_cut_start, h->d_cut_end);
+    return MCL_OK;
+}
+
+// Phase 5 (cell, sweep): what the kernel works from in the sorted order -- k_rays_sweep the unit table and the units' sums,
+// k_rays_cell the means of its slices
+int ray_units(mcl_engine *h, const RayPlan &p, mcl::RayArgs &a)
+{
+    const int64_t n = a.n;
+    const int nparts = (int)(mcl::kSortKeySpace / mcl::kHistTile);
+    if (p.sweep) {
+        // units of the sorted order (cut at tile borders when the set is ordered by whole tiles), from the bucket
+        // offsets the scatter has just used -- before they are cleared
+        const size_t mu = (size_t)max_sweep_units(n);
+        MCL_TRY(h->d_unit_sums.reserve(h, mu * 2));
+        MCL_TRY(h->d_unit_begin.reserve(h, mu + 1));
+        MCL_TRY(h->d_nunits.reserve(h, 1));
+        hipLaunchKernelGGL(mcl::k_unit_table, dim3(1), dim3(1024), 0, h->stream, h->d_bbox, n, h->d_hist, h->d_histpart, h->d_tile_used,
+                           p.radix ? h->d_cut_start : (uint32_t *)nullptr, h->d_cut_end, h->d_unit_begin, h->d_nunits, (int)mu);
+        // (... and, after a counting sort, the histogram's used tiles back to zero: k_hist_clear's work)
+        hipLaunchKernelGGL(mcl::k_unit_sums, dim3((unsigned)std::min<int64_t>(max_sweep_units(n), (n + mcl::kSwUnit - 1) / mcl::kSwUnit + 256)), dim3(256), 0, h->stream, h->d_pcs, h->d_unit_begin, h->d_nunits,
+                           h->d_unit_sums, p.radix ? (uint32_t *)nullptr : h->d_hist, h->d_tile_used, nparts);
+    } else {
+        if (!p.radix) hipLaunchKernelGGL(mcl::k_hist_clear, dim3(nparts), dim3(256), 0, h->stream, h->d_hist, h->d_tile_used);
+        MCL_TRY(h->d_slice_mean.reserve(h, (size_t)p.nsl));
+        hipLaunchKernelGGL(mcl::k_slice_means, dim3((unsigned)p.nsl), dim3(256), 0, h->stream, h->d_pcs, n, (n + p.nsl - 1) / p.nsl, h->d_slice_mean);
+    }
+    a.pcs = h->d_pcs; a.ths = h->d_ths; a.perm = h->d_perm; a.slice_mean = h->d_slice_mean;
+    a.distw = h->d_distw; a.distw_stride = (size_t)h->Hp * h->Wps;
+    return MCL_OK;
+}
+
+// Phase 6 (sweep): the table of this scan, the work items (k_sweep_plan) and the lists of the far pass
+int ray_sweep_items(mcl_engine *h, const RayPlan &p, mcl::RayArgs &a)
+{
+    if (!h->d_Ltd) return fail(h, MCL_ERR_HIP, "k_rays_sweep: table not allocated (internal)");
+    if (!h->ltd_ready) build_ltd(h);          // a caller whose table decision was made for another particle count
+    MCL_TRY(launch_sweep_plan(h, a.n, p.nseg, p.sweep_g, p.hyb));
+    a.sweep_g = p.sweep_g; a.Ltd = h->d_Ltd; a.ltd_cols = h->ltd_cols;
+    a.split16 = h->env_sw_split16 >= 0 ? h->env_sw_split16 : 0;
+    a.beam_csx = h->sweep_global ? h->d_beam_csxg : h->d_beam_csx; a.beam_pad = h->beam_pad; a.beam_margin = h->beam_margin;
+    a.beam_csi = h->d_beam_csi; a.beam_err = h->d_beam_err; a.rec_k = 2.0 * h->rec_c;
+    a.distg = h->d_distg; a.distg_stride = h->distg_stride; a.distg_pitch = h->distg_pitch;
+    a.items = h->d_items; a.centres = h->d_centres; a.nitems = 0; a.nitems_ptr = h->d_nitems; a.unit_sums = h->d_unit_sums; a.unit_begin = h->d_unit_begin; a.slot_space = 1;
+    MCL_TRY(h->d_far_list.reserve(h, (size_t)h->cap));
+    MCL_TRY(h->d_far_sorted.reserve(h, (size_t)h->cap));
+    MCL_TRY(h->d_far_cnt.reserve(h, (size_t)h->cap / mcl::kFarTile + 2));
+    a.far_sorted = h->d_far_sorted;
+    a.far_windowed = p.far_windowed ? 1 : 0;
+    a.far_list = h->d_far_list; a.far_count = h->d_result + 15;      // word 15 of the result block, zeroed by phase 3
+    return MCL_OK;
+}
+
+// Phases 7 and 8 with work lists: the ray kernel, then what it left undecided -- the particles its windows did not fit (windowed far
+// pass, k_rays_far), the listed rays (k_rays_fix), the exact march (k_rays_exact).  Every form is named here once; COUNT
+// (debug_count_probes) is the caller's template argument.  k_rays_sweep's stop event is EV_K1 (its duration, dispatch included, at no
+// cost; EV_K0 is k_sweep_plan's); the legacy kernels are bracketed by records.
+template <bool COUNT>
+int ray_kernel_lists(mcl_engine *h, const RayPlan &p, const mcl::RayArgs &a)
+{
+    const dim3 qg((unsigned)p.nseg), b(mcl::kRayThreads);   // persistent: 2 workgroups per CU
+    if (!p.sweep) HIPCHK(h, hipEventRecord(h->ev[EV_K0], h->stream));
+    if (p.hyb) hipExtLaunchKernelGGL((mcl::k_rays_sweep<COUNT, false, true, false, true>), qg, b, p.qlds, h->stream, nullptr, h->ev[EV_K1], 0, a);
+    else if (p.glob && p.rec) hipExtLaunchKernelGGL((mcl::k_rays_sweep<COUNT, true, true, true>), qg, b, p.qlds, h->stream, nullptr, h->ev[EV_K1], 0, a);
+    else if (p.glob) hipExtLaunchKernelGGL((mcl::k_rays_sweep<COUNT, true>), qg, b, p.qlds, h->stream, nullptr, h->ev[EV_K1], 0, a);
+    else if (p.sweep && p.rec && p.pairs) hipExtLaunchKernelGGL((mcl::k_rays_sweep<COUNT, false, true, true>), qg, b, p.qlds, h->stream, nullptr, h->ev[EV_K1], 0, a);
+    else if (p.sweep && p.rec) hipExtLaunchKernelGGL((mcl::k_rays_sweep<COUNT, false, true>), qg, b, p.qlds, h->stream, nullptr, h->ev[EV_K1], 0, a);
+    else if (p.sweep) hipExtLaunchKernelGGL((mcl::k_rays_sweep<COUNT>), qg, b, p.qlds, h->stream, nullptr, h->ev[EV_K1], 0, a);
+#ifdef MCL_LEGACY_RAY_KERNELS
+    else if (p.ordered) hipLaunchKernelGGL((mcl::k_rays_cell<COUNT>), qg, b, p.qlds, h->stream, a);
+    else hipLaunchKernelGGL((mcl::k_rays_quad<COUNT>), qg, b, p.qlds, h->stream, a);
+#endif
+    if (!p.sweep) HIPCHK(h, hipEventRecord(h->ev[EV_K1], h->stream));
+    if (p.sweep && p.far_windowed) MCL_TRY(launch_far_windowed(h, a, a.n, COUNT));
+    hipLaunchKernelGGL((mcl::k_rays_far<COUNT>), dim3(p.gfar), b, 0, h->stream, a);
+    hipLaunchKernelGGL((mcl::k_rays_fix<COUNT>), dim3(p.nseg * p.fix_split), dim3(256), 0, h->stream, a);
+    hipLaunchKernelGGL((mcl::k_rays_exact<COUNT>), dim3(2 * h->num_cu), dim3(256), 0, h->stream, a);
+    return MCL_OK;
+}
+// (instantiated here, not at the end of the unit: mcl_create's layout checks name the forms of k_rays_sweep too, and the first naming places a kernel)
+template int ray_kernel_lists<true>(mcl_engine *, const RayPlan &, const mcl::RayArgs &);
+template int ray_kernel_lists<false>(mcl_engine *, const RayPlan &, const mcl::RayArgs &);
+
+// Phase 7 (and 8): the ray kernel of the plan's mode; without work lists one launch, timed by records unless it is part of a captured tail
+int ray_kernel(mcl_engine *h, const RayPlan &p, const mcl::RayArgs &a)
+{
+    if (p.lists) return p.count ? ray_kernel_lists<true>(h, p, a) : ray_kernel_lists<false>(h, p, a);
+    const dim3 g(p.grid), b(mcl::kRayThreads);
+    if (p.timed) HIPCHK(h, hipEventRecord(h->ev[EV_K0], h->stream));
+    if (p.mode == MCL_RAYS_MARCH) ray_kernel_march(h, p, a);
+    else if (p.count) hipLaunchKernelGGL((mcl::k_rays_skip<1, true>), g, b, p.lds, h->stream, a);
+    else {
+        switch (p.R) {
+        case 1: hipLaunchKernelGGL((mcl::k_rays_skip<1, false>), g, b, p.lds, h->stream, a); break;
+        case 2: hipLaunchKernelGGL((mcl::k_rays_skip<2, false>), g, b, p.lds, h->stream, a); break;
+        case 3: hipLaunchKernelGGL((mcl::k_rays_skip<3, false>), g, b, p.lds, h->stream, a); break;
+        default: hipLaunchKernelGGL((mcl::k_rays_skip<4, false>), g, b, p.lds, h->stream, a); break;
         }
     }
-    if (!windows && !h->capturing && !direct_table) HIPCHK(h, hipEventRecord(h->ev[EV_K1], h->stream));
-    h->last_mode = mode;
+    if (p.timed) HIPCHK(h, hipEventRecord(h->ev[EV_K1], h->stream));
+    return MCL_OK;
+}
+
+// Phase 9 (work lists): the accumulators -> d_logw in particle order, and the overflow flag of the fix-up lists
+void ray_combine(mcl_engine *h, const RayPlan &p, int64_t n)
+{
+    if (p.sweep) {
+        // the slot accumulators (k_rays_sweep's per-wedge sums + what the far / fix / exact kernels added) -> d_logw in particle
+        // order, the per-workgroup maxima, and the overflow flag of the fix-up lists (k_fix_overflow's job for the other kernels)
+        hipExtLaunchKernelGGL(mcl::k_combine_logw, dim3(mcl::kRedBlocks), dim3(256), 0, h->stream, nullptr, h->ev[EV_RAYS], 0, n, h->d_perm.p, h->d_logw_acc.p,
+                              h->d_logw.p, h->d_maxpart.p, h->d_fix_count.p, p.nseg, p.segcap, h->d_fix_over);
+        h->ev_rays_bound = true;               // (the stage's last kernel: EV_RAYS is its stop event)
+        h->max_partials_ready = true;
+    } else {
+        hipLaunchKernelGGL(mcl::k_fix_overflow, dim3(1), dim3(256), 0, h->stream, h->d_fix_count, p.nseg, p.segcap, h->d_fix_over);
+        hipLaunchKernelGGL(mcl::k_gather_logw, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d_logw_acc, n, h->d_logw);
+    }
+}
+
+// Phase 10 (MCL_DEBUG_WG): four words per persistent workgroup, cleared before the ray kernel and written to the named file after the stage
+int ray_debug_begin(mcl_engine *h, const RayPlan &p, mcl::RayArgs &a, DevBuf<unsigned long long> &d_dbg)
+{
+    if (h->env_debug_wg.empty()) return MCL_OK;
+    MCL_TRY(d_dbg.reserve(h, (size_t)p.nseg * 4));
+    HIPCHK(h, hipMemset(d_dbg, 0, (size_t)p.nseg * 32));
+    a.dbg = d_dbg;
+    return MCL_OK;
+}
+
+int ray_debug_dump(mcl_engine *h, const RayPlan &p, DevBuf<unsigned long long> &d_dbg)
+{
+    if (!d_dbg) return MCL_OK;
+    std::vector<unsigned long long> hd((size_t)p.nseg * 4);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(hd.data(), d_dbg, hd.size() * 8, hipMemcpyDeviceToHost));
+    if (FILE *f = fopen(h->env_debug_wg.c_str(), "wb")) { fwrite(hd.data(), 8, hd.size(), f); fclose(f); }
+    return MCL_OK;
+}
+
+// The ray stage of n particles: log-weights into d_logw.  force_skip: the redo after a fix-up list overflow (fix_lists_overflowed).
+int launch_rays(mcl_engine *h, const double *x, const double *y, const double *th, int64_t n, bool force_skip = false, bool direct_table = false)
+{
+    mcl::RayArgs a = ray_args(h, x, y, th, n, direct_table);
+    MCL_TRY(ray_step_buffer(h, a));
+    h->last_work_lists = false;
+    h->last_lf = false;
+    h->max_partials_ready = false;
+    const RayPlan p = plan_rays(h, n, force_skip, direct_table);
+    if (p.mode == 0) return fail(h, MCL_ERR_UNSUPPORTED, "MCL_RAYS_QUAD / MCL_RAYS_CELL / MCL_RAYS_SWEEP not usable with this map / beam set");
+    DevBuf<unsigned long long> d_dbg;
+    if (p.lists) MCL_TRY(ray_fix_lists(h, p, a));
+    ray_prep(h, p, a);
+    if (p.ordered) { MCL_TRY(ray_order(h, p, a)); MCL_TRY(ray_units(h, p, a)); }
+    // the tables of this update's scan were built on the second stream beside the resampling and the ordering: from here on they are read
+    if (p.lists && h->obs_wait_pending) { h->obs_wait_pending = false; HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_obs, 0)); }
+    if (p.sweep) MCL_TRY(ray_sweep_items(h, p, a));
+    // What a decision leaves behind is written once per launch: the hybrid's back-off by plan_rays, before anything is launched;
+    // far_fresh and last_sweep_* here, behind every reservation that can still fail and before the debug buffer's (as they always were).
+    if (p.sweep) h->far_fresh = false;
+    if (p.lists) { h->last_sweep_global = p.glob ? 1 : (p.hyb ? 2 : 0); h->last_sweep_rec = p.rec ? 1 : 0; h->last_sweep_pairs = (p.rec && (p.glob || p.pairs)) ? 1 : 0; }
+    if (p.lists) MCL_TRY(ray_debug_begin(h, p, a, d_dbg));
+    MCL_TRY(ray_kernel(h, p, a));
+    if (p.lists) {
+        ray_combine(h, p, n);
+        MCL_TRY(ray_debug_dump(h, p, d_dbg));
+        h->last_work_lists = true;
+    }
+    h->last_mode = p.mode;
     h->prep_folded = false;
     h->layout_stale_used = false; h->keys_done = false;
     if (!h->capturing) h->pc_ready = false;
@@ -550,7 +679,7 @@ int upload_observation(mcl_engine *h)
     dim3 g((h->bpad + 255) / 256, h->P + 1);
     hipLaunchKernelGGL(mcl::k_obs_build_lt, g, dim3(256), 0, h->stream, h->d_obs, h->res, h->P, h->d_L, h->B, h->bpad, h->d_obs_idx, h->d_Lt,
                        h->d_Lt + (size_t)(h->P + 1) * h->bpad);
-    if (choose_ray_mode(h, h->N, false) == 5) build_ltd(h);
+    if (mode_sweep(choose_ray_mode(h, h->N, false))) build_ltd(h);
     HIPCHK(h, hipGetLastError());
     return MCL_OK;
 }
@@ -582,7 +711,7 @@ int weights_and_cdf(mcl_engine *h, bool result_to_host = false, const mcl::KldAr
     const int64_t n = h->N;
     if (h->cfg.weight_mode == MCL_WEIGHT_LOG && h->cfg.resample_neff_permille == 0 && n <= mcl::kTinyTailMax) {
         // d_pc holds (cos, sin) of the current headings whenever a ray kernel other than the literal march ran on them
-        const double4 *pc = h->last_mode >= 2 && !h->last_lf ? h->d_pc : nullptr;
+        const double4 *pc = mode_fills_pc(h->last_mode) && !h->last_lf ? h->d_pc : nullptr;
         if (kld && result_to_host)
             hipLaunchKernelGGL(mcl::k_tiny_tail<true>, dim3(1), dim3(1024), (size_t)n * sizeof(uint64_t), h->stream, h->d_logw, h->d_x[h->cur],
                                h->d_y[h->cur], h->d_th[h->cur], pc, n, h->d_w, h->d_q, h->d_cdf, h->d_scalars, h->h_result, ++h->result_seq, *kld);
@@ -698,7 +827,7 @@ int launch_lfield(mcl_engine *h, const float *obs, int stride, int64_t n)
     if (rc != MCL_OK) return rc;
     HIPCHK(h, hipEventRecord(h->ev[EV_K1], h->stream));
     h->max_partials_ready = false;
-    h->last_quad = false;
+    h->last_work_lists = false;
     h->last_lf = true;
     return MCL_OK;
 }
@@ -1488,25 +1617,24 @@ static void resample_common_args(const mcl_engine *h, mcl::ResampleArgs &a, cons
 static void resample_ray_extras(mcl_engine *h, int64_t n, mcl::ResampleArgs &a, bool fresh_children = false)
 {
     const int rmode = choose_ray_mode(h, n, false);
-    if (!(rmode == 2 || rmode >= 4)) return;
+    if (!(rmode == MCL_RAYS_SKIP || mode_orders(rmode))) return;
     a.pc_out = h->d_pc; a.ox = h->ox; a.oy = h->oy; a.res = h->res;
-    if (rmode >= 4) { a.clr_logw_acc = h->d_logw_acc; a.clr_far_flags = reinterpret_cast<uint32_t *>(h->d_far.p); }
+    if (mode_orders(rmode)) { a.clr_logw_acc = h->d_logw_acc; a.clr_far_flags = reinterpret_cast<uint32_t *>(h->d_far.p); }
     h->pc_ready = true;
     // The ordering of the ray stage works from the layout (bounding box, occupied tiles) of the PREVIOUS update's children
     // when there is one: the set moves by a cell or so per update and the order only decides which rays share a wave.
     // Radix ordering: this kernel then writes the (key, index) pairs too and the sort starts right after it.
     const auto [ntx_abs, nty_abs, tiles_ok] = sort_tiles(h);
     // (not for children injected anywhere on the map: fresh_children, an update of recovery injection -- DESIGN.md §4.9)
-    if (rmode >= 4 && h->layout_valid && h->layout_n == n && !h->env_no_stale_layout && !fresh_children) {
+    if (mode_orders(rmode) && h->layout_valid && h->layout_n == n && !h->env_no_stale_layout && !fresh_children) {
         h->layout_stale_used = true;
-        const bool radix = h->env_sort_radix >= 0 ? h->env_sort_radix != 0 : n >= 3000000;
-        if (radix && h->d_skey2) {
+        if (sort_radix(h, n) && h->d_skey2) {
             a.key_out = h->d_skey; a.val_out = h->d_srank; a.key_bbox = h->d_bbox; a.key_tilemap = tiles_ok ? h->d_tilemap : nullptr;
             a.key_ntx = ntx_abs; a.key_Wp = h->Wp; a.key_Hp = h->Hp;
             h->keys_done = true;
         }
     }
-    if (rmode >= 4 && h->prep_cache_valid && h->prep_cache_n == n && !h->env_no_prep_fold) {
+    if (mode_orders(rmode) && h->prep_cache_valid && h->prep_cache_n == n && !h->env_no_prep_fold) {
         a.prep = h->prep_cache; a.prep_on = 1;      // launch_rays checks that this is what it would have cleared
         if (h->layout_stale_used) a.prep.bbox = nullptr;     // the layout in d_bbox is in use: not reset
         h->prep_passed = a.prep;
@@ -1520,7 +1648,7 @@ static void resample_ray_extras(mcl_engine *h, int64_t n, mcl::ResampleArgs &a, 
 static int layout_mark(mcl_engine *h, int64_t n)
 {
     h->layout_wanted = false;
-    if (choose_ray_mode(h, n, false) < 4 || h->env_no_stale_layout) return MCL_OK;
+    if (!mode_orders(choose_ray_mode(h, n, false)) || h->env_no_stale_layout) return MCL_OK;
     HIPCHK(h, hipEventRecord(h->ev_children, h->stream));
     h->layout_wanted = true;
     // (launched right here the layout kernels share the device with the sort: measured 0.04-0.06 ms per update slower at 1M and
@@ -1532,17 +1660,12 @@ static int next_layout_launch(mcl_engine *h, int64_t n)
 {
     if (!h->layout_wanted) return MCL_OK;
     h->layout_wanted = false;
-    const auto [ntx_abs, nty_abs, tiles_ok] = sort_tiles(h);
-    const int bstride = n >= (1 << 20) ? 16 : 1;
     // (the layout of the NEXT update, made beside this one's ray stage: whether that update takes the hybrid form is not known
     //  yet -- its units are cut for the hybrid's windows, which costs the global-field form nothing but shorter runs)
-    const int play = h->env_no_bucket_cuts ? -1 : (choose_ray_mode(h, n, false) == 5 ? sweep_play(h, sweep_hybrid(h)) : 0);
+    const int play = unit_play(h, choose_ray_mode(h, n, false), sweep_hybrid(h));
     HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_children, 0));
     hipLaunchKernelGGL(mcl::k_bbox_init, dim3(1), dim3(64), 0, h->stream2, h->d_bbox_nx, play);
-    hipLaunchKernelGGL(mcl::k_cell_bbox, dim3((unsigned)std::min<int64_t>((n / bstride + 255) / 256, 128)), dim3(256), 0, h->stream2, h->d_pc, n,
-                       bstride, h->Wp, h->Hp, h->d_bbox_nx, tiles_ok ? h->d_tilemark_nx : (int *)nullptr, ntx_abs);
-    if (tiles_ok)
-        hipLaunchKernelGGL(mcl::k_tile_compact, dim3(1), dim3(1024), 0, h->stream2, h->d_bbox_nx, h->d_tilemark_nx, h->d_tilemap_nx, ntx_abs * nty_abs);
+    launch_layout(h, h->stream2, n, h->d_bbox_nx, h->d_tilemark_nx, h->d_tilemap_nx);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->ev_layout, h->stream2));
     h->layout_pending = true;
@@ -1653,7 +1776,7 @@ static int plan_update(mcl_engine *h, Update &u)
     // outright has no work lists, no allocation and no fallback.  (Neither a likelihood-field update -- DESIGN.md §4.10 -- nor one that
     // changes the size of the set, which do_update treats as a set from outside, takes them.)
     const bool small = u.resample_and_move && !h->lf_on && h->cfg.graph_mode != 1 && h->graph_warm && u.n == u.n_par && !u.keep &&
-                       h->cfg.weight_mode == MCL_WEIGHT_LOG && h->cfg.resample_neff_permille == 0 && choose_ray_mode(h, u.n, false) == 2;
+                       h->cfg.weight_mode == MCL_WEIGHT_LOG && h->cfg.resample_neff_permille == 0 && choose_ray_mode(h, u.n, false) == MCL_RAYS_SKIP;
     // tiny: three launches and no copy: resampling + motion + per-particle constants + table rows of the scan | rays against the static
     // table | weights, sums, CDF and the result block written straight to pinned host memory, all in one workgroup
     u.tiny = small && u.n <= mcl::kTinyTailMax;
@@ -1741,7 +1864,7 @@ static int launch_update_resample(mcl_engine *h, Update &u, const double *d_norm
     // kernels produce: with a windowed ray kernel they are built on a second stream beside those, and the ray stage waits for
     // them (a copy and two or three small launches off the critical path of an update: ~15 us).  Enqueued AFTER the resampling
     // kernel: that one is on the critical path, and a small update is bound by the order the host submits in.
-    if (!u.tiny && !h->lf_on && !h->env_no_obs_overlap && choose_ray_mode(h, n, false) >= 3) {
+    if (!u.tiny && !h->lf_on && !h->env_no_obs_overlap && mode_work_lists(choose_ray_mode(h, n, false))) {
         std::swap(h->stream, h->stream2);
         const int rc_obs = prepare_observation(h, u.obs, u.obs_stride);
         hipError_t ee = rc_obs ? hipSuccess : hipEventRecord(h->ev_obs, h->stream);
@@ -1805,7 +1928,7 @@ static bool graph_ready(mcl_engine *h, const Update &u)
     h->capturing = false;
     const hipError_t ee = hipStreamEndCapture(h->stream, &graph);
     hipError_t ie = hipErrorUnknown;
-    if (!rc && ce == hipSuccess && ee == hipSuccess && graph && h->last_mode == 2)
+    if (!rc && ce == hipSuccess && ee == hipSuccess && graph && h->last_mode == MCL_RAYS_SKIP)
         ie = hipGraphInstantiate(&h->graph_exec[gi], graph, nullptr, nullptr, 0);
     if (graph) (void)hipGraphDestroy(graph);
     if (ie == hipSuccess) return true;
@@ -1880,7 +2003,7 @@ static int tail_launches(mcl_engine *h, const Update &u)
     if (!h->ev_sensor_bound) HIPCHK(h, hipEventRecord(h->ev[EV_SENSOR], h->stream));
     rc = fetch_scalars(h);                 // one D2H copy (scalars, counters, overflow flag); synchronises the stream
     if (rc) return rc;
-    if (h->last_quad && h->h_fix_count != 0) {
+    if (fix_lists_overflowed(h)) {
         // more undecided rays than the work list holds (only with debug_force_exact at large sizes or a
         // pathological map): redo the ray stage with the self-contained k_rays_skip
         HIPCHK(h, hipMemsetAsync(h->d_counters, 0, 4 * sizeof(unsigned long long), h->stream));
@@ -2740,7 +2863,7 @@ int mcl_host::stage_rays_finish(mcl_engine_t *h, const float *obs, int32_t n_bea
         std::memcpy(h->h_scalars, h->h_result, 8 * sizeof(double));       // [0] = local max log-weight (mcl_get_host_scalars)
         std::memcpy(h->h_counters, h->h_result + 8, 4 * sizeof(unsigned long long));
         h->h_fix_count = h->h_result[12];
-        if (!(h->last_quad && h->h_fix_count != 0) || attempt == 1) break;
+        if (!fix_lists_overflowed(h) || attempt == 1) break;
         // work-list overflow (only with debug_force_exact at large sizes): once more with the self-contained k_rays_skip
         int rc = stage_rays_launch(h, obs, n_beams, true);
         if (rc) return rc;
@@ -2934,7 +3057,7 @@ int mcl_stage_complete(mcl_engine_t *h, const double global_sums[5], int32_t *re
     // more undecided rays than the fix-up lists hold (debug_force_exact at large sizes, a pathological map): the log-weights of
     // this update are incomplete.  The caller runs the ray stage again through mcl_stage_rays (which falls back to the
     // self-contained kernel) and the two exchanges after it; the children are untouched
-    *redo = (h->last_quad && h->h_fix_count != 0) ? 1 : 0;
+    *redo = fix_lists_overflowed(h) ? 1 : 0;
     for (int i = 0; i < 5; ++i) h->global_sums[i] = global_sums[i];
     // (the carry of adaptive resampling is committed by mcl_stage_finish, which the host calls once the update stands)
     return MCL_OK;

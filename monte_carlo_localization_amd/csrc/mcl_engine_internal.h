@@ -232,8 +232,8 @@ struct mcl_engine {
     bool env_comm_no_pregather = false; // MCL_COMM_NO_PREGATHER: mcl_comm_update gathers the lists when it starts, not when the previous one ends
     mcl::PrepClear prep_passed{};       // what the resampling kernel was given to clear (prep_folded)
     DevBuf<double2> d_slice_mean;       // one per slice of the sorted order
-    bool last_quad = false;             // the last ray stage ran k_rays_quad (overflow check pending)
-    int last_mode = 0;                  // 1 march, 2 skip, 3 quad, 4 cell, 5 sweep
+    bool last_work_lists = false;       // the last ray stage ran a kernel with fix-up lists (quad, cell, sweep): fix_lists_overflowed
+    int last_mode = 0;                  // the MCL_RAYS_* enumerator of the kernel the last ray stage ran (0: none yet)
     unsigned long long result_seq = 0;  // stamps the result block a small update writes to pinned memory (h_result[kResultStamp])
     int env_tiny_poll = 1;
     bool far_fresh = true;              // no ray stage has seen the current particle set yet (set / initialised since the last one)
@@ -322,6 +322,10 @@ struct mcl_engine {
     } while (0)
 
 #define MCL_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
+
+// Did the fix-up lists of the last ray stage overflow?  (h_fix_count: the flag as fetched with the result block.)  Its log-weights
+// are incomplete then, and the caller runs the stage again with the self-contained k_rays_skip (force_skip).
+inline bool fix_lists_overflowed(const mcl_engine *h) { return h->last_work_lists && h->h_fix_count != 0; }
 
 // Where the parents of a staged resample come from.
 struct ParentSource {

@@ -364,7 +364,7 @@ int mcl_group_update(mcl_group_t *g, const double action[3], const float *obs, i
             int rc = stage_weights_finish(e);                         // THE host wait of this device's update
             if (rc) return gfail(g, rc, e->err);
             stage_rays_note(e);
-            overflow = overflow || (e->last_quad && e->h_fix_count != 0);
+            overflow = overflow || fix_lists_overflowed(e);
             for (int k = 0; k < 5; ++k) gs[k] += e->global_sums[k];      // unpack_result left the LOCAL sums there
             sww += e->h_scalars[7];
             qt += e->q_total;
