@@ -638,6 +638,47 @@ int mcl_host_search_bound_table(const float *lf, int32_t K, float *ub /* K + 1 e
 int mcl_host_search_prune_next(const mcl_search_prune_config_t *pc, int64_t pairs, int64_t n_scored, int64_t first_below_c,
                                int64_t *n_next);
 
+/* ---- global search over a scan sequence with exact pruning -------------------------------------------------
+ * mcl_global_search_sequence scores every lattice pose against every scan and keeps and sorts the whole volume.
+ * mcl_global_search_sequence_pruned reports the same hits -- pose, log_likelihood bits and index, nms included -- from the (block,
+ * heading) pairs a bound on the SUMMED score cannot rule out, and keeps no volume.  The lattice, the headings, the offsets, the
+ * per-scan used beams, the summed score and the order of the hits are S1 - S5's and SQ1 - SQ5's; the blocks, the pooled field, the
+ * rounds and the result are P1 - P5's.  scans, rel and n_scans as in mcl_global_search_sequence; c and pc as in
+ * mcl_global_search_pruned.  With S = block, n = n_headings, N = n_scans:
+ *   PS1 blocks, pooled field, bound table, rounds, result.  P1, P2, P4 and P5 unchanged, w = (S - 1) * stride_cells + 2 included:
+ *     a displacement moves a block, it does not stretch it.  hits[0 .. min(max_hits, C)) are exactly the first entries
+ *     mcl_global_search_sequence reports for the same config, scans and rel; *n_hits is the number written.
+ *   PS2 offsets and beam lists.  SQ1 and SQ3 unchanged: the host forms and uploads the table of (ax_ks, ay_ks, theta_ks), the
+ *     device never re-derives it; every scan has its own list of used beams, the lists are concatenated with N + 1 offsets.
+ *   PS3 the bound of a pair.  Per scan s: the block's corner centres (x_lo, y_lo) and (x_hi, y_hi) of P3 each get + ax_ks / + ay_ks
+ *     by one rounded fp64 add (SQ2's add) and then go through LF4's cell coordinate; with sincos(theta_ks), every used beam of scan s
+ *     is evaluated at both corners exactly as in P3 -- the two nested fmas, the floors, the hi - lo < w guard, Ub[Dp[ly][lx]], Ub[K]
+ *     off the pooled field, Ub[0] and a guard fallback counted otherwise.  U_s is the in-order fp64 sum of the scan's terms from
+ *     +0.0, and U = ((+0.0 + U_0) + U_1) + ... in scan order.  Why it holds: a rounded add is monotone, so x_lo + ax_ks <= x_p +
+ *     ax_ks <= x_hi + ax_ks for every position p of the block (y likewise) -- the scan pose of SQ2 lies between the shifted corners
+ *     -- and LF4's cell coordinate and the end point's cell are monotone in it, so by P3 every term is >= the pose's term for
+ *     that beam.  Rounded addition is monotone in each operand, so U_s >= acc_s of SQ4 and, fold by fold, U >= the summed score of
+ *     every pose of the block, compared as doubles, -inf included (a U_s of -inf makes U -inf, and then some acc_s is -inf too).
+ *     mcl_get_search_bounds returns U of the last pruned call of either kind.
+ *   PS4 score of a scored pair.  Bit for bit SQ4: the scans outside, the beams inside, one accumulator per scan, folded in scan
+ *     order; so a scored pose has the bits of mcl_global_search_sequence's volume.
+ *   PS5 identity, where it works, buffers.  With N = 1 and rel = (0, 0, 0) the hits, U and stats[0 .. 8) are bit for bit those of
+ *     mcl_global_search_pruned with the same scan (SQ7's argument, for the corners as for the positions).  The conditions and the
+ *     refusals are P6's and SQ's together: the likelihood-field model ON; single engine only (MCL_ERR_UNSUPPORTED with a
+ *     communicator or in a group); MCL_ERR_INVALID_ARG for n_scans outside [1, MCL_SEARCH_MAX_SCANS], a null scans or rel, a rel
+ *     entry that is not finite, n_beams != B, max_hits = 0, block outside {2, 4, 8}, first_pairs < 0, reserved != 0, pairs * S * S >=
+ *     2^31, and everything S8 refuses, MCL_ERR_NOT_READY where S8 says so.  Read-only: it uses the pooled field, the block tables,
+ *     U, the sort buffers and the store of mcl_global_search_pruned and the beam lists, their N + 1 offsets and the offset table of
+ *     mcl_global_search_sequence, and nothing else; an engine that never makes this call reports the same mcl_get_search_bytes as
+ *     before after every other call.  The score volume of an earlier mcl_global_search / _sequence stays as it was.  One host wait
+ *     per round.  Every later update and search is bit-identical to one of an engine that never called it.
+ *   stats = the eight of mcl_global_search_pruned (used beams: of all scans, as SQ6), then [8] = N; stats may be NULL.
+ *   Not here: a streamed, beam-model or sharded variant, refinement over a sequence. */
+int mcl_global_search_sequence_pruned(mcl_engine_t *h, const mcl_search_config_t *c /* NULL = the defaults */,
+                                      const mcl_search_prune_config_t *pc /* NULL = the defaults */, const float *scans,
+                                      const double *rel, int32_t n_scans, int32_t n_beams, int32_t max_hits, mcl_search_hit_t *hits,
+                                      int64_t *n_hits, uint64_t stats[9]);
+
 /* ---- pose refinement: a dense local window around each seed pose, scored against one scan (correlative scan matching on the
  *      likelihood field) ---------------------------------------------------------------------------------
  * A hit of mcl_global_search sits on the search's lattice, a cluster mean or an /initialpose is only roughly right.  For each of

@@ -33,6 +33,9 @@
 //              two radix sorts       the store's entries by index, then stably by key: the candidates, best first
 //              k_search_decide       c, stop or not, the first rank below c
 //              (copy)                the round's state and the first max_hits entries; the round's one host wait
+// mcl_global_search_sequence_pruned (§4.21) is the same call with S scans: the staging of mcl_global_search_sequence,
+// k_search_bound_seq and k_search_score_block_seq in the places of k_search_bound and k_search_score_block (PruneKernels), and
+// everything else unchanged.
 #include "mcl_search.h"
 #include "mcl_search_beam.h"
 #include "mcl_search_pruned.h"
@@ -775,12 +778,47 @@ struct PruneBytes {
     ~PruneBytes() { s->device_bytes += pb.bytes - before; }
 };
 
-int search_pruned(mcl_engine *h, const mcl_search_config_t *cfg, const mcl_search_prune_config_t *pcfg, const float *obs, int32_t n_beams,
-                  int32_t max_hits, mcl_search_hit_t *hits, int64_t *n_hits, uint64_t *stats)
+// What differs between the pruned searches: how the scans reach the device (stage_scans' `single`) and the two kernels that read
+// them.  Everything else -- the checks, the buffers, the order of the bounds, the rounds, the result -- is search_pruned.
+struct PruneKernels {
+    bool single;                                 // mcl_global_search_pruned: one scan, its kernels read q.a alone
+    void (*bound)(mcl_engine *h, const mcl_prune::SeqArgs &q, dim3 grid, size_t lds);
+    void (*score)(mcl_engine *h, const mcl_prune::SeqArgs &q, dim3 grid, size_t lds);
+};
+
+template <class Kernel, class KernelArgs>
+void prune_launch(mcl_engine *h, Kernel with_lds, Kernel without, dim3 grid, size_t lds, const KernelArgs &a)
+{
+    if (lds) hipLaunchKernelGGL(with_lds, grid, dim3(kThreads), lds, h->stream, a);
+    else hipLaunchKernelGGL(without, grid, dim3(kThreads), 0, h->stream, a);
+}
+
+const PruneKernels kPruneSingle = {
+    true,
+    [](mcl_engine *h, const mcl_prune::SeqArgs &q, dim3 grid, size_t lds) {
+        prune_launch(h, mcl_prune::k_search_bound<true>, mcl_prune::k_search_bound<false>, grid, lds, q.a);
+    },
+    [](mcl_engine *h, const mcl_prune::SeqArgs &q, dim3 grid, size_t lds) {
+        prune_launch(h, mcl_prune::k_search_score_block<true>, mcl_prune::k_search_score_block<false>, grid, lds, q.a);
+    }};
+const PruneKernels kPruneSequence = {
+    false,
+    [](mcl_engine *h, const mcl_prune::SeqArgs &q, dim3 grid, size_t lds) {
+        prune_launch(h, mcl_prune::k_search_bound_seq<true>, mcl_prune::k_search_bound_seq<false>, grid, lds, q);
+    },
+    [](mcl_engine *h, const mcl_prune::SeqArgs &q, dim3 grid, size_t lds) {
+        prune_launch(h, mcl_prune::k_search_score_block_seq<true>, mcl_prune::k_search_score_block_seq<false>, grid, lds, q);
+    }};
+
+// mcl_global_search_pruned (kPruneSingle: one scan, rel unused) and mcl_global_search_sequence_pruned (kPruneSequence) behind
+// their own argument checks
+int search_pruned(mcl_engine *h, const PruneKernels &kern, const mcl_search_config_t *cfg, const mcl_search_prune_config_t *pcfg,
+                  const float *scans, const double *rel, int n_scans, int32_t n_beams, int32_t max_hits, mcl_search_hit_t *hits,
+                  int64_t *n_hits, uint64_t *stats)
 {
     // P6: everything that can refuse the call, before anything is allocated for it
     mcl_search_config_t c;
-    SIDE_TRY(search_check(h, cfg, obs, n_beams, max_hits, hits, n_hits, c));
+    SIDE_TRY(search_check(h, cfg, scans, n_beams, max_hits, hits, n_hits, c));
     if (max_hits == 0) return fail(h, MCL_ERR_INVALID_ARG, "pruned search: max_hits must be >= 1 (with no hit to report the call has nothing to do)");
     mcl_search_prune_config_t pc;
     if (pcfg) pc = *pcfg; else mcl_default_search_prune_config(&pc);
@@ -794,7 +832,7 @@ int search_pruned(mcl_engine *h, const mcl_search_config_t *cfg, const mcl_searc
     if (n_poses >= MCL_MAX_TOTAL_PARTICLES)
         return fail(h, MCL_ERR_INVALID_ARG, "global search: n_positions * n_headings must stay below 2^27 (a larger stride_cells or fewer headings)");
     SIDE_TRY(search_headings_upload(h, s, c.n_headings));
-    SIDE_TRY(search_alloc_scan(h, s, (size_t)h->B));
+    SIDE_TRY(search_alloc_scan(h, s, (size_t)n_scans * (size_t)h->B));
     if (!s->prune) s->prune.reset(new PruneBufs());
     PruneBufs &pb = *s->prune;
     const PruneBytes count_bytes{s, pb, pb.bytes};
@@ -817,11 +855,13 @@ int search_pruned(mcl_engine *h, const mcl_search_config_t *cfg, const mcl_searc
     SIDE_TRY(pb.d_round.reserve(h, 1, &pb.bytes));
     SIDE_TRY(pb.h_round.reserve(h, 1));
 
-    // the scan; the bounds, their order, the slot map
-    const int nb = stage_used_beams(h, c.beam_stride, obs, s->h_obs, s->h_beams);
-    if (nb > 0) HIPCHK(h, hipMemcpyAsync(s->d_beams, s->h_beams, (size_t)nb * sizeof(double2), hipMemcpyHostToDevice, h->stream));
+    // the scans; the bounds, their order, the slot map
+    int nb = 0;
+    SIDE_TRY(stage_scans(h, s, c, scans, rel, n_scans, kern.single, nb));
     HIPCHK(h, hipMemsetAsync(pb.d_guard, 0, sizeof(unsigned long long), h->stream));
-    mcl_prune::Args a{};
+    mcl_prune::SeqArgs q{};
+    q.off = s->d_off; q.beam_begin = s->d_begin; q.n_scans = n_scans;
+    mcl_prune::Args &a = q.a;
     a.xy = s->d_xy; a.pmap = s->d_pmap; a.theta = s->d_theta;
     a.n_pos = (int32_t)s->n_pos; a.n_head = c.n_headings; a.nx = s->nx; a.ny = s->ny;
     a.S = S; a.n_blocks = pb.plan.n_blocks; a.nbx = pb.plan.nbx;
@@ -842,8 +882,7 @@ int search_pruned(mcl_engine *h, const mcl_search_config_t *cfg, const mcl_searc
     a.round = pb.d_round;
     const size_t lds = lf_lds_bytes(h);
     const dim3 grid_bound((unsigned)((uint64_t)a.groups_per_heading * (uint64_t)c.n_headings));
-    if (lds) hipLaunchKernelGGL(mcl_prune::k_search_bound<true>, grid_bound, dim3(kThreads), lds, h->stream, a);
-    else hipLaunchKernelGGL(mcl_prune::k_search_bound<false>, grid_bound, dim3(kThreads), 0, h->stream, a);
+    kern.bound(h, q, grid_bound, lds);
     HIPCHK(h, hipGetLastError());
     size_t tb = 0;
     HIPCHK(h, rocprim::radix_sort_pairs(nullptr, tb, pb.d_ukey[0].p, pb.d_ukey[1].p, pb.d_upair[0].p, pb.d_upair[1].p, (size_t)n_pairs, 0, 64, h->stream));
@@ -869,8 +908,7 @@ int search_pruned(mcl_engine *h, const mcl_search_config_t *cfg, const mcl_searc
         a.store = pb.store; a.ckey = pb.ckey[0]; a.cval = pb.cval[0];
         a.r0 = (uint32_t)n_scored; a.r1 = (uint32_t)next; a.n_scored = (uint32_t)next;
         const dim3 grid_score((unsigned)((next - n_scored + kThreads / 64 - 1) / (kThreads / 64)));
-        if (lds) hipLaunchKernelGGL(mcl_prune::k_search_score_block<true>, grid_score, dim3(kThreads), lds, h->stream, a);
-        else hipLaunchKernelGGL(mcl_prune::k_search_score_block<false>, grid_score, dim3(kThreads), 0, h->stream, a);
+        kern.score(h, q, grid_score, lds);
         HIPCHK(h, hipGetLastError());
         n_scored = next;
         ++rounds;
@@ -999,7 +1037,22 @@ int mcl_global_search_pruned(mcl_engine_t *h, const mcl_search_config_t *cfg, co
                              int32_t n_beams, int32_t max_hits, mcl_search_hit_t *hits, int64_t *n_hits, uint64_t stats[8])
 {
     if (!h) return MCL_ERR_INVALID_ARG;
-    return search_pruned(h, cfg, pcfg, obs, n_beams, max_hits, hits, n_hits, stats);
+    return search_pruned(h, kPruneSingle, cfg, pcfg, obs, nullptr, 1, n_beams, max_hits, hits, n_hits, stats);
+}
+
+int mcl_global_search_sequence_pruned(mcl_engine_t *h, const mcl_search_config_t *cfg, const mcl_search_prune_config_t *pcfg,
+                                      const float *scans, const double *rel, int32_t n_scans, int32_t n_beams, int32_t max_hits,
+                                      mcl_search_hit_t *hits, int64_t *n_hits, uint64_t stats[9])
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    // the sequence's own arguments, where the call works (PS5), then everything the pruned search checks
+    if (const char *why = mcl_host::search_sequence_invalid(rel, n_scans)) return fail(h, MCL_ERR_INVALID_ARG, why);
+    if (!scans) return fail(h, MCL_ERR_INVALID_ARG, "global search: scans is null");
+    if (h->comm || h->in_group)
+        return fail(h, MCL_ERR_UNSUPPORTED, "pruned sequence search: single-engine only: this engine has a communicator or belongs to a device group");
+    SIDE_TRY(search_pruned(h, kPruneSequence, cfg, pcfg, scans, rel, n_scans, n_beams, max_hits, hits, n_hits, stats));
+    if (stats) stats[8] = (uint64_t)n_scans;
+    return MCL_OK;
 }
 
 int mcl_get_search_bounds(mcl_engine_t *h, double *out, size_t n)

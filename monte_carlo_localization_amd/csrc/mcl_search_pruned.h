@@ -2,7 +2,9 @@
 // mcl_global_search cut into S x S blocks of positions, an upper bound U of every (block, heading) pair's scores that holds as
 // bits (P1 - P3), and the scores of the pairs whose bound says they might matter.  The arguments of its kernels and the kernels
 // themselves; only mcl_search.hip includes it, after mcl_search.h.  A score comes from lf_beam_value in k_search_score's order, so
-// it is mcl_global_search's bit for bit.
+// it is mcl_global_search's bit for bit.  The same over a scan sequence (mcl_global_search_sequence_pruned, §4.21, PS1 - PS5): the
+// bound and the block scores summed over the scans in k_search_score_seq's order; the ranking, the marking and the decision are
+// shared.
 #pragma once
 #include "mcl_search.h"
 
@@ -206,6 +208,120 @@ __global__ __launch_bounds__(kThreads) void k_search_score_block(Args a)
             acc += (double)mcl::lf_beam_value(a.beams[j], s, c, px, py, W, H, a.W, a.D, lf, off);
     }
     a.store[(size_t)r * SS + lane] = acc;
+}
+
+// ---- the pruned search over a scan sequence (mcl_global_search_sequence_pruned): Args as above -- beams holds the
+// S used-beam lists one after the other, nb their total -- and what joins the scans (mcl_srch::SeqArgs' three)
+struct SeqArgs {
+    Args a;
+    const double *off;              // n_head x n_scans triples (ax_ks, ay_ks, theta_ks), formed on the host (SQ1)
+    const int32_t *beam_begin;      // n_scans + 1: scan s owns beams[beam_begin[s] .. beam_begin[s + 1])
+    int n_scans;
+};
+
+// PS3.  k_search_bound's decomposition: one lane per pair, a workgroup = 256 consecutive live blocks at ONE heading.  For one
+// (heading, scan) the triple of SQ1, the sine and cosine of theta_ks, the bounds of the beam list and every beam's pair are uniform
+// over the workgroup (scalar loads, addressed from blockIdx and the loop counters alone).  Both corners of the block get the
+// displacement by SQ2's one rounded add each, which is monotone, so every pose of the block has its scan pose between the shifted
+// corners; from there a beam's term is k_search_bound's, and for one beam neighbouring lanes still read neighbouring windows of
+// Dp: the displacement is the same for all of them.  The scans outside, the beams inside; one accumulator per scan -- the in-order
+// fp64 sum of the terms from +0.0 -- folded into the total in scan order, as SQ4 folds the scores.  Ub is staged once per
+// workgroup, not once per scan.
+template <bool LDS_TABLE>
+__global__ __launch_bounds__(kThreads) void k_search_bound_seq(SeqArgs q)
+{
+    extern __shared__ float s_ub[];
+    const Args &a = q.a;
+    const float *ub = a.ub;
+    if constexpr (LDS_TABLE) {
+        for (int k = threadIdx.x; k <= a.K; k += kThreads) s_ub[k] = a.ub[k];
+        __syncthreads();
+        ub = s_ub;
+    }
+    const uint32_t k = blockIdx.x / a.groups_per_heading;
+    const uint32_t b = (blockIdx.x - k * a.groups_per_heading) * (uint32_t)kThreads + threadIdx.x;
+    if (b >= (uint32_t)a.n_blocks) return;
+    const double4 cn = a.corner[b];
+    const double w = (double)a.w, xmin = (double)(1 - a.w), W = (double)a.W, H = (double)a.H;
+    const int Wp = a.W + a.w - 1;
+    const float top = ub[0], off = ub[a.K];
+    const double *o = q.off + (size_t)k * (size_t)q.n_scans * 3;
+    double total = 0.0;
+    unsigned fell = 0;
+    for (int sc = 0; sc < q.n_scans; ++sc, o += 3) {
+        double s, c;
+        sincos(o[2], &s, &c);
+        const double px0 = mcl::lf_cell_coord(cn.x + o[0], a.ox, a.inv_res), py0 = mcl::lf_cell_coord(cn.y + o[1], a.oy, a.inv_res);
+        const double px1 = mcl::lf_cell_coord(cn.z + o[0], a.ox, a.inv_res), py1 = mcl::lf_cell_coord(cn.w + o[1], a.oy, a.inv_res);
+        const int j1 = q.beam_begin[sc + 1];
+        double acc = 0.0;
+#pragma unroll 2
+        for (int j = q.beam_begin[sc]; j < j1; ++j) {
+            const double2 bm = a.beams[j];
+            const double lx = floor(fma(c, bm.x, fma(-s, bm.y, px0))), ly = floor(fma(s, bm.x, fma(c, bm.y, py0)));
+            const double hx = floor(fma(c, bm.x, fma(-s, bm.y, px1))), hy = floor(fma(s, bm.x, fma(c, bm.y, py1)));
+            float v = top;
+            if (hx - lx < w && hy - ly < w) {                               // (false for NaN)
+                v = off;                                                    // a window wholly off the map in either axis: K
+                if (lx >= xmin && lx < W && ly >= xmin && ly < H)
+                    v = ub[a.Dp[(size_t)((int)ly + a.w - 1) * (size_t)Wp + (size_t)((int)lx + a.w - 1)]];
+            } else {
+                ++fell;
+            }
+            acc += (double)v;
+        }
+        total += acc;
+    }
+    const uint32_t pair = k * (uint32_t)a.n_blocks + b;
+    a.U[pair] = total;
+    a.ukey[pair] = score_key(total);
+    a.upair[pair] = pair;
+    if (fell) atomicAdd(a.guard, (unsigned long long)fell);
+}
+
+// PS4.  k_search_score_block's decomposition: one WAVE per pair of the ranks [r0, r1), one lane per lattice position of its block;
+// the pair is the wave's, so the triples of SQ1, their sines and cosines, the beam lists' bounds and every beam's pair arrive by
+// scalar loads.  The loop is k_search_score_seq's, so a score is mcl_global_search_sequence's bit for bit.  Lanes without a
+// position write -inf and take no part in the loop.
+template <bool LDS_TABLE>
+__global__ __launch_bounds__(kThreads) void k_search_score_block_seq(SeqArgs q)
+{
+    extern __shared__ float s_lf[];
+    const Args &a = q.a;
+    const float *lf = a.lf;
+    if constexpr (LDS_TABLE) {
+        for (int k = threadIdx.x; k <= a.K; k += kThreads) s_lf[k] = a.lf[k];
+        __syncthreads();
+        lf = s_lf;
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t r = a.r0 + (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (uint32_t)(kThreads / 64) + (threadIdx.x >> 6)));
+    if (r >= a.r1) return;
+    const uint32_t SS = (uint32_t)(a.S * a.S);
+    if (lane >= SS) return;
+    const uint32_t pair = a.pair_sorted[r];
+    const uint32_t k = pair / (uint32_t)a.n_blocks, b = pair - k * (uint32_t)a.n_blocks;
+    const int32_t p = block_position(a, b, lane);
+    double total = -__builtin_inf();
+    if (p >= 0) {
+        const double2 xy = a.xy[p];
+        const double W = (double)a.W, H = (double)a.H;
+        const float off = lf[a.K];
+        const double *o = q.off + (size_t)k * (size_t)q.n_scans * 3;
+        total = 0.0;
+        for (int sc = 0; sc < q.n_scans; ++sc, o += 3) {
+            double s, c;
+            sincos(o[2], &s, &c);
+            const double px = mcl::lf_cell_coord(xy.x + o[0], a.ox, a.inv_res), py = mcl::lf_cell_coord(xy.y + o[1], a.oy, a.inv_res);
+            const int j1 = q.beam_begin[sc + 1];
+            double acc = 0.0;
+#pragma unroll 4
+            for (int j = q.beam_begin[sc]; j < j1; ++j)
+                acc += (double)mcl::lf_beam_value(a.beams[j], s, c, px, py, W, H, a.W, a.D, lf, off);
+            total += acc;
+        }
+    }
+    a.store[(size_t)r * SS + lane] = total;
 }
 
 // S5 over the scored pairs, through the slot map: one lane per store entry e = r * S * S + l of the ranks [0, n_scored).  The

@@ -53,7 +53,7 @@ EXPORTS = [
     "mcl_default_search_stream_config", "mcl_global_search_streamed", "mcl_host_search_slabs",
     "mcl_global_search_beam", "mcl_host_search_beam_grid", "mcl_get_search_beam_table",
     "mcl_default_search_prune_config", "mcl_global_search_pruned", "mcl_get_search_bounds", "mcl_host_search_blocks", "mcl_host_lf_pool",
-    "mcl_host_search_bound_table", "mcl_host_search_prune_next",
+    "mcl_host_search_bound_table", "mcl_host_search_prune_next", "mcl_global_search_sequence_pruned",
     "mcl_default_refine_config", "mcl_refine_poses", "mcl_refine_poses_beam", "mcl_get_refine_scores", "mcl_get_refine_bytes", "mcl_host_refine_window",
     "mcl_host_refine_reduce",
     "mcl_default_recovery_config", "mcl_set_recovery", "mcl_get_recovery_state", "mcl_set_recovery_state", "mcl_host_recovery_step",
@@ -278,6 +278,9 @@ def load_library(legacy=False):
         lib.mcl_global_search_pruned.argtypes = [C.c_void_p, C.POINTER(SearchConfig), C.POINTER(SearchPruneConfig), C.c_void_p, C.c_int32,
                                                  C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]
         lib.mcl_get_search_bounds.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.mcl_global_search_sequence_pruned.argtypes = [C.c_void_p, C.POINTER(SearchConfig), C.POINTER(SearchPruneConfig), C.c_void_p,
+                                                          C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int64),
+                                                          C.c_void_p]
         lib.mcl_host_search_blocks.argtypes = [C.POINTER(SearchConfig), C.POINTER(SearchPruneConfig), C.c_void_p, C.c_uint32, C.c_uint32,
                                                C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                                C.c_void_p, C.c_size_t]
@@ -1246,8 +1249,32 @@ class Engine:
                                     device_bytes=int(st[3]), pairs=int(st[4]), pairs_scored=int(st[5]), rounds=int(st[6]),
                                     guard_fallbacks=int(st[7]))
 
+    def global_search_sequence_pruned(self, scans, rel, max_hits=16, block=0, first_pairs=0, prune_reserved=(0, 0, 0, 0, 0, 0), **fields):
+        """global_search_sequence's hits from the blocks of poses an upper bound on the summed score cannot rule out
+        (mcl_global_search_sequence_pruned): the same structured array, bit for bit, without the score volume.
+        `scans`: (S, B) ranges; `rel`: (S, 3) rows of (dx, dy, dtheta); block and first_pairs as in global_search_pruned.  Returns
+        (hits, {global_search_pruned's keys, n_scans}); used_beams counts all scans' beams."""
+        o, r = np.asarray(scans, np.float32), np.asarray(rel, np.float64)
+        if o.ndim != 2:
+            raise ValueError("scans must be (S, B)")
+        if r.ndim != 2 or r.shape[1] != 3 or r.shape[0] != o.shape[0]:
+            raise ValueError("rel must be (S, 3), one row per scan")
+        o, r = _c(o, np.float32), _c(r, np.float64)
+        c, pc = default_search_config(**fields), search_prune_config(block, first_pairs, prune_reserved)
+        S = o.shape[0]
+        hits = np.zeros(int(max_hits), SEARCH_HIT_DTYPE)
+        n, st = C.c_int64(), np.zeros(9, np.uint64)
+        self._chk(self.lib.mcl_global_search_sequence_pruned(self._h, C.byref(c), C.byref(pc), _p(o) if S else None, _p(r) if S else None,
+                                                             C.c_int32(S), C.c_int32(o.shape[1]), C.c_int32(int(max_hits)),
+                                                             _p(hits) if hits.size else None, C.byref(n), _p(st)),
+                  "mcl_global_search_sequence_pruned")
+        self._search_pairs = int(st[4])
+        return hits[:n.value], dict(n_hits=n.value, n_positions=int(st[0]), n_poses=int(st[1]), used_beams=int(st[2]),
+                                    device_bytes=int(st[3]), pairs=int(st[4]), pairs_scored=int(st[5]), rounds=int(st[6]),
+                                    guard_fallbacks=int(st[7]), n_scans=int(st[8]))
+
     def search_bounds(self):
-        """The bounds U of the last global_search_pruned (mcl_get_search_bounds): one double per (block, heading) pair, pair =
+        """The bounds U of the last global_search_pruned or global_search_sequence_pruned (mcl_get_search_bounds): one double per (block, heading) pair, pair =
         k * n_blocks + b in host_search_blocks' order.  Raises before a pruned search and after set_map."""
         out = np.empty(getattr(self, "_search_pairs", 0) or 1, np.float64)
         self._chk(self.lib.mcl_get_search_bounds(self._h, _p(out), C.c_size_t(out.size)), "mcl_get_search_bounds")

@@ -1,6 +1,7 @@
 // search_pruned_check.cpp -- the host side of mcl_global_search_pruned (rules P1 / P2 / P4): the block plan, the
-// pooled field's window and the round schedule over their boundary and refusal cases, as a stand-alone host program for a sanitizer
-// build: no device is opened.  Build it together with the host arithmetic unit, e.g.
+// pooled field's window and the round schedule over their boundary and refusal cases, and the one table the search over a scan
+// sequence adds to them (mcl_global_search_sequence_pruned, §4.21: SQ1's offsets at every scan count), as a stand-alone host program
+// for a sanitizer build: no device is opened.  Build it together with the host arithmetic unit, e.g.
 //   hipcc -x hip --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
 //         tools/search_pruned_check.cpp monte_carlo_localization_amd/csrc/mcl_host_math.hip -o search_pruned_check
 // It prints "ok" and returns 0, or says which case failed.
@@ -174,6 +175,52 @@ int main()
         CHECK(mcl_host_search_prune_next(&pc, 10, 1, 0, nullptr) == MCL_ERR_INVALID_ARG);
         pc.first_pairs = -1;
         CHECK(mcl_host_search_prune_next(&pc, 10, 0, 0, &n) == MCL_ERR_INVALID_ARG);
+    }
+
+    // ---- §4.21 (PS2): what mcl_global_search_sequence_pruned uploads beside the single search's tables is SQ1's table, n x N
+    // triples, formed by the one host function both sequence searches call.  Its size at every N the call accepts, its last triple
+    // written and nothing behind it, the rows of a zero rel (PS5's identity rests on them), the refusals PS5 takes from SQ
+    {
+        mcl_default_search_config(&c);
+        c.n_headings = 8;
+        const double ang = 0.3, PI = 3.14159265358979323846;
+        for (int N = 1; N <= MCL_SEARCH_MAX_SCANS; ++N) {
+            std::vector<double> rel((size_t)N * 3);
+            for (int s = 0; s < N; ++s) { rel[3 * s] = -0.5 * s; rel[3 * s + 1] = 0.13 * s; rel[3 * s + 2] = s == N - 1 ? 0.0 : ang; }
+            const size_t n = (size_t)c.n_headings * (size_t)N * 3;
+            std::vector<double> off(n + 1, 77.0);
+            CHECK(mcl_host_search_sequence_offsets(&c, rel.data(), N, off.data(), n) == MCL_OK);
+            CHECK(off[n] == 77.0);
+            std::vector<double> theta((size_t)c.n_headings);
+            CHECK(mcl_host_search_headings(&c, theta.data(), theta.size()) == MCL_OK);
+            for (int k = 0; k < c.n_headings; ++k) {
+                const double *last = &off[((size_t)k * N + (size_t)(N - 1)) * 3];
+                CHECK(last[2] == theta[(size_t)k]);                                  // theta_k + 0.0 is theta_k
+                if (N == 1) CHECK(last[0] == 0.0 && last[1] == 0.0);                 // a zero rel: no displacement (of either sign)
+                if (N > 1) {
+                    const double *first = &off[((size_t)k * N + 1) * 3];             // scan 1: dx = -0.5, dy = 0.13
+                    const double dx = -0.5, dy = 0.13, ck = std::cos(theta[(size_t)k]), sk = std::sin(theta[(size_t)k]);
+                    CHECK(first[0] == ck * dx - sk * dy && first[1] == sk * dx + ck * dy);
+                    CHECK(std::fabs(std::hypot(first[0], first[1]) - std::hypot(dx, dy)) < 1e-12);
+                }
+                CHECK(theta[(size_t)k] >= -PI && theta[(size_t)k] < PI);
+            }
+            CHECK(mcl_host_search_sequence_offsets(&c, rel.data(), N, off.data(), n - 1) == MCL_ERR_INVALID_ARG);
+        }
+        double rel[3 * (MCL_SEARCH_MAX_SCANS + 1)] = {0.0}, out[8 * 3 * (MCL_SEARCH_MAX_SCANS + 1)];
+        CHECK(mcl_host_search_sequence_offsets(&c, rel, 0, out, 0) == MCL_ERR_INVALID_ARG);
+        CHECK(mcl_host_search_sequence_offsets(&c, rel, -1, out, 0) == MCL_ERR_INVALID_ARG);
+        CHECK(mcl_host_search_sequence_offsets(&c, rel, MCL_SEARCH_MAX_SCANS + 1, out, (size_t)8 * 3 * (MCL_SEARCH_MAX_SCANS + 1)) == MCL_ERR_INVALID_ARG);
+        CHECK(mcl_host_search_sequence_offsets(&c, nullptr, 1, out, 24) == MCL_ERR_INVALID_ARG);
+        CHECK(mcl_host_search_sequence_offsets(&c, rel, 1, nullptr, 24) == MCL_ERR_INVALID_ARG);
+        CHECK(mcl_host_search_sequence_offsets(nullptr, rel, 1, out, 24) == MCL_ERR_INVALID_ARG);
+        for (double bad : {(double)NAN, (double)INFINITY, -(double)INFINITY})
+            for (int i = 0; i < 6; ++i) {
+                rel[i] = bad;
+                CHECK(mcl_host_search_sequence_offsets(&c, rel, 2, out, 48) == MCL_ERR_INVALID_ARG);
+                rel[i] = 0.0;
+            }
+        CHECK(mcl_host_search_sequence_offsets(&c, rel, 2, out, 48) == MCL_OK);
     }
     std::printf(failures ? "%d case(s) failed\n" : "ok\n", failures);
     return failures ? 1 : 0;
