@@ -999,6 +999,26 @@ int mcl_host_wedge_tight_table(int32_t wedge, int32_t *values, uint8_t *reachabl
  * starts inside the ringed grid of its field and advances by at most max_range_px samples of at most one cell per axis, so
  * out[5] < out[4] < 2^32 is the whole memory-safety argument (tests/test_sweep_addressing.py enumerates it).  Host only. */
 int mcl_host_sweep_global_layout(uint32_t width, uint32_t height, int32_t max_range_px, int64_t out[6]);
+/* ---- the tables under the ray stage, read back from the device as stored (for tests: tests/test_gpu_ray_tables.py holds them to
+ *      the host functions above byte for byte).  Each call only copies: it launches nothing and changes no state.
+ *   Wedge fields: what mcl_set_map built (the tight rule, or the Euclidean one under MCL_WEDGE_METRIC=0).  MCL_WEDGES fields of Hp
+ *     rows x Wps bytes (Hp = height + 1, Wp = width + 1, Wps = Wp rounded up to a multiple of 8), n = MCL_WEDGES * Hp * Wps, in the
+ *     stored encoding: a stop cell is 255, a skip above 127 is 127, the padding columns [Wp, Wps) are 0.  dims (may be NULL)
+ *     receives {Hp, Wp, Wps}; out may be NULL (n is then ignored).  MCL_ERR_NOT_READY without a map or without wedge fields.
+ *   Ring fields: the mirrored, ringed copies the global-field and hybrid forms probe, the whole allocation: n = out[4] of
+ *     mcl_host_sweep_global_layout.  Field k (quadrant q = k / (MCL_WEDGES / 4)) starts at k * out[3]: (Hp + 4) rows of out[1] bytes
+ *     with the stored wedge field at offset (2, 2), mirrored in x for q = 1, 2 and in y for q = 2, 3; every other byte, the tail
+ *     rows up to out[3] included, is 255.  MCL_ERR_NOT_READY when the engine holds none (the LDS form).
+ *   Sweep table: the fp64 table of the last scan as MCL_RAYS_SWEEP's ray stage used it, rows x cols doubles, row-major.  Row r
+ *     stands for r - 127 samples left: entry (r, j + margin) = (double)L[obs_idx[j]][P - max(r - 127, 0)] for beam j and
+ *     r <= P + 127, L the float log table and obs_idx the scan's table rows; the last row (r = P + 128), the columns before
+ *     `margin` and those from margin + n_beams on are 0.  dims (may be NULL) receives {rows = P + 129, cols, margin}; out may be
+ *     NULL.  MCL_ERR_NOT_READY when no sweep ray stage has built the table for the current scan (mcl_set_map and
+ *     mcl_set_beam_angles drop it).
+ *   A wrong n is MCL_ERR_INVALID_ARG. */
+int mcl_get_wedge_fields(mcl_engine_t *h, uint8_t *out, size_t n, int32_t dims[3]);
+int mcl_get_ring_fields(mcl_engine_t *h, uint8_t *out, size_t n);
+int mcl_get_sweep_table(mcl_engine_t *h, double *out, size_t n, int32_t dims[3]);
 
 /* ---- multi-GPU staging (one engine per rank; collectives are the host's) -- */
 /* Device pointers of engine-owned buffers so the host can hand them to RCCL without copies. */

@@ -2504,6 +2504,46 @@ int mcl_get_likelihood_table(mcl_engine_t *h, float *out, size_t n, int32_t *K)
     return MCL_OK;
 }
 
+// ---- the tables under the ray stage, read back as stored (test infrastructure: copies only, no launch, no state changed)
+int mcl_get_wedge_fields(mcl_engine_t *h, uint8_t *out, size_t n, int32_t dims[3])
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    if (!h->have_map || !h->d_distw) return fail(h, MCL_ERR_NOT_READY, "no map is set or this map has no wedge fields");
+    if (dims) { dims[0] = h->Hp; dims[1] = h->Wp; dims[2] = h->Wps; }
+    if (!out) return MCL_OK;
+    if (n != (size_t)mcl::kWedges * h->Hp * h->Wps) return fail(h, MCL_ERR_INVALID_ARG, "the wedge fields have MCL_WEDGES x Hp x Wps bytes");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipMemcpyAsync(out, h->d_distw, n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MCL_OK;
+}
+
+int mcl_get_ring_fields(mcl_engine_t *h, uint8_t *out, size_t n)
+{
+    if (!h || !out) return MCL_ERR_INVALID_ARG;
+    if (!h->have_map || !h->d_distg) return fail(h, MCL_ERR_NOT_READY, "no map is set or the engine holds no ringed copies of the wedge fields");
+    if (n != h->distg_stride * (size_t)mcl::kWedges) return fail(h, MCL_ERR_INVALID_ARG, "the ringed fields have the bytes of mcl_host_sweep_global_layout's allocation");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipMemcpyAsync(out, h->d_distg, n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MCL_OK;
+}
+
+int mcl_get_sweep_table(mcl_engine_t *h, double *out, size_t n, int32_t dims[3])
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    if (!h->have_map || h->B <= 0 || !h->d_Ltd || !h->ltd_ready)
+        return fail(h, MCL_ERR_NOT_READY, "no sweep ray stage has built its table for the current scan");
+    const int rows = mcl::sweep_table_rows(h->P);
+    if (dims) { dims[0] = rows; dims[1] = h->ltd_cols; dims[2] = h->beam_margin; }
+    if (!out) return MCL_OK;
+    if (n != (size_t)rows * h->ltd_cols) return fail(h, MCL_ERR_INVALID_ARG, "the table has rows x cols entries");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipMemcpyAsync(out, h->d_Ltd, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MCL_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // multi-GPU staging
 // ---------------------------------------------------------------------------------------------

@@ -139,8 +139,10 @@ MCL_HD inline int wedge_skip_cell(const int32_t *nxt, const int32_t *prv, int Wp
 // smallest |x| (the strip's near line meets the steeper edge there), dist(origin, that set ∩ {x}) is convex in x, and the minimum
 // of a convex function over the sliding window [ox-1, ox+1] does not decrease once the window has reached the minimiser; for
 // |oy| <= 1 the strip holds the origin and the value is gap's.  The final max with today's (monotone) value keeps that order.
-// tests/test_wedge_tight.py enumerates every row for |o| <= 255 and all wedges, on the compiled arithmetic (built without
-// contraction, so the host twin and the kernel compute the same bits).
+// tests/test_wedge_tight.py enumerates every row for |o| <= 255 and all wedges, on the compiled arithmetic of the host twin.
+// That the kernel computes the same bytes (both are built without contraction; the kernel takes its stop cells from the uploaded
+// isotropic field, the twin from the grid) is what tests/test_gpu_ray_tables.py checks: the device's fields read back
+// (mcl_get_wedge_fields) against the twin's, byte for byte, under both rules.
 constexpr double kWedgeWiden = 1e-7;     // rad, each side
 constexpr double kWedgeSlack = 1e-6;     // px, before the floor
 

@@ -44,6 +44,7 @@ EXPORTS = [
     "mcl_stage_rays_async", "mcl_stage_weights_async", "mcl_stage_complete", "mcl_stage_keep",
     "mcl_comm_available", "mcl_comm_unique_id", "mcl_comm_create", "mcl_comm_destroy", "mcl_comm_update", "mcl_comm_stats", "mcl_comm_set_lists", "mcl_comm_get_vector", "mcl_comm_last_exchange", "mcl_comm_selftest",
     "mcl_host_sweep_global_layout", "mcl_get_ray_kernel_variant", "mcl_host_skip_field_wedge_tight", "mcl_host_wedge_tight_table",
+    "mcl_get_wedge_fields", "mcl_get_ring_fields", "mcl_get_sweep_table",
     "mcl_default_kld_config", "mcl_set_kld", "mcl_get_particle_count", "mcl_get_kld_state", "mcl_host_kld_bins", "mcl_host_kld_target",
     "mcl_default_cluster_config", "mcl_pose_clusters", "mcl_get_cluster_labels",
     "mcl_query_scans", "mcl_score_poses", "mcl_get_query_counters",
@@ -312,6 +313,10 @@ def load_library(legacy=False):
         lib.mcl_default_likelihood_field_config.restype = None
         lib.mcl_set_likelihood_field.argtypes = [C.c_void_p, C.POINTER(LikelihoodFieldConfig)]
         lib.mcl_get_likelihood_field.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.mcl_get_wedge_fields.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32)]
+        lib.mcl_get_ring_fields.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.mcl_get_sweep_table.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32)]
+        lib.mcl_host_sweep_global_layout.argtypes = [C.c_uint32, C.c_uint32, C.c_int32, C.POINTER(C.c_int64)]
         lib.mcl_get_likelihood_table.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32)]
         lib.mcl_host_likelihood_field.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(LikelihoodFieldConfig),
                                                   C.c_void_p, C.c_size_t]
@@ -819,6 +824,15 @@ def host_skip_field_wedge(grid, wedge: int) -> np.ndarray:
     return out
 
 
+def host_sweep_global_layout(width: int, height: int, max_range_px: int) -> dict:
+    """mcl_host_sweep_global_layout: {ok, pitch, rows, stride, alloc, max_offset} of the ringed copies of the wedge fields."""
+    out = (C.c_int64 * 6)()
+    rc = load_library().mcl_host_sweep_global_layout(C.c_uint32(width), C.c_uint32(height), C.c_int32(max_range_px), out)
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_sweep_global_layout rc={rc}", rc)
+    return dict(ok=bool(out[0]), pitch=int(out[1]), rows=int(out[2]), stride=int(out[3]), alloc=int(out[4]), max_offset=int(out[5]))
+
+
 def host_skip_field_wedge_tight(grid, wedge: int) -> np.ndarray:
     """The wedge field under the tight rule (jumps bounded by the distance travelled inside the wedge): what set_map builds."""
     g = _c(grid, np.int8)
@@ -1153,6 +1167,34 @@ class Engine:
         out = np.empty(K.value + 1, np.float32)
         self._chk(self.lib.mcl_get_likelihood_table(self._h, _p(out), C.c_size_t(out.size), None), "mcl_get_likelihood_table")
         return out
+
+    # -- the tables under the ray stage, as stored on the device (read-only; tests/test_gpu_ray_tables.py)
+    def wedge_fields(self):
+        """The wedge fields mcl_set_map built: (WEDGES, Hp, Wps) uint8 in the stored encoding, padding columns included; the
+        padded grid is [:, :, :Wp] with Wp = map width + 1."""
+        dims = (C.c_int32 * 3)()
+        self._chk(self.lib.mcl_get_wedge_fields(self._h, None, C.c_size_t(0), dims), "mcl_get_wedge_fields")
+        out = np.empty((WEDGES, dims[0], dims[2]), np.uint8)
+        self._chk(self.lib.mcl_get_wedge_fields(self._h, _p(out), C.c_size_t(out.size), None), "mcl_get_wedge_fields")
+        return out
+
+    def ring_fields(self):
+        """The mirrored, ringed copies of the wedge fields (the global-field and hybrid forms), the whole allocation of
+        host_sweep_global_layout as a flat uint8 array; EngineError NOT_READY on an engine that holds none."""
+        if getattr(self, "map_shape", None) is None:
+            raise EngineError("mcl_get_ring_fields: no map set", MCL_ERR_NOT_READY)
+        H, W = self.map_shape
+        out = np.empty(max(host_sweep_global_layout(W, H, self.max_range_px)["alloc"], 1), np.uint8)
+        self._chk(self.lib.mcl_get_ring_fields(self._h, _p(out), C.c_size_t(out.size)), "mcl_get_ring_fields")
+        return out
+
+    def sweep_table(self):
+        """((rows, cols) float64, beam_margin): the fp64 table of the last scan as RAYS_SWEEP's ray stage used it."""
+        dims = (C.c_int32 * 3)()
+        self._chk(self.lib.mcl_get_sweep_table(self._h, None, C.c_size_t(0), dims), "mcl_get_sweep_table")
+        out = np.empty((dims[0], dims[1]), np.float64)
+        self._chk(self.lib.mcl_get_sweep_table(self._h, _p(out), C.c_size_t(out.size), None), "mcl_get_sweep_table")
+        return out, int(dims[2])
 
     def particle_count(self) -> int:
         n = C.c_int64()
