@@ -460,7 +460,7 @@ int mcl_comm_update(mcl_engine_t *h, const double action[3], const float *obs, i
     const int64_t *counts = c->counts;
     const uint64_t *totals = c->totals;
     // Lists or not is decided from what EVERY rank knows alike (the previous update's summed vector): all ranks take the same branch.
-    bool lists = c->lists_known && !h->env_comm_no_lists;
+    bool lists = c->lists_known && !h->env.comm_no_lists;
     uint64_t weight = 0;
     for (int r = 0; r < G && lists; ++r) {
         lists = counts[r] >= 0;
@@ -540,7 +540,7 @@ int mcl_comm_update(mcl_engine_t *h, const double action[3], const float *obs, i
         bool all = true;
         uint64_t wsum = 0;
         for (int r = 0; r < G; ++r) { all = all && c->counts[r] >= 0; wsum |= c->counts[r] > 0 ? c->totals[r] : 0ull; }
-        if (all && wsum != 0 && !h->env_comm_no_pregather && !next_keeps) {
+        if (all && wsum != 0 && !h->env.comm_no_pregather && !next_keeps) {
             CommLocal pre;                         // (a local failure of the export shows in the next update: `gathered` stays false here)
             rc = comm_gather_lists(h, c->counts, pre);
             if (rc) return rc;

@@ -89,7 +89,7 @@ bool mode_fills_pc(int mode) { return mode != 0 && mode != MCL_RAYS_MARCH; }    
 // the global-field form alone, as in round 4.
 bool sweep_hybrid(const mcl_engine *h)
 {
-    return h->sweep_global && h->env_sweep_hybrid != 0 && h->rec_ok && h->sweep_hyb_layout_ok && h->d_beam_err != nullptr &&
+    return h->sweep_global && h->env.sweep_hybrid != 0 && h->rec_ok && h->sweep_hyb_layout_ok && h->d_beam_err != nullptr &&
            h->d_distw != nullptr && h->d_distg != nullptr && (size_t)mcl::kSwWinBytes + (size_t)h->ltd_cols * 8 <= 80 * 1024 - 64;
 }
 
@@ -104,7 +104,7 @@ bool sweep_far_expected(const mcl_engine *h) { return h->far_fresh || h->h_resul
 bool sweep_hybrid_decide(mcl_engine *h)
 {
     if (!sweep_hybrid(h)) return false;
-    if (h->env_sweep_hybrid == 2) return true;
+    if (h->env.sweep_hybrid == 2) return true;
     if (h->far_fresh) { h->hyb_backoff = 0; h->hyb_skip = 0; return false; }
     if (h->last_sweep_global == 2) {
         if (h->h_result[15] >= mcl::kFarWindowedMin / 2) { h->hyb_backoff = h->hyb_backoff ? std::min(32, 2 * h->hyb_backoff) : 1; h->hyb_skip = h->hyb_backoff; }
@@ -126,7 +126,7 @@ int sweep_play(const mcl_engine *h, bool hybrid)
 // the window play the units of a layout are cut for and k_sweep_plan works with (0: no windowed kernel; -1: no cuts at all, MCL_NO_BUCKET_CUTS)
 int unit_play(const mcl_engine *h, int mode, bool hybrid)
 {
-    return h->env_no_bucket_cuts ? -1 : (mode_sweep(mode) ? sweep_play(h, hybrid) : 0);
+    return h->env.no_bucket_cuts ? -1 : (mode_sweep(mode) ? sweep_play(h, hybrid) : 0);
 }
 
 // upper bound on the units of n sorted particles: the plain grid plus one cut per bucket of a sparse set (mcl::k_unit_table)
@@ -143,7 +143,7 @@ int launch_sweep_plan(mcl_engine *h, int64_t n, int nwg, int g, bool hybrid)
     const int play = sweep_play(h, hybrid);                             // cells a window leaves for the particles of an item
     // (EV_K0 = the stop event of the kernel before the ray kernel, EV_K1 = the ray kernel's own: its duration, dispatch included, at no cost)
     hipExtLaunchKernelGGL(mcl::k_sweep_plan, dim3(1), dim3(1024), mcl::kPlanLds, h->stream, nullptr, h->ev[EV_K0], 0, h->d_unit_sums.p, h->d_nunits.p, ngroups, nwg,
-                          (double)(play / 2 - 1), h->env_sw_guide > 0 ? h->env_sw_guide : (h->sweep_global ? 3 : 2), h->d_items.p, h->d_centres.p, h->d_nitems.p);
+                          (double)(play / 2 - 1), h->env.sw_guide > 0 ? h->env.sw_guide : (h->sweep_global ? 3 : 2), h->d_items.p, h->d_centres.p, h->d_nitems.p);
     HIPCHK(h, hipGetLastError());
     return MCL_OK;
 }
@@ -191,7 +191,7 @@ int choose_ray_mode(const mcl_engine *h, int64_t n, bool force_skip, const char 
     // with 64-particle groups and enough rays to amortise the sort (measured, wall ms skip / quad / cell:
     // 4096 x 1081 0.16/0.28/0.40, 65536 x 1081 0.55/0.56/0.44, 65536 x 61 0.21/0.33/0.25, 262144 x 61 0.47/0.76/0.40);
     // below that the self-contained k_rays_skip (one launch, no work lists) is the quickest
-    const int64_t cell_min = h->env_cell_min > 0 ? h->env_cell_min : 65536;
+    const int64_t cell_min = h->env.cell_min > 0 ? h->env.cell_min : 65536;
     const bool big = n >= cell_min && n * (int64_t)h->B >= (8 << 20);
     if (big && sweep_ok) {
         w = sweep_hybrid(h) ? "AUTO: at least 65536 particles and 2^23 rays, evenly spaced beams; MAX_RANGE_PX > 243 (or MCL_SWEEP_GLOBAL): k_rays_sweep walks in LDS windows and goes on in the wedge fields in global memory where a ray leaves its window"
@@ -219,7 +219,7 @@ SortTiles sort_tiles(const mcl_engine *h)
 // histograms: one returning L2 atomic per particle (~1 per clock and XCD) + a scatter.  From 3M particles a radix
 // sort of (key, index) pairs is quicker -- keys only, rocPRIM's device sort (a plain library sort), then a gather:
 // 4M x 1081 6.57 -> 6.47 ms per update; below, its fixed cost of a dozen launches loses (2M +0.03, 262 144 +0.05 ms).
-bool sort_radix(const mcl_engine *h, int64_t n) { return h->env_sort_radix >= 0 ? h->env_sort_radix != 0 : n >= 3000000; }
+bool sort_radix(const mcl_engine *h, int64_t n) { return h->env.sort_radix >= 0 ? h->env.sort_radix != 0 : n >= 3000000; }
 
 // The layout the ordering works from, on `stream`: the bounding box of the particles in d_pc (every 16th of a large set), and
 // the occupied tiles of the map numbered compactly when the map has at most kSortMaxTiles of them (bbox[5] says so)
@@ -267,7 +267,11 @@ struct RayPlan {
     unsigned gfar = 1;                                      // k_rays_far's grid
     bool hyb = false, glob = false, rec = false, pairs = false;   // the form of k_rays_sweep
     size_t qlds = 0;                                        // LDS of the kernel with work lists
-    bool far_windowed = false, radix = false, stale_layout = false;
+    bool far_windowed = false, radix = false;
+    // what the resampling launch left for this stage (RayHandoff): constants in d_pc | ordering by the previous layout | (key, index)
+    // pairs written | the few words cleared, given clear_passed | the wait for ev_obs is this launch's to issue
+    bool constants_ready = false, stale_layout = false, keys_written = false, clear_folded = false, obs_wait = false;
+    mcl::PrepClear clear_passed{};
 };
 
 // Slices, list segments and grids of the kernels with work lists (quad, cell, sweep)
@@ -275,13 +279,13 @@ void plan_work_lists(const mcl_engine *h, int64_t n, RayPlan &p)
 {
     // item granularity: 32 slices per CU (measured best at 4M: 4/8/16/32/64 -> 22.1/20.2/19.7/19.6/20.2 ms), but at
     // least 256 particles per slice so that the 78 KB window load stays amortised
-    const int spc = h->env_qslices_per_cu > 0 ? h->env_qslices_per_cu : 32;
+    const int spc = h->env.qslices_per_cu > 0 ? h->env.qslices_per_cu : 32;
     p.nsl = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)spc * h->num_cu, (n + 255) / 256));
     if (p.ordered) {
         // k_rays_cell: a slice is a run of the sorted order; 2048 particles = two 64-particle groups per wave.  Longer
         // slices amortise the window load better, shorter ones balance the persistent workgroups better
         // (measured at 4M: 1024/2048/4096/8192/16384 -> 8.59/8.04/7.86/7.96/8.64 ms; at 256k: 2048/4096 -> 0.68/0.79 ms)
-        int64_t slice_len = h->env_cell_slice > 0 ? std::max<int64_t>(64, h->env_cell_slice) : (n >= (1 << 21) ? 4096 : 2048);
+        int64_t slice_len = h->env.cell_slice > 0 ? std::max<int64_t>(64, h->env.cell_slice) : (n >= (1 << 21) ? 4096 : 2048);
         p.nsl = (int)std::max<int64_t>(1, (n + slice_len - 1) / slice_len);
     }
     if (p.sweep) {
@@ -292,7 +296,7 @@ void plan_work_lists(const mcl_engine *h, int64_t n, RayPlan &p)
         // 0.58 / 0.80 -> 0.53 / 0.77, 1M: 1.72 / 2.13 -> 1.63 / 2.07; at 4M G = 1 and 2 are level).
         // Round 3: with the per-wedge sums added atomically (no partial-sum array per group) G = 1 wins at every size
         // (4M x 1081, ms per update G = 1 / 2 / 4: 6.80 / 6.91 / 7.08; levine stand-in 7.89 / 8.00 / 8.24)
-        p.sweep_g = h->env_sweep_g > 0 ? h->env_sweep_g : 1;
+        p.sweep_g = h->env.sweep_g > 0 ? h->env.sweep_g : 1;
         if (p.sweep_g > mcl::kWedges || (mcl::kWedges % p.sweep_g) != 0) p.sweep_g = 1;
         p.nsl = (int)((n + mcl::kSwUnit - 1) / mcl::kSwUnit);
     }
@@ -326,7 +330,7 @@ void plan_sweep_form(mcl_engine *h, RayPlan &p)
     // PAIRS (two rays per lane) where the walk waits for memory: always in the global-field form; in LDS windows for a set
     // that was set / initialised since the last update (the spread cloud of a re-localisation: -11 % on its first update, where
     // the tracking cloud gains nothing and the levine stand-in loses 2 %); MCL_SWEEP_PAIRS=0 / 1 overrides
-    p.pairs = p.rec && !p.hyb && (h->env_sweep_pairs >= 0 ? h->env_sweep_pairs != 0 : (p.glob || p.far_windowed));
+    p.pairs = p.rec && !p.hyb && (h->env.sweep_pairs >= 0 ? h->env.sweep_pairs != 0 : (p.glob || p.far_windowed));
     p.qlds = (p.glob ? 0 : (size_t)mcl::kSwWinBytes) + (p.rec ? (size_t)h->ltd_cols * 8 : 0);
 }
 
@@ -342,11 +346,14 @@ RayPlan plan_rays(mcl_engine *h, int64_t n, bool force_skip, bool direct_table)
     p.grid = (int)std::max<int64_t>(1, std::min<int64_t>(h->num_cu, (n + 15) / 16));
     p.lds = (size_t)h->tw_cells * h->tw_cells / 2;
     p.timed = !p.lists && !h->capturing && !direct_table;
+    const RayHandoff &ho = h->handoff;
+    p.constants_ready = ho.constants;
     if (!p.lists) return p;
     plan_work_lists(h, n, p);
     if (p.sweep) plan_sweep_form(h, p);
     else p.qlds = (size_t)h->qside * h->qside;
-    p.stale_layout = p.ordered && h->layout_stale_used;      // d_bbox / d_tilemap hold the layout to order by: not remade
+    p.stale_layout = p.ordered && ho.stale_layout;           // d_bbox / d_tilemap hold the layout to order by: not remade
+    p.keys_written = ho.keys; p.clear_folded = ho.folded; p.clear_passed = ho.passed; p.obs_wait = ho.obs_wait;
     p.radix = p.ordered && sort_radix(h, n);
     return p;
 }
@@ -415,7 +422,7 @@ void ray_prep(mcl_engine *h, const RayPlan &p, const mcl::RayArgs &a)
 {
     const dim3 grid((unsigned)((a.n + 255) / 256));
     if (!p.lists) {
-        if (p.mode == MCL_RAYS_SKIP && !h->pc_ready)
+        if (p.mode == MCL_RAYS_SKIP && !p.constants_ready)
             hipLaunchKernelGGL(mcl::k_particle_prep, grid, dim3(256), 0, h->stream, a.x, a.y, a.th, a.n, h->ox, h->oy, h->res, h->d_pc, h->d_angle, h->B,
                                (short4 *)nullptr, mcl::PrepClear{});
         return;
@@ -426,11 +433,11 @@ void ray_prep(mcl_engine *h, const RayPlan &p, const mcl::RayArgs &a)
     if (p.sweep) clr.far_count = h->d_result + 15;
     if (p.ordered && !p.stale_layout) clr.bbox = h->d_bbox;          // (the histogram is left all-zero by k_hist_clear of the previous sort)
     clr.bbox_play = unit_play(h, p.mode, p.hyb);
-    if (p.ordered && h->pc_ready) {         // the resampling kernel left the constants and zeroed the per-particle scratch
+    if (p.ordered && p.constants_ready) {          // the resampling kernel left the constants and zeroed the per-particle scratch
         clr.logw_acc = nullptr; clr.far_flags = nullptr;
         // ... and, from the second update of a configuration on, the few words that are not per particle as well
-        const mcl::PrepClear &pc0 = h->prep_passed;
-        const bool done = h->prep_folded && clr.fix_count == pc0.fix_count && clr.fix_words == pc0.fix_words &&
+        const mcl::PrepClear &pc0 = p.clear_passed;
+        const bool done = p.clear_folded && clr.fix_count == pc0.fix_count && clr.fix_words == pc0.fix_words &&
                           clr.fix_over == pc0.fix_over && clr.exact_count == pc0.exact_count && clr.far_count == pc0.far_count &&
                           clr.bbox == pc0.bbox && clr.bbox_play == pc0.bbox_play && !clr.hist && !pc0.hist;
         if (!done) hipLaunchKernelGGL(mcl::k_prep_small, dim3(1), dim3(256), 0, h->stream, clr);
@@ -474,7 +481,7 @@ int ray_order(mcl_engine *h, const RayPlan &p, const mcl::RayArgs &a)
     size_t tb = 0;
     HIPCHK(h, rocprim::radix_sort_pairs(nullptr, tb, h->d_skey.p, h->d_skey2.p, h->d_srank.p, h->d_sval2.p, (size_t)n, 0, mcl::kSortKeyLog2, h->stream));
     MCL_TRY(h->d_sort_tmp.reserve(h, tb));
-    if (!(p.stale_layout && h->keys_done))       // (else the resampling kernel wrote the pairs)
+    if (!(p.stale_layout && p.keys_written))    // (else the resampling kernel wrote the pairs)
         hipLaunchKernelGGL(mcl::k_sort_keys, dim3(nb256), dim3(256), 0, h->stream, h->d_pc, a.th, n, h->Wp, h->Hp, h->d_bbox, h->d_skey, h->d_srank,
                            h->d_tilemap, ntx_abs);
     tb = h->d_sort_tmp.cap;
@@ -519,7 +526,7 @@ int ray_sweep_items(mcl_engine *h, const RayPlan &p, mcl::RayArgs &a)
     if (!h->ltd_ready) build_ltd(h);          // a caller whose table decision was made for another particle count
     MCL_TRY(launch_sweep_plan(h, a.n, p.nseg, p.sweep_g, p.hyb));
     a.sweep_g = p.sweep_g; a.Ltd = h->d_Ltd; a.ltd_cols = h->ltd_cols;
-    a.split16 = h->env_sw_split16 >= 0 ? h->env_sw_split16 : 0;
+    a.split16 = h->env.sw_split16 >= 0 ? h->env.sw_split16 : 0;
     a.beam_csx = h->sweep_global ? h->d_beam_csxg : h->d_beam_csx; a.beam_pad = h->beam_pad; a.beam_margin = h->beam_margin;
     a.beam_csi = h->d_beam_csi; a.beam_err = h->d_beam_err; a.rec_k = 2.0 * h->rec_c;
     a.distg = h->d_distg; a.distg_stride = h->distg_stride; a.distg_pitch = h->distg_pitch;
@@ -591,7 +598,7 @@ void ray_combine(mcl_engine *h, const RayPlan &p, int64_t n)
         // order, the per-workgroup maxima, and the overflow flag of the fix-up lists (k_fix_overflow's job for the other kernels)
         hipExtLaunchKernelGGL(mcl::k_combine_logw, dim3(mcl::kRedBlocks), dim3(256), 0, h->stream, nullptr, h->ev[EV_RAYS], 0, n, h->d_perm.p, h->d_logw_acc.p,
                               h->d_logw.p, h->d_maxpart.p, h->d_fix_count.p, p.nseg, p.segcap, h->d_fix_over);
-        h->ev_rays_bound = true;               // (the stage's last kernel: EV_RAYS is its stop event)
+        h->stage_ev.rays_bound = true;         // (the stage's last kernel: EV_RAYS is its stop event)
         h->max_partials_ready = true;
     } else {
         hipLaunchKernelGGL(mcl::k_fix_overflow, dim3(1), dim3(256), 0, h->stream, h->d_fix_count, p.nseg, p.segcap, h->d_fix_over);
@@ -602,7 +609,7 @@ void ray_combine(mcl_engine *h, const RayPlan &p, int64_t n)
 // Phase 10 (MCL_DEBUG_WG): four words per persistent workgroup, cleared before the ray kernel and written to the named file after the stage
 int ray_debug_begin(mcl_engine *h, const RayPlan &p, mcl::RayArgs &a, DevBuf<unsigned long long> &d_dbg)
 {
-    if (h->env_debug_wg.empty()) return MCL_OK;
+    if (h->env.debug_wg.empty()) return MCL_OK;
     MCL_TRY(d_dbg.reserve(h, (size_t)p.nseg * 4));
     HIPCHK(h, hipMemset(d_dbg, 0, (size_t)p.nseg * 32));
     a.dbg = d_dbg;
@@ -615,11 +622,23 @@ int ray_debug_dump(mcl_engine *h, const RayPlan &p, DevBuf<unsigned long long> &
     std::vector<unsigned long long> hd((size_t)p.nseg * 4);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipMemcpy(hd.data(), d_dbg, hd.size() * 8, hipMemcpyDeviceToHost));
-    if (FILE *f = fopen(h->env_debug_wg.c_str(), "wb")) { fwrite(hd.data(), 8, hd.size(), f); fclose(f); }
+    if (FILE *f = fopen(h->env.debug_wg.c_str(), "wb")) { fwrite(hd.data(), 8, hd.size(), f); fclose(f); }
     return MCL_OK;
 }
 
+// Nothing is prepared for a ray stage any more: the one way the hand-off is voided (graph_reset, the top of an update and of a staged
+// resample, a staged ray stage with no resample before it) and consumed (launch_rays; tail_graph for the launches its graph replays).
+// A wait owed on ev_obs stays owed until it is issued: it orders the streams, and graph_reset can run inside launch_rays before it.
+void ray_handoff_void(mcl_engine *h)
+{
+    const bool owed = h->handoff.obs_wait;
+    h->handoff = {};
+    h->handoff.obs_wait = owed;
+}
+
 // The ray stage of n particles: log-weights into d_logw.  force_skip: the redo after a fix-up list overflow (fix_lists_overflowed).
+// Consumes the hand-off of the resampling launch where it ends well (an early error return leaves it standing, as it leaves the stage
+// unrun); recorded into a graph it consumes nothing: every replay finds the constants in d_pc, and tail_graph consumes them.
 int launch_rays(mcl_engine *h, const double *x, const double *y, const double *th, int64_t n, bool force_skip = false, bool direct_table = false)
 {
     mcl::RayArgs a = ray_args(h, x, y, th, n, direct_table);
@@ -634,7 +653,7 @@ int launch_rays(mcl_engine *h, const double *x, const double *y, const double *t
     ray_prep(h, p, a);
     if (p.ordered) { MCL_TRY(ray_order(h, p, a)); MCL_TRY(ray_units(h, p, a)); }
     // the tables of this update's scan were built on the second stream beside the resampling and the ordering: from here on they are read
-    if (p.lists && h->obs_wait_pending) { h->obs_wait_pending = false; HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_obs, 0)); }
+    if (p.obs_wait) { h->handoff.obs_wait = false; HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_obs, 0)); }
     if (p.sweep) MCL_TRY(ray_sweep_items(h, p, a));
     // What a decision leaves behind is written once per launch: the hybrid's back-off by plan_rays, before anything is launched;
     // far_fresh and last_sweep_* here, behind every reservation that can still fail and before the debug buffer's (as they always were).
@@ -648,9 +667,7 @@ int launch_rays(mcl_engine *h, const double *x, const double *y, const double *t
         h->last_work_lists = true;
     }
     h->last_mode = p.mode;
-    h->prep_folded = false;
-    h->layout_stale_used = false; h->keys_done = false;
-    if (!h->capturing) h->pc_ready = false;
+    if (!h->capturing) ray_handoff_void(h);
     HIPCHK(h, hipGetLastError());
     return MCL_OK;
 }
@@ -674,8 +691,7 @@ void build_ltd(mcl_engine *h)
 int upload_observation(mcl_engine *h)
 {
     HIPCHK(h, hipMemcpyAsync(h->d_obs, h->h_obs, (size_t)h->B * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    int rc = h->capturing ? MCL_OK : ensure_lt(h);          // no allocation while a graph is being captured (sizes are warm)
-    if (rc) return rc;
+    if (!h->capturing) MCL_TRY(ensure_lt(h));               // no allocation while a graph is being captured (sizes are warm)
     dim3 g((h->bpad + 255) / 256, h->P + 1);
     hipLaunchKernelGGL(mcl::k_obs_build_lt, g, dim3(256), 0, h->stream, h->d_obs, h->res, h->P, h->d_L, h->B, h->bpad, h->d_obs_idx, h->d_Lt,
                        h->d_Lt + (size_t)(h->P + 1) * h->bpad);
@@ -706,7 +722,7 @@ int sensor_and_weights(mcl_engine *h, const double *d_global_max, bool defer_sum
 
 // weights, sums and the CDF of the current log-weights (the tail of an update).  Small updates take one launch.
 // kld (a small update with KLD on, result_to_host): the tail also clears the words the resampling kernel marked
-int weights_and_cdf(mcl_engine *h, bool result_to_host = false, const mcl::KldArgs *kld = nullptr)
+int weights_and_cdf(mcl_engine *h, bool result_to_host = false, const mcl::KldArgs *kld = nullptr, bool *bind_sensor = nullptr)
 {
     const int64_t n = h->N;
     if (h->cfg.weight_mode == MCL_WEIGHT_LOG && h->cfg.resample_neff_permille == 0 && n <= mcl::kTinyTailMax) {
@@ -726,9 +742,18 @@ int weights_and_cdf(mcl_engine *h, bool result_to_host = false, const mcl::KldAr
         h->compact_n = -1; h->compact_pending = false; h->list_epoch++;
         return MCL_OK;
     }
-    int rc = sensor_and_weights(h, nullptr, true);             // (the sums are finished by the scan's spine)
-    if (rc) return rc;
-    return scan_weights(h, h->d_q, h->d_cdf, n, 0, nullptr);   // CDF for the next resample / visualize
+    MCL_TRY(sensor_and_weights(h, nullptr, true));             // (the sums are finished by the scan's spine)
+    return scan_weights(h, h->d_q, h->d_cdf, n, 0, nullptr, bind_sensor);   // CDF for the next resample / visualize
+}
+
+// The scan of the engine's own weights as the last kernel of its stage -- behind the weights of an update's tail (all: weights_and_cdf),
+// or alone behind the staged flow's -- with EV_SENSOR closed by its stop event where it can be bound, else by a record behind it.
+int close_sensor_stage(mcl_engine *h, bool all)
+{
+    bool bound = false;
+    MCL_TRY(all ? weights_and_cdf(h, false, nullptr, &bound) : scan_weights(h, h->d_q, h->d_cdf, h->N, 0, nullptr, &bound));
+    if (!bound) HIPCHK(h, hipEventRecord(h->ev[EV_SENSOR], h->stream));
+    return MCL_OK;
 }
 
 // ---- KLD-adaptive particle count (mcl_set_kld)
@@ -857,9 +882,9 @@ void mcl_host::graph_reset(mcl_engine *h)
     for (int k = 0; k < 2; ++k)
         if (h->graph_exec[k]) { (void)hipGraphExecDestroy(h->graph_exec[k]); h->graph_exec[k] = nullptr; }
     h->graph_warm = false;
-    h->prep_cache_valid = false; h->prep_folded = false;
-    h->layout_valid = false; h->layout_stale_used = false; h->keys_done = false;
-    h->pc_ready = false;                    // whatever changed (map, beams, particles, a buffer): the ray stage makes its own constants
+    h->prep_cache_valid = false;
+    h->layout.valid = false;
+    ray_handoff_void(h);                    // whatever changed (map, beams, particles, a buffer): the ray stage makes its own constants
 }
 
 // mcl_update is not refused on an engine with a communicator or in a group, so such an engine can hold a captured graph too: a spine
@@ -873,12 +898,12 @@ int mcl_host::reserve_scan_spine(mcl_engine *h, int64_t n)
     return h->d_blocktot.reserve(h, need);
 }
 
-int mcl_host::scan_weights(mcl_engine *h, const uint64_t *d_q, uint64_t *d_cdf, int64_t n, uint64_t offset, uint64_t *d_total)
+int mcl_host::scan_weights(mcl_engine *h, const uint64_t *d_q, uint64_t *d_cdf, int64_t n, uint64_t offset, uint64_t *d_total, bool *bind_sensor)
 {
     int nb = (int)((n + mcl::kScanTile - 1) / mcl::kScanTile);
     // the scan of the engine's own weights also leaves the compact list of the particles that carry weight
     mcl::CompactOut co{};
-    const bool own = d_q == h->d_q && d_cdf == h->d_cdf && offset == 0 && !h->env_no_compact && h->d_ccdf;
+    const bool own = d_q == h->d_q && d_cdf == h->d_cdf && offset == 0 && !h->env.no_compact && h->d_ccdf;
     if (own) {
         co.block_cnt = h->d_blockcnt; co.ccdf = h->d_ccdf; co.cidx = h->d_cidx; co.crec = h->d_crec; co.ctop = h->d_ctop;
         co.x = h->d_x[h->cur]; co.y = h->d_y[h->cur]; co.th = h->d_th[h->cur];
@@ -895,10 +920,10 @@ int mcl_host::scan_weights(mcl_engine *h, const uint64_t *d_q, uint64_t *d_cdf, 
         graph_reset(h);                    // a captured update graph holds the old pointer
         MCL_TRY(h->d_leaders.reserve(h, nlead));
     }
-    if (h->bind_sensor_event && own && !h->capturing) {          // the update's last kernel: EV_SENSOR is its stop event
+    if (bind_sensor && own && !h->capturing) {          // the stage's last kernel: EV_SENSOR is its stop event, and the caller is told
         hipExtLaunchKernelGGL(mcl::k_scan_final, dim3(nb), dim3(mcl::kScanThreads), 0, h->stream, nullptr, h->ev[EV_SENSOR], 0, d_q, n, h->d_blocktot.p, d_cdf,
                               h->d_leaders.p, co);
-        h->ev_sensor_bound = true; h->bind_sensor_event = false;
+        *bind_sensor = true;
     } else {
         hipLaunchKernelGGL(mcl::k_scan_final, dim3(nb), dim3(mcl::kScanThreads), 0, h->stream, d_q, n, h->d_blocktot, d_cdf, h->d_leaders, co);
     }
@@ -932,6 +957,33 @@ void mcl_host::unpack_result(mcl_engine *h)
 int mcl_abi_version(void) { return MCL_ABI_VERSION; }
 
 const char *mcl_last_error(const mcl_engine_t *h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+
+// The tuning knobs of the environment, read once per engine (never on the update path)
+static EnvKnobs read_knobs()
+{
+    EnvKnobs k;
+    if (const char *e = getenv("MCL_CELL_MIN")) k.cell_min = atoll(e);
+    if (const char *e = getenv("MCL_CELL_SLICE")) k.cell_slice = atoll(e);
+    if (const char *e = getenv("MCL_QSLICES_PER_CU")) k.qslices_per_cu = atoi(e);
+    if (const char *e = getenv("MCL_QSIDE")) k.qside = atoi(e);
+    if (const char *e = getenv("MCL_SWEEP_G")) k.sweep_g = atoi(e);
+    if (const char *e = getenv("MCL_TINY_POLL")) k.tiny_poll = atoi(e);
+    if (const char *e = getenv("MCL_NO_COMPACT")) k.no_compact = atoi(e);
+    if (const char *e = getenv("MCL_SORT")) k.sort_radix = std::strcmp(e, "radix") == 0 ? 1 : (std::strcmp(e, "hist") == 0 ? 0 : -1);
+    if (const char *e = getenv("MCL_DEBUG_WG")) k.debug_wg = e;
+    k.no_bucket_cuts = getenv("MCL_NO_BUCKET_CUTS") != nullptr;
+    if (const char *e = getenv("MCL_SWEEP_GLOBAL")) k.sweep_global = atoi(e) != 0;
+    if (const char *e = getenv("MCL_SWEEP_HYBRID")) k.sweep_hybrid = atoi(e);
+    if (const char *e = getenv("MCL_SW_GUIDE")) k.sw_guide = atoi(e);
+    if (const char *e = getenv("MCL_SW_SPLIT16")) k.sw_split16 = atoi(e) != 0;
+    if (const char *e = getenv("MCL_SWEEP_PAIRS")) k.sweep_pairs = atoi(e) != 0 ? 1 : 0;
+    k.no_obs_overlap = getenv("MCL_NO_OBS_OVERLAP") != nullptr;
+    k.no_prep_fold = getenv("MCL_NO_PREP_FOLD") != nullptr;
+    k.no_stale_layout = getenv("MCL_NO_STALE_LAYOUT") != nullptr;
+    k.comm_no_pregather = getenv("MCL_COMM_NO_PREGATHER") != nullptr;
+    k.comm_no_lists = getenv("MCL_COMM_NO_LISTS") != nullptr;
+    return k;
+}
 
 int mcl_create(const mcl_config_t *cfg, mcl_engine_t **out)
 {
@@ -973,27 +1025,7 @@ int mcl_create(const mcl_config_t *cfg, mcl_engine_t **out)
     }
     mcl_engine *h = new mcl_engine();
     h->cfg = *cfg;
-    // tuning knobs of the environment, read once here (never on the update path)
-    if (const char *e = getenv("MCL_CELL_MIN")) h->env_cell_min = atoll(e);
-    if (const char *e = getenv("MCL_CELL_SLICE")) h->env_cell_slice = atoll(e);
-    if (const char *e = getenv("MCL_QSLICES_PER_CU")) h->env_qslices_per_cu = atoi(e);
-    if (const char *e = getenv("MCL_QSIDE")) h->env_qside = atoi(e);
-    if (const char *e = getenv("MCL_SWEEP_G")) h->env_sweep_g = atoi(e);
-    if (const char *e = getenv("MCL_TINY_POLL")) h->env_tiny_poll = atoi(e);
-    if (const char *e = getenv("MCL_NO_COMPACT")) h->env_no_compact = atoi(e);
-    if (const char *e = getenv("MCL_SORT")) h->env_sort_radix = std::strcmp(e, "radix") == 0 ? 1 : (std::strcmp(e, "hist") == 0 ? 0 : -1);
-    if (const char *e = getenv("MCL_DEBUG_WG")) h->env_debug_wg = e;
-    h->env_no_bucket_cuts = getenv("MCL_NO_BUCKET_CUTS") != nullptr;
-    if (const char *e = getenv("MCL_SWEEP_GLOBAL")) h->env_sweep_global = atoi(e) != 0;
-    if (const char *e = getenv("MCL_SWEEP_HYBRID")) h->env_sweep_hybrid = atoi(e);
-    if (const char *e = getenv("MCL_SW_GUIDE")) h->env_sw_guide = atoi(e);
-    if (const char *e = getenv("MCL_SW_SPLIT16")) h->env_sw_split16 = atoi(e) != 0;
-    if (const char *e = getenv("MCL_SWEEP_PAIRS")) h->env_sweep_pairs = atoi(e) != 0 ? 1 : 0;
-    h->env_no_obs_overlap = getenv("MCL_NO_OBS_OVERLAP") != nullptr;
-    h->env_no_prep_fold = getenv("MCL_NO_PREP_FOLD") != nullptr;
-    h->env_no_stale_layout = getenv("MCL_NO_STALE_LAYOUT") != nullptr;
-    h->env_comm_no_pregather = getenv("MCL_COMM_NO_PREGATHER") != nullptr;
-    h->env_comm_no_lists = getenv("MCL_COMM_NO_LISTS") != nullptr;
+    h->env = read_knobs();
     h->num_cu = prop.multiProcessorCount;
     h->cap = cfg->max_particles;
     auto bail = [&](const char *what) {
@@ -1053,12 +1085,12 @@ int mcl_create(const mcl_config_t *cfg, mcl_engine_t **out)
     CRT(hipMemset(h->d_hist, 0, (size_t)mcl::kSortBuckets * 4));          // kept all-zero between sorts (k_hist_clear)
     CRT(hipMemset(h->d_tile_used, 0, (size_t)(mcl::kSortKeySpace / mcl::kHistTile) * 4));
     CRB(h->d_bbox, 8);
-    CRB(h->d_bbox_nx, 8);
-    CRB(h->d_tilemap_nx, (size_t)mcl::kSortMaxTiles);
-    CRB(h->d_tilemark_nx, (size_t)mcl::kSortMaxTiles);
-    CRT(hipMemset(h->d_tilemark_nx, 0, (size_t)mcl::kSortMaxTiles * sizeof(int)));
-    CRT(hipEventCreateWithFlags(&h->ev_children, hipEventDisableTiming));
-    CRT(hipEventCreateWithFlags(&h->ev_layout, hipEventDisableTiming));
+    CRB(h->layout.d_bbox_nx, 8);
+    CRB(h->layout.d_tilemap_nx, (size_t)mcl::kSortMaxTiles);
+    CRB(h->layout.d_tilemark_nx, (size_t)mcl::kSortMaxTiles);
+    CRT(hipMemset(h->layout.d_tilemark_nx, 0, (size_t)mcl::kSortMaxTiles * sizeof(int)));
+    CRT(hipEventCreateWithFlags(&h->layout.ev_children, hipEventDisableTiming));
+    CRT(hipEventCreateWithFlags(&h->layout.ev_layout, hipEventDisableTiming));
     CRT(hipEventCreateWithFlags(&h->ev_ext_in, hipEventDisableTiming));
     CRT(hipEventCreateWithFlags(&h->ev_ext_out, hipEventDisableTiming));
     CRB(h->d_cut_start, (size_t)mcl::kSwMaxCuts);
@@ -1152,8 +1184,8 @@ void mcl_destroy(mcl_engine_t *h)
     for (int i = 0; i < EV_COUNT; ++i)
         if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
     if (h->ev_obs) (void)hipEventDestroy(h->ev_obs);
-    if (h->ev_children) (void)hipEventDestroy(h->ev_children);
-    if (h->ev_layout) (void)hipEventDestroy(h->ev_layout);
+    if (h->layout.ev_children) (void)hipEventDestroy(h->layout.ev_children);
+    if (h->layout.ev_layout) (void)hipEventDestroy(h->layout.ev_layout);
     if (h->ev_ext_in) (void)hipEventDestroy(h->ev_ext_in);
     if (h->ev_ext_out) (void)hipEventDestroy(h->ev_ext_out);
     if (h->stream2) (void)hipStreamDestroy(h->stream2);
@@ -1191,11 +1223,11 @@ int mcl_set_map(mcl_engine_t *h, const int8_t *data, uint32_t width, uint32_t he
     h->tw_cells = 568;
     // k_rays_quad: byte window of side S in half the LDS (S*S <= 80 KiB, S % 8 == 0); usable when the extent
     // budget S - (P+2) - 3 is at least 48 cells, otherwise k_rays_skip's full-LDS nibble window is used
-    { const int S = h->env_qside > 0 ? h->env_qside : 280; h->qside = (S - (P + 2) - 3 >= 32) ? S : 0; }
+    { const int S = h->env.qside > 0 ? h->env.qside : 280; h->qside = (S - (P + 2) - 3 >= 32) ? S : 0; }
     // k_rays_sweep: the 256-cell LDS windows hold ranges up to 243 px; beyond that (or with MCL_SWEEP_GLOBAL=1) the same walk
     // probes mirrored copies of the wedge fields in global memory, a position's cell dwords being absolute offsets there (no
     // bound on the range from the position format)
-    h->sweep_global = h->env_sweep_global || !mcl::sweep_window_fits(P);
+    h->sweep_global = h->env.sweep_global || !mcl::sweep_window_fits(P);
     h->distg_why_not = nullptr;
     const bool want_wedges = h->qside > 0 || h->sweep_global;     // wedge + quadrant fields (k_rays_far reads the latter)
     build_sensor_table(h->cfg, P, h->table);
@@ -1246,8 +1278,8 @@ int mcl_set_map(mcl_engine_t *h, const int8_t *data, uint32_t width, uint32_t he
         hipLaunchKernelGGL(mcl::k_row_tables, dim3((h->Hp + 63) / 64), dim3(64), 0, h->stream, h->d_dist, h->Wp, h->Hp, h->Wps, d_nxt, d_prv);
         // the tight rule of mcl_wedge.h (jumps bounded by the distance travelled inside the wedge); MCL_WEDGE_METRIC=0 keeps the
         // Euclidean rule: the same binary with either field, for A/B measurements (read here, so a process can build both)
-        const char *env_metric = getenv("MCL_WEDGE_METRIC");
-        const bool tight = !(env_metric && atoi(env_metric) == 0);
+        const char *metric = getenv("MCL_WEDGE_METRIC");
+        const bool tight = !(metric && atoi(metric) == 0);
         int rc_w = MCL_OK;
         for (int k = 0; k < mcl::kWedges && rc_w == MCL_OK; ++k) {
             mcl::wedge_rows(k, rows.data());
@@ -1436,10 +1468,9 @@ int mcl_set_beam_angles(mcl_engine_t *h, const float *angles, int32_t n_beams)
 // weights, sums and CDF (d_max_override: the weight to scale by, on the device), and everything kept about the old set is dropped.
 static int adopt_particle_set(mcl_engine *h, int64_t n, const double *d_max_override)
 {
-    int rc = weight_stats(h, false, d_max_override, true);
-    if (!rc) rc = scan_weights(h, h->d_q, h->d_cdf, n, 0, nullptr);
-    if (!rc) rc = fetch_scalars(h);
-    if (rc) return rc;
+    MCL_TRY(weight_stats(h, false, d_max_override, true));
+    MCL_TRY(scan_weights(h, h->d_q, h->d_cdf, n, 0, nullptr));
+    MCL_TRY(fetch_scalars(h));
     h->have_particles = true;
     h->far_fresh = true;
     h->pack_valid[0] = h->pack_valid[1] = false;
@@ -1620,25 +1651,26 @@ static void resample_ray_extras(mcl_engine *h, int64_t n, mcl::ResampleArgs &a, 
     if (!(rmode == MCL_RAYS_SKIP || mode_orders(rmode))) return;
     a.pc_out = h->d_pc; a.ox = h->ox; a.oy = h->oy; a.res = h->res;
     if (mode_orders(rmode)) { a.clr_logw_acc = h->d_logw_acc; a.clr_far_flags = reinterpret_cast<uint32_t *>(h->d_far.p); }
-    h->pc_ready = true;
+    RayHandoff &ho = h->handoff;
+    ho.constants = true;
     // The ordering of the ray stage works from the layout (bounding box, occupied tiles) of the PREVIOUS update's children
     // when there is one: the set moves by a cell or so per update and the order only decides which rays share a wave.
     // Radix ordering: this kernel then writes the (key, index) pairs too and the sort starts right after it.
     const auto [ntx_abs, nty_abs, tiles_ok] = sort_tiles(h);
     // (not for children injected anywhere on the map: fresh_children, an update of recovery injection -- DESIGN.md §4.9)
-    if (mode_orders(rmode) && h->layout_valid && h->layout_n == n && !h->env_no_stale_layout && !fresh_children) {
-        h->layout_stale_used = true;
+    if (mode_orders(rmode) && h->layout.valid && h->layout.n == n && !h->env.no_stale_layout && !fresh_children) {
+        ho.stale_layout = true;
         if (sort_radix(h, n) && h->d_skey2) {
             a.key_out = h->d_skey; a.val_out = h->d_srank; a.key_bbox = h->d_bbox; a.key_tilemap = tiles_ok ? h->d_tilemap : nullptr;
             a.key_ntx = ntx_abs; a.key_Wp = h->Wp; a.key_Hp = h->Hp;
-            h->keys_done = true;
+            ho.keys = true;
         }
     }
-    if (mode_orders(rmode) && h->prep_cache_valid && h->prep_cache_n == n && !h->env_no_prep_fold) {
+    if (mode_orders(rmode) && h->prep_cache_valid && h->prep_cache_n == n && !h->env.no_prep_fold) {
         a.prep = h->prep_cache; a.prep_on = 1;      // launch_rays checks that this is what it would have cleared
-        if (h->layout_stale_used) a.prep.bbox = nullptr;     // the layout in d_bbox is in use: not reset
-        h->prep_passed = a.prep;
-        h->prep_folded = true;
+        if (ho.stale_layout) a.prep.bbox = nullptr;          // the layout in d_bbox is in use: not reset
+        ho.passed = a.prep;
+        ho.folded = true;
     }
 }
 
@@ -1647,10 +1679,10 @@ static void resample_ray_extras(mcl_engine *h, int64_t n, mcl::ResampleArgs &a, 
 //  ordering kernels of the main stream are on the critical path of a small update, these are not)
 static int layout_mark(mcl_engine *h, int64_t n)
 {
-    h->layout_wanted = false;
-    if (!mode_orders(choose_ray_mode(h, n, false)) || h->env_no_stale_layout) return MCL_OK;
-    HIPCHK(h, hipEventRecord(h->ev_children, h->stream));
-    h->layout_wanted = true;
+    h->layout.wanted = false;
+    if (!mode_orders(choose_ray_mode(h, n, false)) || h->env.no_stale_layout) return MCL_OK;
+    HIPCHK(h, hipEventRecord(h->layout.ev_children, h->stream));
+    h->layout.wanted = true;
     // (launched right here the layout kernels share the device with the sort: measured 0.04-0.06 ms per update slower at 1M and
     //  4M particles than behind the ray stage, where they run in the shadow of the persistent kernel's tail)
     return MCL_OK;
@@ -1658,27 +1690,27 @@ static int layout_mark(mcl_engine *h, int64_t n)
 
 static int next_layout_launch(mcl_engine *h, int64_t n)
 {
-    if (!h->layout_wanted) return MCL_OK;
-    h->layout_wanted = false;
+    if (!h->layout.wanted) return MCL_OK;
+    h->layout.wanted = false;
     // (the layout of the NEXT update, made beside this one's ray stage: whether that update takes the hybrid form is not known
     //  yet -- its units are cut for the hybrid's windows, which costs the global-field form nothing but shorter runs)
     const int play = unit_play(h, choose_ray_mode(h, n, false), sweep_hybrid(h));
-    HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_children, 0));
-    hipLaunchKernelGGL(mcl::k_bbox_init, dim3(1), dim3(64), 0, h->stream2, h->d_bbox_nx, play);
-    launch_layout(h, h->stream2, n, h->d_bbox_nx, h->d_tilemark_nx, h->d_tilemap_nx);
+    HIPCHK(h, hipStreamWaitEvent(h->stream2, h->layout.ev_children, 0));
+    hipLaunchKernelGGL(mcl::k_bbox_init, dim3(1), dim3(64), 0, h->stream2, h->layout.d_bbox_nx, play);
+    launch_layout(h, h->stream2, n, h->layout.d_bbox_nx, h->layout.d_tilemark_nx, h->layout.d_tilemap_nx);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev_layout, h->stream2));
-    h->layout_pending = true;
+    HIPCHK(h, hipEventRecord(h->layout.ev_layout, h->stream2));
+    h->layout.pending = true;
     return MCL_OK;
 }
 
 // End of an update: the layout made beside its ray stage becomes the one the next update orders by.
 int mcl_host::layout_adopt(mcl_engine *h, int64_t n)
 {
-    if (!h->layout_pending) return MCL_OK;
-    HIPCHK(h, hipEventSynchronize(h->ev_layout));
-    std::swap(h->d_bbox, h->d_bbox_nx); std::swap(h->d_tilemap, h->d_tilemap_nx);
-    h->layout_valid = true; h->layout_n = n; h->layout_pending = false;
+    if (!h->layout.pending) return MCL_OK;
+    HIPCHK(h, hipEventSynchronize(h->layout.ev_layout));
+    std::swap(h->d_bbox, h->layout.d_bbox_nx); std::swap(h->d_tilemap, h->layout.d_tilemap_nx);
+    h->layout.valid = true; h->layout.n = n; h->layout.pending = false;
     return MCL_OK;
 }
 
@@ -1711,8 +1743,8 @@ static bool odo_args_of(const mcl_engine *h, const double action[3], mcl::OdoArg
 
 // The resampling kernel of an update: one of twelve entry points, [odometry model][KLD][injection: none | uniform | mixture]; the
 // arguments follow ResampleArgs in that order of the ones that are present (kld, rec or mix -- never both --, odo: null = absent).
-// timed: EV_RESAMPLE is the kernel's stop event.
-static void launch_resample(mcl_engine *h, dim3 grid, size_t lds, bool timed, mcl::ResampleArgs &a, mcl::KldArgs *kld, mcl::RecArgs *rec,
+// timed: EV_RESAMPLE is the kernel's stop event, and the answer says so.
+static bool launch_resample(mcl_engine *h, dim3 grid, size_t lds, bool timed, mcl::ResampleArgs &a, mcl::KldArgs *kld, mcl::RecArgs *rec,
                             mcl::MixArgs *mix, mcl::OdoArgs *odo)
 {
     static const void *const entry[2][2][3] = {
@@ -1728,12 +1760,9 @@ static void launch_resample(mcl_engine *h, dim3 grid, size_t lds, bool timed, mc
     if (mix) args[na++] = mix;
     if (odo) args[na++] = odo;
     const void *fn = entry[odo ? 1 : 0][kld ? 1 : 0][mix ? 2 : (rec ? 1 : 0)];
-    if (timed) {
-        (void)hipExtLaunchKernel(fn, grid, dim3(256), args, lds, h->stream, nullptr, h->ev[EV_RESAMPLE], 0);
-        h->ev_resample_bound = true;
-    } else {
-        (void)hipLaunchKernel(fn, grid, dim3(256), args, lds, h->stream);
-    }
+    if (timed) (void)hipExtLaunchKernel(fn, grid, dim3(256), args, lds, h->stream, nullptr, h->ev[EV_RESAMPLE], 0);
+    else (void)hipLaunchKernel(fn, grid, dim3(256), args, lds, h->stream);
+    return timed;
 }
 
 // One mcl_update / mcl_sensor_update, on do_update's stack: the call, what plan_update decided about it, what the resampling launch left
@@ -1744,7 +1773,8 @@ struct Update {
     bool kld, keep, rec, mix;           // KLD sizes this draw | adaptive resampling keeps the set | the injecting kernel runs | ... from the proposal
     uint64_t rec_thr; double prev_sum_w;
     bool tiny, graph_ok;                // the tail: one workgroup | the captured graph | (neither) launch by launch
-    mcl::KldArgs kld_cur; bool obs_early;   // (resampling launch) the bins the tiny tail clears | the scan's tables are built on the second stream
+    // (resampling launch) the bins the tiny tail clears | the scan's tables are built on the second stream | EV_RESAMPLE is the kernel's stop event
+    mcl::KldArgs kld_cur; bool obs_early, resample_bound;
 };
 
 // Phase 1: what this update is -- sizes, keep, recovery, and which of the three tails it takes.  Nothing is submitted here.
@@ -1823,7 +1853,6 @@ static int launch_update_resample(mcl_engine *h, Update &u, const double *d_norm
     if (!h->lf_on) resample_ray_extras(h, n, a, u.rec);
     size_t cdf_lds = 0;
     if (!a.tile_excl && a.do_resample && n_par <= mcl::kTinyTailMax) { a.cdf_lds_entries = (int)n_par; cdf_lds = (size_t)n_par * sizeof(uint64_t); }
-    h->ev_resample_bound = false;
     const dim3 grid((unsigned)((n + 255) / 256));
     mcl::RecArgs rec_args{};
     mcl::MixArgs mix_args{};
@@ -1851,20 +1880,20 @@ static int launch_update_resample(mcl_engine *h, Update &u, const double *d_norm
     // (the motion model's scalars are plain arguments of this launch, which is outside the captured graph and the tail)
     mcl::OdoArgs odo_cur{};
     const bool odo = odo_args_of(h, u.action, odo_cur);
-    launch_resample(h, grid, cdf_lds, !u.tiny && !h->capturing, a, u.kld ? &u.kld_cur : nullptr, u.rec && !u.mix ? &rec_args : nullptr,
-                    u.mix ? &mix_args : nullptr, odo ? &odo_cur : nullptr);
+    u.resample_bound = launch_resample(h, grid, cdf_lds, !u.tiny && !h->capturing, a, u.kld ? &u.kld_cur : nullptr, u.rec && !u.mix ? &rec_args : nullptr,
+                                       u.mix ? &mix_args : nullptr, odo ? &odo_cur : nullptr);
     if (u.kld && !u.tiny) {
         const int64_t most = std::min<int64_t>(n, (int64_t)h->kld_bits);
         hipLaunchKernelGGL(mcl::k_kld_clear, dim3((unsigned)std::min<int64_t>((most + 255) / 256, 1024)), dim3(256), 0, h->stream, u.kld_cur);
     }
     HIPCHK(h, hipGetLastError());
     h->N = n;                          // the children: the ray stage and everything after it run on them
-    if (a.pc_out) { const int rc_l = layout_mark(h, n); if (rc_l) return rc_l; }
+    if (a.pc_out) MCL_TRY(layout_mark(h, n));
     // The tables of this update's scan (table rows of the observed ranges, Lt, Ltd) depend on nothing the resampling and ordering
     // kernels produce: with a windowed ray kernel they are built on a second stream beside those, and the ray stage waits for
     // them (a copy and two or three small launches off the critical path of an update: ~15 us).  Enqueued AFTER the resampling
     // kernel: that one is on the critical path, and a small update is bound by the order the host submits in.
-    if (!u.tiny && !h->lf_on && !h->env_no_obs_overlap && mode_work_lists(choose_ray_mode(h, n, false))) {
+    if (!u.tiny && !h->lf_on && !h->env.no_obs_overlap && mode_work_lists(choose_ray_mode(h, n, false))) {
         std::swap(h->stream, h->stream2);
         const int rc_obs = prepare_observation(h, u.obs, u.obs_stride);
         hipError_t ee = rc_obs ? hipSuccess : hipEventRecord(h->ev_obs, h->stream);
@@ -1884,15 +1913,14 @@ static int launch_update_resample(mcl_engine *h, Update &u, const double *d_norm
 // Phase 3, the one-workgroup tail of a small update: rays against the static table, then weights, sums, CDF and result in one launch.
 static int tail_tiny(mcl_engine *h, const Update &u)
 {
-    int rc = launch_rays(h, h->d_x[h->cur], h->d_y[h->cur], h->d_th[h->cur], u.n, false, true);
-    if (!rc) rc = weights_and_cdf(h, true, u.kld ? &u.kld_cur : nullptr);
-    if (rc) return rc;
+    MCL_TRY(launch_rays(h, h->d_x[h->cur], h->d_y[h->cur], h->d_th[h->cur], u.n, false, true));
+    MCL_TRY(weights_and_cdf(h, true, u.kld ? &u.kld_cur : nullptr));
     // The result block lands in pinned memory stamped with this update's sequence number: spin on the stamp instead of
     // the stream's completion signal (the signal's path through the runtime costs several microseconds at this size).
     // Everything later on this engine is ordered behind the kernels by the stream; a stamp that never comes (a faulted
     // kernel) ends in the ordinary synchronisation, which reports the error.
     bool seen = false;
-    if (h->env_tiny_poll) {
+    if (h->env.tiny_poll) {
         const volatile unsigned long long *stamp = h->h_result + kResultStamp;
         const auto give_up = u.t0 + std::chrono::milliseconds(20);
         for (unsigned spin = 0; !seen; ++spin) {
@@ -1943,10 +1971,10 @@ static bool graph_ready(mcl_engine *h, const Update &u)
 static int tail_graph(mcl_engine *h, const Update &u)
 {
     HIPCHK(h, hipGraphLaunch(h->graph_exec[h->cur], h->stream));
-    h->pc_ready = false;
+    ray_handoff_void(h);                   // (the replayed ray stage took the constants)
     HIPCHK(h, hipEventRecord(h->ev[EV_SENSOR], h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->compact_pending = h->d_ccdf != nullptr && !h->env_no_compact && u.n > mcl::kTinyTailMax;   // the captured scan wrote a list
+    h->compact_pending = h->d_ccdf != nullptr && !h->env.no_compact && u.n > mcl::kTinyTailMax;   // the captured scan wrote a list
     unpack_result(h);
     h->carry_pending = false;
     // the captured tail is one unit: its time is reported as the ray-cast stage (query prep and table evaluation
@@ -1968,58 +1996,45 @@ static void add_carry(mcl_engine *h, int64_t n)
 // Phase 3, launch by launch: every regular update, and the first of a configuration (which leaves graph_warm).
 static int tail_launches(mcl_engine *h, const Update &u)
 {
-    int rc;
     h->ray_ms_is_graph_tail = false;
-    h->ev_rays_bound = false;
+    h->stage_ev = {};
     if (h->lf_on) {
         // the likelihood field: no observation tables, no ordering, no ray stage; k_lfield writes d_logw
-        h->ev_query_skipped = false;
-        rc = launch_lfield(h, u.obs, u.obs_stride, u.n);
-        if (rc) return rc;
+        MCL_TRY(launch_lfield(h, u.obs, u.obs_stride, u.n));
     } else {
-        if (u.obs_early) {
-            // (the ordering kernels of the ray stage do not read the tables either: the stream waits for them where the ray kernel is
-            //  launched -- launch_rays --, not here: 13 us of a 262 144-particle update)
-            h->obs_wait_pending = true;
-        } else {
-            rc = prepare_observation(h, u.obs, u.obs_stride);
-            if (rc) return rc;
+        // (tables made beside the ordering: the ordering kernels of the ray stage do not read them either, so the stream waits for them
+        //  where the ray kernel is launched -- launch_rays --, not here: 13 us of a 262 144-particle update; and there is no
+        //  query-preparation stage on this stream, nothing to time)
+        h->handoff.obs_wait = h->stage_ev.query_skipped = u.obs_early;
+        if (!u.obs_early) {
+            MCL_TRY(prepare_observation(h, u.obs, u.obs_stride));
+            HIPCHK(h, hipEventRecord(h->ev[EV_QUERY], h->stream));
         }
-        // (the tables were made beside the ordering: no query-preparation stage on this stream, nothing to time)
-        h->ev_query_skipped = u.obs_early;
-        if (!u.obs_early) HIPCHK(h, hipEventRecord(h->ev[EV_QUERY], h->stream));
-        rc = launch_rays(h, h->d_x[h->cur], h->d_y[h->cur], h->d_th[h->cur], u.n);
-        if (h->obs_wait_pending) { h->obs_wait_pending = false; HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_obs, 0)); }      // (a path that launched no windowed kernel)
-        if (rc) return rc;
-        rc = next_layout_launch(h, u.n);          // (second stream; behind the ray stage in submission order, beside it on the device)
-        if (rc) return rc;
+        const int rc = launch_rays(h, h->d_x[h->cur], h->d_y[h->cur], h->d_th[h->cur], u.n);
+        if (h->handoff.obs_wait) { h->handoff.obs_wait = false; HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_obs, 0)); }      // (a path that launched no windowed kernel)
+        MCL_TRY(rc);
+        MCL_TRY(next_layout_launch(h, u.n));      // (second stream; behind the ray stage in submission order, beside it on the device)
     }
     if (u.keep) add_carry(h, u.n);
-    if (u.keep || !h->ev_rays_bound) HIPCHK(h, hipEventRecord(h->ev[EV_RAYS], h->stream));
-    h->bind_sensor_event = true; h->ev_sensor_bound = false;
-    rc = weights_and_cdf(h);
-    h->bind_sensor_event = false;
-    if (rc) return rc;
-    if (!h->ev_sensor_bound) HIPCHK(h, hipEventRecord(h->ev[EV_SENSOR], h->stream));
-    rc = fetch_scalars(h);                 // one D2H copy (scalars, counters, overflow flag); synchronises the stream
-    if (rc) return rc;
+    if (u.keep || !h->stage_ev.rays_bound) HIPCHK(h, hipEventRecord(h->ev[EV_RAYS], h->stream));
+    MCL_TRY(close_sensor_stage(h, true));
+    MCL_TRY(fetch_scalars(h));             // one D2H copy (scalars, counters, overflow flag); synchronises the stream
     if (fix_lists_overflowed(h)) {
         // more undecided rays than the work list holds (only with debug_force_exact at large sizes or a
         // pathological map): redo the ray stage with the self-contained k_rays_skip
         HIPCHK(h, hipMemsetAsync(h->d_counters, 0, 4 * sizeof(unsigned long long), h->stream));
-        rc = launch_rays(h, h->d_x[h->cur], h->d_y[h->cur], h->d_th[h->cur], u.n, true);
-        if (!rc && u.keep) add_carry(h, u.n);
-        if (!rc) rc = weights_and_cdf(h);
-        if (!rc) rc = fetch_scalars(h);
-        if (rc) return rc;
+        MCL_TRY(launch_rays(h, h->d_x[h->cur], h->d_y[h->cur], h->d_th[h->cur], u.n, true));
+        if (u.keep) add_carry(h, u.n);
+        MCL_TRY(weights_and_cdf(h));
+        MCL_TRY(fetch_scalars(h));
     }
     if (h->carry_pending) { h->carry_idx ^= 1; h->carry_valid = true; h->carry_pending = false; }   // this update's logw - max
-    if ((rc = layout_adopt(h, u.n)) != MCL_OK) return rc;
+    MCL_TRY(layout_adopt(h, u.n));
     h->graph_warm = true;                  // every buffer this configuration needs exists now
     h->timings[0] = elapsed(h->ev[EV_START], h->ev[EV_RESAMPLE]);
     h->timings[1] = 0.0;                   // motion is fused into the resample/gather kernel
-    h->timings[2] = h->ev_query_skipped ? 0.0 : elapsed(h->ev[EV_RESAMPLE], h->ev[EV_QUERY]);
-    h->timings[3] = elapsed(h->ev[h->ev_query_skipped ? EV_RESAMPLE : EV_QUERY], h->ev[EV_RAYS]);
+    h->timings[2] = h->stage_ev.query_skipped ? 0.0 : elapsed(h->ev[EV_RESAMPLE], h->ev[EV_QUERY]);
+    h->timings[3] = elapsed(h->ev[h->stage_ev.query_skipped ? EV_RESAMPLE : EV_QUERY], h->ev[EV_RAYS]);
     h->timings[4] = elapsed(h->ev[EV_RAYS], h->ev[EV_SENSOR]);
     return MCL_OK;
 }
@@ -2046,8 +2061,7 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
     if (!obs || n_beams != h->B || (resample_and_move && !action)) return fail(h, MCL_ERR_INVALID_ARG, "bad action/observation");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     Update u{action, obs, obs_stride, uniforms, resample_and_move, std::chrono::steady_clock::now()};     // (the rest: zero)
-    int rc = plan_update(h, u);
-    if (rc) return rc;
+    MCL_TRY(plan_update(h, u));
     const double *d_norm = nullptr, *d_uni = nullptr;
     if (resample_and_move) {
         if (normals) {
@@ -2068,16 +2082,11 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
     }
     if (u.rec) h->far_fresh = true;        // injected children anywhere on the map: the ray stage plans as for a set from outside
     h->recov_cnt_slot = -1; h->recov_injected = 0;
-    h->pc_ready = false;
-    h->layout_stale_used = false; h->keys_done = false;      // (set by the resampling launch when this update orders by the previous update's layout)
+    ray_handoff_void(h);                   // (written by this update's resampling launch, if it has one)
     if (!u.tiny) HIPCHK(h, hipEventRecord(h->ev[EV_START], h->stream));
-    if (resample_and_move) {
-        rc = launch_update_resample(h, u, d_norm, d_uni);
-        if (rc) return rc;
-    }
-    if (!u.tiny && !(resample_and_move && h->ev_resample_bound)) HIPCHK(h, hipEventRecord(h->ev[EV_RESAMPLE], h->stream));
-    rc = u.tiny ? tail_tiny(h, u) : (u.graph_ok && graph_ready(h, u)) ? tail_graph(h, u) : tail_launches(h, u);
-    if (rc) return rc;
+    if (resample_and_move) MCL_TRY(launch_update_resample(h, u, d_norm, d_uni));
+    if (!u.tiny && !u.resample_bound) HIPCHK(h, hipEventRecord(h->ev[EV_RESAMPLE], h->stream));
+    MCL_TRY(u.tiny ? tail_tiny(h, u) : (u.graph_ok && graph_ready(h, u)) ? tail_graph(h, u) : tail_launches(h, u));
     finish_update(h, u);
     return MCL_OK;
 }
@@ -2629,8 +2638,7 @@ int mcl_stage_distinct_parents(mcl_engine_t *h, const int32_t *d_parent, int64_t
     HIPCHK(h, hipMemsetAsync(h->d_bm, 0, (size_t)nwords * 4, h->stream));
     hipLaunchKernelGGL(mcl::k_bm_mark, dim3((unsigned)((n_children + 255) / 256)), dim3(256), 0, h->stream, d_parent, n_children, n_total, h->d_bm);
     hipLaunchKernelGGL(mcl::k_bm_pop, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, h->stream, h->d_bm, nwords, h->d_bm_pop);
-    int rc = scan_weights(h, h->d_bm_pop, h->d_bm_pref, nwords, 0, nullptr);
-    if (rc) return rc;
+    MCL_TRY(scan_weights(h, h->d_bm_pop, h->d_bm_pref, nwords, 0, nullptr));
     h->blocktot_for = nullptr;                  // the spine now describes the bitmap's prefix, not a CDF
     hipLaunchKernelGGL(mcl::k_bm_expand, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, h->stream, h->d_bm, h->d_bm_pref, nwords, d_distinct);
     hipLaunchKernelGGL(mcl::k_bm_slot, dim3((unsigned)((n_children + 255) / 256)), dim3(256), 0, h->stream, d_parent, n_children, n_total, h->d_bm,
@@ -2699,17 +2707,15 @@ int mcl_host::stage_resample_launch(mcl_engine_t *h, const ParentSource &src, co
     if (action) motion_scalars(action, a.dt, a.v, a.w);
     a.do_resample = src.keep ? 0 : 1;
     a.idx_out_base = src.keep ? child_first : 0;
-    h->layout_stale_used = false; h->keys_done = false; h->pc_ready = false;
+    ray_handoff_void(h);
     // as in mcl_update: the ray stage's per-particle constants, its zeroed scratch and (by the previous update's layout) the sort
     // keys come out of this kernel; the layout of these children is made on the second stream for the next update
     if (!index_only) resample_ray_extras(h, n, a);
     mcl::OdoArgs odo_cur{};
     const bool odo = !index_only && odo_args_of(h, action, odo_cur);       // (an index-only pass moves nothing)
-    const bool bound_before = h->ev_resample_bound;
-    launch_resample(h, dim3((unsigned)((n + 255) / 256)), 0, !index_only, a, nullptr, nullptr, nullptr, odo ? &odo_cur : nullptr);
-    h->ev_resample_bound = bound_before;               // (the staged flow reads EV_RESAMPLE itself)
+    (void)launch_resample(h, dim3((unsigned)((n + 255) / 256)), 0, !index_only, a, nullptr, nullptr, nullptr, odo ? &odo_cur : nullptr);   // (bound: the staged flow reads EV_RESAMPLE itself)
     HIPCHK(h, hipGetLastError());
-    if (a.pc_out) { const int rc_l = layout_mark(h, n); if (rc_l) return rc_l; }
+    if (a.pc_out) MCL_TRY(layout_mark(h, n));
     if (index_only) {
         HIPCHK(h, hipMemcpyAsync(src.idx_only_out, h->d_idx, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
         h->have_idx = true;
@@ -2729,8 +2735,7 @@ int mcl_host::stage_resample_launch(mcl_engine_t *h, const ParentSource &src, co
 static int stage_resample_sync(mcl_engine_t *h, const ParentSource &src, const uint64_t *d_cdf, int64_t n_parents, uint64_t q_total,
                                int64_t child_first, int64_t n_children_total, const double action[3])
 {
-    int rc = stage_resample_launch(h, src, d_cdf, n_parents, q_total, child_first, n_children_total, action);
-    if (rc) return rc;
+    MCL_TRY(stage_resample_launch(h, src, d_cdf, n_parents, q_total, child_first, n_children_total, action));
     HIPCHK(h, hipStreamSynchronize(h->stream));           // the children (or the indices) are final: the host may export / gather them now
     return MCL_OK;
 }
@@ -2797,8 +2802,7 @@ int mcl_export_compact(mcl_engine_t *h, void *d_chunk, int64_t chunk_entries)
 {
     if (!h) return MCL_ERR_INVALID_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    const int rc = export_compact_launch(h, d_chunk, chunk_entries, h->cfg.device, h->stream);
-    if (rc) return rc;
+    MCL_TRY(export_compact_launch(h, d_chunk, chunk_entries, h->cfg.device, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MCL_OK;
 }
@@ -2840,9 +2844,8 @@ int mcl_stage_resample_compact(mcl_engine_t *h, const void *d_chunks, int32_t n_
                                const double action[3])
 {
     if (const int rc = refuse_stage(h)) return rc;
-    const int rc = stage_resample_compact_launch(h, d_chunks, n_shards, chunk_entries, counts, totals, n_per_shard, self_shard, child_first,
-                                                 n_children_total, action, nullptr);
-    if (rc) return rc;
+    MCL_TRY(stage_resample_compact_launch(h, d_chunks, n_shards, chunk_entries, counts, totals, n_per_shard, self_shard, child_first,
+                                          n_children_total, action, nullptr));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MCL_OK;
 }
@@ -2855,24 +2858,20 @@ int mcl_host::stage_rays_launch(mcl_engine_t *h, const float *obs, int32_t n_bea
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const int64_t n = h->N;
     const int c = h->cur;
-    int rc = MCL_OK;
     if (!force_skip) {
-        rc = prepare_observation(h, obs, 1);
-        if (rc) return rc;
+        MCL_TRY(prepare_observation(h, obs, 1));
         HIPCHK(h, hipEventRecord(h->ev[EV_QUERY], h->stream));
     } else {
         HIPCHK(h, hipMemsetAsync(h->d_counters, 0, 4 * sizeof(unsigned long long), h->stream));
     }
-    if (!h->pc_ready) { h->layout_stale_used = false; h->keys_done = false; }     // no staged resampling before this call: nothing prepared
-    h->ev_rays_bound = false;
-    rc = launch_rays(h, h->d_x[c], h->d_y[c], h->d_th[c], n, force_skip);
-    if (rc) return rc;
-    rc = next_layout_launch(h, n);
-    if (rc) return rc;
+    if (!h->handoff.constants) ray_handoff_void(h);     // no staged resampling before this call: nothing prepared
+    h->stage_ev.rays_bound = false;
+    MCL_TRY(launch_rays(h, h->d_x[c], h->d_y[c], h->d_th[c], n, force_skip));
+    MCL_TRY(next_layout_launch(h, n));
     if (h->stage_kept) {
         add_carry(h, n);
         HIPCHK(h, hipEventRecord(h->ev[EV_RAYS], h->stream));
-    } else if (!h->ev_rays_bound) HIPCHK(h, hipEventRecord(h->ev[EV_RAYS], h->stream));
+    } else if (!h->stage_ev.rays_bound) HIPCHK(h, hipEventRecord(h->ev[EV_RAYS], h->stream));
     if (!h->max_partials_ready)
         hipLaunchKernelGGL(mcl::k_reduce_max, dim3(mcl::kRedBlocks), dim3(mcl::kRedThreads), 0, h->stream, h->d_logw, n, h->d_maxpart);
     hipLaunchKernelGGL(mcl::k_final_max, dim3(1), dim3(mcl::kRedThreads), 0, h->stream, h->d_maxpart, mcl::kRedBlocks, h->d_scalars, d_max_out);
@@ -2905,8 +2904,7 @@ int mcl_host::stage_rays_finish(mcl_engine_t *h, const float *obs, int32_t n_bea
         h->h_fix_count = h->h_result[12];
         if (!fix_lists_overflowed(h) || attempt == 1) break;
         // work-list overflow (only with debug_force_exact at large sizes): once more with the self-contained k_rays_skip
-        int rc = stage_rays_launch(h, obs, n_beams, true);
-        if (rc) return rc;
+        MCL_TRY(stage_rays_launch(h, obs, n_beams, true));
     }
     stage_rays_note(h);
     return MCL_OK;
@@ -2915,8 +2913,7 @@ int mcl_host::stage_rays_finish(mcl_engine_t *h, const float *obs, int32_t n_bea
 int mcl_stage_rays(mcl_engine_t *h, const float *obs, int32_t n_beams)
 {
     if (const int rc = refuse_stage(h)) return rc;
-    int rc = stage_rays_launch(h, obs, n_beams, false);
-    if (rc) return rc;
+    MCL_TRY(stage_rays_launch(h, obs, n_beams, false));
     return stage_rays_finish(h, obs, n_beams);
 }
 
@@ -2927,8 +2924,7 @@ int mcl_stage_propagate(mcl_engine_t *h, const double *d_px, const double *d_py,
     if (const int rc = refuse_stage(h)) return rc;
     if (!h) return MCL_ERR_INVALID_ARG;
     if (!obs || n_beams != h->B) return fail(h, MCL_ERR_INVALID_ARG, "bad observation");
-    int rc = mcl_stage_resample(h, d_px, d_py, d_pth, d_cdf, n_parents, q_total, child_first, n_children_total, action);
-    if (rc) return rc;
+    MCL_TRY(mcl_stage_resample(h, d_px, d_py, d_pth, d_cdf, n_parents, q_total, child_first, n_children_total, action));
     return mcl_stage_rays(h, obs, n_beams);
 }
 
@@ -2956,16 +2952,11 @@ int mcl_host::stage_weights_launch(mcl_engine_t *h, double global_max_logw, cons
         std::memcpy(&h->h_result[kResultStage], &global_max_logw, sizeof(double));   // pinned: stays valid until the copy has run
         HIPCHK(h, hipMemcpyAsync(h->d_scalars, &h->h_result[kResultStage], sizeof(double), hipMemcpyHostToDevice, h->stream));
     }
-    int rc = weight_stats(h, true, h->d_scalars, true);        // (the scan below finishes the sums)
-    if (rc) return rc;
+    MCL_TRY(weight_stats(h, true, h->d_scalars, true));        // (the scan below finishes the sums)
     // (adaptive resampling: the carry this wrote -- logw minus the GLOBAL maximum -- becomes current in mcl_stage_finish, once the
     //  host knows that the update is not redone from the ray stage on)
     // the shard's own CDF follows its new weights: mcl_sample_particles (visualize) and a later plain mcl_update search it
-    h->bind_sensor_event = true; h->ev_sensor_bound = false;
-    rc = scan_weights(h, h->d_q, h->d_cdf, h->N, 0, nullptr);
-    h->bind_sensor_event = false;
-    if (rc) return rc;
-    if (!h->ev_sensor_bound) HIPCHK(h, hipEventRecord(h->ev[EV_SENSOR], h->stream));
+    MCL_TRY(close_sensor_stage(h, false));
     HIPCHK(h, hipMemcpyAsync(h->h_result, h->d_result, kResultWords * 8, hipMemcpyDeviceToHost, h->stream));
     return MCL_OK;
 }
@@ -2982,8 +2973,7 @@ int mcl_host::stage_weights_finish(mcl_engine_t *h)
 int mcl_stage_weights(mcl_engine_t *h, double global_max_logw)
 {
     if (const int rc = refuse_stage(h)) return rc;
-    int rc = stage_weights_launch(h, global_max_logw);
-    if (rc) return rc;
+    MCL_TRY(stage_weights_launch(h, global_max_logw));
     return stage_weights_finish(h);
 }
 
@@ -3060,8 +3050,7 @@ int mcl_stage_rays_async(mcl_engine_t *h, const float *obs, int32_t n_beams, dou
 {
     if (const int rc = refuse_stage(h)) return rc;
     if (!h || !d_local_max) return MCL_ERR_INVALID_ARG;
-    const int rc = stage_rays_launch(h, obs, n_beams, false, d_local_max);
-    if (rc) return rc;
+    MCL_TRY(stage_rays_launch(h, obs, n_beams, false, d_local_max));
     h->stage_async_rays = true;
     return MCL_OK;
 }
@@ -3072,8 +3061,7 @@ int mcl_stage_weights_async(mcl_engine_t *h, const double *d_global_max, double 
     if (!h || !d_global_max || !d_vec || n_shards <= 0 || n_shards > mcl::kMaxShards || self_shard < 0 || self_shard >= n_shards)
         return MCL_ERR_INVALID_ARG;
     if (!h->stage_async_rays) return fail(h, MCL_ERR_NOT_READY, "mcl_stage_rays_async first");
-    const int rc = stage_weights_launch(h, 0.0, d_global_max);       // ends with the copy of the result block to pinned memory
-    if (rc) return rc;
+    MCL_TRY(stage_weights_launch(h, 0.0, d_global_max));       // ends with the copy of the result block to pinned memory
     hipLaunchKernelGGL(mcl::k_stage_pack, dim3(1), dim3(64), 0, h->stream, h->d_result, d_vec, n_shards, self_shard, h->compact_pending ? 1 : 0,
                        (unsigned long long)h->compact_cap);
     HIPCHK(h, hipGetLastError());
@@ -3092,8 +3080,7 @@ int mcl_stage_complete(mcl_engine_t *h, const double global_sums[5], int32_t *re
     unpack_result(h);
     stage_rays_note(h);
     h->timings[4] = elapsed(h->ev[EV_RAYS], h->ev[EV_SENSOR]);
-    const int rc = layout_adopt(h, h->N);
-    if (rc) return rc;
+    MCL_TRY(layout_adopt(h, h->N));
     // more undecided rays than the fix-up lists hold (debug_force_exact at large sizes, a pathological map): the log-weights of
     // this update are incomplete.  The caller runs the ray stage again through mcl_stage_rays (which falls back to the
     // self-contained kernel) and the two exchanges after it; the children are untouched
@@ -3108,8 +3095,7 @@ int mcl_scan_weights(mcl_engine_t *h, const uint64_t *d_q, uint64_t *d_cdf, int6
     if (!h || !d_q || !d_cdf || n <= 0) return MCL_ERR_INVALID_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     MCL_TRY(reserve_scan_spine(h, n));     // (sized for cap at mcl_create; a gathered array may be longer)
-    int rc = scan_weights(h, d_q, d_cdf, n, offset, nullptr);
-    if (rc) return rc;
+    MCL_TRY(scan_weights(h, d_q, d_cdf, n, offset, nullptr));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MCL_OK;
 }

@@ -53,17 +53,62 @@ struct mcl_search;
 void search_free(struct mcl_search *s);    // mcl_search.hip
 struct mcl_refine;
 void refine_free(struct mcl_refine *r);    // mcl_refine.hip
+
+// ---- the three records that travel between the pieces of an update, and the environment's knobs
+// What the resampling launch prepared for the ray stage of the same update.  resample_ray_extras is the only writer of the
+// resampling part, tail_launches of obs_wait; plan_rays copies it into the RayPlan, launch_rays consumes it, ray_handoff_void voids it.
+struct RayHandoff {
+    bool constants = false;             // d_pc holds the constants of the current particles (ordering modes: and the per-particle scratch is zeroed)
+    bool stale_layout = false;          // this update orders by the previous update's layout: d_bbox / d_tilemap are not remade
+    bool keys = false;                  // ... and the resampling kernel wrote the (key, index) pairs of the library sort
+    bool folded = false; mcl::PrepClear passed{};   // the resampling kernel also cleared the few words that are not per particle: exactly these
+    bool obs_wait = false;              // the scan's tables are built on stream2: the stream waits for ev_obs where the ray stage first reads them
+};
+// Stage events BOUND TO DISPATCHES: the stop event of hipExtLaunchKernelGGL costs nothing, a hipEventRecord between two kernels of
+// a stream ~3 us of pipeline (tools/ubench/event_cost.hip; elapsed times across different launches are valid).  A launch that binds
+// one says so (launch_resample and scan_weights to their callers, the ray stage here); the code that would record it then does not.
+struct StageEvents {
+    bool rays_bound = false;            // EV_RAYS is k_combine_logw's stop event (ray_combine); cleared by the callers of launch_rays
+    bool query_skipped = false;         // EV_QUERY was not recorded: the tables were built beside the ordering (tail_launches' timings)
+};
+// The ordering layout (bounding box, occupied tiles) of an update's children is made on the second stream right after the
+// resampling kernel and used by the NEXT update, whose resampling kernel then writes the sort keys itself: d_bbox / d_tilemap are
+// the layout in use, d_*_nx the one being made; swapped at the end of an update.  wanted (layout_mark: ev_children is recorded
+// behind the resampling kernel) -> pending (next_layout_launch: the kernels are on stream2, ev_layout behind them) -> valid, n
+// (layout_adopt: d_bbox describes the previous update's n children; cleared by graph_reset: map, beams, particles set from outside).
+struct NextLayout {
+    bool wanted = false, pending = false, valid = false; int64_t n = 0;
+    hipEvent_t ev_children = nullptr, ev_layout = nullptr;
+    DevBuf<int> d_bbox_nx, d_tilemap_nx, d_tilemark_nx;
+};
+// Read once at mcl_create (read_knobs), never on the update path; 0 / negative = default where a number is wanted.
+// (MCL_WEDGE_METRIC, MCL_NO_BEAM_PAD and MCL_SWEEP_NO_REC are read where the map / the beams are set.)
+struct EnvKnobs {
+    int64_t cell_min = 0, cell_slice = 0;            // MCL_CELL_MIN, MCL_CELL_SLICE
+    int qslices_per_cu = 0, qside = 0, sweep_g = 0;  // MCL_QSLICES_PER_CU, MCL_QSIDE, MCL_SWEEP_G
+    int tiny_poll = 1, no_compact = 0;  // MCL_TINY_POLL=0: a tiny update waits for the stream, not the stamp; MCL_NO_COMPACT=1: the scan writes no compact list
+    int sort_radix = -1;                // MCL_SORT=radix / hist forces one ordering path; default: by size
+    std::string debug_wg;               // MCL_DEBUG_WG=<file>: four words per persistent workgroup (ray_debug_dump)
+    bool no_bucket_cuts = false;        // MCL_NO_BUCKET_CUTS: units on the plain grid of 1024 slots, sparse sets ordered by whole tiles (rounds 2-3 before the cuts)
+    bool sweep_global = false;          // MCL_SWEEP_GLOBAL=1: k_rays_sweep on the wedge fields in global memory whatever the range
+    int sweep_hybrid = 1;               // MCL_SWEEP_HYBRID=0: ranges beyond the window take the global-field form alone; 2: the hybrid also for a fresh / spread set
+    int sw_guide = 0;                   // MCL_SW_GUIDE=<n>: the guide of k_sweep_plan's run lengths (default 2; 3 for the forms of ranges beyond the LDS window)
+    int sw_split16 = -1;                // MCL_SW_SPLIT16=0/1 forces RayArgs::split16 (default: by size)
+    int sweep_pairs = -1;               // MCL_SWEEP_PAIRS: -1 the engine decides, 0 / 1 forced (A/B measurements)
+    bool no_obs_overlap = false;        // MCL_NO_OBS_OVERLAP: the observation tables are built on the main stream, after the resampling kernel
+    bool no_prep_fold = false;          // MCL_NO_PREP_FOLD: k_prep_small stays a launch of its own
+    bool no_stale_layout = false;       // MCL_NO_STALE_LAYOUT: every update makes its own layout first (rounds 1-3)
+    bool comm_no_pregather = false;     // MCL_COMM_NO_PREGATHER: mcl_comm_update gathers the lists when it starts, not when the previous one ends
+    bool comm_no_lists = false;         // MCL_COMM_NO_LISTS: mcl_comm_update takes the dense exchange on every update
+};
+
 struct mcl_engine {
     mcl_config_t cfg{};
     int num_cu = 256;
     hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;      // the per-update observation tables are built here, beside the resampling and ordering kernels
-    hipEvent_t ev_obs = nullptr;        // ... and the ray stage waits for this
-    bool obs_wait_pending = false;      // ... where its first kernel that reads them is launched (launch_rays)
-    hipEvent_t ev[EV_COUNT]{};
+    hipStream_t stream2 = nullptr;      // the per-update observation tables and the next layout are built here, beside the main stream's kernels
     std::string err;
-
-    // map
+    // ---- map
     bool have_map = false;
     int W = 0, H = 0, P = 0, Wp = 0, Hp = 0, Wps = 0, tw_cells = 0;
     double res = 0, ox = 0, oy = 0;
@@ -72,12 +117,15 @@ struct mcl_engine {
     DevBuf<uint8_t> d_dist;
     DevBuf<uint8_t> d_dist4;            // nibble-packed copy of d_dist (k_rays_skip's LDS window is a straight copy of it)
     DevBuf<uint8_t> d_distq[4];         // directional skip fields, one per quadrant (k_rays_quad / k_rays_far)
+    DevBuf<uint8_t> d_distw;            // kWedges wedge fields (k_rays_cell, k_rays_sweep's LDS windows), each Hp x Wps bytes
     DevBuf<float> d_L;                  // [r_obs][d]
     DevBuf<double> d_table;             // double table (product mode)
-
-    // beams
+    DevBuf<uint32_t> d_free;            // linear indices of free cells (data == 0), row-major, cpp:199-213
+    uint64_t n_free = 0; uint32_t init_idx = 0;
+    // ---- beams, and the tables of one scan
     int B = 0, bpad = 0;
     std::vector<float> angles;
+    std::vector<double2> beam_cs_host;  // (cos, sin) of every beam angle (set_beam_angles)
     DevBuf<float> d_angle;
     DevBuf<double2> d_beam_cs;
     DevBuf<double2> d_beam_csx;         // k_rays_sweep's copy with virtual beams either side (set_beam_angles)
@@ -86,74 +134,45 @@ struct mcl_engine {
     // (one entry per table column), cos / sin of the increment; rec_ok: the scan qualifies
     DevBuf<double2> d_beam_csi;
     DevBuf<double> d_beam_err;
-    double rec_c = 1.0, rec_s = 0.0;
-    bool rec_ok = false;
+    double rec_c = 1.0, rec_s = 0.0; bool rec_ok = false;
+    bool quad_ok = false;               // beam angles monotone over less than a full turn
     int beam_pad = 0, beam_margin = 0;
     DevBuf<int32_t> d_obs_idx;
     DevBuf<float> d_obs;
     HostBuf<float> h_obs;               // pinned staging for the per-update scan
-    DevBuf<uint32_t> d_free;            // linear indices of free cells (data == 0), row-major, cpp:199-213
-    uint64_t n_free = 0;
-    uint32_t init_idx = 0;
+    hipEvent_t ev_obs = nullptr;        // the tables below were built on stream2 (handoff.obs_wait: the ray stage has yet to wait for it)
     DevBuf<float> d_Lt;                 // [Lt | Lt with the rows reversed (k_rays_cell)]
     DevBuf<double> d_Ltd;               // k_rays_sweep's fp64 table (mcl_rays_sweep.h), built per update when that kernel runs
     int ltd_cols = 0;
     bool ltd_ready = false;             // d_Ltd holds the table of the observation in d_obs_idx (cleared when a new scan is staged)
-    bool sweep_layout_ok = false;       // k_rays_sweep's static LDS ends where its raw window offset (kQLdsBase) assumes
-    bool sweep_hyb_layout_ok = false;   // ... and of its hybrid form
-    int env_sweep_hybrid = 1;           // MCL_SWEEP_HYBRID=0: ranges beyond the window take the global-field form alone; 2: the hybrid also for a fresh / spread set
-    int env_sw_guide = 0;               // MCL_SW_GUIDE=<n>: the guide of k_sweep_plan's run lengths (default 2; 3 for the forms of ranges beyond the LDS window)
-    int hyb_backoff = 0, hyb_skip = 0;  // updates in the global-field form after a hybrid update that flagged many particles (sweep_hybrid_decide)
-    int last_sweep_global = 0, last_sweep_rec = 0, last_sweep_pairs = 0;    // the form of k_rays_sweep the last ray stage ran
-    int env_sweep_pairs = -1;           // MCL_SWEEP_PAIRS: -1 the engine decides, 0 / 1 forced (A/B measurements)
-    bool sweep_rec_layout_ok = false;   // the same for the <.., REC> instantiations (LDS form: window + offset table; global form: the table)
-    bool quad_layout_ok = false, cell_layout_ok = false;   // the same for k_rays_quad / k_rays_cell
-    bool skip_layout_ok = false;        // k_rays_skip has no static LDS (its window is addressed from LDS offset 0)
-    // k_rays_sweep on the wedge fields in GLOBAL memory (ranges a 256-cell LDS window cannot hold; MCL_SWEEP_GLOBAL=1 forces it)
-    DevBuf<uint8_t> d_distg;            // kWedges mirrored fields with a two-cell stop ring and a tail of stop rows each (k_ring_field)
-    int distg_pitch = 0;                // row pitch
-    size_t distg_stride = 0;            // bytes per field, tail included
-    const char *distg_why_not = nullptr;     // why the global-field form of k_rays_sweep is not available for this map, if it is not
-    bool sweep_global = false;          // this map takes the global-field variant (decided at mcl_set_map)
-    bool env_sweep_global = false;
-    int env_sw_split16 = -1;            // MCL_SW_SPLIT16=0/1 forces RayArgs::split16 (default: by size)
-    bool env_no_obs_overlap = false;    // MCL_NO_OBS_OVERLAP: the observation tables are built on the main stream, after the resampling kernel
-    bool env_no_prep_fold = false;      // MCL_NO_PREP_FOLD: k_prep_small stays a launch of its own
-    // the few words the ray stage wants cleared (k_prep_small's job): what the last windowed launch passed, so that the NEXT
-    // update's resampling kernel can do it (prep_folded: it did, with exactly prep_cache)
-    mcl::PrepClear prep_cache{};
-    bool prep_cache_valid = false, prep_folded = false;
-    int64_t prep_cache_n = 0;
-    bool max_partials_ready = false;    // k_combine_logw left the per-workgroup maxima of d_logw in d_part
-    DevBuf<int4> d_items;               // k_rays_sweep's work items (guided schedule), planned on the device every update
-    DevBuf<int4> d_centres;             // per run of units: window centre, first unit, units (k_sweep_plan)
-    DevBuf<int> d_nitems;               // number of work items (written by k_sweep_plan)
-    int64_t plan_n = 0;
-    DevBuf<double4> d_unit_sums;        // per unit of the sorted order: (sum px, sum py, count, -), bounding box
-    DevBuf<uint32_t> d_unit_begin;      // first slot of every unit + one (k_unit_table)
-    DevBuf<int> d_nunits;               // number of units of this update's sorted order
-    // environment knobs, read once at mcl_create (0 / negative = default)
-    int64_t env_cell_min = 0, env_cell_slice = 0;
-    int env_qslices_per_cu = 0, env_qside = 0, env_sweep_g = 0;
-    std::string env_debug_wg;
-
-    // particles
+    // ---- particle set
     int64_t cap = 0, N = 0;
     bool have_particles = false;
     DevBuf<double> d_x[2], d_y[2], d_th[2];
     int cur = 0;
-    DevBuf<double> d_w, d_logw, d_tmp;   // tmp: cap*3 doubles
+    DevBuf<double4> d_pack[2];          // (x, y, theta, -) records of buffer 0/1, written by k_resample_motion
+    bool pack_valid[2] = {false, false};
+    DevBuf<int32_t> d_idx;
+    DevBuf<double> d_inject;            // cap*4 (normals + uniforms)
+    DevBuf<double> d_tmp;               // cap*3 doubles
+    bool resampled_last = true;
+    bool far_fresh = true;              // no ray stage has seen the current particle set yet (set / initialised since the last one)
+    uint32_t update_idx = 0;
+    // ---- weights, CDF, compact list
+    DevBuf<double> d_w, d_logw;
+    DevBuf<double> d_logw_acc;          // the kernels with work lists accumulate here with atomics; k_combine_logw (legacy kernels: k_gather_logw) -> d_logw
     DevBuf<double> d_carry[2];          // logw - max of the last update (adaptive resampling: what a kept particle carries)
     int carry_idx = 0;                  // d_carry[carry_idx] is current; k_weights writes the other one
     bool carry_valid = false, carry_pending = false;
-    bool resampled_last = true;
-    // hipGraph of the update's tail (observation upload ... result read-back) for the k_rays_skip path, one per particle buffer
-    hipGraphExec_t graph_exec[2] = {nullptr, nullptr};
-    bool graph_warm = false;            // a regular update has run since the sizes / map / beams last changed
-    bool capturing = false;
-    DevBuf<double> d_logw_acc;          // k_rays_quad/far/fix accumulate here with atomics; k_gather_logw copies to d_logw
     DevBuf<uint64_t> d_q, d_cdf;
     DevBuf<uint64_t> d_blocktot;        // the scan's spine (reserve_scan_spine)
+    const uint64_t *blocktot_for = nullptr;   // which CDF array d_blocktot currently describes
+    int64_t blocktot_n = 0;
+    DevBuf<uint64_t> d_leaders;         // last CDF entry of every 16-entry group of the array d_blocktot describes
+    DevBuf<double> d_part;              // kRedBlocks * 8: per-workgroup partial sums (k_weights)
+    DevBuf<double> d_maxpart;           // kRedBlocks: per-workgroup maxima of d_logw (k_combine_logw / k_reduce_max)
+    bool max_partials_ready = false;    // k_combine_logw left the per-workgroup maxima of d_logw in d_maxpart
+    bool sums_pending = false;          // k_weights left partial sums that the next scan's spine turns into scalars[1..7]
     DevBuf<uint32_t> d_bm;              // mcl_stage_distinct_parents: bitmap over the global particle indices, its popcounts and their prefix
     DevBuf<uint64_t> d_bm_pop, d_bm_pref;
     // compact list of the particles with a non-zero fixed-point weight, written by the scan of d_q (mcl::CompactOut)
@@ -165,92 +184,85 @@ struct mcl_engine {
     int64_t compact_n = -1;             // entries of the list that describes d_cdf / the current particles; -1: none
     bool compact_pending = false;       // the last scan wrote a list; its length arrives with the next result read-back
     bool compact_used = false;          // the last resampling drew from a compact list
-    DevBuf<uint64_t> d_gcdf, d_gtop; // merged CDF of the shards' gathered lists (mcl_stage_resample_compact)
-    int env_no_compact = 0;
-    DevBuf<uint64_t> d_leaders;         // last CDF entry of every 16-entry group of the array d_blocktot describes
-    DevBuf<double4> d_pack[2];          // (x, y, theta, -) records of buffer 0/1, written by k_resample_motion
-    bool pack_valid[2] = {false, false};
-    DevBuf<int32_t> d_idx;
-    DevBuf<uint8_t> d_steps;
-    const uint64_t *blocktot_for = nullptr;   // which CDF array d_blocktot currently describes
-    int64_t blocktot_n = 0;
-    DevBuf<double> d_part;              // kRedBlocks * 8: per-workgroup partial sums (k_weights)
-    DevBuf<double> d_maxpart;           // kRedBlocks: per-workgroup maxima of d_logw (k_combine_logw / k_reduce_max)
-    bool sums_pending = false;          // k_weights left partial sums that the next scan's spine turns into scalars[1..7]
-    double *d_scalars = nullptr;        // 8 (a view into d_result, like the next two)
-    unsigned long long *d_counters = nullptr;  // 4
-    DevBuf<double> d_inject;            // cap*4 (normals + uniforms)
-    DevBuf<double4> d_pc;               // cap: per-particle constants for k_rays_skip / k_rays_quad
-    DevBuf<short4> d_qr;                // cap: per-particle quadrant ranges (k_rays_quad)
-    bool quad_ok = false;               // beam angles monotone over less than a full turn
-    int qside = 0;                      // k_rays_quad window side (0: not usable for this map)
-    DevBuf<unsigned long long> d_fix_list, d_fix_count;      // d_fix_count: 8 words (64 bytes) per segment
-    unsigned long long *d_fix_over = nullptr;
-    DevBuf<unsigned long long> d_exact_list;     // level-3 rays for k_rays_exact; its counter is word 14 of d_result
-    unsigned long long fix_cap = 0;
-    int fix_segments = 0;
-    DevBuf<uint8_t> d_far;              // cap * 4 flags
-    DevBuf<uint32_t> d_far_list;        // k_rays_sweep: slots with a flagged quadrant (cap entries, allocated on first use)
-    DevBuf<uint32_t> d_far_sorted, d_far_cnt;   // the same in ascending order (k_far_*), per-2048-slot counts
-    // cell sort for k_rays_cell
+    unsigned long long list_epoch = 0;  // counts the rewrites of the compact list (a gathered copy of an older one is stale)
+    DevBuf<uint64_t> d_gcdf, d_gtop;    // merged CDF of the shards' gathered lists (mcl_stage_resample_compact)
+    // ---- ordering (k_rays_cell, k_rays_sweep: the particles by tile, cell and heading)
     DevBuf<double4> d_pcs;              // cap: pc in sorted order
     DevBuf<double> d_ths;               // cap: heading in sorted order
-    DevBuf<uint8_t> d_distw;            // kWedges wedge fields for k_rays_cell, each Hp x Wps bytes
     DevBuf<uint32_t> d_perm, d_skey, d_srank;   // cap each
-    DevBuf<uint32_t> d_skey2, d_sval2;   // MCL_SORT=radix: sorted keys / indices
+    DevBuf<uint32_t> d_skey2, d_sval2;  // MCL_SORT=radix: sorted keys / indices
     DevBuf<uint8_t> d_sort_tmp;         // rocPRIM's scratch, in bytes
-    int env_sort_radix = -1;           // MCL_SORT=radix / hist forces one ordering path; default: by size
     DevBuf<uint32_t> d_tile_used;       // one mark per kHistTile buckets of the sort histogram: touched by this update's sort
     DevBuf<uint32_t> d_hist, d_histpart;                   // kSortBuckets, kSortBuckets / kHistTile
     DevBuf<int> d_bbox;                 // 7: bounding box, occupied tiles, numbering in use, window play
     DevBuf<uint32_t> d_cut_start, d_cut_end;   // kSwMaxCuts each: where the buckets of a sparse set start / end in the radix-sorted order (zero between sorts)
-    bool env_no_bucket_cuts = false;    // MCL_NO_BUCKET_CUTS: units on the plain grid of 1024 slots, sparse sets ordered by whole tiles (rounds 2-3 before the cuts)
-    DevBuf<int> d_tilemap, d_tilemark;   // kSortMaxTiles each: tile of the map -> compact id; marks of the occupied tiles (zero between sorts)
-    // The ordering layout (bounding box, occupied tiles) of an update's children is made on the second stream right after the
-    // resampling kernel and used by the NEXT update, whose resampling kernel then writes the sort keys itself: d_bbox / d_tilemap are
-    // the layout in use, *_nx the one being made; swapped at the end of an update.  layout_valid: d_bbox describes the previous
-    // update's children of this configuration (cleared by graph_reset: map, beams, particles set from outside).
-    DevBuf<int> d_bbox_nx, d_tilemap_nx, d_tilemark_nx;
-    hipEvent_t ev_children = nullptr, ev_layout = nullptr;
+    DevBuf<int> d_tilemap, d_tilemark;  // kSortMaxTiles each: tile of the map -> compact id; marks of the occupied tiles (zero between sorts)
+    DevBuf<double2> d_slice_mean;       // one per slice of the sorted order
+    DevBuf<double4> d_unit_sums;        // per unit of the sorted order: (sum px, sum py, count, -), bounding box
+    DevBuf<uint32_t> d_unit_begin;      // first slot of every unit + one (k_unit_table)
+    DevBuf<int> d_nunits;               // number of units of this update's sorted order
+    // ---- ray-stage work lists
+    DevBuf<double4> d_pc;               // cap: per-particle constants of every ray kernel but the literal march (k_particle_prep, or the resampling kernel)
+    DevBuf<short4> d_qr;                // cap: per-particle quadrant ranges (k_rays_quad)
+    DevBuf<uint8_t> d_steps;
+    DevBuf<unsigned long long> d_fix_list, d_fix_count;      // d_fix_count: 8 words (64 bytes) per segment
+    unsigned long long *d_fix_over = nullptr;
+    DevBuf<unsigned long long> d_exact_list;     // level-3 rays for k_rays_exact; its counter is word 14 of d_result
+    unsigned long long fix_cap = 0; int fix_segments = 0;
+    DevBuf<uint8_t> d_far;              // cap * 4 flags
+    DevBuf<uint32_t> d_far_list;        // k_rays_sweep: slots with a flagged quadrant (cap entries, allocated on first use)
+    DevBuf<uint32_t> d_far_sorted, d_far_cnt;   // the same in ascending order (k_far_*), per-2048-slot counts
+    DevBuf<int4> d_items;               // k_rays_sweep's work items (guided schedule), planned on the device every update
+    DevBuf<int4> d_centres;             // per run of units: window centre, first unit, units (k_sweep_plan)
+    DevBuf<int> d_nitems;               // number of work items (written by k_sweep_plan)
+    int64_t plan_n = 0;
+    int reserved_cus = 0;               // CUs the persistent grids leave free (for RCCL kernels running beside them)
+    // ---- which ray kernel, which form of k_rays_sweep, and its fields in global memory
+    bool sweep_layout_ok = false;       // k_rays_sweep's static LDS ends where its raw window offset (kQLdsBase) assumes
+    bool sweep_hyb_layout_ok = false;   // ... and of its hybrid form
+    bool sweep_rec_layout_ok = false;   // the same for the <.., REC> instantiations (LDS form: window + offset table; global form: the table)
+    bool quad_layout_ok = false, cell_layout_ok = false;   // the same for k_rays_quad / k_rays_cell
+    bool skip_layout_ok = false;        // k_rays_skip has no static LDS (its window is addressed from LDS offset 0)
+    int qside = 0;                      // k_rays_quad window side (0: not usable for this map)
+    // k_rays_sweep on the wedge fields in GLOBAL memory (ranges a 256-cell LDS window cannot hold; MCL_SWEEP_GLOBAL=1 forces it)
+    DevBuf<uint8_t> d_distg;            // kWedges mirrored fields with a two-cell stop ring and a tail of stop rows each (k_ring_field)
+    int distg_pitch = 0;                // row pitch
+    size_t distg_stride = 0;            // bytes per field, tail included
+    const char *distg_why_not = nullptr;     // why the global-field form of k_rays_sweep is not available for this map, if it is not
+    bool sweep_global = false;          // this map takes the global-field variant (decided at mcl_set_map)
+    int hyb_backoff = 0, hyb_skip = 0;  // updates in the global-field form after a hybrid update that flagged many particles (sweep_hybrid_decide)
+    int last_sweep_global = 0, last_sweep_rec = 0, last_sweep_pairs = 0;    // the form of k_rays_sweep the last ray stage ran
+    bool last_work_lists = false;       // the last ray stage ran a kernel with fix-up lists (quad, cell, sweep): fix_lists_overflowed
+    int last_mode = 0;                  // the MCL_RAYS_* enumerator of the kernel the last ray stage ran (0: none yet)
+    // ---- hand-offs between the pieces of an update, and what outlives one
+    RayHandoff handoff;
+    // the few words the ray stage wants cleared (k_prep_small's job): what the last windowed launch passed, so that the NEXT
+    // update's resampling kernel can do it (handoff.folded).  A cache across updates, not a hand-off: dropped by graph_reset alone.
+    mcl::PrepClear prep_cache{};
+    bool prep_cache_valid = false; int64_t prep_cache_n = 0;
+    hipEvent_t ev[EV_COUNT]{};
+    StageEvents stage_ev;
+    NextLayout layout;
+    // hipGraph of the update's tail (observation upload ... result read-back) for the k_rays_skip path, one per particle buffer
+    hipGraphExec_t graph_exec[2] = {nullptr, nullptr};
+    bool graph_warm = false;            // a regular update has run since the sizes / map / beams last changed
+    bool capturing = false;
     hipEvent_t ev_ext_in = nullptr, ev_ext_out = nullptr;   // ordering against a caller's stream (mcl_stream_wait_external / mcl_external_wait_stream)
     bool stage_async_rays = false, stage_async_weights = false;
     bool stage_kept = false;            // the staged flow's last children are the previous particles themselves (mcl_stage_keep)
-    struct mcl_comm *comm = nullptr;    // RCCL communicator of a sharded set (mcl_comm_create), or null
-    unsigned long long list_epoch = 0;  // counts the rewrites of the compact list (a gathered copy of an older one is stale)
-    bool layout_valid = false, layout_pending = false;
-    int64_t layout_n = 0;
-    // Stage events BOUND TO DISPATCHES: the stop event of hipExtLaunchKernelGGL costs nothing, a hipEventRecord between two kernels
-    // of a stream ~3 us of pipeline (tools/ubench/event_cost.hip; elapsed times across different launches are valid).  Set by the
-    // launch that bound the event, cleared by the code that would otherwise record it.
-    bool ev_resample_bound = false, ev_rays_bound = false, ev_sensor_bound = false, ev_query_skipped = false;
-    bool bind_sensor_event = false;     // the next scan of the engine's own weights binds EV_SENSOR to its last kernel
-    bool layout_wanted = false;         // the resampling kernel left children to make the next layout of (layout_mark -> next_layout_launch)
-    bool layout_stale_used = false;     // this update orders by the previous update's layout (do_update -> launch_rays)
-    bool keys_done = false;             // ... and its resampling kernel wrote the (key, index) pairs
-    bool env_no_stale_layout = false;   // MCL_NO_STALE_LAYOUT: every update makes its own layout first (rounds 1-3)
-    bool env_comm_no_lists = false;     // MCL_COMM_NO_LISTS: mcl_comm_update takes the dense exchange on every update
-    bool env_comm_no_pregather = false; // MCL_COMM_NO_PREGATHER: mcl_comm_update gathers the lists when it starts, not when the previous one ends
-    mcl::PrepClear prep_passed{};       // what the resampling kernel was given to clear (prep_folded)
-    DevBuf<double2> d_slice_mean;       // one per slice of the sorted order
-    bool last_work_lists = false;       // the last ray stage ran a kernel with fix-up lists (quad, cell, sweep): fix_lists_overflowed
-    int last_mode = 0;                  // the MCL_RAYS_* enumerator of the kernel the last ray stage ran (0: none yet)
-    unsigned long long result_seq = 0;  // stamps the result block a small update writes to pinned memory (h_result[kResultStamp])
-    int env_tiny_poll = 1;
-    bool far_fresh = true;              // no ray stage has seen the current particle set yet (set / initialised since the last one)
-    bool pc_ready = false;              // d_pc already holds the constants of the current particles (written by k_resample_motion)
-    int reserved_cus = 0;               // CUs k_rays_quad's persistent grid leaves free (for RCCL kernels running beside it)
-    DevBuf<unsigned long long> d_result;      // [0..7] scalars, [8..11] counters, [12..13] overflow flag + work counter: one D2H copy
+    // ---- results and timings
+    DevBuf<unsigned long long> d_result;      // the words of the constant block above (kResultWords): one D2H copy
     HostBuf<unsigned long long> h_result;     // pinned mirror of d_result
-    double h_scalars[8]{};
-    uint64_t q_total = 0;
+    double *d_scalars = nullptr;        // 8 (a view into d_result, like the next one and d_fix_over)
+    unsigned long long *d_counters = nullptr;  // 4
+    unsigned long long result_seq = 0;  // stamps the result block a small update writes to pinned memory (h_result[kResultStamp])
+    double h_scalars[8]{}; uint64_t q_total = 0;
     double global_sums[5]{};            // sum w, wx, wy, wsin, wcos actually used for outputs
     bool have_idx = false, have_steps = false, have_logw = false;
-    uint32_t update_idx = 0;
-    double timings[6]{};
-    double ray_ms = 0;
+    double timings[6]{}, ray_ms = 0;
     bool ray_ms_is_graph_tail = false;  // ray_ms is the whole captured tail of a small update, not one kernel
-    unsigned long long h_counters[4]{};
-    unsigned long long h_fix_count = 0;
+    unsigned long long h_counters[4]{}, h_fix_count = 0;
+    // ---- options
     // KLD-adaptive particle count (mcl_set_kld): the resampling kernel marks the bin of every drawn parent in
     // d_kld_bm and lists the words of new bins in d_kld_list; the counter of update t is d_kld_cnt[kld_parity], the clearing
     // kernel of that update zeroes the other one
@@ -277,10 +289,8 @@ struct mcl_engine {
     // components (0: none -- the free cells), as uploaded (thresholds, 9 doubles per component) and the host's copy of both for
     // the getter.  Allocated by the first call that sets one.
     int32_t mix_n = 0;
-    std::vector<uint64_t> mix_thr;
-    std::vector<double> mix_fac;
-    DevBuf<uint64_t> d_mix_thr;
-    DevBuf<double> d_mix_fac;
+    std::vector<uint64_t> mix_thr; std::vector<double> mix_fac;
+    DevBuf<uint64_t> d_mix_thr; DevBuf<double> d_mix_fac;
     // likelihood-field sensor model (mcl_set_likelihood_field): the field and table of the current map (lf_K < 0:
     // not built), the used beams of an update's scan staged in pinned memory; last_lf: the last log-weights came from k_lfield
     bool lf_on = false, last_lf = false;
@@ -292,10 +302,11 @@ struct mcl_engine {
     std::vector<float> lf_tab;
     DevBuf<double2> d_lf_beams;
     HostBuf<double2> h_lf_beams;
-    std::vector<double2> beam_cs_host;  // (cos, sin) of every beam angle (set_beam_angles)
     // motion model (mcl_set_motion_model): REFERENCE, or an odometry model whose per-update scalars go to the
     // k_resample_odo* kernels as plain arguments
     mcl_motion_config_t motion{};
+    // ---- side-call owners (released by mcl_destroy before the engine's own buffers, the streams idle)
+    struct mcl_comm *comm = nullptr;    // RCCL communicator of a sharded set (mcl_comm_create), or null
     // pose clustering (mcl_pose_clusters): its own buffers, allocated on the first call; set_epoch counts the
     // changes of the particle set or its weights (the labels of a clustering are valid while it is unchanged)
     struct mcl_cluster *clu = nullptr;
@@ -310,6 +321,8 @@ struct mcl_engine {
     unsigned long long map_epoch = 0;
     // pose refinement (mcl_refine_poses): its own buffers, allocated on the first call
     struct mcl_refine *rfn = nullptr;
+    // ---- knobs
+    EnvKnobs env;
 };
 
 #define HIPCHK(h, call)                                                                          \
@@ -353,7 +366,8 @@ float elapsed(hipEvent_t a, hipEvent_t b);
 void graph_reset(mcl_engine *h);
 // room in d_blocktot for the scan of n entries (scan_weights); a spine that moves drops the captured graphs and the layout
 int reserve_scan_spine(mcl_engine *h, int64_t n);
-int scan_weights(mcl_engine *h, const uint64_t *d_q, uint64_t *d_cdf, int64_t n, uint64_t offset, uint64_t *d_total);
+// bind_sensor: this is the last kernel of its stage; set where EV_SENSOR became the stop event of the scan's last kernel (the engine's own weights, no capture)
+int scan_weights(mcl_engine *h, const uint64_t *d_q, uint64_t *d_cdf, int64_t n, uint64_t offset, uint64_t *d_total, bool *bind_sensor = nullptr);
 void unpack_result(mcl_engine *h);
 int layout_adopt(mcl_engine *h, int64_t n);
 int set_particles_impl(mcl_engine_t *h, const double *xyz, const double *weights, int64_t n, const double *weight_scale);

@@ -58,6 +58,8 @@ SCENARIOS = [
     S("count_global", SWEEP, (1, 1, 1), ray_kernel=5, debug_count_probes=1, env={"MCL_SWEEP_GLOBAL": "1", "MCL_SWEEP_HYBRID": "0"}),
     S("count_skip", SKIP, n=1500, ray_kernel=2, debug_count_probes=1),
     S("stage_rays", SWEEP, (0, 1, 1), call="stage_rays", ray_kernel=5),
+    # two shards on one device: the staged resample (stage_resample_launch) meets no layout / the stale layout / + the prep fold
+    S("group_staged", SWEEP, (0, 1, 0), call="group", updates=3, ray_kernel=5),
     S("legacy_quad", QUAD, ray_kernel=3),
     S("legacy_cell", CELL, n=1500, updates=2, ray_kernel=4),
 ]
@@ -94,6 +96,9 @@ def run(engine_mod, orc, sc):
     saved = {k: os.environ.get(k) for k in sc["env"]}
     os.environ.update(sc["env"])                                  # (read at mcl_create)
     try:
+        if sc["call"] == "group":
+            return run_group(engine_mod.Group([0, 0], max_particles=sc["n"] // 2, seed=11, max_range_m=sc["max_range_m"], **sc["cfg"]),
+                             sc, g, om, ang, scan, p)
         e = engine_mod.Engine(max_particles=sc["n"], seed=11, max_range_m=sc["max_range_m"], **sc["cfg"])
     finally:
         for k, v in saved.items():
@@ -110,6 +115,24 @@ def run(engine_mod, orc, sc):
                     steps=e.ray_steps() if sc["cfg"].get("keep_ray_steps") else None, om=om, ang=ang, scan=scan)
     finally:
         e.close()
+
+
+def run_group(grp, sc, g, om, ang, scan, p):
+    """The same on a two-shard group of one device (sc["n"] particles in all): kernel and variant of the last shard's engine, particles
+    and log-weights of the shards one behind the other"""
+    try:
+        grp.set_map(g.data, g.resolution, g.origin_x, g.origin_y)
+        grp.set_beam_angles(ang)
+        grp.set_particles(p, np.full(sc["n"], 1.0 / sc["n"]))
+        for _ in range(sc["updates"]):
+            grp.update(ACTION, scan)
+        e = grp.engine(grp.size - 1)
+        v = e.ray_kernel_variant()
+        return dict(kernel=e.ray_kernel_name(), variant=(2 if v["hybrid"] else int(v["global_fields"]), int(v["turned_directions"]), int(v["pairs"])),
+                    particles=grp.get_particles(), logw=np.concatenate([grp.engine(i).log_weights() for i in range(grp.size)]),
+                    idx=None, steps=None, om=om, ang=ang, scan=scan)
+    finally:
+        grp.close()
 
 
 def launches(path):
