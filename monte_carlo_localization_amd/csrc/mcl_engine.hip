@@ -308,7 +308,17 @@ void plan_work_lists(const mcl_engine *h, int64_t n, RayPlan &p)
     // (both forms of k_rays_sweep work with 32 fractional bits: a walk of ~70 rays is handed over once in several thousand)
     const unsigned long long rays_per_seg = (unsigned long long)n * h->B / p.nseg + 64, seg_div = 256;
     p.segcap = std::max<unsigned long long>(2048, (rays_per_seg / seg_div + 7) & ~7ull);
-    if ((unsigned long long)n * h->B <= (4ull << 20)) p.segcap = (2 * rays_per_seg + 7) & ~7ull;   // small launch: room for every ray
+    // small launch: room for every ray.  A segment may serve a single (units, wedge) item there, and twice the even share covers a
+    // scan of a quarter turn and more (a Hokuyo puts 91 of its 1081 beams into one wedge: 1.35 sixteenths); a 45-degree scan puts
+    // half its beams into one wedge, so k_rays_sweep's share follows the scan (wedge_beams_max), within the 64 MB the factor 2
+    // takes at 4M rays
+    unsigned long long share = 2;
+    if (p.sweep && h->B > 0) {
+        const unsigned long long rays = std::max<unsigned long long>(1, (unsigned long long)n * h->B);
+        const unsigned long long by_scan = ((unsigned long long)h->wedge_beams_max * p.items_per_slice + h->B - 1) / h->B;
+        share = std::max<unsigned long long>(2, std::min<unsigned long long>(by_scan, (8ull << 20) / rays));
+    }
+    if ((unsigned long long)n * h->B <= (4ull << 20)) p.segcap = (share * rays_per_seg + 7) & ~7ull;
     // k_rays_far is bound by global-memory latency: 4 workgroups per CU worth of blocks (2 resident at a time)
     p.gfar = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4 * (int64_t)h->num_cu, (n + 15) / 16));
     p.fix_split = std::max(1, std::min(16, (8 * h->num_cu) / std::max(p.nseg, 1)));   // ~8 workgroups of k_rays_fix per CU (2 .. 16 per segment: no difference, round 4)
@@ -647,7 +657,12 @@ int launch_rays(mcl_engine *h, const double *x, const double *y, const double *t
     h->last_lf = false;
     h->max_partials_ready = false;
     const RayPlan p = plan_rays(h, n, force_skip, direct_table);
-    if (p.mode == 0) return fail(h, MCL_ERR_UNSUPPORTED, "MCL_RAYS_QUAD / MCL_RAYS_CELL / MCL_RAYS_SWEEP not usable with this map / beam set");
+    if (p.mode == 0) {
+        // (the sentence mcl_get_planned_ray_kernel gives for the same configuration: an error that says what to change)
+        const char *why = "";
+        choose_ray_mode(h, n, force_skip, &why);
+        return fail(h, MCL_ERR_UNSUPPORTED, std::string("MCL_RAYS_QUAD / MCL_RAYS_CELL / MCL_RAYS_SWEEP not usable with this map / beam set: ") + why);
+    }
     DevBuf<unsigned long long> d_dbg;
     if (p.lists) MCL_TRY(ray_fix_lists(h, p, a));
     ray_prep(h, p, a);
@@ -1379,8 +1394,10 @@ int mcl_set_beam_angles(mcl_engine_t *h, const float *angles, int32_t n_beams)
     if (h->quad_ok && !((double)angles[n_beams - 1] - (double)angles[0] < 2.0 * M_PI - 1e-3)) h->quad_ok = false;
     h->angles.assign(angles, angles + n_beams);
     // padded so that k_rays_skip never clamps its beam index, with at least one entry after the last beam: k_rays_sweep's
-    // beam walk requests the NEXT beam's direction on every trip, the last one included
-    const int ncs = (n_beams + 1 + 255) & ~255;
+    // beam walk requests the NEXT beam's direction on every trip, the last one included.  A multiple of 768 = lcm(256, 192):
+    // k_rays_skip<R> reads whole groups of 64 R entries, and with three rays per lane a group is 192 of them (2701 beams: 2880
+    // entries read, where a multiple of 256 gave 2816)
+    const int ncs = (n_beams + 1 + 767) / 768 * 768;
     std::vector<double2> cs(ncs);
     for (int j = 0; j < ncs; ++j) {
         double a = (double)angles[j < n_beams ? j : n_beams - 1];   // cpp:533 widens the float angle
@@ -1394,6 +1411,18 @@ int mcl_set_beam_angles(mcl_engine_t *h, const float *angles, int32_t n_beams)
     const double span = n_beams > 1 ? (double)angles[n_beams - 1] - (double)angles[0] : 0.0;
     const double inc = n_beams > 1 ? span / (double)(n_beams - 1) : 0.0;
     const double wedge = 2.0 * M_PI / (double)mcl::kWedges;
+    // the most beams one direction wedge holds, wherever a heading puts it: a closed interval of 2 pi / 16 of beam angle, around
+    // the turn (what one work item of k_rays_sweep can hand to its fix-up list segment per particle: plan_work_lists)
+    h->wedge_beams_max = n_beams;
+    if (h->quad_ok) {
+        const auto turned = [&](int k) { return (double)angles[k % n_beams] + (k >= n_beams ? 2.0 * M_PI : 0.0); };
+        int most = 1;
+        for (int i = 0, j = 0; j < 2 * n_beams; ++j) {
+            while (turned(j) - turned(i) > wedge + 1e-9) ++i;
+            most = std::max(most, std::min(j - i + 1, (int)n_beams));
+        }
+        h->wedge_beams_max = most;
+    }
     if (h->quad_ok && inc > 0.0 && span + wedge < 2.0 * M_PI - 1e-3 && !getenv("MCL_NO_BEAM_PAD")) {
         bool regular = true;
         for (int j = 0; j < n_beams && regular; ++j)

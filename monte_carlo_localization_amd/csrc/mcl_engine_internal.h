@@ -137,6 +137,7 @@ struct mcl_engine {
     double rec_c = 1.0, rec_s = 0.0; bool rec_ok = false;
     bool quad_ok = false;               // beam angles monotone over less than a full turn
     int beam_pad = 0, beam_margin = 0;
+    int wedge_beams_max = 0;            // the most beams a direction wedge of 2 pi / 16 holds (mcl_set_beam_angles)
     DevBuf<int32_t> d_obs_idx;
     DevBuf<float> d_obs;
     HostBuf<float> h_obs;               // pinned staging for the per-update scan

@@ -22,6 +22,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import scan_geometries as scg                                     # noqa: E402
 import side_geometries as sg                                      # noqa: E402
 
 SWEEP, SKIP, MARCH, QUAD, CELL = "k_rays_sweep", "k_rays_skip", "k_rays_march", "k_rays_quad", "k_rays_cell"
@@ -44,6 +45,10 @@ SCENARIOS = [
     S("sweep_pairs", SWEEP, (0, 1, 1), ray_kernel=5),                            # first update of a fresh set: PAIRS + the windowed far pass
     S("sweep_rec", SWEEP, (0, 1, 0), updates=2, ray_kernel=5),
     S("sweep_fetched", SWEEP, (0, 0, 0), n=1500, beams="jitter", updates=2, ray_kernel=5),
+    # members of tests/scan_geometries.py by name: 45 degrees of scan (thirteen of a lane's sixteen wedges hold no beam), and 1600 beams with
+    # virtual beams whose 1920 table columns leave REC no room in LDS (fetched directions)
+    S("sweep_narrow", SWEEP, (0, 1, 1), beams="narrow_rear", ray_kernel=5),
+    S("sweep_fetched_padded", SWEEP, (0, 0, 0), n=1500, beams="rec1600", ray_kernel=5),
     S("sweep_global_rec", SWEEP, (1, 1, 1), ray_kernel=5, env={"MCL_SWEEP_GLOBAL": "1", "MCL_SWEEP_HYBRID": "0"}),
     S("sweep_global_fetched", SWEEP, (1, 0, 0), n=1500, beams="jitter", ray_kernel=5, env={"MCL_SWEEP_GLOBAL": "1", "MCL_SWEEP_HYBRID": "0"}),
     S("sweep_hybrid", SWEEP, (2, 1, 0), updates=2, max_range_m=13.0, ray_kernel=5, env={"MCL_SWEEP_HYBRID": "2"}),
@@ -80,7 +85,9 @@ def inputs(orc, sc):
     g = sg.small()
     om = orc.OracleMap(g.data, g.resolution, g.origin_x, g.origin_y, max_range_m=sc["max_range_m"])
     rng = np.random.default_rng(5)
-    if sc["beams"] == "even":
+    if sc["beams"] in scg.NAMES:
+        ang = scg.family()[sc["beams"]].copy()
+    elif sc["beams"] == "even":
         ang = (-0.75 * np.pi + np.arange(181) * (1.5 * np.pi / 180)).astype(np.float32)
     else:
         ang = np.sort(-0.75 * np.pi + (np.arange(61) + rng.uniform(-0.4, 0.4, 61)) * (1.5 * np.pi / 60)).astype(np.float32)
