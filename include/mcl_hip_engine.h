@@ -163,7 +163,7 @@ int mcl_get_particles(mcl_engine_t *h, double *xyz_colmajor, int64_t n);
 int mcl_get_weights(mcl_engine_t *h, double *weights, int64_t n);
 /* visualize()'s weighted sample of k rows (cpp:949-956): k draws from the current weights.
  * uniforms: k doubles in [0,1) (e.g. from the host's rng_) or NULL for Philox draws.
- * out: k x 3 column-major. */
+ * out: k x 3 column-major.  1 <= k <= 65536, whatever the engine's max_particles (k may exceed it). */
 int mcl_sample_particles(mcl_engine_t *h, int32_t k, const double *uniforms, double *out_colmajor);
 /* get_current_pose()'s particles_.colwise().mean() (cpp:903-908). */
 int mcl_particle_mean(mcl_engine_t *h, double out[3]);

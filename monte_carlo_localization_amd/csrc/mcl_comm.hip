@@ -351,7 +351,7 @@ static int comm_gather_lists(mcl_engine_t *h, const int64_t *counts, CommLocal &
     const int G = c->n_ranks;
     int64_t longest = 0, listed = 0;
     for (int r = 0; r < G; ++r) { longest = std::max(longest, counts[r]); listed += counts[r]; }
-    const int64_t entries = std::max<int64_t>(64, (longest + 63) & ~(int64_t)63);
+    const int64_t entries = compact_chunk_entries(longest);
     c->gathered = false;
     if ((size_t)entries * kCompactEntryBytes * (size_t)G > c->d_chunk_all.cap) {       // (reserved last: it stands for both)
         // (without buffers of the agreed size this rank cannot take part in the all-gather: a hard failure)

@@ -1620,8 +1620,13 @@ int mcl_sample_particles(mcl_engine_t *h, int32_t k, const double *uniforms, dou
     if (!h->have_particles) return MCL_ERR_NOT_READY;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     double *d_u = nullptr;
+    // the rows and the uniforms share d_tmp (3 cap doubles from mcl_create): a draw of more than three quarters of the engine's
+    // capacity -- any draw at all from an engine of one particle -- grows it (no graph holds this pointer; the stream is idle first)
+    if ((size_t)k * 4 > h->d_tmp.cap) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        MCL_TRY(h->d_tmp.reserve(h, (size_t)k * 4));
+    }
     double *d_out = h->d_tmp;
-    if ((int64_t)k * 4 > h->cap * 3) return fail(h, MCL_ERR_INVALID_ARG, "k too large for this engine");
     if (uniforms) {
         d_u = h->d_tmp + (size_t)3 * k;
         HIPCHK(h, hipMemcpyAsync(d_u, uniforms, (size_t)k * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -2806,13 +2811,6 @@ int mcl_stage_motion_records(mcl_engine_t *h, const void *d_records, int64_t n_r
 }
 
 // ---- sharded sets: the shards exchange their compact lists instead of every weight --------------------------------
-int mcl_compact_chunk_bytes(int64_t chunk_entries, int64_t *bytes)
-{
-    if (!bytes || chunk_entries <= 0 || (chunk_entries & 63)) return MCL_ERR_INVALID_ARG;
-    *bytes = chunk_entries * kCompactEntryBytes;
-    return MCL_OK;
-}
-
 int mcl_host::export_compact_launch(mcl_engine_t *h, void *d_chunk, int64_t chunk_entries, int dst_device, hipStream_t stream)
 {
     if (!h || !d_chunk || chunk_entries <= 0 || (chunk_entries & 63)) return MCL_ERR_INVALID_ARG;

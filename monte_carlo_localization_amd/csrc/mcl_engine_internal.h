@@ -38,9 +38,6 @@ constexpr unsigned long long kExactCap = 1ull << 16;   // level-3 rays per launc
 constexpr int kResultWords = 18;
 constexpr int kResultStage = 40;             // h_result word that stages a host value on its way to the device
 constexpr int kResultStamp = 32;             // h_result word a small update's last kernel stamps (the host polls it)
-// An entry of a compact list as the shards exchange it (mcl_export_compact): [ccdf: 8 | crec: 32 | cidx: 4] bytes,
-// stored column by column in a chunk of chunk_entries entries (the ccdf column, then the crec column, then the cidx column)
-constexpr int kCompactEntryBytes = 44;
 
 struct mcl_comm;
 void comm_free(struct mcl_comm *c);        // mcl_comm.hip
@@ -155,7 +152,7 @@ struct mcl_engine {
     bool pack_valid[2] = {false, false};
     DevBuf<int32_t> d_idx;
     DevBuf<double> d_inject;            // cap*4 (normals + uniforms)
-    DevBuf<double> d_tmp;               // cap*3 doubles
+    DevBuf<double> d_tmp;               // cap*3 doubles; 4 k after an mcl_sample_particles of more than 3/4 cap rows
     bool resampled_last = true;
     bool far_fresh = true;              // no ray stage has seen the current particle set yet (set / initialised since the last one)
     uint32_t update_idx = 0;

@@ -267,7 +267,7 @@ int mcl_group_update(mcl_group_t *g, const double action[3], const float *obs, i
     bool compact = g->q_total != 0 && !keep;
     int64_t longest = 0;
     for (int s = 0; s < G; ++s) { compact = compact && g->eng[s]->compact_n >= 0; longest = std::max(longest, g->eng[s]->compact_n); }
-    const int64_t centries = std::max<int64_t>(64, (longest + 63) & ~(int64_t)63);
+    const int64_t centries = compact_chunk_entries(longest);
     for (int s = 0; s < G; ++s) {
         mcl_engine *e = g->eng[s];
         GHIP(g, hipSetDevice(e->cfg.device));

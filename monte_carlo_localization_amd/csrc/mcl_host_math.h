@@ -7,6 +7,10 @@
 #include <vector>
 #include "mcl_types.h"
 
+// An entry of a compact list as the shards exchange it (mcl_export_compact): [ccdf: 8 | crec: 32 | cidx: 4] bytes,
+// stored column by column in a chunk of chunk_entries entries (the ccdf column, then the crec column, then the cidx column)
+constexpr int kCompactEntryBytes = 44;
+
 namespace mcl_host {
 const char *bad_sensor_fields(const mcl_config_t &c);
 void build_sensor_table(const mcl_config_t &c, int P, std::vector<double> &t);
@@ -18,6 +22,8 @@ const char *kld_invalid(const mcl_kld_config_t *k, int64_t cap);
 bool kld_grid(const mcl_kld_config_t *k, uint32_t W, uint32_t H, float res, int64_t &nx, int64_t &ny, uint64_t &bits);
 mcl::KldArgs kld_args_of(const mcl_kld_config_t *k, int64_t nx, int64_t ny, double ox, double oy);
 int64_t kld_target(const mcl_kld_config_t *k, int64_t bins, int64_t n_current);
+// the chunk of a list exchange (device group, communicator): room for the longest list in whole groups of 64 entries, at least one
+int64_t compact_chunk_entries(int64_t longest);
 const char *recov_invalid(const mcl_recovery_config_t *c);
 double recov_likelihood(const mcl_recovery_config_t &c, double max_logw, double sum_w, double denom, int n_beams);
 void recov_fold(const mcl_recovery_config_t &c, double &S, double &F, double l);

@@ -286,6 +286,11 @@ int64_t kld_target(const mcl_kld_config_t *k, int64_t bins, int64_t n_current)
     return target;
 }
 
+int64_t compact_chunk_entries(int64_t longest)
+{
+    return std::max<int64_t>(64, (longest + 63) & ~(int64_t)63);
+}
+
 // ---- recovery by random-particle injection (mcl_set_recovery): host double throughout
 const char *recov_invalid(const mcl_recovery_config_t *c)
 {
@@ -892,6 +897,13 @@ int mcl_host_kld_target(const mcl_kld_config_t *k, int64_t bins, int64_t n_curre
 {
     if (!k || !n_next || n_current < 0 || n_current >= MCL_MAX_TOTAL_PARTICLES || kld_invalid(k, 0)) return MCL_ERR_INVALID_ARG;
     *n_next = kld_target(k, bins, n_current);
+    return MCL_OK;
+}
+
+int mcl_compact_chunk_bytes(int64_t chunk_entries, int64_t *bytes)
+{
+    if (!bytes || chunk_entries <= 0 || (chunk_entries & 63)) return MCL_ERR_INVALID_ARG;
+    *bytes = chunk_entries * kCompactEntryBytes;
     return MCL_OK;
 }
 
