@@ -1019,6 +1019,29 @@ int mcl_host_sweep_global_layout(uint32_t width, uint32_t height, int32_t max_ra
 int mcl_get_wedge_fields(mcl_engine_t *h, uint8_t *out, size_t n, int32_t dims[3]);
 int mcl_get_ring_fields(mcl_engine_t *h, uint8_t *out, size_t n);
 int mcl_get_sweep_table(mcl_engine_t *h, double *out, size_t n, int32_t dims[3]);
+/* ---- the order the ray stage worked in (for tests and tools: tests/test_gpu_sort_fine.py, tools/order_trip_sim.py).
+ * The key the particles are ordered by, computed on the host by the code the device runs (csrc/mcl_sort_key.h):
+ *   coarse (22 bits: tile, cell, half cell, heading bin -- what units, cuts and windows are made from) << fine | fine bits,
+ *   fine in 0 .. 10: fs = max(fine - 2, 0) / 4 further sub-cell bits per axis (y above x), then ft = fine - 2 fs further heading
+ *   bits; all zero for a particle whose cell lies outside the box, whose position or heading is not finite, or whose heading
+ *   is 2^32 rad or more.  keys[i] >> fine is the key of fine = 0 for every fine.  Another split of the same bits is asked for
+ *   as fine | (fs + 1) << 4 (fs sub-cell bits per axis, 2 fs <= fine; wherever a `fine` is passed or returned below).
+ * bbox: the seven layout words (min / max sort cell in x and y as {x0, y0, x1, y1}, occupied tiles, 1 when the tiles are numbered
+ * compactly, window play); tilemap: compact id per 32 x 32-cell tile of the padded map, row-major, ntx_abs tiles per row (used
+ * when bbox[5] != 0, may be NULL otherwise); px, py: pixel coordinates (x - origin_x) / resolution, NaN for a particle whose
+ * heading is not finite or beyond 1e6 rad, as the engine forms them; theta: headings; n: particles to key; n_layout: particles of
+ * the set the layout is made for (its density decides the split of the bits: the engine passes the size of the set).  Host only. */
+int mcl_host_sort_key(const int32_t bbox[7], const int32_t *tilemap, int32_t ntx_abs, uint32_t width, uint32_t height,
+                      const double *px, const double *py, const double *theta, int64_t n, int64_t n_layout, int32_t fine, uint32_t *keys);
+/* The order of the last update's ray stage when it went through the radix sort (MCL_SORT=radix, or 3 000 000 particles and more):
+ * keys[s] = sorted key of slot s, perm[s] = index of the particle in slot s (n entries each, either may be NULL), bbox (may be
+ * NULL) = the layout words the keys were made from, tilemap (may be NULL; n_tiles = tiles of the padded map, (width / 32 + 1) x
+ * (height / 32 + 1), at most 8192) = the tile numbering that goes with them (meaningful when bbox[5] != 0),
+ * *n_out / *fine (may be NULL) = particles ordered and fine bits of the keys
+ * (MCL_SORT_FINE=<0..10> in the environment of mcl_create sets them, MCL_SORT_FINE_SUB=<fs> their split; 0 is the coarse key alone).  Copies only.
+ * MCL_ERR_NOT_READY when the last ray stage did not order that way, MCL_ERR_INVALID_ARG for a wrong n. */
+int mcl_get_sort_order(mcl_engine_t *h, uint32_t *keys, uint32_t *perm, size_t n, int32_t bbox[7], int32_t *tilemap, size_t n_tiles,
+                       int64_t *n_out, int32_t *fine);
 
 /* ---- multi-GPU staging (one engine per rank; collectives are the host's) -- */
 /* Device pointers of engine-owned buffers so the host can hand them to RCCL without copies. */

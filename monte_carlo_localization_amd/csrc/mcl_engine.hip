@@ -220,6 +220,15 @@ SortTiles sort_tiles(const mcl_engine *h)
 // sort of (key, index) pairs is quicker -- keys only, rocPRIM's device sort (a plain library sort), then a gather:
 // 4M x 1081 6.57 -> 6.47 ms per update; below, its fixed cost of a dozen launches loses (2M +0.03, 262 144 +0.05 ms).
 bool sort_radix(const mcl_engine *h, int64_t n) { return h->env.sort_radix >= 0 ? h->env.sort_radix != 0 : n >= 3000000; }
+// The fine key bits of the radix path (SortLayout::fine), the one place they come from: ray_order's keys, sort width and gather, and the
+// keys the resampling kernel writes.  The counting sort has none (its histogram is the coarse key space).
+// (one word, mcl::sort_fine_code: the bits and, where MCL_SORT_FINE_SUB or the default names it, how many of them per axis are sub-cell bits)
+int sort_fine(const mcl_engine *h)
+{
+    const int f = h->env.sort_fine >= 0 ? std::min(h->env.sort_fine, mcl::kSortMaxFine) : mcl::kSortFineDefault;
+    const int fs = h->env.sort_fine_sub >= 0 ? h->env.sort_fine_sub : (h->env.sort_fine >= 0 ? -1 : mcl::kSortFineSubDefault);
+    return mcl::sort_fine_code(f, std::min(fs, 5));
+}
 
 // The layout the ordering works from, on `stream`: the bounding box of the particles in d_pc (every 16th of a large set), and
 // the occupied tiles of the map numbered compactly when the map has at most kSortMaxTiles of them (bbox[5] says so)
@@ -488,16 +497,19 @@ int ray_order(mcl_engine *h, const RayPlan &p, const mcl::RayArgs &a)
     }
     MCL_TRY(h->d_skey2.reserve(h, (size_t)h->cap));
     MCL_TRY(h->d_sval2.reserve(h, (size_t)h->cap));
+    // (the keys carry sort_fine(h) bits below the coarse 22: they only order the particles inside a bucket, and every reader drops them)
+    const int fine = sort_fine(h), key_bits = mcl::kSortKeyLog2 + mcl::sort_fine_bits(fine);
     size_t tb = 0;
-    HIPCHK(h, rocprim::radix_sort_pairs(nullptr, tb, h->d_skey.p, h->d_skey2.p, h->d_srank.p, h->d_sval2.p, (size_t)n, 0, mcl::kSortKeyLog2, h->stream));
+    HIPCHK(h, rocprim::radix_sort_pairs(nullptr, tb, h->d_skey.p, h->d_skey2.p, h->d_srank.p, h->d_sval2.p, (size_t)n, 0, key_bits, h->stream));
     MCL_TRY(h->d_sort_tmp.reserve(h, tb));
     if (!(p.stale_layout && p.keys_written))    // (else the resampling kernel wrote the pairs)
         hipLaunchKernelGGL(mcl::k_sort_keys, dim3(nb256), dim3(256), 0, h->stream, h->d_pc, a.th, n, h->Wp, h->Hp, h->d_bbox, h->d_skey, h->d_srank,
-                           h->d_tilemap, ntx_abs);
+                           h->d_tilemap, ntx_abs, fine);
     tb = h->d_sort_tmp.cap;
-    HIPCHK(h, rocprim::radix_sort_pairs(h->d_sort_tmp.p, tb, h->d_skey.p, h->d_skey2.p, h->d_srank.p, h->d_sval2.p, (size_t)n, 0, mcl::kSortKeyLog2, h->stream));
+    HIPCHK(h, rocprim::radix_sort_pairs(h->d_sort_tmp.p, tb, h->d_skey.p, h->d_skey2.p, h->d_srank.p, h->d_sval2.p, (size_t)n, 0, key_bits, h->stream));
     hipLaunchKernelGGL(mcl::k_sort_gather, dim3(nb256), dim3(256), 0, h->stream, h->d_pc, a.th, n, h->d_sval2, h->d_pcs, h->d_ths, h->d_perm,
-                       p.sweep ? h->d_skey2 : (const uint32_t *)nullptr, h->d_bbox, h->d_cut_start, h->d_cut_end);
+                       p.sweep ? h->d_skey2 : (const uint32_t *)nullptr, h->d_bbox, h->d_cut_start, h->d_cut_end, fine);
+    h->order_last = {h->d_bbox.p, h->d_tilemap.p, n, fine};                // (mcl_get_sort_order)
     return MCL_OK;
 }
 
@@ -666,6 +678,7 @@ int launch_rays(mcl_engine *h, const double *x, const double *y, const double *t
     DevBuf<unsigned long long> d_dbg;
     if (p.lists) MCL_TRY(ray_fix_lists(h, p, a));
     ray_prep(h, p, a);
+    h->order_last = {};                     // (ray_order's radix path sets it)
     if (p.ordered) { MCL_TRY(ray_order(h, p, a)); MCL_TRY(ray_units(h, p, a)); }
     // the tables of this update's scan were built on the second stream beside the resampling and the ordering: from here on they are read
     if (p.obs_wait) { h->handoff.obs_wait = false; HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_obs, 0)); }
@@ -899,6 +912,7 @@ void mcl_host::graph_reset(mcl_engine *h)
     h->graph_warm = false;
     h->prep_cache_valid = false;
     h->layout.valid = false;
+    h->order_last = {};
     ray_handoff_void(h);                    // whatever changed (map, beams, particles, a buffer): the ray stage makes its own constants
 }
 
@@ -985,6 +999,8 @@ static EnvKnobs read_knobs()
     if (const char *e = getenv("MCL_TINY_POLL")) k.tiny_poll = atoi(e);
     if (const char *e = getenv("MCL_NO_COMPACT")) k.no_compact = atoi(e);
     if (const char *e = getenv("MCL_SORT")) k.sort_radix = std::strcmp(e, "radix") == 0 ? 1 : (std::strcmp(e, "hist") == 0 ? 0 : -1);
+    if (const char *e = getenv("MCL_SORT_FINE")) k.sort_fine = atoi(e);
+    if (const char *e = getenv("MCL_SORT_FINE_SUB")) k.sort_fine_sub = atoi(e);
     if (const char *e = getenv("MCL_DEBUG_WG")) k.debug_wg = e;
     k.no_bucket_cuts = getenv("MCL_NO_BUCKET_CUTS") != nullptr;
     if (const char *e = getenv("MCL_SWEEP_GLOBAL")) k.sweep_global = atoi(e) != 0;
@@ -1696,7 +1712,7 @@ static void resample_ray_extras(mcl_engine *h, int64_t n, mcl::ResampleArgs &a, 
         ho.stale_layout = true;
         if (sort_radix(h, n) && h->d_skey2) {
             a.key_out = h->d_skey; a.val_out = h->d_srank; a.key_bbox = h->d_bbox; a.key_tilemap = tiles_ok ? h->d_tilemap : nullptr;
-            a.key_ntx = ntx_abs; a.key_Wp = h->Wp; a.key_Hp = h->Hp;
+            a.key_ntx = ntx_abs; a.key_Wp = h->Wp; a.key_Hp = h->Hp; a.key_fine = sort_fine(h);
             ho.keys = true;
         }
     }
@@ -2557,6 +2573,30 @@ int mcl_get_wedge_fields(mcl_engine_t *h, uint8_t *out, size_t n, int32_t dims[3
     if (n != (size_t)mcl::kWedges * h->Hp * h->Wps) return fail(h, MCL_ERR_INVALID_ARG, "the wedge fields have MCL_WEDGES x Hp x Wps bytes");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipMemcpyAsync(out, h->d_distw, n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MCL_OK;
+}
+
+int mcl_get_sort_order(mcl_engine_t *h, uint32_t *keys, uint32_t *perm, size_t n, int32_t bbox[7], int32_t *tilemap, size_t n_tiles,
+                       int64_t *n_out, int32_t *fine)
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    const OrderLast &o = h->order_last;
+    if (!o.bbox || o.n <= 0) return fail(h, MCL_ERR_NOT_READY, "the last ray stage did not order its particles through the radix sort");
+    if (n_out) *n_out = o.n;
+    if (fine) *fine = o.fine;                 // (a sort_fine_code)
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (keys || perm) {
+        if (n != (size_t)o.n) return fail(h, MCL_ERR_INVALID_ARG, "keys and perm have one entry per particle of the last update");
+        if (keys) HIPCHK(h, hipMemcpyAsync(keys, h->d_skey2, n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        if (perm) HIPCHK(h, hipMemcpyAsync(perm, h->d_perm, n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    }
+    if (bbox) HIPCHK(h, hipMemcpyAsync(bbox, o.bbox, 7 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (tilemap) {
+        const auto [ntx_abs, nty_abs, tiles_ok] = sort_tiles(h);
+        if (n_tiles != (size_t)ntx_abs * nty_abs || !tiles_ok) return fail(h, MCL_ERR_INVALID_ARG, "the tile map has one entry per 32 x 32-cell tile of the padded map (at most 8192)");
+        HIPCHK(h, hipMemcpyAsync(tilemap, o.tilemap, n_tiles * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MCL_OK;
 }

@@ -85,6 +85,9 @@ struct EnvKnobs {
     int qslices_per_cu = 0, qside = 0, sweep_g = 0;  // MCL_QSLICES_PER_CU, MCL_QSIDE, MCL_SWEEP_G
     int tiny_poll = 1, no_compact = 0;  // MCL_TINY_POLL=0: a tiny update waits for the stream, not the stamp; MCL_NO_COMPACT=1: the scan writes no compact list
     int sort_radix = -1;                // MCL_SORT=radix / hist forces one ordering path; default: by size
+    int sort_fine = -1;                 // MCL_SORT_FINE=<0..10>: fine key bits of the radix path (0: the coarse key alone); default: mcl::kSortFineDefault
+    int sort_fine_sub = -1;             // MCL_SORT_FINE_SUB=<fs>: how many of them per axis are sub-cell bits; default: the rule of SortLayout for a
+                                        //   given MCL_SORT_FINE, mcl::kSortFineSubDefault with the default bits
     std::string debug_wg;               // MCL_DEBUG_WG=<file>: four words per persistent workgroup (ray_debug_dump)
     bool no_bucket_cuts = false;        // MCL_NO_BUCKET_CUTS: units on the plain grid of 1024 slots, sparse sets ordered by whole tiles (rounds 2-3 before the cuts)
     bool sweep_global = false;          // MCL_SWEEP_GLOBAL=1: k_rays_sweep on the wedge fields in global memory whatever the range
@@ -98,6 +101,10 @@ struct EnvKnobs {
     bool comm_no_pregather = false;     // MCL_COMM_NO_PREGATHER: mcl_comm_update gathers the lists when it starts, not when the previous one ends
     bool comm_no_lists = false;         // MCL_COMM_NO_LISTS: mcl_comm_update takes the dense exchange on every update
 };
+
+// What the last radix ordering worked from, for mcl_get_sort_order: the layout buffers its keys were made from (d_bbox / d_tilemap at the time:
+// layout_adopt swaps them out at the end of the update, and nothing writes them before the next update), n and the fine bits.
+struct OrderLast { const int *bbox = nullptr, *tilemap = nullptr; int64_t n = 0; int fine = 0; };
 
 struct mcl_engine {
     mcl_config_t cfg{};
@@ -193,6 +200,7 @@ struct mcl_engine {
     DevBuf<uint32_t> d_tile_used;       // one mark per kHistTile buckets of the sort histogram: touched by this update's sort
     DevBuf<uint32_t> d_hist, d_histpart;                   // kSortBuckets, kSortBuckets / kHistTile
     DevBuf<int> d_bbox;                 // 7: bounding box, occupied tiles, numbering in use, window play
+    OrderLast order_last;               // (ray_order; voided where the layout is: graph_reset)
     DevBuf<uint32_t> d_cut_start, d_cut_end;   // kSwMaxCuts each: where the buckets of a sparse set start / end in the radix-sorted order (zero between sorts)
     DevBuf<int> d_tilemap, d_tilemark;  // kSortMaxTiles each: tile of the map -> compact id; marks of the occupied tiles (zero between sorts)
     DevBuf<double2> d_slice_mean;       // one per slice of the sorted order

@@ -11,6 +11,7 @@
 #include "mcl_motion.h"
 #include "mcl_refine_core.h"
 #include "mcl_wedge.h"
+#include "mcl_sort_key.h"
 
 namespace mcl_host {
 
@@ -863,6 +864,23 @@ int mcl_host_sweep_global_layout(uint32_t width, uint32_t height, int32_t max_ra
     const mcl::SweepGlobalLayout g = mcl::sweep_global_layout(Wp, Hp, max_range_px);
     out[0] = g.ok ? 1 : 0; out[1] = g.pitch; out[2] = g.rows; out[3] = (int64_t)g.stride; out[4] = (int64_t)g.alloc;
     out[5] = (int64_t)mcl::sweep_global_max_offset(g, Wp, Hp, max_range_px, mcl::kWedges - 1);
+    return MCL_OK;
+}
+
+int mcl_host_sort_key(const int32_t bbox[7], const int32_t *tilemap, int32_t ntx_abs, uint32_t width, uint32_t height,
+                      const double *px, const double *py, const double *theta, int64_t n, int64_t n_layout, int32_t fine, uint32_t *keys)
+{
+    if (!bbox || !px || !py || !theta || !keys || n < 0 || n_layout < 0 || width == 0 || height == 0 || fine < 0 || (fine & 15) > mcl::kSortMaxFine || fine >= 8 << 4)
+        return MCL_ERR_INVALID_ARG;
+    const int Wp = (int)width + 1, Hp = (int)height + 1;
+    const int hx = Wp * mcl::kSortSub - 1, hy = Hp * mcl::kSortSub - 1;
+    // a box inside the padded grid (an empty one holds no particle to key), and with numbered tiles a map for every tile of it
+    if (bbox[0] < 0 || bbox[1] < 0 || bbox[2] > hx || bbox[3] > hy || bbox[0] > bbox[2] || bbox[1] > bbox[3]) return MCL_ERR_INVALID_ARG;
+    if (bbox[5] != 0 && (!tilemap || ntx_abs < (hx >> 5) + 1 || bbox[4] < 0)) return MCL_ERR_INVALID_ARG;
+    for (int64_t i = 0; i < n; ++i) {
+        const double gx = px[i] * mcl::kSortSub, gy = py[i] * mcl::kSortSub;        // (what the ordering kernels hand sort_key, term for term)
+        keys[i] = mcl::sort_key(bbox, tilemap, ntx_abs, mcl::cell_of(gx, hx), mcl::cell_of(gy, hy), theta[i], n_layout, gx - floor(gx), gy - floor(gy), fine);
+    }
     return MCL_OK;
 }
 

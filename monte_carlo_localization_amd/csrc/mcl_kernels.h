@@ -15,6 +15,7 @@
 #include "mcl_device_math.h"
 #include "mcl_wedge.h"
 #include "mcl_motion.h"
+#include "mcl_sort_key.h"
 
 namespace mcl {
 
@@ -200,14 +201,6 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_final(const uint64_t *__r
 //   then row gather (cpp:664) and the motion model (cpp:474-502) with the three normals.
 // ------------------------------------------------------------------------------------------------
 
-#ifndef MCL_SORT_SUB
-#define MCL_SORT_SUB 1
-#endif
-constexpr int kSortSub = MCL_SORT_SUB;               // sort cells per grid cell and axis (the ordering kernels below)
-// (defined with the ordering kernels below; the resampling kernel makes the sort keys of its children itself when it is given a layout)
-__device__ __forceinline__ int cell_of(double g, int hi);
-__device__ __forceinline__ uint32_t sort_key(const int *__restrict__ bbox, const int *__restrict__ tilemap, int ntx_abs, int cx, int cy, double th,
-                                         int64_t n, double fx = 0.0, double fy = 0.0);
 
 __device__ __forceinline__ void prep_small_clear(const PrepClear &clr, int i, int nthreads)
 {
@@ -273,6 +266,7 @@ struct ResampleArgs {
     uint32_t *key_out, *val_out;      // null: keys are made by k_sort_keys / k_sort_hist
     const int *key_bbox, *key_tilemap;
     int key_ntx, key_Wp, key_Hp;
+    int key_fine;                     // fine bits of those keys (SortLayout::fine: the engine's setting of the radix path)
     PrepClear prep;                   // prep_on: the first workgroup also clears the few words of the ray stage that are not per
     int prep_on;                      //   particle (what k_prep_small would do in a launch of its own)
     const float *obs_src;             // this update's ranges (pinned host memory, read once by the first workgroup), or null
@@ -592,7 +586,7 @@ __device__ __forceinline__ void resample_motion_body(const ResampleArgs &a, cons
             // the same key k_sort_keys would make (same function, same arguments), from the layout handed in
             a.key_out[m] = sort_key(a.key_bbox, a.key_tilemap, a.key_ntx, cell_of(c.z * kSortSub, a.key_Wp * kSortSub - 1),
                                     cell_of(c.w * kSortSub, a.key_Hp * kSortSub - 1), th, a.n_children, c.z * kSortSub - floor(c.z * kSortSub),
-                                    c.w * kSortSub - floor(c.w * kSortSub));
+                                    c.w * kSortSub - floor(c.w * kSortSub), a.key_fine);
             a.val_out[m] = (uint32_t)m;
         }
     }
@@ -1368,29 +1362,10 @@ __global__ __launch_bounds__(256) void k_wedge_field_tight(const int32_t *__rest
 // returns is the particle's rank inside (bucket, xcd); the scan orders the counters bucket-major, xcd-minor.  The
 // rank order varies from run to run — harmless: the order only decides which rays share a wave, every log-weight
 // is an exact sum.
-// (22 key bits and half cells.  24 bits / quarter cells and 26 bits / eighths were built and measured at the end of round 5: the ray
-//  kernel of the bench workload issues the same number of instructions launch for launch with all three -- the density gate of
-//  sort_layout, not the key space, ends the split there, so the order is the same -- and yet runs 1 % faster or slower: with where
-//  the buffers lie (the histogram allocation is 128 MB / 512 MB / 2 GB), which is all that is left to differ:
-//  profiles/r05_experiments/sort_key_bits.txt.  Not taken.)
-#ifndef MCL_SORT_KEY_LOG2
-#define MCL_SORT_KEY_LOG2 22
-#endif
-constexpr int kSortKeyLog2 = MCL_SORT_KEY_LOG2;
-constexpr uint32_t kSortKeySpace = 1u << kSortKeyLog2;
-#ifndef MCL_SORT_MAX_SUB
-#define MCL_SORT_MAX_SUB 1
-#endif
+// (the key itself -- kSortKeySpace, SortLayout, sort_layout, sort_key, cell_of -- is in mcl_sort_key.h: host and device)
 constexpr int kSortXcds = 8;                        // copies of the histogram (XCC_ID & 7)
 constexpr uint32_t kSortBuckets = kSortKeySpace * kSortXcds;
 constexpr int kHistTile = 4096;                     // entries per workgroup of the bucket scan
-
-__device__ __forceinline__ int cell_of(double g, int hi)
-{
-    // padded cell coordinate of a pixel coordinate, clamped into the padded grid (NaN -> 0)
-    int c = (g > -1.0) ? ((g < 1e9) ? (int)floor(g) + 1 : hi) : 0;
-    return c < 0 ? 0 : (c > hi ? hi : c);
-}
 
 // bbox[0..3] = min cx, min cy, max cx, max cy over every `stride`-th particle (initialised to +big / -big by the
 // host).  A sample is enough: sort_key clamps cells into the box, so a particle outside it merely lands in an
@@ -1463,110 +1438,6 @@ __global__ __launch_bounds__(1024) void k_tile_compact(int *__restrict__ bbox, i
     for (int t = threadIdx.x; t < ntiles_abs; t += 1024)
         if (tilemap[t] < 0) tilemap[t] = T;           // (written by this thread in the loop above: t = t0 + threadIdx.x)
     if (threadIdx.x == 0) { bbox[4] = T; bbox[5] = 1; }
-}
-
-#ifndef MCL_SORT_SUB_GATE
-#define MCL_SORT_SUB_GATE 32.0
-#endif
-constexpr double kSortSubGate = MCL_SORT_SUB_GATE;  // particles a bucket must hold (an eighth of its heading bins taken as occupied) to be split in four
-constexpr int kSortMaxSub = MCL_SORT_MAX_SUB;        // sub-cell bits per axis a dense set may get (0: none)
-// How the key bits are split for this update's set: a pure function of the bounding box / occupied-tile count and n, so that
-// every particle -- and k_unit_table, which needs to know where a tile's keys start -- derives the same layout.
-//   key = ((((tile << inner | iy) << inner | ix) << ss | sy) << ss | sx) << tb | heading bin
-struct SortLayout {
-    int cs, tb, inner, ss;
-    uint32_t ntx;
-    int tx0, ty0;
-    bool compact;
-    bool nocut;                       // bbox[6] < 0 (MCL_NO_BUCKET_CUTS): the plain grid of units, sparse sets by whole tiles
-    bool sparse;                      // ordered by whole buckets of 2^cs x 2^cs cells (a spread cloud): units are cut at their borders
-    uint64_t ntiles;
-    __device__ __forceinline__ int tile_shift() const { return 2 * inner + 2 * ss + tb; }
-    // Units are cut where the sorted order changes GROUP: a sparse set's bucket, a dense set's 32 x 32 tile (a set that sits on
-    // a few far-apart clusters -- the steady state of a global re-localisation -- otherwise has units that end in one cluster
-    // and begin in the next, whose minority side no window reaches: 0.85 ms of far pass per update at 4M on ~30 clusters).
-    __device__ __forceinline__ int cut_shift() const { return sparse ? 2 * ss + tb : tile_shift(); }                 // key bits below the group
-    __device__ __forceinline__ uint64_t cut_groups() const { return sparse ? ntiles << (2 * inner) : ntiles; }       // groups of the key space
-    // (k_sort_gather notes the borders, k_unit_table uses them: one rule for both)
-    __device__ __forceinline__ bool cuts() const;
-};
-constexpr int kSwMaxCuts = 65536;     // buckets up to which a sparse set's units are cut at bucket borders (k_unit_table)
-__device__ __forceinline__ bool SortLayout::cuts() const
-{
-    return compact && !nocut && cut_groups() <= (uint64_t)kSwMaxCuts && (cut_groups() << cut_shift()) <= kSortKeySpace;
-}
-__device__ __forceinline__ SortLayout sort_layout(const int *__restrict__ bbox, int64_t n)
-{
-    SortLayout L;
-    L.tx0 = bbox[0] >> 5; L.ty0 = bbox[1] >> 5;
-    L.ntx = (uint32_t)((bbox[2] >> 5) - L.tx0 + 1);
-    const uint32_t nty = (uint32_t)((bbox[3] >> 5) - L.ty0 + 1);
-    L.compact = bbox[5] != 0;
-    L.ntiles = L.compact ? (uint64_t)bbox[4] + 1u : (uint64_t)L.ntx * nty;       // + 1: the overflow tile
-    // cells the set can be taken to live on: its bounding box, or its occupied tiles if that is less
-    double cells_est = (double)(bbox[2] - bbox[0] + 1) * (double)(bbox[3] - bbox[1] + 1);
-    if (L.compact && (double)bbox[4] * 1024.0 < cells_est) cells_est = (double)bbox[4] * 1024.0;
-    // Heading first: the lanes of a wave must agree on which wedge their beams are in, so six heading bits (5.6 degrees)
-    // are kept while the in-tile resolution is coarsened to make room (a particle set spread over a large bounding box
-    // -- several far-apart clusters -- otherwise spends the whole key space on empty cells: 80 % slower ray stage);
-    // only a bounding box of more than 2^14 tiles gives heading bits up.  What is left over goes to the heading.
-    // A SPARSE set (fewer than 8 particles per cell of the bounding box: the uniform cloud of global localisation, or a
-    // few far-apart clusters) is ordered by whole 32 x 32 tiles: 1024 consecutive particles cover hundreds of cells
-    // whatever the bucket size, and with one bucket per tile the 64 particles of a wave are neighbours in heading
-    // (first update of the global regime: ray kernel 13.8 -> 11.4 ms).  A dense set keeps single cells: there the
-    // compactness of a unit is what the windows and the probe loop live on (coarser buckets cost 4-30 %).
-    int cs = 0, tb = 6;
-    L.nocut = bbox[6] < 0;
-    L.sparse = cells_est > 0.0 && (double)n < 8.0 * cells_est;
-    if (L.sparse) {
-        cs = 5;
-        // ... of the size the play of a ray window can hold: a unit is one bucket's particles, and a unit wider than the play
-        // loses its particles to the far pass (the levine stand-in's 239-px range leaves 12 cells: whole tiles put 3.5M of the
-        // 4M particles of a uniform cloud there, 35 ms).  Smaller buckets only while one still holds a couple of chunks.
-        const int play = bbox[6];
-        while (play > 0 && cs > 1 && (1 << cs) >= play - 2 && (double)n * (double)(1 << (2 * cs - 2)) >= 128.0 * cells_est) --cs;
-    }
-    while (cs < 5 && ((L.ntiles << (10 - 2 * cs + tb)) > kSortKeySpace)) ++cs;
-    while (tb > 0 && ((L.ntiles << (10 - 2 * cs + tb)) > kSortKeySpace)) --tb;
-    const int inner = 5 - cs;                             // log2 of the bucket grid inside one tile
-    const uint64_t ncell = L.ntiles << (2 * inner);
-    while (tb < 8 && (ncell << (tb + 1)) <= kSortKeySpace) ++tb;
-    // Bits left over once the cells have their full resolution and the heading its eight bits go to the position inside
-    // the cell (half cells, then quarter cells): a collapsed set is thousands of particles per cell, and rays that start
-    // within half a cell of each other keep company longer (levine stand-in: ray kernel -10 %, Spielberg -3 %).
-    int ss = 0;
-    if (cs == 0 && tb == 8) {
-        // ... as long as a bucket still holds a few waves' worth: particles per cell of the bounding box, an eighth of the
-        // heading bins taken as occupied (262 144 particles on 25 cells are better off without: 43 per bucket)
-        double per_bucket = cells_est > 0.0 ? (double)n / cells_est / 32.0 : 0.0;
-        while (ss < kSortMaxSub && (ncell << (tb + 2 * (ss + 1))) <= kSortKeySpace && per_bucket >= kSortSubGate) { ++ss; per_bucket *= 0.25; }
-    }
-    L.cs = cs; L.tb = tb; L.inner = inner; L.ss = ss;
-    return L;
-}
-
-__device__ __forceinline__ uint32_t sort_key(const int *__restrict__ bbox, const int *__restrict__ tilemap, int ntx_abs, int cx, int cy, double th,
-                                         int64_t n, double fx, double fy)
-{
-    cx = cx < bbox[0] ? bbox[0] : (cx > bbox[2] ? bbox[2] : cx);
-    cy = cy < bbox[1] ? bbox[1] : (cy > bbox[3] ? bbox[3] : cy);
-    const SortLayout L = sort_layout(bbox, n);
-    const int cs = L.cs, tb = L.tb, inner = L.inner, ss = L.ss;
-    uint32_t tile = (uint32_t)((cy >> 5) - L.ty0) * L.ntx + (uint32_t)((cx >> 5) - L.tx0);
-    if (L.compact) tile = (uint32_t)tilemap[(cy >> 5) * ntx_abs + (cx >> 5)];
-    const uint32_t ix = (uint32_t)(cx & 31) >> cs, iy = (uint32_t)(cy & 31) >> cs;
-    uint64_t key = ((((uint64_t)tile << inner) | iy) << inner) | ix;
-    if (ss > 0) {
-        const uint32_t sx = (fx >= 0.0 && fx < 1.0) ? (uint32_t)(fx * (double)(1 << ss)) : 0u;
-        const uint32_t sy = (fy >= 0.0 && fy < 1.0) ? (uint32_t)(fy * (double)(1 << ss)) : 0u;
-        key = (((key << ss) | sy) << ss) | sx;
-    }
-    double f = th * 0.15915494309189533577;               // heading as a fraction of a turn
-    f -= floor(f);
-    uint32_t tq = (f >= 0.0 && f < 1.0) ? (uint32_t)(f * (double)(1u << tb)) : 0u;
-    if (tq >> tb) tq = (1u << tb) - 1u;
-    key = (key << tb) | tq;
-    return key < kSortKeySpace ? (uint32_t)key : kSortKeySpace - 1u;    // a bounding box beyond the key space: unsorted tail
 }
 
 __global__ __launch_bounds__(256) void k_sort_hist(const double4 *__restrict__ pc, const double *__restrict__ th, int64_t n, int Wp, int Hp,
@@ -1678,23 +1549,23 @@ __global__ __launch_bounds__(256) void k_sort_scatter(const double4 *__restrict_
 //      rocPRIM's (a plain library sort, like a library GEMM would be), the gather puts the records in sorted order ----
 __global__ __launch_bounds__(256) void k_sort_keys(const double4 *__restrict__ pc, const double *__restrict__ th, int64_t n, int Wp, int Hp,
                                                   const int *__restrict__ bbox, uint32_t *__restrict__ key_out, uint32_t *__restrict__ val_out,
-                                                  const int *__restrict__ tilemap, int ntx_abs)
+                                                  const int *__restrict__ tilemap, int ntx_abs, int fine)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const double4 c = pc[i];
     key_out[i] = sort_key(bbox, tilemap, ntx_abs, cell_of(c.z * kSortSub, Wp * kSortSub - 1), cell_of(c.w * kSortSub, Hp * kSortSub - 1), th[i], n,
-                          c.z * kSortSub - floor(c.z * kSortSub), c.w * kSortSub - floor(c.w * kSortSub));
+                          c.z * kSortSub - floor(c.z * kSortSub), c.w * kSortSub - floor(c.w * kSortSub), fine);
     val_out[i] = (uint32_t)i;
 }
 // cut_start[g] + 1 / cut_end[g]: first slot + 1 and end of bucket g in the sorted order (0 / anything: nobody there), written where
 // the sorted keys change bucket -- what k_unit_table needs to cut a sparse set's units at bucket borders (it zeroes the
-// entries it reads).  sorted_keys null: no borders wanted.
+// entries it reads).  sorted_keys null: no borders wanted.  fine: the fine bits the keys were made with (dropped with the rest below a group).
 __global__ __launch_bounds__(256) void k_sort_gather(const double4 *__restrict__ pc, const double *__restrict__ th, int64_t n,
                                                     const uint32_t *__restrict__ order, double4 *__restrict__ pcs, double *__restrict__ ths,
                                                     uint32_t *__restrict__ perm, const uint32_t *__restrict__ sorted_keys = nullptr,
                                                     const int *__restrict__ bbox = nullptr, uint32_t *__restrict__ cut_start = nullptr,
-                                                    uint32_t *__restrict__ cut_end = nullptr)
+                                                    uint32_t *__restrict__ cut_end = nullptr, int fine = 0)
 {
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n) return;
@@ -1703,7 +1574,7 @@ __global__ __launch_bounds__(256) void k_sort_gather(const double4 *__restrict__
     ths[s] = th[i];
     perm[s] = i;
     if (sorted_keys) {
-        const SortLayout L = sort_layout(bbox, n);
+        const SortLayout L = sort_layout(bbox, n, fine);
         if (L.cuts()) {
             const int sh = L.cut_shift();
             const uint32_t g = sorted_keys[s] >> sh;

@@ -44,7 +44,7 @@ EXPORTS = [
     "mcl_stage_rays_async", "mcl_stage_weights_async", "mcl_stage_complete", "mcl_stage_keep",
     "mcl_comm_available", "mcl_comm_unique_id", "mcl_comm_create", "mcl_comm_destroy", "mcl_comm_update", "mcl_comm_stats", "mcl_comm_set_lists", "mcl_comm_get_vector", "mcl_comm_last_exchange", "mcl_comm_selftest",
     "mcl_host_sweep_global_layout", "mcl_get_ray_kernel_variant", "mcl_host_skip_field_wedge_tight", "mcl_host_wedge_tight_table",
-    "mcl_get_wedge_fields", "mcl_get_ring_fields", "mcl_get_sweep_table",
+    "mcl_get_wedge_fields", "mcl_get_ring_fields", "mcl_get_sweep_table", "mcl_host_sort_key", "mcl_get_sort_order",
     "mcl_default_kld_config", "mcl_set_kld", "mcl_get_particle_count", "mcl_get_kld_state", "mcl_host_kld_bins", "mcl_host_kld_target",
     "mcl_default_cluster_config", "mcl_pose_clusters", "mcl_get_cluster_labels",
     "mcl_query_scans", "mcl_score_poses", "mcl_get_query_counters",
@@ -317,6 +317,10 @@ def load_library(legacy=False):
         lib.mcl_get_ring_fields.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         lib.mcl_get_sweep_table.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32)]
         lib.mcl_host_sweep_global_layout.argtypes = [C.c_uint32, C.c_uint32, C.c_int32, C.POINTER(C.c_int64)]
+        lib.mcl_host_sort_key.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_int64, C.c_int64, C.c_int32, C.c_void_p]
+        lib.mcl_get_sort_order.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
+                                           C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         lib.mcl_get_likelihood_table.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32)]
         lib.mcl_host_likelihood_field.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(LikelihoodFieldConfig),
                                                   C.c_void_p, C.c_size_t]
@@ -844,6 +848,47 @@ def host_skip_field_wedge_tight(grid, wedge: int) -> np.ndarray:
     return out
 
 
+SORT_KEY_LOG2, SORT_MAX_FINE = 22, 10      # bits of the coarse ordering key, and the most fine bits below it (csrc/mcl_sort_key.h)
+
+
+def sort_fine_code(fine: int, fine_sub: int | None = None) -> int:
+    """the fine setting as the one word the C calls take: the bits, and the sub-cell bits per axis where they are not the rule's"""
+    if not 0 <= int(fine) <= SORT_MAX_FINE or (fine_sub is not None and not 0 <= 2 * int(fine_sub) <= int(fine)):
+        raise EngineError(f"sort key: fine={fine} fine_sub={fine_sub} (0 .. {SORT_MAX_FINE} bits, at most half of them per axis)", MCL_ERR_INVALID_ARG)
+    return int(fine) | ((int(fine_sub) + 1) << 4 if fine_sub is not None else 0)
+
+
+def sort_tile_grid(width: int, height: int):
+    """(tiles per row, rows of tiles) of the 32 x 32-cell tiles over the padded map: the shape of an ordering tile map."""
+    return (int(width) >> 5) + 1, (int(height) >> 5) + 1
+
+
+def host_sort_key(bbox, tilemap, width: int, height: int, px, py, theta, fine: int = 0, n_layout: int | None = None,
+                  fine_sub: int | None = None) -> np.ndarray:
+    """mcl_host_sort_key: the ordering keys (uint32) of particles at pixel coordinates (px, py) with headings theta, under the
+    layout words `bbox` (7 int32) and the tile map (None when bbox[5] == 0), with `fine` bits below the coarse 22 -- the code
+    the device runs, on the CPU.  n_layout: the size of the set the layout is for (its density decides the split of the bits);
+    default: the number of particles given.  fine_sub: how many of the fine bits, per axis, are sub-cell bits (default: the
+    rule, max(fine - 2, 0) // 4)."""
+    bb = _c(np.asarray(bbox).reshape(-1)[:7], np.int32)
+    x, y, t = _c(px, np.float64), _c(py, np.float64), _c(theta, np.float64)
+    if bb.size != 7 or not (x.shape == y.shape == t.shape) or x.ndim != 1:
+        raise ValueError("host_sort_key: bbox has 7 words; px, py, theta are 1-D and of one length")
+    ntx, nty = sort_tile_grid(width, height)
+    tm = None
+    if tilemap is not None:
+        tm = _c(tilemap, np.int32)
+        if tm.size != ntx * nty:
+            raise ValueError(f"host_sort_key: the tile map has {ntx} x {nty} entries for this map")
+    out = np.empty(x.size, np.uint32)
+    rc = load_library().mcl_host_sort_key(_p(bb), _p(tm) if tm is not None else None, C.c_int32(ntx), C.c_uint32(width), C.c_uint32(height),
+                                          _p(x), _p(y), _p(t), C.c_int64(x.size), C.c_int64(x.size if n_layout is None else n_layout),
+                                          C.c_int32(sort_fine_code(fine, fine_sub)), _p(out))
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_sort_key rc={rc}", rc)
+    return out
+
+
 WEDGE_R = 255
 
 
@@ -1195,6 +1240,22 @@ class Engine:
         out = np.empty((dims[0], dims[1]), np.float64)
         self._chk(self.lib.mcl_get_sweep_table(self._h, _p(out), C.c_size_t(out.size), None), "mcl_get_sweep_table")
         return out, int(dims[2])
+
+    def sort_order(self):
+        """The order of the last update's ray stage (radix ordering path): dict(keys, perm, bbox, tilemap, n, fine, fine_sub) -- the
+        sorted keys and the particle index per slot, the layout words and tile map the keys were made from (tilemap None for a map
+        of more than 8192 tiles), the fine bits of the keys and how many of them per axis are sub-cell bits (None: the rule's).  EngineError NOT_READY when the last ray stage did not order that way."""
+        n, fine = C.c_int64(), C.c_int32()
+        self._chk(self.lib.mcl_get_sort_order(self._h, None, None, C.c_size_t(0), None, None, C.c_size_t(0), C.byref(n), C.byref(fine)),
+                  "mcl_get_sort_order")
+        keys, perm, bbox = np.empty(n.value, np.uint32), np.empty(n.value, np.uint32), np.empty(7, np.int32)
+        H, W = self.map_shape
+        ntx, nty = sort_tile_grid(W, H)
+        tm = np.empty(ntx * nty, np.int32) if ntx * nty <= 8192 else None
+        self._chk(self.lib.mcl_get_sort_order(self._h, _p(keys), _p(perm), C.c_size_t(n.value), _p(bbox), _p(tm) if tm is not None else None,
+                                              C.c_size_t(tm.size if tm is not None else 0), None, None), "mcl_get_sort_order")
+        return dict(keys=keys, perm=perm, bbox=bbox, tilemap=tm, n=int(n.value), fine=int(fine.value) & 15,
+                    fine_sub=(int(fine.value) >> 4) - 1 if int(fine.value) >> 4 else None)
 
     def particle_count(self) -> int:
         n = C.c_int64()
