@@ -453,7 +453,7 @@ int mcl_host_search_headings(const mcl_search_config_t *c, double *theta, size_t
  *     scan: x_p + 0.0 (or + -0.0) is x_p, theta_k + 0.0 is theta_k (theta_k = 0 stays +0.0), and +0.0 + acc_0 is acc_0.
  *   Refused with MCL_ERR_INVALID_ARG, the message naming the cause: n_scans outside [1, MCL_SEARCH_MAX_SCANS]; a null scans or
  *     rel; a rel entry that is not finite; n_beams != B; and everything S8 refuses, MCL_ERR_NOT_READY where S8 says so.
- *   Not here: refinement over a sequence (mcl_refine_poses on the anchor scan is the next step), the beam model, shards. */
+ *   Not here: the beam model, shards.  (Refinement over the same sequence: mcl_refine_poses_sequence.) */
 #define MCL_SEARCH_MAX_SCANS 16
 int mcl_global_search_sequence(mcl_engine_t *h, const mcl_search_config_t *c /* NULL = the defaults */, const float *scans,
                                const double *rel, int32_t n_scans, int32_t n_beams, int32_t max_hits, mcl_search_hit_t *hits,
@@ -673,7 +673,7 @@ int mcl_host_search_prune_next(const mcl_search_prune_config_t *pc, int64_t pair
  *     before after every other call.  The score volume of an earlier mcl_global_search / _sequence stays as it was.  One host wait
  *     per round.  Every later update and search is bit-identical to one of an engine that never called it.
  *   stats = the eight of mcl_global_search_pruned (used beams: of all scans, as SQ6), then [8] = N; stats may be NULL.
- *   Not here: a streamed, beam-model or sharded variant, refinement over a sequence. */
+ *   Not here: a streamed, beam-model or sharded variant.  (Refinement over the same sequence: mcl_refine_poses_sequence.) */
 int mcl_global_search_sequence_pruned(mcl_engine_t *h, const mcl_search_config_t *c /* NULL = the defaults */,
                                       const mcl_search_prune_config_t *pc /* NULL = the defaults */, const float *scans,
                                       const double *rel, int32_t n_scans, int32_t n_beams, int32_t max_hits, mcl_search_hit_t *hits,
@@ -786,6 +786,56 @@ int mcl_host_refine_reduce(const mcl_refine_config_t *c, const double seed[3], f
  *   Not here: a window that is iterated or re-centred, pruning of the window, shards. */
 int mcl_refine_poses_beam(mcl_engine_t *h, const mcl_refine_config_t *c /* NULL = the defaults */, const double *seeds_colmajor,
                           int32_t M, const float *obs, int32_t n_beams, mcl_refine_result_t *out, uint64_t stats[6]);
+
+/* ---- pose refinement over a scan sequence joined by odometry -------------------------------------------------
+ * The sequence searches rank places one scan cannot tell apart; mcl_refine_poses on the anchor scan then re-ranks their hits by
+ * exactly that scan.  mcl_refine_poses_sequence scores every window pose against S scans, each from where that pose implies the
+ * robot was when the scan arrived, so the records keep the ranking of the search that made the seeds.  A seed and every window
+ * pose is the robot's pose at the ANCHOR.  scans is S x n_beams, scan-major; rel is S x 3 as in mcl_global_search_sequence
+ * (rel[s]: the robot's pose at scan s in its frame at the anchor; any finite rel is accepted).  The config, the window (R1), the
+ * records and mcl_get_refine_scores / mcl_get_refine_bytes are mcl_refine_poses'.  With nt = 2 half_theta + 1:
+ *   RS1 offsets, on the host.  For seed m and window heading index it, theta = R1's heading t0_m + (double)(it - half_theta) *
+ *     step_theta_rad (the multiply and the add each rounded: one function on host and device); c = cos(theta), s = sin(theta)
+ *     from the host's libm, once per (m, it).  For scan s, in SQ1's arithmetic:
+ *       theta_s = theta + dtheta_s                         (one rounded add)
+ *       ax = c * dx_s - s * dy_s,  ay = s * dx_s + c * dy_s   (two rounded multiplies, then one rounded add or subtract; no fma:
+ *                                                            the host unit is compiled with contraction off)
+ *     The table off[((m * nt + it) * S + s) * 3 + {0, 1, 2}] = {ax, ay, theta_s} is uploaded; the device never re-derives it
+ *     (SQ1's reason: the host's and the device's sincos need not agree in the last bit).  mcl_host_refine_sequence_offsets is the
+ *     same code without a device (n == M * nt * S * 3).  The table has M nt S rows of 24 bytes; a call with more than
+ *     MCL_REFINE_SEQ_MAX_ROWS rows is refused before anything is allocated (2^21 rows: 48 MiB pinned and 48 MiB on the device;
+ *     4096 seeds x 21 headings x 16 scans = 1 376 256 rows fit).  A zero rel gives ax = ay = 0 (of either sign), theta_s = theta.
+ *   RS2 pose of scan s at window pose (m, w): (x_w + ax, y_w + ay, theta_s), x_w and y_w from R1, each coordinate one rounded
+ *     fp64 add on the device; theta_s is NOT wrapped; the device takes sincos(theta_s) as k_refine_score takes it of a window
+ *     heading.
+ *   RS3 beams.  SQ3: every scan gets its own list of used beams (j % beam_stride == 0 and 0 <= r_sj < max_range_m), in beam
+ *     order, by the update's own rule; the lists are concatenated on the device, S + 1 offsets say where each begins.  Scans may
+ *     have different numbers of used beams, zero included.
+ *   RS4 score.  acc_s is, bit for bit, what mcl_score_poses returns for the pose of RS2 and scan s (for beam_stride > 1: with the
+ *     readings of the other beams replaced by NaN).  score[m n_win + w] = ((+0.0 + acc_0) + acc_1) + ... in scan order, in
+ *     fp64: finite or -inf, never NaN.
+ *   RS5 records.  R3 / R4 unchanged, on the summed volume (the same reduction kernel; mcl_host_refine_reduce restates it).  best
+ *     and mean are anchor poses, best_log_likelihood and seed_log_likelihood summed scores.
+ *   RS6 identity.  With S = 1 and rel = (0, 0, 0) the volume and the M records are bit for bit those of mcl_refine_poses with the
+ *     same scan (SQ7's argument), through the sequence's own kernel: the host has no special case for S = 1.
+ *   RS7 placement, stats, refusals.  R6 holds: the buffers are the refinement's own -- the table, the S + 1 offsets and a beam
+ *     list of S scans beside mcl_refine_poses' (mcl_get_refine_bytes counts them) --, one host wait per call, and every later
+ *     update is bit-identical to one of an engine that never refined.  stats = R5's four, with the used beams summed over the
+ *     scans, then [4] = S; stats may be NULL.  Everything R7 refuses is refused with the same status; MCL_ERR_INVALID_ARG also
+ *     for n_scans outside [1, MCL_SEARCH_MAX_SCANS], a null scans or rel, a rel entry that is not finite, and more than
+ *     MCL_REFINE_SEQ_MAX_ROWS rows (the message names the cap and the three factors).
+ *   Not here: the beam model (mcl_refine_poses_beam stays single-scan: no beam-model sequence search feeds it), shards, a search
+ *     over odometry error, per-scan scores in the record (mcl_score_poses at RS2's poses gives them), a window that is iterated
+ *     or re-centred. */
+#define MCL_REFINE_SEQ_MAX_ROWS (1 << 21)
+int mcl_refine_poses_sequence(mcl_engine_t *h, const mcl_refine_config_t *c /* NULL = the defaults */, const double *seeds_colmajor,
+                              int32_t M, const float *scans, const double *rel, int32_t n_scans, int32_t n_beams,
+                              mcl_refine_result_t *out, uint64_t stats[5]);
+/* RS1 on the host, without a device: out receives n == M * nt * n_scans * 3 doubles.  MCL_ERR_INVALID_ARG for a refused config
+ * (NULL = the defaults), M outside [1, 4096], n_scans outside [1, MCL_SEARCH_MAX_SCANS], a null pointer, a seed or a rel entry
+ * that is not finite, more than MCL_REFINE_SEQ_MAX_ROWS rows, a wrong n. */
+int mcl_host_refine_sequence_offsets(const mcl_refine_config_t *c, const double *seeds_colmajor, int32_t M, const double *rel,
+                                     int32_t n_scans, double *out, size_t n);
 
 /* ---- recovery by random-particle injection (augmented MCL, Probabilistic Robotics Table 8.3; AMCL's recovery_alpha_slow /
  *      recovery_alpha_fast) -------------------------------------------------------------------------------

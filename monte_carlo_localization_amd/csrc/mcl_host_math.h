@@ -87,4 +87,11 @@ void lf_pool(const uint16_t *D, int W, int H, int K, int w, uint16_t *out);     
 void search_bound_table(const float *lf, int K, float *ub);                             // K + 1 entries
 int64_t search_prune_next(const mcl_search_prune_config_t &pc, int64_t pairs, int64_t n_scored, int64_t first_below_c);
 const char *refine_invalid(const mcl_refine_config_t *c);
+// The refinement over a scan sequence (mcl_refine_poses_sequence).  What RS7 refuses of rel and of the table's
+// size (M seeds x nt window headings x S scans rows against MCL_REFINE_SEQ_MAX_ROWS): null / empty when fine, else why not.
+// RS1: the table off[((m * nt + it) * S + s) * 3 + {0, 1, 2}] = {ax, ay, theta_s} of M column-major seeds.
+const char *refine_sequence_invalid(const double *rel, int n_scans);
+std::string refine_sequence_rows_refused(int64_t M, int64_t nt, int64_t S);
+void refine_sequence_offsets(int32_t half_theta, double step_theta, const double *seeds_colmajor, int32_t M, const double *rel, int n_scans,
+                             double *out);
 }  // namespace mcl_host

@@ -690,6 +690,44 @@ const char *refine_invalid(const mcl_refine_config_t *c)
     return nullptr;
 }
 
+// ---- the refinement over a scan sequence (mcl_refine_poses_sequence): what RS7 refuses of rel and of the
+// table's size, and RS1
+const char *refine_sequence_invalid(const double *rel, int n_scans)
+{
+    static_assert(MCL_SEARCH_MAX_SCANS == 16, "the message below names the limit");
+    if (n_scans < 1 || n_scans > MCL_SEARCH_MAX_SCANS) return "refine: n_scans must be in [1, 16] (MCL_SEARCH_MAX_SCANS)";
+    if (!rel) return "refine: rel is null";
+    for (int i = 0; i < 3 * n_scans; ++i)
+        if (!std::isfinite(rel[i])) return "refine: rel has an entry that is not finite";
+    return nullptr;
+}
+
+std::string refine_sequence_rows_refused(int64_t M, int64_t nt, int64_t S)
+{
+    if (M * nt * S <= (int64_t)MCL_REFINE_SEQ_MAX_ROWS) return std::string();
+    return "refine: the offset table would have " + std::to_string(M * nt * S) + " rows (" + std::to_string(M) + " seeds x " +
+           std::to_string(nt) + " window headings x " + std::to_string(S) + " scans), more than MCL_REFINE_SEQ_MAX_ROWS = " +
+           std::to_string((int64_t)MCL_REFINE_SEQ_MAX_ROWS);
+}
+
+void refine_sequence_offsets(int32_t half_theta, double step_theta, const double *seeds_colmajor, int32_t M, const double *rel, int n_scans,
+                             double *out)
+{
+    const int32_t nt = 2 * half_theta + 1;
+    for (int32_t m = 0; m < M; ++m)
+        for (int32_t it = 0; it < nt; ++it) {
+            const double th = mcl_rf::coord(seeds_colmajor[(size_t)2 * (size_t)M + (size_t)m], it - half_theta, step_theta);     // R1's heading
+            const double c = std::cos(th), s = std::sin(th);
+            double *o = out + ((size_t)m * (size_t)nt + (size_t)it) * (size_t)n_scans * 3;
+            for (int sc = 0; sc < n_scans; ++sc, o += 3) {
+                const double dx = rel[3 * sc], dy = rel[3 * sc + 1];
+                o[0] = c * dx - s * dy;                    // each product rounded, then the difference (contraction is off)
+                o[1] = s * dx + c * dy;
+                o[2] = th + rel[3 * sc + 2];
+            }
+        }
+}
+
 // G1: the lower Cholesky factor of a symmetric positive semi-definite 3 x 3 matrix (row-major), L = {L00, L10, L11, L20, L21, L22}
 const char *gaussian_factor(const double cov[9], double L[6])
 {
@@ -1259,6 +1297,23 @@ int mcl_host_refine_reduce(const mcl_refine_config_t *c, const double seed[3], f
     for (int k = 0; k < mcl_rf::kSums; ++k) sums[k] = part[(size_t)k * mcl_rf::kThreads];
     const int32_t wc = (g.half_theta * g.nx + g.half_xy) * g.nx + g.half_xy;
     mcl_rf::finish(g, seed[0], seed[1], seed[2], wb, scores[wb], scores[wc], sums, out);
+    return MCL_OK;
+}
+
+int mcl_host_refine_sequence_offsets(const mcl_refine_config_t *c, const double *seeds_colmajor, int32_t M, const double *rel,
+                                     int32_t n_scans, double *out, size_t n)
+{
+    mcl_refine_config_t d;
+    mcl_default_refine_config(&d);
+    if (!c) c = &d;
+    if (refine_invalid(c) || !seeds_colmajor || M < 1 || M > mcl_rf::kMaxSeeds || refine_sequence_invalid(rel, n_scans) || !out)
+        return MCL_ERR_INVALID_ARG;
+    for (int64_t i = 0; i < (int64_t)3 * M; ++i)
+        if (!std::isfinite(seeds_colmajor[i])) return MCL_ERR_INVALID_ARG;
+    const int64_t nt = 2 * (int64_t)c->half_theta + 1;
+    if (!refine_sequence_rows_refused(M, nt, n_scans).empty()) return MCL_ERR_INVALID_ARG;
+    if (n != (size_t)M * (size_t)nt * (size_t)n_scans * 3) return MCL_ERR_INVALID_ARG;
+    refine_sequence_offsets(c->half_theta, c->step_theta_rad, seeds_colmajor, M, rel, n_scans, out);
     return MCL_OK;
 }
 

@@ -95,6 +95,56 @@ __global__ __launch_bounds__(kThreads) void k_refine_score(Args a)
     a.score[i] = acc;
 }
 
+// The refinement over a scan sequence (mcl_refine_poses_sequence): Args as above -- beams holds the S used-beam
+// lists one after the other, nb their total -- and what joins the scans.
+struct SeqArgs {
+    Args a;
+    const double *off;              // M x nt x S triples (ax, ay, theta_s), formed on the host (RS1)
+    const int32_t *beam_begin;      // S + 1: scan s owns beams[beam_begin[s] .. beam_begin[s + 1])
+    int S;
+};
+
+// k_refine_score's decomposition: one lane per window pose i = m * n_win + w, ix fastest.  A wave may straddle two headings or two
+// seeds, so the row (m, it) of the table is per lane: per (lane, scan) one 24-byte triple, one sincos and two cell coordinates
+// (RS2), nothing against the beams.  The bounds of a scan's beam list and every beam's pair are wave-uniform.  k_search_score_seq's
+// loop: the scans outside, the beams inside; one accumulator per scan -- the in-order sum of LF5, what k_lfield gives for the pose
+// of RS2 -- folded into the total in scan order (RS4).  Lf is staged once per workgroup, not once per scan.  Stores score[i] alone.
+template <bool LDS_TABLE>
+__global__ __launch_bounds__(kThreads) void k_refine_score_seq(SeqArgs q)
+{
+    extern __shared__ float s_lf[];
+    const Args &a = q.a;
+    const float *lf = a.lf;
+    if constexpr (LDS_TABLE) {
+        for (int k = threadIdx.x; k <= a.K; k += kThreads) s_lf[k] = a.lf[k];
+        __syncthreads();
+        lf = s_lf;
+    }
+    const int32_t i = (int32_t)(blockIdx.x * (uint32_t)kThreads + threadIdx.x);
+    if (i >= a.n_total) return;
+    const int32_t m = i / a.win.n_win, w = i - m * a.win.n_win;
+    int32_t dx, dy, dt;
+    offsets(a.win, w, dx, dy, dt);
+    const double x = coord(a.seeds[m], dx, a.win.sx);
+    const double y = coord(a.seeds[(size_t)a.M + m], dy, a.win.sx);
+    const double W = (double)a.W, H = (double)a.H;
+    const float off = lf[a.K];
+    const double *o = q.off + ((size_t)m * (size_t)a.win.nt + (size_t)(dt + a.win.half_theta)) * (size_t)q.S * 3;
+    double total = 0.0;
+    for (int sc = 0; sc < q.S; ++sc, o += 3) {
+        double s, c;
+        sincos(o[2], &s, &c);
+        const double px = mcl::lf_cell_coord(__dadd_rn(x, o[0]), a.ox, a.inv_res), py = mcl::lf_cell_coord(__dadd_rn(y, o[1]), a.oy, a.inv_res);
+        const int j1 = q.beam_begin[sc + 1];
+        double acc = 0.0;
+#pragma unroll 4
+        for (int j = q.beam_begin[sc]; j < j1; ++j)
+            acc += (double)mcl::lf_beam_value(a.beams[j], s, c, px, py, W, H, a.W, a.D, lf, off);
+        total += acc;
+    }
+    a.score[i] = total;
+}
+
 // One workgroup per seed.  Pass 1: every lane keeps the best (R3) of its window poses l, l + 256, ...; a tree over the lanes finds
 // the window's (the order is total: any association gives the same pose).  Pass 2: every lane adds R4's ten terms of the same
 // poses in ascending order, a fixed tree adds the 256 partial sums; lane 0 writes the record.

@@ -56,7 +56,7 @@ EXPORTS = [
     "mcl_default_search_prune_config", "mcl_global_search_pruned", "mcl_get_search_bounds", "mcl_host_search_blocks", "mcl_host_lf_pool",
     "mcl_host_search_bound_table", "mcl_host_search_prune_next", "mcl_global_search_sequence_pruned",
     "mcl_default_refine_config", "mcl_refine_poses", "mcl_refine_poses_beam", "mcl_get_refine_scores", "mcl_get_refine_bytes", "mcl_host_refine_window",
-    "mcl_host_refine_reduce",
+    "mcl_host_refine_reduce", "mcl_refine_poses_sequence", "mcl_host_refine_sequence_offsets",
     "mcl_default_recovery_config", "mcl_set_recovery", "mcl_get_recovery_state", "mcl_set_recovery_state", "mcl_host_recovery_step",
     "mcl_set_recovery_proposal", "mcl_get_recovery_proposal", "mcl_host_recovery_proposal",
     "mcl_default_likelihood_field_config", "mcl_set_likelihood_field", "mcl_get_likelihood_field", "mcl_get_likelihood_table",
@@ -174,6 +174,7 @@ REFINE_DTYPE = np.dtype([("best", np.float64, (3,)), ("best_log_likelihood", np.
                          ("weight_sum", np.float64)])
 assert REFINE_DTYPE.itemsize == 152 and C.sizeof(RefineConfig) == 40
 MAX_REFINE_SEEDS, MAX_REFINE_WINDOW = 4096, 32768
+MAX_REFINE_SEQ_ROWS = 1 << 21    # MCL_REFINE_SEQ_MAX_ROWS
 
 
 class EngineError(RuntimeError):
@@ -297,6 +298,10 @@ def load_library(legacy=False):
         lib.mcl_get_refine_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         lib.mcl_host_refine_window.argtypes = [C.POINTER(RefineConfig), C.c_void_p, C.c_float, C.c_void_p, C.c_size_t]
         lib.mcl_host_refine_reduce.argtypes = [C.POINTER(RefineConfig), C.c_void_p, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.mcl_refine_poses_sequence.argtypes = [C.c_void_p, C.POINTER(RefineConfig), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                                  C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        lib.mcl_host_refine_sequence_offsets.argtypes = [C.POINTER(RefineConfig), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                                         C.c_size_t]
         lib.mcl_init_particles_mixture.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                                    C.c_int64]
         lib.mcl_default_recovery_config.argtypes = [C.POINTER(RecoveryConfig)]
@@ -728,6 +733,29 @@ def host_refine_reduce(seed, resolution, scores, **fields) -> np.ndarray:
     if rc != MCL_OK:
         raise EngineError(f"mcl_host_refine_reduce rc={rc}", rc)
     return out[0]
+
+
+def host_refine_sequence_offsets(seeds, rel, **fields) -> np.ndarray:
+    """The table a refinement over a scan sequence uploads (mcl_host_refine_sequence_offsets, rule RS1; no device needed): shape
+    (M, nt, S, 3), [m, it, s] = (ax, ay, theta_s) -- scan s's displacement from the anchor in the map frame at window heading it
+    of seed m, and its heading.  `seeds`: (M, 3) rows of (x, y, theta), or one; `rel`: (S, 3) rows of (dx, dy, dtheta) in the
+    anchor's frame.  `fields` override mcl_default_refine_config."""
+    c = default_refine_config(**fields)
+    p = _rel_rows(seeds)
+    r = _rel_rows(rel)
+    M, S, nt = p.shape[0], r.shape[0], 2 * int(c.half_theta) + 1
+    rows = M * nt * S
+    if rows > MAX_REFINE_SEQ_ROWS:                            # (RS1's cap, here too: such a table is never allocated)
+        raise EngineError(f"mcl_host_refine_sequence_offsets rc={MCL_ERR_INVALID_ARG}: {rows} rows, more than {MAX_REFINE_SEQ_ROWS}",
+                          MCL_ERR_INVALID_ARG)
+    # an empty table (no seed, no scan, a refused half_theta) still goes to the C call, which names the refusal by its status
+    out = np.empty((M, nt, S, 3) if rows > 0 else (1, 1, 1, 3), np.float64)
+    pc = _c(p.T, np.float64)                                  # column-major, as the refinement takes its seeds
+    rc = load_library().mcl_host_refine_sequence_offsets(C.byref(c), _p(pc) if M else None, C.c_int32(M), _p(r) if S else None,
+                                                         C.c_int32(S), _p(out), C.c_size_t(out.size))
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_refine_sequence_offsets rc={rc}", rc)
+    return out
 
 
 def seed_counts(log_likelihoods, n) -> np.ndarray:
@@ -1185,6 +1213,43 @@ class Engine:
         self.set_recovery_proposal(means, covs, w)
         return hits
 
+    def propose_from_scans(self, scans, rel, max_hits=16, refine=True, weights="equal", cov=None, refine_fields=None, pruned=True,
+                           **search_fields):
+        """propose_from_scan over a scan sequence joined by odometry: the hits of global_search_sequence_pruned
+        (pruned=False: of global_search_sequence), refined by refine_poses_sequence against the same scans, so that the few
+        hypotheses the proposal holds are ranked by every scan and not by the anchor's alone.  Likelihood-field model only
+        (MCL_ERR_NOT_READY otherwise; the model is never switched).  propose_from_scan's rules: hits at -inf dropped, one
+        component per hit from the refined mean and covariance (refine=False: the hit poses with `cov`, default one lattice
+        step), weights "equal" or "likelihood" (seed_counts' shares of the summed scores), the proposal cleared when no hit is
+        left.  Returns the hits.
+            if e.recovery_state()[2] > 0: e.propose_from_scans(scans, relative_poses(odom))
+            e.update(action, scans[-1])"""
+        if weights not in ("equal", "likelihood"):
+            raise ValueError('weights must be "equal" or "likelihood"')
+        if self.lib.mcl_get_likelihood_table(self._h, None, C.c_size_t(0), None) != MCL_OK:
+            raise EngineError("propose_from_scans: needs the likelihood-field model (the sequence searches and refine_poses_sequence read its field)",
+                              MCL_ERR_NOT_READY)
+        search = self.global_search_sequence_pruned if pruned else self.global_search_sequence
+        hits, _ = search(scans, rel, max_hits=max_hits, **search_fields)
+        hits = hits[np.isfinite(hits["log_likelihood"])]
+        if hits.size == 0:
+            self.set_recovery_proposal(None)
+            return hits
+        ll = hits["log_likelihood"]
+        if refine:
+            r, _ = self.refine_poses_sequence(hits["pose"], scans, rel, **(refine_fields or {}))
+            means, covs, ll = r["mean"], r["cov"], r["best_log_likelihood"]
+        else:
+            means = hits["pose"]
+            if cov is None:
+                sc = default_search_config(**search_fields)
+                res = getattr(self, "map_resolution", 0.0)
+                cov = np.diag([(sc.stride_cells * res) ** 2, (sc.stride_cells * res) ** 2, (2.0 * np.pi / sc.n_headings) ** 2])
+            covs = np.broadcast_to(_c(cov, np.float64).reshape(3, 3), (hits.size, 3, 3))
+        w = seed_counts(ll, 1 << 30).astype(np.float64) if weights == "likelihood" else None
+        self.set_recovery_proposal(means, covs, w)
+        return hits
+
     # -- likelihood-field sensor model (off by default; DESIGN.md §4.10)
     def set_likelihood_field(self, on=True, **fields):
         """Switches the likelihood-field sensor model on with mcl_default_likelihood_field_config's values (AMCL's) overridden by
@@ -1390,7 +1455,7 @@ class Engine:
         them from odometry).  Returns what global_search returns, plus n_scans; used_beams counts all scans' beams.
             rel = relative_poses(odom)
             hits, _ = e.global_search_sequence(scans, rel)
-            r, _ = e.refine_poses(hits["pose"], scans[-1])"""
+            r, _ = e.refine_poses_sequence(hits["pose"], scans, rel)"""
         c = default_search_config(**fields)
         o = _c(np.atleast_2d(np.asarray(scans, np.float32)), np.float32)
         if o.ndim != 2:
@@ -1521,9 +1586,37 @@ class Engine:
         return out, dict(n_win=int(st[0]), n_poses=int(st[1]), used_beams=int(st[2]), device_bytes=int(st[3]), rays=int(st[4]),
                          level3_rays=int(st[5]))
 
+    def refine_poses_sequence(self, poses, scans, rel, **fields):
+        """refine_poses against a sequence of scans joined by odometry (mcl_refine_poses_sequence): every seed and
+        every window pose is the robot's pose at the anchor, and scan s is scored from where that pose puts the robot at scan s,
+        so the records keep the ranking of the sequence search that made the seeds.  `scans`: (S, B) ranges; `rel`: (S, 3) rows
+        of (dx, dy, dtheta), the pose at scan s in the anchor's frame (relative_poses makes them from odometry).  Returns
+        (records, {refine_poses' keys, n_scans}); used_beams counts all scans' beams, the log-likelihoods are summed scores.
+            rel = relative_poses(odom)
+            hits, _ = e.global_search_sequence_pruned(scans, rel)
+            r, _ = e.refine_poses_sequence(hits["pose"], scans, rel)
+            e.init_particles_mixture(r["mean"], r["cov"], seed_counts(r["best_log_likelihood"], n))"""
+        c = default_refine_config(**fields)
+        p = self._query_poses(poses)
+        M = p.shape[1]
+        o = _c(np.atleast_2d(np.asarray(scans, np.float32)), np.float32)
+        if o.ndim != 2:
+            raise ValueError("scans must be (S, B)")
+        r = _rel_rows(rel)
+        if r.shape[0] != o.shape[0]:
+            raise ValueError("scans and rel must have one row per scan")
+        S = o.shape[0]
+        out = np.zeros(M, REFINE_DTYPE)
+        st = np.zeros(5, np.uint64)
+        self._chk(self.lib.mcl_refine_poses_sequence(self._h, C.byref(c), _p(p) if M else None, C.c_int32(M), _p(o) if o.size else None,
+                                                     _p(r) if S else None, C.c_int32(S), C.c_int32(o.shape[1]),
+                                                     _p(out) if M else None, _p(st)), "mcl_refine_poses_sequence")
+        self._refine_shape = (M, int(st[0]))
+        return out, dict(n_win=int(st[0]), n_poses=int(st[1]), used_beams=int(st[2]), device_bytes=int(st[3]), n_scans=int(st[4]))
+
     def refine_scores(self):
-        """The score volume of the last refine_poses or refine_poses_beam (mcl_get_refine_scores): (M, n_win) doubles, window index
-        ix fastest."""
+        """The score volume of the last refine_poses, refine_poses_beam or refine_poses_sequence (mcl_get_refine_scores): (M, n_win)
+        doubles, window index ix fastest."""
         shape = getattr(self, "_refine_shape", None) or (1, 1)
         out = np.empty(shape, np.float64)
         self._chk(self.lib.mcl_get_refine_scores(self._h, _p(out), C.c_size_t(out.size)), "mcl_get_refine_scores")
