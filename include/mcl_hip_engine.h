@@ -951,6 +951,62 @@ int mcl_host_likelihood_field(const int8_t *data, uint32_t width, uint32_t heigh
 int mcl_host_likelihood_table(const mcl_config_t *cfg, const mcl_likelihood_field_config_t *c, float resolution, float *out,
                               size_t n, int32_t *K);
 
+/* ---- beam skipping for the likelihood field (AMCL's likelihood_field_prob with do_beamskip, beam_skip_distance,
+ *      beam_skip_threshold, beam_skip_error_threshold) ---------------------------------------------------------
+ * Off by default; it can only be on while the likelihood field is.  A beam whose measured end point lies near a mapped obstacle
+ * for only a small share of the particle set -- an obstacle that is not in the map -- is left out of every particle's weight.
+ * It applies to mcl_update, mcl_update_scan and mcl_sensor_update and only changes how the log-weights are produced; everything
+ * after them (weights, resampling, adaptive resampling, KLD, recovery, clusters, expected pose) is unchanged.  The side calls
+ * (mcl_score_poses, every mcl_global_search*, every mcl_refine_poses*, and with them propose_from_scan of the Python binding)
+ * score poses, not a set: they ignore it.
+ *   BS1 agreement.  Ka = ceil((distance_m / res)^2), the expression K is formed with (res the float resolution widened), held
+ *     at 65536.  A used beam (LF3) of a particle agrees iff its end cell (LF4, the same rotation-form arithmetic) is on the map
+ *     and D[cell] < Ka -- for an integer squared distance d^2 exactly d * res < distance_m.  Off the map a beam never agrees
+ *     (AMCL's !MAP_VALID).  With Ka > K every end point on the map agrees, as with AMCL's clamped occ_dist.
+ *   BS2 counts.  cnt[j] = the number of the update's n particles (the set this update weights: after resampling and motion)
+ *     whose beam j agrees.  Integers added in any order: exact, and the same for every schedule.
+ *   BS3 keep.  AMCL keeps a beam iff cnt / (double)n > threshold.  The host forms, once per update, min_count = the least integer
+ *     c in [1, n + 1] with (double)c / (double)n > threshold (searched up and down from floor(threshold * n): exact whatever the
+ *     rounding); the device compares integers: kept iff cnt[j] >= min_count.
+ *   BS4 too many skipped.  n_skipped = the number of used beams not kept; min_skipped = the least integer s >= 0 with
+ *     (double)s >= error_threshold * (double)n_used, held at n_used + 1.  If n_skipped >= min_skipped, integrate_all = 1 and every
+ *     used beam is kept (AMCL: the filter may have converged to a wrong pose).  AMCL's loop also counts out-of-range beams as
+ *     skipped; here only used beams enter either side of the comparison.  error_threshold = 0 always integrates all, a value
+ *     above 1 never does (a scan without a used beam has nothing to keep either way: 0 >= 0 sets integrate_all).
+ *   BS5 log-weight.  logw_i = sum over the kept used beams, in beam order, of (double)Lf[D[cell_ij]]: LF5 over the kept beams, the
+ *     in-order fp64 sum.  So an update with beam skipping equals, bit for bit, the same update without it on the scan whose
+ *     skipped beams read NaN: log-weights, weights, resample indices, the next particles, the pose, the KLD state and the
+ *     recovery averages (recovery keeps dividing by B, as it does for unused beams).
+ *   BS6 state.  After such an update mcl_get_beam_skip_state reads, per scan beam j in [0, B): counts[j] (0 for an unused beam)
+ *     and kept[j] (0 not used, 1 summed, 2 skipped), and the record below.  counts, kept and st may each be NULL; n must be B.
+ *     MCL_ERR_NOT_READY before the first such update and while the feature is off.
+ *   MCL_ERR_INVALID_ARG for distance_m not finite and > 0, threshold outside [0, 1], error_threshold not finite and >= 0,
+ *     reserved != 0.  mcl_set_beam_skip returns MCL_ERR_NOT_READY while the likelihood field is off;
+ *     mcl_set_likelihood_field(NULL) switches beam skipping off too, re-setting the field's config while it is on keeps it.  The
+ *     likelihood field's refusals (communicator, device group, mcl_stage_*, weight_mode PRODUCT) cover this feature: it cannot be
+ *     on without the field.  Agreement is counted over the set being weighted, with no memory across updates; there is no pz^3
+ *     term and no gaussian_norm. */
+typedef struct {
+    double distance_m;                      /* default 0.5 (AMCL's beam_skip_distance)                                        */
+    double threshold;                       /* default 0.3 (beam_skip_threshold)                                              */
+    double error_threshold;                 /* default 0.9 (beam_skip_error_threshold)                                        */
+    int32_t reserved[2];                    /* must be 0                                                                      */
+} mcl_beam_skip_config_t;
+typedef struct {
+    int64_t n_particles, min_count;         /* BS2's n, BS3                                                                   */
+    int32_t n_used, n_kept, n_skipped, min_skipped, integrate_all, ka;     /* n_kept = n_used when integrate_all              */
+} mcl_beam_skip_state_t;
+void mcl_default_beam_skip_config(mcl_beam_skip_config_t *c);
+int mcl_set_beam_skip(mcl_engine_t *h, const mcl_beam_skip_config_t *c);                 /* NULL = off (the default) */
+int mcl_get_beam_skip_state(mcl_engine_t *h, uint32_t *counts, uint8_t *kept, size_t n, mcl_beam_skip_state_t *st);
+/* BS1 / BS3 / BS4 and the mask on the host, without a device: the functions the engine itself forms its thresholds with.  Any
+ * output may be NULL.  n_particles in [1, 2^31), n_used >= 0; counts_used / kept_used hold the used beams only, kept_used in
+ * BS6's coding (1 summed, 2 skipped); counts_used may be NULL only with n_used = 0. */
+int mcl_host_beam_skip_thresholds(const mcl_beam_skip_config_t *c, float resolution, int64_t n_particles, int32_t n_used,
+                                  int32_t *ka, int64_t *min_count, int32_t *min_skipped);
+int mcl_host_beam_skip_plan(const mcl_beam_skip_config_t *c, const uint32_t *counts_used, int32_t n_used, int64_t n_particles,
+                            uint8_t *kept_used, int32_t *n_skipped, int32_t *integrate_all);
+
 /* ---- odometry motion models and covariance-based pose initialisation (Probabilistic Robotics Table 5.6,
  *      sample_motion_model_odometry; AMCL's robot_model_type differential / omnidirectional with alpha1..alpha5;
  *      DESIGN.md §4.11) ---------------------------------------------------------------------------------------------------

@@ -865,18 +865,75 @@ int lf_build(mcl_engine *h)
     return MCL_OK;
 }
 
-// The sensor stage of a likelihood-field update: the used beams of the scan in beam order (LF3), one copy, k_lfield (LF4, LF5).
-// EV_QUERY / EV_K0 .. EV_K1 bracket the kernel (stage 3 and mcl_get_ray_kernel_ms).
+// The sensor stage with beam skipping on, in k_lfield's place between the same events: the counting pass (BS1,
+// BS2; it also leaves the full sums in d_logw), the plan (BS3, BS4, the state record) and the summing pass over the kept beams
+// (BS5), with no host wait between them -- n and nb are known here, so min_count and min_skipped are.  d_bs_cnt is zeroed by the
+// caller, in-stream.
+int launch_lfield_skip(mcl_engine *h, int64_t n, int nb)
+{
+    mcl::LfArgs a{};
+    a.x = h->d_x[h->cur]; a.y = h->d_y[h->cur]; a.th = h->d_th[h->cur]; a.n = n;
+    a.beams = h->d_lf_beams; a.nb = nb;
+    a.D = h->d_lf_D; a.W = h->W; a.H = h->H;
+    a.ox = h->ox; a.oy = h->oy; a.inv_res = 1.0 / h->res;
+    a.lf = h->d_lf_tab; a.K = h->lf_K;
+    a.logw = h->d_logw;
+    const int ka = mcl_host::bs_ka(&h->bs, (float)h->res);
+    const int64_t min_count = mcl_host::bs_min_count(h->bs.threshold, n);
+    const int min_skipped = mcl_host::bs_min_skipped(h->bs.error_threshold, nb);
+    const bool lds_table = h->lf_K < mcl::kLfLdsEntries;
+    const int tab_words = lds_table ? (h->lf_K + 1 + 3) & ~3 : 0;
+    const bool lds_cnt = nb <= mcl::kBsLdsBeams && tab_words + nb <= mcl::kLfLdsEntries;
+    mcl::BsCountArgs b{};
+    b.cnt = h->d_bs_cnt; b.tiles = (n + 255) / 256; b.ka = (uint32_t)ka; b.cnt_off = tab_words;
+    const size_t lds = (size_t)(tab_words + (lds_cnt ? nb : 0)) * sizeof(float);
+    const dim3 grid1((unsigned)std::min<int64_t>(b.tiles, (int64_t)h->num_cu * mcl::kBsWorkgroupsPerCu)), grid((unsigned)b.tiles);
+    if (lds_table && lds_cnt)
+        hipLaunchKernelGGL((mcl::k_lfield_agree<true, true>), grid1, dim3(256), lds, h->stream, a, b);
+    else if (lds_table)
+        hipLaunchKernelGGL((mcl::k_lfield_agree<true, false>), grid1, dim3(256), lds, h->stream, a, b);
+    else if (lds_cnt)
+        hipLaunchKernelGGL((mcl::k_lfield_agree<false, true>), grid1, dim3(256), lds, h->stream, a, b);
+    else
+        hipLaunchKernelGGL((mcl::k_lfield_agree<false, false>), grid1, dim3(256), lds, h->stream, a, b);
+    mcl::BsPlanArgs p{};
+    p.cnt = h->d_bs_cnt; p.beams = h->d_lf_beams; p.nb = nb; p.n = n; p.min_count = min_count; p.min_skipped = min_skipped; p.ka = ka;
+    p.kept = h->d_bs_kept; p.beams_kept = h->d_bs_beams; p.st = h->d_bs_state;
+    hipLaunchKernelGGL(mcl::k_lf_skip_plan, dim3(1), dim3(256), 0, h->stream, p);
+    a.beams = h->d_bs_beams;
+    if (lds_table)
+        hipLaunchKernelGGL(mcl::k_lfield_kept<true>, grid, dim3(256), (size_t)(h->lf_K + 1) * sizeof(float), h->stream, a, h->d_bs_state.p);
+    else
+        hipLaunchKernelGGL(mcl::k_lfield_kept<false>, grid, dim3(256), 0, h->stream, a, h->d_bs_state.p);
+    HIPCHK(h, hipGetLastError());
+    h->bs_B = h->B;
+    h->bs_idx.resize((size_t)nb);
+    h->bs_have = true;
+    return MCL_OK;
+}
+
+// The sensor stage of a likelihood-field update: the used beams of the scan in beam order (LF3), one copy, k_lfield (LF4, LF5) --
+// or, with beam skipping on, the zeroed counters and launch_lfield_skip's three kernels in its place.
+// EV_QUERY / EV_K0 .. EV_K1 bracket the kernels (stage 3 and mcl_get_ray_kernel_ms).
 int launch_lfield(mcl_engine *h, const float *obs, int stride, int64_t n)
 {
     MCL_TRY(h->h_lf_beams.reserve(h, (size_t)h->B));
     MCL_TRY(h->d_lf_beams.reserve(h, (size_t)h->B));
-    const int nb = mcl_host::lf_used_beams(h, obs, stride, h->h_lf_beams);
+    if (h->bs_on) { h->bs_have = false; h->bs_idx.resize((size_t)h->B); }
+    const int nb = mcl_host::lf_used_beams(h, obs, stride, h->h_lf_beams, h->bs_on ? h->bs_idx.data() : nullptr);
     if (nb > 0)
         HIPCHK(h, hipMemcpyAsync(h->d_lf_beams, h->h_lf_beams, (size_t)nb * sizeof(double2), hipMemcpyHostToDevice, h->stream));
+    if (h->bs_on) {
+        MCL_TRY(h->d_bs_cnt.reserve(h, (size_t)h->B));
+        MCL_TRY(h->d_bs_kept.reserve(h, (size_t)h->B));
+        MCL_TRY(h->d_bs_beams.reserve(h, (size_t)h->B));
+        MCL_TRY(h->d_bs_state.reserve(h, 1));
+        if (nb > 0) HIPCHK(h, hipMemsetAsync(h->d_bs_cnt, 0, (size_t)nb * sizeof(unsigned int), h->stream));
+    }
     HIPCHK(h, hipEventRecord(h->ev[EV_QUERY], h->stream));
     HIPCHK(h, hipEventRecord(h->ev[EV_K0], h->stream));
-    const int rc = mcl_host::launch_lfield_on(h, h->d_x[h->cur], h->d_y[h->cur], h->d_th[h->cur], n, h->d_lf_beams, nb, h->d_logw);
+    const int rc = h->bs_on ? launch_lfield_skip(h, n, nb)
+                            : mcl_host::launch_lfield_on(h, h->d_x[h->cur], h->d_y[h->cur], h->d_th[h->cur], n, h->d_lf_beams, nb, h->d_logw);
     if (rc != MCL_OK) return rc;
     HIPCHK(h, hipEventRecord(h->ev[EV_K1], h->stream));
     h->max_partials_ready = false;
@@ -2526,6 +2583,7 @@ int mcl_set_likelihood_field(mcl_engine_t *h, const mcl_likelihood_field_config_
     h->far_fresh = true;
     if (!c) {
         h->lf_on = false;
+        h->bs_on = h->bs_have = false;       // (beam skipping cannot be on without the field)
         return MCL_OK;
     }
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -2534,8 +2592,46 @@ int mcl_set_likelihood_field(mcl_engine_t *h, const mcl_likelihood_field_config_
     h->lf_K = -1;
     if (h->have_map) {
         const int rc = lf_build(h);
-        if (rc) { h->lf_on = false; return rc; }
+        if (rc) { h->lf_on = false; h->bs_on = h->bs_have = false; return rc; }
     }
+    return MCL_OK;
+}
+
+int mcl_set_beam_skip(mcl_engine_t *h, const mcl_beam_skip_config_t *c)
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    if (c) {
+        if (!h->lf_on) return fail(h, MCL_ERR_NOT_READY, "beam skipping needs the likelihood field (mcl_set_likelihood_field) switched on first");
+        if (const char *why = bs_invalid(c)) return fail(h, MCL_ERR_INVALID_ARG, why);
+        h->bs = *c;
+    }
+    h->bs_on = c != nullptr;
+    h->bs_have = false;
+    return MCL_OK;
+}
+
+int mcl_get_beam_skip_state(mcl_engine_t *h, uint32_t *counts, uint8_t *kept, size_t n, mcl_beam_skip_state_t *st)
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    if (!h->bs_on || !h->bs_have) return fail(h, MCL_ERR_NOT_READY, "beam skipping is off or no update has run with it");
+    if (n != (size_t)h->bs_B) return fail(h, MCL_ERR_INVALID_ARG, "counts and kept have one entry per beam of the scan");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const size_t nb = h->bs_idx.size();
+    std::vector<uint32_t> cnt(nb);
+    std::vector<uint8_t> kp(nb);
+    mcl_beam_skip_state_t rec{};
+    if (nb && counts) HIPCHK(h, hipMemcpyAsync(cnt.data(), h->d_bs_cnt, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (nb && kept) HIPCHK(h, hipMemcpyAsync(kp.data(), h->d_bs_kept, nb, hipMemcpyDeviceToHost, h->stream));
+    if (st) HIPCHK(h, hipMemcpyAsync(&rec, h->d_bs_state, sizeof rec, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (counts) std::memset(counts, 0, n * sizeof(uint32_t));
+    if (kept) std::memset(kept, 0, n);
+    for (size_t k = 0; k < nb; ++k) {
+        const size_t j = (size_t)h->bs_idx[k];
+        if (counts) counts[j] = cnt[k];
+        if (kept) kept[j] = kp[k];
+    }
+    if (st) *st = rec;
     return MCL_OK;
 }
 
@@ -3180,13 +3276,14 @@ void launch_pack_records(hipStream_t stream, const double *x, const double *y, c
 {
     hipLaunchKernelGGL(mcl::k_pack_records, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x, y, th, n, out);
 }
-int lf_used_beams(const mcl_engine *h, const float *obs, int stride, double2 *out)
+int lf_used_beams(const mcl_engine *h, const float *obs, int stride, double2 *out, int32_t *idx)
 {
     const double inv_res = 1.0 / h->res;
     int nb = 0;
     for (int j = 0; j < h->B; ++j) {
         const double r = (double)obs[(size_t)j * stride];
         if (!(r >= 0.0 && r < h->cfg.max_range_m)) continue;             // NaN, +-inf, negative, max range: no contribution
+        if (idx) idx[nb] = j;
         out[nb++] = make_double2(r * h->beam_cs_host[(size_t)j].x * inv_res, r * h->beam_cs_host[(size_t)j].y * inv_res);
     }
     return nb;

@@ -308,6 +308,17 @@ struct mcl_engine {
     std::vector<float> lf_tab;
     DevBuf<double2> d_lf_beams;
     HostBuf<double2> h_lf_beams;
+    // beam skipping (mcl_set_beam_skip; only while lf_on): the per-beam counters, the mask, the compacted beam
+    // list and the state record of the last such update, all reserved by the first update that runs with it on.  bs_have: that
+    // state is readable; bs_idx: the scan beam of every used beam of that update (lf_used_beams), bs_B its scan's beam count
+    bool bs_on = false, bs_have = false;
+    mcl_beam_skip_config_t bs{};
+    int bs_B = 0;
+    std::vector<int32_t> bs_idx;
+    DevBuf<unsigned int> d_bs_cnt;
+    DevBuf<uint8_t> d_bs_kept;
+    DevBuf<double2> d_bs_beams;
+    DevBuf<mcl_beam_skip_state_t> d_bs_state;
     // motion model (mcl_set_motion_model): REFERENCE, or an odometry model whose per-update scalars go to the
     // k_resample_odo* kernels as plain arguments
     mcl_motion_config_t motion{};
@@ -397,8 +408,9 @@ void launch_stage_pack(hipStream_t stream, const unsigned long long *d_result, d
 void launch_pack_records(hipStream_t stream, const double *x, const double *y, const double *th, int64_t n, double4 *out);
 void launch_group_max(hipStream_t stream, const mcl::GroupMaxArgs &a);
 // the likelihood field outside the update (mcl_query.hip): the used beams of a scan in beam order (LF3) into `out` (B entries of
-// room), their number returned; k_lfield over n poses and nb such beams on the engine's stream, the caller's buffers throughout
-int lf_used_beams(const mcl_engine *h, const float *obs, int stride, double2 *out);
+// room), their number returned, with `idx` given also the scan beam of each; k_lfield over n poses and nb such beams on the engine's
+// stream, the caller's buffers throughout
+int lf_used_beams(const mcl_engine *h, const float *obs, int stride, double2 *out, int32_t *idx = nullptr);
 int launch_lfield_on(mcl_engine *h, const double *x, const double *y, const double *th, int64_t n, const double2 *d_beams, int nb,
                      double *logw);
 }  // namespace mcl_host

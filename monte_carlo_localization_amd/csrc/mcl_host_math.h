@@ -36,6 +36,11 @@ std::string recov_proposal(int32_t M, const double *means, const double *covs, c
 const char *lf_invalid(const mcl_likelihood_field_config_t *c);
 int lf_cap(const mcl_likelihood_field_config_t *c, float resolution);
 void lf_table(const mcl_config_t &cfg, const mcl_likelihood_field_config_t &c, double res, int K, std::vector<float> &t);
+// beam skipping: BS1's Ka (held at 65536), BS3's min_count, BS4's min_skipped
+const char *bs_invalid(const mcl_beam_skip_config_t *c);
+int bs_ka(const mcl_beam_skip_config_t *c, float resolution);
+int64_t bs_min_count(double threshold, int64_t n);
+int32_t bs_min_skipped(double error_threshold, int32_t n_used);
 const char *motion_invalid(const mcl_motion_config_t *c);
 const char *gaussian_factor(const double cov[9], double L[6]);
 const char *search_invalid(const mcl_search_config_t *c);

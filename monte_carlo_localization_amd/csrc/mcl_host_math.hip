@@ -368,6 +368,46 @@ void lf_table(const mcl_config_t &cfg, const mcl_likelihood_field_config_t &c, d
     }
 }
 
+// ---- beam skipping (mcl_set_beam_skip): the integer thresholds of an update, formed once on the host
+const char *bs_invalid(const mcl_beam_skip_config_t *c)
+{
+    if (!(std::isfinite(c->distance_m) && c->distance_m > 0.0)) return "beam skipping: distance_m must be finite and > 0";
+    if (!(c->threshold >= 0.0 && c->threshold <= 1.0)) return "beam skipping: threshold must lie in [0, 1]";
+    if (!(std::isfinite(c->error_threshold) && c->error_threshold >= 0.0)) return "beam skipping: error_threshold must be finite and >= 0";
+    if (c->reserved[0] != 0 || c->reserved[1] != 0) return "beam skipping: reserved must be 0";
+    return nullptr;
+}
+
+// BS1: Ka = ceil((distance_m / res)^2), K's expression; held at 65536 (every D is below it, the off-map sentinel is not)
+int bs_ka(const mcl_beam_skip_config_t *c, float resolution)
+{
+    const double q = c->distance_m / (double)resolution;
+    const double k = std::ceil(q * q);
+    return k < 65536.0 ? (int)k : 65536;
+}
+
+// BS3: the least c in [1, n + 1] with (double)c / (double)n > threshold (c / n does not decrease with c, and (n + 1) / n > 1)
+int64_t bs_min_count(double threshold, int64_t n)
+{
+    const double dn = (double)n;
+    int64_t c = (int64_t)std::floor(threshold * dn);
+    c = std::min(std::max<int64_t>(c, 1), n + 1);
+    while (c <= n && !((double)c / dn > threshold)) ++c;
+    while (c > 1 && (double)(c - 1) / dn > threshold) --c;
+    return c;
+}
+
+// BS4: the least s >= 0 with (double)s >= error_threshold * (double)n_used, held at n_used + 1
+int32_t bs_min_skipped(double error_threshold, int32_t n_used)
+{
+    const double x = error_threshold * (double)n_used;
+    if (x > (double)n_used) return n_used + 1;
+    int64_t s = (int64_t)std::ceil(x);
+    while (s > 0 && (double)(s - 1) >= x) --s;
+    while ((double)s < x) ++s;
+    return (int32_t)std::min<int64_t>(s, (int64_t)n_used + 1);
+}
+
 // LF1 on the host: exact squared distances from the lower envelopes of edt_1d (columns, then rows), clamped to K
 static void lf_field_host(const int8_t *grid, int W, int H, int K, uint16_t *out)
 {
@@ -1080,6 +1120,43 @@ int mcl_host_likelihood_table(const mcl_config_t *cfg, const mcl_likelihood_fiel
     std::vector<float> t;
     lf_table(*cfg, *c, (double)resolution, k, t);
     std::memcpy(out, t.data(), n * sizeof(float));
+    return MCL_OK;
+}
+
+void mcl_default_beam_skip_config(mcl_beam_skip_config_t *c)
+{
+    if (!c) return;
+    *c = mcl_beam_skip_config_t{};
+    c->distance_m = 0.5; c->threshold = 0.3; c->error_threshold = 0.9;                // AMCL's defaults
+}
+
+static bool bs_host_args_ok(const mcl_beam_skip_config_t *c, int64_t n_particles, int32_t n_used)
+{
+    return c && !bs_invalid(c) && n_particles >= 1 && n_particles <= 0x7fffffff && n_used >= 0 && n_used < 0x7fffffff;
+}
+
+int mcl_host_beam_skip_thresholds(const mcl_beam_skip_config_t *c, float resolution, int64_t n_particles, int32_t n_used,
+                                  int32_t *ka, int64_t *min_count, int32_t *min_skipped)
+{
+    if (!bs_host_args_ok(c, n_particles, n_used) || !(resolution > 0.0f) || !std::isfinite(resolution)) return MCL_ERR_INVALID_ARG;
+    if (ka) *ka = bs_ka(c, resolution);
+    if (min_count) *min_count = bs_min_count(c->threshold, n_particles);
+    if (min_skipped) *min_skipped = bs_min_skipped(c->error_threshold, n_used);
+    return MCL_OK;
+}
+
+int mcl_host_beam_skip_plan(const mcl_beam_skip_config_t *c, const uint32_t *counts_used, int32_t n_used, int64_t n_particles,
+                            uint8_t *kept_used, int32_t *n_skipped, int32_t *integrate_all)
+{
+    if (!bs_host_args_ok(c, n_particles, n_used) || (!counts_used && n_used > 0)) return MCL_ERR_INVALID_ARG;
+    const int64_t min_count = bs_min_count(c->threshold, n_particles);
+    int32_t skipped = 0;
+    for (int32_t j = 0; j < n_used; ++j) skipped += (int64_t)counts_used[j] < min_count;
+    const int all = skipped >= bs_min_skipped(c->error_threshold, n_used);
+    if (kept_used)
+        for (int32_t j = 0; j < n_used; ++j) kept_used[j] = all || (int64_t)counts_used[j] >= min_count ? 1 : 2;
+    if (n_skipped) *n_skipped = skipped;
+    if (integrate_all) *integrate_all = all;
     return MCL_OK;
 }
 

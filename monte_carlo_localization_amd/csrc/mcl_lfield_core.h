@@ -28,4 +28,20 @@ __device__ __forceinline__ float lf_beam_value(const double2 b, double s, double
     return v;
 }
 
+// What lf_beam_dist returns off the map (or for NaN): above every D (<= 65535) and never below Ka (<= 65536; BS1)
+constexpr uint32_t kLfOffMap = 0x10000u;
+
+// lf_beam_value's end cell (the same two FMA pairs, floors and bounds test), returning D[cell] itself, or kLfOffMap off the map:
+// the value of the beam is lf[D] (off the map Lf[K]), and it agrees (BS1) iff D < Ka.
+__device__ __forceinline__ uint32_t lf_beam_dist(const double2 b, double s, double c, double px, double py, double W, double H, int Wi,
+                                                 const uint16_t *D)
+{
+    const double fx = floor(fma(c, b.x, fma(-s, b.y, px)));
+    const double fy = floor(fma(s, b.x, fma(c, b.y, py)));
+    uint32_t d = kLfOffMap;
+    if (fx >= 0.0 && fx < W && fy >= 0.0 && fy < H)       // (false for NaN: off the map)
+        d = D[(size_t)(int)fy * (size_t)Wi + (size_t)(int)fx];
+    return d;
+}
+
 }  // namespace mcl

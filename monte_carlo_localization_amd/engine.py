@@ -61,6 +61,8 @@ EXPORTS = [
     "mcl_set_recovery_proposal", "mcl_get_recovery_proposal", "mcl_host_recovery_proposal",
     "mcl_default_likelihood_field_config", "mcl_set_likelihood_field", "mcl_get_likelihood_field", "mcl_get_likelihood_table",
     "mcl_host_likelihood_field", "mcl_host_likelihood_table",
+    "mcl_default_beam_skip_config", "mcl_set_beam_skip", "mcl_get_beam_skip_state", "mcl_host_beam_skip_thresholds",
+    "mcl_host_beam_skip_plan",
     "mcl_default_motion_config", "mcl_set_motion_model", "mcl_get_motion_model", "mcl_host_motion_scalars", "mcl_host_motion_sample",
     "mcl_init_particles_gaussian", "mcl_host_gaussian_factor", "mcl_group_set_motion_model", "mcl_group_init_particles_gaussian",
 ]
@@ -98,6 +100,20 @@ class LikelihoodFieldConfig(C.Structure):
     """mcl_likelihood_field_config_t: the likelihood-field sensor model (Engine.set_likelihood_field)."""
     _fields_ = [("z_hit", C.c_double), ("z_rand", C.c_double), ("sigma_hit_m", C.c_double), ("max_occ_dist_m", C.c_double),
                 ("reserved", C.c_int32 * 2)]
+
+
+class BeamSkipConfig(C.Structure):
+    """mcl_beam_skip_config_t: beam skipping for the likelihood field (Engine.set_beam_skip)."""
+    _fields_ = [("distance_m", C.c_double), ("threshold", C.c_double), ("error_threshold", C.c_double), ("reserved", C.c_int32 * 2)]
+
+
+class BeamSkipState(C.Structure):
+    """mcl_beam_skip_state_t: what the last update with beam skipping decided (Engine.beam_skip_state, rule BS6)."""
+    _fields_ = [("n_particles", C.c_int64), ("min_count", C.c_int64), ("n_used", C.c_int32), ("n_kept", C.c_int32),
+                ("n_skipped", C.c_int32), ("min_skipped", C.c_int32), ("integrate_all", C.c_int32), ("ka", C.c_int32)]
+
+
+assert C.sizeof(BeamSkipConfig) == 32 and C.sizeof(BeamSkipState) == 40
 
 
 class MotionConfig(C.Structure):
@@ -331,6 +347,14 @@ def load_library(legacy=False):
                                                   C.c_void_p, C.c_size_t]
         lib.mcl_host_likelihood_table.argtypes = [C.POINTER(Config), C.POINTER(LikelihoodFieldConfig), C.c_float, C.c_void_p,
                                                   C.c_size_t, C.POINTER(C.c_int32)]
+        lib.mcl_default_beam_skip_config.argtypes = [C.POINTER(BeamSkipConfig)]
+        lib.mcl_default_beam_skip_config.restype = None
+        lib.mcl_set_beam_skip.argtypes = [C.c_void_p, C.POINTER(BeamSkipConfig)]
+        lib.mcl_get_beam_skip_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(BeamSkipState)]
+        lib.mcl_host_beam_skip_thresholds.argtypes = [C.POINTER(BeamSkipConfig), C.c_float, C.c_int64, C.c_int32, C.POINTER(C.c_int32),
+                                                      C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        lib.mcl_host_beam_skip_plan.argtypes = [C.POINTER(BeamSkipConfig), C.c_void_p, C.c_int32, C.c_int64, C.c_void_p,
+                                                C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         lib.mcl_default_motion_config.argtypes = [C.POINTER(MotionConfig)]
         lib.mcl_default_motion_config.restype = None
         lib.mcl_set_motion_model.argtypes = [C.c_void_p, C.POINTER(MotionConfig)]
@@ -461,6 +485,43 @@ def host_likelihood_table(resolution, cfg: Config | None = None, **fields) -> np
     if rc != MCL_OK:
         raise EngineError(f"mcl_host_likelihood_table rc={rc}", rc)
     return out
+
+
+def default_beam_skip_config(**over) -> BeamSkipConfig:
+    """mcl_default_beam_skip_config (AMCL's defaults), with fields overridden by keyword."""
+    c = BeamSkipConfig()
+    load_library().mcl_default_beam_skip_config(C.byref(c))
+    for name, v in over.items():
+        if name not in dict(BeamSkipConfig._fields_):
+            raise AttributeError(name)
+        setattr(c, name, (C.c_int32 * 2)(*v) if name == "reserved" else v)
+    return c
+
+
+def host_beam_skip_thresholds(resolution, n_particles, n_used, **fields):
+    """(ka, min_count, min_skipped) of an update of n_particles particles with n_used used beams (mcl_host_beam_skip_thresholds,
+    rules BS1, BS3, BS4; no device needed): the integers the engine itself forms for its kernels."""
+    c = default_beam_skip_config(**fields)
+    ka, mc, ms = C.c_int32(), C.c_int64(), C.c_int32()
+    rc = load_library().mcl_host_beam_skip_thresholds(C.byref(c), np.float32(resolution), C.c_int64(int(n_particles)),
+                                                      C.c_int32(int(n_used)), C.byref(ka), C.byref(mc), C.byref(ms))
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_beam_skip_thresholds rc={rc}", rc)
+    return ka.value, mc.value, ms.value
+
+
+def host_beam_skip_plan(counts_used, n_particles, **fields):
+    """(kept_used, n_skipped, integrate_all) for the agreement counts of the used beams (mcl_host_beam_skip_plan, rules BS3, BS4; no
+    device needed): kept_used is uint8 per used beam, 1 summed, 2 skipped."""
+    c = default_beam_skip_config(**fields)
+    cnt = _c(counts_used, np.uint32).ravel()
+    kept = np.zeros(cnt.size, np.uint8)
+    ns, ia = C.c_int32(), C.c_int32()
+    rc = load_library().mcl_host_beam_skip_plan(C.byref(c), _p(cnt) if cnt.size else None, C.c_int32(cnt.size),
+                                                C.c_int64(int(n_particles)), _p(kept) if cnt.size else None, C.byref(ns), C.byref(ia))
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_beam_skip_plan rc={rc}", rc)
+    return kept, ns.value, ia.value
 
 
 def default_motion_config(**over) -> MotionConfig:
@@ -1260,6 +1321,26 @@ class Engine:
         c = default_likelihood_field_config(**fields)
         self._chk(self.lib.mcl_set_likelihood_field(self._h, C.byref(c)), "mcl_set_likelihood_field")
         return c
+
+    # -- beam skipping for the likelihood field (off by default)
+    def set_beam_skip(self, on=True, **fields):
+        """Switches beam skipping on with mcl_default_beam_skip_config's values (AMCL's) overridden by keyword (distance_m,
+        threshold, error_threshold), or off.  The likelihood field must be on; switching the field off switches this off too."""
+        if not on:
+            self._chk(self.lib.mcl_set_beam_skip(self._h, None), "mcl_set_beam_skip")
+            return
+        c = default_beam_skip_config(**fields)
+        self._chk(self.lib.mcl_set_beam_skip(self._h, C.byref(c)), "mcl_set_beam_skip")
+
+    def beam_skip_state(self):
+        """What the last update with beam skipping decided (mcl_get_beam_skip_state, rule BS6): the record's fields plus `counts`
+        (uint32) and `kept` (uint8: 0 not used, 1 summed, 2 skipped), one entry per beam of the scan."""
+        B = int(self.n_beams)
+        counts, kept, st = np.zeros(B, np.uint32), np.zeros(B, np.uint8), BeamSkipState()
+        self._chk(self.lib.mcl_get_beam_skip_state(self._h, _p(counts), _p(kept), C.c_size_t(B), C.byref(st)), "mcl_get_beam_skip_state")
+        out = {name: int(getattr(st, name)) for name, _ in BeamSkipState._fields_}
+        out["counts"], out["kept"] = counts, kept
+        return out
 
     def likelihood_field(self):
         """The device's field D of the current map: shape (H, W), uint16."""
