@@ -1148,6 +1148,11 @@ int mcl_host_sort_key(const int32_t bbox[7], const int32_t *tilemap, int32_t ntx
  * MCL_ERR_NOT_READY when the last ray stage did not order that way, MCL_ERR_INVALID_ARG for a wrong n. */
 int mcl_get_sort_order(mcl_engine_t *h, uint32_t *keys, uint32_t *perm, size_t n, int32_t bbox[7], int32_t *tilemap, size_t n_tiles,
                        int64_t *n_out, int32_t *fine);
+/* The form of the per-particle constants that ordering's gather read: *heading_form = 1 when the resampling kernel had left
+ * (heading, 0, pixel x, pixel y) and the gather took the sincos (one scattered fetch per particle), 0 for the full
+ * (cos, sin, pixel x, pixel y) beside the heading column (the first update of a set, whose keys k_sort_keys makes).
+ * MCL_ERR_NOT_READY as above. */
+int mcl_get_sort_record_form(mcl_engine_t *h, int32_t *heading_form);
 
 /* ---- multi-GPU staging (one engine per rank; collectives are the host's) -- */
 /* Device pointers of engine-owned buffers so the host can hand them to RCCL without copies. */

@@ -280,6 +280,7 @@ struct RayPlan {
     // what the resampling launch left for this stage (RayHandoff): constants in d_pc | ordering by the previous layout | (key, index)
     // pairs written | the few words cleared, given clear_passed | the wait for ev_obs is this launch's to issue
     bool constants_ready = false, stale_layout = false, keys_written = false, clear_folded = false, obs_wait = false;
+    bool heading_form = false;                              // d_pc holds the heading form and the radix gather of this launch reads it
     mcl::PrepClear clear_passed{};
 };
 
@@ -367,6 +368,12 @@ RayPlan plan_rays(mcl_engine *h, int64_t n, bool force_skip, bool direct_table)
     p.timed = !p.lists && !h->capturing && !direct_table;
     const RayHandoff &ho = h->handoff;
     p.constants_ready = ho.constants;
+    // the heading form of d_pc has one reader that finishes it, the gather of the radix path in front of k_rays_sweep, whose kernels
+    // (fix-up, far, exact) read the gathered pcs by slot; a launch that takes another road (the counting sort, k_rays_cell whose
+    // fix-up and far kernels read d_pc by particle index, a kernel that reads d_pc itself) makes the full form with k_particle_prep,
+    // as if nothing had been prepared
+    p.heading_form = ho.heading && ho.keys && ho.stale_layout && mode_sweep(p.mode) && sort_radix(h, n);
+    if (ho.heading && !p.heading_form) p.constants_ready = false;
     if (!p.lists) return p;
     plan_work_lists(h, n, p);
     if (p.sweep) plan_sweep_form(h, p);
@@ -508,8 +515,8 @@ int ray_order(mcl_engine *h, const RayPlan &p, const mcl::RayArgs &a)
     tb = h->d_sort_tmp.cap;
     HIPCHK(h, rocprim::radix_sort_pairs(h->d_sort_tmp.p, tb, h->d_skey.p, h->d_skey2.p, h->d_srank.p, h->d_sval2.p, (size_t)n, 0, key_bits, h->stream));
     hipLaunchKernelGGL(mcl::k_sort_gather, dim3(nb256), dim3(256), 0, h->stream, h->d_pc, a.th, n, h->d_sval2, h->d_pcs, h->d_ths, h->d_perm,
-                       p.sweep ? h->d_skey2 : (const uint32_t *)nullptr, h->d_bbox, h->d_cut_start, h->d_cut_end, fine);
-    h->order_last = {h->d_bbox.p, h->d_tilemap.p, n, fine};                // (mcl_get_sort_order)
+                       p.sweep ? h->d_skey2 : (const uint32_t *)nullptr, h->d_bbox, h->d_cut_start, h->d_cut_end, fine, p.heading_form ? 1 : 0);
+    h->order_last = {h->d_bbox.p, h->d_tilemap.p, n, fine, p.heading_form};   // (mcl_get_sort_order, mcl_get_sort_record_form)
     return MCL_OK;
 }
 
@@ -1771,6 +1778,9 @@ static void resample_ray_extras(mcl_engine *h, int64_t n, mcl::ResampleArgs &a, 
             a.key_out = h->d_skey; a.val_out = h->d_srank; a.key_bbox = h->d_bbox; a.key_tilemap = tiles_ok ? h->d_tilemap : nullptr;
             a.key_ntx = ntx_abs; a.key_Wp = h->Wp; a.key_Hp = h->Hp; a.key_fine = sort_fine(h);
             ho.keys = true;
+            // ... and, in front of k_rays_sweep, leaves the sincos of the constants to the gather behind that sort (k_rays_cell's
+            // fix-up and far kernels read (cos, sin) from d_pc by particle index; so does the one-workgroup tail of a small set)
+            if (mode_sweep(rmode) && n > mcl::kTinyTailMax) { a.pc_heading = 1; ho.heading = true; }
         }
     }
     if (mode_orders(rmode) && h->prep_cache_valid && h->prep_cache_n == n && !h->env.no_prep_fold) {
@@ -2694,6 +2704,15 @@ int mcl_get_sort_order(mcl_engine_t *h, uint32_t *keys, uint32_t *perm, size_t n
         HIPCHK(h, hipMemcpyAsync(tilemap, o.tilemap, n_tiles * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MCL_OK;
+}
+
+int mcl_get_sort_record_form(mcl_engine_t *h, int32_t *heading_form)
+{
+    if (!h || !heading_form) return MCL_ERR_INVALID_ARG;
+    const OrderLast &o = h->order_last;
+    if (!o.bbox || o.n <= 0) return fail(h, MCL_ERR_NOT_READY, "the last ray stage did not order its particles through the radix sort");
+    *heading_form = o.heading ? 1 : 0;
     return MCL_OK;
 }
 

@@ -58,6 +58,8 @@ struct RayHandoff {
     bool constants = false;             // d_pc holds the constants of the current particles (ordering modes: and the per-particle scratch is zeroed)
     bool stale_layout = false;          // this update orders by the previous update's layout: d_bbox / d_tilemap are not remade
     bool keys = false;                  // ... and the resampling kernel wrote the (key, index) pairs of the library sort
+    bool heading = false;               // ... and, for k_rays_sweep, d_pc in the heading form (heading, 0, pixel x, pixel y): k_sort_gather finishes the constants;
+                                        //   a launch that does not come to that gather has k_particle_prep make the full form (plan_rays)
     bool folded = false; mcl::PrepClear passed{};   // the resampling kernel also cleared the few words that are not per particle: exactly these
     bool obs_wait = false;              // the scan's tables are built on stream2: the stream waits for ev_obs where the ray stage first reads them
 };
@@ -104,7 +106,8 @@ struct EnvKnobs {
 
 // What the last radix ordering worked from, for mcl_get_sort_order: the layout buffers its keys were made from (d_bbox / d_tilemap at the time:
 // layout_adopt swaps them out at the end of the update, and nothing writes them before the next update), n and the fine bits.
-struct OrderLast { const int *bbox = nullptr, *tilemap = nullptr; int64_t n = 0; int fine = 0; };
+// heading: its gather read the heading form of d_pc (RayHandoff::heading).
+struct OrderLast { const int *bbox = nullptr, *tilemap = nullptr; int64_t n = 0; int fine = 0; bool heading = false; };
 
 struct mcl_engine {
     mcl_config_t cfg{};

@@ -267,6 +267,8 @@ struct ResampleArgs {
     const int *key_bbox, *key_tilemap;
     int key_ntx, key_Wp, key_Hp;
     int key_fine;                     // fine bits of those keys (SortLayout::fine: the engine's setting of the radix path)
+    int pc_heading;                   // with key_out: pc_out gets the heading form (heading, 0, pixel x, pixel y) -- k_sort_gather, the one
+                                      //   reader of such a record besides k_cell_bbox (.z / .w), takes the sincos (RayHandoff::heading)
     PrepClear prep;                   // prep_on: the first workgroup also clears the few words of the ray stage that are not per
     int prep_on;                      //   particle (what k_prep_small would do in a launch of its own)
     const float *obs_src;             // this update's ranges (pinned host memory, read once by the first workgroup), or null
@@ -580,7 +582,7 @@ __device__ __forceinline__ void resample_motion_body(const ResampleArgs &a, cons
     a.cx[m] = x; a.cy[m] = y; a.cth[m] = th;
     if (a.cpack) a.cpack[m] = make_double4(x, y, th, 0.0);
     if (a.pc_out) {
-        const double4 c = particle_constants(x, y, th, a.ox, a.oy, a.res);
+        const double4 c = a.pc_heading ? particle_heading_record(x, y, th, a.ox, a.oy, a.res) : particle_constants(x, y, th, a.ox, a.oy, a.res);
         a.pc_out[m] = c;
         if (a.key_out) {
             // the same key k_sort_keys would make (same function, same arguments), from the layout handed in
@@ -1565,13 +1567,16 @@ __global__ __launch_bounds__(256) void k_sort_gather(const double4 *__restrict__
                                                     const uint32_t *__restrict__ order, double4 *__restrict__ pcs, double *__restrict__ ths,
                                                     uint32_t *__restrict__ perm, const uint32_t *__restrict__ sorted_keys = nullptr,
                                                     const int *__restrict__ bbox = nullptr, uint32_t *__restrict__ cut_start = nullptr,
-                                                    uint32_t *__restrict__ cut_end = nullptr, int fine = 0)
+                                                    uint32_t *__restrict__ cut_end = nullptr, int fine = 0, int heading_form = 0)
 {
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n) return;
     const uint32_t i = order[s];
-    pcs[s] = pc[i];
-    ths[s] = th[i];
+    // heading_form: pc holds (heading, 0, pixel x, pixel y) -- one scattered fetch per particle instead of two, and the sincos
+    // of the constants is taken here, where the SIMDs wait for those fetches (same function, same argument: the same bits)
+    const double4 rec = pc[i];
+    if (heading_form) { pcs[s] = particle_constants_of(rec); ths[s] = rec.x; }
+    else { pcs[s] = rec; ths[s] = th[i]; }
     perm[s] = i;
     if (sorted_keys) {
         const SortLayout L = sort_layout(bbox, n, fine);

@@ -19,6 +19,22 @@ __device__ __forceinline__ double4 particle_constants(double x, double y, double
     return make_double4(c, s, heading_ok ? (x - ox) / res : nanv, heading_ok ? (y - oy) / res : nanv);
 }
 
+// The same constants in two steps, for an update whose ordering gather finishes them (the radix path: k_resample_* writes the
+// heading form, k_sort_gather makes the full form of it): (heading, 0, pixel x, pixel y) with particle_constants' pixel position ...
+__device__ __forceinline__ double4 particle_heading_record(double x, double y, double t, double ox, double oy, double res)
+{
+    const bool heading_ok = t == t && fabs(t) < 1e6;
+    const double nanv = __longlong_as_double(0x7ff8000000000000ll);
+    return make_double4(t, 0.0, heading_ok ? (x - ox) / res : nanv, heading_ok ? (y - oy) / res : nanv);
+}
+// ... and particle_constants' sincos of the same argument: the bits of particle_constants(x, y, t, ..)
+__device__ __forceinline__ double4 particle_constants_of(const double4 &rec)
+{
+    double s, c;
+    sincos(rec.x, &s, &c);
+    return make_double4(c, s, rec.z, rec.w);
+}
+
 // lidarCB's downsampled range -> table row of a beam, cpp:549-554, 570, 573 (NaN -> 0)
 __device__ __forceinline__ int obs_index_of(float obs, double res, int P)
 {

@@ -44,7 +44,7 @@ EXPORTS = [
     "mcl_stage_rays_async", "mcl_stage_weights_async", "mcl_stage_complete", "mcl_stage_keep",
     "mcl_comm_available", "mcl_comm_unique_id", "mcl_comm_create", "mcl_comm_destroy", "mcl_comm_update", "mcl_comm_stats", "mcl_comm_set_lists", "mcl_comm_get_vector", "mcl_comm_last_exchange", "mcl_comm_selftest",
     "mcl_host_sweep_global_layout", "mcl_get_ray_kernel_variant", "mcl_host_skip_field_wedge_tight", "mcl_host_wedge_tight_table",
-    "mcl_get_wedge_fields", "mcl_get_ring_fields", "mcl_get_sweep_table", "mcl_host_sort_key", "mcl_get_sort_order",
+    "mcl_get_wedge_fields", "mcl_get_ring_fields", "mcl_get_sweep_table", "mcl_host_sort_key", "mcl_get_sort_order", "mcl_get_sort_record_form",
     "mcl_default_kld_config", "mcl_set_kld", "mcl_get_particle_count", "mcl_get_kld_state", "mcl_host_kld_bins", "mcl_host_kld_target",
     "mcl_default_cluster_config", "mcl_pose_clusters", "mcl_get_cluster_labels",
     "mcl_query_scans", "mcl_score_poses", "mcl_get_query_counters",
@@ -1402,6 +1402,13 @@ class Engine:
                                               C.c_size_t(tm.size if tm is not None else 0), None, None), "mcl_get_sort_order")
         return dict(keys=keys, perm=perm, bbox=bbox, tilemap=tm, n=int(n.value), fine=int(fine.value) & 15,
                     fine_sub=(int(fine.value) >> 4) - 1 if int(fine.value) >> 4 else None)
+
+    def sort_record_form(self) -> str:
+        """'heading' when the gather of the last update's radix ordering read (heading, 0, px, py) records the resampling kernel had
+        left and took the sincos itself, 'full' when it read (cos, sin, px, py) beside the heading column (mcl_get_sort_record_form)."""
+        f = C.c_int32()
+        self._chk(self.lib.mcl_get_sort_record_form(self._h, C.byref(f)), "mcl_get_sort_record_form")
+        return "heading" if f.value else "full"
 
     def particle_count(self) -> int:
         n = C.c_int64()

@@ -21,14 +21,17 @@ HBM_PEAK_GBS = 8000.0
 ALG = {
     "k_resample_motion": (32 + 8, 24 + 4 + 32 + 8 + 4,
                           "R: the parent's 32-byte record out of the compact list + its search (ctop / ccdf, cache-resident); "
-                          "W: x, y, theta, parent index, the ray stage's constants (cos, sin, px, py), zeroed accumulator and far flags",
-                          "VALU: two Philox4x32-10 calls, fp64 log + sqrt twice, four fp64 sincos (Box-Muller, motion, heading "
-                          "constants) per child; the gather hits a list of a few MB"),
+                          "W: x, y, theta, parent index, the ray stage's record, zeroed accumulator and far flags; the record is (heading, 0, px, py) on the "
+                          "radix path in front of k_rays_sweep from a set's second update on, else (cos, sin, px, py)",
+                          "VALU: two Philox4x32-10 calls, fp64 log + sqrt twice, four fp64 sincos (Box-Muller, motion, heading constants) per "
+                          "child -- three where it writes the heading form (radix path, from the second update on: that sincos is "
+                          "k_sort_gather's); the gather hits a list of a few MB"),
     "k_sort_keys": (32 + 8, 4 + 4, "R: constants + heading; W: 22-bit key + index", "at HBM / Infinity-Cache speed"),
-    "k_sort_gather": (4 + 32 + 8 + 8, 32 + 8 + 4,
-                      "R: sorted index, then the constants and the heading of THAT particle (two scattered fetches), neighbouring "
-                      "keys for the unit cuts; W: sorted constants, headings, slot -> particle",
-                      "scattered 32-byte + 8-byte reads: a 128-byte line is fetched for each (over-fetch x3-x4)"),
+    "k_sort_gather": (4 + 32 + 8, 32 + 8 + 4,
+                      "R: sorted index, then the record (heading, 0, px, py) of THAT particle (one scattered fetch; the first update "
+                      "of a set fetches the constants and the heading column: 8 bytes and a fetch more), neighbouring keys for the "
+                      "unit cuts; W: sorted constants (the sincos is taken here), headings, slot -> particle",
+                      "scattered 32-byte reads: a 64-byte fetch for each (over-fetch x2)"),
     "k_unit_sums": (32, 0, "R: sorted constants (bounding box per unit)", ""),
     "k_combine_logw": (8 + 4, 8, "R: slot accumulator, slot -> particle; W: log-weight at the particle's index",
                        "one scattered 8-byte store per particle (a partial line write each)"),
