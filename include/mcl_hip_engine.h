@@ -208,6 +208,8 @@ int mcl_get_counters(mcl_engine_t *h, uint64_t out[4]);
 int mcl_get_compact_list(const mcl_engine_t *h, int64_t *n_entries, int32_t *used_by_last_update);
 /* switches cfg.debug_count_probes on an existing engine (the next update tallies counters[2]; bench.py's untimed probe count) */
 int mcl_set_debug_count_probes(mcl_engine_t *h, int32_t on);
+/* sets cfg.debug_force_exact (0, 1 or 2) on an existing engine, for tests that run a forced and a plain ray stage on one engine */
+int mcl_set_debug_force_exact(mcl_engine_t *h, int32_t level);
 /* duration (ms) of the dominant kernel (ray cast + likelihood) in the last update, measured
  * with HIP events on the engine's own stream */
 int mcl_get_ray_kernel_ms(const mcl_engine_t *h, double *ms);

@@ -272,6 +272,7 @@ struct RayPlan {
     size_t lds = 0;                                         // ... and the nibble window of k_rays_skip
     int nsl = 1, items_per_slice = 4, sweep_g = 1;          // slices (units for k_rays_sweep), work items per slice, wedges per item
     int nseg = 1, fix_split = 1;                            // persistent workgroups = fix-up list segments; k_rays_fix workgroups per segment
+    bool fix_flat = false; int fix_grid = 1;                // k_rays_fix: the flat deal (else per segment) and its grid
     unsigned long long segcap = 0;                          // entries per segment
     unsigned gfar = 1;                                      // k_rays_far's grid
     bool hyb = false, glob = false, rec = false, pairs = false;   // the form of k_rays_sweep
@@ -331,7 +332,12 @@ void plan_work_lists(const mcl_engine *h, int64_t n, RayPlan &p)
     if ((unsigned long long)n * h->B <= (4ull << 20)) p.segcap = (share * rays_per_seg + 7) & ~7ull;
     // k_rays_far is bound by global-memory latency: 4 workgroups per CU worth of blocks (2 resident at a time)
     p.gfar = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4 * (int64_t)h->num_cu, (n + 15) / 16));
-    p.fix_split = std::max(1, std::min(16, (8 * h->num_cu) / std::max(p.nseg, 1)));   // ~8 workgroups of k_rays_fix per CU (2 .. 16 per segment: no difference, round 4)
+    p.fix_split = std::max(1, std::min(16, (mcl::kFixWgPerCu * h->num_cu) / std::max(p.nseg, 1)));   // ~8 workgroups of k_rays_fix per CU (2 .. 16 per segment: no difference, round 4)
+    // k_rays_fix deals the listed rays of ALL segments evenly over its grid when a workgroup's LDS holds the prefix of their counts (32-bit
+    // sums); otherwise fix_split workgroups share a segment.  MCL_FIX_DEAL=seg takes the latter on any launch, MCL_FIX_WG=<per CU> sizes the
+    // flat grid (profiles/fix_pass.md): A/B switches on one build, the same results.
+    p.fix_flat = !h->env.fix_deal_seg && p.nseg <= mcl::kFixSegMax && (unsigned long long)p.nseg * p.segcap < (1ull << 32);
+    p.fix_grid = p.fix_flat ? std::max(1, (h->env.fix_wg > 0 ? std::min(h->env.fix_wg, 16) : mcl::kFixWgPerCu) * h->num_cu) : p.nseg * p.fix_split;
 }
 
 // Which form of k_rays_sweep THIS update takes, and whether the windowed far pass goes with it
@@ -591,7 +597,7 @@ int ray_kernel_lists(mcl_engine *h, const RayPlan &p, const mcl::RayArgs &a)
     if (!p.sweep) HIPCHK(h, hipEventRecord(h->ev[EV_K1], h->stream));
     if (p.sweep && p.far_windowed) MCL_TRY(launch_far_windowed(h, a, a.n, COUNT));
     hipLaunchKernelGGL((mcl::k_rays_far<COUNT>), dim3(p.gfar), b, 0, h->stream, a);
-    hipLaunchKernelGGL((mcl::k_rays_fix<COUNT>), dim3(p.nseg * p.fix_split), dim3(256), 0, h->stream, a);
+    hipLaunchKernelGGL((mcl::k_rays_fix<COUNT>), dim3((unsigned)p.fix_grid), dim3(256), 0, h->stream, a, p.fix_flat ? 1 : 0);
     hipLaunchKernelGGL((mcl::k_rays_exact<COUNT>), dim3(2 * h->num_cu), dim3(256), 0, h->stream, a);
     return MCL_OK;
 }
@@ -1065,6 +1071,8 @@ static EnvKnobs read_knobs()
     if (const char *e = getenv("MCL_SORT")) k.sort_radix = std::strcmp(e, "radix") == 0 ? 1 : (std::strcmp(e, "hist") == 0 ? 0 : -1);
     if (const char *e = getenv("MCL_SORT_FINE")) k.sort_fine = atoi(e);
     if (const char *e = getenv("MCL_SORT_FINE_SUB")) k.sort_fine_sub = atoi(e);
+    if (const char *e = getenv("MCL_FIX_WG")) k.fix_wg = atoi(e);
+    if (const char *e = getenv("MCL_FIX_DEAL")) k.fix_deal_seg = std::strcmp(e, "seg") == 0;
     if (const char *e = getenv("MCL_DEBUG_WG")) k.debug_wg = e;
     k.no_bucket_cuts = getenv("MCL_NO_BUCKET_CUTS") != nullptr;
     if (const char *e = getenv("MCL_SWEEP_GLOBAL")) k.sweep_global = atoi(e) != 0;
@@ -2329,6 +2337,14 @@ int mcl_set_debug_count_probes(mcl_engine_t *h, int32_t on)
     if (!h) return MCL_ERR_INVALID_ARG;
     graph_reset(h);                        // a captured tail holds the non-counting kernel
     h->cfg.debug_count_probes = on ? 1 : 0;
+    return MCL_OK;
+}
+
+int mcl_set_debug_force_exact(mcl_engine_t *h, int32_t level)
+{
+    if (!h || level < 0 || level > 2) return MCL_ERR_INVALID_ARG;
+    graph_reset(h);                        // (RayArgs::force_exact is an argument of the captured kernels)
+    h->cfg.debug_force_exact = level;
     return MCL_OK;
 }
 

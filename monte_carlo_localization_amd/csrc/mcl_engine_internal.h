@@ -90,6 +90,8 @@ struct EnvKnobs {
     int sort_fine = -1;                 // MCL_SORT_FINE=<0..10>: fine key bits of the radix path (0: the coarse key alone); default: mcl::kSortFineDefault
     int sort_fine_sub = -1;             // MCL_SORT_FINE_SUB=<fs>: how many of them per axis are sub-cell bits; default: the rule of SortLayout for a
                                         //   given MCL_SORT_FINE, mcl::kSortFineSubDefault with the default bits
+    int fix_wg = 0;                     // MCL_FIX_WG=<n>: workgroups of k_rays_fix per CU in the flat deal (default mcl::kFixWgPerCu)
+    bool fix_deal_seg = false;          // MCL_FIX_DEAL=seg: k_rays_fix deals per segment (what it does anyway beyond mcl::kFixSegMax segments)
     std::string debug_wg;               // MCL_DEBUG_WG=<file>: four words per persistent workgroup (ray_debug_dump)
     bool no_bucket_cuts = false;        // MCL_NO_BUCKET_CUTS: units on the plain grid of 1024 slots, sparse sets ordered by whole tiles (rounds 2-3 before the cuts)
     bool sweep_global = false;          // MCL_SWEEP_GLOBAL=1: k_rays_sweep on the wedge fields in global memory whatever the range

@@ -1666,38 +1666,47 @@ __device__ __forceinline__ int first_beam_in_wedge(double th, const float *__res
 namespace mcl {
 #endif
 
-// Levels 2 and 3 for the rays k_rays_quad could not decide: one thread per listed ray, fp64 positions on the
-// global byte field (padded global coordinates shifted by 2^18), then the literal march if still ambiguous.
-template <bool COUNT>
-__global__ __launch_bounds__(256) void k_rays_fix(RayArgs a)
+// Levels 2 and 3 for the rays the ray kernel could not decide (k_rays_fix): fp64 positions on the global byte field (padded
+// global coordinates shifted by 2^18), then the literal march if still ambiguous.  profiles/fix_pass.md has the measurements
+// behind the two things below: the flat deal, one add per slot and wave.
+constexpr int kFixSegMax = 1024;      // segments whose prefix a workgroup keeps in LDS (the persistent grid has 2 per CU)
+constexpr int kFixWgPerCu = 6;        // workgroups of k_rays_fix per CU: what 73 .. 80 VGPRs keep resident (6 waves per SIMD)
+
+// One add per run of equal slots in a wave: consecutive list entries are the ~68 beams one walk handed over, so the 64 lanes
+// of a wave mostly hold ONE slot, and 64 fp64 atomics to one address are served one after the other.  Segmented reduction
+// over the runs of equal `p` among the lanes that `add`, then one atomicAdd by the run's first lane.  The sums are fp64 sums
+// of fp32 table entries, exact in any order (E4), and a -inf term gives -inf in any order: the accumulators keep their bits.
+// All 64 lanes must be here.
+__device__ __forceinline__ void wave_run_add(double *__restrict__ acc, int64_t p, bool add, double v, int lane)
 {
-    unsigned long long cnt_exact = 0, cnt_probe = 0, cnt_l2 = 0;
-    // gridDim.x = split * fix_segments: `split` workgroups share one segment (the kernel is bound by the latency of
-    // its dependent global loads, so it wants every CU full of waves rather than one workgroup per segment)
-    const int split = max(1, (int)gridDim.x / a.fix_segments);
-    const int part = blockIdx.x % split;
-    for (int seg = blockIdx.x / split; seg < a.fix_segments; seg += gridDim.x / split) {
-    // the counters were updated by memory-side atomics: read them the same way (a cached copy may be stale)
-    // (k_rays_quad / k_rays_cell append with memory-side atomics and are read back the same way; k_rays_sweep's lists and counts
-    //  are plain stores of an earlier kernel -- slot_space -- which plain loads see)
-    unsigned long long n = 0;
-    if (threadIdx.x == 0) n = a.slot_space ? a.fix_count[(size_t)seg * 8] : atomicAdd(&a.fix_count[(size_t)seg * 8], 0ull);
-    n = __shfl((long long)n, 0, 64);
-    {
-        __shared__ unsigned long long n_sh;
-        if (threadIdx.x == 0) n_sh = n;
-        __syncthreads();
-        n = n_sh;
-        __syncthreads();
+    const long long key = add ? (long long)p : -1ll;
+    const long long prev = __shfl_up(key, 1, 64);
+    const bool head = lane == 0 || !add || prev != key;               // a lane with nothing to add is a run of its own
+    const unsigned long long heads = __ballot(head);
+    const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
+    const int next = above ? lane + __ffsll((long long)above) : 64;   // first lane of the next run
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const double o = __shfl_down(v, d, 64);
+        if (lane + d < next) v += o;                                  // v: the sum of lanes lane .. min(lane + 2d, next) - 1
     }
-    if (n > a.fix_cap) n = 0;                              // overflow (or a ray kernel that stood down): the host re-runs the stage with
-                                                           // k_rays_skip and discards this one, so nothing of the segment is traced
-    cnt_l2 += (threadIdx.x == 0 && part == 0) ? n : 0;
-    const unsigned long long *list = a.fix_list + (size_t)seg * a.fix_cap;
-    for (unsigned long long k = (unsigned long long)part * blockDim.x + threadIdx.x; k < n; k += (unsigned long long)blockDim.x * split) {
-        const unsigned long long e = a.slot_space ? list[k] : atomicAdd(const_cast<unsigned long long *>(&list[k]), 0ull);
-        const int64_t p = (int64_t)(e >> 16);                     // particle index, or sorted slot (slot_space)
-        const int j = (int)(e & 0xFFFF);
+    if (head && add) atomicAdd(&acc[p], v);
+}
+
+// One listed ray of a lane, all 64 lanes of the wave together.  e: the entry; an entry that is not `valid` (the ragged end of
+// the deal) repeats a valid one so that the lane stays with its wave, is not traced and adds nothing.  The ray itself is what
+// it always was: the wedge field, or the isotropic one for a non-finite heading, !sane, the hand-over to the exact list and
+// the inline march when that list is full, store_step, the counters.
+template <bool COUNT>
+__device__ __forceinline__ void fix_ray(const RayArgs &a, unsigned long long e, bool valid, int lane, unsigned long long &cnt_exact,
+                                        unsigned long long &cnt_probe)
+{
+    const int64_t p = (int64_t)(e >> 16);                     // particle index, or sorted slot (slot_space)
+    const int j = (int)(e & 0xFFFF);
+    bool add = valid;
+    int r = a.P;
+    unsigned np = 0;
+    if (valid) {
         const double4 pci = a.slot_space ? a.pcs[p] : a.pc[p];
         // k_rays_sweep's rays are re-traced on the field of their own wedge (half the probes of the isotropic field)
         const uint8_t *wfield = nullptr;
@@ -1708,27 +1717,114 @@ __global__ __launch_bounds__(256) void k_rays_fix(RayArgs a)
         const double2 cs = a.beam_cs[j];
         const double ux = pci.x * cs.x - pci.y * cs.y, uy = pci.y * cs.x + pci.x * cs.y;
         const RayOrigin o = ray_origin(a, pci.z, pci.w);
-        int r = a.P;
         uint32_t amb = o.amb0;
-        unsigned np = 0;
         if (o.sane)
             r = trace_fp64<false, COUNT>(a, nullptr, 0, kOriginBase, o.p0x, o.p0y, ux, uy, first_skip(a, o, wfield ? wfield : a.dist, wfield != nullptr),
                                          amb, np, wfield, wfield != nullptr);
         if (takes_literal_march(a, o.sane, amb)) {
             // level 3, the literal march: 207 dependent steps in one thread would set the duration of this kernel, so the
             // (few) rays that need it go to k_rays_exact, which gives each of them a whole wave
+            bool handed = false;
             if (a.exact_list) {
                 const unsigned long long slot = atomicAdd(a.exact_count, 1ull);
-                if (slot < a.exact_cap) { atomicExch(&a.exact_list[slot], e); continue; }
+                if (slot < a.exact_cap) { atomicExch(&a.exact_list[slot], e); handed = true; }
             }
-            const int64_t i = a.slot_space ? (int64_t)a.perm[p] : p;
-            r = march_exact(a, a.x[i], a.y[i], a.th[i] + (double)a.beam_angle[j]);
-            ++cnt_exact;
+            if (!handed) {
+                const int64_t i = a.slot_space ? (int64_t)a.perm[p] : p;
+                r = march_exact(a, a.x[i], a.y[i], a.th[i] + (double)a.beam_angle[j]);
+                ++cnt_exact;
+            }
+            add = !handed;
         }
-        atomicAdd(&a.logw[p], (double)a.Lt[(size_t)r * a.bpad + j]);
+    }
+    const double v = add ? (double)a.Lt[(size_t)r * a.bpad + j] : 0.0;
+    wave_run_add(a.logw, p, add, v, lane);
+    if (add) {
         if (a.steps || a.steps16) store_step(a, a.slot_space ? (int64_t)a.perm[p] : p, j, r);
         if (COUNT) cnt_probe += np;
     }
+}
+
+// The deal.  flat: every workgroup forms the exclusive prefix of the segments' usable counts in LDS (512 strided 8-byte reads
+// out of L2 and one scan: the whole grid is resident, so this is paid once, side by side) and a grid-stride loop maps a global
+// ray index to (segment, k) by bisection: no lane waits for the fullest segment (the sweep's workgroups flag ~23 walks each,
+// Poisson-distributed), and there is no load by thread 0 with two barriers per segment.  A wave reads 64 consecutive entries,
+// which mostly share a slot (wave_run_add).  !flat (more segments than the LDS table holds): `split` workgroups share a
+// segment, as before.  The counts and entries of the legacy kernels (slot_space == 0) were written by memory-side atomics and
+// are read the same way.  Every loop is bounded by a count clipped to fix_cap; nothing waits for another workgroup.
+template <bool COUNT>
+__global__ __launch_bounds__(256) void k_rays_fix(RayArgs a, int flat)
+{
+    __shared__ uint32_t pre[kFixSegMax + 1];
+    __shared__ uint32_t wsum[4];
+    __shared__ unsigned long long n_sh;
+    unsigned long long cnt_exact = 0, cnt_probe = 0, cnt_l2 = 0;
+    const int lane = threadIdx.x & 63;
+    if (flat) {
+        const int nseg = a.fix_segments;                             // <= kFixSegMax, nseg * fix_cap < 2^32 (the host checked)
+        uint32_t c[4], t = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int seg = (int)threadIdx.x * 4 + i;
+            unsigned long long n = 0;
+            if (seg < nseg) n = a.slot_space ? a.fix_count[(size_t)seg * 8] : atomicAdd(&a.fix_count[(size_t)seg * 8], 0ull);
+            if (n > a.fix_cap) n = 0;                                // overflow (or a ray kernel that stood down): the host re-runs the stage with
+            c[i] = (uint32_t)n;                                      // k_rays_skip and discards this one, so nothing of the segment is traced
+            t += c[i];
+        }
+        uint32_t inc = t;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t up = __shfl_up(inc, d, 64);
+            if (lane >= d) inc += up;
+        }
+        if (lane == 63) wsum[threadIdx.x >> 6] = inc;
+        __syncthreads();
+        uint32_t run = inc - t;
+        for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) run += wsum[w];
+        if (threadIdx.x == 0) pre[0] = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int seg = (int)threadIdx.x * 4 + i;
+            run += c[i];
+            if (seg < nseg) pre[seg + 1] = run;
+        }
+        __syncthreads();
+        const unsigned long long total = pre[nseg];
+        if (blockIdx.x == 0 && threadIdx.x == 0) cnt_l2 = total;     // level2_rays: once per launch
+        for (unsigned long long base = (unsigned long long)blockIdx.x * 256; base < total; base += (unsigned long long)gridDim.x * 256) {
+            const unsigned long long idx = base + threadIdx.x;
+            const bool valid = idx < total;
+            const uint32_t ic = (uint32_t)(valid ? idx : total - 1);
+            int lo = 0, hi = nseg - 1;                               // the segment with pre[seg] <= ic < pre[seg + 1]
+            for (int it = 0; it < 11 && lo < hi; ++it) {             // (11 halvings empty any range of kFixSegMax)
+                const int mid = (lo + hi) >> 1;
+                if (pre[mid + 1] <= ic) lo = mid + 1; else hi = mid;
+            }
+            const unsigned long long *src = a.fix_list + (size_t)lo * a.fix_cap + (ic - pre[lo]);
+            const unsigned long long e = a.slot_space ? *src : atomicAdd(const_cast<unsigned long long *>(src), 0ull);
+            fix_ray<COUNT>(a, e, valid, lane, cnt_exact, cnt_probe);
+        }
+    } else {
+        // gridDim.x = split * fix_segments: `split` workgroups share one segment
+        const int split = max(1, (int)gridDim.x / a.fix_segments);
+        const int part = blockIdx.x % split;
+        for (int seg = blockIdx.x / split; seg < a.fix_segments; seg += gridDim.x / split) {
+            if (threadIdx.x == 0) n_sh = a.slot_space ? a.fix_count[(size_t)seg * 8] : atomicAdd(&a.fix_count[(size_t)seg * 8], 0ull);
+            __syncthreads();
+            unsigned long long n = n_sh;
+            __syncthreads();
+            if (n > a.fix_cap) n = 0;
+            cnt_l2 += (threadIdx.x == 0 && part == 0) ? n : 0;
+            const unsigned long long *list = a.fix_list + (size_t)seg * a.fix_cap;
+            for (unsigned long long base = (unsigned long long)part * 256; base < n; base += (unsigned long long)split * 256) {
+                const unsigned long long idx = base + threadIdx.x;
+                const bool valid = idx < n;
+                const unsigned long long ic = valid ? idx : n - 1;
+                const unsigned long long e = a.slot_space ? list[ic] : atomicAdd(const_cast<unsigned long long *>(&list[ic]), 0ull);
+                fix_ray<COUNT>(a, e, valid, lane, cnt_exact, cnt_probe);
+            }
+        }
     }
     if (a.counters) {
         if (cnt_exact) atomicAdd(&a.counters[0], cnt_exact);

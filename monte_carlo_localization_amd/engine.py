@@ -38,7 +38,7 @@ EXPORTS = [
     "mcl_group_set_beam_angles", "mcl_group_set_particles", "mcl_group_init_particles_pose", "mcl_group_init_global",
     "mcl_group_update", "mcl_group_expected_pose", "mcl_group_get_particles", "mcl_group_get_weights",
     "mcl_group_get_resample_indices", "mcl_group_get_stage_timings", "mcl_group_exchange_bytes",
-    "mcl_set_debug_count_probes", "mcl_set_particles_shard", "mcl_get_compact_list", "mcl_compact_chunk_bytes", "mcl_export_compact",
+    "mcl_set_debug_count_probes", "mcl_set_debug_force_exact", "mcl_set_particles_shard", "mcl_get_compact_list", "mcl_compact_chunk_bytes", "mcl_export_compact",
     "mcl_stage_resample_compact", "mcl_group_exchanged_lists", "mcl_get_ray_steps16", "mcl_get_planned_ray_kernel",
     "mcl_stream_wait_external", "mcl_external_wait_stream", "mcl_export_compact_async", "mcl_stage_resample_compact_async",
     "mcl_stage_rays_async", "mcl_stage_weights_async", "mcl_stage_complete", "mcl_stage_keep",
@@ -1765,6 +1765,9 @@ class Engine:
 
     def set_debug_count_probes(self, on):
         self._chk(self.lib.mcl_set_debug_count_probes(self._h, C.c_int32(1 if on else 0)), "mcl_set_debug_count_probes")
+
+    def set_debug_force_exact(self, level):
+        self._chk(self.lib.mcl_set_debug_force_exact(self._h, C.c_int32(int(level))), "mcl_set_debug_force_exact")
 
     def ray_kernel_ms(self):
         v = C.c_double()
