@@ -1009,6 +1009,52 @@ int mcl_host_beam_skip_thresholds(const mcl_beam_skip_config_t *c, float resolut
 int mcl_host_beam_skip_plan(const mcl_beam_skip_config_t *c, const uint32_t *counts_used, int32_t n_used, int64_t n_particles,
                             uint8_t *kept_used, int32_t *n_skipped, int32_t *integrate_all);
 
+/* ---- sensor mount: a lidar that is not at the robot's origin, and a further scan fused into the same posterior
+ *      (AMCL's static base -> laser transform) -------------------------------------------------------------------
+ * Off by default.  The particles stay base poses; only the sensor stages see the mount.
+ *   SM1 the mount.  m = (mx, my, mtheta): the sensor's pose in the base frame, metres and radians, every component finite,
+ *     |mtheta| <= 2 pi (else MCL_ERR_INVALID_ARG, nothing touched).  (0, 0, 0), with either sign of zero, means no mount: the state
+ *     after mcl_create.
+ *   SM2 the sensor pose of a base pose (x, y, theta), fp64, in this order, no contraction: s, c = sincos(theta);
+ *     xs = x + (c mx - s my); ys = y + (s mx + c my); thetas = theta + mtheta (one rounded add, not wrapped).  A non-finite input
+ *     gives what these operations give; the sensor stage treats (xs, ys, thetas) exactly as it treats a particle there.
+ *   SM3 what sees it.  mcl_update, mcl_update_scan, mcl_sensor_update, mcl_sensor_update_fuse, the staged calls (mcl_stage_rays*)
+ *     and the device group, with every ray kernel and every tail, the likelihood field with and without beam skipping, and
+ *     mcl_query_scans / mcl_score_poses, whose input poses are base poses.  The kernels are handed the sensor poses; the sort keys,
+ *     the bounding box and the tile layout are theirs.
+ *   SM4 what does not.  Resampling, motion, KLD bins, clusters, recovery injection, the initialisers, the weights and the expected
+ *     pose, mcl_get_particles, mcl_sample_particles and mcl_particle_mean work on the base poses.  Every mcl_global_search* and
+ *     mcl_refine_poses* is defined in the SENSOR frame and ignores the mount: its poses are sensor poses, and
+ *     mcl_host_sensor_unmount / mcl_host_sensor_mount_cov bring a hit, a mean and a covariance to the base frame.
+ *   SM5 off is off.  With no mount nothing new is allocated or launched and every result keeps its bits.  With a mount the
+ *     resampling kernel prepares nothing for the ray stage, which makes its own constants, keys and layout from the sensor poses.
+ *   SM6 setting it voids the captured graphs and the ordering layout, like mcl_set_beam_angles; particles, weights, beams, the map
+ *     and every option stay.  The scratch of the sensor poses (three columns of max_particles doubles) is reserved by the first
+ *     sensor stage that runs with a mount.
+ * mcl_mount_poses runs SM2 on the device with the current mount on k <= 65536 arbitrary poses (column-major in and out, buffers of
+ * its own): bit for bit what the stages use; with no mount it copies.  mcl_get_sensor_poses reads the poses the last sensor stage
+ * actually read: MCL_ERR_NOT_READY when none has run with a mount or the particles have changed since, MCL_ERR_INVALID_ARG when n
+ * is not that stage's count.
+ * mcl_sensor_update_fuse weighs a FURTHER scan into the same posterior: the work of mcl_sensor_update with the current beams, mount
+ * and sensor model (beam skipping applies to this scan alone), then logw_i <- prev_i + new_i -- one rounded fp64 add, prev exactly
+ * what mcl_get_log_weights returned before the call, -inf stays -inf -- and the unchanged weight stage on the sum (E5 included;
+ * with adaptive resampling the carry is that of the sum).  MCL_ERR_NOT_READY unless the last weighting call (mcl_update*,
+ * mcl_sensor_update, this call) was on the current particle set: mcl_set_particles*, the initialisers, the staged calls (every
+ * staged resample, every staged ray stage) and mcl_set_map void that; the beams, the mount, the likelihood field and beam skipping may change in between.  weight_mode LOG,
+ * single engine only (MCL_ERR_UNSUPPORTED otherwise).  It counts no KLD bins and folds nothing into the recovery averages. */
+int mcl_set_sensor_mount(mcl_engine_t *h, const double mount[3]);
+int mcl_get_sensor_mount(const mcl_engine_t *h, double out[3]);
+int mcl_mount_poses(mcl_engine_t *h, const double *poses_colmajor, int64_t k, double *out_colmajor);
+int mcl_get_sensor_poses(mcl_engine_t *h, double *out_colmajor, int64_t n);
+int mcl_sensor_update_fuse(mcl_engine_t *h, const float *obs, int32_t n_beams);
+/* On the host, no device: SM2 with the host's libm over n >= 1 column-major poses; its inverse b = s (-) m: theta = thetas - mtheta,
+ * then x = xs - (c mx - s my), y = ys - (s mx + c my) with s, c = sincos(theta); and J cov J^T (row-major 3 x 3) with the
+ * Jacobian of SM2 at the base pose `pose` (to_base = 0) or of the inverse at the sensor pose `pose` (to_base = 1).
+ * MCL_ERR_INVALID_ARG for a mount SM1 refuses, a null pointer, n < 1, a non-finite pose or covariance entry (mount_cov). */
+int mcl_host_sensor_mount(const double mount[3], const double *poses_colmajor, int64_t n, double *out_colmajor);
+int mcl_host_sensor_unmount(const double mount[3], const double *poses_colmajor, int64_t n, double *out_colmajor);
+int mcl_host_sensor_mount_cov(const double mount[3], const double pose[3], const double cov9[9], int to_base, double out9[9]);
+
 /* ---- odometry motion models and covariance-based pose initialisation (Probabilistic Robotics Table 5.6,
  *      sample_motion_model_odometry; AMCL's robot_model_type differential / omnidirectional with alpha1..alpha5;
  *      DESIGN.md §4.11) ---------------------------------------------------------------------------------------------------
@@ -1334,6 +1380,7 @@ int mcl_group_init_global(mcl_group_t *g, int64_t n_total);
 /* mcl_init_particles_gaussian / mcl_set_motion_model on every shard (the same particles as one engine holding them all) */
 int mcl_group_init_particles_gaussian(mcl_group_t *g, const double mean[3], const double cov[9], int64_t n_total);
 int mcl_group_set_motion_model(mcl_group_t *g, const mcl_motion_config_t *c);
+int mcl_group_set_sensor_mount(mcl_group_t *g, const double mount[3]);    /* the same mount on every engine of the group (§4.25) */
 int mcl_group_update(mcl_group_t *g, const double action[3], const float *obs, int32_t n_beams);
 int mcl_group_expected_pose(mcl_group_t *g, double out[3]);
 int mcl_group_get_particles(mcl_group_t *g, double *xyz, int64_t n_total);

@@ -20,6 +20,7 @@
 #include "mcl_kernels.h"
 #include "mcl_host_math.h"
 #include "mcl_lfield.h"
+#include "mcl_mount.h"
 
 static_assert(MCL_WEDGES == mcl::kWedges || MCL_KWEDGES != 16, "include/mcl_hip_engine.h and csrc/mcl_wedge.h disagree");
 
@@ -42,6 +43,7 @@ int ensure_lt(mcl_engine *h)
 }
 
 void build_ltd(mcl_engine *h);
+int sensor_poses(mcl_engine *h, const double *&x, const double *&y, const double *&th, int64_t n);
 
 // weights/q/sums from either log-weights (from_log) or raw weights already in d_w.  defer_sums: the caller scans d_q next
 // (scan_weights), whose one-workgroup spine then also reduces the partial sums -- one launch less.
@@ -676,6 +678,7 @@ void ray_handoff_void(mcl_engine *h)
 // unrun); recorded into a graph it consumes nothing: every replay finds the constants in d_pc, and tail_graph consumes them.
 int launch_rays(mcl_engine *h, const double *x, const double *y, const double *th, int64_t n, bool force_skip = false, bool direct_table = false)
 {
+    MCL_TRY(sensor_poses(h, x, y, th, n));      // (a mount: k_mount_poses in front of the stage's first kernel, and the stage reads its output)
     mcl::RayArgs a = ray_args(h, x, y, th, n, direct_table);
     MCL_TRY(ray_step_buffer(h, a));
     h->last_work_lists = false;
@@ -768,7 +771,7 @@ int weights_and_cdf(mcl_engine *h, bool result_to_host = false, const mcl::KldAr
     const int64_t n = h->N;
     if (h->cfg.weight_mode == MCL_WEIGHT_LOG && h->cfg.resample_neff_permille == 0 && n <= mcl::kTinyTailMax) {
         // d_pc holds (cos, sin) of the current headings whenever a ray kernel other than the literal march ran on them
-        const double4 *pc = mode_fills_pc(h->last_mode) && !h->last_lf ? h->d_pc : nullptr;
+        const double4 *pc = mode_fills_pc(h->last_mode) && !h->last_lf && !h->last_mounted ? h->d_pc : nullptr;   // (a mounted stage leaves the SENSORS' headings there)
         if (kld && result_to_host)
             hipLaunchKernelGGL(mcl::k_tiny_tail<true>, dim3(1), dim3(1024), (size_t)n * sizeof(uint64_t), h->stream, h->d_logw, h->d_x[h->cur],
                                h->d_y[h->cur], h->d_th[h->cur], pc, n, h->d_w, h->d_q, h->d_cdf, h->d_scalars, h->h_result, ++h->result_seq, *kld);
@@ -882,10 +885,10 @@ int lf_build(mcl_engine *h)
 // BS2; it also leaves the full sums in d_logw), the plan (BS3, BS4, the state record) and the summing pass over the kept beams
 // (BS5), with no host wait between them -- n and nb are known here, so min_count and min_skipped are.  d_bs_cnt is zeroed by the
 // caller, in-stream.
-int launch_lfield_skip(mcl_engine *h, int64_t n, int nb)
+int launch_lfield_skip(mcl_engine *h, const double *x, const double *y, const double *th, int64_t n, int nb)
 {
     mcl::LfArgs a{};
-    a.x = h->d_x[h->cur]; a.y = h->d_y[h->cur]; a.th = h->d_th[h->cur]; a.n = n;
+    a.x = x; a.y = y; a.th = th; a.n = n;
     a.beams = h->d_lf_beams; a.nb = nb;
     a.D = h->d_lf_D; a.W = h->W; a.H = h->H;
     a.ox = h->ox; a.oy = h->oy; a.inv_res = 1.0 / h->res;
@@ -944,9 +947,10 @@ int launch_lfield(mcl_engine *h, const float *obs, int stride, int64_t n)
         if (nb > 0) HIPCHK(h, hipMemsetAsync(h->d_bs_cnt, 0, (size_t)nb * sizeof(unsigned int), h->stream));
     }
     HIPCHK(h, hipEventRecord(h->ev[EV_QUERY], h->stream));
+    const double *x = h->d_x[h->cur], *y = h->d_y[h->cur], *th = h->d_th[h->cur];
+    MCL_TRY(sensor_poses(h, x, y, th, n));      // (a mount: the field is read at the sensors' poses)
     HIPCHK(h, hipEventRecord(h->ev[EV_K0], h->stream));
-    const int rc = h->bs_on ? launch_lfield_skip(h, n, nb)
-                            : mcl_host::launch_lfield_on(h, h->d_x[h->cur], h->d_y[h->cur], h->d_th[h->cur], n, h->d_lf_beams, nb, h->d_logw);
+    const int rc = h->bs_on ? launch_lfield_skip(h, x, y, th, n, nb) : mcl_host::launch_lfield_on(h, x, y, th, n, h->d_lf_beams, nb, h->d_logw);
     if (rc != MCL_OK) return rc;
     HIPCHK(h, hipEventRecord(h->ev[EV_K1], h->stream));
     h->max_partials_ready = false;
@@ -1310,6 +1314,7 @@ int mcl_set_map(mcl_engine_t *h, const int8_t *data, uint32_t width, uint32_t he
     graph_reset(h);
     if (!(resolution > 0.0f)) return fail(h, MCL_ERR_INVALID_ARG, "invalid map resolution");   // cpp:236-240
     recov_unset(h);
+    h->weighted = false;                    // (mcl_sensor_update_fuse: log-weights formed against the old map are not added to)
     h->mix_n = 0;                           // a proposal belongs to the map its scan was matched against
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const double res = (double)resolution;                    // cpp:191
@@ -1592,6 +1597,7 @@ static int adopt_particle_set(mcl_engine *h, int64_t n, const double *d_max_over
     h->far_fresh = true;
     h->pack_valid[0] = h->pack_valid[1] = false;
     h->have_idx = h->have_steps = h->have_logw = false;
+    h->sp_valid = h->weighted = false;
     comm_forget(h->comm);                   // a sharded set: the other shards' lists are unknown again
     h->stage_kept = false;
     kld_reset(h);
@@ -1769,6 +1775,7 @@ static void resample_common_args(const mcl_engine *h, mcl::ResampleArgs &a, cons
 // the (key, index) pairs of the ordering and the few words launch_rays would clear.
 static void resample_ray_extras(mcl_engine *h, int64_t n, mcl::ResampleArgs &a, bool fresh_children = false)
 {
+    if (h->mounted) return;                 // SM5: the ray stage works on the sensors' poses, which this kernel does not form
     const int rmode = choose_ray_mode(h, n, false);
     if (!(rmode == MCL_RAYS_SKIP || mode_orders(rmode))) return;
     a.pc_out = h->d_pc; a.ox = h->ox; a.oy = h->oy; a.res = h->res;
@@ -1900,6 +1907,7 @@ struct Update {
     bool tiny, graph_ok;                // the tail: one workgroup | the captured graph | (neither) launch by launch
     // (resampling launch) the bins the tiny tail clears | the scan's tables are built on the second stream | EV_RESAMPLE is the kernel's stop event
     mcl::KldArgs kld_cur; bool obs_early, resample_bound;
+    bool fuse;                          // mcl_sensor_update_fuse: the previous log-weights (d_logw_prev) are added to this stage's
 };
 
 // Phase 1: what this update is -- sizes, keep, recovery, and which of the three tails it takes.  Nothing is submitted here.
@@ -2028,6 +2036,7 @@ static int launch_update_resample(mcl_engine *h, Update &u, const double *d_norm
         u.obs_early = true;
     }
     h->cur = nx;                       // cpp:689 as a pointer swap
+    h->sp_valid = false;               // (the sensor poses of the parents)
     h->resampled_last = !u.keep;
     h->pack_valid[nx] = a.cpack != nullptr;
     h->compact_used = compact;
@@ -2097,6 +2106,7 @@ static int tail_graph(mcl_engine *h, const Update &u)
 {
     HIPCHK(h, hipGraphLaunch(h->graph_exec[h->cur], h->stream));
     ray_handoff_void(h);                   // (the replayed ray stage took the constants)
+    if (h->mounted) { h->sp_valid = true; h->sp_n = u.n; }      // (... and the replayed k_mount_poses wrote these children's sensor poses)
     HIPCHK(h, hipEventRecord(h->ev[EV_SENSOR], h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->compact_pending = h->d_ccdf != nullptr && !h->env.no_compact && u.n > mcl::kTinyTailMax;   // the captured scan wrote a list
@@ -2117,6 +2127,9 @@ static void add_carry(mcl_engine *h, int64_t n)
     hipLaunchKernelGGL(mcl::k_add_carry, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d_logw, h->d_carry[h->carry_idx], n);
     h->max_partials_ready = false;
 }
+
+// mcl_sensor_update_fuse: the log-weights the previous weighting call left for these particles add to this scan's
+static void add_prev_logw(mcl_engine *h, int64_t n);
 
 // Phase 3, launch by launch: every regular update, and the first of a configuration (which leaves graph_warm).
 static int tail_launches(mcl_engine *h, const Update &u)
@@ -2141,7 +2154,8 @@ static int tail_launches(mcl_engine *h, const Update &u)
         MCL_TRY(next_layout_launch(h, u.n));      // (second stream; behind the ray stage in submission order, beside it on the device)
     }
     if (u.keep) add_carry(h, u.n);
-    if (u.keep || !h->stage_ev.rays_bound) HIPCHK(h, hipEventRecord(h->ev[EV_RAYS], h->stream));
+    if (u.fuse) add_prev_logw(h, u.n);
+    if (u.keep || u.fuse || !h->stage_ev.rays_bound) HIPCHK(h, hipEventRecord(h->ev[EV_RAYS], h->stream));
     MCL_TRY(close_sensor_stage(h, true));
     MCL_TRY(fetch_scalars(h));             // one D2H copy (scalars, counters, overflow flag); synchronises the stream
     if (fix_lists_overflowed(h)) {
@@ -2150,6 +2164,7 @@ static int tail_launches(mcl_engine *h, const Update &u)
         HIPCHK(h, hipMemsetAsync(h->d_counters, 0, 4 * sizeof(unsigned long long), h->stream));
         MCL_TRY(launch_rays(h, h->d_x[h->cur], h->d_y[h->cur], h->d_th[h->cur], u.n, true));
         if (u.keep) add_carry(h, u.n);
+        if (u.fuse) add_prev_logw(h, u.n);
         MCL_TRY(weights_and_cdf(h));
         MCL_TRY(fetch_scalars(h));
     }
@@ -2168,8 +2183,9 @@ static int tail_launches(mcl_engine *h, const Update &u)
 static void finish_update(mcl_engine *h, const Update &u)
 {
     if (u.kld) kld_decide(h, u.keep);
-    recov_after(h, u.rec, u.keep, u.prev_sum_w, u.n);
+    if (!u.fuse) recov_after(h, u.rec, u.keep, u.prev_sum_w, u.n);      // (a fused scan folds nothing into the averages)
     h->have_logw = true;
+    h->weighted = true;
     h->have_steps = h->cfg.keep_ray_steps != 0 && !h->lf_on;
     if (u.resample_and_move) h->update_idx++;
     h->timings[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u.t0).count();
@@ -2178,7 +2194,7 @@ static void finish_update(mcl_engine *h, const Update &u)
 }
 
 static int do_update(mcl_engine_t *h, const double action[3], const float *obs, int32_t n_beams, const double *normals,
-                     const double *uniforms, bool resample_and_move, int obs_stride = 1)
+                     const double *uniforms, bool resample_and_move, int obs_stride = 1, bool fuse = false)
 {
     if (!h) return MCL_ERR_INVALID_ARG;
     h->set_epoch++;                         // (the labels of a clustering are void from here on)
@@ -2186,6 +2202,8 @@ static int do_update(mcl_engine_t *h, const double action[3], const float *obs, 
     if (!obs || n_beams != h->B || (resample_and_move && !action)) return fail(h, MCL_ERR_INVALID_ARG, "bad action/observation");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     Update u{action, obs, obs_stride, uniforms, resample_and_move, std::chrono::steady_clock::now()};     // (the rest: zero)
+    u.fuse = fuse;
+    h->weighted = false;                    // (until this update has formed its weights: finish_update)
     MCL_TRY(plan_update(h, u));
     const double *d_norm = nullptr, *d_uni = nullptr;
     if (resample_and_move) {
@@ -2225,6 +2243,21 @@ int mcl_update(mcl_engine_t *h, const double action[3], const float *obs, int32_
 int mcl_sensor_update(mcl_engine_t *h, const float *obs, int32_t n_beams)
 {
     return do_update(h, nullptr, obs, n_beams, nullptr, nullptr, false);
+}
+
+int mcl_sensor_update_fuse(mcl_engine_t *h, const float *obs, int32_t n_beams)
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    if (h->cfg.weight_mode != MCL_WEIGHT_LOG) return fail(h, MCL_ERR_UNSUPPORTED, "sensor_update_fuse: weight_mode LOG only");
+    if (h->comm || h->in_group) return fail(h, MCL_ERR_UNSUPPORTED, "sensor_update_fuse is single-engine only (not with a communicator or in a device group)");
+    if (!ready(h, true)) return fail(h, MCL_ERR_NOT_READY, "map, beam angles and particles must be set first");
+    if (!obs || n_beams != h->B) return fail(h, MCL_ERR_INVALID_ARG, "bad action/observation");
+    if (!h->weighted || !h->have_logw)
+        return fail(h, MCL_ERR_NOT_READY, "sensor_update_fuse: the last weighting call (mcl_update*, mcl_sensor_update) was not on the current particle set");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    MCL_TRY(h->d_logw_prev.reserve(h, (size_t)h->cap));
+    HIPCHK(h, hipMemcpyAsync(h->d_logw_prev, h->d_logw, (size_t)h->N * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    return do_update(h, nullptr, obs, n_beams, nullptr, nullptr, false, 1, true);
 }
 
 int mcl_update_scan(mcl_engine_t *h, const double action[3], const float *ranges, int32_t n_ranges, int32_t angle_step)
@@ -2931,6 +2964,7 @@ int mcl_host::stage_resample_launch(mcl_engine_t *h, const ParentSource &src, co
     h->compact_used = src.gcdf != nullptr;
     h->have_idx = true;
     h->have_logw = false;
+    h->sp_valid = h->weighted = false;
     h->resampled_last = !src.keep;
     h->stage_kept = src.keep;              // mcl_stage_rays adds the previous update's log-weights (minus their maximum)
     h->update_idx++;
@@ -3064,6 +3098,7 @@ int mcl_host::stage_rays_launch(mcl_engine_t *h, const float *obs, int32_t n_bea
     }
     if (!h->handoff.constants) ray_handoff_void(h);     // no staged resampling before this call: nothing prepared
     h->stage_ev.rays_bound = false;
+    h->weighted = false;                    // (d_logw is rewritten by a staged stage: mcl_sensor_update_fuse has nothing to add to)
     MCL_TRY(launch_rays(h, h->d_x[c], h->d_y[c], h->d_th[c], n, force_skip));
     MCL_TRY(next_layout_launch(h, n));
     if (h->stage_kept) {
@@ -3343,3 +3378,70 @@ int launch_lfield_on(mcl_engine *h, const double *x, const double *y, const doub
 }
 void launch_group_max(hipStream_t stream, const mcl::GroupMaxArgs &a) { hipLaunchKernelGGL(mcl::k_group_max, dim3(1), dim3(1), 0, stream, a); }
 }  // namespace mcl_host
+
+// ---- sensor mount (mcl_set_sensor_mount).  Down here, behind every other launch of the unit: the kernels of
+// mcl_mount.h are named last, so the code object keeps the kernels it had in the places they had.
+namespace {
+
+// The poses a sensor stage of n particles is handed: with no mount the ones it was given (nothing is launched, nothing reserved);
+// with one, k_mount_poses on the stream -- in front of the stage's first kernel -- into the engine's scratch, and that scratch.
+int sensor_poses(mcl_engine *h, const double *&x, const double *&y, const double *&th, int64_t n)
+{
+    h->last_mounted = h->mounted;
+    if (!h->mounted) { h->sp_valid = false; return MCL_OK; }     // (this stage reads the base poses: the scratch is no stage's any more)
+    if (h->d_sth.cap < (size_t)h->cap) {
+        if (h->capturing) return fail(h, MCL_ERR_HIP, "sensor-pose buffers missing during capture (internal)");
+        MCL_TRY(h->d_sx.reserve(h, (size_t)h->cap));
+        MCL_TRY(h->d_sy.reserve(h, (size_t)h->cap));
+        MCL_TRY(h->d_sth.reserve(h, (size_t)h->cap));
+    }
+    if (n < 1 || n > h->cap) return fail(h, MCL_ERR_INVALID_ARG, "sensor poses: particle count out of range (internal)");
+    mcl::launch_mount_poses(h->stream, x, y, th, n, h->mount, h->d_sx, h->d_sy, h->d_sth);
+    HIPCHK(h, hipGetLastError());
+    x = h->d_sx; y = h->d_sy; th = h->d_sth;
+    h->sp_valid = true; h->sp_n = n;
+    return MCL_OK;
+}
+
+}  // namespace
+
+static void add_prev_logw(mcl_engine *h, int64_t n)
+{
+    hipLaunchKernelGGL(mcl::k_add_logw, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d_logw.p, h->d_logw_prev.p, n);
+    h->max_partials_ready = false;
+}
+
+int mcl_set_sensor_mount(mcl_engine_t *h, const double mount[3])
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    if (!mount || !mount_valid(mount))
+        return fail(h, MCL_ERR_INVALID_ARG, "sensor mount: three finite numbers (mx, my, mtheta) with |mtheta| <= 2 pi");
+    // graph_reset-class state, like the beam angles: a captured tail holds the mount as a kernel argument, the cleared-word cache
+    // and the pending layout belong to the poses the last stage worked on.  Particles, weights and every option stay.
+    graph_reset(h);
+    for (int k = 0; k < 3; ++k) h->mount[k] = mount[k];
+    h->mounted = !(mount[0] == 0.0 && mount[1] == 0.0 && mount[2] == 0.0);         // (either sign of zero)
+    return MCL_OK;
+}
+
+int mcl_get_sensor_mount(const mcl_engine_t *h, double out[3])
+{
+    if (!h || !out) return MCL_ERR_INVALID_ARG;
+    for (int k = 0; k < 3; ++k) out[k] = h->mounted ? h->mount[k] : 0.0;
+    return MCL_OK;
+}
+
+int mcl_get_sensor_poses(mcl_engine_t *h, double *out_colmajor, int64_t n)
+{
+    if (!h || !out_colmajor) return MCL_ERR_INVALID_ARG;
+    if (!h->sp_valid || !h->d_sth)
+        return fail(h, MCL_ERR_NOT_READY, "sensor poses: no sensor stage has run with a mount on the current particles");
+    if (n != h->sp_n) return fail(h, MCL_ERR_INVALID_ARG, "sensor poses: n is not the particle count of that stage");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const size_t nb = (size_t)n * sizeof(double);
+    HIPCHK(h, hipMemcpyAsync(out_colmajor, h->d_sx, nb, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(out_colmajor + n, h->d_sy, nb, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(out_colmajor + 2 * n, h->d_sth, nb, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MCL_OK;
+}

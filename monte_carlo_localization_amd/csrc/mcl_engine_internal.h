@@ -327,6 +327,18 @@ struct mcl_engine {
     // motion model (mcl_set_motion_model): REFERENCE, or an odometry model whose per-update scalars go to the
     // k_resample_odo* kernels as plain arguments
     mcl_motion_config_t motion{};
+    // sensor mount (mcl_set_sensor_mount): the sensor's pose in the base frame (mounted: not all zero); the sensor
+    // poses of the particles, written by k_mount_poses in front of a sensor stage and reserved by the first stage that runs with a
+    // mount.  last_mounted: the last sensor stage read them (d_pc then holds the sensors' headings, not the particles');
+    // sp_valid / sp_n: they are those of the current particles (mcl_get_sensor_poses)
+    double mount[3] = {0.0, 0.0, 0.0};
+    bool mounted = false, last_mounted = false, sp_valid = false;
+    int64_t sp_n = 0;
+    DevBuf<double> d_sx, d_sy, d_sth;
+    // mcl_sensor_update_fuse: the log-weights of the previous weighting call while the new ones are formed (reserved by the first
+    // such call); weighted: the last weighting call (mcl_update*, mcl_sensor_update, the fuse call) was on the current particles
+    DevBuf<double> d_logw_prev;
+    bool weighted = false;
     // ---- side-call owners (released by mcl_destroy before the engine's own buffers, the streams idle)
     struct mcl_comm *comm = nullptr;    // RCCL communicator of a sharded set (mcl_comm_create), or null
     // pose clustering (mcl_pose_clusters): its own buffers, allocated on the first call; set_epoch counts the

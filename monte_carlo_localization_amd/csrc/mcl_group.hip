@@ -224,6 +224,16 @@ int mcl_group_set_motion_model(mcl_group_t *g, const mcl_motion_config_t *c)
     return MCL_OK;
 }
 
+int mcl_group_set_sensor_mount(mcl_group_t *g, const double mount[3])
+{
+    if (!g) return MCL_ERR_INVALID_ARG;
+    for (auto *e : g->eng) {
+        const int rc = mcl_set_sensor_mount(e, mount);
+        if (rc) return gfail(g, rc, e->err);
+    }
+    return MCL_OK;
+}
+
 int mcl_group_init_global(mcl_group_t *g, int64_t n_total)
 {
     if (!g) return MCL_ERR_INVALID_ARG;

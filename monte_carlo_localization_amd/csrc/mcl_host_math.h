@@ -41,6 +41,8 @@ const char *bs_invalid(const mcl_beam_skip_config_t *c);
 int bs_ka(const mcl_beam_skip_config_t *c, float resolution);
 int64_t bs_min_count(double threshold, int64_t n);
 int32_t bs_min_skipped(double error_threshold, int32_t n_used);
+// sensor mount: SM1's validity -- every component finite, |mtheta| <= 2 pi
+bool mount_valid(const double mount[3]);
 const char *motion_invalid(const mcl_motion_config_t *c);
 const char *gaussian_factor(const double cov[9], double L[6]);
 const char *search_invalid(const mcl_search_config_t *c);

@@ -427,6 +427,12 @@ static void lf_field_host(const int8_t *grid, int W, int H, int K, uint16_t *out
     }
 }
 
+// ---- sensor mount (mcl_set_sensor_mount): SM1
+bool mount_valid(const double mount[3])
+{
+    return std::isfinite(mount[0]) && std::isfinite(mount[1]) && std::isfinite(mount[2]) && std::fabs(mount[2]) <= 2.0 * M_PI;
+}
+
 // ---- odometry motion models and the Gaussian pose initialisation (the header's M1-M6 / G1) ----
 const char *motion_invalid(const mcl_motion_config_t *c)
 {
@@ -1391,6 +1397,57 @@ int mcl_host_refine_sequence_offsets(const mcl_refine_config_t *c, const double 
     if (!refine_sequence_rows_refused(M, nt, n_scans).empty()) return MCL_ERR_INVALID_ARG;
     if (n != (size_t)M * (size_t)nt * (size_t)n_scans * 3) return MCL_ERR_INVALID_ARG;
     refine_sequence_offsets(c->half_theta, c->step_theta_rad, seeds_colmajor, M, rel, n_scans, out);
+    return MCL_OK;
+}
+
+// ---- sensor mount on the host: SM2 with the host's libm, its inverse, and the covariance through either
+int mcl_host_sensor_mount(const double mount[3], const double *poses_colmajor, int64_t n, double *out_colmajor)
+{
+    if (!mount || !mount_valid(mount) || !poses_colmajor || !out_colmajor || n < 1) return MCL_ERR_INVALID_ARG;
+    const double mx = mount[0], my = mount[1], mth = mount[2];
+    for (int64_t i = 0; i < n; ++i) {
+        const double x = poses_colmajor[i], y = poses_colmajor[n + i], th = poses_colmajor[2 * n + i];
+        const double s = std::sin(th), c = std::cos(th);
+        out_colmajor[i] = x + (c * mx - s * my);
+        out_colmajor[n + i] = y + (s * mx + c * my);
+        out_colmajor[2 * n + i] = th + mth;
+    }
+    return MCL_OK;
+}
+
+int mcl_host_sensor_unmount(const double mount[3], const double *poses_colmajor, int64_t n, double *out_colmajor)
+{
+    if (!mount || !mount_valid(mount) || !poses_colmajor || !out_colmajor || n < 1) return MCL_ERR_INVALID_ARG;
+    const double mx = mount[0], my = mount[1], mth = mount[2];
+    for (int64_t i = 0; i < n; ++i) {
+        const double xs = poses_colmajor[i], ys = poses_colmajor[n + i], ths = poses_colmajor[2 * n + i];
+        const double th = ths - mth;
+        const double s = std::sin(th), c = std::cos(th);
+        out_colmajor[i] = xs - (c * mx - s * my);
+        out_colmajor[n + i] = ys - (s * mx + c * my);
+        out_colmajor[2 * n + i] = th;
+    }
+    return MCL_OK;
+}
+
+int mcl_host_sensor_mount_cov(const double mount[3], const double pose[3], const double cov9[9], int to_base, double out9[9])
+{
+    if (!mount || !mount_valid(mount) || !pose || !cov9 || !out9 || (to_base != 0 && to_base != 1)) return MCL_ERR_INVALID_ARG;
+    for (int k = 0; k < 3; ++k) if (!std::isfinite(pose[k])) return MCL_ERR_INVALID_ARG;
+    for (int k = 0; k < 9; ++k) if (!std::isfinite(cov9[k])) return MCL_ERR_INVALID_ARG;
+    // the Jacobian of SM2 at a base pose, or of its inverse at a sensor pose: the identity but for the heading column
+    const double th = to_base ? pose[2] - mount[2] : pose[2];
+    const double s = std::sin(th), c = std::cos(th);
+    const double jx = to_base ? (s * mount[0] + c * mount[1]) : -(s * mount[0] + c * mount[1]);
+    const double jy = to_base ? -(c * mount[0] - s * mount[1]) : (c * mount[0] - s * mount[1]);
+    const double J[9] = {1.0, 0.0, jx, 0.0, 1.0, jy, 0.0, 0.0, 1.0};
+    double JS[9];
+    for (int r = 0; r < 3; ++r)
+        for (int q = 0; q < 3; ++q) JS[r * 3 + q] = J[r * 3 + 0] * cov9[0 * 3 + q] + J[r * 3 + 1] * cov9[1 * 3 + q] + J[r * 3 + 2] * cov9[2 * 3 + q];
+    double o[9];
+    for (int r = 0; r < 3; ++r)
+        for (int q = 0; q < 3; ++q) o[r * 3 + q] = JS[r * 3 + 0] * J[q * 3 + 0] + JS[r * 3 + 1] * J[q * 3 + 1] + JS[r * 3 + 2] * J[q * 3 + 2];
+    for (int k = 0; k < 9; ++k) out9[k] = o[k];
     return MCL_OK;
 }
 

@@ -4,6 +4,7 @@
 //
 // A call, on the engine's stream:
 //   (copy)         the poses (and the scan) from pinned staging
+//   k_mount_poses  (a sensor mount set) the poses given are base poses: every kernel below reads the sensors'
 //   k_query_rays   one lane per ray: levels 2 and 3 of the ray stage on the isotropic field; level-3 rays are listed
 //   k_query_exact  one wave per listed ray: the literal march
 //   k_query_obs    (score) table row and validity of every beam
@@ -12,6 +13,7 @@
 //   (copy)         the results; one host wait
 #include "mcl_query.h"
 #include "mcl_side_buffers.h"
+#include "mcl_mount.h"
 
 #include <algorithm>
 #include <cstring>
@@ -24,6 +26,7 @@ using mcl_host::fail;
 struct mcl_query {
     DevBuf<double> d_pose;                      // 3 K: x, y, theta columns
     HostBuf<double> h_pose;
+    DevBuf<double> d_pose_s;                    // 3 K: their sensor poses (only with a mount; mcl_mount_poses)
     DevBuf<uint16_t> d_steps;
     DevBuf<float> d_ranges;
     DevBuf<unsigned long long> d_list;
@@ -90,6 +93,13 @@ int query_cast(mcl_engine *h, mcl_query *q, Args &a, const double *poses, int32_
     HIPCHK(h, hipMemsetAsync(q->d_hdr, 0, sizeof(Header), h->stream));
     fill_ray_args(h, a.ray);
     a.x = q->d_pose; a.y = q->d_pose + K; a.th = q->d_pose + 2 * (size_t)K;
+    if (h->mounted) {
+        SIDE_TRY(q->d_pose_s.reserve(h, q->d_pose.cap, &q->device_bytes));
+        double *sx = q->d_pose_s, *sy = q->d_pose_s + K, *sth = q->d_pose_s + 2 * (size_t)K;
+        mcl::launch_mount_poses(h->stream, a.x, a.y, a.th, K, h->mount, sx, sy, sth);
+        HIPCHK(h, hipGetLastError());
+        a.x = sx; a.y = sy; a.th = sth;
+    }
     a.K = K;
     a.steps = q->d_steps;
     a.ranges = want_ranges ? q->d_ranges : nullptr;
@@ -174,6 +184,32 @@ int mcl_score_poses(mcl_engine_t *h, const double *poses_colmajor, int32_t K, co
     HIPCHK(h, hipMemcpyAsync(q->h_out, q->d_out, (size_t)K * sizeof(mcl_pose_score_t), hipMemcpyDeviceToHost, h->stream));
     SIDE_TRY(query_finish(h, q));
     std::memcpy(out, q->h_out, (size_t)K * sizeof(mcl_pose_score_t));
+    return MCL_OK;
+}
+
+int mcl_mount_poses(mcl_engine_t *h, const double *poses_colmajor, int64_t k, double *out_colmajor)
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    if (!poses_colmajor || !out_colmajor) return fail(h, MCL_ERR_INVALID_ARG, "mount_poses: poses / out is null");
+    if (k < 1 || k > kMaxPoses) return fail(h, MCL_ERR_INVALID_ARG, "mount_poses: k must be in [1, 65536]");
+    const size_t K = (size_t)k;
+    if (!h->mounted) {                          // no mount: the sensor is the base
+        std::memmove(out_colmajor, poses_colmajor, 3 * K * sizeof(double));
+        return MCL_OK;
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (!h->qry) h->qry = new mcl_query();
+    mcl_query *q = h->qry;
+    SIDE_TRY(q->d_pose.reserve(h, 3 * K, &q->device_bytes));
+    SIDE_TRY(q->h_pose.reserve(h, 3 * K));
+    SIDE_TRY(q->d_pose_s.reserve(h, q->d_pose.cap, &q->device_bytes));
+    std::memcpy(q->h_pose, poses_colmajor, 3 * K * sizeof(double));
+    HIPCHK(h, hipMemcpyAsync(q->d_pose, q->h_pose, 3 * K * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    mcl::launch_mount_poses(h->stream, q->d_pose, q->d_pose + K, q->d_pose + 2 * K, k, h->mount, q->d_pose_s, q->d_pose_s + K, q->d_pose_s + 2 * K);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(q->h_pose, q->d_pose_s, 3 * K * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::memcpy(out_colmajor, q->h_pose, 3 * K * sizeof(double));
     return MCL_OK;
 }
 

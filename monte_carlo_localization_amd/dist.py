@@ -543,6 +543,11 @@ class ShardedFilter:
         checked): the children are then those of one engine holding the whole set."""
         return self.shard.set_motion_model(model, **fields)
 
+    def set_sensor_mount(self, mount):
+        """Engine.set_sensor_mount on this rank's shard.  Every rank must set the same mount (as for the motion model; not
+        checked): the weights are then those of one mounted engine holding the whole set."""
+        return self.shard.set_sensor_mount(mount)
+
     def init_particles_gaussian(self, mean, cov):
         """This rank's part of a Gaussian cloud of n_total particles (Engine.init_particles_gaussian with the shard's offset)."""
         self.shard.init_particles_gaussian(mean, cov, self.n, first_global_index=self.rank * self.n, n_total=self.n_total)

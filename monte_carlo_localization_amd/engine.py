@@ -65,6 +65,8 @@ EXPORTS = [
     "mcl_host_beam_skip_plan",
     "mcl_default_motion_config", "mcl_set_motion_model", "mcl_get_motion_model", "mcl_host_motion_scalars", "mcl_host_motion_sample",
     "mcl_init_particles_gaussian", "mcl_host_gaussian_factor", "mcl_group_set_motion_model", "mcl_group_init_particles_gaussian",
+    "mcl_set_sensor_mount", "mcl_get_sensor_mount", "mcl_mount_poses", "mcl_get_sensor_poses", "mcl_sensor_update_fuse",
+    "mcl_group_set_sensor_mount", "mcl_host_sensor_mount", "mcl_host_sensor_unmount", "mcl_host_sensor_mount_cov",
 ]
 MOTION_REFERENCE, MOTION_DIFF, MOTION_OMNI = 0, 1, 2
 MOTION_MODELS = {"reference": MOTION_REFERENCE, "diff": MOTION_DIFF, "omni": MOTION_OMNI}
@@ -365,6 +367,15 @@ def load_library(legacy=False):
         lib.mcl_host_gaussian_factor.argtypes = [C.c_void_p, C.c_void_p]
         lib.mcl_group_set_motion_model.argtypes = [C.c_void_p, C.POINTER(MotionConfig)]
         lib.mcl_group_init_particles_gaussian.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+        lib.mcl_set_sensor_mount.argtypes = [C.c_void_p, C.c_void_p]
+        lib.mcl_get_sensor_mount.argtypes = [C.c_void_p, C.c_void_p]
+        lib.mcl_mount_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.mcl_get_sensor_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        lib.mcl_sensor_update_fuse.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        lib.mcl_group_set_sensor_mount.argtypes = [C.c_void_p, C.c_void_p]
+        lib.mcl_host_sensor_mount.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.mcl_host_sensor_unmount.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.mcl_host_sensor_mount_cov.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _libs[path] = _lib = lib
     return _lib
 
@@ -496,6 +507,53 @@ def default_beam_skip_config(**over) -> BeamSkipConfig:
             raise AttributeError(name)
         setattr(c, name, (C.c_int32 * 2)(*v) if name == "reserved" else v)
     return c
+
+
+def _mount3(mount):
+    m = np.ascontiguousarray(np.zeros(3) if mount is None else mount, np.float64).reshape(-1)
+    if m.size != 3:
+        raise ValueError("a sensor mount is (mx, my, mtheta)")
+    return m
+
+
+def _host_mount_call(name, mount, poses):
+    m = _mount3(mount)
+    p = np.ascontiguousarray(poses, np.float64)
+    if p.ndim == 1 and p.size == 3:
+        p = p.reshape(3, 1)
+    if p.ndim != 2 or p.shape[0] != 3:
+        raise ValueError("poses must be (3, n): the rows x, y, theta")
+    out = np.empty_like(p)
+    rc = getattr(load_library(), name)(_p(m), _p(p), C.c_int64(p.shape[1]), _p(out))
+    if rc != MCL_OK:
+        raise EngineError(f"{name} rc={rc}", rc)
+    return out
+
+
+def host_sensor_mount(mount, poses):
+    """The sensor poses (3, n) of the base poses (3, n) under `mount` = (mx, my, mtheta) (mcl_host_sensor_mount: rule SM2 of
+    DESIGN.md §4.25 with the host's libm; no device needed)."""
+    return _host_mount_call("mcl_host_sensor_mount", mount, poses)
+
+
+def host_sensor_unmount(mount, poses):
+    """The base poses (3, n) of the sensor poses (3, n): the inverse composition (mcl_host_sensor_unmount; no device needed)."""
+    return _host_mount_call("mcl_host_sensor_unmount", mount, poses)
+
+
+def host_sensor_mount_cov(mount, pose, cov, to_base=False):
+    """J cov J^T (3, 3) with the Jacobian of SM2 at the base pose `pose`, or (to_base=True) of its inverse at the sensor pose `pose`
+    (mcl_host_sensor_mount_cov; no device needed)."""
+    m = _mount3(mount)
+    p = np.ascontiguousarray(pose, np.float64).reshape(-1)
+    c = np.ascontiguousarray(cov, np.float64).reshape(-1)
+    if p.size != 3 or c.size != 9:
+        raise ValueError("pose is (x, y, theta), cov 3 x 3")
+    out = np.empty((3, 3), np.float64)
+    rc = load_library().mcl_host_sensor_mount_cov(_p(m), _p(p), _p(c), C.c_int(1 if to_base else 0), _p(out))
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_sensor_mount_cov rc={rc}", rc)
+    return out
 
 
 def host_beam_skip_thresholds(resolution, n_particles, n_used, **fields):
@@ -1133,6 +1191,54 @@ class Engine:
         self._chk(self.lib.mcl_get_motion_model(self._h, C.byref(c)), "mcl_get_motion_model")
         return c
 
+    # -- sensor mount (off by default)
+    def set_sensor_mount(self, mount):
+        """The sensor's pose (mx, my, mtheta) in the base frame for the sensor stages that follow (mcl_set_sensor_mount); None or
+        (0, 0, 0) = no mount.  The particles stay base poses."""
+        m = _mount3(mount)
+        self._chk(self.lib.mcl_set_sensor_mount(self._h, _p(m)), "mcl_set_sensor_mount")
+
+    def sensor_mount(self):
+        out = np.empty(3)
+        self._chk(self.lib.mcl_get_sensor_mount(self._h, _p(out)), "mcl_get_sensor_mount")
+        return out
+
+    def mount_poses(self, poses):
+        """The sensor poses (3, k) of the base poses (3, k), k <= 65536, formed on the device with the current mount
+        (mcl_mount_poses): bit for bit what the sensor stages use.  With no mount a copy."""
+        p = np.ascontiguousarray(poses, np.float64)
+        if p.ndim != 2 or p.shape[0] != 3:
+            raise ValueError("poses must be (3, k): the rows x, y, theta")
+        out = np.empty_like(p)
+        self._chk(self.lib.mcl_mount_poses(self._h, _p(p), C.c_int64(p.shape[1]), _p(out)), "mcl_mount_poses")
+        return out
+
+    def sensor_poses(self):
+        """The (3, n) sensor poses the last sensor stage read (mcl_get_sensor_poses); MCL_ERR_NOT_READY when none has run with a
+        mount or the particles have changed since."""
+        out = np.empty((3, self.n), np.float64)
+        self._chk(self.lib.mcl_get_sensor_poses(self._h, _p(out), C.c_int64(self.n)), "mcl_get_sensor_poses")
+        return out
+
+    def sensor_update_fuse(self, obs):
+        """Weighs a further scan into the posterior of the last weighting call (mcl_sensor_update_fuse): the log-weights of `obs`
+        under the current beams, mount and sensor model add to the ones in place.  Two lidars:
+            e.set_sensor_mount(front); e.set_beam_angles(a_front); e.update(action, scan_front)
+            e.set_sensor_mount(rear);  e.set_beam_angles(a_rear);  e.sensor_update_fuse(scan_rear)"""
+        o = _c(obs, np.float32)
+        self._chk(self.lib.mcl_sensor_update_fuse(self._h, _p(o), C.c_int32(o.size)), "mcl_sensor_update_fuse")
+
+    def _proposal_to_base(self, means, covs):
+        """The searches and refinements work in the sensor frame: with a mount set, their means and covariances go to the base frame
+        (host_sensor_unmount, host_sensor_mount_cov) before they become a proposal.  No mount: the arrays as they are."""
+        m = self.sensor_mount()
+        if not m.any():
+            return means, covs
+        means = np.ascontiguousarray(means, np.float64).reshape(-1, 3)
+        covs = np.ascontiguousarray(covs, np.float64).reshape(-1, 3, 3)
+        base = host_sensor_unmount(m, means.T).T
+        return base, np.stack([host_sensor_mount_cov(m, means[i], covs[i], to_base=True) for i in range(means.shape[0])])
+
     def update_scan(self, action, ranges, angle_step):
         a, r = _c(action, np.float64), _c(ranges, np.float32)
         self._chk(self.lib.mcl_update_scan(self._h, _p(a), _p(r), C.c_int32(r.size), C.c_int32(angle_step)), "mcl_update_scan")
@@ -1271,7 +1377,7 @@ class Engine:
                 cov = np.diag([(sc.stride_cells * res) ** 2, (sc.stride_cells * res) ** 2, (2.0 * np.pi / sc.n_headings) ** 2])
             covs = np.broadcast_to(_c(cov, np.float64).reshape(3, 3), (hits.size, 3, 3))
         w = seed_counts(ll, 1 << 30).astype(np.float64) if weights == "likelihood" else None
-        self.set_recovery_proposal(means, covs, w)
+        self.set_recovery_proposal(*self._proposal_to_base(means, covs), w)
         return hits
 
     def propose_from_scans(self, scans, rel, max_hits=16, refine=True, weights="equal", cov=None, refine_fields=None, pruned=True,
@@ -1308,7 +1414,7 @@ class Engine:
                 cov = np.diag([(sc.stride_cells * res) ** 2, (sc.stride_cells * res) ** 2, (2.0 * np.pi / sc.n_headings) ** 2])
             covs = np.broadcast_to(_c(cov, np.float64).reshape(3, 3), (hits.size, 3, 3))
         w = seed_counts(ll, 1 << 30).astype(np.float64) if weights == "likelihood" else None
-        self.set_recovery_proposal(means, covs, w)
+        self.set_recovery_proposal(*self._proposal_to_base(means, covs), w)
         return hits
 
     # -- likelihood-field sensor model (off by default)
@@ -2085,6 +2191,11 @@ class Group:
         c = default_motion_config(model=model, **fields)
         self._chk(self.lib.mcl_group_set_motion_model(self._h, C.byref(c)), "mcl_group_set_motion_model")
         return c
+
+    def set_sensor_mount(self, mount):
+        """Engine.set_sensor_mount on every shard (mcl_group_set_sensor_mount)."""
+        m = _mount3(mount)
+        self._chk(self.lib.mcl_group_set_sensor_mount(self._h, _p(m)), "mcl_group_set_sensor_mount")
 
     def update(self, action, obs):
         a = _c(action, np.float64)
