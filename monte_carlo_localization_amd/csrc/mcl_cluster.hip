@@ -51,7 +51,7 @@ __global__ __launch_bounds__(kThreads) void k_clu_bin(Args a)
         else if (qi != 0) b = bb;
         a.pbin[i] = b;
     }
-    // test-then-set, one fetch-or per distinct new bin of the wave (the KLD marking's scheme, mcl_kernels.h)
+    // test-then-set, one fetch-or per distinct new bin of the wave (the KLD marking's scheme, mcl_resample.h)
     const uint32_t wi = b >> 5, bit = 1u << (b & 31u);
     const bool need = b != kNone && !(a.bm[wi] & bit);
     for (unsigned long long pending = __ballot(need); pending;) {
@@ -502,10 +502,7 @@ int mcl_get_cluster_labels(mcl_engine_t *h, int32_t *labels, int64_t n)
     if (!c || !c->labels_valid || !h->have_particles || c->labels_epoch != h->set_epoch || c->labels_n != h->N)
         return fail(h, MCL_ERR_NOT_READY, "clusters: no clustering of the current particle set (call mcl_pose_clusters first)");
     if (!labels || n != h->N) return fail(h, MCL_ERR_INVALID_ARG, "clusters: labels must hold N entries");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipMemcpyAsync(labels, c->label, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return MCL_OK;
+    return read_back(h, {{labels, c->label, (size_t)n * sizeof(int32_t)}});
 }
 
 }  // extern "C"

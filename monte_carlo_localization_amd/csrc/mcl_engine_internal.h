@@ -1,6 +1,7 @@
 // mcl_engine_internal.h -- what the translation units of libmcl_hip_engine.so share: the engine object, the status helpers, and
 // the handful of engine-side functions the sharded hosts are built on.  Not part of the ABI (include/mcl_hip_engine.h is).
 //   mcl_engine.hip   the engine: map / beams / particles, the update and its stages, every kernel
+//   mcl_engine_access.hip  the engine's entry points that launch nothing: read-backs, reports of host state, option setters
 //   mcl_host_math.hip  the host arithmetic (tables, fields, per-update scalars) and the ABI's mcl_host_*: no HIP, no mcl_engine
 //   mcl_comm.hip     mcl_comm_*: one process per GPU, the collectives of an update over RCCL on the engine's stream
 //   mcl_group.hip    mcl_group_*: several GPUs behind one handle, driven by one process (peer copies)
@@ -12,15 +13,19 @@
 //   mcl_refine.hip   mcl_refine_poses: the score of a dense window around each seed pose, its best pose, mean and covariance (its
 //                    own kernels and buffers, called outside the update)
 //   mcl_buffers.h    Buf / DevBuf / HostBuf: every device and pinned buffer of the files above owns its memory through these
-// Only mcl_engine.hip includes the kernels (mcl_kernels.h); mcl_comm.hip and mcl_group.hip reach the few kernels they launch
-// through the launch_* functions below.  Every function declared here is defined once, under this name.
+// Only mcl_engine.hip includes the kernels (mcl_kernels.h: the ordered list of the per-stage headers); mcl_engine_access.hip
+// launches none, mcl_comm.hip and mcl_group.hip reach the few kernels they launch through the launch_* functions below.  Every
+// function declared here is defined once, under this name.
 #pragma once
 #include "../../include/mcl_hip_engine.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -368,11 +373,24 @@ struct mcl_engine {
         }                                                                                        \
     } while (0)
 
+#define MCL_HIDDEN __attribute__((visibility("hidden")))    // on what the split of the engine unit made shared: the dynamic symbols stay the ones the library had
 #define MCL_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
 
 // Did the fix-up lists of the last ray stage overflow?  (h_fix_count: the flag as fetched with the result block.)  Its log-weights
 // are incomplete then, and the caller runs the stage again with the self-contained k_rays_skip (force_skip).
 inline bool fix_lists_overflowed(const mcl_engine *h) { return h->last_work_lists && h->h_fix_count != 0; }
+
+// One read-back step: the engine's device selected, the copies enqueued on its stream in the order given (an entry without a
+// destination is skipped), one wait for the stream.
+struct ReadBack { void *dst; const void *src; size_t bytes; };
+MCL_HIDDEN inline int read_back(mcl_engine *h, std::initializer_list<ReadBack> copies)
+{
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    for (const ReadBack &c : copies)
+        if (c.dst) HIPCHK(h, hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MCL_OK;
+}
 
 // Where the parents of a staged resample come from.
 struct ParentSource {
@@ -394,6 +412,22 @@ struct ParentSource {
 namespace mcl_host {
 int fail(mcl_engine *h, int code, const char *msg);
 int fail(mcl_engine *h, int code, const std::string &msg);
+// what the option setters of both engine units refuse on a sharded engine, and what they reset
+MCL_HIDDEN inline int refuse_shared(mcl_engine *h, const char *what)
+{
+    return !h->comm && !h->in_group ? MCL_OK : fail(h, MCL_ERR_UNSUPPORTED, std::string(what) + " is single-engine only: this engine has a communicator or belongs to a device group");
+}
+inline void recov_unset(mcl_engine *h) { h->recov_S = h->recov_F = NAN; }
+// a new particle set (set / initialised): the next update draws clamp(N, min, max)
+inline void kld_reset(mcl_engine *h)
+{
+    h->kld_bins_last = -1;
+    h->kld_n_next = h->kld_on ? std::min(std::max(h->N, h->kld.min_particles), h->kld.max_particles) : h->N;
+}
+MCL_HIDDEN int kld_alloc(mcl_engine *h);
+// The ordering's tiles over the padded map: occupied tiles are numbered compactly when the map has at most kSortMaxTiles of them
+struct SortTiles { int ntx_abs, nty_abs; bool ok; };
+MCL_HIDDEN SortTiles sort_tiles(const mcl_engine *h);
 std::string &create_error();                 // what mcl_*_last_error(NULL) reports (thread-local)
 bool ready(mcl_engine *h, bool need_particles);
 float elapsed(hipEvent_t a, hipEvent_t b);

@@ -122,7 +122,7 @@ struct RayArgs {
     int force_exact;
 };
 
-// the fp64 positions of levels 2 and 3 (the three precision levels are described at k_rays_skip, mcl_kernels.h)
+// the fp64 positions of levels 2 and 3 (the three precision levels are described at k_rays_skip, mcl_rays_basic.h)
 // fp64 fixed-point extraction: t = p + kMagic puts floor(p)+2^19 in the low 20 bits of the high
 // dword and the fraction (2^-32 units, biased by +4) in the low dword; lo < kGuard <=> within 2^-30 px.
 constexpr double kMagic = 1572864.0 + 0x1p-30;   // 1.5 * 2^20 + 2^-30

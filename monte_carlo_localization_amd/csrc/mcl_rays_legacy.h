@@ -1,7 +1,7 @@
 // mcl_rays_legacy.h -- k_rays_quad (K3c) and k_rays_cell (K3d): the windowed ray kernels of rounds 1-2, the predecessors of
 // k_rays_sweep (mcl_rays_sweep.h).  AUTO never picks them; they are compiled only with -DMCL_LEGACY_RAY_KERNELS
 // (libmcl_hip_engine_legacy.so, which the tests load for ray_kernel = MCL_RAYS_QUAD / MCL_RAYS_CELL: two more implementations of
-// cpp:586-650 that the sweep kernel is compared with).  Included from mcl_kernels.h, inside its includes' context.
+// cpp:586-650 that the sweep kernel is compared with).  Included from mcl_rays_lists.h, inside mcl_kernels.h's includes' context.
 #pragma once
 
 namespace mcl {

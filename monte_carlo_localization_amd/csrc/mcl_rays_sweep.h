@@ -28,7 +28,6 @@
 
 namespace mcl {
 
-constexpr int kSwUnder = 127;            // table rows below "no hit": samples left in [-127, -1] after an over-long jump
 constexpr int kSwUnit = 1024;            // particles per scheduling unit: one pass of the 16 waves of a workgroup
 constexpr int kSwFx = 32;                // fractional bits of a position: the low dword of a 64-bit value, the cell index is the high dword
 constexpr int kSwSide = 256;             // window side in cells
@@ -73,14 +72,12 @@ constexpr int kSwMinExtent = 8;          // cells of play a window must leave fo
 constexpr double kSwDirScale = 4294967296.0 - 3.0;
 // level-1 error bound per axis in units of 2^-32 px: a direction component is off by at most 3 units (scale: -3 .. 0, the + 1 of
 // the inner magic, two roundings of half a unit: -3 .. +2) on each of at most P samples, the origin by half a unit, the
-// reference's own accumulated rounding (cpp:622-625: P sequential fp64 adds) by < 0.2 unit (3e-11 px, mcl_kernels.h); + slack
+// reference's own accumulated rounding (cpp:622-625: P sequential fp64 adds) by < 0.2 unit (3e-11 px, mcl_rays_basic.h); + slack
 __host__ __device__ inline uint32_t sweep_guard_units(int P) { return 3u * (uint32_t)(P + 1) + ((uint32_t)(P + 1) >> 6) + 8u; }
 
 __host__ __device__ inline bool sweep_window_fits(int P) { return kSwSide - (P + 2) - 3 >= kSwMinExtent; }
 
-// rows of the per-update fp64 table of k_rays_sweep: row r = samples left + kSwUnder, plus one all-zero row
-__host__ __device__ inline int sweep_table_rows(int P) { return P + kSwUnder + 2; }
-
+// (kSwUnder and sweep_table_rows, the rows of the per-update fp64 table, are in mcl_types.h: the read-back unit needs them too)
 // Ltd[r][j]: r = left + kSwUnder for left in [-kSwUnder, P] -> (double)L[obs_idx[j]][P - max(left, 0)];
 // r = P + kSwUnder + 1 -> 0 (undecided rays: k_rays_fix adds their entry).  Beam j lives in column j + margin; the columns
 // before beam 0 and from beam B on are 0 (lanes without rays, and the virtual beams that pad a scan-edge wedge, see k_rays_sweep).

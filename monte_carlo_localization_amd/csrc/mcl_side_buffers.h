@@ -76,10 +76,7 @@ inline int read_volume(mcl_engine *h, const Volume *v, const double *d_score, do
 {
     if (!v || v->n == 0 || v->epoch != h->map_epoch || !h->have_map) return mcl_host::fail(h, MCL_ERR_NOT_READY, no_volume);
     if (n != (size_t)v->n) return mcl_host::fail(h, MCL_ERR_INVALID_ARG, wrong_size);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipMemcpyAsync(out, d_score, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return MCL_OK;
+    return read_back(h, {{out, d_score, n * sizeof(double)}});
 }
 
 }  // namespace mcl_side

@@ -1,5 +1,5 @@
 // The key the ray stage orders the particles by: how its bits are split for an update's set (sort_layout) and the key of one
-// particle (sort_key).  Host and device: the ordering kernels of mcl_kernels.h and the resampling kernel make keys with these
+// particle (sort_key).  Host and device: the ordering kernels of mcl_order.h and the resampling kernel make keys with these
 // functions, mcl_host_sort_key (mcl_host_math.hip) is the same code run on the CPU.
 #pragma once
 

@@ -1,6 +1,6 @@
 // mcl_types.h -- the few plain types and constants that both the kernels (mcl_kernels.h) and the host-only translation units
 // (mcl_comm.hip, mcl_group.hip, mcl_cluster.hip, through mcl_engine_internal.h) need.  The only device code is kld_bin, the
-// pose-space bin rule that the KLD marking (mcl_kernels.h), its host restatement and the pose clustering (mcl_cluster.hip) share.
+// pose-space bin rule that the KLD marking (mcl_resample.h), its host restatement and the pose clustering (mcl_cluster.hip) share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -11,6 +11,9 @@ constexpr int kScanThreads = 256;
 constexpr int kScanItems = 8;
 constexpr int kScanTile = kScanThreads * kScanItems;
 constexpr int kMaxShards = 16;
+constexpr int kSwUnder = 127;            // table rows below "no hit": samples left in [-127, -1] after an over-long jump
+// rows of the per-update fp64 table of k_rays_sweep (mcl_rays_sweep.h): row r = samples left + kSwUnder, plus one all-zero row
+__host__ __device__ inline int sweep_table_rows(int P) { return P + kSwUnder + 2; }
 
 // scratch the ray stage needs zeroed, cleared here instead of by one memset each (null = not used by this launch)
 struct PrepClear {

@@ -1,4 +1,4 @@
-"""numpy restatement of the tables under the ray stage, each from its comment (csrc/mcl_wedge.h, csrc/mcl_kernels.h above
+"""numpy restatement of the tables under the ray stage, each from its comment (csrc/mcl_wedge.h, csrc/mcl_field_build.h above
 k_ring_field, csrc/mcl_rays_sweep.h above k_build_ltd, include/mcl_hip_engine.h), not from the kernels' code: what
 tests/test_gpu_ray_tables.py holds the device's bytes to.  A plain helper module (like lfield_ref.py): no device, no fixtures.
 

@@ -58,8 +58,13 @@ tot = [0, 0, 0, 0]
 for lib in ("libmcl_hip_engine.so", "libmcl_hip_engine_legacy.so"):
     for o in sorted(glob.glob(f"{change}/monte_carlo_localization_amd/csrc/_build/{lib}/*.o")):
         tu = os.path.basename(o)
-        cp, mp, ip = kernels(f"{parent}/monte_carlo_localization_amd/csrc/_build/{lib}/{tu}")
         cc, mc, ic = kernels(o)
+        po = f"{parent}/monte_carlo_localization_amd/csrc/_build/{lib}/{tu}"
+        if not os.path.exists(po):           # a unit the parent does not have
+            print(f"{lib:30s} {tu:18s} new unit: kernels {len(mc)}")
+            tot[1] += len(mc)
+            continue
+        cp, mp, ip = kernels(po)
         differ = [k for k in sorted(set(mp) | set(mc)) if mp.get(k) != mc.get(k) or ip.get(k) != ic.get(k) or k not in ip]
         # a kernel behind one that changed its size: the same metadata and instruction words at another address
         moved = [k for k in differ if mp.get(k) == mc.get(k) and k in ip and k in ic and unplaced(ip[k]) == unplaced(ic[k])]
