@@ -74,12 +74,15 @@ typedef enum {
                                      library answers MCL_ERR_UNSUPPORTED                                */
     MCL_RAYS_CELL = 4,            /* QUAD on particles ordered by grid cell and heading, one particle per
                                      lane: the lanes of a wave trace near-identical rays.  LEGACY, as QUAD */
-    MCL_RAYS_SWEEP = 5            /* cell-sorted particles, one particle per lane, work items planned on the device (runs of
+    MCL_RAYS_SWEEP = 5,           /* cell-sorted particles, one particle per lane, work items planned on the device (runs of
                                      units x direction wedges), 256-cell mirrored LDS windows, 64-bit fixed-point positions,
                                      beam directions turned by the scan's increment (evenly spaced scans); ranges up to 243 px
                                      in LDS windows, beyond that the same walk on mirrored copies of the wedge fields in global
                                      memory (any range whose sixteen fields fit 2^32 bytes).  What AUTO runs from 65 536 particles
                                      and 2^23 rays; below that MCL_RAYS_SKIP. */
+    MCL_RAYS_DESKEW = 6           /* reported only (mcl_get_ray_kernel_id, mcl_get_planned_ray_kernel): the kernel of an update with
+                                     per-beam sensor offsets on (mcl_set_beam_offsets), one wave per particle, every beam cast from
+                                     its own origin.  It cannot be requested through cfg.ray_kernel. */
 } mcl_ray_kernel;
 
 /* Upper bound (exclusive) on max_particles and on the particle total of a sharded set: weights are quantised to 2^-36 and
@@ -1054,6 +1057,60 @@ int mcl_sensor_update_fuse(mcl_engine_t *h, const float *obs, int32_t n_beams);
 int mcl_host_sensor_mount(const double mount[3], const double *poses_colmajor, int64_t n, double *out_colmajor);
 int mcl_host_sensor_unmount(const double mount[3], const double *poses_colmajor, int64_t n, double *out_colmajor);
 int mcl_host_sensor_mount_cov(const double mount[3], const double pose[3], const double cov9[9], int to_base, double out9[9]);
+
+/* ---- scan de-skew: per-beam sensor offsets, for a scan taken while the robot moves ------------------------------
+ * Off by default.  A table of B triples o_j = (ox_j, oy_j, dtheta_j): the sensor's pose when beam j was taken, expressed in the
+ * sensor's frame at the scan's reference time -- the time at which the particles are the robot's pose.  S_i = (xs, ys, thetas) is
+ * particle i's sensor pose: SM2's output with a mount, the particle itself without one.
+ *   DS1 effective angle.  a'_j = (float)((double)a_j + dtheta_j); its direction pair (cos, sin) is formed of that float exactly as
+ *     mcl_set_beam_angles forms a beam's.  In directions, an engine with offsets is an engine whose beam angles are a'.  The table
+ *     is formed on the host once per mcl_set_beam_offsets (B sincos) and lives in buffers of its own: the engine's own beam
+ *     directions and angles, and everything the side calls read, stay untouched.
+ *   DS2 origin.  With (s, c) = sincos(thetas), taken once per particle as the ray stage takes it: x_ij = xs + (c ox_j - s oy_j),
+ *     y_ij = ys + (s ox_j + c oy_j) -- SM2's arithmetic and order, fp64, no contraction.  Its pixel position is
+ *     ((x_ij - origin_x) / res, (y_ij - origin_y) / res); a garbage heading (NaN, |thetas| >= 1e6) gives NaN, as for a particle.
+ *   DS3 step.  r_ij is E3's step of cast_ray from (x_ij, y_ij) at angle thetas + (double)a'_j: bit for bit what mcl_query_scans
+ *     returns for beam j of the pose (x_ij, y_ij, thetas) on an engine whose angles are a'.  debug_force_exact 1 and 2 are honoured.
+ *   DS4 weight.  The rows are E2 of the scan, unchanged; logw_i = sum_j (double)L[row_j][r_ij] (E4), added in Q3's fixed order (lane
+ *     strides, then the butterfly): the same state gives the same bits, also for tables outside E4's exactness condition.
+ *   DS5 likelihood field.  The used beam's pair becomes ((ox_j + r_j c'_j) inv_res, (oy_j + r_j s'_j) inv_res) with DS1's pair
+ *     (c'_j, s'_j); LF3-LF5 and BS1-BS5 are unchanged.  Only the update path forms its pairs so: mcl_query_scans / mcl_score_poses,
+ *     every mcl_global_search* and every mcl_refine_poses* ignore the offsets, as they ignore beam skipping.
+ *   DS6 off and zero.  NULL is off: nothing is launched, allocated or changed, every result keeps its bits.  A table of zeros is on
+ *     and takes the new path; under both models its log-weights equal the plain update's bit for bit.  mcl_set_beam_angles turns
+ *     the offsets off: the table belonged to the old beams.
+ * Honoured by mcl_update, mcl_update_scan, mcl_sensor_update and mcl_sensor_update_fuse, under the beam model (one kernel,
+ * MCL_RAYS_DESKEW, one launch; ray steps are kept where cfg.keep_ray_steps asks) and under the likelihood field with and without beam
+ * skipping, with and without a mount.  With offsets on an update runs launch by launch (no one-workgroup tail, no captured graph),
+ * and the resampling kernel prepares nothing for the ray stage.  Turning them on or off voids the captured graphs once; a new table
+ * while they are on is one asynchronous upload on the engine's stream, with no host wait and no reset.
+ * mcl_set_beam_offsets: MCL_ERR_NOT_READY before the beam angles exist; MCL_ERR_INVALID_ARG for n_beams != B or a non-finite
+ * component; MCL_ERR_UNSUPPORTED with a communicator or in a device group (the mcl_stage_* calls are refused while offsets are on),
+ * with weight_mode PRODUCT, and with cfg.ray_kernel other than MCL_RAYS_AUTO.  mcl_get_beam_offsets: the table as given (zeros when
+ * off), DS1's float angles (the beam angles when off), whether they are on; any output may be NULL.
+ * mcl_beam_origins runs DS2 on the device for k <= 65536 given SENSOR poses (column-major 3 x k) and the current table (zeros when
+ * off): x[k * B] then y[k * B], pose-major -- bit for bit the origins the ray stage casts from for a sane heading; for a garbage
+ * heading (NaN, |thetas| >= 1e6) the stage gives the ray a NaN pixel position and marches it literally from this origin (DS2), and
+ * this call returns what DS2's additions give, finite or not.
+ * On the host, no device.  mcl_host_scan_motion_offsets is the constant-twist rule a node needs.  motion = (u, v, w): the base's
+ * body-frame twist integrated over the scan's unit of t (the odometry twist times the sweep duration); t: one stamp per beam
+ * (NULL: j / (B - 1), 0 for B = 1); t_ref: the reference time in the same unit; mount: SM1's (NULL: the sensor at the base).
+ *   DM1 with tau = t_j - t_ref and theta = tau w: Delta = (tau (A u - Bc v), tau (Bc u + A v), theta), A = sin theta / theta,
+ *     Bc = (1 - cos theta) / theta; for |theta| < 1e-8 the series A = 1 - theta^2 / 6, Bc = theta / 2.
+ *   DM2 o_j = m^-1 o Delta o m: the sensor's pose under Delta (SM2's lines), then R(-mtheta) (that position - (mx, my)); its heading
+ *     component is theta whatever the mount.  A zero twist gives a table of zeros.
+ * MCL_ERR_INVALID_ARG for a non-finite input, a mount SM1 refuses, a null pointer, n_beams < 1.
+ * mcl_host_beam_offset_table is DS1 as the setter runs it (effective_angles: B floats; dirs: cos[B] then sin[B]; either may be
+ * NULL), mcl_host_beam_offset_pairs DS5's pair of every beam (pairs: x[B] then y[B], in cells) from such a table's dirs. */
+int mcl_set_beam_offsets(mcl_engine_t *h, const double *offsets_colmajor /* 3 x n_beams: ox, oy, dtheta; NULL = off */, int32_t n_beams);
+int mcl_get_beam_offsets(const mcl_engine_t *h, double *offsets_colmajor, float *effective_angles, int32_t n_beams, int32_t *on);
+int mcl_beam_origins(mcl_engine_t *h, const double *sensor_poses_colmajor, int64_t k, double *xy /* x[k*B] then y[k*B], pose-major */);
+int mcl_host_scan_motion_offsets(const double motion[3], const double mount[3] /* NULL: sensor at the base */,
+                                 const double *t /* n_beams stamps; NULL: j/(B-1), 0 for B = 1 */, double t_ref,
+                                 int32_t n_beams, double *offsets_colmajor);
+int mcl_host_beam_offset_table(const float *angles, const double *offsets_colmajor, int32_t n_beams, float *effective_angles, double *dirs);
+int mcl_host_beam_offset_pairs(const float *ranges, const double *offsets_colmajor, const double *dirs, int32_t n_beams, double resolution,
+                               double *pairs);
 
 /* ---- odometry motion models and covariance-based pose initialisation (Probabilistic Robotics Table 5.6,
  *      sample_motion_model_odometry; AMCL's robot_model_type differential / omnidirectional with alpha1..alpha5;

@@ -213,6 +213,7 @@ int mcl_comm_create(mcl_engine_t *h, const unsigned char id[128], int32_t n_rank
     if (h->kld_on) return fail(h, MCL_ERR_UNSUPPORTED, "KLD sampling (mcl_set_kld) is single-engine only: switch it off before mcl_comm_create");
     if (h->recov_on) return fail(h, MCL_ERR_UNSUPPORTED, "recovery (mcl_set_recovery) is single-engine only: switch it off before mcl_comm_create");
     if (h->lf_on) return fail(h, MCL_ERR_UNSUPPORTED, "the likelihood field (mcl_set_likelihood_field) is single-engine only: switch it off before mcl_comm_create");
+    if (h->ds_on) return fail(h, MCL_ERR_UNSUPPORTED, "per-beam sensor offsets (mcl_set_beam_offsets) are single-engine only: switch them off (pass NULL) before mcl_comm_create");
     RcclApi &api = rccl_api();
     if (!api.lib) return fail(h, MCL_ERR_UNSUPPORTED, api.why);
     if (h->cfg.weight_mode != MCL_WEIGHT_LOG)

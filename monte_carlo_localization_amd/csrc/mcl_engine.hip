@@ -42,6 +42,8 @@ int ensure_lt(mcl_engine *h)
 }
 
 void build_ltd(mcl_engine *h);
+struct RayPlan;
+void ray_kernel_deskew(mcl_engine *h, const RayPlan &p, mcl::RayArgs &a);
 int sensor_poses(mcl_engine *h, const double *&x, const double *&y, const double *&th, int64_t n);
 
 // weights/q/sums from either log-weights (from_log) or raw weights already in d_w.  defer_sums: the caller scans d_q next
@@ -83,7 +85,7 @@ int fetch_scalars(mcl_engine *h)
 bool mode_work_lists(int mode) { return mode == MCL_RAYS_QUAD || mode == MCL_RAYS_CELL || mode == MCL_RAYS_SWEEP; }   // quadrant / wedge windows + fix-up lists
 bool mode_orders(int mode) { return mode == MCL_RAYS_CELL || mode == MCL_RAYS_SWEEP; }       // cell-sorted particles, one particle per lane
 bool mode_sweep(int mode) { return mode == MCL_RAYS_SWEEP; }
-bool mode_fills_pc(int mode) { return mode != 0 && mode != MCL_RAYS_MARCH; }                // every kernel but the literal march works from d_pc
+bool mode_fills_pc(int mode) { return mode != 0 && mode != MCL_RAYS_MARCH && mode != MCL_RAYS_DESKEW; }   // every kernel but the literal march and k_rays_deskew works from d_pc
 
 // The hybrid form of k_rays_sweep (ranges beyond the LDS window: the walk leaves the window into the global wedge fields where a
 // ray is that long): for evenly spaced scans (the turned-direction walk), when both sets of fields exist.  MCL_SWEEP_HYBRID=0:
@@ -159,6 +161,10 @@ int choose_ray_mode(const mcl_engine *h, int64_t n, bool force_skip, const char 
     const char *dummy;
     const char *&w = why ? *why : dummy;
     const int rk = h->cfg.ray_kernel;
+    // per-beam sensor offsets (mcl_set_beam_offsets): every beam has its own origin, which one kernel handles; the
+    // setter refuses a configured kernel, so nothing below is overruled
+    if (rk == MCL_RAYS_DESKEW) { w = "MCL_RAYS_DESKEW cannot be configured: it is the kernel of an update with per-beam offsets on (mcl_set_beam_offsets); set ray_kernel to MCL_RAYS_AUTO"; return 0; }
+    if (h->ds_on) { w = "per-beam sensor offsets are on (mcl_set_beam_offsets): k_rays_deskew casts every beam from its own origin, in one launch (under the likelihood field no ray kernel runs: k_lfield takes the offsets in its beams' pairs)"; return MCL_RAYS_DESKEW; }
     if (rk == MCL_RAYS_MARCH) { w = "configured: MCL_RAYS_MARCH"; return MCL_RAYS_MARCH; }
     // k_rays_skip without its LDS layout (never seen): the literal march, same results
     if (rk == MCL_RAYS_SKIP || force_skip) {
@@ -365,6 +371,7 @@ RayPlan plan_rays(mcl_engine *h, int64_t n, bool force_skip, bool direct_table)
     p.grid = (int)std::max<int64_t>(1, std::min<int64_t>(h->num_cu, (n + 15) / 16));
     p.lds = (size_t)h->tw_cells * h->tw_cells / 2;
     p.timed = !p.lists && !h->capturing && !direct_table;
+    if (p.mode == MCL_RAYS_DESKEW) p.grid = (int)((n + mcl::kDeskewWaves - 1) / mcl::kDeskewWaves);      // a wave per particle: no lists, not ordered, no sweep
     const RayHandoff &ho = h->handoff;
     p.constants_ready = ho.constants;
     // the heading form of d_pc has one reader that finishes it, the gather of the radix path in front of k_rays_sweep, whose kernels
@@ -605,6 +612,7 @@ int ray_kernel(mcl_engine *h, const RayPlan &p, const mcl::RayArgs &a)
     const dim3 g(p.grid), b(mcl::kRayThreads);
     if (p.timed) HIPCHK(h, hipEventRecord(h->ev[EV_K0], h->stream));
     if (p.mode == MCL_RAYS_MARCH) ray_kernel_march(h, p, a);
+    else if (p.mode == MCL_RAYS_DESKEW) { mcl::RayArgs d = a; ray_kernel_deskew(h, p, d); }
     else if (p.count) hipLaunchKernelGGL((mcl::k_rays_skip<1, true>), g, b, p.lds, h->stream, a);
     else {
         switch (p.R) {
@@ -795,7 +803,8 @@ int close_sensor_stage(mcl_engine *h, bool all)
 int refuse_stage(mcl_engine *h)
 {
     const char *on = !h ? nullptr : h->kld_on ? "KLD sampling (mcl_set_kld)" : h->recov_on ? "recovery (mcl_set_recovery)"
-                   : h->lf_on ? "the likelihood field (mcl_set_likelihood_field)" : nullptr;
+                   : h->lf_on ? "the likelihood field (mcl_set_likelihood_field)"
+                   : h->ds_on ? "per-beam sensor offsets (mcl_set_beam_offsets; pass NULL to switch them off)" : nullptr;
     if (!on) return MCL_OK;
     return fail(h, MCL_ERR_UNSUPPORTED, std::string(on) + " is single-engine only: the mcl_stage_* calls are refused while it is on");
 }
@@ -883,7 +892,7 @@ int launch_lfield(mcl_engine *h, const float *obs, int stride, int64_t n)
     MCL_TRY(h->h_lf_beams.reserve(h, (size_t)h->B));
     MCL_TRY(h->d_lf_beams.reserve(h, (size_t)h->B));
     if (h->bs_on) { h->bs_have = false; h->bs_idx.resize((size_t)h->B); }
-    const int nb = mcl_host::lf_used_beams(h, obs, stride, h->h_lf_beams, h->bs_on ? h->bs_idx.data() : nullptr);
+    const int nb = mcl_host::lf_used_beams(h, obs, stride, h->h_lf_beams, h->bs_on ? h->bs_idx.data() : nullptr, h->ds_on);   // (DS5: the update path alone)
     if (nb > 0)
         HIPCHK(h, hipMemcpyAsync(h->d_lf_beams, h->h_lf_beams, (size_t)nb * sizeof(double2), hipMemcpyHostToDevice, h->stream));
     if (h->bs_on) {
@@ -1431,6 +1440,7 @@ int mcl_set_beam_angles(mcl_engine_t *h, const float *angles, int32_t n_beams)
     if (!h) return MCL_ERR_INVALID_ARG;
     if (!angles || n_beams <= 0 || n_beams > 65536) return fail(h, MCL_ERR_INVALID_ARG, "bad beam angles");
     recov_unset(h);
+    h->ds_on = false;                    // DS6: a table of offsets belonged to the old beams (graph_reset above has voided what held it)
     HIPCHK(h, hipSetDevice(h->cfg.device));
     h->B = 0;                            // until every buffer below exists again (ready() tests B > 0)
     h->bpad = (n_beams + 63) & ~63;
@@ -2834,7 +2844,7 @@ void launch_pack_records(hipStream_t stream, const double *x, const double *y, c
 {
     hipLaunchKernelGGL(mcl::k_pack_records, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x, y, th, n, out);
 }
-int lf_used_beams(const mcl_engine *h, const float *obs, int stride, double2 *out, int32_t *idx)
+int lf_used_beams(const mcl_engine *h, const float *obs, int stride, double2 *out, int32_t *idx, bool deskew)
 {
     const double inv_res = 1.0 / h->res;
     int nb = 0;
@@ -2842,7 +2852,8 @@ int lf_used_beams(const mcl_engine *h, const float *obs, int stride, double2 *ou
         const double r = (double)obs[(size_t)j * stride];
         if (!(r >= 0.0 && r < h->cfg.max_range_m)) continue;             // NaN, +-inf, negative, max range: no contribution
         if (idx) idx[nb] = j;
-        out[nb++] = make_double2(r * h->beam_cs_host[(size_t)j].x * inv_res, r * h->beam_cs_host[(size_t)j].y * inv_res);
+        if (deskew) out[nb++] = mcl_host::deskew_pair(r, h->ds_off[(size_t)j], h->ds_off[(size_t)h->B + j], h->ds_cs_host[(size_t)j], inv_res);
+        else out[nb++] = make_double2(r * h->beam_cs_host[(size_t)j].x * inv_res, r * h->beam_cs_host[(size_t)j].y * inv_res);
     }
     return nb;
 }
@@ -2897,4 +2908,75 @@ static void add_prev_logw(mcl_engine *h, int64_t n)
 {
     hipLaunchKernelGGL(mcl::k_add_logw, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d_logw.p, h->d_logw_prev.p, n);
     h->max_partials_ready = false;
+}
+
+// ---- per-beam sensor offsets (mcl_set_beam_offsets).  Behind the mount's launches: k_rays_deskew is named last.
+namespace {
+
+// The beam model's sensor stage with offsets on: the one kernel, on the sensor poses launch_rays formed, with the offsets' own directions
+// and float angles (DS1) in place of the engine's, the scan's rows and the static table (no transposed table is read, no sweep table built).
+void ray_kernel_deskew(mcl_engine *h, const RayPlan &p, mcl::RayArgs &a)
+{
+    a.beam_cs = h->d_ds_cs(); a.beam_angle = h->d_ds_angle();
+    a.Ldirect = h->d_L; a.obs_idx = h->d_obs_idx;
+    const dim3 g((unsigned)p.grid), b(mcl::kDeskewThreads);
+    if (a.steps16) hipLaunchKernelGGL(mcl::k_rays_deskew<2>, g, b, 0, h->stream, a, h->d_ds_off());
+    else if (a.steps) hipLaunchKernelGGL(mcl::k_rays_deskew<1>, g, b, 0, h->stream, a, h->d_ds_off());
+    else hipLaunchKernelGGL(mcl::k_rays_deskew<0>, g, b, 0, h->stream, a, h->d_ds_off());
+}
+
+}  // namespace
+
+int mcl_set_beam_offsets(mcl_engine_t *h, const double *offsets_colmajor, int32_t n_beams)
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    if (!offsets_colmajor) {                // off: the default.  Turning them off voids what was captured or handed off with them on, once
+        if (h->ds_on) graph_reset(h);
+        h->ds_on = false;
+        return MCL_OK;
+    }
+    if (h->B <= 0 || h->beam_cs_host.empty()) return fail(h, MCL_ERR_NOT_READY, "beam offsets: set the beam angles first (mcl_set_beam_angles)");
+    if (n_beams != h->B) return fail(h, MCL_ERR_INVALID_ARG, "beam offsets: n_beams does not match the beam angles");
+    if (h->comm || h->in_group)
+        return fail(h, MCL_ERR_UNSUPPORTED, "per-beam sensor offsets are single-engine only: this engine has a communicator or belongs to a device group");
+    if (h->cfg.weight_mode != MCL_WEIGHT_LOG) return fail(h, MCL_ERR_UNSUPPORTED, "per-beam sensor offsets need weight_mode LOG: create the engine with MCL_WEIGHT_LOG");
+    if (h->cfg.ray_kernel != MCL_RAYS_AUTO)
+        return fail(h, MCL_ERR_UNSUPPORTED, "per-beam sensor offsets take a ray kernel of their own: create the engine with ray_kernel MCL_RAYS_AUTO");
+    const size_t B = (size_t)h->B;
+    for (size_t k = 0; k < 3 * B; ++k)
+        if (!std::isfinite(offsets_colmajor[k])) return fail(h, MCL_ERR_INVALID_ARG, "beam offsets: every component (ox, oy, dtheta) must be finite");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    // one block: [B double2: DS1's pairs | 3 B doubles: the table | B floats: a'], staged in pinned memory and uploaded in one copy
+    const size_t words = mcl_host::deskew_block_words(B);
+    if (h->d_ds.cap < words) {
+        if (h->ds_on) { graph_reset(h); h->ds_on = false; }
+        MCL_TRY(h->d_ds.reserve(h, words));
+        MCL_TRY(h->h_ds.reserve(h, words));
+    }
+    h->ds_B = h->B;
+    h->ds_off.assign(offsets_colmajor, offsets_colmajor + 3 * B);
+    h->ds_cs_host.resize(B); h->ds_angle.resize(B);
+    mcl_host::deskew_table(h->angles.data(), offsets_colmajor, h->B, h->ds_angle.data(), h->ds_cs_host.data());
+    // (a stage that reads the block has been waited for by its update: the staging words are free; a second call before any update
+    //  queues a second copy behind the first, and the last one written is the one the next stage reads)
+    std::memcpy(h->h_ds.p, h->ds_cs_host.data(), B * sizeof(double2));
+    std::memcpy(h->h_ds.p + 2 * B, h->ds_off.data(), 3 * B * sizeof(double));
+    std::memcpy(h->h_ds.p + 5 * B, h->ds_angle.data(), B * sizeof(float));
+    HIPCHK(h, hipMemcpyAsync(h->d_ds, h->h_ds, words * sizeof(double), hipMemcpyHostToDevice, h->stream));     // no host wait
+    if (!h->ds_on) graph_reset(h);          // turning them on: the captured tails and the hand-off were made for the other ray stage
+    h->ds_on = true;
+    return MCL_OK;
+}
+
+int mcl_get_beam_offsets(const mcl_engine_t *h, double *offsets_colmajor, float *effective_angles, int32_t n_beams, int32_t *on)
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    if (on) *on = h->ds_on ? 1 : 0;
+    if (!offsets_colmajor && !effective_angles) return MCL_OK;
+    if (h->B <= 0 || n_beams != h->B) return MCL_ERR_INVALID_ARG;
+    const size_t B = (size_t)h->B;
+    // off: a table of zeros and the beam angles themselves
+    if (offsets_colmajor) for (size_t k = 0; k < 3 * B; ++k) offsets_colmajor[k] = h->ds_on ? h->ds_off[k] : 0.0;
+    if (effective_angles) for (size_t j = 0; j < B; ++j) effective_angles[j] = h->ds_on ? h->ds_angle[j] : h->angles[j];
+    return MCL_OK;
 }

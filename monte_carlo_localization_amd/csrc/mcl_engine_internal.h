@@ -340,6 +340,19 @@ struct mcl_engine {
     bool mounted = false, last_mounted = false, sp_valid = false;
     int64_t sp_n = 0;
     DevBuf<double> d_sx, d_sy, d_sth;
+    // per-beam sensor offsets (mcl_set_beam_offsets): on or off; the table as given (3 x B column-major), DS1's float
+    // angles a' and direction pairs on the host (the getter; DS5's pair formation), and ONE device block [pairs | table | angles] (mcl_host::deskew_block_words) with
+    // its pinned staging twin, so that a new table is one asynchronous copy.  Buffers of their own: beam_cs / angles stay untouched.
+    bool ds_on = false;
+    int ds_B = 0;
+    std::vector<double> ds_off;
+    std::vector<float> ds_angle;
+    std::vector<double2> ds_cs_host;
+    DevBuf<double> d_ds;
+    HostBuf<double> h_ds;
+    const double2 *d_ds_cs() const { return reinterpret_cast<const double2 *>(d_ds.p); }
+    const double *d_ds_off() const { return d_ds.p + 2 * (size_t)ds_B; }
+    const float *d_ds_angle() const { return reinterpret_cast<const float *>(d_ds.p + 5 * (size_t)ds_B); }
     // mcl_sensor_update_fuse: the log-weights of the previous weighting call while the new ones are formed (reserved by the first
     // such call); weighted: the last weighting call (mcl_update*, mcl_sensor_update, the fuse call) was on the current particles
     DevBuf<double> d_logw_prev;
@@ -461,7 +474,7 @@ void launch_group_max(hipStream_t stream, const mcl::GroupMaxArgs &a);
 // the likelihood field outside the update (mcl_query.hip): the used beams of a scan in beam order (LF3) into `out` (B entries of
 // room), their number returned, with `idx` given also the scan beam of each; k_lfield over n poses and nb such beams on the engine's
 // stream, the caller's buffers throughout
-int lf_used_beams(const mcl_engine *h, const float *obs, int stride, double2 *out, int32_t *idx = nullptr);
+int lf_used_beams(const mcl_engine *h, const float *obs, int stride, double2 *out, int32_t *idx = nullptr, bool deskew = false);   // deskew: DS5's pairs (the update path alone)
 int launch_lfield_on(mcl_engine *h, const double *x, const double *y, const double *th, int64_t n, const double2 *d_beams, int nb,
                      double *logw);
 }  // namespace mcl_host

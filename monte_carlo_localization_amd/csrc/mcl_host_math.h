@@ -43,6 +43,12 @@ int64_t bs_min_count(double threshold, int64_t n);
 int32_t bs_min_skipped(double error_threshold, int32_t n_used);
 // sensor mount: SM1's validity -- every component finite, |mtheta| <= 2 pi
 bool mount_valid(const double mount[3]);
+// per-beam sensor offsets.  DS1: a'_j = (float)((double)a_j + dtheta_j) and its direction pair, formed of that
+// float as mcl_set_beam_angles forms a beam's.  DS5: the likelihood field's pair of a used beam of range r.  The device block of a
+// table of B beams, in doubles: [B pairs | 3 B table | B float angles].
+void deskew_table(const float *angles, const double *offsets_colmajor, int32_t n_beams, float *effective_angles, double2 *cs);
+inline double2 deskew_pair(double r, double ox, double oy, double2 cs, double inv_res) { return make_double2((ox + r * cs.x) * inv_res, (oy + r * cs.y) * inv_res); }
+inline size_t deskew_block_words(size_t B) { return 5 * B + (B + 1) / 2; }
 const char *motion_invalid(const mcl_motion_config_t *c);
 const char *gaussian_factor(const double cov[9], double L[6]);
 const char *search_invalid(const mcl_search_config_t *c);

@@ -433,6 +433,17 @@ bool mount_valid(const double mount[3])
     return std::isfinite(mount[0]) && std::isfinite(mount[1]) && std::isfinite(mount[2]) && std::fabs(mount[2]) <= 2.0 * M_PI;
 }
 
+// ---- per-beam sensor offsets (mcl_set_beam_offsets): DS1
+void deskew_table(const float *angles, const double *offsets_colmajor, int32_t n_beams, float *effective_angles, double2 *cs)
+{
+    for (int32_t j = 0; j < n_beams; ++j) {
+        const float af = (float)((double)angles[j] + offsets_colmajor[2 * (size_t)n_beams + j]);
+        const double a = (double)af;                                   // cpp:533 widens the float angle
+        if (effective_angles) effective_angles[j] = af;
+        if (cs) cs[j] = make_double2(std::cos(a), std::sin(a));
+    }
+}
+
 // ---- odometry motion models and the Gaussian pose initialisation (the header's M1-M6 / G1) ----
 const char *motion_invalid(const mcl_motion_config_t *c)
 {
@@ -1448,6 +1459,70 @@ int mcl_host_sensor_mount_cov(const double mount[3], const double pose[3], const
     for (int r = 0; r < 3; ++r)
         for (int q = 0; q < 3; ++q) o[r * 3 + q] = JS[r * 3 + 0] * J[q * 3 + 0] + JS[r * 3 + 1] * J[q * 3 + 1] + JS[r * 3 + 2] * J[q * 3 + 2];
     for (int k = 0; k < 9; ++k) out9[k] = o[k];
+    return MCL_OK;
+}
+
+// ---- per-beam sensor offsets on the host: the constant-twist table (DM1, DM2) and the setter's table formation
+int mcl_host_scan_motion_offsets(const double motion[3], const double mount[3], const double *t, double t_ref, int32_t n_beams,
+                                 double *offsets_colmajor)
+{
+    if (!motion || !offsets_colmajor || n_beams < 1 || !std::isfinite(t_ref)) return MCL_ERR_INVALID_ARG;
+    for (int k = 0; k < 3; ++k) if (!std::isfinite(motion[k])) return MCL_ERR_INVALID_ARG;
+    if (mount && !mount_valid(mount)) return MCL_ERR_INVALID_ARG;
+    if (t) for (int32_t j = 0; j < n_beams; ++j) if (!std::isfinite(t[j])) return MCL_ERR_INVALID_ARG;
+    const double u = motion[0], v = motion[1], w = motion[2];
+    const size_t B = (size_t)n_beams;
+    for (int32_t j = 0; j < n_beams; ++j) {
+        const double tj = t ? t[j] : (n_beams > 1 ? (double)j / (double)(n_beams - 1) : 0.0);
+        // DM1: the base's pose at t_j in its frame at t_ref, a constant twist integrated over tau
+        const double tau = tj - t_ref, th = tau * w;
+        double A, Bc;
+        if (std::fabs(th) < 1e-8) { A = 1.0 - th * th / 6.0; Bc = th / 2.0; }
+        else { A = std::sin(th) / th; Bc = (1.0 - std::cos(th)) / th; }
+        double d[3] = {tau * (A * u - Bc * v) + 0.0, tau * (Bc * u + A * v) + 0.0, th + 0.0};      // (+ 0.0: a zero twist gives +0, whatever tau's sign)
+        if (mount) {
+            // DM2: o = m^-1 o Delta o m -- the sensor's pose under Delta (mcl_host_sensor_mount's lines), then into the frame of the
+            // sensor at t_ref: the base pose of the sensor pose m seen from the origin is the inverse composition (.._unmount's lines)
+            const double mx = mount[0], my = mount[1], mth = mount[2];
+            const double s = std::sin(d[2]), c = std::cos(d[2]);
+            const double xs = d[0] + (c * mx - s * my), ys = d[1] + (s * mx + c * my);
+            // m^-1 applied on the left: translate by -m's position, turn by -mtheta
+            const double sm = std::sin(mth), cm = std::cos(mth);
+            const double ex = xs - mx, ey = ys - my;
+            d[0] = (cm * ex + sm * ey) + 0.0;
+            d[1] = (cm * ey - sm * ex) + 0.0;
+            // (the heading component: (theta + mtheta) - mtheta is theta whatever the mount)
+        }
+        offsets_colmajor[j] = d[0]; offsets_colmajor[B + j] = d[1]; offsets_colmajor[2 * B + j] = d[2];
+    }
+    return MCL_OK;
+}
+
+int mcl_host_beam_offset_table(const float *angles, const double *offsets_colmajor, int32_t n_beams, float *effective_angles, double *dirs)
+{
+    if (!angles || !offsets_colmajor || n_beams < 1 || (!effective_angles && !dirs)) return MCL_ERR_INVALID_ARG;
+    const size_t B = (size_t)n_beams;
+    for (size_t k = 0; k < 3 * B; ++k) if (!std::isfinite(offsets_colmajor[k])) return MCL_ERR_INVALID_ARG;
+    std::vector<float> af(B);
+    std::vector<double2> cs(B);
+    deskew_table(angles, offsets_colmajor, n_beams, af.data(), cs.data());
+    for (size_t j = 0; j < B; ++j) {
+        if (effective_angles) effective_angles[j] = af[j];
+        if (dirs) { dirs[j] = cs[j].x; dirs[B + j] = cs[j].y; }
+    }
+    return MCL_OK;
+}
+
+int mcl_host_beam_offset_pairs(const float *ranges, const double *offsets_colmajor, const double *dirs, int32_t n_beams, double resolution,
+                               double *pairs)
+{
+    if (!ranges || !offsets_colmajor || !dirs || !pairs || n_beams < 1 || !(resolution > 0.0) || !std::isfinite(resolution)) return MCL_ERR_INVALID_ARG;
+    const size_t B = (size_t)n_beams;
+    const double inv_res = 1.0 / resolution;
+    for (size_t j = 0; j < B; ++j) {
+        const double2 p = deskew_pair((double)ranges[j], offsets_colmajor[j], offsets_colmajor[B + j], make_double2(dirs[j], dirs[B + j]), inv_res);
+        pairs[j] = p.x; pairs[B + j] = p.y;
+    }
     return MCL_OK;
 }
 

@@ -28,3 +28,4 @@
 #include "mcl_rays_lists.h"         // (mcl_rays_legacy.h in its place, under MCL_LEGACY_RAY_KERNELS)
 #include "mcl_weights.h"
 #include "mcl_rays_sweep.h"
+#include "mcl_rays_deskew.h"        // (last: per-beam sensor offsets)

@@ -6,6 +6,8 @@
 
 #include <cstdint>
 
+#include "mcl_ray_core.h"
+
 namespace mcl {
 
 // SM2, the only statement of it on the device: fp64, in this order, no contraction (the library is built with -ffp-contract=off);
@@ -15,8 +17,7 @@ __device__ __forceinline__ void mount_pose(double x, double y, double th, double
 {
     double s, c;
     sincos(th, &s, &c);
-    xs = x + (c * mx - s * my);
-    ys = y + (s * mx + c * my);
+    frame_point(x, y, s, c, mx, my, xs, ys);
     ths = th + mth;
 }
 

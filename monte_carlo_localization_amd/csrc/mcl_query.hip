@@ -27,6 +27,8 @@ struct mcl_query {
     DevBuf<double> d_pose;                      // 3 K: x, y, theta columns
     HostBuf<double> h_pose;
     DevBuf<double> d_pose_s;                    // 3 K: their sensor poses (only with a mount; mcl_mount_poses)
+    DevBuf<double> d_org_pose, d_org;           // mcl_beam_origins: 3 K sensor poses in, 2 K B origins out, and their pinned staging
+    HostBuf<double> h_org_pose, h_org;
     DevBuf<uint16_t> d_steps;
     DevBuf<float> d_ranges;
     DevBuf<unsigned long long> d_list;
@@ -210,6 +212,49 @@ int mcl_mount_poses(mcl_engine_t *h, const double *poses_colmajor, int64_t k, do
     HIPCHK(h, hipMemcpyAsync(q->h_pose, q->d_pose_s, 3 * K * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     std::memcpy(out_colmajor, q->h_pose, 3 * K * sizeof(double));
+    return MCL_OK;
+}
+
+// DS2 for k given sensor poses and the engine's table of per-beam offsets: one lane per (pose, beam), the pose's
+// sincos per lane (nothing against a read-back), frame_point as k_rays_deskew calls it: the metric origin, also for a garbage heading,
+// whose ray k_rays_deskew starts from a NaN pixel position and marches literally from here.  Buffers of its own.
+static __global__ __launch_bounds__(256) void k_beam_origins(const double *__restrict__ x, const double *__restrict__ y,
+                                                             const double *__restrict__ th, int64_t k, int B, const double *__restrict__ off,
+                                                             double *__restrict__ ox, double *__restrict__ oy)
+{
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= k * B) return;
+    const int64_t i = e / B;
+    const int j = (int)(e - i * B);
+    double s, c;
+    sincos(th[i], &s, &c);
+    double xb, yb;
+    mcl::frame_point(x[i], y[i], s, c, off ? off[j] : 0.0, off ? off[(size_t)B + j] : 0.0, xb, yb);
+    ox[e] = xb; oy[e] = yb;
+}
+
+int mcl_beam_origins(mcl_engine_t *h, const double *sensor_poses_colmajor, int64_t k, double *xy)
+{
+    if (!h) return MCL_ERR_INVALID_ARG;
+    if (!sensor_poses_colmajor || !xy) return fail(h, MCL_ERR_INVALID_ARG, "beam_origins: poses / xy is null");
+    if (k < 1 || k > kMaxPoses) return fail(h, MCL_ERR_INVALID_ARG, "beam_origins: k must be in [1, 65536]");
+    if (h->B <= 0) return fail(h, MCL_ERR_NOT_READY, "beam_origins: no beam angles are set");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (!h->qry) h->qry = new mcl_query();
+    mcl_query *q = h->qry;
+    const size_t K = (size_t)k, KB = K * (size_t)h->B;
+    SIDE_TRY(q->d_org_pose.reserve(h, 3 * K, &q->device_bytes));
+    SIDE_TRY(q->h_org_pose.reserve(h, 3 * K));
+    SIDE_TRY(q->d_org.reserve(h, 2 * KB, &q->device_bytes));
+    SIDE_TRY(q->h_org.reserve(h, 2 * KB));
+    std::memcpy(q->h_org_pose, sensor_poses_colmajor, 3 * K * sizeof(double));
+    HIPCHK(h, hipMemcpyAsync(q->d_org_pose, q->h_org_pose, 3 * K * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_beam_origins, dim3((unsigned)((KB + 255) / 256)), dim3(256), 0, h->stream, q->d_org_pose.p, q->d_org_pose.p + K,
+                       q->d_org_pose.p + 2 * K, k, h->B, h->ds_on ? h->d_ds_off() : (const double *)nullptr, q->d_org.p, q->d_org.p + KB);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(q->h_org, q->d_org, 2 * KB * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::memcpy(xy, q->h_org, 2 * KB * sizeof(double));
     return MCL_OK;
 }
 

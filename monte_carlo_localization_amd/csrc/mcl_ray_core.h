@@ -35,6 +35,21 @@ __device__ __forceinline__ double4 particle_constants_of(const double4 &rec)
     return make_double4(c, s, rec.z, rec.w);
 }
 
+// particle_constants' pixel position alone, for a caller that took the sincos of the heading once for many positions (k_rays_deskew)
+__device__ __forceinline__ double2 pixel_position(double x, double y, bool heading_ok, double ox, double oy, double res)
+{
+    const double nanv = __longlong_as_double(0x7ff8000000000000ll);
+    return make_double2(heading_ok ? (x - ox) / res : nanv, heading_ok ? (y - oy) / res : nanv);
+}
+
+// The point (mx, my) of a frame at (x, y) whose heading has the sine s and the cosine c: SM2's position (mount_pose, mcl_mount.h) and
+// DS2's beam origin, the one statement of both.  fp64, in this order, no contraction.
+__device__ __forceinline__ void frame_point(double x, double y, double s, double c, double mx, double my, double &xs, double &ys)
+{
+    xs = x + (c * mx - s * my);
+    ys = y + (s * mx + c * my);
+}
+
 // lidarCB's downsampled range -> table row of a beam, cpp:549-554, 570, 573 (NaN -> 0)
 __device__ __forceinline__ int obs_index_of(float obs, double res, int P)
 {

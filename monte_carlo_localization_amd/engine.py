@@ -17,11 +17,13 @@ LIB_PATH = os.environ.get("MCL_LIB") or os.path.join(_HERE, "libmcl_hip_engine.s
 MCL_OK = 0
 MCL_ERR_INVALID_ARG = -1
 MCL_ERR_NOT_READY = -2
+MCL_ERR_UNSUPPORTED = -5
 MCL_ERR_PEER = -6          # sharded update: another rank reported a failure; the update is void on every rank
 MCL_ERR_TIMEOUT = -7       # sharded update: a collective did not finish in time; the communicator was aborted
 RESAMPLE_MULTINOMIAL, RESAMPLE_SYSTEMATIC = 0, 1
 WEIGHT_LOG, WEIGHT_PRODUCT = 0, 1
 RAYS_AUTO, RAYS_MARCH, RAYS_SKIP, RAYS_QUAD, RAYS_CELL, RAYS_SWEEP = 0, 1, 2, 3, 4, 5
+RAYS_DESKEW = 6            # reported only: the kernel of an update with per-beam sensor offsets on (Engine.set_beam_offsets)
 BUF_X, BUF_Y, BUF_THETA, BUF_QWEIGHT, BUF_LOGW, BUF_SCALARS = range(6)
 
 EXPORTS = [
@@ -67,6 +69,8 @@ EXPORTS = [
     "mcl_init_particles_gaussian", "mcl_host_gaussian_factor", "mcl_group_set_motion_model", "mcl_group_init_particles_gaussian",
     "mcl_set_sensor_mount", "mcl_get_sensor_mount", "mcl_mount_poses", "mcl_get_sensor_poses", "mcl_sensor_update_fuse",
     "mcl_group_set_sensor_mount", "mcl_host_sensor_mount", "mcl_host_sensor_unmount", "mcl_host_sensor_mount_cov",
+    "mcl_set_beam_offsets", "mcl_get_beam_offsets", "mcl_beam_origins", "mcl_host_scan_motion_offsets", "mcl_host_beam_offset_table",
+    "mcl_host_beam_offset_pairs",
 ]
 MOTION_REFERENCE, MOTION_DIFF, MOTION_OMNI = 0, 1, 2
 MOTION_MODELS = {"reference": MOTION_REFERENCE, "diff": MOTION_DIFF, "omni": MOTION_OMNI}
@@ -376,6 +380,12 @@ def load_library(legacy=False):
         lib.mcl_host_sensor_mount.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         lib.mcl_host_sensor_unmount.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         lib.mcl_host_sensor_mount_cov.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        lib.mcl_set_beam_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        lib.mcl_get_beam_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        lib.mcl_beam_origins.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.mcl_host_scan_motion_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_void_p]
+        lib.mcl_host_beam_offset_table.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        lib.mcl_host_beam_offset_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p]
         _libs[path] = _lib = lib
     return _lib
 
@@ -553,6 +563,59 @@ def host_sensor_mount_cov(mount, pose, cov, to_base=False):
     rc = load_library().mcl_host_sensor_mount_cov(_p(m), _p(p), _p(c), C.c_int(1 if to_base else 0), _p(out))
     if rc != MCL_OK:
         raise EngineError(f"mcl_host_sensor_mount_cov rc={rc}", rc)
+    return out
+
+
+def host_scan_motion_offsets(motion, n_beams, t=None, t_ref=1.0, mount=None):
+    """The (3, n_beams) table of per-beam sensor offsets (rows ox, oy, dtheta) of a scan taken under a constant twist
+    (mcl_host_scan_motion_offsets, rules DM1 / DM2 of DESIGN.md §4.26; no device needed).  motion = (u, v, w): the base's body-frame
+    twist integrated over the scan's unit of t (the odometry twist times the sweep duration); t: one stamp per beam (None:
+    j / (B - 1)); t_ref: the time at which the particles are the robot's pose (1.0: the end of the sweep); mount: the sensor mount."""
+    mo = np.ascontiguousarray(motion, np.float64).reshape(-1)
+    if mo.size != 3:
+        raise ValueError("motion is (u, v, w)")
+    m = None if mount is None else _mount3(mount)
+    tt = None if t is None else np.ascontiguousarray(t, np.float64).reshape(-1)
+    if tt is not None and tt.size != int(n_beams):
+        raise ValueError("t holds one stamp per beam")
+    out = np.empty((3, max(int(n_beams), 0)), np.float64)
+    rc = load_library().mcl_host_scan_motion_offsets(_p(mo), _p(m), _p(tt), C.c_double(float(t_ref)), C.c_int32(int(n_beams)), _p(out))
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_scan_motion_offsets rc={rc}", rc)
+    return out
+
+
+def _offsets3(offsets, n_beams=None):
+    o = np.ascontiguousarray(offsets, np.float64)
+    if o.ndim != 2 or o.shape[0] != 3 or (n_beams is not None and o.shape[1] != n_beams):
+        raise ValueError("beam offsets are (3, n_beams): the rows ox, oy, dtheta")
+    return o
+
+
+def host_beam_offset_table(angles, offsets):
+    """(effective float angles a' (B,), their direction pairs (2, B): cos, sin) of rule DS1, as Engine.set_beam_offsets forms them
+    (mcl_host_beam_offset_table; no device needed)."""
+    a = _c(angles, np.float32).reshape(-1)
+    o = _offsets3(offsets, a.size)
+    eff, dirs = np.empty(a.size, np.float32), np.empty((2, a.size), np.float64)
+    rc = load_library().mcl_host_beam_offset_table(_p(a), _p(o), C.c_int32(a.size), _p(eff), _p(dirs))
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_beam_offset_table rc={rc}", rc)
+    return eff, dirs
+
+
+def host_beam_offset_pairs(ranges, offsets, dirs, resolution):
+    """The likelihood field's pair (2, B), in cells, of every beam of `ranges` under rule DS5 (mcl_host_beam_offset_pairs; no device
+    needed); dirs as host_beam_offset_table returns them."""
+    r = _c(ranges, np.float32).reshape(-1)
+    o = _offsets3(offsets, r.size)
+    d = np.ascontiguousarray(dirs, np.float64)
+    if d.shape != (2, r.size):
+        raise ValueError("dirs is (2, B)")
+    out = np.empty((2, r.size), np.float64)
+    rc = load_library().mcl_host_beam_offset_pairs(_p(r), _p(o), _p(d), C.c_int32(r.size), C.c_double(float(np.float32(resolution))), _p(out))      # (the map's float resolution, widened: set_map)
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_beam_offset_pairs rc={rc}", rc)
     return out
 
 
@@ -1228,6 +1291,37 @@ class Engine:
         o = _c(obs, np.float32)
         self._chk(self.lib.mcl_sensor_update_fuse(self._h, _p(o), C.c_int32(o.size)), "mcl_sensor_update_fuse")
 
+    # -- scan de-skew: per-beam sensor offsets (off by default)
+    def set_beam_offsets(self, offsets):
+        """The (3, n_beams) table of per-beam sensor offsets (rows ox, oy, dtheta: the sensor's pose when beam j was taken, in the
+        sensor's frame at the scan's reference time) for the updates that follow (mcl_set_beam_offsets); None = off.  A node:
+            e.set_beam_offsets(host_scan_motion_offsets(twist * sweep_time, B, mount=m)); e.update(action, scan)"""
+        if offsets is None:
+            self._chk(self.lib.mcl_set_beam_offsets(self._h, None, C.c_int32(0)), "mcl_set_beam_offsets")
+            return
+        o = np.ascontiguousarray(offsets, np.float64)
+        if o.ndim != 2 or o.shape[0] != 3:
+            raise ValueError("beam offsets are (3, n_beams): the rows ox, oy, dtheta")
+        self._chk(self.lib.mcl_set_beam_offsets(self._h, _p(o), C.c_int32(o.shape[1])), "mcl_set_beam_offsets")
+
+    def beam_offsets(self):
+        """(the table (3, B) as given -- zeros when off --, rule DS1's float angles (B,) -- the beam angles when off --, whether
+        offsets are on) (mcl_get_beam_offsets)."""
+        o, a, on = np.empty((3, self.n_beams), np.float64), np.empty(self.n_beams, np.float32), C.c_int32()
+        self._chk(self.lib.mcl_get_beam_offsets(self._h, _p(o), _p(a), C.c_int32(self.n_beams), C.byref(on)), "mcl_get_beam_offsets")
+        return o, a, bool(on.value)
+
+    def beam_origins(self, poses):
+        """(x, y), each (k, B): rule DS2's origin of every beam of the SENSOR poses (3, k), k <= 65536, formed on the device with the
+        current table (mcl_beam_origins): bit for bit where the ray stage casts from (a garbage heading -- NaN, |theta| >= 1e6 -- is
+        marched literally from here, its walk having no pixel position).  Offsets off: every beam at the pose."""
+        p = np.ascontiguousarray(poses, np.float64)
+        if p.ndim != 2 or p.shape[0] != 3:
+            raise ValueError("poses must be (3, k): the rows x, y, theta")
+        out = np.empty((2, p.shape[1], self.n_beams), np.float64)
+        self._chk(self.lib.mcl_beam_origins(self._h, _p(p), C.c_int64(p.shape[1]), _p(out)), "mcl_beam_origins")
+        return out[0], out[1]
+
     def _proposal_to_base(self, means, covs):
         """The searches and refinements work in the sensor frame: with a mount set, their means and covariances go to the base frame
         (host_sensor_unmount, host_sensor_mount_cov) before they become a proposal.  No mount: the arrays as they are."""
@@ -1886,10 +1980,14 @@ class Engine:
         self._chk(self.lib.mcl_get_effective_sample_size(self._h, C.byref(v), C.byref(r)), "mcl_get_effective_sample_size")
         return v.value, bool(r.value)
 
-    def ray_kernel_name(self):
+    def ray_kernel_id(self):
+        """The MCL_RAYS_* enumerator of the kernel the last ray stage ran (mcl_get_ray_kernel_id; 0: none yet)."""
         v = C.c_int32()
         self._chk(self.lib.mcl_get_ray_kernel_id(self._h, C.byref(v)), "mcl_get_ray_kernel_id")
-        return {1: "k_rays_march", 2: "k_rays_skip", 3: "k_rays_quad", 4: "k_rays_cell", 5: "k_rays_sweep"}.get(v.value, "?")
+        return v.value
+
+    def ray_kernel_name(self):
+        return {1: "k_rays_march", 2: "k_rays_skip", 3: "k_rays_quad", 4: "k_rays_cell", 5: "k_rays_sweep", 6: "k_rays_deskew"}.get(self.ray_kernel_id(), "?")
 
     def ray_kernel_variant(self):
         """Form of k_rays_sweep the last ray stage ran: dict(global_fields, hybrid, turned_directions, pairs)."""
@@ -1897,7 +1995,7 @@ class Engine:
         self._chk(self.lib.mcl_get_ray_kernel_variant(self._h, v), "mcl_get_ray_kernel_variant")
         return dict(global_fields=v[0] == 1, hybrid=v[0] == 2, turned_directions=bool(v[1]), pairs=bool(v[2]))
 
-    RAY_KERNEL_NAMES = {0: None, 1: "k_rays_march", 2: "k_rays_skip", 3: "k_rays_quad", 4: "k_rays_cell", 5: "k_rays_sweep"}
+    RAY_KERNEL_NAMES = {0: None, 1: "k_rays_march", 2: "k_rays_skip", 3: "k_rays_quad", 4: "k_rays_cell", 5: "k_rays_sweep", 6: "k_rays_deskew"}
 
     def planned_ray_kernel(self, n_particles=0):
         """(kernel an update over n_particles WILL run -- None: the configured one cannot run with this map / beam set --, what
