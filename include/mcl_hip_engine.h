@@ -1452,6 +1452,49 @@ int mcl_group_get_stage_timings(const mcl_group_t *g, double ms[6]);           /
 int mcl_group_exchange_bytes(const mcl_group_t *g, uint64_t out[2]);
 int32_t mcl_group_exchanged_lists(const mcl_group_t *g);
 
+/* ---- map patches: a changed rectangle of the grid without a full mcl_set_map --------------------------------
+ * mcl_update_map_region replaces the cells [x0, x0 + width) x [y0, y0 + height) of the map held by `cells` (row-major, row_stride
+ * cells per row, >= width); dimensions, resolution and origin stay.  Afterwards the engine is, byte for byte, an engine on which
+ * mcl_set_map was called with the edited grid: the grid, the isotropic skip field and its nibble copy, the four quadrant fields,
+ * the sixteen wedge fields under the rule the last mcl_set_map used (MCL_WEDGE_METRIC is not read again), their ringed copies where
+ * held, the free-cell list and the likelihood field when the model is on; and it voids what mcl_set_map voids (the captured
+ * graphs and the ordering layout, the recovery averages, the recovery proposal, the fuse call's log-weights, the searches'
+ * lattice, volumes and tables through the map epoch).  The particles, the beams and what depends on the range or the resolution
+ * alone stay.  Every later result equals, bit for bit, that of the engine given the full mcl_set_map instead.
+ *   The device work follows the changed cells, not the map: each table is rebuilt inside the window around the cells whose stop bit
+ * (value > 50) changed that mcl_host_map_patch_plan forms.  A patch that changes no value returns MCL_OK with changed_cells = 0,
+ * launches nothing and voids nothing; one that changes values but no stop bit rewrites the grid and the free list only.
+ * Synchronous, like mcl_set_map.  MCL_ERR_NOT_READY without a map; MCL_ERR_INVALID_ARG for a null pointer, an empty rectangle,
+ * one that leaves the map, or row_stride < width (nothing changes then).  MCL_ERR_HIP part-way leaves "map not set".
+ *   Sharded ranks (mcl_comm_*) must all be given the same patch; that is not checked. */
+typedef struct {
+    int32_t changed_cells, changed_stop_cells;   /* cells whose value / whose (value > 50) differs from the map held */
+    int32_t window[4];                            /* x0, y0, x1, y1 (inclusive, padded-grid cells) of the skip-field window rebuilt; x1 < x0: none */
+    int32_t lf_window[4];                         /* the same for the likelihood field, grid cells; none when the model is off */
+    int64_t free_cells;                           /* n_free after the patch */
+    double  ms;                                   /* wall time of the call */
+} mcl_map_patch_stats_t;
+int mcl_update_map_region(mcl_engine_t *h, const int8_t *cells, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height,
+                          uint32_t row_stride /* cells per row of `cells`, >= width */, mcl_map_patch_stats_t *st /* may be NULL */);
+/* The windows of a patch whose stop-bit changes lie in the box stop_bbox = {x0, y0, x1, y1} (grid cells, inclusive) of a
+ * map_w x map_h map: window = the padded-grid cells of the skip fields a change in the box can alter (the box's padded cells
+ * widened by 254, the reach of a skip value capped at 255; the quadrant and wedge fields change inside it, on the side their rays
+ * come from), lf_window = the grid cells of a likelihood field of reach lf_reach (the box widened by it; {0, 0, -1, -1} for
+ * lf_reach <= 0).  Both clipped to the map, as is the box.  MCL_ERR_INVALID_ARG for a null pointer, an inverted box or one with
+ * no cell inside the map.  Host only; the device path forms its windows here. */
+int mcl_host_map_patch_plan(uint32_t map_w, uint32_t map_h, const int32_t stop_bbox[4] /* grid cells, inclusive */,
+                            int32_t lf_reach /* <= 0: model off */, int32_t window[4], int32_t lf_window[4]);
+/* A map-derived table as stored on the device (copies only, like mcl_get_wedge_fields): the grid (int8, H x W), the isotropic skip
+ * field (Hp x Wps bytes), its nibble copy (Hp x Wps / 2), quadrant field 0 .. 3 (Hp x Wps; MCL_ERR_NOT_READY on a map that has
+ * none) or the free-cell list (n_free uint32).  *needed (may be NULL) receives the byte count; out may be NULL (n_bytes is then
+ * ignored), else n_bytes must equal it. */
+enum { MCL_MAP_TABLE_GRID = 0, MCL_MAP_TABLE_SKIP = 1, MCL_MAP_TABLE_SKIP_NIBBLES = 2, MCL_MAP_TABLE_QUADRANT0 = 3 /* .. 6 */,
+       MCL_MAP_TABLE_FREE_CELLS = 7 };
+int mcl_get_map_table(mcl_engine_t *h, int32_t which, void *out, size_t n_bytes, size_t *needed);
+/* mcl_update_map_region on every engine of the group (no statistics); the first failure is the group's error, as mcl_group_set_map's. */
+int mcl_group_update_map_region(mcl_group_t *g, const int8_t *cells, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height,
+                                uint32_t row_stride);
+
 #ifdef __cplusplus
 }
 #endif

@@ -812,10 +812,8 @@ int refuse_stage(mcl_engine *h)
 // the field and the table of the current map on the device (model on, map set, K checked by the caller)
 int lf_build(mcl_engine *h)
 {
-    const int K = lf_cap(&h->lf, (float)h->res);
-    int reach = (int)std::ceil(std::sqrt((double)K));                    // the least reach with reach^2 >= K
-    while (reach * reach < K) ++reach;
-    while (reach > 0 && (reach - 1) * (reach - 1) >= K) --reach;
+    int K, reach;
+    lf_reach_of(h, K, reach);
     lf_table(h->cfg, h->lf, h->res, K, h->lf_tab);
     h->lf_K = -1;                                                         // until both buffers hold this map's
     h->lf_epoch++;
@@ -1367,6 +1365,7 @@ int mcl_set_map(mcl_engine_t *h, const int8_t *data, uint32_t width, uint32_t he
         // Euclidean rule: the same binary with either field, for A/B measurements (read here, so a process can build both)
         const char *metric = getenv("MCL_WEDGE_METRIC");
         const bool tight = !(metric && atoi(metric) == 0);
+        h->wedge_tight = tight;
         int rc_w = MCL_OK;
         for (int k = 0; k < mcl::kWedges && rc_w == MCL_OK; ++k) {
             mcl::wedge_rows(k, rows.data());
@@ -1415,6 +1414,11 @@ int mcl_set_map(mcl_engine_t *h, const int8_t *data, uint32_t width, uint32_t he
             if (data[i] == 0) fr.push_back((uint32_t)i);
         h->d_free.drop();
         h->n_free = fr.size();
+        h->free_row.assign((size_t)h->H + 1, 0);             // (a map patch splices whole rows of the list)
+        for (size_t y = 0, i = 0; y <= (size_t)h->H; ++y) {
+            while (i < fr.size() && fr[i] < y * (size_t)h->W) ++i;
+            h->free_row[y] = i;
+        }
         if (h->n_free) {
             MCL_TRY(h->d_free.reserve(h, fr.size()));
             HIPCHK(h, hipMemcpy(h->d_free, fr.data(), fr.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -1432,6 +1436,94 @@ int mcl_set_map(mcl_engine_t *h, const int8_t *data, uint32_t width, uint32_t he
         if (rc) { h->have_map = false; return rc; }
     }
     return MCL_OK;
+}
+
+// ---- the kernels of a map patch (mcl_map_patch.h; the flow is mcl_map_patch.hip's), one function per table.  Every launch covers
+// a window inside the table it writes; what it reads lies inside the extended region formed here, clipped to the grid.
+namespace {
+inline mcl::PatchWin patch_win(const int32_t w[4]) { return mcl::PatchWin{w[0], w[1], w[2] - w[0] + 1, w[3] - w[1] + 1}; }
+inline dim3 patch_grid(int w, int rows) { return dim3((unsigned)((w + 255) / 256), (unsigned)rows); }
+int patch_launched(mcl_engine *h, const char *what)
+{
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MCL_OK : fail(h, MCL_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+}  // namespace
+
+int mcl_host::launch_patch_skip_field(mcl_engine *h, const int32_t win[4], MapPatchTmp &t)
+{
+    const mcl::PatchWin w = patch_win(win);
+    const int R = mcl::kPatchReach;
+    // the dilated stop set around the window, out to the one-cell stop border of the work grid at most
+    const int ex0 = std::max(win[0] - R, -1), ey0 = std::max(win[1] - R, -1), ex1 = std::min(win[2] + R, h->Wp), ey1 = std::min(win[3] + R, h->Hp);
+    const mcl::PatchWin e{ex0, ey0, ex1 - ex0 + 1, ey1 - ey0 + 1};
+    MCL_TRY(t.mask.reserve(h, (size_t)e.w * e.h));
+    MCL_TRY(t.g.reserve(h, (size_t)e.w * w.h));
+    hipLaunchKernelGGL(mcl::k_patch_stop_mask, patch_grid(e.w, e.h), dim3(256), 0, h->stream, h->d_grid.p, h->W, h->Wp, h->Hp, e, t.mask.p);
+    hipLaunchKernelGGL(mcl::k_patch_iso_cols, patch_grid(e.w, w.h), dim3(256), 0, h->stream, t.mask.p, e, w.y0, w.h, t.g.p);
+    hipLaunchKernelGGL(mcl::k_patch_iso_rows, patch_grid(w.w, w.h), dim3(256), 0, h->stream, t.g.p, e, h->d_grid.p, h->W, h->Wp, h->Hp, w, h->Wps, h->d_dist.p);
+    const int b0 = win[0] / 2, bw = win[2] / 2 - b0 + 1;            // whole bytes of the nibble copy (win[2] / 2 < Wps / 2)
+    hipLaunchKernelGGL(mcl::k_patch_nibbles, patch_grid(bw, w.h), dim3(256), 0, h->stream, h->d_dist.p, h->Wps, b0, w.y0, bw, h->d_dist4.p);
+    return patch_launched(h, "map patch, isotropic field");
+}
+
+int mcl_host::launch_patch_quadrant(mcl_engine *h, int q, const int32_t win[4], MapPatchTmp &t)
+{
+    static const int qsx[4] = {1, -1, -1, 1}, qsy[4] = {1, 1, -1, -1};
+    const mcl::PatchWin w = patch_win(win);
+    const int R = mcl::kPatchReach + 1;
+    // the rows ahead of the window, the row beyond the grid included
+    const int ey0 = qsy[q] > 0 ? win[1] : std::max(win[1] - R, -1), ey1 = qsy[q] > 0 ? std::min(win[3] + R, h->Hp) : win[3], eh = ey1 - ey0 + 1;
+    MCL_TRY(t.hq[q].reserve(h, (size_t)w.w * eh));
+    hipLaunchKernelGGL(mcl::k_patch_quad_rows, patch_grid(w.w, eh), dim3(256), 0, h->stream, h->d_grid.p, h->W, h->Wp, h->Hp, qsx[q], w, ey0, eh, t.hq[q].p);
+    hipLaunchKernelGGL(mcl::k_patch_quad_cols, patch_grid(w.w, w.h), dim3(256), 0, h->stream, t.hq[q].p, h->d_grid.p, h->W, h->Wp, h->Hp, qsy[q], w, ey0, eh,
+                       h->Wps, h->d_distq[q].p);
+    return patch_launched(h, "map patch, quadrant field");
+}
+
+int mcl_host::launch_patch_wedges(mcl_engine *h, const int32_t win[4], const int32_t quad[4][4], MapPatchTmp &t)
+{
+    constexpr int nrow = 2 * mcl::kWedgeR + 1;
+    static const std::vector<mcl::WedgeRow> all_rows = [] {          // (constants of the wedges; they outlive every copy enqueued from them)
+        std::vector<mcl::WedgeRow> r((size_t)mcl::kWedges * nrow);
+        for (int k = 0; k < mcl::kWedges; ++k) mcl::wedge_rows(k, r.data() + (size_t)k * nrow);
+        return r;
+    }();
+    // the row tables of the window widened by the offsets a cell searches, in that region's own coordinates
+    const int ex0 = std::max(win[0] - mcl::kWedgeR, 0), ey0 = std::max(win[1] - mcl::kWedgeR, 0);
+    const int ex1 = std::min(win[2] + mcl::kWedgeR, h->Wp - 1), ey1 = std::min(win[3] + mcl::kWedgeR, h->Hp - 1);
+    const mcl::PatchWin e{ex0, ey0, ex1 - ex0 + 1, ey1 - ey0 + 1};
+    MCL_TRY(t.nxt.reserve(h, (size_t)e.w * e.h));
+    MCL_TRY(t.prv.reserve(h, (size_t)e.w * e.h));
+    MCL_TRY(t.rows.reserve(h, all_rows.size()));
+    HIPCHK(h, hipMemcpyAsync(t.rows.p, all_rows.data(), all_rows.size() * sizeof(mcl::WedgeRow), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(mcl::k_patch_row_tables, dim3((e.h + 63) / 64), dim3(64), 0, h->stream, h->d_dist.p, h->Wps, e, t.nxt.p, t.prv.p);
+    const size_t fsz = (size_t)h->Hp * h->Wps;
+    for (int k = 0; k < mcl::kWedges; ++k) {
+        const int q = k >> mcl::kWedgeShift;
+        const mcl::PatchWin w = patch_win(quad[q]);
+        uint8_t *field = h->d_distw.p + (size_t)k * fsz;
+        if (h->wedge_tight)
+            hipLaunchKernelGGL(mcl::k_patch_wedge_field<true>, patch_grid(w.w, w.h), dim3(256), 0, h->stream, t.nxt.p, t.prv.p, e, w, h->Wps,
+                               t.rows.p + (size_t)k * nrow, mcl::wedge_cone(k), field);
+        else
+            hipLaunchKernelGGL(mcl::k_patch_wedge_field<false>, patch_grid(w.w, w.h), dim3(256), 0, h->stream, t.nxt.p, t.prv.p, e, w, h->Wps,
+                               t.rows.p + (size_t)k * nrow, mcl::WedgeCone{}, field);
+        if (h->d_distg)
+            hipLaunchKernelGGL(mcl::k_patch_ring_field, patch_grid(w.w, w.h), dim3(256), 0, h->stream, field, h->Wp, h->Hp, h->Wps, h->distg_pitch,
+                               (q == 0 || q == 3) ? 1 : 0, (q == 0 || q == 1) ? 1 : 0, w, h->d_distg.p + (size_t)k * h->distg_stride);
+    }
+    return patch_launched(h, "map patch, wedge fields");
+}
+
+int mcl_host::launch_patch_lfield(mcl_engine *h, const int32_t win[4], int reach, int K, MapPatchTmp &t)
+{
+    const mcl::PatchWin w = patch_win(win);
+    const int ex0 = std::max(win[0] - reach, 0), ew = std::min(win[2] + reach, h->W - 1) - ex0 + 1;
+    MCL_TRY(t.lf_g.reserve(h, (size_t)ew * w.h));
+    hipLaunchKernelGGL(mcl::k_patch_lf_cols, patch_grid(ew, w.h), dim3(256), 0, h->stream, h->d_grid.p, h->W, h->H, reach, ex0, ew, w.y0, w.h, t.lf_g.p);
+    hipLaunchKernelGGL(mcl::k_patch_lf_rows, patch_grid(w.w, w.h), dim3(256), 0, h->stream, t.lf_g.p, ex0, ew, h->W, reach, K, w, h->d_lf_D.p);
+    return patch_launched(h, "map patch, likelihood field");
 }
 
 int mcl_set_beam_angles(mcl_engine_t *h, const float *angles, int32_t n_beams)

@@ -12,6 +12,8 @@
 //                    kernels and buffers, called outside the update)
 //   mcl_refine.hip   mcl_refine_poses: the score of a dense window around each seed pose, its best pose, mean and covariance (its
 //                    own kernels and buffers, called outside the update)
+//   mcl_map_patch.hip  mcl_update_map_region: a changed rectangle of the map into every map-derived table (the kernels are
+//                    mcl_map_patch.h's, reached through the launch_patch_* functions below), mcl_get_map_table
 //   mcl_buffers.h    Buf / DevBuf / HostBuf: every device and pinned buffer of the files above owns its memory through these
 // Only mcl_engine.hip includes the kernels (mcl_kernels.h: the ordered list of the per-stage headers); mcl_engine_access.hip
 // launches none, mcl_comm.hip and mcl_group.hip reach the few kernels they launch through the launch_* functions below.  Every
@@ -30,6 +32,7 @@
 #include <vector>
 
 #include "mcl_types.h"
+#include "mcl_wedge.h"
 #include "mcl_host_math.h"
 #include "mcl_buffers.h"
 
@@ -136,6 +139,8 @@ struct mcl_engine {
     DevBuf<double> d_table;             // double table (product mode)
     DevBuf<uint32_t> d_free;            // linear indices of free cells (data == 0), row-major, cpp:199-213
     uint64_t n_free = 0; uint32_t init_idx = 0;
+    std::vector<uint64_t> free_row;     // H + 1: entries of d_free before row y (a map patch splices the rows it touches, mcl_map_patch.hip)
+    bool wedge_tight = true;            // the rule of the wedge fields held (MCL_WEDGE_METRIC as mcl_set_map read it)
     // ---- beams, and the tables of one scan
     int B = 0, bpad = 0;
     std::vector<float> angles;
@@ -471,6 +476,21 @@ void launch_spin_ms(hipStream_t stream, double ms);
 void launch_stage_pack(hipStream_t stream, const unsigned long long *d_result, double *d_vec, int n_shards, int self, int listed, unsigned long long list_cap);
 void launch_pack_records(hipStream_t stream, const double *x, const double *y, const double *th, int64_t n, double4 *out);
 void launch_group_max(hipStream_t stream, const mcl::GroupMaxArgs &a);
+// the kernels of a map patch (mcl_map_patch.h), table by table, enqueued on the engine's stream; windows inclusive {x0, y0, x1, y1},
+// the temporaries the caller's (launch_patch_* reserve them by the window and they live until the caller has waited for the stream)
+struct MapPatchTmp { DevBuf<uint8_t> mask, g, hq[4]; DevBuf<int32_t> nxt, prv; DevBuf<mcl::WedgeRow> rows; DevBuf<uint16_t> lf_g; };
+int launch_patch_skip_field(mcl_engine *h, const int32_t win[4], MapPatchTmp &t);                      // d_dist, d_dist4
+int launch_patch_quadrant(mcl_engine *h, int q, const int32_t win[4], MapPatchTmp &t);                 // d_distq[q]
+int launch_patch_wedges(mcl_engine *h, const int32_t win[4], const int32_t quad[4][4], MapPatchTmp &t);  // d_distw (after d_dist), d_distg
+int launch_patch_lfield(mcl_engine *h, const int32_t win[4], int reach, int K, MapPatchTmp &t);        // d_lf_D
+// the likelihood field's K and reach on the current map (lf_build's), the model on
+inline void lf_reach_of(const mcl_engine *h, int &K, int &reach)
+{
+    K = lf_cap(&h->lf, (float)h->res);
+    reach = (int)std::ceil(std::sqrt((double)K));                        // the least reach with reach^2 >= K
+    while (reach * reach < K) ++reach;
+    while (reach > 0 && (reach - 1) * (reach - 1) >= K) --reach;
+}
 // the likelihood field outside the update (mcl_query.hip): the used beams of a scan in beam order (LF3) into `out` (B entries of
 // room), their number returned, with `idx` given also the scan beam of each; k_lfield over n poses and nb such beams on the engine's
 // stream, the caller's buffers throughout

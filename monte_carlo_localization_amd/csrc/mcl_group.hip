@@ -151,6 +151,16 @@ int mcl_group_set_map(mcl_group_t *g, const int8_t *data, uint32_t width, uint32
     return MCL_OK;
 }
 
+int mcl_group_update_map_region(mcl_group_t *g, const int8_t *cells, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, uint32_t row_stride)
+{
+    if (!g) return MCL_ERR_INVALID_ARG;
+    for (auto *e : g->eng) {
+        const int rc = mcl_update_map_region(e, cells, x0, y0, width, height, row_stride, nullptr);
+        if (rc) return gfail(g, rc, e->err);
+    }
+    return MCL_OK;
+}
+
 int mcl_group_set_beam_angles(mcl_group_t *g, const float *angles, int32_t n_beams)
 {
     if (!g) return MCL_ERR_INVALID_ARG;

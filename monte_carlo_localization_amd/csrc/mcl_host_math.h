@@ -16,6 +16,13 @@ const char *bad_sensor_fields(const mcl_config_t &c);
 void build_sensor_table(const mcl_config_t &c, int P, std::vector<double> &t);
 void build_distance_field(const int8_t *grid, int W, int H, int Wp, int Hp, int Wps, std::vector<uint8_t> &dist);
 void build_directional_field(const int8_t *grid, int W, int H, int Wp, int Hp, int Wps, int sx, int sy, std::vector<uint8_t> &dist);
+// The windows of a map patch (mcl_update_map_region), inclusive, x1 < x0: none.  From the box of the grid cells
+// whose stop bit changed: `win` the isotropic field's (padded cells; the union of the others), quad[q] the window of quadrant field
+// q and of the wedge fields of that quadrant, lf the likelihood field's (grid cells; lf_reach <= 0: none).  The box is clipped to
+// the map; false when it is inverted or has no cell inside.
+constexpr int kMapPatchReach = 254;      // a stop cell further away than this, per axis, changes no skip value (the cap is 255)
+struct MapPatchPlan { int32_t win[4], quad[4][4], lf[4]; };
+bool map_patch_plan(int W, int H, const int32_t stop_bbox[4], int lf_reach, MapPatchPlan &p);
 void motion_scalars(const double action[3], double &dt, double &v, double &w);
 uint32_t systematic_offset(uint32_t seed_lo, uint32_t seed_hi, uint32_t update_idx);
 const char *kld_invalid(const mcl_kld_config_t *k, int64_t cap);

@@ -202,6 +202,32 @@ void build_directional_field(const int8_t *grid, int W, int H, int Wp, int Hp, i
     (void)INF; (void)H;
 }
 
+// Which cells of which table a changed stop cell can alter.  Grid cell (gx, gy) is padded cell (gx + 1, gy + 1),
+// and grid row / column 0 also feeds padded row / column 0.  A skip value is min(floor(gap) + 1, 255): a stop cell changes it only
+// where its gap is below 254, and gap >= |offset| - 1 per axis (isotropic: the dilated cell is one nearer, the centre distance
+// one more), so the offsets that matter are at most kMapPatchReach per axis -- on every side for the isotropic field, on the side
+// the rays come from for a quadrant field and the wedge fields of that quadrant.  The likelihood field is capped at K <= reach^2.
+bool map_patch_plan(int W, int H, const int32_t b[4], int lf_reach, MapPatchPlan &p)
+{
+    if (W <= 0 || H <= 0 || b[2] < b[0] || b[3] < b[1] || b[2] < 0 || b[3] < 0 || b[0] >= W || b[1] >= H) return false;
+    const int gx0 = std::max(b[0], 0), gy0 = std::max(b[1], 0), gx1 = std::min(b[2], W - 1), gy1 = std::min(b[3], H - 1);
+    const int px0 = gx0 == 0 ? 0 : gx0 + 1, py0 = gy0 == 0 ? 0 : gy0 + 1, px1 = gx1 + 1, py1 = gy1 + 1;      // the padded stop cells
+    const int R = kMapPatchReach;
+    p.win[0] = std::max(px0 - R, 0); p.win[1] = std::max(py0 - R, 0); p.win[2] = std::min(px1 + R, W); p.win[3] = std::min(py1 + R, H);
+    static const int qsx[4] = {1, -1, -1, 1}, qsy[4] = {1, 1, -1, -1};
+    for (int q = 0; q < 4; ++q) {
+        p.quad[q][0] = qsx[q] > 0 ? p.win[0] : px0; p.quad[q][2] = qsx[q] > 0 ? px1 : p.win[2];
+        p.quad[q][1] = qsy[q] > 0 ? p.win[1] : py0; p.quad[q][3] = qsy[q] > 0 ? py1 : p.win[3];
+    }
+    if (lf_reach > 0) {
+        p.lf[0] = (int32_t)std::max<int64_t>((int64_t)gx0 - lf_reach, 0); p.lf[1] = (int32_t)std::max<int64_t>((int64_t)gy0 - lf_reach, 0);
+        p.lf[2] = (int32_t)std::min<int64_t>((int64_t)gx1 + lf_reach, W - 1); p.lf[3] = (int32_t)std::min<int64_t>((int64_t)gy1 + lf_reach, H - 1);
+    } else {
+        p.lf[0] = p.lf[1] = 0; p.lf[2] = p.lf[3] = -1;
+    }
+    return true;
+}
+
 // cpp:452-471
 void motion_scalars(const double action[3], double &dt, double &v, double &w)
 {
@@ -959,6 +985,16 @@ int mcl_host_sweep_global_layout(uint32_t width, uint32_t height, int32_t max_ra
     const mcl::SweepGlobalLayout g = mcl::sweep_global_layout(Wp, Hp, max_range_px);
     out[0] = g.ok ? 1 : 0; out[1] = g.pitch; out[2] = g.rows; out[3] = (int64_t)g.stride; out[4] = (int64_t)g.alloc;
     out[5] = (int64_t)mcl::sweep_global_max_offset(g, Wp, Hp, max_range_px, mcl::kWedges - 1);
+    return MCL_OK;
+}
+
+int mcl_host_map_patch_plan(uint32_t map_w, uint32_t map_h, const int32_t stop_bbox[4], int32_t lf_reach, int32_t window[4], int32_t lf_window[4])
+{
+    if (!stop_bbox || !window || !lf_window || map_w == 0 || map_h == 0 || map_w > 200000 || map_h > 200000) return MCL_ERR_INVALID_ARG;
+    MapPatchPlan p;
+    if (!map_patch_plan((int)map_w, (int)map_h, stop_bbox, lf_reach, p)) return MCL_ERR_INVALID_ARG;
+    std::memcpy(window, p.win, sizeof(p.win));
+    std::memcpy(lf_window, p.lf, sizeof(p.lf));
     return MCL_OK;
 }
 

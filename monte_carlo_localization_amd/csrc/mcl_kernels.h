@@ -28,4 +28,5 @@
 #include "mcl_rays_lists.h"         // (mcl_rays_legacy.h in its place, under MCL_LEGACY_RAY_KERNELS)
 #include "mcl_weights.h"
 #include "mcl_rays_sweep.h"
-#include "mcl_rays_deskew.h"        // (last: per-beam sensor offsets)
+#include "mcl_rays_deskew.h"        // (per-beam sensor offsets)
+#include "mcl_map_patch.h"          // (last: the windowed field builders of a map patch; off the update path)

@@ -71,6 +71,7 @@ EXPORTS = [
     "mcl_group_set_sensor_mount", "mcl_host_sensor_mount", "mcl_host_sensor_unmount", "mcl_host_sensor_mount_cov",
     "mcl_set_beam_offsets", "mcl_get_beam_offsets", "mcl_beam_origins", "mcl_host_scan_motion_offsets", "mcl_host_beam_offset_table",
     "mcl_host_beam_offset_pairs",
+    "mcl_update_map_region", "mcl_host_map_patch_plan", "mcl_get_map_table", "mcl_group_update_map_region",
 ]
 MOTION_REFERENCE, MOTION_DIFF, MOTION_OMNI = 0, 1, 2
 MOTION_MODELS = {"reference": MOTION_REFERENCE, "diff": MOTION_DIFF, "omni": MOTION_OMNI}
@@ -341,6 +342,12 @@ def load_library(legacy=False):
         lib.mcl_set_likelihood_field.argtypes = [C.c_void_p, C.POINTER(LikelihoodFieldConfig)]
         lib.mcl_get_likelihood_field.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         lib.mcl_get_wedge_fields.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32)]
+        lib.mcl_update_map_region.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                              C.POINTER(MapPatchStats)]
+        lib.mcl_group_update_map_region.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
+        lib.mcl_host_map_patch_plan.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32),
+                                                C.POINTER(C.c_int32)]
+        lib.mcl_get_map_table.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         lib.mcl_get_ring_fields.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         lib.mcl_get_sweep_table.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32)]
         lib.mcl_host_sweep_global_layout.argtypes = [C.c_uint32, C.c_uint32, C.c_int32, C.POINTER(C.c_int64)]
@@ -1113,6 +1120,37 @@ def host_wedge_tight_table(wedge: int):
     return val, reach.astype(bool)
 
 
+class MapPatchStats(C.Structure):
+    _fields_ = [("changed_cells", C.c_int32), ("changed_stop_cells", C.c_int32), ("window", C.c_int32 * 4), ("lf_window", C.c_int32 * 4),
+                ("free_cells", C.c_int64), ("ms", C.c_double)]
+
+
+# mcl_get_map_table: name -> (selector, dtype)
+MAP_TABLES = {"grid": (0, np.int8), "skip": (1, np.uint8), "skip_nibbles": (2, np.uint8), "quadrant0": (3, np.uint8), "quadrant1": (4, np.uint8),
+              "quadrant2": (5, np.uint8), "quadrant3": (6, np.uint8), "free_cells": (7, np.uint32)}
+
+
+def host_map_patch_plan(width: int, height: int, stop_bbox, lf_reach: int = 0):
+    """mcl_host_map_patch_plan: (window, lf_window), each (x0, y0, x1, y1) inclusive (x1 < x0: none) -- the padded-grid cells of the
+    skip fields, and the grid cells of a likelihood field of reach lf_reach, that a stop-bit change inside the box stop_bbox
+    (grid cells, inclusive) of a width x height map can alter.  EngineError INVALID_ARG for an inverted box or one outside the map."""
+    box = (C.c_int32 * 4)(*[int(v) for v in stop_bbox])
+    win, lfw = (C.c_int32 * 4)(), (C.c_int32 * 4)()
+    rc = load_library().mcl_host_map_patch_plan(C.c_uint32(width), C.c_uint32(height), box, C.c_int32(lf_reach), win, lfw)
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_map_patch_plan rc={rc}", rc)
+    return tuple(win), tuple(lfw)
+
+
+def _patch_cells(cells2d):
+    c = np.asarray(cells2d, np.int8)
+    if c.ndim != 2:
+        raise ValueError("update_map_region: cells must be a 2-D array (rows, columns)")
+    if c.strides[1] != 1 or c.strides[0] < c.shape[1]:       # (a view whose rows are contiguous is passed as it is, with its row stride)
+        c = np.ascontiguousarray(c, np.int8)
+    return c
+
+
 def host_skip_field_dir(grid, quadrant: int) -> np.ndarray:
     """Directional skip field for rays of one direction quadrant (0:+x+y 1:-x+y 2:-x-y 3:+x-y)."""
     g = _c(grid, np.int8)
@@ -1166,6 +1204,25 @@ class Engine:
                                        C.c_double(origin_x), C.c_double(origin_y)), "mcl_set_map")
         self.map_shape = (H, W)
         self.map_resolution = float(np.float32(resolution))
+
+    def update_map_region(self, cells2d, x0: int, y0: int) -> dict:
+        """mcl_update_map_region: the cells [x0, x0 + w) x [y0, y0 + h) of the map replaced by cells2d (h, w), every map-derived
+        table brought to what set_map of the edited grid would build.  Returns the statistics of the patch."""
+        c = _patch_cells(cells2d)
+        st = MapPatchStats()
+        self._chk(self.lib.mcl_update_map_region(self._h, _p(c), C.c_uint32(x0), C.c_uint32(y0), C.c_uint32(c.shape[1]), C.c_uint32(c.shape[0]),
+                                                 C.c_uint32(c.strides[0]), C.byref(st)), "mcl_update_map_region")
+        return dict(changed_cells=int(st.changed_cells), changed_stop_cells=int(st.changed_stop_cells), window=tuple(st.window),
+                    lf_window=tuple(st.lf_window), free_cells=int(st.free_cells), ms=float(st.ms))
+
+    def map_table(self, name: str) -> np.ndarray:
+        """A map-derived table as stored on the device (mcl_get_map_table), flat: one of MAP_TABLES."""
+        which, dt = MAP_TABLES[name]
+        need = C.c_size_t()
+        self._chk(self.lib.mcl_get_map_table(self._h, C.c_int32(which), None, C.c_size_t(0), C.byref(need)), "mcl_get_map_table")
+        out = np.empty(need.value // np.dtype(dt).itemsize, dt)
+        self._chk(self.lib.mcl_get_map_table(self._h, C.c_int32(which), _p(out), C.c_size_t(need.value), None), "mcl_get_map_table")
+        return out
 
     @property
     def max_range_px(self) -> int:
@@ -2253,6 +2310,12 @@ class Group:
         H, W = g.shape
         self._chk(self.lib.mcl_group_set_map(self._h, _p(g), C.c_uint32(W), C.c_uint32(H), C.c_float(resolution),
                                              C.c_double(origin_x), C.c_double(origin_y)), "mcl_group_set_map")
+
+    def update_map_region(self, cells2d, x0: int, y0: int):
+        """mcl_group_update_map_region: Engine.update_map_region on every engine of the group."""
+        c = _patch_cells(cells2d)
+        self._chk(self.lib.mcl_group_update_map_region(self._h, _p(c), C.c_uint32(x0), C.c_uint32(y0), C.c_uint32(c.shape[1]), C.c_uint32(c.shape[0]),
+                                                       C.c_uint32(c.strides[0])), "mcl_group_update_map_region")
 
     def set_beam_angles(self, angles):
         a = _c(angles, np.float32)
