@@ -1258,6 +1258,32 @@ int mcl_get_sort_order(mcl_engine_t *h, uint32_t *keys, uint32_t *perm, size_t n
  * (cos, sin, pixel x, pixel y) beside the heading column (the first update of a set, whose keys k_sort_keys makes).
  * MCL_ERR_NOT_READY as above. */
 int mcl_get_sort_record_form(mcl_engine_t *h, int32_t *heading_form);
+/* ---- the guide of the compact parent list (csrc/mcl_compact_guide.h; for tests and tools: tests/test_compact_guide_host.py,
+ * tests/test_gpu_compact_guide.py).  The scan that writes the list (mcl_get_compact_list) also writes, for 2^m evenly spaced
+ * thresholds, where the list's search starts:
+ *   s = max(0, bit_width(q_total) - m), the bucket of a threshold is thr >> s, bmax = q_total >> s;
+ *   guide[b], b = 0 .. bmax: the first list position p with ccdf[p] >= (b << s); a reader takes guide[b + 1] as n_compact when
+ *   b + 1 > bmax.  For thr in bucket b the first entry with ccdf > thr lies in [guide[b], guide[b + 1]].
+ * mcl_host_compact_guide fills guide (n_guide = bmax + 1 words; NULL: only *s / *bmax are computed) from a list's strictly increasing
+ * CDF column whose last entry is q_total, by the rule the scan kernel follows -- entry p writes the words of the boundaries in
+ * (ccdf[p - 1], ccdf[p]], entry 0 also word 0 -- and reports in *n_written (may be NULL) how many words it stored: bmax + 1, each once.
+ * mcl_host_compact_search returns for each of n thresholds the position the resampling kernel selects: the first entry with
+ * ccdf > thr, found between the two guide words, clamped to n_compact - 1.  It reads word b + 1 of every bucket it looks up without
+ * using the one behind bmax, so n_guide >= bmax + 2 (the engine's table has that word too).  m in 8 .. 20.  Host only. */
+int mcl_host_compact_guide(const uint64_t *ccdf, int64_t n_compact, uint64_t q_total, int32_t m, uint32_t *guide, size_t n_guide,
+                           int32_t *s, uint32_t *bmax, int64_t *n_written);
+int mcl_host_compact_search(const uint64_t *ccdf, int64_t n_compact, const uint32_t *guide, size_t n_guide, int32_t s, uint32_t bmax,
+                            const uint64_t *thr, int64_t n, int64_t *pos);
+/* The guide of the list that describes the current particles, as the device holds it: info = {s, bmax, n_compact, q_total (the
+ * grand total the scan left on the device), m, 1 when the last update's resampling searched through the guide}; guide (may be
+ * NULL) receives n_guide = bmax + 1 words, ccdf (may be NULL) the list's n_ccdf = n_compact CDF values.  Copies only.
+ * Without a list, with an empty one or without a guide (MCL_RESAMPLE_GUIDE=0 in the environment of mcl_create) a call that asks
+ * for guide or ccdf is MCL_ERR_NOT_READY, and one that asks for neither reports {-1, -1, the list's length or -1, 0, m or 0, the
+ * last draw's path}; MCL_ERR_INVALID_ARG for a wrong size.  The guide serves the multinomial draw of a single engine without KLD sizing; systematic
+ * resampling, KLD sampling, sharded lists, a dense CDF and injected indices keep the search through ctop, and an engine configured
+ * for systematic resampling, with KLD sampling on, with a communicator or in a device group does not have its scans write a guide
+ * (the call is then MCL_ERR_NOT_READY as above).  MCL_RESAMPLE_GUIDE_M=<8..20> sets m (default 17). */
+int mcl_get_compact_guide(mcl_engine_t *h, uint32_t *guide, size_t n_guide, uint64_t *ccdf, size_t n_ccdf, int64_t info[6]);
 
 /* ---- multi-GPU staging (one engine per rank; collectives are the host's) -- */
 /* Device pointers of engine-owned buffers so the host can hand them to RCCL without copies. */

@@ -782,7 +782,7 @@ int weights_and_cdf(mcl_engine *h, bool result_to_host = false, const mcl::KldAr
         h->max_partials_ready = false;
         h->carry_pending = false;
         h->blocktot_for = nullptr;             // no spine / leaders for this CDF: the resampling search bisects it directly
-        h->compact_n = -1; h->compact_pending = false; h->list_epoch++;
+        h->compact_n = -1; h->compact_pending = false; h->guide_valid = h->guide_pending = false; h->list_epoch++;
         return MCL_OK;
     }
     MCL_TRY(sensor_and_weights(h, nullptr, true));             // (the sums are finished by the scan's spine)
@@ -988,12 +988,18 @@ int mcl_host::scan_weights(mcl_engine *h, const uint64_t *d_q, uint64_t *d_cdf, 
         co.block_cnt = h->d_blockcnt; co.ccdf = h->d_ccdf; co.cidx = h->d_cidx; co.crec = h->d_crec; co.ctop = h->d_ctop;
         co.x = h->d_x[h->cur]; co.y = h->d_y[h->cur]; co.th = h->d_th[h->cur];
         co.cap = (uint32_t)h->compact_cap; co.total = h->d_result + 16;
+        // the guide, while this engine can draw through it: a single engine (a sharded set searches the merged lists) without KLD sizing.
+        // The spine leaves the grand total in its own word of the result block (besides the caller's d_total, if any): k_scan_final,
+        // the resampling kernel and mcl_get_compact_guide all take the shift from that one word.
+        if (h->d_cguide && !h->kld_on && !h->comm && !h->in_group) {
+            co.guide = h->d_cguide; co.q_total = reinterpret_cast<const uint64_t *>(h->d_result.p + kResultGuideTotal); co.guide_m = h->guide_m;
+        }
     }
     hipLaunchKernelGGL(mcl::k_scan_partials, dim3(nb), dim3(mcl::kScanThreads), 0, h->stream, d_q, n, h->d_blocktot, co.block_cnt);
     // (the spine is one workgroup that runs right after k_weights: it also finishes that kernel's partial sums, when asked)
     const bool fold = h->sums_pending && d_q == h->d_q;
     hipLaunchKernelGGL(mcl::k_scan_spine, dim3(1), dim3(1024), 0, h->stream, h->d_blocktot, nb, offset, d_total, co.block_cnt, co.total,
-                       fold ? h->d_part : (const double *)nullptr, mcl::kRedBlocks, h->d_scalars);
+                       fold ? h->d_part : (const double *)nullptr, mcl::kRedBlocks, h->d_scalars, const_cast<uint64_t *>(co.q_total));
     if (fold) h->sums_pending = false;
     const size_t nlead = (size_t)((n + 15) >> mcl::kLeaderShift) + 1;
     if (nlead > h->d_leaders.cap) {
@@ -1009,7 +1015,7 @@ int mcl_host::scan_weights(mcl_engine *h, const uint64_t *d_q, uint64_t *d_cdf, 
     }
     HIPCHK(h, hipGetLastError());
     h->blocktot_for = d_cdf; h->blocktot_n = n;
-    if (d_cdf == h->d_cdf) { h->compact_n = -1; h->compact_pending = own; h->list_epoch++; }
+    if (d_cdf == h->d_cdf) { h->compact_n = -1; h->compact_pending = own; h->guide_valid = false; h->guide_pending = co.guide != nullptr; h->list_epoch++; }
     return MCL_OK;
 }
 
@@ -1031,6 +1037,8 @@ void mcl_host::unpack_result(mcl_engine *h)
         const unsigned long long na = h->h_result[16];
         h->compact_n = na <= (unsigned long long)h->compact_cap ? (int64_t)na : -1;       // 0: a valid, empty list (no weight here)
         h->compact_pending = false;
+        h->guide_valid = h->guide_pending && h->compact_n > 0;
+        h->guide_pending = false;
     }
 }
 
@@ -1054,6 +1062,8 @@ static EnvKnobs read_knobs()
     if (const char *e = getenv("MCL_SORT_FINE_SUB")) k.sort_fine_sub = atoi(e);
     if (const char *e = getenv("MCL_FIX_WG")) k.fix_wg = atoi(e);
     if (const char *e = getenv("MCL_FIX_DEAL")) k.fix_deal_seg = std::strcmp(e, "seg") == 0;
+    if (const char *e = getenv("MCL_RESAMPLE_GUIDE")) k.resample_guide = atoi(e);
+    if (const char *e = getenv("MCL_RESAMPLE_GUIDE_M")) k.guide_m = atoi(e);
     if (const char *e = getenv("MCL_DEBUG_WG")) k.debug_wg = e;
     k.no_bucket_cuts = getenv("MCL_NO_BUCKET_CUTS") != nullptr;
     if (const char *e = getenv("MCL_SWEEP_GLOBAL")) k.sweep_global = atoi(e) != 0;
@@ -1143,11 +1153,16 @@ int mcl_create(const mcl_config_t *cfg, mcl_engine_t **out)
     CRB(h->d_ctop, (size_t)h->compact_cap / 64 + 1);
     CRB(h->d_cidx, (size_t)h->compact_cap);
     CRB(h->d_crec, (size_t)h->compact_cap);
+    if (h->env.resample_guide && h->cfg.resample_mode == MCL_RESAMPLE_MULTINOMIAL) {     // (the systematic comb never reads one)
+        h->guide_m = h->env.guide_m > 0 ? std::min(std::max(h->env.guide_m, mcl::kGuideLog2Min), mcl::kGuideLog2Max) : mcl::kGuideLog2Default;
+        CRB(h->d_cguide, mcl::guide_words(h->guide_m));
+        CRT(hipMemset(h->d_cguide, 0, mcl::guide_words(h->guide_m) * sizeof(uint32_t)));  // (the word behind the last boundary is fetched, never written, never used)
+    }
     CRB(h->d_idx, cap);
     CRB(h->d_part, (size_t)mcl::kRedBlocks * 8);
     CRB(h->d_maxpart, (size_t)mcl::kRedBlocks);
-    CRB(h->d_result, 32);
-    CRT(hipMemset(h->d_result, 0, 32 * 8));
+    CRB(h->d_result, kResultAlloc);
+    CRT(hipMemset(h->d_result, 0, kResultAlloc * 8));
     CRB(h->h_result, 48);
     std::memset(h->h_result, 0, 48 * 8);
     h->d_scalars = reinterpret_cast<double *>(h->d_result.p);
@@ -2007,6 +2022,10 @@ static int launch_update_resample(mcl_engine *h, Update &u, const double *d_norm
     if (compact) {
         a.ccdf = h->d_ccdf; a.ctop = h->d_ctop; a.n_compact = h->compact_n; a.cidx = h->d_cidx; a.crec = h->d_crec;
         a.cpack = nullptr;               // the next update most likely draws from a compact list again: no record per child
+        // the list's guide, for the multinomial draw (the systematic comb compares 128-bit products; a KLD-sized draw keeps the ctop search)
+        if (h->guide_valid && a.mode == MCL_RESAMPLE_MULTINOMIAL && !u.kld) {
+            a.cguide = h->d_cguide; a.cguide_q = reinterpret_cast<const uint64_t *>(h->d_result.p + kResultGuideTotal); a.cguide_m = h->guide_m;
+        }
     } else {
         if (!h->pack_valid[c] && n_par > 65536 && !u.keep) {   // records first: one fetch per gathered parent instead of three
             hipLaunchKernelGGL(mcl::k_pack_records, dim3((unsigned)((n_par + 255) / 256)), dim3(256), 0, h->stream, h->d_x[c], h->d_y[c], h->d_th[c], n_par, h->d_pack[c]);
@@ -2085,6 +2104,7 @@ static int launch_update_resample(mcl_engine *h, Update &u, const double *d_norm
     h->resampled_last = !u.keep;
     h->pack_valid[nx] = a.cpack != nullptr;
     h->compact_used = compact;
+    h->guide_used = a.cguide != nullptr;
     h->have_idx = true;
     return MCL_OK;
 }
@@ -2130,6 +2150,7 @@ static bool graph_ready(mcl_engine *h, const Update &u)
     int rc = upload_observation(h);
     if (!rc) rc = launch_rays(h, h->d_x[gi], h->d_y[gi], h->d_th[gi], u.n);
     if (!rc) rc = weights_and_cdf(h);
+    h->graph_guide[gi] = h->guide_pending;          // (what the captured scan writes, at every replay)
     hipError_t ce = hipSuccess;
     if (!rc) ce = hipMemcpyAsync(h->h_result, h->d_result, kResultWords * 8, hipMemcpyDeviceToHost, h->stream);
     h->capturing = false;
@@ -2155,6 +2176,7 @@ static int tail_graph(mcl_engine *h, const Update &u)
     HIPCHK(h, hipEventRecord(h->ev[EV_SENSOR], h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->compact_pending = h->d_ccdf != nullptr && !h->env.no_compact && u.n > mcl::kTinyTailMax;   // the captured scan wrote a list
+    h->guide_valid = false; h->guide_pending = h->compact_pending && h->graph_guide[h->cur];       // ... and, if it did at capture, the guide
     unpack_result(h);
     h->carry_pending = false;
     // the captured tail is one unit: its time is reported as the ray-cast stage (query prep and table evaluation
@@ -2559,6 +2581,7 @@ int mcl_host::stage_resample_launch(mcl_engine_t *h, const ParentSource &src, co
     h->cur = nx;
     h->pack_valid[nx] = a.cpack != nullptr;
     h->compact_used = src.gcdf != nullptr;
+    h->guide_used = false;
     h->have_idx = true;
     h->have_logw = false;
     h->sp_valid = h->weighted = false;

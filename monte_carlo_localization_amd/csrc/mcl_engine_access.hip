@@ -3,6 +3,7 @@
 // header with a non-static __global__ is included.  What launches, asks choose_ray_mode or belongs to the staged flow: mcl_engine.hip.
 #include "mcl_engine_internal.h"
 #include "mcl_wedge.h"
+#include "mcl_compact_guide.h"
 #include <cstring>
 
 using namespace mcl_host;
@@ -392,6 +393,30 @@ int mcl_get_sort_order(mcl_engine_t *h, uint32_t *keys, uint32_t *perm, size_t n
         HIPCHK(h, hipMemcpyAsync(tilemap, o.tilemap, n_tiles * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MCL_OK;
+}
+
+int mcl_get_compact_guide(mcl_engine_t *h, uint32_t *guide, size_t n_guide, uint64_t *ccdf, size_t n_ccdf, int64_t info[6])
+{
+    if (!h || !info) return MCL_ERR_INVALID_ARG;
+    info[0] = -1; info[1] = -1; info[2] = h->compact_n; info[3] = 0; info[4] = h->d_cguide ? h->guide_m : 0; info[5] = h->guide_used ? 1 : 0;
+    if (!h->guide_valid || h->compact_n <= 0) {
+        if (!guide && !ccdf) return MCL_OK;               // (what the host knows without a list: its length, m, the last draw's path)
+        return fail(h, MCL_ERR_NOT_READY, "no compact list with a guide describes the current particles");
+    }
+    uint64_t q = 0;
+    MCL_TRY(read_back(h, {{&q, h->d_result.p + kResultGuideTotal, sizeof(q)}}));
+    const int s = mcl::guide_shift(q, h->guide_m);
+    const uint32_t bmax = mcl::guide_bmax(q, s);
+    info[0] = s; info[1] = (int64_t)bmax; info[2] = h->compact_n; info[3] = (int64_t)q; info[4] = h->guide_m; info[5] = h->guide_used ? 1 : 0;
+    if (guide) {
+        if (n_guide != (size_t)bmax + 1) return fail(h, MCL_ERR_INVALID_ARG, "the guide has bmax + 1 words");
+        MCL_TRY(read_back(h, {{guide, h->d_cguide, n_guide * sizeof(uint32_t)}}));
+    }
+    if (ccdf) {
+        if (n_ccdf != (size_t)h->compact_n) return fail(h, MCL_ERR_INVALID_ARG, "the list has n_compact entries");
+        MCL_TRY(read_back(h, {{ccdf, h->d_ccdf, n_ccdf * sizeof(uint64_t)}}));
+    }
     return MCL_OK;
 }
 

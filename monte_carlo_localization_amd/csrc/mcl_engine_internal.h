@@ -44,6 +44,9 @@ constexpr unsigned long long kExactCap = 1ull << 16;   // level-3 rays per launc
 // length, [15] far-list length (and the staging word of a global maximum), [16] length of the compact parent list, [17] pose-space
 // bins the update's draw occupied (KLD sampling, mcl_set_kld)
 constexpr int kResultWords = 18;
+constexpr int kResultGuideTotal = 18;        // d_result word (device only, behind the copied ones): the grand total of the scan that wrote the compact list's guide
+constexpr int kResultAlloc = 32;             // words d_result is allocated with
+static_assert(kResultGuideTotal >= kResultWords && kResultGuideTotal < kResultAlloc, "the guide's total lies behind the copied words, inside the block");
 constexpr int kResultStage = 40;             // h_result word that stages a host value on its way to the device
 constexpr int kResultStamp = 32;             // h_result word a small update's last kernel stamps (the host polls it)
 
@@ -100,6 +103,8 @@ struct EnvKnobs {
                                         //   given MCL_SORT_FINE, mcl::kSortFineSubDefault with the default bits
     int fix_wg = 0;                     // MCL_FIX_WG=<n>: workgroups of k_rays_fix per CU in the flat deal (default mcl::kFixWgPerCu)
     bool fix_deal_seg = false;          // MCL_FIX_DEAL=seg: k_rays_fix deals per segment (what it does anyway beyond mcl::kFixSegMax segments)
+    int resample_guide = 1;             // MCL_RESAMPLE_GUIDE=0: no guide of the compact list, the resampling search goes through ctop (the search of earlier rounds)
+    int guide_m = 0;                    // MCL_RESAMPLE_GUIDE_M=<8..20>: log2 of the guide's buckets (default mcl::kGuideLog2Default)
     std::string debug_wg;               // MCL_DEBUG_WG=<file>: four words per persistent workgroup (ray_debug_dump)
     bool no_bucket_cuts = false;        // MCL_NO_BUCKET_CUTS: units on the plain grid of 1024 slots, sparse sets ordered by whole tiles (rounds 2-3 before the cuts)
     bool sweep_global = false;          // MCL_SWEEP_GLOBAL=1: k_rays_sweep on the wedge fields in global memory whatever the range
@@ -200,6 +205,15 @@ struct mcl_engine {
     DevBuf<uint64_t> d_ccdf, d_ctop;
     DevBuf<uint32_t> d_cidx;
     DevBuf<double4> d_crec;
+    // the list's guide (mcl_compact_guide.h): written by the scan that writes the list while the engine can use it (guide_wanted:
+    // a single engine without KLD sizing), read by the multinomial draw; null with MCL_RESAMPLE_GUIDE=0 or systematic resampling.
+    // guide_pending / guide_valid follow compact_pending / compact_n: one writer (scan_weights), voided wherever the list is.
+    DevBuf<uint32_t> d_cguide;
+    int guide_m = 0;                    // log2 of its buckets
+    bool guide_pending = false;         // the last scan of the engine's own weights wrote the guide beside the list
+    bool guide_valid = false;           // ... and the list it belongs to is the valid one (compact_n > 0)
+    bool graph_guide[2] = {false, false};   // the captured tail of particle buffer 0 / 1 writes the guide
+    bool guide_used = false;            // the last resampling searched through it
     int64_t compact_cap = 0;            // room in the list (cap / 4, at least 4096)
     int64_t compact_n = -1;             // entries of the list that describes d_cdf / the current particles; -1: none
     bool compact_pending = false;       // the last scan wrote a list; its length arrives with the next result read-back

@@ -12,6 +12,7 @@
 #include "mcl_refine_core.h"
 #include "mcl_wedge.h"
 #include "mcl_sort_key.h"
+#include "mcl_compact_guide.h"
 
 namespace mcl_host {
 
@@ -1012,6 +1013,40 @@ int mcl_host_sort_key(const int32_t bbox[7], const int32_t *tilemap, int32_t ntx
         const double gx = px[i] * mcl::kSortSub, gy = py[i] * mcl::kSortSub;        // (what the ordering kernels hand sort_key, term for term)
         keys[i] = mcl::sort_key(bbox, tilemap, ntx_abs, mcl::cell_of(gx, hx), mcl::cell_of(gy, hy), theta[i], n_layout, gx - floor(gx), gy - floor(gy), fine);
     }
+    return MCL_OK;
+}
+
+int mcl_host_compact_guide(const uint64_t *ccdf, int64_t n_compact, uint64_t q_total, int32_t m, uint32_t *guide, size_t n_guide,
+                           int32_t *s_out, uint32_t *bmax_out, int64_t *n_written)
+{
+    if (!ccdf || n_compact <= 0 || n_compact > 0xffffffffll || m < mcl::kGuideLog2Min || m > mcl::kGuideLog2Max || ccdf[n_compact - 1] != q_total)
+        return MCL_ERR_INVALID_ARG;
+    const int s = mcl::guide_shift(q_total, m);
+    const uint32_t bmax = mcl::guide_bmax(q_total, s);
+    if (s_out) *s_out = s;
+    if (bmax_out) *bmax_out = bmax;
+    if (!guide) return MCL_OK;
+    if (n_guide != (size_t)bmax + 1) return MCL_ERR_INVALID_ARG;
+    int64_t written = 0;
+    uint64_t prev = 0;
+    for (int64_t p = 0; p < n_compact; ++p) {                 // the scan's rule, entry by entry: every owner writes its own range
+        const uint64_t c = ccdf[p];
+        if (c <= prev) return MCL_ERR_INVALID_ARG;            // (a list entry carries weight: the CDF is strictly increasing)
+        uint32_t b0, b1;
+        mcl::guide_owner_range(c, c - prev, s, (uint32_t)p, b0, b1);
+        for (uint32_t b = b0; b < b1; ++b) { guide[b] = (uint32_t)p; ++written; }
+        prev = c;
+    }
+    if (n_written) *n_written = written;
+    return MCL_OK;
+}
+
+int mcl_host_compact_search(const uint64_t *ccdf, int64_t n_compact, const uint32_t *guide, size_t n_guide, int32_t s, uint32_t bmax,
+                            const uint64_t *thr, int64_t n, int64_t *pos)
+{
+    if (!ccdf || !guide || !thr || !pos || n < 0 || n_compact <= 0 || n_compact > 0xffffffffll || s < 0 || s > 63 || n_guide < (size_t)bmax + 2)
+        return MCL_ERR_INVALID_ARG;
+    for (int64_t i = 0; i < n; ++i) pos[i] = (int64_t)mcl::compact_guide_search(ccdf, (uint32_t)n_compact, guide, s, bmax, thr[i]);
     return MCL_OK;
 }
 

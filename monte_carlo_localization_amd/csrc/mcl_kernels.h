@@ -16,6 +16,7 @@
 #include "mcl_wedge.h"
 #include "mcl_motion.h"
 #include "mcl_sort_key.h"
+#include "mcl_compact_guide.h"
 
 // Each stage header is included from here only, inside the context of the includes above.  The order of these includes is the order
 // of the kernels in the code object (tools/kernel_compare.py compares it with a parent's): a new header goes where its kernels are to lie.

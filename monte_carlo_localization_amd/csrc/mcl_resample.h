@@ -70,6 +70,11 @@ struct ResampleArgs {
     const double4 *crec;              // ... and its record
     const unsigned char *cchunks;     // gathered lists (cidx / crec null): entry p lives in chunk p / ccap
     int64_t cchunk_bytes, ccap;
+    // the single list's guide (mcl_compact_guide.h; the scan that wrote the list wrote it, and left its grand total in *cguide_q),
+    // or null: a multinomial draw then takes two guide words and bisects the few entries between them instead of ctop and a group
+    const uint32_t *cguide;
+    const uint64_t *cguide_q;
+    int cguide_m;
     // the ordering of the ray stage: (key, index) of every child from the layout (bounding box, occupied tiles) of the PREVIOUS update's
     // children -- the set moves by a cell or so per update, and a key only decides which rays share a wave -- so that the radix
     // sort can start right after this kernel (k_cell_bbox / k_tile_compact / k_sort_keys off the critical path)
@@ -243,7 +248,13 @@ __device__ __forceinline__ void resample_motion_body(const ResampleArgs &a, cons
             const bool by_thr = a.mode == 0;
             const uint64_t thr = (__umul64hi(r0, r1) << 11) | ((r0 * r1) >> 53);
             auto above = [&](uint64_t c) -> bool { return by_thr ? c > thr : mul_gt(c, lmul, r0, r1); };
-            if (a.ccdf) {
+            if (a.cguide && by_thr) {
+                // compact list with its guide: the shift comes from the total the list was scanned to, so the table and the
+                // search agree whatever the host holds; the result is the search's below, entry for entry
+                const uint64_t gq = *a.cguide_q;
+                const int gs = guide_shift(gq, a.cguide_m);
+                cpos = (int64_t)compact_guide_search(a.ccdf, (uint32_t)a.n_compact, a.cguide, gs, guide_bmax(gq, gs), thr);
+            } else if (a.ccdf) {
                 // compact list: first group of 64 whose last entry exceeds the threshold (ctop: dense, a few KB), then
                 // inside that group's 512 bytes
                 const int64_t ng = a.n_compact >> kCompactGroupShift;

@@ -37,8 +37,14 @@ struct CompactOut {
     const double *x, *y, *th;
     uint32_t cap;               // room in the arrays above
     unsigned long long *total;  // alive particles of this scan (may exceed cap: the list is then unusable)
+    // the list's guide (mcl_compact_guide.h), or null: guide[b] = first entry at or above the boundary b << s, s from guide_m and
+    // the grand total the spine left in *q_total before this kernel started
+    uint32_t *guide;
+    const uint64_t *q_total;
+    int guide_m;
 };
 constexpr int kCompactGroupShift = 6;
+constexpr uint32_t kGuideInline = 4;       // guide words an entry's thread writes alone; a longer range is filled by its wave
 
 __global__ __launch_bounds__(kScanThreads) void k_scan_partials(const uint64_t *__restrict__ q, int64_t n,
                                                                uint64_t *__restrict__ block_tot, uint32_t *__restrict__ block_cnt)
@@ -74,7 +80,8 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_partials(const uint64_t *
 __global__ __launch_bounds__(1024) void k_scan_spine(uint64_t *__restrict__ block_tot, int nb, uint64_t offset,
                                                      uint64_t *__restrict__ grand_total, uint32_t *__restrict__ block_cnt,
                                                      unsigned long long *__restrict__ alive_total,
-                                                     const double *__restrict__ sum_part = nullptr, int n_sum_part = 0, double *__restrict__ scalars = nullptr)
+                                                     const double *__restrict__ sum_part = nullptr, int n_sum_part = 0, double *__restrict__ scalars = nullptr,
+                                                     uint64_t *__restrict__ guide_total = nullptr)      // the grand total once more: CompactOut::q_total
 {
     __shared__ uint64_t sm[16];
     if (sum_part) {
@@ -111,6 +118,7 @@ __global__ __launch_bounds__(1024) void k_scan_spine(uint64_t *__restrict__ bloc
         __syncthreads();
     }
     if (threadIdx.x == 0 && grand_total) *grand_total = carry_s;
+    if (threadIdx.x == 0 && guide_total) *guide_total = carry_s;
     if (threadIdx.x == 0 && alive_total) *alive_total = (unsigned long long)carry_c;
 }
 
@@ -155,9 +163,13 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_final(const uint64_t *__r
         if ((last & 15) == 15 && last < n) leaders[last >> kLeaderShift] = off + v[kScanItems - 1];
         else if (base < n && n - 1 <= last && ((n - 1) & 15) != 15) leaders[(n - 1) >> kLeaderShift] = off + v[(n - 1) - base];   // ragged last group
     }
+    uint32_t pos0 = 0;
+    if (co.block_cnt) {
+        pos0 = co.block_cnt[blockIdx.x] + incc - cnt;
+        for (int k = 0; k < w; ++k) pos0 += smc[k];
+    }
     if (co.block_cnt && alive) {
-        uint32_t pos = co.block_cnt[blockIdx.x] + incc - cnt;
-        for (int k = 0; k < w; ++k) pos += smc[k];
+        uint32_t pos = pos0;
 #pragma unroll
         for (int k = 0; k < kScanItems; ++k)
             if ((alive >> k) & 1u) {
@@ -171,6 +183,28 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_final(const uint64_t *__r
                 }
                 ++pos;
             }
+    }
+    if (co.block_cnt && co.guide) {
+        // The guide words of this thread's entries (guide_owner_range: every word has one owner, so nothing is cleared first).
+        // An entry that owns a few words writes them itself; a longer range -- one particle with all the weight owns every word --
+        // is handed to the wave: ballot, broadcast, 64 words per store.  Every lane of the wave comes through here, whatever it holds.
+        const int gs = guide_shift(*co.q_total, co.guide_m);
+        uint32_t pos = pos0;
+#pragma unroll
+        for (int k = 0; k < kScanItems; ++k) {
+            const bool mine = ((alive >> k) & 1u) && pos < co.cap;
+            uint32_t b0 = 0u, b1 = 0u;
+            if (mine) guide_owner_range(off + v[k], v[k] - (k ? v[k - 1] : 0ull), gs, pos, b0, b1);
+            const uint32_t nb = b1 - b0;
+            if (nb <= kGuideInline)
+                for (uint32_t j = 0; j < nb; ++j) co.guide[b0 + j] = pos;
+            for (unsigned long long wide = __ballot(nb > kGuideInline); wide; wide &= wide - 1ull) {
+                const int l = __ffsll((long long)wide) - 1;
+                const uint32_t wb0 = (uint32_t)__shfl((int)b0, l), wnb = (uint32_t)__shfl((int)nb, l), wpos = (uint32_t)__shfl((int)pos, l);
+                for (uint32_t j = (uint32_t)lane; j < wnb; j += 64u) co.guide[wb0 + j] = wpos;
+            }
+            pos += (alive >> k) & 1u;
+        }
     }
 }
 

@@ -72,6 +72,7 @@ EXPORTS = [
     "mcl_set_beam_offsets", "mcl_get_beam_offsets", "mcl_beam_origins", "mcl_host_scan_motion_offsets", "mcl_host_beam_offset_table",
     "mcl_host_beam_offset_pairs",
     "mcl_update_map_region", "mcl_host_map_patch_plan", "mcl_get_map_table", "mcl_group_update_map_region",
+    "mcl_host_compact_guide", "mcl_host_compact_search", "mcl_get_compact_guide",
 ]
 MOTION_REFERENCE, MOTION_DIFF, MOTION_OMNI = 0, 1, 2
 MOTION_MODELS = {"reference": MOTION_REFERENCE, "diff": MOTION_DIFF, "omni": MOTION_OMNI}
@@ -355,6 +356,12 @@ def load_library(legacy=False):
                                           C.c_int64, C.c_int64, C.c_int32, C.c_void_p]
         lib.mcl_get_sort_order.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
                                            C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        if hasattr(lib, "mcl_get_compact_guide"):          # (a build from before the guide, loaded through MCL_LIB for an A/B run, has none of the three)
+            lib.mcl_host_compact_guide.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32),
+                                                   C.POINTER(C.c_uint32), C.POINTER(C.c_int64)]
+            lib.mcl_host_compact_search.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_int32, C.c_uint32, C.c_void_p, C.c_int64,
+                                                    C.c_void_p]
+            lib.mcl_get_compact_guide.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.mcl_get_likelihood_table.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32)]
         lib.mcl_host_likelihood_field.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(LikelihoodFieldConfig),
                                                   C.c_void_p, C.c_size_t]
@@ -1103,6 +1110,41 @@ def host_sort_key(bbox, tilemap, width: int, height: int, px, py, theta, fine: i
                                           C.c_int32(sort_fine_code(fine, fine_sub)), _p(out))
     if rc != MCL_OK:
         raise EngineError(f"mcl_host_sort_key rc={rc}", rc)
+    return out
+
+
+def host_compact_guide(ccdf, m: int, fill=None):
+    """mcl_host_compact_guide: the guide of a compact parent list with the strictly increasing CDF column `ccdf` (uint64; its last
+    entry is the total) for 2^m buckets, by the rule the scan kernel follows.  Returns (guide, s, bmax, words written): guide has
+    bmax + 2 uint32 words, 0 .. bmax written and the last one left at `fill` (default 0xffffffff) -- the word the search's pair
+    fetch touches and never uses."""
+    c = _c(ccdf, np.uint64)
+    if c.ndim != 1 or c.size == 0:
+        raise ValueError("host_compact_guide: ccdf is 1-D and not empty")
+    lib = load_library()
+    s, bmax, nw = C.c_int32(), C.c_uint32(), C.c_int64()
+    q = C.c_uint64(int(c[-1]))
+    rc = lib.mcl_host_compact_guide(_p(c), C.c_int64(c.size), q, C.c_int32(m), None, C.c_size_t(0), C.byref(s), C.byref(bmax), None)
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_compact_guide rc={rc}", rc)
+    guide = np.full(bmax.value + 2, 0xffffffff if fill is None else fill, np.uint32)
+    rc = lib.mcl_host_compact_guide(_p(c), C.c_int64(c.size), q, C.c_int32(m), _p(guide), C.c_size_t(bmax.value + 1), C.byref(s), C.byref(bmax),
+                                    C.byref(nw))
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_compact_guide rc={rc}", rc)
+    return guide, s.value, bmax.value, nw.value
+
+
+def host_compact_search(ccdf, guide, s: int, bmax: int, thr) -> np.ndarray:
+    """mcl_host_compact_search: for every threshold the list position the resampling kernel selects -- the first entry with
+    ccdf > thr, searched between the two guide words of the threshold's bucket, clamped to the last entry (int64).  guide: the
+    bmax + 2 words of host_compact_guide."""
+    c, g, t = _c(ccdf, np.uint64), _c(guide, np.uint32), _c(thr, np.uint64)
+    out = np.empty(t.size, np.int64)
+    rc = load_library().mcl_host_compact_search(_p(c), C.c_int64(c.size), _p(g), C.c_size_t(g.size), C.c_int32(s), C.c_uint32(bmax), _p(t),
+                                                C.c_int64(t.size), _p(out))
+    if rc != MCL_OK:
+        raise EngineError(f"mcl_host_compact_search rc={rc}", rc)
     return out
 
 
@@ -2019,6 +2061,26 @@ class Engine:
         n, u = C.c_int64(), C.c_int32()
         self._chk(self.lib.mcl_get_compact_list(self._h, C.byref(n), C.byref(u)), "mcl_get_compact_list")
         return n.value, bool(u.value)
+
+    def compact_guide(self):
+        """mcl_get_compact_guide: the guide of the compact parent list as the device holds it, a dict of guide (bmax + 1 uint32
+        words), ccdf (the list's uint64 CDF column), s, bmax, n_compact, q_total, m and used (the last update's resampling
+        searched through the guide).  EngineError (NOT_READY) without a list or a guide."""
+        info = np.zeros(6, np.int64)
+        self._chk(self.lib.mcl_get_compact_guide(self._h, None, C.c_size_t(0), None, C.c_size_t(0), _p(info)), "mcl_get_compact_guide")
+        if info[1] < 0:
+            raise EngineError("mcl_get_compact_guide: no compact list with a guide describes the current particles", MCL_ERR_NOT_READY)
+        guide, ccdf = np.empty(int(info[1]) + 1, np.uint32), np.empty(int(info[2]), np.uint64)
+        self._chk(self.lib.mcl_get_compact_guide(self._h, _p(guide), C.c_size_t(guide.size), _p(ccdf), C.c_size_t(ccdf.size), _p(info)),
+                  "mcl_get_compact_guide")
+        return dict(guide=guide, ccdf=ccdf, s=int(info[0]), bmax=int(info[1]), n_compact=int(info[2]), q_total=int(np.uint64(info[3])),
+                    m=int(info[4]), used=bool(info[5]))
+
+    def compact_guide_used(self) -> bool:
+        """whether the last update's resampling searched the compact list through its guide (mcl_get_compact_guide)"""
+        info = np.zeros(6, np.int64)
+        self._chk(self.lib.mcl_get_compact_guide(self._h, None, C.c_size_t(0), None, C.c_size_t(0), _p(info)), "mcl_get_compact_guide")
+        return bool(info[5])
 
     def set_debug_count_probes(self, on):
         self._chk(self.lib.mcl_set_debug_count_probes(self._h, C.c_int32(1 if on else 0)), "mcl_set_debug_count_probes")
